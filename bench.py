@@ -5,6 +5,7 @@ plus the fp64-MFMA roofline fraction of the dominant kernel and a CPU baseline.
     python bench.py --gpus N --steps K --warmup W          (N > 1: spawns its own N rank processes, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W          (ranks started by the launcher)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR    (+ what the last timed step computed, DIR/*.npy)
 
 A "step" is one full pass of the loop body of pymes/solver/ccsd.py:159-209 (dressed Fock,
 T1-dressed V blocks, singles + doubles residuals, amplitude update, DIIS, energy, norms) on
@@ -327,6 +328,31 @@ def other_configs(device=0):
     return out
 
 
+DUMP_T2_FULL_BYTES = 32 << 20       # --dump-outputs: T2 up to this size is written whole, a larger one as a fixed sample
+DUMP_T2_SAMPLE = 1 << 21             # entries of that sample (16 MB of float64)
+DUMP_SAMPLE_SEED = 20240601          # its flat indices: the same for every run and build at a given (nocc, nvirt)
+
+
+def dump_outputs(out_dir, result, t1, t2):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files under `out_dir`:
+    step_result.npy  (e_1b, e_dir, e_ex, |T2|, |dT2|), the return value of CCSD.iterate
+    t1.npy           the amplitudes T1[a,i] the step left in the solver state
+    t2.npy           T2[a,b,i,j] whole when it fits in DUMP_T2_FULL_BYTES, else
+    t2_sample.npy    T2 at DUMP_T2_SAMPLE flat indices drawn with DUMP_SAMPLE_SEED (sorted, without repeats).
+    Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"step_result": np.asarray(result, dtype=np.float64), "t1": np.asarray(t1, dtype=np.float64)}
+    t2 = np.asarray(t2, dtype=np.float64)
+    if t2.nbytes <= DUMP_T2_FULL_BYTES:
+        arrays["t2"] = t2
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, t2.size, DUMP_T2_SAMPLE))
+        arrays["t2_sample"] = t2.reshape(-1)[idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -357,7 +383,14 @@ def main():
                     help="skip the C2 / C4 / C5 legs that follow the headline measurement on a single GPU (~10 s)")
     ap.add_argument("--as-rank", type=int, default=0)
     ap.add_argument("--of", type=int, default=8)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one unsharded GPU: after the timed steps, write what the last timed step computed (its energies "
+                         "and norms, T1, T2 or a fixed sample of it) as DIR/<name>.npy in float64 (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus != 1 or args.stub_collectives or os.environ.get("PYMES_FORCE_SHARDED")):
+        raise SystemExit("--dump-outputs needs the single-rank path: --gpus 1, no --stub-collectives, no PYMES_FORCE_SHARDED")
     if args.owner_tiles:
         os.environ["PYMES_OWNER_TILES"] = "1"
     if args.stub_collectives and args.gpus != 1:
@@ -435,6 +468,7 @@ def main():
     ctx.sync()
     t_setup = time.time() - t0
     energies = []
+    last_result = []     # the return value of the latest step (--dump-outputs)
 
     shortcuts = []       # T1 = 0 shortcut taken by a step (only the very first step from MP2 may: the workload has T1 != 0)
 
@@ -443,6 +477,7 @@ def main():
         with contextlib.redirect_stdout(io.StringIO()):
             e = solver.iterate(st)
         energies.append(e[0] + e[1] + e[2])
+        last_result[:] = e
 
     # the interpreter's cyclic collector stays off from here to the end of the timed region (as CCSD.solve does for its own
     # loop, and as timeit does): a generation-2 collection of this process takes ~38 ms and would land in some step
@@ -490,6 +525,11 @@ def main():
         raise SystemExit("bench.py: a timed step took the T1 = 0 shortcut - the measured step is not the full CCSD iteration")
     phases, collectives = pdist.trace.summary(args.steps)      # of the timed steps only
     pdist.trace.on = False
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the amplitudes as the last timed step left them, before the counting pass below iterates on (the residual segment
+        # that step enqueued for the next one writes only the residual buffers)
+        dumped = dump_outputs(args.dump_outputs, last_result, st["t1"].get(), st["t2"].get())
     replayed = bool(st.get("graph") is not None and separate)
     if separate:        # the same number of steps again, eagerly, with one event pair per GEMM call
         # (the last timed step has enqueued the residual segment of the step after it — the pipelined iteration, DESIGN 6d;
@@ -565,6 +605,8 @@ def main():
                           # the same marks: a phase whose host time is close to its device time waited for the host
                           "phases_ms": phases, "phases_host_ms": getattr(pdist.trace, "host_ms", {})},
         }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if sharded_run:
             # rank 0's view of the sharded iteration: device time per phase (HIP events on the stream the kernels and the
             # collectives are ordered on), per collective the time the stream stood still in its wait() (= exposed

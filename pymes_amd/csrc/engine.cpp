@@ -82,7 +82,8 @@ double* Arena::alloc(int64_t doubles) {
             dev::phase_sync();
             top_ = want_;
         }
-        deferred_ = false;                         // (else: above the hole; an enclosing scope's release takes it back)
+        deferred_ = false;                         // (else: above the hole; the release of the scope that marked at
+                                                   // or below want_ — an enclosing or the current sibling one — takes it back)
     }
     if (top_ + bytes > cap_)
         throw Error("workspace exhausted: need " + std::to_string((top_ + bytes) >> 20) + " MiB, have " +

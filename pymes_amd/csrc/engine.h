@@ -46,7 +46,10 @@ class Arena {
     void init(size_t bytes);
     void release();
     double* alloc(int64_t doubles);
-    size_t mark() const { return top_; }
+    // (while a release is deferred, the mark is that release's `want_`, below top_: everything above `want_` is dead or was
+    // allocated after the release, so a sibling scope that starts now gives back the hole together with its own allocations
+    // when it resets to this mark — with top_ as the mark the hole would be lost for good and the arena would creep upwards)
+    size_t mark() const { return deferred_ ? want_ : top_; }
     // While tasks of an open phase are recorded but not launched (device_api.h, phase launches) a released region is NOT
     // handed out again: a later temporary at the same address would be ordered behind every recorded reader of the old one
     // (a write-after-read hazard that exists only because of the reuse) and the phase would lose the concurrency it is there

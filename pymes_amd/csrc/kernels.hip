@@ -3267,6 +3267,7 @@ struct PhaseQueue {
     long ws_cursor = 0;                // rolling sub-allocation of the split-K workspace among the tasks of a phase
     double* ws = nullptr;              // that workspace (the engine's; remembered from the products of the phase)
     long ws_doubles = 0;
+    bool ws_wrapped = false;           // phase_ws has wrapped to the start since the phase opened (phase_fuse_accumulations)
     bool hold = false;                 // dev::phase_hold: the end of a C-interface call does not launch what is recorded
     bool log = false;                  // PYMES_PHASE_LOG
     uintptr_t fuse_bytes = 2u << 20;   // PYMES_PHASE_FUSE_MB
@@ -3344,14 +3345,18 @@ inline bool phase_conflict(const PhaseRec& a, const PhaseRec& b) {       // a ea
     return false;
 }
 // a slice of the split-K / matrix-vector workspace for one task of the open phase (rolling: a wrap-around is ordered by the
-// hazard analysis like any other reuse)
+// hazard analysis like any other reuse — the slices are handed out in queue order)
 inline double* phase_ws(double* ws, long ws_doubles, long need) {
     PhaseQueue& P = g_phase;
     if (!ws || need > ws_doubles) return nullptr;
     P.ws = ws;
     P.ws_doubles = ws_doubles;
     need = (need + 15) & ~15L;
-    if (P.ws_cursor + need > ws_doubles) P.ws_cursor = 0;
+    if (P.ws_cursor + need > ws_doubles) {
+        if (P.log) fprintf(stderr, "[phase] workspace wrap: %ld doubles at %ld of %ld\n", need, P.ws_cursor, ws_doubles);
+        P.ws_cursor = 0;
+        P.ws_wrapped = true;
+    }
     double* p = ws + P.ws_cursor;
     P.ws_cursor += need;
     return p;
@@ -3364,7 +3369,10 @@ inline double* phase_ws(double* ws, long ws_doubles, long need) {
 // C = C + P_1 + P_2 + ... (fixed order: deterministic) follows the last of them: a chain of n becomes two levels.  The
 // singles residual (six products into a v x o array), Q_kb + W_kb, the X_ac T / t Q_kb / V_abic t sum of the finish and the
 // one-index terms of a sigma build are such chains.  Costs one write and one read of the array per redirected member, so
-// only small arrays take part.
+// only small arrays take part.  The private buffers are handed out at flush time, OUT of queue order: they must lie above
+// every slice the recorded tasks use, so a group is left unfused when the workspace has wrapped in the phase or has no room
+// left above the cursor (a buffer on the slice of a product recorded between a member and the combining task would be
+// overwritten by that product's partial tiles).
 void phase_fuse_accumulations(std::vector<PhaseRec>& q) {
     PhaseQueue& P = g_phase;
     // (arrays up to 2 MB: a redirected member costs one write and one read of the array more.  Measured at (20,80), same box:
@@ -3412,6 +3420,13 @@ void phase_fuse_accumulations(std::vector<PhaseRec>& q) {
         lk.p.c[0] = 1.0;
         int nx = 1, last = -1;
         PhaseRec comb;
+        const long room = P.ws_doubles - P.ws_cursor, need = (long)G.members.size() * ((len + 15) & ~15L);
+        if (P.ws_wrapped || need > room) {
+            if (P.log)
+                fprintf(stderr, "[phase] fusion declined: %zu members of %ld doubles (%s)\n", G.members.size(), len,
+                        P.ws_wrapped ? "the workspace has wrapped" : "no room above the cursor");
+            continue;
+        }
         for (int m : G.members) {
             double* buf = phase_ws(P.ws, P.ws_doubles, len);
             if (!buf) break;
@@ -3465,7 +3480,7 @@ void phase_flush() {
     if (P.q.empty() || P.flushing) return;
     struct Guard {
         PhaseQueue& P;
-        ~Guard() { P.flushing = false; P.q.clear(); P.ws_cursor = 0; P.ws = nullptr; P.ws_doubles = 0; }
+        ~Guard() { P.flushing = false; P.q.clear(); P.ws_cursor = 0; P.ws_wrapped = false; P.ws = nullptr; P.ws_doubles = 0; }
     } guard{P};
     P.flushing = true;
     ++P.flushes;

@@ -56,10 +56,10 @@ void graph_abort(stream_t) {}
 void graph_launch(graph_t, stream_t) { throw std::runtime_error("hostsim: no launch graphs"); }
 void graph_destroy(graph_t) {}
 void memcpy_h2d(void* d, const void* h, size_t n, stream_t) { std::memcpy(d, h, n); }
-void memcpy_d2h(void* h, const void* d, size_t n, stream_t) { std::memcpy(h, d, n); }
+void memcpy_d2h(void* h, const void* d, size_t n, stream_t) { phase_sync(); std::memcpy(h, d, n); }
 void memcpy_d2d(void* d, const void* s, size_t n, stream_t) { std::memmove(d, s, n); }
 void memset_zero(void* d, size_t n, stream_t) { std::memset(d, 0, n); }
-void stream_sync(stream_t) {}
+void stream_sync(stream_t) { phase_sync(); }
 size_t mem_free_bytes() { return size_t(1) << 34; }
 size_t mem_total_bytes() { return size_t(1) << 35; }
 
@@ -70,10 +70,13 @@ void prof_enable(bool on) { g_prof = on; }
 void prof_reset() { g_launches = 0; g_flops = 0; }
 void prof_query(int, long* l, long* nk, double* ms, double* f) { *l = g_launches; *nk = g_launches; *ms = 0.0; *f = g_flops; }
 
+static void phase_record();        // (phase state: below)
+
 void gemv_batch_begin() {}          // the simulator executes every product at once
 void gemv_batch_end() {}
 
 void gemm(const Gemm& g, stream_t) {
+    phase_record();
     if (!((g.a_sm == 1 || g.a_sk == 1 || g.M == 1 || g.K == 1) && (g.b_sk == 1 || g.b_sn == 1 || g.N == 1 || g.K == 1)))
         throw std::runtime_error("hostsim gemm: operand without unit stride");
     for (int64_t z1 = 0; z1 < g.nb1; ++z1)
@@ -93,6 +96,7 @@ void gemm(const Gemm& g, stream_t) {
 }
 
 void permute(const Permute& p, stream_t) {
+    phase_record();
     int64_t total = 1;
     for (int i = 0; i < p.rank; ++i) total *= p.dim[i];
     // out may alias in only for identical index maps (axpby on itself); buffer otherwise-unsafe cases
@@ -235,6 +239,7 @@ static thread_local unsigned g_read_gen[16] = {0};
 static thread_local int g_read_next = 0;
 // (ticket = slot | generation << 8, as the HIP backend: a reused or never-started slot is refused)
 int readback_start(const double* dev_ptr, int n, stream_t) {
+    phase_sync();
     if (n < 1 || n > 128) throw std::runtime_error("readback: 1..128 doubles");
     const int slot = g_read_next;
     g_read_next = (slot + 1) % 16;
@@ -258,6 +263,7 @@ int energy_norms_start(const double* f, const double* t1, const double* t2, cons
 }
 
 void lincomb(double* out, int nx, const double* const* x, const double* c, int64_t n, stream_t) {
+    phase_record();
     if (nx < 0 || nx > 8) throw std::runtime_error("lincomb: at most 8 terms");
     for (int64_t i = 0; i < n; ++i) {
         double s = 0.0;
@@ -272,17 +278,49 @@ static thread_local bool g_group_open = false;
 void gemm_group_begin(stream_t) { g_group_open = true; g_group_launches = g_group_products = 0; }
 void gemm_group_end() { g_group_open = false; }
 void gemm_group_sync() {}
-void phase_sync() {}
-bool phase_pending() { return false; }
-long phase_generation() { return 0; }
-void phase_enable(int) {}
-void phase_hold(bool) {}
-void phase_call_end() {}
+// phase state (kernels.hip, phase_push ... phase_flush): the simulator executes every operation at once, but the ENGINE's
+// view of an open phase is modelled, so that its deferred arena releases (engine.cpp, Arena::reset / alloc) run here too.
+// A product, permutation or linear combination issued while phases are enabled leaves the phase pending until the next
+// sync (phase_sync, the end of a C-interface call outside a hold, a read-back or copy), which counts one generation.
+struct SimPhase {
+    int enabled = -1;           // -1: PYMES_PHASE decides at first use (default on)
+    bool pending = false, hold = false;
+    long tasks = 0, flushes = 0;
+};
+static thread_local SimPhase g_phase;
+void phase_sync() {
+    if (!g_phase.pending) return;
+    g_phase.pending = false;
+    ++g_phase.flushes;
+}
+static void phase_record() {
+    SimPhase& P = g_phase;
+    if (P.enabled < 0) {
+        const char* e = std::getenv("PYMES_PHASE");
+        P.enabled = (e && e[0] == '0') ? 0 : 1;
+    }
+    if (!P.enabled) return;
+    P.pending = true;
+    ++P.tasks;
+}
+bool phase_pending() { return g_phase.pending; }
+long phase_generation() { return g_phase.flushes; }
+void phase_enable(int mode) {
+    phase_sync();
+    g_phase.enabled = mode < 0 ? -1 : (mode ? 1 : 0);
+}
+void phase_hold(bool on) {
+    g_phase.hold = on;
+    if (!on) phase_sync();
+}
+void phase_call_end() {
+    if (!g_phase.hold) phase_sync();
+}
 void phase_stats(long* tasks, long* launches, long* levels, long* flushes) {
-    if (tasks) *tasks = 0;
+    if (tasks) *tasks = g_phase.tasks;
     if (launches) *launches = 0;
     if (levels) *levels = 0;
-    if (flushes) *flushes = 0;
+    if (flushes) *flushes = g_phase.flushes;
 }
 void gemm_group_stats(long* launches, long* products) {
     if (launches) *launches = g_group_launches;
@@ -331,6 +369,7 @@ void diis_step(double* state, int npairs, const double* const* x, const double* 
 }
 
 void lincomb_dev(double* out, int nx, const double* const* x, const double* coeff, int64_t n, stream_t) {
+    phase_record();
     if (nx < 0 || nx > 8) throw std::runtime_error("lincomb_dev: at most 8 terms");
     for (int64_t i = 0; i < n; ++i) {
         double s = 0.0;

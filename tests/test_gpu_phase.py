@@ -305,3 +305,192 @@ def test_random_mixed_operations(gpu_lib, seed):
         assert np.isfinite(host).all() and np.abs(got - host).max() < 1e-11 * max(1.0, np.abs(host).max()), np.abs(got - host).max()
     finally:
         ctx.close()
+
+
+# ---- split-K workspace reuse inside one held phase (the fusion-room rule) --------------------------------------
+WS_DOUBLES = 32 << 20           # the engine's split-K workspace (engine.cpp): 256 MiB
+
+
+def splitk_slice(M, N, K):
+    """Doubles of the split-K workspace that phase_gemm (kernels.hip) takes for ONE recorded product M x N x K (batch 1):
+    64 x 64 tiles (64 x 32 / 32 x 64 when a side is at most 32), BK = 16; with ktiles = ceil(K / 16) >= 16 the last,
+    partially filled round of tiles (rem = tiles % 1024, all of them for a small output) is split over k in `sp` pieces,
+    2 <= sp <= min(512, max(8, 2048 // rem), ktiles // 8, capacity // rem), the one that minimises
+    ceil(rem sp / 1024) / sp + 1e-5 sp if that is below 0.8.  0: no k-split (no slice)."""
+    BM, BN = 64, 64
+    if N <= 32:
+        BN = 32
+    elif M <= 32:
+        BM = 32
+    tiles = -(-M // BM) * -(-N // BN)
+    ktiles = -(-K // 16)
+    rem = tiles % 1024
+    if ktiles < 16 or rem == 0:
+        return 0
+    smax = min(512, max(8, 2048 // rem), ktiles // 8, (WS_DOUBLES // (BM * BN)) // rem)
+    best, best_cost = 1, 1.0
+    for sp in range(2, smax + 1):
+        c = -(-(rem * sp) // 1024) / sp + 1e-5 * sp
+        if c < best_cost - 1e-9:
+            best, best_cost = sp, c
+    if best < 2 or best_cost >= 0.8:
+        return 0
+    kt_per = -(-ktiles // best)
+    nsplit = -(-ktiles // kt_per)
+    return (rem * nsplit * BM * BN + 15) // 16 * 16
+
+
+def test_fusion_after_workspace_wrap(gpu_lib, capfd):
+    """A fused accumulation chain whose private buffers would land on the slice of a split-K product recorded inside the
+    chain.  In one held phase: R = A0 B0 (beta 0: opens the fusion group), R += A1 B1 (a member), nine products
+    Q_j = X_j Y of M = 64, N = 6400, K = 2560, then R += A2 B2 (a member).  Each Q_j is recorded (M <= 64 keeps it off the
+    LDS-DMA kernel; PYMES_PHASE_MAX_US lifts its ~86-us estimate under the cap) with a k-split: 100 tiles of 64 x 64,
+    ktiles = 160, sp = 10 (splitk_slice), a slice of 100 * 10 * 4096 = 4,096,000 doubles.  Eight slices fill 32.8 M of the
+    33.55 M doubles, the ninth wraps to 0 and leaves the cursor at 4,096,000 — the start of Q_2's slice.  Fusion hands out
+    its buffers at flush time from that cursor: member 1's buffer would be overwritten by Q_2's partial tiles before the
+    combining task reads it.  The rule (kernels.hip, phase_fuse_accumulations): no fusion once the workspace has wrapped."""
+    M, N, K, nq = 64, 6400, 2560, 9
+    slice_ = splitk_slice(M, N, K)
+    assert slice_ == 4096000 and (nq - 1) * slice_ <= WS_DOUBLES < nq * slice_      # (precondition: exactly one wrap)
+    ctx = Context(2, 3, lib=gpu_lib, workspace_bytes=1 << 28)
+    rng = np.random.default_rng(11)
+    try:
+        m, n, k = 64, 64, 32
+        # R between two arrays nobody reads: an operand's range has one double of slack at its top (pbox), and an operand
+        # right below R would "touch" it — the group would close before the last member and nothing would be at stake
+        guard = [ctx.zeros((64,))]
+        R = ctx.array(rng.standard_normal((m, n)))
+        guard.append(ctx.zeros((64,)))
+        As = [rng.standard_normal((m, k)) for _ in range(3)]
+        Bs = [rng.standard_normal((k, n)) for _ in range(3)]
+        Xs = [rng.standard_normal((M, K)) / np.sqrt(K) for _ in range(nq)]
+        Y = rng.standard_normal((K, N))
+        dA, dB, dX, dY = [ctx.array(a) for a in As], [ctx.array(b) for b in Bs], [ctx.array(x) for x in Xs], ctx.array(Y)
+        Q = [ctx.array(np.full((M, N), np.nan)) for _ in range(nq)]
+        ctx.sync()
+        capfd.readouterr()
+        with phase_env(ctx, PYMES_PHASE_MAX_US="1000", PYMES_PHASE_LOG="1"):
+            before = ctx.phase_stats()
+            with ctx.phase_hold():
+                ctx.dgemm(m, n, k, 1.0, dA[0], k, 1, dB[0], n, 1, 0.0, R, n)
+                ctx.dgemm(m, n, k, 1.0, dA[1], k, 1, dB[1], n, 1, 1.0, R, n)
+                for x, q in zip(dX, Q):
+                    ctx.dgemm(M, N, K, 1.0, x, K, 1, dY, N, 1, 0.0, q, N)
+                ctx.dgemm(m, n, k, 1.0, dA[2], k, 1, dB[2], n, 1, 1.0, R, n)
+            after = ctx.phase_stats()
+        err = capfd.readouterr().err
+        # everything recorded, in one phase: 3 small products + a (tiles, reduction) pair per split product
+        assert after["tasks"] - before["tasks"] == 3 + 2 * nq and after["flushes"] - before["flushes"] == 1
+        for j, (x, q) in enumerate(zip(Xs, Q)):
+            want = x @ Y
+            assert np.abs(q.get() - want).max() < 1e-12 * np.abs(want).max(), j
+        want = sum(a @ b for a, b in zip(As, Bs))
+        assert np.abs(R.get() - want).max() < 1e-12 * np.abs(want).max()
+        assert err.count("[phase] workspace wrap") == 1, err[-2000:]
+        assert "[phase] fusion declined: 2 members" in err, err[-2000:]
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("seed", list(range(3)))
+def test_random_workspace_wraps(gpu_lib, seed, capfd):
+    """Fifty-six recorded operations in ONE held phase whose split-K slices wrap the workspace two times or more: k-split
+    products (splitk_slice) into large outputs, beta = 1 accumulation chains into small contiguous arrays (fusion
+    candidates; some members k-split themselves), matrix-vector contractions whose row-chunk partials take workspace slices
+    too (the column-sum path of gemv_dispatch), and now and then a product that reads an accumulation target in the middle
+    of its chain — against the same sequence in numpy."""
+    ctx = Context(2, 3, lib=gpu_lib, workspace_bytes=1 << 28)
+    rng = np.random.default_rng(900 + seed)
+    try:
+        LD, KMAX = 6400, 4096
+        big_shapes = [(64, 6400, 2560), (64, 3200, 2560), (48, 6400, 4096), (32, 6400, 2560), (64, 6400, 2048)]
+        host = {"Y": rng.standard_normal((KMAX, LD))}
+        host.update({f"X{i}": rng.standard_normal((64, KMAX)) for i in range(3)})
+        host.update({f"O{i}": rng.standard_normal((64, LD)) for i in range(4)})            # large outputs
+        host.update({f"T{i}": rng.standard_normal((40, 48)) for i in range(3)})            # accumulation targets
+        host.update({f"W{i}": rng.standard_normal((40, 20)) for i in range(2)})            # readers' outputs
+        host.update({f"v{i}": rng.standard_normal((1, LD)) for i in range(2)})             # matrix-vector outputs
+        host.update({f"x{i}": rng.standard_normal((1, KMAX)) for i in range(2)})
+        host.update({f"A{k}": rng.standard_normal((40, k)) for k in (16, 32, 320)})
+        host.update({f"B{k}": rng.standard_normal((k, 48)) for k in (16, 32, 320)})
+        host["Z"] = rng.standard_normal((48, 20))
+        dev = {name: ctx.array(a) for name, a in host.items()}
+        ctx.sync()
+        slices = 0
+        capfd.readouterr()
+        with phase_env(ctx, PYMES_PHASE_MAX_US="100000", PYMES_PHASE_LOG="1"):
+            before = ctx.phase_stats()
+            with ctx.phase_hold():
+                for _ in range(56):
+                    kind = rng.choice(["big", "big", "big", "big", "acc", "acc", "acc", "gemv", "read"])
+                    beta = float(rng.choice([0.0, 1.0, 1.0]))
+                    if kind == "big":
+                        M, N, K = big_shapes[int(rng.integers(len(big_shapes)))]
+                        x, o = f"X{int(rng.integers(3))}", f"O{int(rng.integers(4))}"
+                        alpha = 1.0 / np.sqrt(K)
+                        ctx.dgemm(M, N, K, alpha, dev[x], KMAX, 1, dev["Y"], LD, 1, beta, dev[o], LD)
+                        host[o][:M, :N] = alpha * (host[x][:M, :K] @ host["Y"][:K, :N]) + beta * host[o][:M, :N]
+                        slices += splitk_slice(M, N, K)
+                    elif kind == "acc":
+                        k, t = int(rng.choice([16, 32, 320])), f"T{int(rng.integers(3))}"
+                        alpha = float(rng.choice([0.5, -1.0])) / np.sqrt(k)
+                        ctx.dgemm(40, 48, k, alpha, dev[f"A{k}"], k, 1, dev[f"B{k}"], 48, 1, beta, dev[t], 48)
+                        host[t] = alpha * (host[f"A{k}"] @ host[f"B{k}"]) + beta * host[t]
+                        slices += splitk_slice(40, 48, k)
+                    elif kind == "gemv":
+                        K, v, x = int(rng.choice([2560, 4096])), f"v{int(rng.integers(2))}", f"x{int(rng.integers(2))}"
+                        alpha = 1.0 / np.sqrt(K)
+                        ctx.dgemm(1, LD, K, alpha, dev[x], KMAX, 1, dev["Y"], LD, 1, beta, dev[v], LD)
+                        host[v] = alpha * (host[x][:, :K] @ host["Y"][:K]) + beta * host[v]
+                    else:
+                        t, w = f"T{int(rng.integers(3))}", f"W{int(rng.integers(2))}"
+                        ctx.dgemm(40, 20, 48, 0.2, dev[t], 48, 1, dev["Z"], 20, 1, 0.0, dev[w], 20)
+                        host[w] = 0.2 * (host[t] @ host["Z"])
+            after = ctx.phase_stats()
+        err = capfd.readouterr().err
+        assert after["flushes"] - before["flushes"] == 1 and after["tasks"] - before["tasks"] >= 50
+        for name, want in host.items():
+            got = dev[name].get()
+            assert np.abs(got - want).max() <= 1e-12 * max(1.0, np.abs(want).max()), (name, np.abs(got - want).max())
+        # (the precondition: the workspace wrapped twice or more — the products' slices, splitk_slice, and the matrix-vector
+        # partials, 80 row chunks x 6400 each)
+        assert slices > WS_DOUBLES and err.count("[phase] workspace wrap") >= 2, (slices, err.count("[phase] workspace wrap"))
+    finally:
+        ctx.close()
+
+
+def _residual_passes(lib, calls, workspace_bytes=0, marks=()):
+    """`calls` whole-step CCSD residuals (pymes_ccsd_residuals) on ONE (8, 32) context, phases on: r1, r2 and the
+    workspace high-water mark after the calls listed in `marks`."""
+    no, nv = 8, 32
+    f, V, _, _ = synthetic_case(no, nv, seed=1, scale=0.3)
+    rng = np.random.default_rng(2)
+    t1h = 0.05 * rng.standard_normal((nv, no))
+    x = 0.05 * rng.standard_normal((nv, nv, no, no))
+    ctx = Context(no, nv, lib=lib, workspace_bytes=workspace_bytes)
+    try:
+        with phase_env(ctx, PYMES_PHASE=None):
+            ctx.set_V_pqrs(V)
+            ctx.set_orbital_energies(f.diagonal()[:no].copy(), f.diagonal()[no:].copy())
+            fd, t1, t2 = ctx.array(f), ctx.array(t1h), ctx.array(x + x.transpose(1, 0, 3, 2))
+            r1, r2 = ctx.empty(t1.shape), ctx.empty(t2.shape)
+            high = {}
+            for i in range(1, calls + 1):
+                ctx.ccsd_residuals(fd, t1, t2, r1, r2)
+                if i in marks:
+                    high[i] = ctx.workspace()[1]
+            assert ctx.phase_stats()["tasks"] > 0
+            return r1.get(), r2.get(), high
+    finally:
+        ctx.close()
+
+
+def test_arena_reuse_across_sibling_scopes(gpu_lib):
+    """pymes_ccsd_residuals runs its dressings, the doubles slab, the singles and the finish as sibling arena scopes with no
+    enclosing one; a release deferred for the open phase (engine.h, Arena) must come back to the next sibling.  The
+    high-water mark is the same after 2 and after 20 passes, and a workspace only 1.25 x that mark serves 20 passes with
+    results bit-identical to those of a generous workspace (phases on in both: the same fusion, the same order of sums)."""
+    r1, r2, high = _residual_passes(gpu_lib, 20, marks=(2, 20))
+    assert high[2] > 0 and high[20] == high[2], high
+    t1, t2, _ = _residual_passes(gpu_lib, 20, workspace_bytes=int(1.25 * high[2]))
+    assert np.array_equal(t1, r1) and np.array_equal(t2, r2)

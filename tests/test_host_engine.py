@@ -357,3 +357,39 @@ def test_amps_warm_start_and_kwargs(sim, capsys):
     res = ccsd.CCSD(no, delta_e=1e-10).solve(f, V, amps=[t1, t2], max_iter=30)
     assert abs(res["ccsd e"] - SOLVES["syn_4_12"]["ccsd"]["e"]) < 5e-8     # a different (warm-started) path
     assert not np.array_equal(t2, t2_before)      # caller's arrays are updated in place (ccsd.py:178-179)
+
+
+def _residual_calls(lib, no, nv, calls, workspace_bytes=0, marks=()):
+    """`calls` whole-step residual passes on ONE context with phases on; (r1, r2, {call: arena high-water mark})."""
+    from oracle.cases import synthetic_case as case
+    f, V, _, _ = case(no, nv, seed=1, scale=0.3)
+    rng = np.random.default_rng(2)
+    t1h = 0.05 * rng.standard_normal((nv, no))
+    x = 0.05 * rng.standard_normal((nv, nv, no, no))
+    ctx = Context(no, nv, lib=lib, workspace_bytes=workspace_bytes)
+    try:
+        ctx.phase_enable(1)
+        ctx.set_V_pqrs(V)
+        ctx.set_orbital_energies(f.diagonal()[:no].copy(), f.diagonal()[no:].copy())
+        fd, t1, t2 = ctx.array(f), ctx.array(t1h), ctx.array(x + x.transpose(1, 0, 3, 2))
+        r1, r2 = ctx.empty(t1.shape), ctx.empty(t2.shape)
+        high = {}
+        for i in range(1, calls + 1):
+            ctx.ccsd_residuals(fd, t1, t2, r1, r2)
+            if i in marks:
+                high[i] = ctx.workspace()[1]
+        return r1.get(), r2.get(), high
+    finally:
+        ctx.close()
+
+
+def test_arena_released_between_sibling_scopes(hostsim_lib):
+    """The whole-step residual runs dress_fock, dress_V, residual_slab, singles_residual_partial and residual_finish as sibling
+    arena scopes with no enclosing one.  While a phase is pending a scope's release is deferred (engine.h, Arena); the next
+    sibling must still give that hole back, so the workspace high-water mark stops growing after the first passes — and a
+    workspace only a little above it serves every later pass, with the same numbers.  The simulator models the phase state
+    (pending from the first recorded operation to the end of the call), so the deferred path runs here."""
+    r1, r2, high = _residual_calls(hostsim_lib, 3, 10, 12, marks=(2, 12))
+    assert high[2] > 0 and high[12] == high[2], high
+    t1, t2, _ = _residual_calls(hostsim_lib, 3, 10, 12, workspace_bytes=int(1.25 * high[2]) + 4096)
+    assert np.array_equal(t1, r1) and np.array_equal(t2, r2)

@@ -115,6 +115,20 @@ int pymes_exchange_asymmetry(pymes_ctx* ctx, const double* A_dev, const double* 
                              double* out_host);
 /* V[p,q,r,s] = sum_Q B[Q,p,r] B[Q,q,s]  (density-fitted / synthetic input), B_host is [naux,n,n] */
 int pymes_set_V_from_factors(pymes_ctx* ctx, const double* B_host, int naux);
+/* Integral sharding (opt-in; before any pymes_set_V_* call): the context never allocates V_abcd.  It stores instead the
+ * undressed pair-packed rows [r0,r1) of rank `rank` of `world` (the chunk of v(v+1)/2 pair rows P(a,b), a >= b, that the
+ * sharded residual steps give that rank): V^+ / V^- as dev ladder_pack_V writes them, row pitches ldp / ldm.  set_V_pqrs and
+ * set_V_block("abcd") from the host upload only the rank's planes V[a,b,:,:] (one bounded staging buffer, 1 GiB);
+ * set_V_from_factors forms the rows straight from B.  The other 15 blocks are held as ever.  Only the sharded ladders of that
+ * (rank, world) are served; every entry point that needs the full or dressed V_abcd fails and names the mode (the block
+ * pointer, set_V_block("abcd") from device memory, pymes_ladder, pymes_doubles_residual, pymes_ccsd_residuals /
+ * _iterate, pymes_ccsd_dress_abcd_rows, dressed or other rows of pymes_ladder_sym, the EOM sigma). */
+int pymes_set_integral_shard(pymes_ctx* ctx, int rank, int world);
+/* bytes the context holds for integrals: undressed and dressed blocks, the stored / packed V_abcd rows, the static packs */
+int pymes_integral_bytes(pymes_ctx* ctx, int64_t* bytes);
+/* read-only view of the stored rows of a sharded context: device pointers, the pair-row range and the row pitches */
+int pymes_shard_rows_ptr(pymes_ctx* ctx, const double** vp, const double** vm, int64_t* row0, int64_t* row1, int64_t* ldp,
+                         int64_t* ldm);
 /* device address of a block ("dressed" = output of pymes_ccsd_dress_V); NULL+error if absent */
 int pymes_V_block_ptr(pymes_ctx* ctx, const char* name, int dressed, double** dev_ptr, int64_t* n_elements);
 /* diag(f): eps_o[no], eps_v[nv] used by the denominators (ccsd.py:149-156) */

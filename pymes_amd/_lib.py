@@ -63,6 +63,9 @@ SIGNATURES = {
     "pymes_exchange_asymmetry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64_p, c_double_p]),
     "pymes_set_V_from_factors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "pymes_V_block_ptr": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, c_pp, c_i64_p]),
+    "pymes_set_integral_shard": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "pymes_integral_bytes": (C.c_int, [C.c_void_p, c_i64_p]),
+    "pymes_shard_rows_ptr": (C.c_int, [C.c_void_p, c_pp, c_pp, c_i64_p, c_i64_p, c_i64_p, c_i64_p]),
     "pymes_set_orbital_energies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pymes_mp2": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, c_double_p]),
     "pymes_ccsd_dress_fock": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -308,6 +308,22 @@ int pymes_V_block_ptr(pymes_ctx* ctx, const char* name, int dressed, double** p,
         if (nel) *nel = v.size();
     });
 }
+int pymes_set_integral_shard(pymes_ctx* ctx, int rank, int world) {
+    return guarded([&] { E(ctx).set_integral_shard(rank, world); });
+}
+int pymes_integral_bytes(pymes_ctx* ctx, int64_t* bytes) {
+    return guarded([&] {
+        need(bytes, "bytes");
+        *bytes = E(ctx).integral_bytes();
+    });
+}
+int pymes_shard_rows_ptr(pymes_ctx* ctx, const double** vp, const double** vm, int64_t* row0, int64_t* row1, int64_t* ldp,
+                         int64_t* ldm) {
+    return guarded([&] {
+        need(vp, "vp"); need(vm, "vm"); need(row0, "row0"); need(row1, "row1"); need(ldp, "ldp"); need(ldm, "ldm");
+        E(ctx).shard_rows(vp, vm, row0, row1, ldp, ldm);
+    });
+}
 int pymes_set_orbital_energies(pymes_ctx* ctx, const double* eo, const double* ev) {
     return guarded([&] {
         need(eo, "eps_o");
@@ -899,6 +915,7 @@ int pymes_eom_sigma_prepare(pymes_ctx* ctx, const double* f_host, const double* 
         *out = nullptr;
         need(f_host, "f_host"); need(t2, "t2");
         Engine& e = E(ctx);
+        e.refuse_if_sharded("EOM sigma");
         if (e.capturing()) throw pymes::Error("eom_sigma_prepare while a launch graph is being recorded");
         pymes::EomSigma* s = new pymes::EomSigma(e, f_host, t2, dressed != 0);
         *out = new pymes_eom{s, ctx};
@@ -925,6 +942,7 @@ int pymes_eom_sigma_apply(pymes_eom* h, int k, const double* const* u1, const do
 int pymes_eom_diagonals(pymes_ctx* ctx, const double* f_host, const double* t2, int dressed, double* d1, double* d2) {
     return guarded([&] {
         need(f_host, "f_host"); need(t2, "t2"); need(d1, "d1"); need(d2, "d2");
+        E(ctx).refuse_if_sharded("EOM diagonals");
         pymes::eom_diagonals(E(ctx), f_host, t2, dressed != 0, d1, d2);
     });
 }

@@ -12,6 +12,8 @@
 // matrices (possibly transposed), with no per-term transposition of the operands.
 #include <algorithm>
 #include <cstring>
+#include <cstdlib>
+#include <vector>
 
 #include "engine.h"
 
@@ -38,8 +40,7 @@ double* Engine::get_static(const std::string& key) {
     if (it != static_.end()) return it->second;
     const int64_t o = no, v = nv;
     TView Vijab = block(P_ijab);
-    double* p = static_cast<double*>(dev::dmalloc(sizeof(double) * o * o * v * v));
-    static_[key] = p;
+    double* p = new_static(key, o * o * v * v);
     // all keys: source labels of V_ijab are "klcd" (k,l occupied; c,d virtual)
     if (key == "Vd") permute(1.0, Vijab, "klcd", 0.0, make_view(p, {v, o, v, o}), "ckdl");        // [(c,k),(d,l)]
     else if (key == "Vx") permute(1.0, Vijab, "klcd", 0.0, make_view(p, {v, o, v, o}), "cldk");   // [(c,l),(d,k)]
@@ -87,6 +88,7 @@ void Engine::mp2(double shift, double* t2, double e_out[2]) {
 // ccd.py:164-254  (the doubles residual; also the CCSD one via dressed blocks, ccsd.py:440-456)
 // -----------------------------------------------------------------------------------
 void Engine::doubles_residual(const double* f, const double* t2, double* r2, unsigned flags) {
+    refuse_if_sharded("doubles_residual");
     const bool dcd = flags & 1u, dressed = flags & 2u, skip_ladder = flags & 4u, sym_ladder = flags & 8u,
                sym_rings = flags & 16u;
     const bool quad = !dcd;
@@ -255,6 +257,7 @@ void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, dou
     const bool quad = !dcd;
     const int64_t o = no, v = nv, nn = n, ov = o * v;
     if (world < 1 || rank < 0 || rank >= world) throw Error("residual_slab: bad rank/world");
+    if (L && !skip_ladder) check_shard_rank("residual_slab", rank, world);
     const double w = quad ? 1.0 : 0.5;
     TView F = make_view(const_cast<double*>(f), {nn, nn});
     auto chunk = [&](int64_t rows, int64_t& lo, int64_t& hi) {
@@ -488,10 +491,8 @@ void Engine::slab_prepare(const double* t2, double* P, int rank, int world, unsi
         xs_oo_tag_.set(t2, rank, world);       // this rank's partial sum: the singles residual takes ccsd.py:434 from it
     }
     if (!static_.count("VpIjab")) {
-        double* vp = static_cast<double*>(dev::dmalloc(sizeof(double) * opp * lpitch(npp)));
-        double* vm = static_cast<double*>(dev::dmalloc(sizeof(double) * opp * lpitch(std::max<int64_t>(npm, 1))));
-        static_["VpIjab"] = vp;
-        static_["VmIjab"] = vm;
+        double* vp = new_static("VpIjab", opp * lpitch(npp));
+        double* vm = new_static("VmIjab", opp * lpitch(std::max<int64_t>(npm, 1)));
         dev::ladder_pack_V(block(P_ijab).p, vp, vm, no, nv, 0, opp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
     }
     {
@@ -711,6 +712,7 @@ void Engine::residual_finish_pairs(const double* f, const double* t2, const doub
 // lower_only: only the entries with b <= a are produced (all the pair-packed ladder reads), in a-blocks of
 // 32 rows with b < block end — 56 % of the traffic of the full rows at nv = 200.
 void Engine::dress_abcd_rows(const double* t1, int a0, int a1, bool lower_only) {
+    refuse_if_sharded("dress_abcd_rows");
     if (a0 < 0 || a1 > nv || a0 > a1) throw Error("dress_abcd_rows: bad range");
     if (a0 == a1) return;
     TView t = make_view(const_cast<double*>(t1), {(int64_t)nv, (int64_t)no});
@@ -735,6 +737,7 @@ void Engine::dress_abcd_rows(const double* t1, int a0, int a1, bool lower_only) 
 }
 
 void Engine::ladder(const double* t2, double* r2, int a0, int a1, bool dressed, double beta) {
+    refuse_if_sharded("ladder");
     const int64_t o = no, v = nv;
     if (a0 < 0 || a1 > nv || a0 > a1) throw Error("ladder: bad a-range");
     if (a0 == a1) return;
@@ -755,7 +758,8 @@ void Engine::ladder_sym(const double* t2, double* L, int64_t row0, int64_t row1,
     if (hole < 0 || hole > 2) throw Error("ladder_sym: hole must be 0, 1 (CCSD) or 2 (DCSD)");
     if (row0 == row1) return;
     const int64_t rows = row1 - row0;
-    if (!(lpack_.valid && lpack_.dressed == dressed && lpack_.row0 == row0 && lpack_.row1 == row1)) {
+    if (shard_on_) check_shard_rows("ladder_sym", row0, row1, dressed);
+    else if (!(lpack_.valid && lpack_.dressed == dressed && lpack_.row0 == row0 && lpack_.row1 == row1)) {
         if (!lpack_.Vp || lpack_.row1 - lpack_.row0 != rows) {
             dev::stream_sync(stream);
             dev::dfree(lpack_.Vp);
@@ -783,9 +787,11 @@ void Engine::ladder_sym(const double* t2, double* L, int64_t row0, int64_t row1,
     TView Lrows = make_view(L + row0 * o * o, {rows, o * o});
     TView LS = slice(Lrows, 1, 0, opp), LA = slice(Lrows, 1, opp, o * o);
     TView SpT = pitched(Sp, npp, opp, ldp), AmT = pitched(Am, npm, opm, ldm);
-    contract(1.0, packed_rows(lpack_.Vp, rows, npp), "rk", SpT, "kn", 0.0, LS, "rn");
+    double* Vp = shard_on_ ? srows_.Vp : lpack_.Vp;        // integral sharding: the stored rows are the only copy
+    double* Vm = shard_on_ ? srows_.Vm : lpack_.Vm;
+    contract(1.0, packed_rows(Vp, rows, npp), "rk", SpT, "kn", 0.0, LS, "rn");
     if (opm > 0) {
-        if (npm > 0) contract(1.0, packed_rows(lpack_.Vm, rows, npm), "rk", AmT, "kn", 0.0, LA, "rn");
+        if (npm > 0) contract(1.0, packed_rows(Vm, rows, npm), "rk", AmT, "kn", 0.0, LA, "rn");
         else zero(LA);
     }
     if (!hole) return;
@@ -804,10 +810,8 @@ void Engine::ladder_sym(const double* t2, double* L, int64_t row0, int64_t row1,
     TView IpK = pitched(Ip, ldp, opp, ldp), ImK = pitched(Im, ldp, opm, ldm);        // with the zero pad row
     if (hole == 1) {
         if (!static_.count("VpIjab")) {      // static per solve: dressed ijab == undressed ijab
-            double* vp = static_cast<double*>(dev::dmalloc(sizeof(double) * opp * lpitch(npp)));
-            double* vm = static_cast<double*>(dev::dmalloc(sizeof(double) * opp * lpitch(std::max<int64_t>(npm, 1))));
-            static_["VpIjab"] = vp;
-            static_["VmIjab"] = vm;
+            double* vp = new_static("VpIjab", opp * lpitch(npp));
+            double* vm = new_static("VmIjab", opp * lpitch(std::max<int64_t>(npm, 1)));
             dev::ladder_pack_V(block(P_ijab).p, vp, vm, no, nv, 0, opp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
         }
         contract(2.0, packed_rows(static_["VpIjab"], opp, npp), "rk", SpT, "kn", 2.0, Ipv, "rn");
@@ -833,6 +837,7 @@ void Engine::ladder_sym(const double* t2, double* L, int64_t row0, int64_t row1,
 // batch z.  EOM-CCSD builds sigma for every vector of the Davidson subspace per pass (eom_ccsd.py:95-101): at (30,120) one
 // vector is 228 tiles on 256 CUs, k vectors are k x 228 tiles with a k-split tail.
 void Engine::ladder_sym_multi(const double* const* xs, int k, double* L_all, bool dressed) {
+    refuse_if_sharded("ladder_sym_multi");
     const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opp = o * (o + 1) / 2,
                   opm = o * (o - 1) / 2;
     if (k < 1) return;
@@ -900,10 +905,8 @@ void Engine::hole_ladder_packed(const double* x, const double* I, double* L, int
         // I += sum_cd V_klcd y_cdij, formed pair-packed as well (the V.T part of the CCSD hole ladder, ccd.py:180, with y
         // in the place of T): [opp x npp] . [npp x opp] instead of the o^2 x v^2 x o^2 product
         if (!static_.count("VpIjab")) {
-            double* vp = static_cast<double*>(dev::dmalloc(sizeof(double) * opp * lpitch(npp)));
-            double* vm = static_cast<double*>(dev::dmalloc(sizeof(double) * opp * lpitch(std::max<int64_t>(npm, 1))));
-            static_["VpIjab"] = vp;
-            static_["VmIjab"] = vm;
+            double* vp = new_static("VpIjab", opp * lpitch(npp));
+            double* vm = new_static("VmIjab", opp * lpitch(std::max<int64_t>(npm, 1)));
             dev::ladder_pack_V(block(P_ijab).p, vp, vm, no, nv, 0, opp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
         }
         ArenaScope s2(arena);
@@ -956,10 +959,8 @@ void Engine::hole_ladder_packed_multi(const double* const* xs, const double* con
     TView Ipv = make_view(Ip, 3, id, is_), Imv = make_view(Im, 3, md, ms);
     if (ys) {
         if (!static_.count("VpIjab")) {
-            double* vp = static_cast<double*>(dev::dmalloc(sizeof(double) * opp * lpitch(npp)));
-            double* vm = static_cast<double*>(dev::dmalloc(sizeof(double) * opp * lpitch(std::max<int64_t>(npm, 1))));
-            static_["VpIjab"] = vp;
-            static_["VmIjab"] = vm;
+            double* vp = new_static("VpIjab", opp * lpitch(npp));
+            double* vm = new_static("VmIjab", opp * lpitch(std::max<int64_t>(npm, 1)));
             dev::ladder_pack_V(block(P_ijab).p, vp, vm, no, nv, 0, opp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
         }
         ArenaScope s2(arena);
@@ -1039,7 +1040,8 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
     const int64_t rows = row1 - row0, qrows = q1 - q0;
     const int64_t ldp = opp + (opp & 1), ldm = std::max<int64_t>(opm + (opm & 1), 2);   // even pitches: 16-byte loads
     // ---- static packs (once per solve) ---------------------------------------------------------
-    if (rows > 0 && !(lpack_.valid && !lpack_.dressed && lpack_.row0 == row0 && lpack_.row1 == row1)) {
+    if (rows > 0 && shard_on_) check_shard_rows("ladder_t1", row0, row1, false);
+    else if (rows > 0 && !(lpack_.valid && !lpack_.dressed && lpack_.row0 == row0 && lpack_.row1 == row1)) {
         if (!lpack_.Vp || lpack_.row1 - lpack_.row0 != rows) {
             dev::stream_sync(stream);
             dev::dfree(lpack_.Vp);
@@ -1075,10 +1077,14 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
             dress_off_ = true;
             dress = false;
         } else {
-            if (wp) { static_["VpDress" + rkey] = wp; static_["VmDress" + rkey] = wm; }
+            if (wp) {
+                static_["VpDress" + rkey] = wp; static_["VmDress" + rkey] = wm;
+                static_doubles_["VpDress" + rkey] = rows * lp; static_doubles_["VmDress" + rkey] = rows * lm;
+            }
             if (need_p) {
                 static_["VpKx"] = px;
                 static_["VmKx"] = mx;
+                static_doubles_["VpKx"] = ov * lp; static_doubles_["VmKx"] = ov * lm;
                 dev::ladder_pack_V(block(P_iabc).p, tp, tm, 0, nv, 0, ov, stream, lp, lm);
                 permute(1.0, make_view(tp, {o, v, lp}), "kxc", 0.0, make_view(px, {v, o, lp}), "xkc");
                 permute(1.0, make_view(tm, {o, v, lm}), "kxc", 0.0, make_view(mx, {v, o, lm}), "xkc");
@@ -1089,17 +1095,13 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
         }
     }
     if (!dress && qrows > 0 && !static_.count("VpK" + kkey)) {
-        double* vp = static_cast<double*>(dev::dmalloc(sizeof(double) * qrows * lpitch(npp)));
-        double* vm = static_cast<double*>(dev::dmalloc(sizeof(double) * qrows * lpitch(std::max<int64_t>(npm, 1))));
-        static_["VpK" + kkey] = vp;
-        static_["VmK" + kkey] = vm;
+        double* vp = new_static("VpK" + kkey, qrows * lpitch(npp));
+        double* vm = new_static("VmK" + kkey, qrows * lpitch(std::max<int64_t>(npm, 1)));
         dev::ladder_pack_V(block(P_iabc).p, vp, vm, 0, nv, q0, q1, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));          // rows (k,b) of V_kbcd as they are
     }
     if (!static_.count("VpIjab")) {
-        double* vp = static_cast<double*>(dev::dmalloc(sizeof(double) * opp * lpitch(npp)));
-        double* vm = static_cast<double*>(dev::dmalloc(sizeof(double) * opp * lpitch(std::max<int64_t>(npm, 1))));
-        static_["VpIjab"] = vp;
-        static_["VmIjab"] = vm;
+        double* vp = new_static("VpIjab", opp * lpitch(npp));
+        double* vm = new_static("VmIjab", opp * lpitch(std::max<int64_t>(npm, 1)));
         dev::ladder_pack_V(block(P_ijab).p, vp, vm, no, nv, 0, opp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
     }
     ArenaScope scope(arena);
@@ -1115,14 +1117,15 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
         stats.permute_calls++;
         stats.permute_bytes += 8.0 * 2.0 * double(v * v * o * o);
         TView SpT = pitched(Sp, npp, opp, ldp), AmT = pitched(Am, npm, opm, ldm);
-        const double* Ap = lpack_.Vp;
-        const double* Am_ = lpack_.Vm;
+        // (integral sharding: the stored rows take the place of the pack; the dressing writes to its own copy as ever)
+        const double* Ap = shard_on_ ? srows_.Vp : lpack_.Vp;
+        const double* Am_ = shard_on_ ? srows_.Vm : lpack_.Vm;
         if (dress && rows > 0) {
             ArenaScope s3(arena);
             double* ws = arena.alloc(dev::ladder_dress_ws_doubles(no, nv));
-            dev::ladder_dress(lpack_.Vp, static_["VpKx"], t1, static_["VpDress" + rkey], no, nv, lpitch(npp), row0, row1, -1.0, ws, stream);
+            dev::ladder_dress(Ap, static_["VpKx"], t1, static_["VpDress" + rkey], no, nv, lpitch(npp), row0, row1, -1.0, ws, stream);
             if (npm > 0)
-                dev::ladder_dress(lpack_.Vm, static_["VmKx"], t1, static_["VmDress" + rkey], no, nv, lpitch(npm), row0, row1, 1.0, ws, stream);
+                dev::ladder_dress(Am_, static_["VmKx"], t1, static_["VmDress" + rkey], no, nv, lpitch(npm), row0, row1, 1.0, ws, stream);
             Ap = static_["VpDress" + rkey];
             Am_ = static_["VmDress" + rkey];
         }
@@ -1551,6 +1554,7 @@ void Engine::cc_update(double* t, double* dt, const double* r, double shift, dou
 // -----------------------------------------------------------------------------------
 // ---- whole steps ------------------------------------------------------------------------------------------------------------
 void Engine::ccsd_residuals(const double* f, const double* t1, const double* t2, unsigned flags, double* r1, double* r2) {
+    refuse_if_sharded("ccsd_residuals (single rank)");
     const int64_t o = no, v = nv, ov = o * v, npp = v * (v + 1) / 2;
     if (!res_ETd_) {
         // all five or none: a failed allocation in the middle must not leave a half-initialised set behind, and a
@@ -1586,6 +1590,7 @@ void Engine::ccsd_residuals(const double* f, const double* t1, const double* t2,
 
 void Engine::ccsd_iterate(const double* f, double* t1, double* t2, unsigned flags, double shift, double delta, double* dt1,
                           double* dt2, double out[6]) {
+    refuse_if_sharded("ccsd_iterate (single rank)");
     const int64_t o = no, v = nv;
     if (!res_r1_) {
         if (capturing_) throw Error("ccsd_iterate: the staging buffers must exist before a launch graph is recorded");
@@ -1744,6 +1749,7 @@ void Engine::ccsd_sharded_residuals(const double* f, double* fd, const double* t
     if (!dev::fused_pair_kernels_ok(no)) throw Error("sharded step: nocc too large for the pair-sharded tail");
     const Hooks h{coll_, stream};
     const int rank = coll_.rank, world = coll_.world;
+    check_shard_rank("ccsd_sharded_residuals", rank, world);
     const int64_t o = no, v = nv, ov = o * v, o2 = o * o;
     // flag bits of include/pymes_amd.h: PYMES_DCD 1, PYMES_USE_DRESSED 2, PYMES_SYM_LADDER 8, PYMES_SYM_RINGS 16,
     // PYMES_SLAB_RINGS_ONLY 64, PYMES_SLAB_LADDERS_ONLY 128
@@ -1818,6 +1824,7 @@ void Engine::ccd_sharded_residuals(const double* f, double* t2, const ShardBuffe
     if (!dev::fused_pair_kernels_ok(no)) throw Error("sharded step: nocc too large for the pair-sharded tail");
     const Hooks h{coll_, stream};
     const int rank = coll_.rank, world = coll_.world;
+    check_shard_rank("ccd_sharded_residuals", rank, world);
     const int64_t o = no, v = nv, ov = o * v, o2 = o * o;
     const unsigned dcd = flags & 1u, kSlabRingsOnly = 64u, kSlabLaddersOnly = 128u;
     const unsigned slab = dcd | 8u | 16u;                      // undressed blocks: CCD / DCD have no T1 (ccd.py:100-121)
@@ -1959,6 +1966,186 @@ void Engine::ccd_energy(const double* t2, double out[2]) {
     energy_norms(nullptr, nullptr, t2, nullptr, r);
     out[0] = r[1];
     out[1] = r[2];
+}
+
+// -----------------------------------------------------------------------------------
+// integral sharding (pymes_set_integral_shard): V_abcd exists only as this rank's rows of its pair-packed form
+// -----------------------------------------------------------------------------------
+namespace {
+// bytes of the one staging buffer through which a host (or device) V_pqrs reaches the device in sharded mode
+int64_t shard_staging_bytes() {
+    if (const char* e = getenv("PYMES_SHARD_STAGING_BYTES")) {
+        const long long b = atoll(e);
+        if (b > 0) return b;
+    }
+    return int64_t(1) << 30;
+}
+}
+
+void Engine::set_integral_shard(int rank, int world) {
+    if (world < 1 || rank < 0 || rank >= world) throw Error("integral shard: need 0 <= rank < world");
+    if (shard_on_) throw Error("the context already shards its integrals");
+    for (int p = 0; p < 16; ++p)
+        if (V_[p] || Vd_[p]) throw Error("pymes_set_integral_shard must be called before any pymes_set_V_* call");
+    shard_on_ = true;
+    shard_rank_ = rank;
+    shard_world_ = world;
+    pair_chunk(rank, world, srows_.row0, srows_.row1);
+}
+
+void Engine::refuse_if_sharded(const char* who) const {
+    if (!shard_on_) return;
+    throw Error(std::string(who) + ": not available with integral sharding (pymes_set_integral_shard, rank " +
+                std::to_string(shard_rank_) + " of " + std::to_string(shard_world_) +
+                "): the context holds only its rows of the pair-packed V_abcd, not the full or dressed block");
+}
+
+void Engine::check_shard_rank(const char* who, int rank, int world) const {
+    if (shard_on_ && (rank != shard_rank_ || world != shard_world_))
+        throw Error(std::string(who) + ": rank " + std::to_string(rank) + " of " + std::to_string(world) +
+                    " does not match the integral shard of this context (rank " + std::to_string(shard_rank_) + " of " +
+                    std::to_string(shard_world_) + ")");
+}
+
+void Engine::check_shard_rows(const char* who, int64_t row0, int64_t row1, bool dressed) const {
+    if (dressed) refuse_if_sharded((std::string(who) + " with the dressed V_abcd").c_str());
+    if (row0 != srows_.row0 || row1 != srows_.row1)
+        throw Error(std::string(who) + ": pair rows [" + std::to_string(row0) + "," + std::to_string(row1) +
+                    ") are not the rows [" + std::to_string(srows_.row0) + "," + std::to_string(srows_.row1) +
+                    ") that this context holds (integral sharding, rank " + std::to_string(shard_rank_) + " of " +
+                    std::to_string(shard_world_) + ")");
+    if (!srows_.set) throw Error(std::string(who) + ": the rows of V_abcd have not been set (integral sharding)");
+}
+
+void Engine::shard_rows(const double** vp, const double** vm, int64_t* row0, int64_t* row1, int64_t* ldp, int64_t* ldm) const {
+    if (!shard_on_) throw Error("pymes_shard_rows_ptr: the context does not shard its integrals");
+    if (!srows_.set) throw Error("pymes_shard_rows_ptr: the rows of V_abcd have not been set");
+    const int64_t v = nv;
+    *vp = srows_.Vp;
+    *vm = srows_.Vm;
+    *row0 = srows_.row0;
+    *row1 = srows_.row1;
+    *ldp = lpitch(v * (v + 1) / 2);
+    *ldm = lpitch(std::max<int64_t>(v * (v - 1) / 2, 1));
+}
+
+void Engine::shard_rows_alloc() {
+    const int64_t v = nv, rows = srows_.row1 - srows_.row0;
+    if (srows_.Vp || rows <= 0) return;
+    srows_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * lpitch(v * (v + 1) / 2)));
+    srows_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * lpitch(std::max<int64_t>(v * (v - 1) / 2, 1))));
+}
+
+int64_t Engine::integral_bytes() const {
+    const int64_t v = nv, lp = lpitch(v * (v + 1) / 2), lm = lpitch(std::max<int64_t>(v * (v - 1) / 2, 1));
+    int64_t d = 0;
+    for (int p = 0; p < 16; ++p) d += (V_[p] ? block_size(p) : 0) + (Vd_[p] ? block_size(p) : 0);
+    for (auto& kv : static_doubles_) d += kv.second;
+    if (lpack_.Vp) d += (lpack_.row1 - lpack_.row0) * (lp + lm);
+    if (srows_.Vp) d += (srows_.row1 - srows_.row0) * (lp + lm);
+    return d * static_cast<int64_t>(sizeof(double));
+}
+
+// The planes V[a,b,:,:] of this rank's pair rows (V0: the element V[0,0,0,0] of the virtual block, strides st), gathered in
+// pair order — consecutive b of one a are one strided copy — into the staging buffer chunk by chunk and packed by
+// ladder_pack_V in its nr == 0 form (the rows of the chunk are consecutive planes).
+void Engine::shard_rows_from(const double* V0, const int64_t st[4], bool on_device) {
+    shard_rows_alloc();
+    const int64_t v = nv, plane = v * v, lp = lpitch(v * (v + 1) / 2), lm = lpitch(std::max<int64_t>(v * (v - 1) / 2, 1));
+    const int64_t r0 = srows_.row0, r1 = srows_.row1;
+    srows_.set = false;
+    if (r1 > r0) {
+        const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(r1 - r0, shard_staging_bytes() / (8 * plane)));
+        std::vector<double> host(on_device ? 0 : cap * plane);
+        double* stage = static_cast<double*>(dev::dmalloc(sizeof(double) * cap * plane));
+        try {
+            for (int64_t c0 = r0; c0 < r1; c0 += cap) {
+                const int64_t c1 = std::min(r1, c0 + cap);
+                for (int64_t r = c0; r < c1;) {
+                    const int64_t a = a_of_pair_row(r), b = r - a * (a + 1) / 2;
+                    const int64_t nb = std::min(c1, (a + 1) * (a + 2) / 2) - r;          // planes (a,b) .. (a,b+nb-1)
+                    const double* src = V0 + a * st[0] + b * st[1];
+                    if (on_device) {
+                        const int64_t dims[3] = {nb, v, v}, sst[3] = {st[1], st[2], st[3]};
+                        copy(make_view(const_cast<double*>(src), 3, dims, sst), make_view(stage + (r - c0) * plane, {nb, v, v}));
+                    } else {
+                        double* dst = host.data() + (r - c0) * plane;
+                        for (int64_t q = 0; q < nb; ++q)
+                            for (int64_t c = 0; c < v; ++c) {
+                                const double* row = src + q * st[1] + c * st[2];
+                                double* out = dst + (q * v + c) * v;
+                                if (st[3] == 1) std::memcpy(out, row, sizeof(double) * v);
+                                else for (int64_t d = 0; d < v; ++d) out[d] = row[d * st[3]];
+                            }
+                    }
+                    r += nb;
+                }
+                if (!on_device) dev::memcpy_h2d(stage, host.data(), sizeof(double) * (c1 - c0) * plane, stream);
+                dev::ladder_pack_V(stage - c0 * plane, srows_.Vp + (c0 - r0) * lp, srows_.Vm + (c0 - r0) * lm, 0, nv, c0, c1,
+                                   stream, lp, lm);
+                dev::stream_sync(stream);            // the staging buffers are refilled next
+            }
+        } catch (...) {
+            dev::dfree(stage);
+            throw;
+        }
+        dev::dfree(stage);
+        // the nr == 0 form packs every row as it is: the V^- rows of the pairs a == b are zero in the [nr,nr,nc,nc] form
+        for (int64_t a = 0; a < v; ++a) {
+            const int64_t r = a * (a + 3) / 2;
+            if (r >= r0 && r < r1) dev::memset_zero(srows_.Vm + (r - r0) * lm, sizeof(double) * lm, stream);
+        }
+        dev::stream_sync(stream);
+    }
+    srows_.set = true;
+}
+
+void Engine::shard_rows_from_factors(const double* Bd, int naux) {
+    shard_rows_alloc();
+    const int64_t v = nv, lp = lpitch(v * (v + 1) / 2), lm = lpitch(std::max<int64_t>(v * (v - 1) / 2, 1));
+    srows_.set = false;
+    if (srows_.row1 > srows_.row0)
+        dev::ladder_pack_V_factors(Bd, srows_.Vp, srows_.Vm, naux, n, no, srows_.row0, srows_.row1, stream, lp, lm);
+    srows_.set = true;
+}
+
+// V_pqrs without staging n^4 on the device: the 15 blocks other than V_abcd (host: gathered in slices of their first index
+// through a bounded host buffer, uploaded into their own storage; device: strided copies as in set_V_full) and the rows
+void Engine::set_V_full_sharded(const double* V, bool on_device, const int64_t strides[4]) {
+    const int64_t nn = n;
+    int64_t st[4] = {nn * nn * nn, nn * nn, nn, 1};
+    if (on_device && strides)
+        for (int i = 0; i < 4; ++i) st[i] = strides[i];
+    std::vector<double> host;
+    for (int pat = 0; pat < 15; ++pat) {
+        if (!V_[pat]) V_[pat] = static_cast<double*>(dev::dmalloc(sizeof(double) * block_size(pat)));
+        int64_t d[4], off = 0;
+        for (int i = 0; i < 4; ++i) {
+            const bool virt = pat >> (3 - i) & 1;
+            d[i] = virt ? nv : no;
+            if (virt) off += no * st[i];
+        }
+        const double* src = V + off;
+        if (on_device) {
+            TView sv = make_view(const_cast<double*>(src), 4, d, st);
+            copy(sv, block_view(V_[pat], pat));
+            continue;
+        }
+        const int64_t slice_el = d[1] * d[2] * d[3];
+        const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(d[0], shard_staging_bytes() / (8 * slice_el)));
+        host.resize(static_cast<size_t>(cap * slice_el));
+        for (int64_t i0 = 0; i0 < d[0]; i0 += cap) {
+            const int64_t i1 = std::min(d[0], i0 + cap);
+            double* out = host.data();
+            for (int64_t i = i0; i < i1; ++i)
+                for (int64_t j = 0; j < d[1]; ++j)
+                    for (int64_t k = 0; k < d[2]; ++k, out += d[3])
+                        std::memcpy(out, src + i * st[0] + j * st[1] + k * st[2], sizeof(double) * d[3]);
+            dev::memcpy_h2d(V_[pat] + i0 * slice_el, host.data(), sizeof(double) * (i1 - i0) * slice_el, stream);
+            dev::stream_sync(stream);
+        }
+    }
+    shard_rows_from(V + no * (st[0] + st[1] + st[2] + st[3]), st, on_device);
 }
 
 }  // namespace pymes

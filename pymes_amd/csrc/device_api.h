@@ -217,6 +217,12 @@ void tau_build(double* tau, const double* t2, const double* t1, int no, int nv, 
 // nr == 0: V is [rows,nc,nc] and the rows [rp0, rp1) are taken as they are (no zero rows in Vm).
 void ladder_pack_V(const double* V, double* Vp, double* Vm, int nr, int nc, int64_t rp0, int64_t rp1, stream_t s,
                    int64_t ldvp = 0, int64_t ldvm = 0);      // row pitches of Vp / Vm (0: nc(nc+1)/2, nc(nc-1)/2)
+// ladder_pack_V_factors: the same rows straight from density-fitting factors B [naux,n,n] (device, n = no + nv), without any
+// v^4 block: V[a,b,c,d] = sum_Q B[Q,no+a,no+c] B[Q,no+b,no+d] for the pair rows P(a,b) in [rp0, rp1), written to Vp / Vm
+// exactly as ladder_pack_V writes them for the [nv,nv,nv,nv] form of that block (zero V^- rows for a == b).  fp64 MFMA; the
+// product library only (the host simulator has no definition: a weak one in the engine throws).
+void ladder_pack_V_factors(const double* B, double* Vp, double* Vm, int naux, int n, int no, int64_t rp0, int64_t rp1,
+                           stream_t s, int64_t ldvp, int64_t ldvm);
 // ladder_dress: T1 dressing of the bra of pair-packed rows (ccsd.py:414-419 as far as the packed ladder reads it).
 // V, W: [row1 - row0][ld], rows r = P(a,b) in [row0,row1); Pk: [nv*no][ld], rows (x,k) = x*no + k of V_kxcd packed like V:
 //   W[r] = V[r] - sum_k t1[a,k] Pk[(b,k)] + sgn sum_k t1[b,k] Pk[(a,k)]     (sgn = -1: "plus" half, +1: "minus" half, whose

@@ -154,6 +154,8 @@ Engine::~Engine() {
         dev::dfree(splitk_ws_);
         dev::dfree(lpack_.Vp);
         dev::dfree(lpack_.Vm);
+        dev::dfree(srows_.Vp);
+        dev::dfree(srows_.Vm);
         dev::dfree(eps_o);
         dev::dfree(eps_v);
         arena.release();
@@ -281,7 +283,15 @@ void Engine::exchange_asymmetry_V(double out[2]) {
 void Engine::invalidate_static() {
     for (auto& kv : static_) dev::dfree(kv.second);
     static_.clear();
-    lpack_.valid = false;
+    static_doubles_.clear();
+    lpack_.valid = false;          // (the rows of an integral shard are not a cache: they stay)
+}
+
+double* Engine::new_static(const std::string& key, int64_t doubles) {
+    double* p = static_cast<double*>(dev::dmalloc(sizeof(double) * doubles));
+    static_[key] = p;
+    static_doubles_[key] = doubles;
+    return p;
 }
 
 int64_t Engine::block_size(int pattern) const {
@@ -298,6 +308,7 @@ bool Engine::has_block(int pattern, bool dressed) const {
     return (dressed ? Vd_[pattern & 15] : V_[pattern & 15]) != nullptr;
 }
 TView Engine::block(int pattern, bool dressed) {
+    if ((pattern & 15) == 15) refuse_if_sharded("integral block 'abcd'");
     double* p = dressed ? Vd_[pattern & 15] : V_[pattern & 15];
     if (!p)
         throw Error(std::string(dressed ? "dressed" : "undressed") + " integral block '" + canonical_name(pattern) +
@@ -306,11 +317,13 @@ TView Engine::block(int pattern, bool dressed) {
 }
 double* Engine::ensure_block(int pattern) {
     pattern &= 15;
+    if (pattern == 15) refuse_if_sharded("storage of the block 'abcd'");
     invalidate_static();
     if (!V_[pattern]) V_[pattern] = static_cast<double*>(dev::dmalloc(sizeof(double) * block_size(pattern)));
     return V_[pattern];
 }
 double* Engine::ensure_dressed(int pattern) {
+    if (pattern == 15) refuse_if_sharded("dressing of the block 'abcd'");
     if (!Vd_[pattern]) Vd_[pattern] = static_cast<double*>(dev::dmalloc(sizeof(double) * block_size(pattern)));
     return Vd_[pattern];
 }
@@ -672,6 +685,10 @@ void Engine::contract(double alpha, const TView& A, const char* sa, const TView&
 // ---------------------------------------------------------------------------------
 void Engine::set_V_full(const double* V, bool on_device, const int64_t strides[4]) {
     invalidate_static();
+    if (shard_on_) {
+        set_V_full_sharded(V, on_device, strides);
+        return;
+    }
     const int64_t nn = n;
     double* full = nullptr;
     const double* src = V;
@@ -710,6 +727,12 @@ void Engine::set_V_full(const double* V, bool on_device, const int64_t strides[4
 void Engine::set_V_block(const char* name, const double* data, bool on_device, const int64_t strides[4]) {
     const int pat = pattern_of_name(name);
     invalidate_static();
+    if (pat == 15 && shard_on_) {
+        if (on_device) refuse_if_sharded("set_V_block('abcd') from device memory");
+        const int64_t v = nv, st[4] = {v * v * v, v * v, v, 1};
+        shard_rows_from(data, st, false);
+        return;
+    }
     if (!V_[pat]) V_[pat] = static_cast<double*>(dev::dmalloc(sizeof(double) * block_size(pat)));
     if (!on_device) {
         dev::memcpy_h2d(V_[pat], data, sizeof(double) * block_size(pat), stream);
@@ -732,7 +755,7 @@ void Engine::set_V_from_factors(const double* B_host, int naux) {
     try {
         dev::memcpy_h2d(Bd, B_host, sizeof(double) * naux * nn * nn, stream);
         TView Bv = make_view(Bd, {naux, nn, nn});
-        for (int pat = 0; pat < 16; ++pat) {
+        for (int pat = 0; pat < (shard_on_ ? 15 : 16); ++pat) {
             if (!V_[pat]) V_[pat] = static_cast<double*>(dev::dmalloc(sizeof(double) * block_size(pat)));
             auto rng = [&](int pos, int64_t& lo, int64_t& hi) {
                 const bool virt = pat >> (3 - pos) & 1;
@@ -747,6 +770,7 @@ void Engine::set_V_from_factors(const double* B_host, int naux) {
             rng(3, lo, hi); Bqs = slice(Bqs, 2, lo, hi);
             contract(1.0, Bpr, "Qpr", Bqs, "Qqs", 0.0, block_view(V_[pat], pat), "pqrs", "pq");
         }
+        if (shard_on_) shard_rows_from_factors(Bd, naux);      // this rank's rows of V_abcd, no v^4 block
         dev::stream_sync(stream);
     } catch (...) {
         dev::dfree(Bd);
@@ -756,3 +780,11 @@ void Engine::set_V_from_factors(const double* B_host, int naux) {
 }
 
 }  // namespace pymes
+
+namespace dev {
+// Backends without the factor kernel (the host simulator): the product library's strong definition (kernels.hip) replaces it.
+__attribute__((weak)) void ladder_pack_V_factors(const double*, double*, double*, int, int, int, int64_t, int64_t, stream_t,
+                                                 int64_t, int64_t) {
+    throw std::runtime_error("ladder_pack_V_factors: not available in this backend");
+}
+}  // namespace dev

@@ -154,6 +154,15 @@ class Engine {
     void set_V_full(const double* V, bool on_device, const int64_t strides[4]);
     void set_V_block(const char* name, const double* data, bool on_device, const int64_t strides[4]);
     void set_V_from_factors(const double* B_host, int naux);
+    // Integral sharding (pymes_set_integral_shard, before any set_V_*): V_abcd is never allocated; the context holds instead the
+    // undressed pair-packed rows [r0,r1) = pair_chunk(rank, world) (V^+ / V^- at the ladder pitch, the layout of
+    // dev::ladder_pack_V) as the only copy of it.  Only the sharded ladders of that (rank, world) are served from them.
+    void set_integral_shard(int rank, int world);
+    bool integral_shard() const { return shard_on_; }
+    void refuse_if_sharded(const char* who) const;     // throws (naming the mode) when the context shards its integrals
+    void shard_rows(const double** vp, const double** vm, int64_t* row0, int64_t* row1, int64_t* ldp, int64_t* ldm) const;
+    // bytes held for integrals: undressed and dressed blocks, the stored / packed ladder rows and the static packs
+    int64_t integral_bytes() const;
     TView block(int pattern, bool dressed = false);       // throws if the block is absent
     double* ensure_block(int pattern);                    // storage of an undressed block (allocated if absent); cached
                                                           // derived quantities are invalidated
@@ -347,6 +356,25 @@ class Engine {
     double* V_[16] = {nullptr};      // undressed blocks (owned)
     double* Vd_[16] = {nullptr};     // dressed blocks (owned, allocated on demand)
     std::map<std::string, double*> static_;   // cached permutations of static blocks (owned)
+    std::map<std::string, int64_t> static_doubles_;   // their sizes (integral_bytes)
+    double* new_static(const std::string& key, int64_t doubles);
+    // integral sharding: this rank's undressed pair-packed rows of V_abcd (owned; never touched by invalidate_static)
+    bool shard_on_ = false;
+    int shard_rank_ = 0, shard_world_ = 1;
+    struct ShardRows {
+        double* Vp = nullptr;
+        double* Vm = nullptr;
+        int64_t row0 = 0, row1 = 0;
+        bool set = false;
+    } srows_;
+    void shard_rows_alloc();
+    // ingestion without the full block: the 15 other blocks and this rank's planes V[a,b,:,:] through one bounded staging
+    // buffer (host or device V_pqrs), or the rows straight from the factors (dev::ladder_pack_V_factors)
+    void set_V_full_sharded(const double* V, bool on_device, const int64_t strides[4]);
+    void shard_rows_from(const double* V0, const int64_t st[4], bool on_device);
+    void shard_rows_from_factors(const double* Bd, int naux);
+    void check_shard_rows(const char* who, int64_t row0, int64_t row1, bool dressed) const;
+    void check_shard_rank(const char* who, int rank, int world) const;
     struct LadderPack {   // V^+ / V^- rows of the pair-packed ladder
         double* Vp = nullptr;
         double* Vm = nullptr;

@@ -1987,6 +1987,63 @@ __global__ void __launch_bounds__(256) ladder_pack_V_kernel(const double* __rest
     }
 }
 
+// The rows of the pair-packed V_abcd straight from density-fitting factors (integral sharding: no v^4 block exists).  Block =
+// one pair row P(a,b) and one 32 x 32 tile (c in tile tc, d in tile td, tc >= td); wave w computes the 16 x 16 quadrant
+// (w >> 1, w & 1) of the two products
+//   X[c,d] = sum_Q B[Q,a,c] B[Q,b,d] = V_abcd,    Y[c,d] = sum_Q B[Q,b,c] B[Q,a,d] = V_abdc
+// with v_mfma_f64_16x16x4_f64 (A: lane holds [row l&15][k l>>4], B: [k l>>4][col l&15], D: col l&15, row (l>>4) + 4 i).
+// The Q-panels of B[:,a,tile] and B[:,b,tile] (virtual indices, rows of 32 contiguous doubles) go through LDS 16 Q at a time.
+// Vp = X + Y, Vm = X - Y (zero for a == b) for c >= d: the values and layout of ladder_pack_V_kernel for the same rows.
+constexpr int kFacK = 16;
+__global__ void __launch_bounds__(256) ladder_pack_V_factors_kernel(const double* __restrict__ B, double* __restrict__ Vp,
+                                                                    double* __restrict__ Vm, int naux, int n, int no, long rp0,
+                                                                    long ntp, long npp, long npm) {
+    __shared__ double sAc[kFacK][33], sBc[kFacK][33], sAd[kFacK][33], sBd[kFacK][33];
+    const long bid = blockIdx.x;
+    const long row = bid / ntp;               // local pair row
+    const long tp = bid - row * ntp;          // tile pair (tc >= td)
+    int a, b, tc, td;
+    unrank_pair(rp0 + row, a, b);
+    unrank_pair(tp, tc, td);
+    const int nv = n - no, c0 = tc * 32, d0 = td * 32;
+    const long nn = (long)n * n;
+    const double* __restrict__ Ba = B + (long)(no + a) * n + no;     // B[Q, no+a, no+x] = Ba[Q nn + x]
+    const double* __restrict__ Bb = B + (long)(no + b) * n + no;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int wc = (w >> 1) * 16, wd = (w & 1) * 16, l15 = lane & 15, l4 = lane >> 4;
+    const int lx = t & 31, lk = t >> 5;       // staging: column lx of the panels, Q rows lk and lk + 8
+    v4d X = {0.0, 0.0, 0.0, 0.0}, Y = {0.0, 0.0, 0.0, 0.0};
+    for (int q0 = 0; q0 < naux; q0 += kFacK) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int k = lk + 8 * h, q = q0 + k;
+            const long qo = (long)q * nn;
+            const bool cok = q < naux && c0 + lx < nv, dok = q < naux && d0 + lx < nv;
+            sAc[k][lx] = cok ? Ba[qo + c0 + lx] : 0.0;
+            sBc[k][lx] = cok ? Bb[qo + c0 + lx] : 0.0;
+            sAd[k][lx] = dok ? Ba[qo + d0 + lx] : 0.0;
+            sBd[k][lx] = dok ? Bb[qo + d0 + lx] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < kFacK; kk += 4) {
+            const int k = kk + l4;
+            X = __builtin_amdgcn_mfma_f64_16x16x4f64(sAc[k][wc + l15], sBd[k][wd + l15], X, 0, 0, 0);
+            Y = __builtin_amdgcn_mfma_f64_16x16x4f64(sBc[k][wc + l15], sAd[k][wd + l15], Y, 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    const int d = d0 + wd + l15;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = c0 + wc + l4 + 4 * i;
+        if (c < nv && d < nv && c >= d) {
+            Vp[row * npp + (long)c * (c + 1) / 2 + d] = X[i] + Y[i];
+            if (c > d) Vm[row * npm + (long)c * (c - 1) / 2 + d] = (a > b) ? X[i] - Y[i] : 0.0;
+        }
+    }
+}
+
 // T1 dressing of the BRA of the pair-packed V_abcd (ccsd.py:414-419 restricted to what the packed ladder reads):
 //   W[P(a,b)][cd] = V[P(a,b)][cd] - sum_k t[a,k] Pk[(b,k)][cd] + sgn sum_k t[b,k] Pk[(a,k)][cd],     a >= b,
 // Pk = the rows (x,k) (x slow) of V_kxcd packed over (c,d) like V itself; sgn = -1 for the symmetric half (V_alcd + V_aldc =
@@ -5188,6 +5245,22 @@ void ladder_pack_V(const double* V, double* Vp, double* Vm, int nr, int nc, int6
     if (nblk > 0x7fffffffL) throw std::runtime_error("ladder_pack_V: grid too large");
     PYMES_LAUNCH(ladder_pack_V_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s, V, Vp, Vm, nr, nc,
                        (long)rp0, nt, ntp, npp, npm);
+    HIP_CHECK(hipGetLastError());
+}
+
+void ladder_pack_V_factors(const double* B, double* Vp, double* Vm, int naux, int n, int no, int64_t rp0, int64_t rp1,
+                           stream_t s, int64_t ldvp, int64_t ldvm) {
+    if (rp1 <= rp0) return;
+    const int nv = n - no;
+    if (naux < 1 || no < 0 || nv < 1 || rp0 < 0 || rp1 > (int64_t)nv * (nv + 1) / 2)
+        throw std::runtime_error("ladder_pack_V_factors: bad shape or pair-row range");
+    const long npp = ldvp ? (long)ldvp : (long)nv * (nv + 1) / 2, npm = ldvm ? (long)ldvm : (long)nv * (nv - 1) / 2;
+    const int nt = (nv + 31) / 32;
+    const long ntp = (long)nt * (nt + 1) / 2;
+    const long nblk = (rp1 - rp0) * ntp;
+    if (nblk > 0x7fffffffL) throw std::runtime_error("ladder_pack_V_factors: grid too large");
+    PYMES_LAUNCH(ladder_pack_V_factors_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s, B, Vp, Vm, naux, n, no,
+                 (long)rp0, ntp, npp, npm);
     HIP_CHECK(hipGetLastError());
 }
 

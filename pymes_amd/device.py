@@ -77,7 +77,7 @@ class DeviceArray:
 
 
 class Context:
-    def __init__(self, no, nv, device=0, workspace_bytes=0, lib=None, stream=None, allocator=None):
+    def __init__(self, no, nv, device=0, workspace_bytes=0, lib=None, stream=None, allocator=None, shard=None):
         self.lib = lib or _lib.default_library()
         self.no, self.nv, self.n = int(no), int(nv), int(no) + int(nv)
         self.device = int(device)
@@ -85,6 +85,18 @@ class Context:
         self.handle = None
         self.lib.call("pymes_ctx_create", C.byref(h), self.device, self.no, self.nv, int(workspace_bytes))
         self.handle = h
+        # shard = (rank, world): integral sharding (include/pymes_amd.h, pymes_set_integral_shard) — V_abcd is held only as
+        # this rank's rows of its pair-packed form; set before any integral is
+        self.shard = None
+        if shard is not None:
+            rank, world = int(shard[0]), int(shard[1])
+            try:
+                self.lib.call("pymes_set_integral_shard", h, rank, world)
+            except BaseException:
+                self.lib.call("pymes_ctx_destroy", h)
+                self.handle = None
+                raise
+            self.shard = (rank, world)
         self._allocator = allocator      # optional callable(n_doubles) -> (ptr, keepalive), e.g. torch-backed
         self._pool = {}
         self._spare, self._spare_bytes = {}, 0      # released buffers by size, for reuse (see _recycle)
@@ -311,6 +323,25 @@ class Context:
         if B.ndim != 3 or B.shape[1:] != (self.n, self.n):
             raise ValueError("B must be [naux, n, n]")
         self.lib.call("pymes_set_V_from_factors", self.handle, _lib.host_ptr(B), int(B.shape[0]))
+
+    def integral_bytes(self):
+        """Bytes the context holds for integrals: blocks (undressed and dressed), stored / packed V_abcd rows, static packs."""
+        b = C.c_int64()
+        self.lib.call("pymes_integral_bytes", self.handle, C.byref(b))
+        return b.value
+
+    def shard_rows(self):
+        """Host copies of the stored rows of a sharded context: (Vp [rows, v(v+1)/2], Vm [rows, v(v-1)/2], row0, row1)."""
+        vp, vm = C.c_void_p(), C.c_void_p()
+        r0, r1, ldp, ldm = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        self.lib.call("pymes_shard_rows_ptr", self.handle, C.byref(vp), C.byref(vm), C.byref(r0), C.byref(r1), C.byref(ldp),
+                      C.byref(ldm))
+        rows, nv = r1.value - r0.value, self.nv
+        if rows <= 0:
+            return np.zeros((0, nv * (nv + 1) // 2)), np.zeros((0, nv * (nv - 1) // 2)), r0.value, r1.value
+        P = DeviceArray(self, vp.value, (rows, ldp.value), owned=False, keepalive=self).get()
+        M = DeviceArray(self, vm.value, (rows, ldm.value), owned=False, keepalive=self).get()
+        return P[:, :nv * (nv + 1) // 2].copy(), M[:, :nv * (nv - 1) // 2].copy(), r0.value, r1.value
 
     def block_shape(self, name):
         return tuple(self.nv if ch in "abcd" else self.no for ch in name)

@@ -15,23 +15,26 @@ class DeviceIntegrals:
         self.no, self.nv = ctx.no, ctx.nv
         self.dtype = np.dtype(np.float64)
         self.shape = (ctx.n,) * 4
+        self.shard = ctx.shard
 
     @classmethod
-    def from_V_pqrs(cls, no, t_V_pqrs, **ctx_kwargs):
-        """pymes/integral/partition.py:4-39 on the device (one upload + 16 pack kernels)."""
+    def from_V_pqrs(cls, no, t_V_pqrs, shard=None, **ctx_kwargs):
+        """pymes/integral/partition.py:4-39 on the device (one upload + 16 pack kernels).  shard = (rank, world): only that
+        rank's rows of the pair-packed V_abcd are uploaded and kept (include/pymes_amd.h, pymes_set_integral_shard)."""
         V = np.asarray(t_V_pqrs)
         if np.iscomplexobj(V):
             raise NotImplementedError("complex integrals are not supported by the fp64 HIP path")
         n = V.shape[0]
-        ctx = Context(no, n - no, **ctx_kwargs)
+        ctx = Context(no, n - no, shard=shard, **ctx_kwargs)
         ctx.set_V_pqrs(V)
         return cls(ctx)
 
     @classmethod
-    def from_factors(cls, no, B, **ctx_kwargs):
-        """V[p,q,r,s] = sum_Q B[Q,p,r] B[Q,q,s], formed block by block with the fp64 MFMA GEMM."""
+    def from_factors(cls, no, B, shard=None, **ctx_kwargs):
+        """V[p,q,r,s] = sum_Q B[Q,p,r] B[Q,q,s], formed block by block with the fp64 MFMA GEMM.  shard = (rank, world): V_abcd
+        is never formed; that rank's rows of its pair-packed form are built straight from B."""
         n = B.shape[1]
-        ctx = Context(no, n - no, **ctx_kwargs)
+        ctx = Context(no, n - no, shard=shard, **ctx_kwargs)
         ctx.set_V_from_factors(B)
         return cls(ctx)
 

@@ -95,7 +95,7 @@ def run_replayable(ctx, st, body, key="residual"):
 
 class CCD:
     def __init__(self, no, delta_e=1.e-8, is_dcd=False, is_diis=True, is_dr_ccd=False, is_bruekner=False,
-                 device=0):
+                 device=0, shard_integrals=False):
         if is_dr_ccd or is_bruekner:
             raise NotImplementedError("dr-CCD and Brueckner energies (ccd.py:95-121) are outside the HIP hot path")
         self.is_dcd = is_dcd
@@ -106,14 +106,30 @@ class CCD:
         self.delta_e = delta_e
         self.max_iter = 50
         self.device = device
+        self.shard_integrals = shard_integrals
         if self.is_diis:
             self.mixer = diis.DIIS(dim_space=6)
 
     # ---- device plumbing shared with CCSD ------------------------------------------------
+    def _integral_shard(self):
+        """(rank, world) whose rows of V_abcd the solver's context keeps (shard_integrals=True), else None."""
+        if not getattr(self, "shard_integrals", False):
+            return None
+        from pymes_amd import dist as pdist
+        if not pdist.sharded():
+            raise ValueError("shard_integrals=True needs the sharded path (torch.distributed with world > 1, "
+                             "PYMES_FORCE_SHARDED=1 or dist.stub); the single-rank path holds the whole V_abcd")
+        rank, world, _ = pdist.world()
+        return rank, world
+
     def _integrals(self, t_fock_pq, t_V_pqrs):
+        shard = self._integral_shard()
         if isinstance(t_V_pqrs, DeviceIntegrals):
+            if shard is not None and t_V_pqrs.shard != shard:
+                raise ValueError("shard_integrals=True: the DeviceIntegrals hold the shard %s, this rank is %s"
+                                 % (t_V_pqrs.shard, shard))
             return t_V_pqrs, False
-        return DeviceIntegrals.from_V_pqrs(self.no, t_V_pqrs, device=self.device), True
+        return DeviceIntegrals.from_V_pqrs(self.no, t_V_pqrs, device=self.device, shard=shard), True
 
     def solve(self, t_fock_pq, t_V_pqrs, level_shift=0., sp=0, amps=None, **kwargs):
         """ccd.py:24-162."""

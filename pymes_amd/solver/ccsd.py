@@ -29,7 +29,8 @@ LOOP_KEYS = ("abij", "klij", "iajb", "iabj", "abcd")
 
 
 class CCSD(ccd.CCD):
-    def __init__(self, no, is_diis=True, delta_e=1.e-8, is_non_canonical=False, is_dcsd=False, device=0):
+    def __init__(self, no, is_diis=True, delta_e=1.e-8, is_non_canonical=False, is_dcsd=False, device=0,
+                 shard_integrals=False):
         self.t_T_ai = None
         self.t_T_abij = None
         self.is_dcd = is_dcsd
@@ -42,6 +43,9 @@ class CCSD(ccd.CCD):
         self.delta_e = delta_e
         self.debug_level = 1
         self.device = device
+        # opt-in: on the sharded path the context keeps only this rank's rows of the pair-packed V_abcd (ValueError on the
+        # single-rank path; include/pymes_amd.h, pymes_set_integral_shard)
+        self.shard_integrals = shard_integrals
         if self.is_diis:
             self.mixer = diis.DIIS(dim_space=6)
 

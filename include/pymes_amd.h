@@ -134,6 +134,27 @@ int pymes_V_block_ptr(pymes_ctx* ctx, const char* name, int dressed, double** de
 /* diag(f): eps_o[no], eps_v[nv] used by the denominators (ccsd.py:149-156) */
 int pymes_set_orbital_energies(pymes_ctx* ctx, const double* eps_o_host, const double* eps_v_host);
 
+/* ---- (T): the perturbative triples correction of CCSD(T) (closed shell, canonical orbitals) -------------------------------
+ * Notation V[p,q,r,s] = <pq|rs>, T[a,b,i,j], t1[a,i], eps = diag(f).  For an occupied triple (i,j,k):
+ *   w_ijk[a,b,c] = sum_f V_iabc[i,f,a,b] T[c,f,k,j] - sum_m V_ijak[i,j,a,m] T[b,c,m,k]
+ *   W_ijk[a,b,c] = w_ijk[abc] + w_ikj[acb] + w_jik[bac] + w_jki[bca] + w_kij[cab] + w_kji[cba]
+ *   Y_ijk[a,b,c] = W_ijk[abc] + V_ijab[j,k,b,c] t1[a,i] + V_ijab[i,k,a,c] t1[b,j] + V_ijab[i,j,a,b] t1[c,k]
+ *   R(Y)[a,b,c]  = 4Y[abc] + Y[bca] + Y[cab] - 2Y[cba] - 2Y[acb] - 2Y[bac]
+ *   S_ijk        = 1/3 sum_abc W[abc] R(Y)[abc] / (eps_i + eps_j + eps_k - eps_a - eps_b - eps_c)
+ *   E(T)         = sum_{i >= j >= k} m_ijk S_ijk,   m = 6 (i > j > k), 3 (two equal), 1 (i = j = k)
+ * The unique triples are numbered i ascending, then j <= i, then k <= j (t = i(i+1)(i+2)/6 + j(j+1)/2 + k);
+ * pymes_ccsd_t_triples gives their number o(o+1)(o+2)/6.  pymes_ccsd_t sums m_ijk S_ijk over [t_begin, t_end) (one rank's
+ * share: the caller adds the ranks' sums) into *e_out_host and, if per_triple_dev is not NULL, writes the m_ijk S_ijk of the
+ * range there (t_end - t_begin doubles, device).  eps_host [n] (host), t1_dev [v,o] (NULL: CCD amplitudes), t2_dev [v,v,o,o]
+ * with T_abij = T_baji.  Reads only the UNDRESSED blocks iabc, aibc, ijak (and ijab with t1): valid after pymes_ccsd_dress_V and
+ * on a context with pymes_set_integral_shard.  Refused: a missing block (named), a call while a launch graph is recorded,
+ * integrals without V_pqrs = V_rspq (max |V_iabc - V_abic|, |V_ijak - V_aijk| above 1e-10 max |V|: transcorrelated
+ * Hamiltonians).  Each per-triple value and the sum (fixed order) are the same whatever the batch of triples the call
+ * holds at once (PYMES_TRIPLES_BATCH=<n> forces it).  Synchronises; frees what it allocates before it returns. */
+int pymes_ccsd_t_triples(pymes_ctx* ctx, int64_t* n_triples);
+int pymes_ccsd_t(pymes_ctx* ctx, const double* eps_host, const double* t1_dev, const double* t2_dev, int64_t t_begin,
+                 int64_t t_end, double* per_triple_dev, double* e_out_host);
+
 /* ---- the CC hot path ------------------------------------------------------------- */
 /* pymes/solver/mp2.py:9-22: T2 = V_abij/(D+shift) into t2_dev; e_out = {direct, exchange} */
 int pymes_mp2(pymes_ctx* ctx, double level_shift, double* t2_dev, double* e_out_host);

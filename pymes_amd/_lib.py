@@ -66,6 +66,9 @@ SIGNATURES = {
     "pymes_set_integral_shard": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pymes_integral_bytes": (C.c_int, [C.c_void_p, c_i64_p]),
     "pymes_shard_rows_ptr": (C.c_int, [C.c_void_p, c_pp, c_pp, c_i64_p, c_i64_p, c_i64_p, c_i64_p]),
+    "pymes_ccsd_t_triples": (C.c_int, [C.c_void_p, c_i64_p]),
+    "pymes_ccsd_t": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                               c_double_p]),
     "pymes_set_orbital_energies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pymes_mp2": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, c_double_p]),
     "pymes_ccsd_dress_fock": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -308,6 +308,19 @@ int pymes_V_block_ptr(pymes_ctx* ctx, const char* name, int dressed, double** p,
         if (nel) *nel = v.size();
     });
 }
+int pymes_ccsd_t_triples(pymes_ctx* ctx, int64_t* n_triples) {
+    return guarded([&] {
+        need(n_triples, "n_triples");
+        *n_triples = Engine::triples_count(E(ctx).no);
+    });
+}
+int pymes_ccsd_t(pymes_ctx* ctx, const double* eps_host, const double* t1_dev, const double* t2_dev, int64_t t_begin,
+                 int64_t t_end, double* per_triple_dev, double* e_out_host) {
+    return guarded([&] {
+        need(eps_host, "eps"); need(t2_dev, "t2"); need(e_out_host, "e_out");
+        *e_out_host = E(ctx).ccsd_t(eps_host, t1_dev, t2_dev, t_begin, t_end, per_triple_dev);
+    });
+}
 int pymes_set_integral_shard(pymes_ctx* ctx, int rank, int world) {
     return guarded([&] { E(ctx).set_integral_shard(rank, world); });
 }

@@ -11,6 +11,7 @@
 // so that every ring/exchange term of ccd.py:190-240 is a plain product of two such
 // matrices (possibly transposed), with no per-term transposition of the operands.
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <cstdlib>
 #include <vector>
@@ -2146,6 +2147,155 @@ void Engine::set_V_full_sharded(const double* V, bool on_device, const int64_t s
         }
     }
     shard_rows_from(V + no * (st[0] + st[1] + st[2] + st[3]), st, on_device);
+}
+
+// ---------------------------------------------------------------------------------
+// (T) correction: include/pymes_amd.h, pymes_ccsd_t (the formulas there and in tests/_triples_reference.py)
+// ---------------------------------------------------------------------------------
+int64_t Engine::triples_count(int no) { return (int64_t)no * (no + 1) * (no + 2) / 6; }
+
+namespace {
+// device buffers of one ccsd_t call, released on every way out
+struct DevBufs {
+    std::vector<void*> p;
+    double* get(int64_t doubles) {
+        p.push_back(dev::dmalloc(sizeof(double) * std::max<int64_t>(doubles, 1)));
+        return static_cast<double*>(p.back());
+    }
+    ~DevBufs() {
+        for (void* q : p) dev::dfree(q);
+    }
+};
+void unrank_triple(int64_t t, int& i, int& j, int& k) {
+    int x = 0;
+    while ((int64_t)(x + 1) * (x + 2) * (x + 3) / 6 <= t) ++x;
+    int64_t r = t - (int64_t)x * (x + 1) * (x + 2) / 6;
+    int y = 0;
+    while ((int64_t)(y + 1) * (y + 2) / 2 <= r) ++y;
+    i = x;
+    j = y;
+    k = (int)(r - (int64_t)y * (y + 1) / 2);
+}
+}  // namespace
+
+double Engine::ccsd_t(const double* eps_host, const double* t1, const double* t2, int64_t t_begin, int64_t t_end,
+                      double* per_triple) {
+    if (capturing_) throw Error("ccsd_t reads its energy back: not inside a launch graph");
+    if (!eps_host) throw Error("ccsd_t: null pointer: eps");
+    if (!t2) throw Error("ccsd_t: null pointer: t2");
+    const int64_t ntot = triples_count(no);
+    if (t_begin < 0 || t_end < t_begin || t_end > ntot)
+        throw Error("ccsd_t: triple range [" + std::to_string(t_begin) + ", " + std::to_string(t_end) + ") outside [0, " +
+                    std::to_string(ntot) + ")");
+    constexpr int P_aijk = 8;
+    // the UNDRESSED blocks only (a T1 dressing of the same context does not touch them)
+    for (int pat : {P_iabc, P_aibc, P_ijak, P_abic, P_aijk})
+        if (!V_[pat]) throw Error("ccsd_t needs the undressed integral block '" + canonical_name(pat) + "', which has not been set");
+    if (t1 && !V_[P_ijab]) throw Error("ccsd_t needs the undressed integral block 'ijab', which has not been set");
+    const int64_t o = no, v = nv, v2 = v * v, v3 = v2 * v;
+    DevBufs bufs;
+    // Hermitian integrals (V_pqrs = V_rspq): V_iabc[i,a,b,c] = V_abic[b,c,i,a], V_ijak[i,j,a,k] = V_aijk[a,k,i,j].  The partner
+    // is permuted into the [d1,d0,d3,d2] layout that dev::exchange_asymmetry compares against (max |A[p,q,r,s] - B[q,p,s,r]|).
+    {
+        DevBufs chk;
+        double* Bt = chk.get(std::max(o * v3, o * o * o * v));     // holds either partner: [v,o,v,v] and [o,o,o,v]
+        double worst = 0.0, vmax = 0.0;
+        const char* what = "";
+        permute(1.0, block(P_abic), "bcia", 0.0, make_view(Bt, {v, o, v, v}), "aicb");
+        const int64_t d1[4] = {o, v, v, v};
+        double r[2];
+        dev::exchange_asymmetry(V_[P_iabc], Bt, d1, r, stream);
+        worst = r[0]; vmax = r[1]; what = "V_iabc - V_abic";
+        permute(1.0, block(P_aijk), "akij", 0.0, make_view(Bt, {o, o, o, v}), "jika");
+        const int64_t d2[4] = {o, o, v, o};
+        dev::exchange_asymmetry(V_[P_ijak], Bt, d2, r, stream);
+        if (r[0] > worst) { worst = r[0]; what = "V_ijak - V_aijk"; }
+        vmax = std::max(vmax, r[1]);
+        if (!(worst <= 1e-10 * vmax)) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "ccsd_t needs Hermitian integrals (V_pqrs = V_rspq): max |%s| = %.3e against max |V| = %.3e "
+                     "(a transcorrelated Hamiltonian has no (T) here)", what, worst, vmax);
+            throw Error(buf);
+        }
+    }
+    if (t_end == t_begin) return 0.0;
+    // the permuted amplitudes: T2o[x][y][f][z] = T[z,f,x,y] (particle products), T2h[m][k][b][c] = T[b,c,m,k] (hole products;
+    // with T[c,b,m,j] = T[b,c,j,m], the exchange symmetry of CC amplitudes)
+    double* T2o = bufs.get(o * o * v2);
+    double* T2h = bufs.get(o * o * v2);
+    const TView Tv = make_view(t2, {v, v, o, o});
+    permute(1.0, Tv, "zfxy", 0.0, make_view(T2o, {o, o, v, v}), "xyfz");
+    permute(1.0, Tv, "bcmk", 0.0, make_view(T2h, {o, o, v, v}), "mkbc");
+    double* eps = bufs.get(n);
+    dev::memcpy_h2d(eps, eps_host, sizeof(double) * n, stream);
+    double* out = per_triple ? per_triple : bufs.get(t_end - t_begin);
+    // batch: W of that many triples is held before one launch of the energy kernel.  Each W_ijk is built by products of its
+    // own (the same launches whatever the batch), so the per-triple values do not depend on it.  Default: 128 MB of W, within a
+    // quarter of the free memory (measured, DESIGN 7b: at (50,200) 8 triples per batch take 21.3 s against 20.1 s for this
+    // default's 2; at (30,120) one triple per batch takes 4x as long, the energy launches under-fill the chip).
+    int64_t batch = 0;
+    if (const char* e = getenv("PYMES_TRIPLES_BATCH")) batch = atoll(e);
+    if (batch <= 0) {
+        const double budget = std::min(128.0 * (1 << 20), 0.25 * (double)dev::mem_free_bytes());
+        batch = std::max<int64_t>(1, (int64_t)(budget / (8.0 * (double)v3)));
+    }
+    batch = std::min<int64_t>({batch, t_end - t_begin, 65535});
+    double* W = bufs.get(batch * v3);
+    double* partial = bufs.get(dev::triples_partial_doubles(nv, batch));
+    const double* Viabc = V_[P_iabc];
+    const double* Vaibc = V_[P_aibc];
+    const double* Vijak = V_[P_ijak];
+    auto mm = [&](double* C, int64_t M, int64_t N, int64_t K, double alpha, double beta, const double* A, int64_t a_sm,
+                  int64_t a_sk, const double* B, int64_t b_sk, int64_t b_sn, int64_t ldc, int64_t nb = 1, int64_t b_b = 0,
+                  int64_t c_b = 0) {
+        dev::Gemm g{};
+        g.M = M; g.N = N; g.K = K;
+        g.alpha = alpha; g.beta = beta;
+        g.A = A; g.a_sm = a_sm; g.a_sk = a_sk;
+        g.B = B; g.b_sk = b_sk; g.b_sn = b_sn;
+        g.C = C; g.ldc = ldc;
+        g.nb1 = nb; g.nb2 = 1;
+        g.a_b1 = 0; g.b_b1 = b_b; g.c_b1 = c_b;
+        g.a_b2 = g.b_b2 = g.c_b2 = 0;
+        g.splitk_ws = nullptr;          // no k-split: the order of every sum is that of the tile kernel alone
+        g.splitk_ws_doubles = 0;
+        dev::gemm(g, stream);
+        stats.gemm_calls++;
+        stats.gemm_flops += 2.0 * (double)M * (double)N * (double)K * (double)nb;
+    };
+    for (int64_t t0 = t_begin; t0 < t_end; t0 += batch) {
+        const int64_t nt = std::min(batch, t_end - t0);
+        for (int64_t q = 0; q < nt; ++q) {
+            int i, j, k;
+            unrank_triple(t0 + q, i, j, k);
+            double* Wq = W + q * v3;
+            // W[a][b][c] = w_ijk[abc] + w_jik[bac] + w_ikj[acb] + w_kij[cab] + w_jki[bca] + w_kji[cba], each w_pqr[x,y,z] =
+            //   sum_f V_iabc[p,f,x,y] T2o[r][q][f][z] - sum_m V_ijak[p,q,x,m] T2h[m][r][y][z]
+            // written with the unit-stride index c as N: V_iabc[p,f,y,x] = V_aibc[f,p,x,y] supplies the swapped pairs.
+            // particle products (K = v)
+            mm(Wq, v2, v, v, 1.0, 0.0, Viabc + i * v3, 1, v2, T2o + (k * o + j) * v2, v, 1, v);                 // w_ijk[a,b,c]
+            mm(Wq, v2, v, v, 1.0, 1.0, Vaibc + j * v2, 1, o * v2, T2o + (k * o + i) * v2, v, 1, v);             // w_jik[b,a,c]
+            mm(Wq, v, v, v, 1.0, 1.0, T2o + (j * o + k) * v2, 1, v, Viabc + i * v3, v2, 1, v, v, v, v2);       // w_ikj[a,c,b]
+            mm(Wq, v, v, v, 1.0, 1.0, T2o + (j * o + i) * v2, 1, v, Vaibc + k * v2, o * v2, 1, v, v, v, v2);   // w_kij[c,a,b]
+            mm(Wq, v, v2, v, 1.0, 1.0, T2o + (i * o + k) * v2, 1, v, Viabc + j * v3, v2, 1, v2);               // w_jki[b,c,a]
+            mm(Wq, v, v2, v, 1.0, 1.0, T2o + (i * o + j) * v2, 1, v, Vaibc + k * v2, o * v2, 1, v2);           // w_kji[c,b,a]
+            // hole products (K = o)
+            mm(Wq, v, v2, o, -1.0, 1.0, Vijak + (i * o + j) * v * o, o, 1, T2h + k * v2, o * v2, 1, v2);       // w_ijk[a,b,c]
+            mm(Wq, v, v2, o, -1.0, 1.0, Vijak + (i * o + k) * v * o, o, 1, T2h + j * o * v2, v2, 1, v2);       // w_ikj[a,c,b]
+            mm(Wq, v, v, o, -1.0, 1.0, Vijak + (j * o + i) * v * o, o, 1, T2h + k * v2, o * v2, 1, v, v, v, v2);   // w_jik[b,a,c]
+            mm(Wq, v, v, o, -1.0, 1.0, Vijak + (j * o + k) * v * o, o, 1, T2h + i * o * v2, v2, 1, v, v, v, v2);   // w_jki[b,c,a]
+            mm(Wq, v2, v, o, -1.0, 1.0, T2h + j * v2, 1, o * v2, Vijak + (k * o + i) * v * o, 1, o, v);         // w_kij[c,a,b]
+            mm(Wq, v2, v, o, -1.0, 1.0, T2h + i * o * v2, 1, v2, Vijak + (k * o + j) * v * o, 1, o, v);         // w_kji[c,b,a]
+        }
+        dev::triples_energy(W, nt, t0, t1 ? V_[P_ijab] : nullptr, t1, eps, partial, out + (t0 - t_begin), no, nv, stream);
+    }
+    // the sum over the range in a fixed order (the same whatever the batch)
+    std::vector<double> h(t_end - t_begin);
+    dev::memcpy_d2h(h.data(), out, sizeof(double) * h.size(), stream);
+    dev::stream_sync(stream);
+    double e = 0.0;
+    for (double x : h) e += x;
+    return e;
 }
 
 }  // namespace pymes

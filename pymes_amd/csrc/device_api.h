@@ -223,6 +223,15 @@ void ladder_pack_V(const double* V, double* Vp, double* Vm, int nr, int nc, int6
 // product library only (the host simulator has no definition: a weak one in the engine throws).
 void ladder_pack_V_factors(const double* B, double* Vp, double* Vm, int naux, int n, int no, int64_t rp0, int64_t rp1,
                            stream_t s, int64_t ldvp, int64_t ldvm);
+// ---- (T) correction (cc.cpp, Engine::ccsd_t): the energy of a batch of nt consecutive unique triples t0, t0 + 1, ... (numbered
+// i ascending, then j <= i, then k <= j).  W [nt][v][v][v] holds W_ijk of each (the connected triples of the six permuted
+// products); Y = W + the disconnected term V_ijab[j,k,b,c] t1[a,i] + V_ijab[i,k,a,c] t1[b,j] + V_ijab[i,j,a,b] t1[c,k] is formed
+// on the fly (t1 [v,o], Vijab [o,o,v,v]; t1 null: Y = W).  eps [n] = diag(f) (device).  out[q] = m_ijk / 3 sum_abc W R(Y) / D
+// (include/pymes_amd.h), each summed in a fixed order whatever nt is; partial: triples_partial_doubles(nv, nt) doubles of
+// scratch.  nt <= 65535.  The product library only (the host simulator has no definition: a weak one in the engine throws).
+int64_t triples_partial_doubles(int nv, int64_t nt);
+void triples_energy(const double* W, int64_t nt, int64_t t0, const double* Vijab, const double* t1, const double* eps,
+                    double* partial, double* out, int no, int nv, stream_t s);
 // ladder_dress: T1 dressing of the bra of pair-packed rows (ccsd.py:414-419 as far as the packed ladder reads it).
 // V, W: [row1 - row0][ld], rows r = P(a,b) in [row0,row1); Pk: [nv*no][ld], rows (x,k) = x*no + k of V_kxcd packed like V:
 //   W[r] = V[r] - sum_k t1[a,k] Pk[(b,k)] + sgn sum_k t1[b,k] Pk[(a,k)]     (sgn = -1: "plus" half, +1: "minus" half, whose

@@ -787,4 +787,10 @@ __attribute__((weak)) void ladder_pack_V_factors(const double*, double*, double*
                                                  int64_t, int64_t) {
     throw std::runtime_error("ladder_pack_V_factors: not available in this backend");
 }
+// ... and without the (T) energy kernel
+__attribute__((weak)) int64_t triples_partial_doubles(int nv, int64_t nt) { return nt * ((int64_t)nv * (nv + 1) / 2); }
+__attribute__((weak)) void triples_energy(const double*, int64_t, int64_t, const double*, const double*, const double*, double*,
+                                          double*, int, int, stream_t) {
+    throw std::runtime_error("triples_energy: not available in this backend");
+}
 }  // namespace dev

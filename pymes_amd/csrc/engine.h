@@ -299,6 +299,12 @@ class Engine {
     int ccsd_sharded_finish(const double* f, const double* t1, const double* tc, const double* dtc, const ShardBuffers& b);
     void ccsd_sharded_energy(int slot, double out[6]);
     void ccsd_sharded_await(double* t2, const ShardBuffers& b);
+    // (T) correction (include/pymes_amd.h, pymes_ccsd_t): the sum of m_ijk S_ijk over the unique triples [t_begin, t_end) from
+    // the UNDRESSED blocks iabc, aibc, ijak (ijab with t1; abic, aijk for the check of V_pqrs = V_rspq), eps = diag(f) [n]
+    // (host), t1 [v,o] (may be null: CCD), t2 [v,v,o,o] exchange-symmetric; per_triple (device, may be null) receives the
+    // m_ijk S_ijk of the range.  Synchronises the stream; everything it allocates is released on return.
+    static int64_t triples_count(int no);
+    double ccsd_t(const double* eps_host, const double* t1, const double* t2, int64_t t_begin, int64_t t_end, double* per_triple);
     void invalidate_static();
 
     double* eps_o = nullptr;

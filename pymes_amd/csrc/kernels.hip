@@ -5815,3 +5815,123 @@ bool gemv_dispatch(const dev::Gemm& g, long a_sm, long a_sk, long b_sk, long b_s
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------------------
+// (T) energy of a batch of occupied triples (cc.cpp, Engine::ccsd_t; include/pymes_amd.h, pymes_ccsd_t)
+// ------------------------------------------------------------------------------------
+namespace {
+
+// t = i(i+1)(i+2)/6 + j(j+1)/2 + k, i >= j >= k: the library's numbering of the unique triples
+__device__ __forceinline__ void unrank_triple(long t, int& i, int& j, int& k) {
+    int x = 0;
+    while ((long)(x + 1) * (x + 2) * (x + 3) / 6 <= t) ++x;
+    long r = t - (long)x * (x + 1) * (x + 2) / 6;
+    int y = 0;
+    while ((long)(y + 1) * (y + 2) / 2 <= r) ++y;
+    i = x;
+    j = y;
+    k = (int)(r - (long)y * (y + 1) / 2);
+}
+
+// One wave per (triple q of the batch, virtual pair a >= b); lane l takes the orbits {a,b,c}, c = l, l + 64, ... <= b.  The six
+// permutations of an orbit, P = (abc, bca, cab, cba, acb, bac), are read once each (W, then Y = W + the disconnected term
+// formed on the fly); the denominator is the same for all six, and R(Y) on the orbit is
+//   R_k = 3 y_k + (sum of the y of k's parity class) - 2 (sum of the other class)      (even: P0..P2, odd: P3..P5),
+// so the orbit contributes sum_k w_k R_k / D, divided by the number of times the list repeats a permutation (2 when two
+// of a, b, c are equal, 6 when all three are).  The lanes' sums are combined in a fixed order (wave_sum): one double per
+// (triple, pair) in `partial`.
+__global__ void __launch_bounds__(64) triples_orbit_kernel(const double* __restrict__ W, long t0, const double* __restrict__ Vijab,
+                                                           const double* __restrict__ t1, const double* __restrict__ eps,
+                                                           double* __restrict__ partial, int no, int nv, long npairs) {
+    const long p = blockIdx.x;
+    const long q = blockIdx.y;
+    int a, b, i, j, k;
+    unrank_pair(p, a, b);
+    unrank_triple(t0 + q, i, j, k);
+    const long v = nv, v2 = v * v;
+    const double* __restrict__ Wq = W + q * v2 * v;
+    const double dab = eps[i] + eps[j] + eps[k] - eps[no + a] - eps[no + b];
+    const double* Vjk = nullptr;
+    const double* Vik = nullptr;
+    const double* Vij = nullptr;
+    double tai = 0.0, tbi = 0.0, taj = 0.0, tbj = 0.0, tak = 0.0, tbk = 0.0;
+    if (t1) {
+        Vjk = Vijab + ((long)j * no + k) * v2;
+        Vik = Vijab + ((long)i * no + k) * v2;
+        Vij = Vijab + ((long)i * no + j) * v2;
+        tai = t1[(long)a * no + i]; tbi = t1[(long)b * no + i];
+        taj = t1[(long)a * no + j]; tbj = t1[(long)b * no + j];
+        tak = t1[(long)a * no + k]; tbk = t1[(long)b * no + k];
+    }
+    double acc = 0.0;
+    for (int c = threadIdx.x; c <= b; c += 64) {
+        const long A = a, B = b, Cc = c;
+        double w[6], y[6];
+        w[0] = Wq[A * v2 + B * v + Cc];
+        w[1] = Wq[B * v2 + Cc * v + A];
+        w[2] = Wq[Cc * v2 + A * v + B];
+        w[3] = Wq[Cc * v2 + B * v + A];
+        w[4] = Wq[A * v2 + Cc * v + B];
+        w[5] = Wq[B * v2 + A * v + Cc];
+#pragma unroll
+        for (int u = 0; u < 6; ++u) y[u] = w[u];
+        if (t1) {
+            const double tci = t1[Cc * no + i], tcj = t1[Cc * no + j], tck = t1[Cc * no + k];
+            // disc(x,y,z) = V_jk[y,z] t1[x,i] + V_ik[x,z] t1[y,j] + V_ij[x,y] t1[z,k]
+            y[0] += Vjk[B * v + Cc] * tai + Vik[A * v + Cc] * tbj + Vij[A * v + B] * tck;     // (a,b,c)
+            y[1] += Vjk[Cc * v + A] * tbi + Vik[B * v + A] * tcj + Vij[B * v + Cc] * tak;     // (b,c,a)
+            y[2] += Vjk[A * v + B] * tci + Vik[Cc * v + B] * taj + Vij[Cc * v + A] * tbk;     // (c,a,b)
+            y[3] += Vjk[B * v + A] * tci + Vik[Cc * v + A] * tbj + Vij[Cc * v + B] * tak;     // (c,b,a)
+            y[4] += Vjk[Cc * v + B] * tai + Vik[A * v + B] * tcj + Vij[A * v + Cc] * tbk;     // (a,c,b)
+            y[5] += Vjk[A * v + Cc] * tbi + Vik[B * v + Cc] * taj + Vij[B * v + A] * tck;     // (b,a,c)
+        }
+        const double se = y[0] + y[1] + y[2], so = y[3] + y[4] + y[5];
+        const double re = se - 2.0 * so, ro = so - 2.0 * se;
+        double s = w[0] * (3.0 * y[0] + re) + w[1] * (3.0 * y[1] + re) + w[2] * (3.0 * y[2] + re) +
+                   w[3] * (3.0 * y[3] + ro) + w[4] * (3.0 * y[4] + ro) + w[5] * (3.0 * y[5] + ro);
+        const double inv_mult = (a == b && b == c) ? (1.0 / 6.0) : ((a == b || b == c) ? 0.5 : 1.0);
+        acc += s * inv_mult / (dab - eps[no + c]);
+    }
+    acc = wave_sum(acc);
+    if (threadIdx.x == 0) partial[q * npairs + p] = acc;
+}
+
+// out[q] = m_ijk / 3 * sum_p partial[q][p], summed in a fixed order
+__global__ void __launch_bounds__(256) triples_sum_kernel(const double* __restrict__ partial, long t0, long npairs,
+                                                          double* __restrict__ out) {
+    __shared__ double sh[4];
+    const long q = blockIdx.x;
+    double s = 0.0;
+    for (long p = threadIdx.x; p < npairs; p += 256) s += partial[q * npairs + p];
+    s = block_sum(s, sh);
+    if (threadIdx.x == 0) {
+        int i, j, k;
+        unrank_triple(t0 + q, i, j, k);
+        const double m = (i == j && j == k) ? 1.0 : ((i == j || j == k) ? 3.0 : 6.0);
+        out[q] = m * s / 3.0;
+    }
+}
+
+}  // namespace
+
+namespace dev {
+
+int64_t triples_partial_doubles(int nv, int64_t nt) { return nt * ((int64_t)nv * (nv + 1) / 2); }
+
+void triples_energy(const double* W, int64_t nt, int64_t t0, const double* Vijab, const double* t1, const double* eps,
+                    double* partial, double* out, int no, int nv, stream_t s) {
+    if (nt <= 0) return;
+    if (!W || !eps || !partial || !out || (t1 && !Vijab)) throw std::runtime_error("triples_energy: null operand");
+    const int64_t ntot = (int64_t)no * (no + 1) * (no + 2) / 6;
+    if (no < 1 || nv < 1 || t0 < 0 || t0 + nt > ntot) throw std::runtime_error("triples_energy: bad shape or triple range");
+    const long npairs = (long)nv * (nv + 1) / 2;
+    if (nt > 65535 || npairs > 0x7fffffffL) throw std::runtime_error("triples_energy: grid too large");
+    hipStream_t st = (hipStream_t)s;
+    PYMES_LAUNCH(triples_orbit_kernel, dim3((unsigned)npairs, (unsigned)nt), dim3(64), 0, st, W, (long)t0, Vijab, t1, eps,
+                 partial, no, nv, npairs);
+    HIP_CHECK(hipGetLastError());
+    PYMES_LAUNCH(triples_sum_kernel, dim3((unsigned)nt), dim3(256), 0, st, (const double*)partial, (long)t0, npairs, out);
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace dev

@@ -155,6 +155,29 @@ int pymes_ccsd_t_triples(pymes_ctx* ctx, int64_t* n_triples);
 int pymes_ccsd_t(pymes_ctx* ctx, const double* eps_host, const double* t1_dev, const double* t2_dev, int64_t t_begin,
                  int64_t t_end, double* per_triple_dev, double* e_out_host);
 
+/* ---- frozen natural orbitals (FNO) and frozen core (closed shell, canonical orbitals, Hermitian integrals) -----------------
+ * Orbital window: the n_frozen lowest occupied orbitals are dropped, the active ones are [n_frozen, no), no' = no - n_frozen.
+ * Amplitudes over the active occupied orbitals and all virtuals, eps = the context's orbital energies (pymes_set_orbital_energies):
+ *   t[a,b,i,j] = V_ijab[i,j,a,b] / (eps_i + eps_j - eps_a - eps_b),      E_MP2 = sum (2 t[a,b,i,j] - t[b,a,i,j]) V_ijab[i,j,a,b]
+ * and the spin-summed virtual block of the unrelaxed MP2 density (symmetric; eigenvalues = natural occupations in [0, 2]):
+ *   D[a,b] = 2 sum_{c,i,j} (2 t[a,c,i,j] - t[c,a,i,j]) t[b,c,i,j]
+ * pymes_fno_density writes D [nv,nv] (host, row-major) and E_MP2 of the window.  v_ijab_dev: a device [no,no,nv,nv] V_ijab
+ * (e.g. formed from density-fitting factors), NULL = the context's own undressed 'ijab' block (then the integrals must be
+ * Hermitian, checked as by pymes_ccsd_t).  The amplitudes are formed on the fly (no o^2 v^2 array); the kernel reads
+ * t[c,a,i,j] as V_jiac / d, so V_ijab = V_jiba is checked.  Fixed summation order without atomics: two calls give bit-identical
+ * D and E_MP2.  Refused: n_frozen outside [0, no), missing orbital energies or blocks, non-Hermitian (transcorrelated)
+ * integrals, a V_ijab without the exchange symmetry, a call while a launch graph is recorded.
+ * pymes_derive_context fills the EMPTY context dst, created with (no - n_frozen, nv_dst), with all 16 blocks of the space
+ * whose occupied orbitals are [n_frozen, no) of src and whose virtuals are the columns of C (host, row-major [nv, nv_dst]):
+ *   V'[p',q',r',s'] = V[p,q,r,s] with occupied indices sliced (p = p' + n_frozen) and every virtual index x' = sum_x C[x,x'] x
+ * One quarter-transform (fp64 MFMA GEMM) per virtual index, through at most one nv^3 nv_dst intermediate; nothing passes through
+ * the host.  dst then serves every call of a context (ladder packs, T1 dressing, pymes_ccsd_t); its orbital energies are the
+ * caller's to set.  Refused: src == dst, a sharded src or dst (pymes_set_integral_shard), a src without all 16 blocks or
+ * with non-Hermitian integrals, a dst with any block set or of the wrong size, n_frozen outside [0, no), nv_dst outside
+ * [1, nv], different devices, a recorded launch graph.  Both calls synchronise and free what they allocate. */
+int pymes_fno_density(pymes_ctx* ctx, const double* v_ijab_dev, int n_frozen, double* D_host, double* e_mp2_host);
+int pymes_derive_context(pymes_ctx* src, pymes_ctx* dst, int n_frozen, const double* C_host, int nv_dst);
+
 /* ---- the CC hot path ------------------------------------------------------------- */
 /* pymes/solver/mp2.py:9-22: T2 = V_abij/(D+shift) into t2_dev; e_out = {direct, exchange} */
 int pymes_mp2(pymes_ctx* ctx, double level_shift, double* t2_dev, double* e_out_host);

@@ -321,6 +321,18 @@ int pymes_ccsd_t(pymes_ctx* ctx, const double* eps_host, const double* t1_dev, c
         *e_out_host = E(ctx).ccsd_t(eps_host, t1_dev, t2_dev, t_begin, t_end, per_triple_dev);
     });
 }
+int pymes_fno_density(pymes_ctx* ctx, const double* v_ijab_dev, int n_frozen, double* D_host, double* e_mp2_host) {
+    return guarded([&] {
+        need(D_host, "D"); need(e_mp2_host, "e_mp2");
+        *e_mp2_host = E(ctx).fno_density(v_ijab_dev, n_frozen, D_host);
+    });
+}
+int pymes_derive_context(pymes_ctx* src, pymes_ctx* dst, int n_frozen, const double* C_host, int nv_dst) {
+    return guarded([&] {
+        need(src, "src"); need(dst, "dst"); need(C_host, "C");
+        E(dst).derive_from(E(src), n_frozen, C_host, nv_dst);
+    });
+}
 int pymes_set_integral_shard(pymes_ctx* ctx, int rank, int world) {
     return guarded([&] { E(ctx).set_integral_shard(rank, world); });
 }

@@ -2178,22 +2178,12 @@ void unrank_triple(int64_t t, int& i, int& j, int& k) {
 }
 }  // namespace
 
-double Engine::ccsd_t(const double* eps_host, const double* t1, const double* t2, int64_t t_begin, int64_t t_end,
-                      double* per_triple) {
-    if (capturing_) throw Error("ccsd_t reads its energy back: not inside a launch graph");
-    if (!eps_host) throw Error("ccsd_t: null pointer: eps");
-    if (!t2) throw Error("ccsd_t: null pointer: t2");
-    const int64_t ntot = triples_count(no);
-    if (t_begin < 0 || t_end < t_begin || t_end > ntot)
-        throw Error("ccsd_t: triple range [" + std::to_string(t_begin) + ", " + std::to_string(t_end) + ") outside [0, " +
-                    std::to_string(ntot) + ")");
+void Engine::check_hermitian(const char* who, const char* why) {
     constexpr int P_aijk = 8;
-    // the UNDRESSED blocks only (a T1 dressing of the same context does not touch them)
-    for (int pat : {P_iabc, P_aibc, P_ijak, P_abic, P_aijk})
-        if (!V_[pat]) throw Error("ccsd_t needs the undressed integral block '" + canonical_name(pat) + "', which has not been set");
-    if (t1 && !V_[P_ijab]) throw Error("ccsd_t needs the undressed integral block 'ijab', which has not been set");
+    for (int pat : {P_iabc, P_abic, P_ijak, P_aijk})
+        if (!V_[pat])
+            throw Error(std::string(who) + " needs the undressed integral block '" + canonical_name(pat) + "', which has not been set");
     const int64_t o = no, v = nv, v2 = v * v, v3 = v2 * v;
-    DevBufs bufs;
     // Hermitian integrals (V_pqrs = V_rspq): V_iabc[i,a,b,c] = V_abic[b,c,i,a], V_ijak[i,j,a,k] = V_aijk[a,k,i,j].  The partner
     // is permuted into the [d1,d0,d3,d2] layout that dev::exchange_asymmetry compares against (max |A[p,q,r,s] - B[q,p,s,r]|).
     {
@@ -2212,12 +2202,31 @@ double Engine::ccsd_t(const double* eps_host, const double* t1, const double* t2
         if (r[0] > worst) { worst = r[0]; what = "V_ijak - V_aijk"; }
         vmax = std::max(vmax, r[1]);
         if (!(worst <= 1e-10 * vmax)) {
-            char buf[200];
-            snprintf(buf, sizeof buf, "ccsd_t needs Hermitian integrals (V_pqrs = V_rspq): max |%s| = %.3e against max |V| = %.3e "
-                     "(a transcorrelated Hamiltonian has no (T) here)", what, worst, vmax);
+            char buf[400];
+            snprintf(buf, sizeof buf, "%s needs Hermitian integrals (V_pqrs = V_rspq): max |%s| = %.3e against max |V| = %.3e "
+                     "(%s)", who, what, worst, vmax, why);
             throw Error(buf);
         }
     }
+}
+
+double Engine::ccsd_t(const double* eps_host, const double* t1, const double* t2, int64_t t_begin, int64_t t_end,
+                      double* per_triple) {
+    if (capturing_) throw Error("ccsd_t reads its energy back: not inside a launch graph");
+    if (!eps_host) throw Error("ccsd_t: null pointer: eps");
+    if (!t2) throw Error("ccsd_t: null pointer: t2");
+    const int64_t ntot = triples_count(no);
+    if (t_begin < 0 || t_end < t_begin || t_end > ntot)
+        throw Error("ccsd_t: triple range [" + std::to_string(t_begin) + ", " + std::to_string(t_end) + ") outside [0, " +
+                    std::to_string(ntot) + ")");
+    constexpr int P_aijk = 8;
+    // the UNDRESSED blocks only (a T1 dressing of the same context does not touch them)
+    for (int pat : {P_iabc, P_aibc, P_ijak, P_abic, P_aijk})
+        if (!V_[pat]) throw Error("ccsd_t needs the undressed integral block '" + canonical_name(pat) + "', which has not been set");
+    if (t1 && !V_[P_ijab]) throw Error("ccsd_t needs the undressed integral block 'ijab', which has not been set");
+    const int64_t o = no, v = nv, v2 = v * v, v3 = v2 * v;
+    DevBufs bufs;
+    check_hermitian("ccsd_t", "a transcorrelated Hamiltonian has no (T) here");
     if (t_end == t_begin) return 0.0;
     // the permuted amplitudes: T2o[x][y][f][z] = T[z,f,x,y] (particle products), T2h[m][k][b][c] = T[b,c,m,k] (hole products;
     // with T[c,b,m,j] = T[b,c,j,m], the exchange symmetry of CC amplitudes)
@@ -2296,6 +2305,121 @@ double Engine::ccsd_t(const double* eps_host, const double* t1, const double* t2
     double e = 0.0;
     for (double x : h) e += x;
     return e;
+}
+
+// ---- frozen natural orbitals (include/pymes_amd.h, pymes_fno_density / pymes_derive_context) --------------------------------
+namespace {
+const char* kFnoHermitian = "frozen natural orbitals are built here for Hermitian integrals only, not for transcorrelated ones";
+}
+
+double Engine::fno_density(const double* Vijab, int n_frozen, double* D_host) {
+    if (capturing_) throw Error("pymes_fno_density reads its result back: not inside a launch graph");
+    if (!D_host) throw Error("pymes_fno_density: null pointer: D");
+    if (n_frozen < 0 || n_frozen >= no)
+        throw Error("pymes_fno_density: n_frozen = " + std::to_string(n_frozen) + " outside [0, no) = [0, " + std::to_string(no) +
+                    ")");
+    need_eps("pymes_fno_density");
+    const int64_t o = no, v = nv;
+    if (!Vijab) {
+        if (!V_[P_ijab]) throw Error("pymes_fno_density needs the undressed integral block 'ijab', which has not been set");
+        check_hermitian("pymes_fno_density", kFnoHermitian);
+        Vijab = V_[P_ijab];
+    }
+    // the kernel reads t[c,a,i,j] as V[j,i,a,c] / d: V_ijab = V_jiba is required
+    {
+        const int64_t d[4] = {o, o, v, v};
+        double r[2];
+        dev::exchange_asymmetry(Vijab, Vijab, d, r, stream);
+        if (!(r[0] <= 1e-10 * r[1])) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "pymes_fno_density needs V_ijab = V_jiba: max |V_ijab - V_jiba| = %.3e against max |V| = %.3e",
+                     r[0], r[1]);
+            throw Error(buf);
+        }
+    }
+    DevBufs bufs;
+    double* partial = bufs.get(dev::fno_density_partial_doubles(no - n_frozen, nv));
+    double* Dd = bufs.get(v * v);
+    double* ed = bufs.get(1);
+    dev::fno_density(Vijab, eps_o, eps_v, no, n_frozen, nv, partial, Dd, ed, stream);
+    double e = 0.0;
+    dev::memcpy_d2h(D_host, Dd, sizeof(double) * v * v, stream);
+    dev::memcpy_d2h(&e, ed, sizeof(double), stream);
+    dev::stream_sync(stream);
+    return e;
+}
+
+void Engine::derive_from(Engine& src, int n_frozen, const double* C_host, int nv_dst) {
+    const char* who = "pymes_derive_context";
+    auto fail = [&](const std::string& m) { throw Error(std::string(who) + ": " + m); };
+    if (&src == this) fail("the source and the destination are the same context");
+    if (capturing_ || src.capturing_) fail("not inside a launch graph");
+    if (src.shard_on_) fail("the source context shards its integrals (pymes_set_integral_shard): derive from a replicated context");
+    if (shard_on_) fail("the destination context shards its integrals (pymes_set_integral_shard): it must be a plain empty context");
+    if (src.device != device) fail("the source and the destination are on different devices");
+    if (!C_host) fail("null pointer: C");
+    if (n_frozen < 0 || n_frozen >= src.no)
+        fail("n_frozen = " + std::to_string(n_frozen) + " outside [0, no) = [0, " + std::to_string(src.no) + ")");
+    if (nv_dst < 1 || nv_dst > src.nv)
+        fail("nv_dst = " + std::to_string(nv_dst) + " outside [1, nv] = [1, " + std::to_string(src.nv) + "]");
+    if (no != src.no - n_frozen || nv != nv_dst)
+        fail("the destination context is (no, nv) = (" + std::to_string(no) + ", " + std::to_string(nv) + "), expected (" +
+             std::to_string(src.no - n_frozen) + ", " + std::to_string(nv_dst) + ")");
+    for (int pat = 0; pat < 16; ++pat) {
+        if (!src.V_[pat]) fail("the source context lacks the integral block '" + canonical_name(pat) + "'");
+        if (V_[pat] || Vd_[pat]) fail("the destination context is not empty (block '" + canonical_name(pat) + "' is set)");
+    }
+    src.check_hermitian(who, kFnoHermitian);
+    dev::stream_sync(src.stream);
+    const int64_t o0 = src.no, v0 = src.nv, o1 = no, v1 = nv;
+    // ping-pong intermediates: the k-th transform of a block with m virtual indices holds o1^(4-m) v0^(m-k-1) v1^(k+1)
+    // doubles; even k go to buffer A, odd k to B, the last one straight into the destination block (at most one v0^3 v1
+    // intermediate: A of V_abcd after its first transform)
+    int64_t needA = 1, needB = 1;
+    for (int pat = 0; pat < 16; ++pat) {
+        const int m = __builtin_popcount(pat);
+        for (int k = 0; k + 1 < m; ++k) {
+            int64_t sz = 1;
+            for (int q = 0; q < 4 - m; ++q) sz *= o1;
+            for (int q = 0; q < m - k - 1; ++q) sz *= v0;
+            for (int q = 0; q < k + 1; ++q) sz *= v1;
+            (k % 2 ? needB : needA) = std::max(k % 2 ? needB : needA, sz);
+        }
+    }
+    DevBufs bufs;
+    double* Cd = bufs.get(v0 * v1);
+    dev::memcpy_h2d(Cd, C_host, sizeof(double) * v0 * v1, stream);
+    double* A = bufs.get(needA);
+    double* B = bufs.get(needB);
+    const TView Cv = make_view(Cd, {v0, v1});
+    const char* lab = "pqrs";
+    for (int pat = 0; pat < 16; ++pat) {
+        TView cur = src.block_view(src.V_[pat], pat);
+        std::vector<int> vpos;
+        for (int q = 0; q < 4; ++q) {
+            if (pat >> (3 - q) & 1) vpos.push_back(q);
+            else cur = slice(cur, q, n_frozen, o0);
+        }
+        const TView dst = block_view(ensure_block(pat), pat);
+        if (vpos.empty()) {
+            copy(cur, dst);
+            continue;
+        }
+        for (size_t k = 0; k < vpos.size(); ++k) {
+            const int q = vpos[k];
+            // out[.., z, ..] = sum_x in[.., x, ..] C[x, z] at position q; the labels in front of q are GEMM batches
+            int64_t dims[4];
+            for (int r = 0; r < 4; ++r) dims[r] = cur.dim[r];
+            dims[q] = v1;
+            const bool last = k + 1 == vpos.size();
+            const TView out = last ? dst : make_view(k % 2 ? B : A, 4, dims, nullptr);
+            std::string lo = lab, lc = std::string(1, lab[q]) + "z", batch(lab, lab + q);
+            lo[q] = 'z';
+            contract(1.0, cur, lab, Cv, lc.c_str(), 0.0, out, lo.c_str(), batch.c_str());
+            cur = out;
+        }
+    }
+    dev::stream_sync(stream);
 }
 
 }  // namespace pymes

@@ -232,6 +232,16 @@ void ladder_pack_V_factors(const double* B, double* Vp, double* Vm, int naux, in
 int64_t triples_partial_doubles(int nv, int64_t nt);
 void triples_energy(const double* W, int64_t nt, int64_t t0, const double* Vijab, const double* t1, const double* eps,
                     double* partial, double* out, int no, int nv, stream_t s);
+// ---- frozen natural orbitals (cc.cpp, Engine::fno_density): over the occupied window [nf, no) and all nv virtuals, with
+// t[a,b,i,j] = V_ijab[i,j,a,b] / (eps_o[i] + eps_o[j] - eps_v[a] - eps_v[b]) formed on the fly (no amplitude array),
+//   D[a][b] = 2 sum_{c,i,j} (2 t[a,c,i,j] - t[c,a,i,j]) t[b,c,i,j]   (exactly symmetric),   e[0] = sum (2 t_abij - t_baij) V_ijab
+// Vijab [no,no,nv,nv] must have the exchange symmetry V_ijab = V_jiba (t[c,a,i,j] is read as V[j,i,a,c] / d).  D [nv,nv],
+// e [1], eps_o [no], eps_v [nv] device; partial: fno_density_partial_doubles(no - nf, nv) doubles of scratch.  Fixed
+// summation order, no atomics: two calls give bit-identical results.  The product library only (the host simulator has no
+// definition: a weak one in the engine throws).
+int64_t fno_density_partial_doubles(int noa, int nv);
+void fno_density(const double* Vijab, const double* eps_o, const double* eps_v, int no, int nf, int nv, double* partial,
+                 double* D, double* e, stream_t s);
 // ladder_dress: T1 dressing of the bra of pair-packed rows (ccsd.py:414-419 as far as the packed ladder reads it).
 // V, W: [row1 - row0][ld], rows r = P(a,b) in [row0,row1); Pk: [nv*no][ld], rows (x,k) = x*no + k of V_kxcd packed like V:
 //   W[r] = V[r] - sum_k t1[a,k] Pk[(b,k)] + sgn sum_k t1[b,k] Pk[(a,k)]     (sgn = -1: "plus" half, +1: "minus" half, whose

@@ -305,6 +305,13 @@ class Engine {
     // m_ijk S_ijk of the range.  Synchronises the stream; everything it allocates is released on return.
     static int64_t triples_count(int no);
     double ccsd_t(const double* eps_host, const double* t1, const double* t2, int64_t t_begin, int64_t t_end, double* per_triple);
+    // V_pqrs = V_rspq on the undressed blocks iabc / abic and ijak / aijk (throws, naming `who` and `why`, otherwise)
+    void check_hermitian(const char* who, const char* why);
+    // frozen natural orbitals (include/pymes_amd.h): pymes_fno_density (Vijab: device [no,no,nv,nv], null = the context's own
+    // block; D_host [nv,nv]; returns E_MP2 of the window [n_frozen, no)) and pymes_derive_context (this = the empty destination
+    // of size (src.no - n_frozen, nv_dst); C_host [src.nv, nv_dst]).  Both synchronise; temporaries are freed on return.
+    double fno_density(const double* Vijab, int n_frozen, double* D_host);
+    void derive_from(Engine& src, int n_frozen, const double* C_host, int nv_dst);
     void invalidate_static();
 
     double* eps_o = nullptr;

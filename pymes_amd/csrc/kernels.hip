@@ -5935,3 +5935,164 @@ void triples_energy(const double* W, int64_t nt, int64_t t0, const double* Vijab
 }
 
 }  // namespace dev
+
+// ---------------------------------------------------------------------------------
+// Frozen natural orbitals: the virtual block of the unrelaxed MP2 density and E_MP2 over an occupied window
+// ---------------------------------------------------------------------------------
+namespace {
+
+// D_ab = 2 sum_K X[a,K] Y[b,K] over K = (i,j,c), i, j in [nf, no), with the amplitudes formed on the fly from V_ijab:
+//   X[a,(ijc)] = 2 t[a,c,i,j] - t[c,a,i,j] = (2 V[i,j,a,c] - V[j,i,a,c]) / d_ijac,   Y[b,(ijc)] = t[b,c,i,j] = V[i,j,b,c] / d_ijbc
+// (t[c,a,i,j] = V[i,j,c,a] / d = V[j,i,a,c] / d: the exchange symmetry V_pqrs = V_qpsr the caller has checked).  Block = one
+// 64 x 64 tile (ta >= tb: D is symmetric, the finish kernel mirrors) and one contiguous split of the flattened K chunks
+// (pair (i,j) slow, 32 c fast); wave w computes the 32 x 32 quadrant (w >> 1, w & 1) as 2 x 2 tiles of
+// v_mfma_f64_16x16x4_f64 (A: lane holds [row l&15][k l>>4], B: [k l>>4][col l&15], D: col l&15, row (l>>4) + 4 i).  Staging:
+// thread t reads c = c0 + (t & 31) of the rows (t >> 5) + 8 h (256-byte row segments), divides by the denominator and writes
+// LDS.  The blocks of the column tb = 0 also sum E_MP2 = sum X[a,c] V[i,j,a,c] over their rows.  No atomics: every block
+// writes its own partial tile and energy, summed in a fixed order by fno_density_finish_kernel.
+constexpr int kFnoT = 64, kFnoK = 32;
+__global__ void __launch_bounds__(256) fno_density_kernel(const double* __restrict__ V, const double* __restrict__ eo,
+                                                          const double* __restrict__ ev, int no, int nf, int nv, int nt,
+                                                          long nchunk, long kc_per, long kc_tot, double* __restrict__ part,
+                                                          double* __restrict__ epart) {
+    __shared__ double sX[kFnoK][kFnoT + 1], sY[kFnoK][kFnoT + 1];
+    __shared__ double sE[256];
+    const long ntp = (long)nt * (nt + 1) / 2;
+    const long tp = blockIdx.x, split = blockIdx.y;
+    int ta, tb;
+    unrank_pair(tp, ta, tb);
+    const int a0 = ta * kFnoT, b0 = tb * kFnoT;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int wa = (w >> 1) * 32, wb = (w & 1) * 32, l15 = lane & 15, l4 = lane >> 4;
+    const int sk = t & 31, sr = t >> 5;
+    const long vv = (long)nv * nv;
+    const int noa = no - nf;
+    const bool do_e = tb == 0;
+    const long kc0 = split * kc_per, kc1 = min(kc_tot, kc0 + kc_per);
+    v4d acc[2][2];
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) acc[x][y] = v4d{0.0, 0.0, 0.0, 0.0};
+    double esum = 0.0;
+    for (long kc = kc0; kc < kc1; ++kc) {
+        const long pr = kc / nchunk;
+        const int c = (int)(kc - pr * nchunk) * kFnoK + sk;
+        const int i = nf + (int)(pr / noa), j = nf + (int)(pr % noa);
+        const double* __restrict__ Vij = V + ((long)i * no + j) * vv;
+        const double* __restrict__ Vji = V + ((long)j * no + i) * vv;
+        const bool cok = c < nv;
+        const double dc = eo[i] + eo[j] - (cok ? ev[c] : 0.0);
+#pragma unroll
+        for (int h = 0; h < 8; ++h) {
+            const int r = sr + 8 * h, a = a0 + r, b = b0 + r;
+            double x = 0.0, y = 0.0;
+            if (cok && a < nv) {
+                const double vij = Vij[(long)a * nv + c];
+                x = (2.0 * vij - Vji[(long)a * nv + c]) / (dc - ev[a]);
+                if (do_e) esum += x * vij;
+            }
+            if (cok && b < nv) y = Vij[(long)b * nv + c] / (dc - ev[b]);
+            sX[sk][r] = x;
+            sY[sk][r] = y;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < kFnoK; kk += 4) {
+            const int k = kk + l4;
+            const double x0 = sX[k][wa + l15], x1 = sX[k][wa + 16 + l15];
+            const double y0 = sY[k][wb + l15], y1 = sY[k][wb + 16 + l15];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, y1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, y1, acc[1][1], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    double* __restrict__ P = part + (split * ntp + tp) * (kFnoT * kFnoT);
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) P[(wa + 16 * x + l4 + 4 * q) * kFnoT + wb + 16 * y + l15] = acc[x][y][q];
+    if (do_e) {
+        sE[t] = esum;
+        __syncthreads();
+        if (t == 0) {
+            double s = 0.0;
+            for (int q = 0; q < 256; ++q) s += sE[q];
+            epart[split * nt + ta] = s;
+        }
+    }
+}
+
+// D[a][b] = 2 sum_split part[split][tile][ra][rb] (the element (max, min) of (a, b) in the tile (max, min) of their row tiles), e = the
+// partial energies summed split by split, row tile by row tile
+__global__ void __launch_bounds__(256) fno_density_finish_kernel(const double* __restrict__ part, const double* __restrict__ epart,
+                                                                 int nv, int nt, long nsplit, double* __restrict__ D,
+                                                                 double* __restrict__ e) {
+    const long ntp = (long)nt * (nt + 1) / 2;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx == 0) {
+        double s = 0.0;
+        for (long q = 0; q < nsplit * nt; ++q) s += epart[q];
+        e[0] = s;
+    }
+    if (idx >= (long)nv * nv) return;
+    const int a = (int)(idx / nv), b = (int)(idx - (long)a * nv);
+    int ta = a / kFnoT, tb = b / kFnoT, ra = a - ta * kFnoT, rb = b - tb * kFnoT;
+    if (ta < tb || (ta == tb && ra < rb)) {       // the lower triangle: D is exactly symmetric
+        int x = ta; ta = tb; tb = x;
+        x = ra; ra = rb; rb = x;
+    }
+    const long tp = (long)ta * (ta + 1) / 2 + tb, off = (long)ra * kFnoT + rb;
+    double s = 0.0;
+    for (long q = 0; q < nsplit; ++q) s += part[(q * ntp + tp) * (kFnoT * kFnoT) + off];
+    D[idx] = 2.0 * s;
+}
+
+struct FnoPlan {
+    int nt;
+    long ntp, nchunk, kc_tot, kc_per, nsplit;
+};
+FnoPlan fno_plan(int noa, int nv) {
+    FnoPlan p;
+    p.nt = (nv + kFnoT - 1) / kFnoT;
+    p.ntp = (long)p.nt * (p.nt + 1) / 2;
+    p.nchunk = (nv + kFnoK - 1) / kFnoK;
+    p.kc_tot = (long)noa * noa * p.nchunk;
+    // about 1024 blocks (4 per CU) whatever the size; a function of (noa, nv) only, so two calls, on any device, sum alike
+    long want = std::max<long>(1, std::min<long>(std::min<long>((1024 + p.ntp - 1) / p.ntp, p.kc_tot), 65535));
+    p.kc_per = (p.kc_tot + want - 1) / want;
+    p.nsplit = (p.kc_tot + p.kc_per - 1) / p.kc_per;
+    return p;
+}
+
+}  // namespace
+
+namespace dev {
+
+int64_t fno_density_partial_doubles(int noa, int nv) {
+    const FnoPlan p = fno_plan(noa, nv);
+    return p.nsplit * p.ntp * (kFnoT * kFnoT) + p.nsplit * p.nt;
+}
+
+void fno_density(const double* Vijab, const double* eps_o, const double* eps_v, int no, int nf, int nv, double* partial,
+                 double* D, double* e, stream_t s) {
+    if (!Vijab || !eps_o || !eps_v || !partial || !D || !e) throw std::runtime_error("fno_density: null operand");
+    if (no < 1 || nv < 1 || nf < 0 || nf >= no) throw std::runtime_error("fno_density: bad shape or occupied window");
+    const FnoPlan p = fno_plan(no - nf, nv);
+    if (p.ntp > 0x7fffffffL) throw std::runtime_error("fno_density: grid too large");
+    double* epart = partial + p.nsplit * p.ntp * (kFnoT * kFnoT);
+    hipStream_t st = (hipStream_t)s;
+    PYMES_LAUNCH(fno_density_kernel, dim3((unsigned)p.ntp, (unsigned)p.nsplit), dim3(256), 0, st, Vijab, eps_o, eps_v, no, nf,
+                 nv, p.nt, p.nchunk, p.kc_per, p.kc_tot, partial, epart);
+    HIP_CHECK(hipGetLastError());
+    const long nblk = ((long)nv * nv + 255) / 256;
+    PYMES_LAUNCH(fno_density_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, (const double*)partial,
+                 (const double*)epart, nv, p.nt, p.nsplit, D, e);
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace dev

@@ -470,8 +470,19 @@ class CCSD(ccd.CCD):
         out = DeviceArray(ctx, lad.ptr + 8 * lo * no * no, (hi - lo, no * no), owned=False, keepalive=lad)
         ctx.contract("rk,kn->rn", rows, t2.reshape(nv * nv, no * no), out=out)
 
-    def solve(self, t_fock_pq, t_V_pqrs, level_shift=0., amps=None, sp=0, **kwargs):
-        """ccsd.py:47-224."""
+    def solve(self, t_fock_pq, t_V_pqrs, level_shift=0., amps=None, sp=0, frozen_core=0, fno_occ_threshold=None,
+              fno_nv=None, **kwargs):
+        """ccsd.py:47-224.
+
+        ``frozen_core=k`` drops the k lowest occupied orbitals; ``fno_occ_threshold`` / ``fno_nv`` keep the frozen natural
+        orbitals with at least that MP2 occupation / the first ``fno_nv`` of them (pymes_amd/solver/fno.py).  With any of
+        the three the solve runs in that space: "ccsd e", "(t) e", "t1", "t2", "hole e" and "particle e" are those of the
+        correlated space (new orbitals), "fno nv" is its number of virtuals and "fno dmp2 e" the MP2 energy of the dropped
+        virtuals (0.0 with the core frozen only); the total is "ccsd(t) e" + "fno dmp2 e".  Sources: a host V_pqrs or
+        replicated DeviceIntegrals; for density-fitting factors call fno.truncate and solve on its result."""
+        if frozen_core or fno_occ_threshold is not None or fno_nv is not None:
+            return self._solve_fno(t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv,
+                                   **kwargs)
         algo_name = "ccsd.solve"
         time_ccsd = time.time()
         max_iter = kwargs.get("max_iter", self.max_iter)
@@ -559,6 +570,31 @@ class CCSD(ccd.CCD):
                 ctx.close()      # (a DIIS history kept in this context is parked on the host on the way: Context.on_close)
             elif ctx.handle:
                 ccd.destroy_graphs(ctx, st)
+
+    def _solve_fno(self, t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv, **kwargs):
+        from pymes_amd.solver import fno
+        if self.shard_integrals:
+            raise ValueError("shard_integrals=True with frozen_core / fno_*: a host V_pqrs or block source is not derived as a "
+                             "sharded context; use fno.truncate(no, f, ('factors', B), shard=(rank, world))")
+        if kwargs.get("device_amplitudes"):
+            raise ValueError("device_amplitudes=True with frozen_core / fno_*: call fno.truncate and solve on its integrals")
+        if isinstance(t_V_pqrs, tuple):
+            raise ValueError("CCSD.solve takes a host V_pqrs or DeviceIntegrals; for factors call fno.truncate first")
+        time_fno = time.time()
+        r = fno.truncate(self.no, t_fock_pq, t_V_pqrs, n_frozen=frozen_core, occ_threshold=fno_occ_threshold,
+                         nv_keep=fno_nv, device=self.device)
+        print_logging_info("FNO: {} frozen core, {} of {} virtuals kept, dMP2 = {:.12f} ({:.3f} seconds)".format(
+            r.n_frozen, r.nv, r.C.shape[0], r.de_mp2, time.time() - time_fno), level=1)
+        no = self.no
+        self.no = r.no
+        try:
+            res = self.solve(r.fock, r.ints, level_shift, amps, sp, **kwargs)
+        finally:
+            self.no = no
+            r.close()
+        res["fno nv"] = r.nv
+        res["fno dmp2 e"] = r.de_mp2
+        return res
 
     # ------------------------------------------------------------------------------------
     # public helpers with the reference's host-array call forms (used by the EOM drivers)

@@ -128,6 +128,13 @@ PYMES_HD inline void finish(double* S, const double* L, const double* V, const d
     bool dependent = false, failed = false;
     for (int i = 0; i < n; ++i) dependent = dependent || (lam[i] < 1e-12 && lam[i] > -1e-12);
     for (int i = 0; i < n; ++i) failed = failed || !(lam[i] == lam[i]);                       // NaN overlaps
+    // an infinite overlap: the Jacobi sweeps leave it on the diagonal and the pseudo-inverse would drop it as if it were an
+    // ordinary eigenvalue, leaving finite coefficients of a subspace that has diverged (numpy.linalg.inv raises there)
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            const double a = L[i * 9 + j] < 0 ? -L[i * 9 + j] : L[i * 9 + j];
+            failed = failed || !(a <= 1.7976931348623157e308);
+        }
     for (int i = 0; i < n; ++i) unit[i] = (i == n - 1) ? -1.0 : 0.0;
     if (dependent) {
         for (int i = 0; i < n; ++i) c[i] = 0.0;

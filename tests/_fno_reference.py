@@ -22,6 +22,19 @@ def mp2_density(no, f, V, n_frozen=0):
     return D, e
 
 
+def mp2_density_ijab(Vijab, eps_o, eps_v, n_frozen=0):
+    """``mp2_density`` from V_ijab [no,no,v,v] and the orbital energies alone (no n^4 V_pqrs): the same D and E_MP2 over
+    occupied [n_frozen, no) and all virtuals."""
+    eo, ev = np.asarray(eps_o)[n_frozen:], np.asarray(eps_v)
+    V = np.asarray(Vijab)[n_frozen:, n_frozen:]
+    d = eo[:, None, None, None] + eo[None, :, None, None] - ev[None, None, :, None] - ev[None, None, None, :]
+    t = (V / d).transpose(2, 3, 0, 1)
+    tt = 2.0 * t - t.transpose(1, 0, 2, 3)
+    D = 2.0 * np.einsum("acij,bcij->ab", tt, t, optimize=True)
+    e = float(np.einsum("abij,ijab->", tt, V, optimize=True))
+    return D, e
+
+
 def sign_rule(M):
     M = M.copy()
     for k in range(M.shape[1]):

@@ -196,6 +196,62 @@ def test_product_gpu(gpu_lib, monkeypatch):
     run_product(gpu_lib, monkeypatch)
 
 
+DIAG_SHAPES = ((7, 33), (12, 48), (5, 70))      # the strided 256-lane loops of the diagonal kernels make several trips
+
+
+def check_eom_diagonals(lib, no, nv, seed):
+    """pymes_eom_diagonals (eom_diag_sums_kernel, eom_diag_doubles_kernel) on integrals and doubles without any symmetry,
+    undressed and after pymes_ccsd_dress_V has dressed the five blocks the call reads, against the host get_diag_singles /
+    get_diag_doubles on the same blocks (oracle dressing); then the FEAST preconditioner 1 / (z - hs d2 + shift) of that d2
+    against numpy complex arithmetic."""
+    import ctypes as C
+    from pymes_amd.device import Context
+    from pymes_amd.integral.partition import BLOCK_NAMES
+    from pymes_amd.solver.eom_ccsd import EOM_CCSD
+    f, V, t1, _ = random_case(no, nv, seed, symmetric=False)
+    t2 = np.random.default_rng(seed + 1).standard_normal((nv, nv, no, no)) * 0.1
+    Vb = oc.split_blocks(no, V)
+    del V
+    read = ("ijab", "iabj", "iajb", "klij", "abcd")
+    host = EOM_CCSD(no, 2)
+    ctx = Context(no, nv, lib=lib)
+    try:
+        for name in BLOCK_NAMES:
+            ctx.set_V_block(name, np.ascontiguousarray(Vb[name]))
+        T = ctx.array(t2)
+        fc = np.ascontiguousarray(f)
+        for dressed in (0, 1):
+            if dressed:
+                ctx.dress_V(ctx.array(t1), read)
+                blocks = oc.dressed_V(t1, Vb, read)
+            else:
+                blocks = {k: Vb[k] for k in read}
+            d1, d2 = ctx.empty((nv, no)), ctx.empty((nv, nv, no, no))
+            ctx.lib.call("pymes_eom_diagonals", ctx.handle, _lib.host_ptr(fc), C.c_void_p(T.ptr), dressed, C.c_void_p(d1.ptr),
+                         C.c_void_p(d2.ptr))
+            w1, w2 = host.get_diag_singles(f, blocks, t2), host.get_diag_doubles(f, blocks, t2)
+            g1, g2 = d1.get(), d2.get()
+            assert np.abs(g1 - w1).max() <= 1e-12 * np.abs(w1).max(), (no, nv, dressed)
+            assert np.abs(g2 - w2).max() <= 1e-12 * np.abs(w2).max(), (no, nv, dressed)
+        zr, zi = ctx.empty((d2.size,)), ctx.empty((d2.size,))
+        z, hs, shift = 0.3 + 0.2j, 1.0 - 0.5j, 0.01
+        ctx.cshift_inv(d2.reshape(d2.size), z, hs, shift, zr, zi)
+        want = 1.0 / (z - hs * g2.ravel() + shift)
+        assert np.abs(zr.get() + 1j * zi.get() - want).max() <= 1e-12 * np.abs(want).max()
+    finally:
+        ctx.close()
+
+
+def test_eom_diagonals_host_logic(hostsim_lib):
+    check_eom_diagonals(hostsim_lib, 7, 33, 51)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("no,nv", DIAG_SHAPES)
+def test_eom_diagonals_gpu(gpu_lib, no, nv):
+    check_eom_diagonals(gpu_lib, no, nv, 50 + no)
+
+
 @pytest.mark.gpu
 def test_sigma_gpu_larger(gpu_lib, monkeypatch):
     from pymes_amd.solver.eom_ccsd import EOM_CCSD

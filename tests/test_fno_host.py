@@ -166,3 +166,13 @@ def test_derive_context_refusals(hostsim_lib):
     finally:
         for c in opened:
             c.close()
+
+
+@pytest.mark.parametrize("nf", [0, 1, 2])
+def test_density_from_vijab_states_the_same_definition(nf):
+    """The reference the multi-tile GPU test uses (V_ijab and orbital energies alone) against the one from the full V_pqrs."""
+    no, nv = 5, 11
+    f, V, _, _ = synthetic_case(no, nv, seed=3, scale=0.3)
+    D, e = ref.mp2_density(no, f, V, nf)
+    D2, e2 = ref.mp2_density_ijab(V[:no, :no, no:, no:], np.diag(f)[:no], np.diag(f)[no:], nf)
+    assert np.abs(D2 - D).max() <= 1e-14 * np.abs(D).max() and abs(e2 - e) <= 1e-14 * abs(e)

@@ -14,6 +14,7 @@ import pytest
 
 from oracle.cases import synthetic_case
 from pymes_amd import _lib
+from pymes_amd.device import Context
 from pymes_amd.integral.device import DeviceIntegrals
 from pymes_amd.integral.partition import BLOCK_NAMES, part_2_body_int
 from pymes_amd.solver import fno
@@ -267,3 +268,91 @@ def test_two_ranks_one_gpu(gpu_lib):
     assert len(out) == 2 and out[0] == out[1]
     for key in ("block", "factors"):
         assert np.abs(np.array(out[0][key]) - want).max() < 1e-9, key
+
+
+def fno_plan(noa, nv):
+    """fno_plan of kernels.hip (64-wide tiles, 32-wide c chunks, about 1024 blocks): (nt, nchunk, kc_tot, want, nsplit)."""
+    nt, nchunk = -(-nv // 64), -(-nv // 32)
+    ntp, kc_tot = nt * (nt + 1) // 2, noa * noa * nchunk
+    want = max(1, min(-(-1024 // ntp), kc_tot, 65535))
+    kc_per = -(-kc_tot // want)
+    return nt, nchunk, kc_tot, want, -(-kc_tot // kc_per)
+
+
+# (no, n_frozen, nv): every nv of the list, active occupied 1, 3 and >= 12, with and without a frozen core
+TILE_CASES = [(1, 0, 32), (13, 1, 32), (2, 1, 33), (3, 0, 63), (12, 0, 63), (5, 2, 64), (1, 0, 64), (12, 0, 65), (2, 1, 65),
+              (4, 1, 96), (3, 0, 96), (1, 0, 128), (14, 2, 128), (3, 0, 129), (12, 0, 129), (2, 1, 200), (5, 2, 200),
+              (13, 1, 200)]
+
+
+def test_density_across_tiles(gpu_lib):
+    """fno_density_kernel beyond one 64 x 64 tile: the off-diagonal tile pairs (unrank_pair), the (max, min) mirror of the finish
+    kernel, the E_MP2 partials of row tiles > 0 and several 32-wide c chunks, on V_ijab = sum_Q B[Q,i,a] B[Q,j,b] built on the
+    device, against the numpy statement of the definition."""
+    plans = {c: fno_plan(c[0] - c[1], c[2]) for c in TILE_CASES}
+    assert {nv for _, _, nv in TILE_CASES} == {32, 33, 63, 64, 65, 96, 128, 129, 200}
+    assert {no - nf for no, nf, _ in TILE_CASES} >= {1, 3} and max(no - nf for no, nf, _ in TILE_CASES) >= 12
+    assert any(p[2] < -(-1024 // (p[0] * (p[0] + 1) // 2)) for p in plans.values())      # kc_tot < the wanted split count
+    assert max(p[4] for p in plans.values()) >= 100                                        # many splits
+    for case in TILE_CASES:
+        no, nf, nv = case
+        nt = plans[case][0]
+        rng = np.random.default_rng(no * 1000 + nv)
+        B = rng.standard_normal((24, no, nv)) * 0.1
+        eps_o = np.sort(rng.uniform(-2.0, -0.5, no))
+        eps_v = np.sort(rng.uniform(0.3, 3.0, nv))
+        ctx = Context(no, nv, lib=gpu_lib)
+        try:
+            Bd = ctx.array(B)
+            Vd = ctx.contract("Qia,Qjb->ijab", Bd, Bd)
+            ctx.set_orbital_energies(eps_o, eps_v)
+            D, e = fno.density(ctx, nf, Vd)
+            D2, e2 = fno.density(ctx, nf, Vd)
+            Vijab = Vd.get()
+        finally:
+            ctx.close()
+        D_ref, e_ref = ref.mp2_density_ijab(Vijab, eps_o, eps_v, nf)
+        if nt >= 2:
+            # a transposed tile store would show here: the block of the tile pair (1, 0), zero-padded to 64 x 64, is far from
+            # its transpose (at nt = 1 the tile is symmetric and the mirror hides the transposition)
+            h = min(64, nv - 64)
+            M = np.zeros((64, 64))
+            M[:h] = D_ref[64:64 + h, :64]
+            assert np.abs(M - M.T)[:h].max() > 0.1 * np.abs(M).max(), case
+        assert np.abs(D - D_ref).max() <= 1e-12 * np.abs(D_ref).max(), case
+        assert abs(e - e_ref) <= 1e-12 * abs(e_ref), case
+        assert np.array_equal(D, D2) and e == e2, case
+
+
+def test_truncate_factors_multi_tile(gpu_lib):
+    """fno.truncate on the production route (the ('factors', B) source, frozen core) with more than 64 kept virtuals, so that
+    both density calls — full space and kept space — run on several tiles, against a numpy restatement from B alone."""
+    from oracle.io_oracle import synthetic_factors
+    no, nv, nf, k = 10, 150, 1, 80
+    B, eps = synthetic_factors(no, nv, seed=12, scale=0.3)
+    f = np.diag(eps)
+    r = fno.truncate(no, f, ("factors", B), n_frozen=nf, nv_keep=k)
+    try:
+        got = (r.occupations.copy(), r.eps_v.copy(), r.C.copy(), r.de_mp2, r.e_mp2_full, r.nv, r.no)
+    finally:
+        r.close()
+    Bov = B[:, :no, no:]
+    D, e_full = ref.mp2_density_ijab(np.einsum("Qia,Qjb->ijab", Bov, Bov, optimize=True), eps[:no], eps[no:], nf)
+    occ, vec = np.linalg.eigh(D)
+    order = np.argsort(-occ, kind="stable")
+    occ, N = occ[order], ref.sign_rule(vec[:, order])[:, :k]
+    assert occ[k - 1] - occ[k] > 1e-3 * (occ[k - 1] - occ[-1])            # a gap at the cut: the kept space is well defined
+    w, W = np.linalg.eigh(N.T @ f[no:, no:] @ N)
+    Cm = ref.sign_rule(N @ W)
+    Bn = np.einsum("Qia,ax->Qix", B[:, nf:no, no:], Cm, optimize=True)
+    _, e_kept = ref.mp2_density_ijab(np.einsum("Qia,Qjb->ijab", Bn, Bn, optimize=True), eps[nf:no], w, 0)
+    occ_g, eps_g, C_g, de_g, e_full_g, nv_g, no_g = got
+    assert (nv_g, no_g) == (k, no - nf)
+    assert np.abs(occ_g - occ).max() <= 1e-12 * occ[0]
+    # (the kept space turns by |dD| / gap at the cut, about 1e-12 for a rounding-level dD, and the semicanonical rotation by
+    # that times |f| / min spacing of eps')
+    assert np.abs(eps_g - w).max() <= 1e-9 * np.abs(w).max()
+    assert np.abs(C_g - Cm).max() < 1e-6
+    assert abs(e_full_g - e_full) <= 1e-12 * abs(e_full)
+    assert abs(de_g - (e_full - e_kept)) <= 1e-8 * abs(e_full)
+    assert de_g < 0.0

@@ -243,44 +243,66 @@ def test_mixer_against_reference_golden(sim):
     check_mixer_against_reference_golden(sim)
 
 
-def test_mixer_near_singular_and_non_finite_subspace(sim):
-    """the native step (csrc/diis_small.h: cyclic Jacobi + LU in place of numpy's eigh / inv) on a linearly
-    dependent history — the same error vector twice, |lambda_min| < 1e-12, the pseudo-inverse branch of diis.py:85-93 — gives
-    numpy's coefficients; a non-finite overlap (a diverged iteration) is refused like numpy.linalg refuses it, instead of
-    writing NaN amplitudes."""
+def check_mixer_near_singular_and_non_finite_subspace(lib):
+    """the native step (csrc/diis_small.h: cyclic Jacobi + LU in place of numpy's eigh / inv) and the
+    device-resident step (pymes_diis_step) on a linearly dependent history — the same error vector twice, |lambda_min| <
+    1e-12, the pseudo-inverse branch of diis.py:85-93 — give numpy's coefficients; a non-finite overlap (a diverged iteration)
+    is refused like numpy.linalg refuses it, instead of writing NaN amplitudes: the native step raises, the device-resident
+    step keeps the newest amplitudes and raises when its state is read back."""
     from pymes_amd.device import PymesError
     from pymes_amd.mixer.diis import DIIS
     rng = np.random.default_rng(3)
     errs = [rng.standard_normal((3, 2)), rng.standard_normal((3, 3, 2, 2))]
     amps = [[rng.standard_normal((3, 2)), rng.standard_normal((3, 3, 2, 2))] for _ in range(3)]
     coeffs = {}
-    for mode in ("numpy", "native"):
-        ctx = Context(2, 3, lib=sim)
+    for mode in ("numpy", "native", "device"):
+        ctx = Context(2, 3, lib=lib)
         mixer = DIIS(dim_space=6)
         try:
             for it in range(3):          # identical error vectors: L is singular from the second call on
-                quiet(mixer.mix, [ctx.array(e) for e in errs], [ctx.array(a) for a in amps[it]], native=(mode == "native"))
+                quiet(mixer.mix, [ctx.array(e) for e in errs], [ctx.array(a) for a in amps[it]], native=(mode == "native"),
+                      on_device=(mode == "device"))
+            if mode == "device":
+                quiet(mixer.log_last)
             assert mode == "numpy" or mixer.last_dependent          # (the pseudo-inverse branch was taken)
             coeffs[mode] = np.array(mixer.last_coefficients)
         finally:
             ctx.close()
-    assert np.allclose(coeffs["native"], coeffs["numpy"], rtol=1e-9, atol=1e-11), coeffs
-    ctx = Context(2, 3, lib=sim)
+    for mode in ("native", "device"):
+        assert np.allclose(coeffs[mode], coeffs["numpy"], rtol=1e-9, atol=1e-11), (mode, coeffs)
+    bad = [errs[0].copy(), errs[1].copy()]
+    bad[1][0, 0, 0, 0] = np.nan
+    ctx = Context(2, 3, lib=lib)
     mixer = DIIS(dim_space=6)
     try:
         quiet(mixer.mix, [ctx.array(e) for e in errs], [ctx.array(a) for a in amps[0]], native=True)
-        bad = [errs[0].copy(), errs[1].copy()]
-        bad[1][0, 0, 0, 0] = np.nan
         with pytest.raises(PymesError):
             quiet(mixer.mix, [ctx.array(e) for e in bad], [ctx.array(a) for a in amps[1]], native=True)
     finally:
         ctx.close()
+    ctx = Context(2, 3, lib=lib)
+    mixer = DIIS(dim_space=6)
+    try:
+        quiet(mixer.mix, [ctx.array(e) for e in errs], [ctx.array(a) for a in amps[0]], on_device=True)
+        quiet(mixer.log_last)
+        out = quiet(mixer.mix, [ctx.array(e) for e in bad], [ctx.array(a) for a in amps[1]], on_device=True)
+        got = [o.get() for o in out]
+        with pytest.raises(np.linalg.LinAlgError):
+            mixer._refresh_host()
+        for g, a in zip(got, amps[1]):          # the newest amplitudes, unchanged
+            assert np.array_equal(g, a)
+    finally:
+        ctx.close()
 
 
-@pytest.mark.parametrize("solver", ["ccsd", "ccd"])
-def test_device_resident_diis_gives_the_same_solve(sim, monkeypatch, solver):
+def test_mixer_near_singular_and_non_finite_subspace(sim):
+    check_mixer_near_singular_and_non_finite_subspace(sim)
+
+
+def check_device_resident_diis_gives_the_same_solve(lib, monkeypatch, solver):
     """PYMES_DEVICE_DIIS=1: overlaps, subspace solve (pymes_diis_step) and extrapolation without a host round trip — same
     iteration count and energy as the oracle's run of the reference algorithm (quirk included), and as the host solve."""
+    monkeypatch.setattr(_lib, "_default", lib)
     no, nv = 3, 6
     f, V, _, _ = synthetic_case(no, nv, seed=4, scale=0.3)
     ref = oc.ccsd_solve(no, f, V, delta_e=1e-11) if solver == "ccsd" else oc.ccd_solve(no, f, V, delta_e=1e-11)
@@ -290,6 +312,11 @@ def test_device_resident_diis_gives_the_same_solve(sim, monkeypatch, solver):
     e = r["ccsd e"] if solver == "ccsd" else r["ccd e"]
     assert s.iterations == ref["iterations"] and abs(e - ref["e"]) < 1e-11
     assert s.mixer._state is None and s.mixer.L.shape == (7, 7)          # the state came back to the host when the context closed
+
+
+@pytest.mark.parametrize("solver", ["ccsd", "ccd"])
+def test_device_resident_diis_gives_the_same_solve(sim, monkeypatch, solver):
+    check_device_resident_diis_gives_the_same_solve(sim, monkeypatch, solver)
 
 
 def test_mixer_history_follows_caller_owned_contexts(sim):

@@ -16,11 +16,14 @@
 #include <cstdlib>
 #include <vector>
 
+#include "../../include/pymes_amd.h"
 #include "engine.h"
 
 #include <cmath>
 
 namespace pymes {
+static_assert(Engine::kT1Zero == PYMES_T1_ZERO && Engine::kOwnerTiles == PYMES_OWNER_TILES,
+              "the engine's flag bits are the public ones");
 
 namespace {
 // Row pitch of the pair-packed integrals V^+- (the K-contiguous left operand of the ladder GEMMs): a multiple of 16 doubles,
@@ -90,8 +93,8 @@ void Engine::mp2(double shift, double* t2, double e_out[2]) {
 // -----------------------------------------------------------------------------------
 void Engine::doubles_residual(const double* f, const double* t2, double* r2, unsigned flags) {
     refuse_if_sharded("doubles_residual");
-    const bool dcd = flags & 1u, dressed = flags & 2u, skip_ladder = flags & 4u, sym_ladder = flags & 8u,
-               sym_rings = flags & 16u;
+    const bool dcd = flags & PYMES_DCD, dressed = flags & PYMES_USE_DRESSED, skip_ladder = flags & PYMES_SKIP_LADDER,
+               sym_ladder = flags & PYMES_SYM_LADDER, sym_rings = flags & PYMES_SYM_RINGS;
     const bool quad = !dcd;
     const int64_t o = no, v = nv, nn = n;
     if (sym_rings) {      // symmetry-reduced evaluation = the one-rank case of the sharded form
@@ -254,7 +257,8 @@ void Engine::pair_layouts_of(const double* t2) {
 
 void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, double* ETx_p, double* L, int rank,
                            int world, unsigned flags, const double* t1, double* QK, const double* P) {
-    const bool dcd = flags & 1u, dressed = flags & 2u, skip_ladder = (flags & 4u) || (flags & 64u), skip_rings = flags & 128u;
+    const bool dcd = flags & PYMES_DCD, dressed = flags & PYMES_USE_DRESSED,
+               skip_ladder = flags & (PYMES_SKIP_LADDER | PYMES_SLAB_RINGS_ONLY), skip_rings = flags & PYMES_SLAB_LADDERS_ONLY;
     const bool quad = !dcd;
     const int64_t o = no, v = nv, nn = n, ov = o * v;
     if (world < 1 || rank < 0 || rank >= world) throw Error("residual_slab: bad rank/world");
@@ -465,7 +469,7 @@ int64_t Engine::slab_prepare_ws_doubles() const {
 }
 
 void Engine::slab_prepare(const double* t2, double* P, int rank, int world, unsigned flags) {
-    const bool dcd = flags & 1u;
+    const bool dcd = flags & PYMES_DCD;
     const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opp = o * (o + 1) / 2, opm = o * (o - 1) / 2;
     const int64_t ldp = opp + (opp & 1), ldm = std::max<int64_t>(opm + (opm & 1), 2);
     if (world < 1 || rank < 0 || rank >= world) throw Error("slab_prepare: bad rank/world");
@@ -521,7 +525,7 @@ void Engine::slab_prepare(const double* t2, double* P, int rank, int world, unsi
 
 void Engine::residual_finish(const double* f, const double* t2, const double* ETd_p, const double* ETx_p,
                              const double* L, double* r2, unsigned flags, const double* t1, const double* QK) {
-    const bool dcd = flags & 1u, dressed = flags & 2u, skip_ladder = flags & 4u;
+    const bool dcd = flags & PYMES_DCD, dressed = flags & PYMES_USE_DRESSED, skip_ladder = flags & PYMES_SKIP_LADDER;
     const bool quad = !dcd;
     const int64_t o = no, v = nv, nn = n;
     const double w = quad ? 1.0 : 0.5;
@@ -549,8 +553,8 @@ void Engine::residual_finish(const double* f, const double* t2, const double* ET
         ladder_sym_unpack(L, r2, 1.0);                  // particle (:187) + hole (:175-186) ladders, pair-packed
     }
     // X_ac = f_ac - w sum Tt[a,d,k,l] V[l,k,d,c]  (:206-221);  Ex += X_ac T[c,b,i,j]  (:231)
-    const bool reuse = (flags & 32u) && lay_t2_ == t2 && lay_[2];     // Tt_d of the preceding residual_slab on this t2
-    const bool have_sum = (flags & 32u) && xs_vv_tag_.is(t2, 0, 1);   // ... and its S_ac (all columns on this rank)
+    const bool reuse = (flags & PYMES_REUSE_LAYOUTS) && lay_t2_ == t2 && lay_[2];     // Tt_d of the preceding residual_slab on this t2
+    const bool have_sum = (flags & PYMES_REUSE_LAYOUTS) && xs_vv_tag_.is(t2, 0, 1);   // ... and its S_ac (all columns on this rank)
     TView Xvv = make_view(arena.alloc(v * v), {v, v});
     copy(Fvv, Xvv);
     TView Exn;
@@ -662,7 +666,7 @@ static int a_of_pair_row(int64_t r) {
 void Engine::residual_finish_pairs(const double* f, const double* t2, const double* ETd_p, const double* ETx_p,
                                    const double* L, double* Rc, unsigned flags, const double* t1, const double* QK,
                                    int rank, int world, const double* Xvv_in) {
-    const bool dcd = flags & 1u, dressed = flags & 2u;
+    const bool dcd = flags & PYMES_DCD, dressed = flags & PYMES_USE_DRESSED;
     const int64_t o = no, v = nv, nn = n;
     const double w = dcd ? 0.5 : 1.0;
     if (!L) throw Error("residual_finish_pairs: L is required");
@@ -1313,7 +1317,7 @@ void Engine::dress_fock(const double* f, const double* t1, double* fd) {
 // X_ac = f_ac - w sum_{kdl} Tt[a,d,k,l] V[l,k,d,c] (ccd.py:206-221), the sum restricted to this rank's chunk of k (one
 // process per GPU; f_ac enters on rank 0 only): v x v partial results to be all-reduced
 void Engine::xvv_partial(const double* f, const double* t2, double* Xvv_p, int rank, int world, unsigned flags) {
-    const bool dcd = flags & 1u;
+    const bool dcd = flags & PYMES_DCD;
     const int64_t o = no, v = nv, nn = n;
     if (world < 1 || rank < 0 || rank >= world) throw Error("xvv_partial: bad rank/world");
     const int64_t c = (o + world - 1) / world, k0 = std::min<int64_t>(rank * c, o), k1 = std::min<int64_t>(k0 + c, o);
@@ -1572,21 +1576,21 @@ void Engine::ccsd_residuals(const double* f, const double* t1, const double* t2,
         }
         res_fd_ = got[0]; res_ETd_ = got[1]; res_ETx_ = got[2]; res_L_ = got[3]; res_QK_ = got[4];
     }
-    const unsigned dcd = flags & 1u;                  // PYMES_DCD
-    const unsigned sym = 8u | 16u;                    // PYMES_SYM_LADDER | PYMES_SYM_RINGS
-    if (flags & kT1Zero) {
+    const unsigned dcd = flags & PYMES_DCD;
+    const unsigned sym = PYMES_SYM_LADDER | PYMES_SYM_RINGS;
+    if (flags & PYMES_T1_ZERO) {
         residual_slab(f, t2, res_ETd_, res_ETx_, res_L_, 0, 1, dcd | sym);                                     // :171
         singles_residual_partial(f, t1, t2, r1, 0, 1, true);                                                   // :167
-        residual_finish(f, t2, res_ETd_, res_ETx_, res_L_, r2, dcd | sym | 32u);                              // (PYMES_REUSE_LAYOUTS)
+        residual_finish(f, t2, res_ETd_, res_ETx_, res_L_, r2, dcd | sym | PYMES_REUSE_LAYOUTS);
         return;
     }
     dress_fock(f, t1, res_fd_);                                                                                // :163
     // V_abcd is never dressed: its T1 dressing (:165, ccsd.py:414-419) is carried by tau = T2 + T1 T1 inside the ladders,
     // that of V_abij by Q_kb and two small products inside the finish; only V~_klij, V~_iajb, V~_iabj are formed
     dress_V(t1, (1u << pattern_of_name("klij")) | (1u << pattern_of_name("iajb")) | (1u << pattern_of_name("iabj")));
-    residual_slab(res_fd_, t2, res_ETd_, res_ETx_, res_L_, 0, 1, dcd | sym | 2u, t1, res_QK_);                // :171 (PYMES_USE_DRESSED)
+    residual_slab(res_fd_, t2, res_ETd_, res_ETx_, res_L_, 0, 1, dcd | sym | PYMES_USE_DRESSED, t1, res_QK_);  // :171
     singles_residual_partial(res_fd_, t1, t2, r1, 0, 1, true);                                                 // :167
-    residual_finish(res_fd_, t2, res_ETd_, res_ETx_, res_L_, r2, dcd | sym | 2u | 32u, t1, res_QK_);
+    residual_finish(res_fd_, t2, res_ETd_, res_ETx_, res_L_, r2, dcd | sym | PYMES_USE_DRESSED | PYMES_REUSE_LAYOUTS, t1, res_QK_);
 }
 
 void Engine::ccsd_iterate(const double* f, double* t1, double* t2, unsigned flags, double shift, double delta, double* dt1,
@@ -1752,11 +1756,9 @@ void Engine::ccsd_sharded_residuals(const double* f, double* fd, const double* t
     const int rank = coll_.rank, world = coll_.world;
     check_shard_rank("ccsd_sharded_residuals", rank, world);
     const int64_t o = no, v = nv, ov = o * v, o2 = o * o;
-    // flag bits of include/pymes_amd.h: PYMES_DCD 1, PYMES_USE_DRESSED 2, PYMES_SYM_LADDER 8, PYMES_SYM_RINGS 16,
-    // PYMES_SLAB_RINGS_ONLY 64, PYMES_SLAB_LADDERS_ONLY 128
-    const unsigned dcd = flags & 1u, kSlabRingsOnly = 64u, kSlabLaddersOnly = 128u;
-    const unsigned slab = dcd | 2u | 8u | 16u;
-    const bool owner = (flags & kOwnerTiles) != 0;
+    const unsigned dcd = flags & PYMES_DCD;
+    const unsigned slab = dcd | PYMES_USE_DRESSED | PYMES_SYM_LADDER | PYMES_SYM_RINGS;
+    const bool owner = (flags & PYMES_OWNER_TILES) != 0;
     h.mark("begin");
     // K-sharded partial sums, all-reduced: the T1.V intermediates of the dressed Fock matrix (ccsd.py:163, this rank's chunk of
     // j).  What needs T1 only comes first: the all-gather of the new T2 that the previous pass left in flight is awaited — and
@@ -1787,7 +1789,7 @@ void Engine::ccsd_sharded_residuals(const double* f, double* fd, const double* t
     h.mark("await T2, slab prepare, fock finish");
     // :171 in two halves: the ring products first, so that the all-gathers of their rows fly while the ladders — whose rows
     // of L never leave the rank — and the singles residual are computed
-    residual_slab(fd, t2, b.ETd, b.ETx, b.L, rank, world, slab | kSlabRingsOnly, t1, b.QK, b.P);
+    residual_slab(fd, t2, b.ETd, b.ETx, b.L, rank, world, slab | PYMES_SLAB_RINGS_ONLY, t1, b.QK, b.P);
     h.mark("ring products");
     // rows of the ring products: two all-gathers of the whole matrices, or ONE all-to-all of the tiles each pair owner reads
     int64_t tD = 0, tE = 0, tO = 0;
@@ -1797,7 +1799,7 @@ void Engine::ccsd_sharded_residuals(const double* f, double* fd, const double* t
         tE = h.allgather(b.ETx, chunk_of(ov, world) * ov);
     }
     h.wait(tJ);
-    residual_slab(fd, t2, b.ETd, b.ETx, b.L, rank, world, slab | kSlabLaddersOnly, t1, b.QK, b.P);
+    residual_slab(fd, t2, b.ETd, b.ETx, b.L, rank, world, slab | PYMES_SLAB_LADDERS_ONLY, t1, b.QK, b.P);
     h.mark("ladders, Q_kb");
     const int64_t tQ = h.allgather(b.QK, chunk_of(ov, world) * o2);
     xvv_partial(fd, t2, b.Xvv, rank, world, dcd);                     // X_ac (ccd.py:206-221) over this rank's chunk of k
@@ -1827,12 +1829,11 @@ void Engine::ccd_sharded_residuals(const double* f, double* t2, const ShardBuffe
     const int rank = coll_.rank, world = coll_.world;
     check_shard_rank("ccd_sharded_residuals", rank, world);
     const int64_t o = no, v = nv, ov = o * v, o2 = o * o;
-    const unsigned dcd = flags & 1u, kSlabRingsOnly = 64u, kSlabLaddersOnly = 128u;
-    const unsigned slab = dcd | 8u | 16u;                      // undressed blocks: CCD / DCD have no T1 (ccd.py:100-121)
-    const bool owner = (flags & kOwnerTiles) != 0;
+    const unsigned slab = (flags & PYMES_DCD) | PYMES_SYM_LADDER | PYMES_SYM_RINGS;   // undressed blocks: CCD / DCD have no T1 (ccd.py:100-121)
+    const bool owner = (flags & PYMES_OWNER_TILES) != 0;
     h.mark("begin");
     ccsd_sharded_await(t2, b);                                 // the new T2 the previous pass left in flight
-    residual_slab(f, t2, b.ETd, b.ETx, b.L, rank, world, slab | kSlabRingsOnly);
+    residual_slab(f, t2, b.ETd, b.ETx, b.L, rank, world, slab | PYMES_SLAB_RINGS_ONLY);
     h.mark("ring products");
     int64_t tD = 0, tE = 0, tO = 0;
     if (owner) tO = owner_tiles_start(b);
@@ -1840,7 +1841,7 @@ void Engine::ccd_sharded_residuals(const double* f, double* t2, const ShardBuffe
         tD = h.allgather(b.ETd, chunk_of(ov, world) * ov);
         tE = h.allgather(b.ETx, chunk_of(ov, world) * ov);
     }
-    residual_slab(f, t2, b.ETd, b.ETx, b.L, rank, world, slab | kSlabLaddersOnly);      // the rows of L stay on the rank
+    residual_slab(f, t2, b.ETd, b.ETx, b.L, rank, world, slab | PYMES_SLAB_LADDERS_ONLY);      // the rows of L stay on the rank
     if (owner) {
         h.wait(tO);
         owner_tiles_finish(b);

@@ -3107,6 +3107,11 @@ enum : unsigned short {
     PK_DOTS1, PK_DOTS2, PK_ENERGY, PK_TAU, PK_PACK_T, PK_LADDER_UNPACK, PK_RING_OPERANDS, PK_T2_LAYOUTS, PK_ASSEMBLE,
     PK_ROWS_UNPACK, PK_FOCK_G12, PK_FOCK_G12_FIN, PK_FOCK_FT, PK_FOCK_FIN, PK_TRACES, PK_DOTS_FINAL, PK_KINDS
 };
+// (PYMES_PHASE_LOG; a new kind also wants a look at phase_kind_heavy below)
+constexpr const char* kPhaseKindNames[] = {"gemm", "splitk", "perm", "permT", "gemvC", "gemvF", "gemvR", "update", "lincomb", "dots1", "dots2",
+                                           "energy", "tau", "packT", "unpackL", "ringops", "layouts", "assemble", "unpackR", "fockG", "fockGf",
+                                           "fockFt", "fockFin", "traces", "dotsF"};
+static_assert(sizeof(kPhaseKindNames) / sizeof(kPhaseKindNames[0]) == PK_KINDS, "one name per phase kind");
 struct SplitkTaskK { GemmK g; int BM, BN; };
 struct PermTaskK { PermK p; long total; int tiles_q, tiles_l; };
 struct GemvTaskK { GemvItem it; double* ws; const double* yin; double beta; };
@@ -3270,6 +3275,22 @@ constexpr int kGramTiles = 64;
 double* g_gram_ws[kMaxDevices] = {nullptr};
 double* g_gram_host[kMaxDevices] = {nullptr};
 std::atomic<long> g_live_allocs{0};
+
+int current_device() {
+    int d = 0;
+    HIP_CHECK(hipGetDevice(&d));
+    if (d < 0 || d >= kMaxDevices) throw std::runtime_error("device ordinal out of range");
+    return d;
+}
+// a kernel's dynamic LDS limit, raised once per (kernel, device)
+template <auto Kernel>
+void allow_dynamic_lds(size_t bytes) {
+    static bool done[kMaxDevices] = {false};
+    const int dv = current_device();
+    if (done[dv]) return;
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done[dv] = true;
+}
 
 // ---- phase queue (host side of phase_kernel) ----------------------------------------------------------------------------
 // [lo, hi) in bytes; pitch != 0: only the rows [lo + i pitch, lo + i pitch + width) of it (a pitched 2-D box: two column
@@ -3555,25 +3576,16 @@ void phase_flush() {
         nlev = std::max(nlev, lev + 1);
     }
     if (P.log) {                      // PYMES_PHASE_LOG: one line per level, kind:blocks:cost of its tasks
-        static const char* names[] = {"gemm", "splitk", "perm", "permT", "gemvC", "gemvF", "gemvR", "update", "lincomb", "dots1", "dots2",
-                                      "energy", "tau", "packT", "unpackL", "ringops", "layouts", "assemble", "unpackR", "fockG", "fockGf",
-                                      "fockFt", "fockFin", "traces", "dotsF"};
         fprintf(stderr, "[phase] flush %ld: %d tasks, %d levels\n", P.flushes, n, nlev);
         for (int lev = 0; lev < nlev; ++lev) {
             fprintf(stderr, "[phase]   L%-2d", lev);
             for (int i = 0; i < n; ++i)
-                if (q[i].level == lev) fprintf(stderr, " %s:%d:%.1f", q[i].kind < PK_KINDS ? names[q[i].kind] : "?", q[i].nblk, q[i].cost);
+                if (q[i].level == lev) fprintf(stderr, " %s:%d:%.1f", q[i].kind < PK_KINDS ? kPhaseKindNames[q[i].kind] : "?", q[i].nblk, q[i].cost);
             fprintf(stderr, "\n");
         }
     }
-    static bool attr_set[kMaxDevices] = {false};
-    int dv = 0;
-    HIP_CHECK(hipGetDevice(&dv));
-    if (dv >= 0 && dv < kMaxDevices && !attr_set[dv]) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(phase_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(phase_light_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        attr_set[dv] = true;
-    }
+    allow_dynamic_lds<phase_kernel>(64 * 1024);
+    allow_dynamic_lds<phase_light_kernel>(64 * 1024);
     std::vector<int> idx;
     for (int lev = 0; lev < nlev; ++lev) {
         idx.clear();
@@ -3613,20 +3625,35 @@ void phase_flush() {
     }
 }
 // Every launch or stream operation below that is NOT recorded as a task goes through these: the open phase is launched
-// first, so that the order of effects on the stream is that of immediate execution.
-#define PYMES_LAUNCH(...) do { phase_flush(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-#define hipMemcpyAsync(...) (phase_flush(), hipMemcpyAsync(__VA_ARGS__))
-#define hipMemsetAsync(...) (phase_flush(), hipMemsetAsync(__VA_ARGS__))
-#define hipMemcpy(...) (phase_flush(), hipMemcpy(__VA_ARGS__))
-#define hipStreamSynchronize(...) (phase_flush(), hipStreamSynchronize(__VA_ARGS__))
-#define hipEventRecord(...) (phase_flush(), hipEventRecord(__VA_ARGS__))
-#define hipStreamWaitEvent(...) (phase_flush(), hipStreamWaitEvent(__VA_ARGS__))
-#define hipGraphLaunch(...) (phase_flush(), hipGraphLaunch(__VA_ARGS__))
-#define hipStreamBeginCapture(...) (phase_flush(), hipStreamBeginCapture(__VA_ARGS__))
-#define hipStreamEndCapture(...) (phase_flush(), hipStreamEndCapture(__VA_ARGS__))
-#define hipFree(...) (phase_flush(), hipFree(__VA_ARGS__))
+// first, so that the order of effects on the stream is that of immediate execution.  Below this block the raw runtime names
+// are poisoned, and tests/test_capi_symbols.py refuses a raw kernel launch anywhere but here and in phase_flush.
+template <typename... P, typename... A>
+hipError_t try_launch_kernel(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+    phase_flush();
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    return hipGetLastError();
+}
+template <typename... P, typename... A>
+void launch_kernel(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+    HIP_CHECK(try_launch_kernel(kernel, grid, block, lds, st, args...));
+}
+inline hipError_t copy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st) {
+    phase_flush();
+    return hipMemcpyAsync(dst, src, bytes, kind, st);
+}
+inline hipError_t set_async(void* dst, int value, size_t bytes, hipStream_t st) { phase_flush(); return hipMemsetAsync(dst, value, bytes, st); }
+inline hipError_t copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) { phase_flush(); return hipMemcpy(dst, src, bytes, kind); }
+inline hipError_t sync_stream(hipStream_t st) { phase_flush(); return hipStreamSynchronize(st); }
+inline hipError_t record_event(hipEvent_t ev, hipStream_t st) { phase_flush(); return hipEventRecord(ev, st); }
+inline hipError_t wait_event(hipStream_t st, hipEvent_t ev, unsigned flags) { phase_flush(); return hipStreamWaitEvent(st, ev, flags); }
+inline hipError_t launch_graph(hipGraphExec_t g, hipStream_t st) { phase_flush(); return hipGraphLaunch(g, st); }
+inline hipError_t begin_capture(hipStream_t st, hipStreamCaptureMode mode) { phase_flush(); return hipStreamBeginCapture(st, mode); }
+inline hipError_t end_capture(hipStream_t st, hipGraph_t* g) { phase_flush(); return hipStreamEndCapture(st, g); }
+inline hipError_t free_device(void* p) { phase_flush(); return hipFree(p); }
+#pragma GCC poison hipMemcpyAsync hipMemsetAsync hipMemcpy hipStreamSynchronize hipEventRecord hipStreamWaitEvent
+#pragma GCC poison hipGraphLaunch hipStreamBeginCapture hipStreamEndCapture hipFree
 
-void wait_idle(hipStream_t st) { HIP_CHECK(hipStreamSynchronize(st)); }
+void wait_idle(hipStream_t st) { HIP_CHECK(sync_stream(st)); }
 
 // Small read-backs that do not drain the stream: a copy into a pinned slot + an event; the host later waits for THAT event
 // while the stream goes on with whatever was enqueued behind it (the next iteration's residual kernels).
@@ -3651,7 +3678,7 @@ bool poll_flag(const long* flag, long seq, hipStream_t st) {
     long spins = 0;
     while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
         if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-            if (st) HIP_CHECK(hipStreamSynchronize(st));
+            if (st) HIP_CHECK(sync_stream(st));
             else HIP_CHECK(hipDeviceSynchronize());
             return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq;
         }
@@ -3679,8 +3706,8 @@ int readback_start_impl(const double* dev_ptr, int n, hipStream_t st) {
     g_read_next[dv] = (slot + 1) % kReadSlots;
     const unsigned gen = (g_read_gen[dv][slot] = (g_read_gen[dv][slot] + 1) & 0x3fffffu);
     g_read_flagged[dv][slot] = false;
-    HIP_CHECK(hipMemcpyAsync(g_read_host[dv] + slot * kReadDoubles, dev_ptr, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipEventRecord(g_read_ev[dv][slot], st));
+    HIP_CHECK(copy_async(g_read_host[dv] + slot * kReadDoubles, dev_ptr, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(record_event(g_read_ev[dv][slot], st));
     return (int)((gen << 8) | (unsigned)slot);
 }
 // A slot that the DEVICE fills (dots_final_kernel): returns the ticket and the arguments of that kernel's result part
@@ -3727,12 +3754,6 @@ void readback_wait_impl(int ticket, double* out, int n) {
     for (int i = 0; i < n; ++i) out[i] = g_read_host[dv][slot * kReadDoubles + i];
 }
 
-int current_device() {
-    int d = 0;
-    HIP_CHECK(hipGetDevice(&d));
-    if (d < 0 || d >= kMaxDevices) throw std::runtime_error("device ordinal out of range");
-    return d;
-}
 long g_dot_seq[kMaxDevices] = {0};
 // arrival counters of dots_final_kernel: a ring of 64 per device, each on a line of its own; a launch takes the next one (the
 // last arriving block leaves it at zero; 64 later launches of the process on that device are far behind any launch in flight)
@@ -3755,16 +3776,8 @@ void launch_gemm(const GemmK& k, long nblocks, hipStream_t st) {
     constexpr int A_T = (AKC ? (BK + 2) * BM : (BM + 16) * BK);
     constexpr int B_T = (BKC ? (BK + 2) * BN : (BN + 16) * BK);
     constexpr size_t lds = (size_t)(STREAM ? 1 : 2) * (A_T + B_T) * sizeof(double);
-    static bool attr_set[kMaxDevices] = {false};
-    auto fn = dgemm_kernel<BM, BN, AKC, BKC, VEC, STREAM>;
-    const int dv = current_device();
-    if (!attr_set[dv]) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dv] = true;
-    }
-    PYMES_LAUNCH(fn, dim3((unsigned)nblocks), dim3(kThreads), lds, st, k);
-    HIP_CHECK(hipGetLastError());
+    allow_dynamic_lds<dgemm_kernel<BM, BN, AKC, BKC, VEC, STREAM>>(lds);
+    launch_kernel(dgemm_kernel<BM, BN, AKC, BKC, VEC, STREAM>, dim3((unsigned)nblocks), dim3(kThreads), lds, st, k);
 }
 
 template <bool AKC, bool BKC>
@@ -3772,16 +3785,8 @@ void launch_gemm_glds(const GemmK& k, long nblocks, hipStream_t st) {
     constexpr int A_T = AKC ? 128 * BK : BK * (128 + 16);
     constexpr int B_T = BKC ? 128 * BK : BK * (128 + 16);
     constexpr size_t lds = (size_t)2 * (A_T + B_T) * sizeof(double);
-    static bool attr_set[kMaxDevices] = {false};
-    auto fn = dgemm_glds_kernel<AKC, BKC>;
-    const int dv = current_device();
-    if (!attr_set[dv]) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds));
-        attr_set[dv] = true;
-    }
-    PYMES_LAUNCH(fn, dim3((unsigned)nblocks), dim3(kThreads), lds, st, k);
-    HIP_CHECK(hipGetLastError());
+    allow_dynamic_lds<dgemm_glds_kernel<AKC, BKC>>(lds);
+    launch_kernel(dgemm_glds_kernel<AKC, BKC>, dim3((unsigned)nblocks), dim3(kThreads), lds, st, k);
 }
 
 // smallest K range per block that still goes to the LDS-DMA kernel (measured at (20,80), DESIGN 5: below it the
@@ -3895,10 +3900,8 @@ void gemv_batch_flush() {
         blocks += it.cblocks * it.nchunk;
         outs += (int)((it.C + 255) / 256);
     }
-    PYMES_LAUNCH(gemv_multi_cols_kernel, dim3((unsigned)blocks), dim3(256), 0, b.st, b.tab, b.ws);
-    HIP_CHECK(hipGetLastError());
-    PYMES_LAUNCH(gemv_multi_finish_kernel, dim3((unsigned)outs), dim3(256), 0, b.st, b.tab, b.ws);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(gemv_multi_cols_kernel, dim3((unsigned)blocks), dim3(256), 0, b.st, b.tab, b.ws);
+    launch_kernel(gemv_multi_finish_kernel, dim3((unsigned)outs), dim3(256), 0, b.st, b.tab, b.ws);
     b.tab.n = 0;
     b.ws_used = 0;
 }
@@ -3927,180 +3930,142 @@ struct GemmGroup {
 thread_local GemmGroup g_group;
 bool gemm_group_pending() { return g_group.n > 0 || g_group.nd > 0; }
 
-void gemm_group_flush_dma() {
+// The event pair around the launches of one product or group while dev::prof_enable is on (nothing otherwise): what
+// dev::prof_query adds up and PYMES_GEMM_LOG prints.
+struct ProfSpan {
+    std::pair<hipEvent_t, hipEvent_t> ev;
+    hipStream_t st;
+    explicit ProfSpan(hipStream_t s) : st(s) {
+        if (!g_prof.on) return;
+        if (!g_prof.pool.empty()) { ev = g_prof.pool.back(); g_prof.pool.pop_back(); }
+        else { HIP_CHECK(hipEventCreate(&ev.first)); HIP_CHECK(hipEventCreate(&ev.second)); }
+        HIP_CHECK(record_event(ev.first, st));
+    }
+    void finish(double flops, int klass, int n_kernels, const char* text) {
+        HIP_CHECK(record_event(ev.second, st));
+        g_prof.ev.push_back(ev);
+        g_prof.flops += flops;
+        g_prof.fl.push_back(flops);
+        g_prof.klass.push_back(klass);
+        g_prof.nk.push_back(n_kernels);
+        g_prof.what.push_back(text);
+    }
+};
+
+// How many ways every product of the LDS-DMA half is cut along K (each cut at least dma_min_k deep): the rule of plan_dma for
+// the tiles of the whole group — a CU turns out one tile per tile-time however many blocks it holds, so s cuts cost about
+// ceil(total s / 256) / s tile-times, + 3 us per cut and the reduction of the partial tiles (profiles/r05/
+// probe_gemm_plan_grid.txt).  A single cut is never chosen when a deeper one is possible: an uncut block applies beta
+// in its own epilogue, element by element.
+long group_cuts_dma(const GemmGroup& q, long total) {
+    long want = 1, ktmax = 0;
+    for (int i = 0; i < q.nd; ++i) ktmax = std::max(ktmax, q.ktiles_d[i]);
+    const double tau = 1.75 * (double)ktmax;
+    double best = 1e300;
+    long smax = 1;                 // (beyond the deepest product's limit a larger s changes nothing but the divisor below)
+    for (int i = 0; i < q.nd; ++i) smax = std::max(smax, q.ktiles_d[i] / (dma_min_k() / BK));
+    for (long sp = 2; sp <= std::min<long>(16, smax); ++sp) {
+        long blocks = 0;
+        bool any_cut = false;
+        for (int i = 0; i < q.nd; ++i) {
+            const long si = std::min(sp, std::max<long>(1, q.ktiles_d[i] / (dma_min_k() / BK)));
+            any_cut = any_cut || si > 1;
+            blocks += q.tiles_d[i] * si;
+        }
+        if (!any_cut) break;
+        if (blocks * 16384 > q.ws_doubles) break;
+        const double cost = (double)((blocks + 255) / 256) / (double)sp + (double)sp * 3.0 / tau +
+                            (5.0 + 0.0437 * (double)(blocks + total)) / tau;
+        if (cost < best - 1e-9) { best = cost; want = sp; }
+    }
+    return want;
+}
+// ... and of the 64 x 64 half: its tiles fill the chip from ~1024 blocks (four co-resident per CU); with fewer tiles in the
+// whole group every product that is deep enough is cut along K by a common factor (>= 8 k-tiles per cut, workspace permitting)
+long group_cuts_64(long total) { return total < 768 ? (1024 + total - 1) / total : 1; }
+
+// One half of the open group as one grid (+ one reduction of its k-split products): the mid-size products on 128 x 128 tiles
+// of the LDS-DMA kernel (dma) or the small ones on 64 x 64 tiles.
+void gemm_group_launch(bool dma) {
     GemmGroup& q = g_group;
-    if (q.nd == 0) return;
+    int& n = dma ? q.nd : q.n;
+    if (n == 0) return;
+    GemmK* ks = dma ? q.kd : q.k;
+    const long* tiles = dma ? q.tiles_d : q.tiles;
+    const long* ktiles = dma ? q.ktiles_d : q.ktiles;
+    const double* fl = dma ? q.flops_d : q.flops;
+    const int tile = dma ? 128 : 64;
+    const long tile_doubles = (long)tile * tile, red_per_tile = tile_doubles / 256;       // partial tile; its reduction blocks
+    const long max_cuts = dma ? 16 : 64, min_ktiles = dma ? dma_min_k() / BK : 8;
     hipStream_t st = q.st;
     long total = 0;
-    for (int i = 0; i < q.nd; ++i) total += q.tiles_d[i];
-    // How many ways every product is cut along K (each cut at least dma_min_k deep): the rule of plan_dma for the tiles of the
-    // whole group — a CU turns out one tile per tile-time however many blocks it holds, so s cuts cost about
-    // ceil(total s / 256) / s tile-times, + 3 us per cut and the reduction of the partial tiles (profiles/r05/
-    // probe_gemm_plan_grid.txt).  A single cut is never chosen when a deeper one is possible: an uncut block applies beta
-    // in its own epilogue, element by element.
-    long want = 1;
-    {
-        long ktmax = 0;
-        for (int i = 0; i < q.nd; ++i) ktmax = std::max(ktmax, q.ktiles_d[i]);
-        const double tau = 1.75 * (double)ktmax;
-        double best = 1e300;
-        long smax = 1;                 // (beyond the deepest product's limit a larger s changes nothing but the divisor below)
-        for (int i = 0; i < q.nd; ++i) smax = std::max(smax, q.ktiles_d[i] / (dma_min_k() / BK));
-        for (long sp = 2; sp <= std::min<long>(16, smax); ++sp) {
-            long blocks = 0;
-            bool any_cut = false;
-            for (int i = 0; i < q.nd; ++i) {
-                const long si = std::min(sp, std::max<long>(1, q.ktiles_d[i] / (dma_min_k() / BK)));
-                any_cut = any_cut || si > 1;
-                blocks += q.tiles_d[i] * si;
-            }
-            if (!any_cut) break;
-            if (blocks * 16384 > q.ws_doubles) break;
-            const double cost = (double)((blocks + 255) / 256) / (double)sp + (double)sp * 3.0 / tau +
-                                (5.0 + 0.0437 * (double)(blocks + total)) / tau;
-            if (cost < best - 1e-9) { best = cost; want = sp; }
-        }
-    }
+    for (int i = 0; i < n; ++i) total += tiles[i];
+    const long want = dma ? group_cuts_dma(q, total) : group_cuts_64(total);
     GroupK grp, red;
-    grp.n = q.nd; grp.tile = 128; red.n = 0; red.tile = 128;
+    grp.n = n; grp.tile = tile; red.n = 0; red.tile = tile;
     long blocks = 0, ws_used = 0, red_blocks = 0;
     double flops = 0.0;
-    for (int i = 0; i < q.nd; ++i) {
-        GemmK& k = q.kd[i];
-        long sp = std::max<long>(1, std::min<long>(std::min<long>(want, 16), q.ktiles_d[i] / (dma_min_k() / BK)));
-        while (sp > 1 && ws_used + q.tiles_d[i] * sp * 16384 > q.ws_doubles) --sp;
-        const long kt_per = (q.ktiles_d[i] + sp - 1) / sp;
+    for (int i = 0; i < n; ++i) {
+        GemmK& k = ks[i];
+        long sp = std::max<long>(1, std::min<long>(std::min<long>(want, max_cuts), ktiles[i] / min_ktiles));
+        while (sp > 1 && ws_used + tiles[i] * sp * tile_doubles > q.ws_doubles) --sp;
+        const long kt_per = (ktiles[i] + sp - 1) / sp;
         k.kchunk = (int)std::max<long>(kt_per * BK, BK);
-        k.nsplit = (int)std::max<long>(1, (q.ktiles_d[i] + kt_per - 1) / std::max<long>(kt_per, 1));
+        k.nsplit = (int)std::max<long>(1, (ktiles[i] + kt_per - 1) / std::max<long>(kt_per, 1));
         k.tile_begin = 0;
         k.ws = nullptr;
         if (k.nsplit > 1) {
             k.ws = q.ws + ws_used;
-            ws_used += q.tiles_d[i] * k.nsplit * 16384;
+            ws_used += tiles[i] * k.nsplit * tile_doubles;
             red.g[red.n] = k;
             red.variant[red.n] = 0;
-            red_blocks += q.tiles_d[i] * 64;
+            red_blocks += tiles[i] * red_per_tile;
             red.blk_end[red.n] = (int)red_blocks;
             ++red.n;
         }
-        blocks += q.tiles_d[i] * k.nsplit;
+        blocks += tiles[i] * k.nsplit;
         grp.blk_end[i] = (int)blocks;
-        grp.variant[i] = 5;
+        grp.variant[i] = dma ? 5 : q.variant[i];
         grp.g[i] = k;
-        flops += q.flops_d[i];
+        flops += fl[i];
     }
-    for (int i = q.nd; i < kGroupMax; ++i) { grp.blk_end[i] = (int)blocks; grp.variant[i] = 0; }
+    for (int i = n; i < kGroupMax; ++i) { grp.blk_end[i] = (int)blocks; grp.variant[i] = 0; }
     for (int i = red.n; i < kGroupMax; ++i) { red.blk_end[i] = (int)red_blocks; red.variant[i] = 0; }
-    const int nq = q.nd;
-    q.nd = 0;
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    if (g_prof.on) {
-        if (!g_prof.pool.empty()) { ev = g_prof.pool.back(); g_prof.pool.pop_back(); }
-        else { HIP_CHECK(hipEventCreate(&ev.first)); HIP_CHECK(hipEventCreate(&ev.second)); }
-        HIP_CHECK(hipEventRecord(ev.first, st));
+    const int nq = n;
+    n = 0;                                     // (an exception below must not leave the queue half-consumed)
+    ProfSpan span(st);
+    if (dma) {
+        constexpr size_t lds = (size_t)2 * (128 * BK + BK * (128 + 16)) * sizeof(double);
+        allow_dynamic_lds<dgemm_glds_group_kernel>(lds);
+        launch_kernel(dgemm_glds_group_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, st, grp);
+    } else {
+        constexpr size_t lds = (size_t)2 * 2 * ((64 + 16) * BK) * sizeof(double);       // the widest variant, double buffered
+        allow_dynamic_lds<dgemm_group_kernel>(lds);
+        launch_kernel(dgemm_group_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, st, grp);
     }
-    constexpr size_t lds = (size_t)2 * (128 * BK + BK * (128 + 16)) * sizeof(double);
-    static bool attr_set[kMaxDevices] = {false};
-    const int dv = current_device();
-    if (!attr_set[dv]) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dgemm_glds_group_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dv] = true;
-    }
-    PYMES_LAUNCH(dgemm_glds_group_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, st, grp);
-    HIP_CHECK(hipGetLastError());
-    if (red.n > 0) {
-        PYMES_LAUNCH(splitk_reduce_group_kernel, dim3((unsigned)red_blocks), dim3(256), 0, st, red);
-        HIP_CHECK(hipGetLastError());
-    }
+    if (red.n > 0) launch_kernel(splitk_reduce_group_kernel, dim3((unsigned)red_blocks), dim3(256), 0, st, red);
     ++q.launches;
     if (g_prof.on) {
-        HIP_CHECK(hipEventRecord(ev.second, st));
-        g_prof.ev.push_back(ev);
-        g_prof.flops += flops;
-        g_prof.fl.push_back(flops);
-        g_prof.klass.push_back(1);
-        g_prof.nk.push_back(1);
         char buf[128];
-        snprintf(buf, sizeof buf, "LDS-DMA group of %d products, %ld blocks, %d k-split, flops=%.4e", nq, blocks, red.n, flops);
-        g_prof.what.push_back(buf);
+        snprintf(buf, sizeof buf, "%sgroup of %d products, %ld blocks, %d k-split, flops=%.4e", dma ? "LDS-DMA " : "", nq, blocks, red.n, flops);
+        span.finish(flops, dma ? 1 : 0, 1, buf);
     }
 }
-
+void gemm_group_flush_dma() { gemm_group_launch(true); }
 void gemm_group_flush() {
-    GemmGroup& q = g_group;
-    gemm_group_flush_dma();
-    if (q.n == 0) return;
-    hipStream_t st = q.st;
-    // k-splitting: 64 x 64 tiles fill the chip from ~1024 blocks (four co-resident per CU); with fewer tiles in the whole
-    // group every product that is deep enough is cut along K by a common factor (>= 8 k-tiles per cut, workspace permitting)
-    long total = 0;
-    for (int i = 0; i < q.n; ++i) total += q.tiles[i];
-    long want = total < 768 ? (1024 + total - 1) / total : 1;
-    GroupK grp, red;
-    grp.n = q.n; grp.tile = 64; red.n = 0; red.tile = 64;
-    long blocks = 0, ws_used = 0, red_blocks = 0;
-    double flops = 0.0;
-    for (int i = 0; i < q.n; ++i) {
-        GemmK& k = q.k[i];
-        long sp = std::max<long>(1, std::min<long>(std::min<long>(want, 64), q.ktiles[i] / 8));
-        while (sp > 1 && ws_used + q.tiles[i] * sp * 4096 > q.ws_doubles) --sp;
-        const long kt_per = (q.ktiles[i] + sp - 1) / sp;
-        k.kchunk = (int)std::max<long>(kt_per * BK, BK);
-        k.nsplit = (int)std::max<long>(1, (q.ktiles[i] + kt_per - 1) / std::max<long>(kt_per, 1));
-        k.tile_begin = 0;
-        k.ws = nullptr;
-        if (k.nsplit > 1) {
-            k.ws = q.ws + ws_used;
-            ws_used += q.tiles[i] * k.nsplit * 4096;
-            red.g[red.n] = k;
-            red.variant[red.n] = 0;
-            red_blocks += q.tiles[i] * 16;
-            red.blk_end[red.n] = (int)red_blocks;
-            ++red.n;
-        }
-        blocks += q.tiles[i] * k.nsplit;
-        grp.blk_end[i] = (int)blocks;
-        grp.variant[i] = q.variant[i];
-        grp.g[i] = k;
-        flops += q.flops[i];
-    }
-    for (int i = q.n; i < kGroupMax; ++i) { grp.blk_end[i] = (int)blocks; grp.variant[i] = 0; }
-    for (int i = red.n; i < kGroupMax; ++i) { red.blk_end[i] = (int)red_blocks; red.variant[i] = 0; }
-    const int nq = q.n;
-    q.n = 0;                                   // (an exception below must not leave the queue half-consumed)
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    if (g_prof.on) {
-        if (!g_prof.pool.empty()) { ev = g_prof.pool.back(); g_prof.pool.pop_back(); }
-        else { HIP_CHECK(hipEventCreate(&ev.first)); HIP_CHECK(hipEventCreate(&ev.second)); }
-        HIP_CHECK(hipEventRecord(ev.first, st));
-    }
-    constexpr size_t lds = (size_t)2 * 2 * ((64 + 16) * BK) * sizeof(double);       // the widest variant, double buffered
-    static bool attr_set[kMaxDevices] = {false};
-    const int dv = current_device();
-    if (!attr_set[dv]) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dgemm_group_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dv] = true;
-    }
-    PYMES_LAUNCH(dgemm_group_kernel, dim3((unsigned)blocks), dim3(kThreads), lds, st, grp);
-    HIP_CHECK(hipGetLastError());
-    if (red.n > 0) {
-        PYMES_LAUNCH(splitk_reduce_group_kernel, dim3((unsigned)red_blocks), dim3(256), 0, st, red);
-        HIP_CHECK(hipGetLastError());
-    }
-    ++q.launches;
-    if (g_prof.on) {
-        HIP_CHECK(hipEventRecord(ev.second, st));
-        g_prof.ev.push_back(ev);
-        g_prof.flops += flops;
-        g_prof.fl.push_back(flops);
-        g_prof.klass.push_back(0);
-        g_prof.nk.push_back(1);
-        char buf[128];
-        snprintf(buf, sizeof buf, "group of %d products, %ld blocks, %d k-split, flops=%.4e", nq, blocks, red.n, flops);
-        g_prof.what.push_back(buf);
-    }
+    gemm_group_launch(true);
+    gemm_group_launch(false);
+}
+// Everything the three queues hold, in the order of immediate execution.  The rule: whatever is launched goes behind the
+// recorded tasks (every launch_kernel starts with phase_flush), so the tasks are first; a product waits in the group only
+// while no task is recorded behind it (phase_push launches a waiting group before it records), so the group follows them;
+// the matrix-vector batch is only ever filled inside Engine::dress_fock's scope, between dev::gemm calls that launch it
+// before they queue or launch a product of another kind, so it is empty wherever it could meet a waiting group.
+// What is not recorded and may read or overwrite queued results (a copy, a synchronisation, a graph boundary) calls this.
+void flush_deferred() {
+    gemv_batch_flush();
+    gemm_group_flush();
+    phase_flush();
 }
 }  // namespace
 
@@ -4112,7 +4077,7 @@ void set_device(int ordinal) {
     int cur = -1;
     HIP_CHECK(hipGetDevice(&cur));
     if (cur != ordinal) {      // launches queued for the device that is being left (an open group / batch of this thread) go first
-        gemv_batch_flush();
+        gemv_batch_flush();    // (not flush_deferred: recorded tasks stay recorded across the switch, as they always have)
         gemm_group_flush();
     }
     HIP_CHECK(hipSetDevice(ordinal));
@@ -4134,7 +4099,7 @@ void* try_dmalloc(size_t bytes) {
 }
 void dfree(void* p) {
     if (!p) return;
-    HIP_CHECK(hipFree(p));
+    HIP_CHECK(free_device(p));
     --g_live_allocs;
 }
 int64_t live_allocations() { return g_live_allocs; }
@@ -4155,18 +4120,18 @@ event_t event_create() {
 void event_destroy(event_t e) {
     if (e) HIP_CHECK(hipEventDestroy((hipEvent_t)e));
 }
-void event_record(event_t e, stream_t s) { HIP_CHECK(hipEventRecord((hipEvent_t)e, (hipStream_t)s)); }
-void stream_wait_event(stream_t s, event_t e) { HIP_CHECK(hipStreamWaitEvent((hipStream_t)s, (hipEvent_t)e, 0)); }
+void event_record(event_t e, stream_t s) { HIP_CHECK(record_event((hipEvent_t)e, (hipStream_t)s)); }
+void stream_wait_event(stream_t s, event_t e) { HIP_CHECK(wait_event((hipStream_t)s, (hipEvent_t)e, 0)); }
 
 bool graphs_supported() { return true; }
 void graph_begin(stream_t s) {
     if (!s) throw std::runtime_error("graph capture needs a stream of its own (not the default stream)");
-    HIP_CHECK(hipStreamBeginCapture((hipStream_t)s, hipStreamCaptureModeRelaxed));
+    HIP_CHECK(begin_capture((hipStream_t)s, hipStreamCaptureModeRelaxed));
 }
 graph_t graph_end(stream_t s) {
-    gemm_group_flush();
+    flush_deferred();
     hipGraph_t g = nullptr;
-    HIP_CHECK(hipStreamEndCapture((hipStream_t)s, &g));
+    HIP_CHECK(end_capture((hipStream_t)s, &g));
     if (!g) throw std::runtime_error("graph capture produced no graph");
     hipGraphExec_t ex = nullptr;
     const hipError_t e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
@@ -4176,34 +4141,34 @@ graph_t graph_end(stream_t s) {
 }
 void graph_abort(stream_t s) {
     hipGraph_t g = nullptr;
-    (void)hipStreamEndCapture((hipStream_t)s, &g);
+    (void)end_capture((hipStream_t)s, &g);
     if (g) (void)hipGraphDestroy(g);
     (void)hipGetLastError();
 }
-void graph_launch(graph_t g, stream_t s) { HIP_CHECK(hipGraphLaunch((hipGraphExec_t)g, (hipStream_t)s)); }
+void graph_launch(graph_t g, stream_t s) { HIP_CHECK(launch_graph((hipGraphExec_t)g, (hipStream_t)s)); }
 void graph_destroy(graph_t g) {
     if (g) HIP_CHECK(hipGraphExecDestroy((hipGraphExec_t)g));
 }
 void memcpy_h2d(void* d, const void* h, size_t bytes, stream_t s) {
-    gemm_group_flush();
-    HIP_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, (hipStream_t)s));
+    flush_deferred();
+    HIP_CHECK(copy_async(d, h, bytes, hipMemcpyHostToDevice, (hipStream_t)s));
     wait_idle((hipStream_t)s);
 }
 void memcpy_d2h(void* h, const void* d, size_t bytes, stream_t s) {
-    gemm_group_flush();
-    HIP_CHECK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, (hipStream_t)s));
+    flush_deferred();
+    HIP_CHECK(copy_async(h, d, bytes, hipMemcpyDeviceToHost, (hipStream_t)s));
     wait_idle((hipStream_t)s);
 }
 void memcpy_d2d(void* d, const void* s_, size_t bytes, stream_t s) {
-    gemm_group_flush();
-    HIP_CHECK(hipMemcpyAsync(d, s_, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
+    flush_deferred();
+    HIP_CHECK(copy_async(d, s_, bytes, hipMemcpyDeviceToDevice, (hipStream_t)s));
 }
 void memset_zero(void* d, size_t bytes, stream_t s) {
-    gemm_group_flush();
-    HIP_CHECK(hipMemsetAsync(d, 0, bytes, (hipStream_t)s));
+    flush_deferred();
+    HIP_CHECK(set_async(d, 0, bytes, (hipStream_t)s));
 }
 void stream_sync(stream_t s) {
-    gemm_group_flush();
+    flush_deferred();
     wait_idle((hipStream_t)s);
 }
 size_t mem_free_bytes() {
@@ -4496,14 +4461,13 @@ void gemm_group_sync() { gemm_group_flush(); }
 // (products queued in an open group — dev::gemm_group_begin / _end, which may span several calls of the C interface — stay
 // queued: a task is never recorded while one is waiting, phase_push, so what is recorded precedes them in the order of effects)
 void phase_sync() {
-    gemv_batch_flush();
+    gemv_batch_flush();          // (not flush_deferred: an open group stays queued, see above)
     phase_flush();
 }
 bool phase_pending() { return !g_phase.q.empty(); }
 long phase_generation() { return g_phase.flushes; }
 void phase_enable(int mode) {
-    gemm_group_flush();
-    phase_sync();
+    flush_deferred();
     g_phase.enabled = mode < 0 ? -1 : (mode ? 1 : 0);       // (-1: the environment is read again at the next operation)
     if (mode == 1) g_phase.serial = false;
 }
@@ -4539,7 +4503,7 @@ void gemm(const Gemm& g, stream_t s) {
     const bool a_kcontig = (a_sk == 1);
     const bool b_kcontig = (b_sk == 1);
     if (gemv_dispatch(g, a_sm, a_sk, b_sk, b_sn, st)) return;
-    gemv_batch_flush();
+    gemv_batch_flush();          // (not flush_deferred: the product may yet join the open group or the open phase)
     if (g_group.active && gemm_group_take_dma(g, a_kcontig, b_kcontig, a_sm, a_sk, b_sk, b_sn, st)) return;
     if (phase_gemm(g, a_kcontig, b_kcontig, a_sm, a_sk, b_sk, b_sn, st)) return;
     if (g_group.active && gemm_group_take(g, a_kcontig, b_kcontig, a_sm, a_sk, b_sk, b_sn, st)) return;
@@ -4649,17 +4613,7 @@ void gemm(const Gemm& g, stream_t s) {
         }
     }
 
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    if (g_prof.on) {
-        if (!g_prof.pool.empty()) {
-            ev = g_prof.pool.back();
-            g_prof.pool.pop_back();
-        } else {
-            HIP_CHECK(hipEventCreate(&ev.first));
-            HIP_CHECK(hipEventCreate(&ev.second));
-        }
-        HIP_CHECK(hipEventRecord(ev.first, st));
-    }
+    ProfSpan span(st);
     bool used_dma = false;
     int n_kernels = 0;
     g_stream64 = stream && BM <= 64 && BN <= 64;
@@ -4678,8 +4632,7 @@ void gemm(const Gemm& g, stream_t s) {
         else if (BM == 32 && BN == 64) dispatch_layout<32, 64>(k, a_kcontig, b_kcontig, vec, nblocks, st);
         else dispatch_layout<64, 64>(k, a_kcontig, b_kcontig, vec, nblocks, st);
         if (k.nsplit > 1) {
-            PYMES_LAUNCH(splitk_reduce_kernel, dim3((unsigned)ntiles, (unsigned)(BM * BN / 256)), dim3(256), 0, st, k, BM, BN);
-            HIP_CHECK(hipGetLastError());
+            launch_kernel(splitk_reduce_kernel, dim3((unsigned)ntiles, (unsigned)(BM * BN / 256)), dim3(256), 0, st, k, BM, BN);
         }
         return k.nsplit;
     };
@@ -4707,8 +4660,7 @@ void gemm(const Gemm& g, stream_t s) {
             GemmK r = k;                   // the reduction sees the tail tiles as a launch of its own: ws[i][ks], i from 0
             r.tile_begin = plan.whole;
             r.mixed = 0;
-            PYMES_LAUNCH(splitk_reduce_kernel, dim3((unsigned)plan.tail, 64u), dim3(256), 0, st, r, 128, 128);
-            HIP_CHECK(hipGetLastError());
+            launch_kernel(splitk_reduce_kernel, dim3((unsigned)plan.tail, 64u), dim3(256), 0, st, r, 128, 128);
             nsplit = -k.nsplit;            // logged as a negative split
         }
     } else {
@@ -4716,20 +4668,14 @@ void gemm(const Gemm& g, stream_t s) {
         if (tail_tiles > 0) nsplit = -launch(main_tiles, tail_tiles, tail_split);   // logged as a negative split
     }
     if (g_prof.on) {
-        HIP_CHECK(hipEventRecord(ev.second, st));
-        g_prof.ev.push_back(ev);
         const double fl = 2.0 * (double)g.M * (double)g.N * (double)g.K * (double)nbatch;
-        g_prof.flops += fl;
-        g_prof.fl.push_back(fl);
-        g_prof.klass.push_back(used_dma ? 1 : 0);
-        g_prof.nk.push_back(n_kernels);
         char buf[256];
         int len = snprintf(buf, sizeof buf, "M=%ld N=%ld K=%ld batch=%ld tile=%dx%d%s akc=%d bkc=%d vec=%d dma=%d split=%d flops=%.4e",
                            (long)g.M, (long)g.N, (long)g.K, (long)nbatch, BM, BN, g_stream64 ? "s" : "", (int)a_kcontig,
                            (int)b_kcontig, vec, (int)used_dma, nsplit, fl);
         if (used_dma && len > 0 && len < (int)sizeof buf)
             snprintf(buf + len, sizeof buf - len, " plan=%ld+%ld/%d", plan.whole, plan.tail, plan.tail ? k.nsplit : 1);
-        g_prof.what.push_back(buf);
+        span.finish(fl, used_dma ? 1 : 0, n_kernels, buf);
     }
 }
 
@@ -4744,7 +4690,7 @@ void gemv_batch_end() {
 }
 
 void permute(const Permute& p, stream_t s) {
-    gemv_batch_flush();
+    gemv_batch_flush();          // (not flush_deferred: the permutation may itself be recorded as a task of the open phase)
     gemm_group_flush();
     hipStream_t st = (hipStream_t)s;
     // canonicalise: drop extent-1 dims, sort by out-stride (descending), merge adjacent dims
@@ -4809,24 +4755,22 @@ void permute(const Permute& p, stream_t s) {
         const long nblk = rest * tq * tl;
         if (nblk > 0x7fffffffL) throw std::runtime_error("permute: grid too large");
         if (phase && nblk < 0x3fffffffL) { record(PK_PERM_TILED, nblk, kPermTileDoubles * (int)sizeof(double), PermTaskK{k, total, tq, tl}); return; }
-        PYMES_LAUNCH(permute_tiled_kernel, dim3((unsigned)nblk), dim3(256), 0, st, k, tq, tl);
+        launch_kernel(permute_tiled_kernel, dim3((unsigned)nblk), dim3(256), 0, st, k, tq, tl);
     } else {
         k.rank = r;
         for (int i = 0; i < r; ++i) { k.dim[i] = m[i].n; k.s_in[i] = m[i].si; k.s_out[i] = m[i].so; }
         for (int i = r; i < 6; ++i) { k.dim[i] = 1; k.s_in[i] = 0; k.s_out[i] = 0; }
         if (phase) { record(PK_PERM_DIRECT, grid_for(total, 256, 256 * 32), 0, PermTaskK{k, total, 0, 0}); return; }
-        PYMES_LAUNCH(permute_direct_kernel, dim3(grid_for(total, 256, 256 * 32)), dim3(256), 0, st, k, total);
+        launch_kernel(permute_direct_kernel, dim3(grid_for(total, 256, 256 * 32)), dim3(256), 0, st, k, total);
     }
-    HIP_CHECK(hipGetLastError());
 }
 
 void mp2_amplitudes(double* t, const double* w, const double* eo, const double* ev, double shift, int no, int nv,
                     stream_t s) {
     const long total = (long)nv * nv * no * no;
     if (!total) return;
-    PYMES_LAUNCH(mp2_amplitudes_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, t, w, eo, ev,
+    launch_kernel(mp2_amplitudes_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, t, w, eo, ev,
                        shift, no, nv, total);
-    HIP_CHECK(hipGetLastError());
 }
 
 void cc_update_to(double* t_out, double* dt, const double* t_in, const double* r, const double* eo, const double* ev,
@@ -4841,8 +4785,7 @@ void cc_update_to(double* t_out, double* dt, const double* t_in, const double* r
         phase_writes(t, {prange(t_out, total), prange(dt, total)});
         return;
     }
-    PYMES_LAUNCH(cc_update_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(cc_update_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, k);
 }
 void cc_update(double* t, double* dt, const double* r, const double* eo, const double* ev, double shift,
                double delta, int no, int nv, int rank, stream_t s) {
@@ -4879,9 +4822,8 @@ static int launch_dots_stage1(int npairs, const double* const* x, const double* 
         phase_writes(t, {prange(ws, 16L * kDotBlocks)});
         return nb;
     }
-    if (vec) PYMES_LAUNCH(dots_stage1_kernel<2>, dim3(nb * npairs), dim3(256), 0, st, k);
-    else PYMES_LAUNCH(dots_stage1_kernel<1>, dim3(nb * npairs), dim3(256), 0, st, k);
-    HIP_CHECK(hipGetLastError());
+    if (vec) launch_kernel(dots_stage1_kernel<2>, dim3(nb * npairs), dim3(256), 0, st, k);
+    else launch_kernel(dots_stage1_kernel<1>, dim3(nb * npairs), dim3(256), 0, st, k);
     return nb;
 }
 // stage 2 (partial sums of `npairs` reductions -> out_dev[npairs]) as a task of the open phase or a launch
@@ -4892,8 +4834,7 @@ static void launch_dots_stage2(int npairs, double* ws, int nb, double* out_dev, 
         phase_writes(t, {prange(out_dev, npairs)});
         return;
     }
-    PYMES_LAUNCH(dots_stage2_kernel, dim3(npairs), dim3(256), 0, st, ws, nb, out_dev);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(dots_stage2_kernel, dim3(npairs), dim3(256), 0, st, ws, nb, out_dev);
 }
 
 // the last stage of a reduction the host waits for (dots_final_kernel), as a task of the open phase or a launch
@@ -4910,8 +4851,7 @@ static void launch_dots_final(DotsFinalK k, double* ws, hipStream_t st) {
         // (the pinned destination is nobody else's: no range to declare; the task is ordered behind stage 1 through ws)
         return;
     }
-    PYMES_LAUNCH(dots_final_kernel, dim3(k.npairs), dim3(256), 0, st, k);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(dots_final_kernel, dim3(k.npairs), dim3(256), 0, st, k);
 }
 
 void dots(int npairs, const double* const* x, const double* const* y, const int64_t* n, double* out_host, stream_t s) {
@@ -4943,8 +4883,7 @@ void diis_step(double* state, int npairs, const double* const* x, const double* 
     const int nb = launch_dots_stage1(npairs, x, y, n, g_dot_ws[dv], st);
     double* out_dev = g_dot_ws[dv] + 16 * kDotBlocks;
     launch_dots_stage2(npairs, g_dot_ws[dv], nb, out_dev, st);
-    PYMES_LAUNCH(diis_step_kernel, dim3(1), dim3(64), 0, st, state, out_dev, ntypes, m, was_full);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(diis_step_kernel, dim3(1), dim3(64), 0, st, state, out_dev, ntypes, m, was_full);
 }
 
 void lincomb_dev(double* out, int nx, const double* const* x, const double* coeff_dev, int64_t n, stream_t s) {
@@ -4952,8 +4891,7 @@ void lincomb_dev(double* out, int nx, const double* const* x, const double* coef
     if (n <= 0) return;
     LinPtrsDev p;
     for (int i = 0; i < 8; ++i) p.x[i] = i < nx ? x[i] : nullptr;
-    PYMES_LAUNCH(lincomb_dev_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, out, p, coeff_dev, nx, (long)n);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(lincomb_dev_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, out, p, coeff_dev, nx, (long)n);
 }
 
 int energy_norms_start(const double* f, const double* t1, const double* t2, const double* Edir, const double* Eex,
@@ -4975,9 +4913,8 @@ int energy_norms_start(const double* f, const double* t1, const double* t2, cons
                         prange(t1, t1 ? (long)no * nv : 0), prange(f, (t1 && f) ? n * n : 0)});
         phase_writes(t, {prange(g_dot_ws[dv], 16L * kDotBlocks)});
     } else {
-        if (vec) PYMES_LAUNCH(energy_norms_kernel<2>, dim3(nb), dim3(256), 0, st, k);
-        else PYMES_LAUNCH(energy_norms_kernel<1>, dim3(nb), dim3(256), 0, st, k);
-        HIP_CHECK(hipGetLastError());
+        if (vec) launch_kernel(energy_norms_kernel<2>, dim3(nb), dim3(256), 0, st, k);
+        else launch_kernel(energy_norms_kernel<1>, dim3(nb), dim3(256), 0, st, k);
     }
     // the six sums straight into a slot of the pinned read-back ring, with the slot's sequence word behind them
     double* out_pin = nullptr;
@@ -4993,7 +4930,7 @@ void energy_norms(const double* f, const double* t1, const double* t2, const dou
     readback_wait_impl(energy_norms_start(f, t1, t2, Edir, Eex, dt2, no, nv, s), out_host, 6);
 }
 int readback_start(const double* dev_ptr, int n, stream_t s) {
-    gemm_group_flush();
+    flush_deferred();
     return readback_start_impl(dev_ptr, n, (hipStream_t)s);
 }
 void readback_wait(int slot, double* out_host, int n) { readback_wait_impl(slot, out_host, n); }
@@ -5006,19 +4943,18 @@ void exchange_asymmetry(const double* A, const double* B, const int64_t d[4], do
     out_host[0] = out_host[1] = 0.0;
     if (!total) return;
     unsigned long long* out_dev = reinterpret_cast<unsigned long long*>(g_dot_ws[dv] + 16 * kDotBlocks);
-    HIP_CHECK(hipMemsetAsync(out_dev, 0, 2 * sizeof(unsigned long long), st));
+    HIP_CHECK(set_async(out_dev, 0, 2 * sizeof(unsigned long long), st));
     const long tr = (d[2] + 63) / 64, ts = (d[3] + 63) / 64, ntiles = d[0] * d[1] * tr * ts;
     const int self = (A == B && d[0] == d[1]) ? 1 : 0;
     const unsigned grid = (unsigned)std::min<long>(ntiles, 256L * 8);
     const bool vec = even(d[2]) && even(d[3]) && aligned16(A) && aligned16(B);
     if (vec)
-        PYMES_LAUNCH(exchange_asym_kernel<true>, dim3(grid), dim3(256), 0, st, A, B, (long)d[0], (long)d[1], (long)d[2],
+        launch_kernel(exchange_asym_kernel<true>, dim3(grid), dim3(256), 0, st, A, B, (long)d[0], (long)d[1], (long)d[2],
                            (long)d[3], (int)tr, (int)ts, ntiles, self, out_dev);
     else
-        PYMES_LAUNCH(exchange_asym_kernel<false>, dim3(grid), dim3(256), 0, st, A, B, (long)d[0], (long)d[1], (long)d[2],
+        launch_kernel(exchange_asym_kernel<false>, dim3(grid), dim3(256), 0, st, A, B, (long)d[0], (long)d[1], (long)d[2],
                            (long)d[3], (int)tr, (int)ts, ntiles, self, out_dev);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(g_dot_host[dv], out_dev, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(copy_async(g_dot_host[dv], out_dev, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
     wait_idle(st);
     out_host[0] = g_dot_host[dv][0];
     out_host[1] = g_dot_host[dv][1];
@@ -5037,8 +4973,7 @@ void lincomb(double* out, int nx, const double* const* x, const double* c, int64
         phase_writes(t, {prange(out, n)});
         return;
     }
-    PYMES_LAUNCH(lincomb_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(lincomb_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, k);
 }
 
 namespace {
@@ -5048,11 +4983,9 @@ void gram_tile(const double* const* x, int mm, const double* const* y, int nn, l
     GramPtrs<MM, NN> p;
     for (int i = 0; i < MM; ++i) p.x[i] = x[i < mm ? i : 0];
     for (int j = 0; j < NN; ++j) p.y[j] = y[j < nn ? j : 0];
-    if (vec) PYMES_LAUNCH((gram_stage1_kernel<MM, NN, 2>), dim3(nblk), dim3(256), 0, st, p, len, ws);
-    else PYMES_LAUNCH((gram_stage1_kernel<MM, NN, 1>), dim3(nblk), dim3(256), 0, st, p, len, ws);
-    HIP_CHECK(hipGetLastError());
-    PYMES_LAUNCH(gram_stage2_kernel, dim3(MM * NN), dim3(256), 0, st, ws, nblk, MM * NN, tile_dev);
-    HIP_CHECK(hipGetLastError());
+    if (vec) launch_kernel(gram_stage1_kernel<MM, NN, 2>, dim3(nblk), dim3(256), 0, st, p, len, ws);
+    else launch_kernel(gram_stage1_kernel<MM, NN, 1>, dim3(nblk), dim3(256), 0, st, p, len, ws);
+    launch_kernel(gram_stage2_kernel, dim3(MM * NN), dim3(256), 0, st, ws, nblk, MM * NN, tile_dev);
 }
 template <int MM>
 void gram_tile_n(const double* const* x, int mm, const double* const* y, int nn, long len, bool vec, int nblk, double* ws,
@@ -5073,9 +5006,8 @@ void lincomb_multi_tile(const double* const* x, int mm, const double* c, int ldc
     for (int j = 0; j < NN; ++j) { p.y[j] = y[j < nn ? j : 0]; p.beta[j] = j < nn ? beta[j] : 0.0; }
     const long nvec = vec ? len / 2 : len;
     const int nblk = (int)std::max<long>(1, std::min<long>(8192, (nvec + 255) / 256));
-    if (vec) PYMES_LAUNCH((lincomb_multi_kernel<MM, NN, 2>), dim3(nblk), dim3(256), 0, st, p, nn, len);
-    else PYMES_LAUNCH((lincomb_multi_kernel<MM, NN, 1>), dim3(nblk), dim3(256), 0, st, p, nn, len);
-    HIP_CHECK(hipGetLastError());
+    if (vec) launch_kernel(lincomb_multi_kernel<MM, NN, 2>, dim3(nblk), dim3(256), 0, st, p, nn, len);
+    else launch_kernel(lincomb_multi_kernel<MM, NN, 1>, dim3(nblk), dim3(256), 0, st, p, nn, len);
 }
 template <int MM>
 void lincomb_multi_tile_n(const double* const* x, int mm, const double* c, int ldc, const double* beta, double* const* y, int nn,
@@ -5117,7 +5049,7 @@ void gram(int m, int n, const double* const* x, const double* const* y, int64_t 
     std::vector<Tile> done;
     auto flush = [&]() {
         if (done.empty()) return;
-        HIP_CHECK(hipMemcpyAsync(g_gram_host[dv], tiles, sizeof(double) * 64 * done.size(), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(copy_async(g_gram_host[dv], tiles, sizeof(double) * 64 * done.size(), hipMemcpyDeviceToHost, st));
         wait_idle(st);
         for (size_t t = 0; t < done.size(); ++t)
             for (int i = 0; i < done[t].mm; ++i)
@@ -5180,22 +5112,19 @@ void lincomb_multi(int m, int n, const double* const* x, const double* c, const 
 
 void cmul(const double* mr, const double* mi, const double* xr, const double* xi, double* yr, double* yi, int64_t n, stream_t s) {
     if (n <= 0) return;
-    PYMES_LAUNCH(cmul_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, mr, mi, xr, xi, yr, yi, (long)n);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(cmul_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, mr, mi, xr, xi, yr, yi, (long)n);
 }
 
 void exchange_split(const double* u, double* us, double* w, double* dg, int no, int nv, stream_t s) {
     const long total = (long)nv * nv * no * no;
     if (!total) return;
-    PYMES_LAUNCH(exchange_split_kernel, dim3(grid_for(total, 256, 256 * 64)), dim3(256), 0, (hipStream_t)s, u, us, w, dg, no, nv,
+    launch_kernel(exchange_split_kernel, dim3(grid_for(total, 256, 256 * 64)), dim3(256), 0, (hipStream_t)s, u, us, w, dg, no, nv,
                        total);
-    HIP_CHECK(hipGetLastError());
 }
 void sgn_ij_add(double* D, const double* R, int no, int nv, stream_t s) {
     const long total = (long)nv * nv * no * no;
     if (!total) return;
-    PYMES_LAUNCH(sgn_ij_add_kernel, dim3(grid_for(total, 256, 256 * 64)), dim3(256), 0, (hipStream_t)s, D, R, no, total);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(sgn_ij_add_kernel, dim3(grid_for(total, 256, 256 * 64)), dim3(256), 0, (hipStream_t)s, D, R, no, total);
 }
 int64_t eom_diag_ws_doubles(int no, int nv) { return EomDiagWs(no, nv).total; }
 void eom_diagonals(const double* V, const double* T, const double* dai, const double* iaai, const double* iaia, const double* ijij,
@@ -5204,20 +5133,16 @@ void eom_diagonals(const double* V, const double* T, const double* dai, const do
     const EomDiagWs w(no, nv);
     const long total = (long)nv * nv * no * no;
     if (w.total > 0x7fffffffL) throw std::runtime_error("eom_diagonals: problem too large for one grid");
-    PYMES_LAUNCH(eom_diag_sums_kernel, dim3((unsigned)w.total), dim3(256), 0, st, V, T, ws, no, nv);
-    HIP_CHECK(hipGetLastError());
-    PYMES_LAUNCH(eom_diag_singles_kernel, dim3((unsigned)(((long)nv * no + 255) / 256)), dim3(256), 0, st, ws, dai, iaai, iaia,
+    launch_kernel(eom_diag_sums_kernel, dim3((unsigned)w.total), dim3(256), 0, st, V, T, ws, no, nv);
+    launch_kernel(eom_diag_singles_kernel, dim3((unsigned)(((long)nv * no + 255) / 256)), dim3(256), 0, st, ws, dai, iaai, iaia,
                        d1, no, nv);
-    HIP_CHECK(hipGetLastError());
-    PYMES_LAUNCH(eom_diag_doubles_kernel, dim3(grid_for(total, 256, 256 * 64)), dim3(256), 0, st, V, T, ws, dai, iaai, iaia, ijij,
+    launch_kernel(eom_diag_doubles_kernel, dim3(grid_for(total, 256, 256 * 64)), dim3(256), 0, st, V, T, ws, dai, iaai, iaia, ijij,
                        abab, d2, no, nv, total);
-    HIP_CHECK(hipGetLastError());
 }
 void cshift_inv(const double* d, double zr, double zi, double hr, double hi, double shift, double* mr, double* mi, int64_t n,
                 stream_t s) {
     if (n <= 0) return;
-    PYMES_LAUNCH(cshift_inv_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, d, zr, zi, hr, hi, shift, mr, mi, (long)n);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(cshift_inv_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, d, zr, zi, hr, hi, shift, mr, mi, (long)n);
 }
 
 void tau_build(double* tau, const double* t2, const double* t1, int no, int nv, stream_t s) {
@@ -5231,8 +5156,7 @@ void tau_build(double* tau, const double* t2, const double* t1, int no, int nv, 
         phase_writes(t, {prange(tau, total)});
         return;
     }
-    PYMES_LAUNCH(tau_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(tau_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, k);
 }
 
 void ladder_pack_V(const double* V, double* Vp, double* Vm, int nr, int nc, int64_t rp0, int64_t rp1, stream_t s, int64_t ldvp,
@@ -5243,9 +5167,8 @@ void ladder_pack_V(const double* V, double* Vp, double* Vm, int nr, int nc, int6
     const long ntp = (long)nt * (nt + 1) / 2;
     const long nblk = (rp1 - rp0) * ntp;
     if (nblk > 0x7fffffffL) throw std::runtime_error("ladder_pack_V: grid too large");
-    PYMES_LAUNCH(ladder_pack_V_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s, V, Vp, Vm, nr, nc,
+    launch_kernel(ladder_pack_V_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s, V, Vp, Vm, nr, nc,
                        (long)rp0, nt, ntp, npp, npm);
-    HIP_CHECK(hipGetLastError());
 }
 
 void ladder_pack_V_factors(const double* B, double* Vp, double* Vm, int naux, int n, int no, int64_t rp0, int64_t rp1,
@@ -5259,9 +5182,8 @@ void ladder_pack_V_factors(const double* B, double* Vp, double* Vm, int naux, in
     const long ntp = (long)nt * (nt + 1) / 2;
     const long nblk = (rp1 - rp0) * ntp;
     if (nblk > 0x7fffffffL) throw std::runtime_error("ladder_pack_V_factors: grid too large");
-    PYMES_LAUNCH(ladder_pack_V_factors_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s, B, Vp, Vm, naux, n, no,
+    launch_kernel(ladder_pack_V_factors_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s, B, Vp, Vm, naux, n, no,
                  (long)rp0, ntp, npp, npm);
-    HIP_CHECK(hipGetLastError());
 }
 
 // nocc within the instantiated MFMA step counts, and the byte offsets inside a tile (16 a of packed rows of the widest half)
@@ -5291,15 +5213,14 @@ void ladder_dress(const double* V, const double* Pk, const double* t1, double* W
     hipStream_t st = (hipStream_t)s;
     const int nk = (no + 3) / 4;
     const long nfrag = ladder_dress_ws_doubles(no, nv);
-    PYMES_LAUNCH(ladder_dress_tfrag_kernel, dim3((unsigned)((nfrag + 255) / 256)), dim3(256), 0, st, t1, ws, no, nv, nk, nfrag);
-#define PYMES_DRESS(NK) case NK: PYMES_LAUNCH(ladder_dress_kernel<NK>, grid, block, 0, st, V, Pk, (const double*)ws, W, no, nv, (long)ld, (long)row0, (long)row1, sgn, ntp); break;
+    launch_kernel(ladder_dress_tfrag_kernel, dim3((unsigned)((nfrag + 255) / 256)), dim3(256), 0, st, t1, ws, no, nv, nk, nfrag);
+#define PYMES_DRESS(NK) case NK: launch_kernel(ladder_dress_kernel<NK>, grid, block, 0, st, V, Pk, (const double*)ws, W, no, nv, (long)ld, (long)row0, (long)row1, sgn, ntp); break;
     switch (nk) {
         PYMES_DRESS(1) PYMES_DRESS(2) PYMES_DRESS(3) PYMES_DRESS(4) PYMES_DRESS(5) PYMES_DRESS(6) PYMES_DRESS(7) PYMES_DRESS(8)
         PYMES_DRESS(9) PYMES_DRESS(10) PYMES_DRESS(11) PYMES_DRESS(12) PYMES_DRESS(13) PYMES_DRESS(14) PYMES_DRESS(15) PYMES_DRESS(16)
         PYMES_DRESS(17) PYMES_DRESS(18) PYMES_DRESS(19) PYMES_DRESS(20)
     }
 #undef PYMES_DRESS
-    HIP_CHECK(hipGetLastError());
 }
 
 void ladder_pack_T(const double* X, const double* t1, double* Sp, double* Am, int nc, int nr, int flags, int64_t ldp,
@@ -5323,8 +5244,7 @@ void ladder_pack_T(const double* X, const double* t1, double* Sp, double* Am, in
                          (flags & PACK_AM_PROWS) ? pbox(Am + rp0 * ldm, {{rp1 - rp0, ldm}, {ldm, 1}}) : prange(Am, am_rows * ldm)});
         return;
     }
-    PYMES_LAUNCH(ladder_pack_T_kernel, dim3((unsigned)(rp1 - rp0)), dim3(256), 0, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(ladder_pack_T_kernel, dim3((unsigned)(rp1 - rp0)), dim3(256), 0, (hipStream_t)s, k);
 }
 
 void ladder_unpack(const double* L, double* R, double beta, int no, int nv, stream_t s) {
@@ -5338,8 +5258,7 @@ void ladder_unpack(const double* L, double* R, double beta, int no, int nv, stre
         phase_writes(t, {prange(R, total)});
         return;
     }
-    PYMES_LAUNCH(ladder_unpack_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(ladder_unpack_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, k);
 }
 
 bool fused_pair_kernels_ok(int no) { return (size_t)no * (no + 1) * sizeof(double) <= 64 * 1024; }
@@ -5358,8 +5277,7 @@ void ring_operands(const double* Viabj, const double* Viajb, double* M, double* 
         phase_writes(t, {prange(M, ov2), prange(N1, ov2)});
         return;
     }
-    PYMES_LAUNCH(ring_operands_kernel, dim3((unsigned)((long)no * nv)), dim3(256), lds, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(ring_operands_kernel, dim3((unsigned)((long)no * nv)), dim3(256), lds, (hipStream_t)s, k);
 }
 
 void t2_layouts(const double* T, double* Td, double* Tx, double* Ttd, int no, int nv, stream_t s, double ca, double cb) {
@@ -5375,9 +5293,8 @@ void t2_layouts(const double* T, double* Td, double* Tx, double* Ttd, int no, in
         phase_writes(t, {prange(Td, Td ? n4 : 0), prange(Tx, n4), prange(Ttd, n4)});
         return;
     }
-    if (res) PYMES_LAUNCH(t2_layouts_kernel<true>, dim3((unsigned)(nv * nv)), dim3(256), lds, (hipStream_t)s, k);
-    else PYMES_LAUNCH(t2_layouts_kernel<false>, dim3((unsigned)(nv * nv)), dim3(256), lds, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
+    if (res) launch_kernel(t2_layouts_kernel<true>, dim3((unsigned)(nv * nv)), dim3(256), lds, (hipStream_t)s, k);
+    else launch_kernel(t2_layouts_kernel<false>, dim3((unsigned)(nv * nv)), dim3(256), lds, (hipStream_t)s, k);
 }
 
 void residual_assemble(const double* V, const double* L, const double* N, const double* D, const double* X, double* R,
@@ -5393,8 +5310,7 @@ void residual_assemble(const double* V, const double* L, const double* N, const 
         phase_writes(t, {prange(R, n4)});
         return;
     }
-    PYMES_LAUNCH(residual_assemble_kernel, dim3((unsigned)((long)nv * (nv + 1) / 2)), dim3(256), lds, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(residual_assemble_kernel, dim3((unsigned)((long)nv * (nv + 1) / 2)), dim3(256), lds, (hipStream_t)s, k);
 }
 
 void scatter(double* dst, const int64_t* idx_host, const double* val_host, int64_t n, stream_t s) {
@@ -5402,15 +5318,14 @@ void scatter(double* dst, const int64_t* idx_host, const double* val_host, int64
     long* idx = nullptr;
     double* val = nullptr;
     HIP_CHECK(hipMalloc(&idx, sizeof(long) * n));
-    if (hipMalloc(&val, sizeof(double) * n) != hipSuccess) { (void)hipFree(idx); throw std::runtime_error("scatter: out of device memory"); }
+    if (hipMalloc(&val, sizeof(double) * n) != hipSuccess) { (void)free_device(idx); throw std::runtime_error("scatter: out of device memory"); }
     hipStream_t st = (hipStream_t)s;
-    HIP_CHECK(hipMemcpyAsync(idx, idx_host, sizeof(long) * n, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(val, val_host, sizeof(double) * n, hipMemcpyHostToDevice, st));
-    PYMES_LAUNCH(scatter_kernel, dim3(grid_for(n)), dim3(256), 0, st, dst, idx, val, (long)n);
-    const hipError_t e = hipGetLastError();
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(idx);
-    (void)hipFree(val);
+    HIP_CHECK(copy_async(idx, idx_host, sizeof(long) * n, hipMemcpyHostToDevice, st));
+    HIP_CHECK(copy_async(val, val_host, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    const hipError_t e = try_launch_kernel(scatter_kernel, dim3(grid_for(n)), dim3(256), 0, st, dst, idx, val, (long)n);
+    (void)sync_stream(st);
+    (void)free_device(idx);
+    (void)free_device(val);
     HIP_CHECK(e);
 }
 
@@ -5419,8 +5334,7 @@ void hf_fock(const double* const dir[4], const double* const exc[4], const doubl
     HfBlocks B;
     for (int i = 0; i < 4; ++i) { B.dir[i] = dir[i]; B.exc[i] = exc[i]; }
     const int n = no + nv;
-    PYMES_LAUNCH(hf_fock_kernel, dim3((n * n + 255) / 256), dim3(256), 0, (hipStream_t)s, B, h_dev, f_dev, no, nv);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(hf_fock_kernel, dim3((n * n + 255) / 256), dim3(256), 0, (hipStream_t)s, B, h_dev, f_dev, no, nv);
 }
 
 int64_t fcidump_fill(double* V, const double* val_host, const int32_t* pqrs_host, int64_t count, int n, bool is_tc,
@@ -5434,45 +5348,41 @@ int64_t fcidump_fill(double* V, const double* val_host, const int32_t* pqrs_host
     unsigned long long bad = 0;
     HIP_CHECK(hipMalloc(&dval, sizeof(double) * std::min(count, chunk)));
     if (hipMalloc(&didx, sizeof(int) * 4 * std::min(count, chunk)) != hipSuccess || hipMalloc(&dbad, sizeof(bad)) != hipSuccess) {
-        (void)hipFree(dval); (void)hipFree(didx);
+        (void)free_device(dval); (void)free_device(didx);
         throw std::runtime_error("fcidump_fill: out of device memory");
     }
-    hipError_t err = hipMemsetAsync(dbad, 0, sizeof(bad), st);
+    hipError_t err = set_async(dbad, 0, sizeof(bad), st);
     for (int pass = 0; pass < 2 && err == hipSuccess; ++pass)          // fill everything, then verify everything
         for (int64_t b0 = 0; b0 < count && err == hipSuccess; b0 += chunk) {
             const int64_t nb = std::min(chunk, count - b0);
-            err = hipMemcpyAsync(dval, val_host + b0, sizeof(double) * nb, hipMemcpyHostToDevice, st);
-            if (err == hipSuccess) err = hipMemcpyAsync(didx, pqrs_host + 4 * b0, sizeof(int) * 4 * nb, hipMemcpyHostToDevice, st);
+            err = copy_async(dval, val_host + b0, sizeof(double) * nb, hipMemcpyHostToDevice, st);
+            if (err == hipSuccess) err = copy_async(didx, pqrs_host + 4 * b0, sizeof(int) * 4 * nb, hipMemcpyHostToDevice, st);
             if (err != hipSuccess) break;
-            PYMES_LAUNCH(fcidump_fill_kernel, dim3(grid_for(nb)), dim3(256), 0, st, V, dval, didx, (long)nb, (long)n,
-                               is_tc ? 1 : 0, pass, dbad);
-            err = hipGetLastError();
-            if (err == hipSuccess) err = hipStreamSynchronize(st);      // the staging buffers are reused
+            err = try_launch_kernel(fcidump_fill_kernel, dim3(grid_for(nb)), dim3(256), 0, st, V, dval, didx, (long)nb, (long)n,
+                                    is_tc ? 1 : 0, pass, dbad);
+            if (err == hipSuccess) err = sync_stream(st);      // the staging buffers are reused
         }
-    if (err == hipSuccess) err = hipMemcpy(&bad, dbad, sizeof(bad), hipMemcpyDeviceToHost);
-    (void)hipFree(dval); (void)hipFree(didx); (void)hipFree(dbad);
+    if (err == hipSuccess) err = copy_sync(&bad, dbad, sizeof(bad), hipMemcpyDeviceToHost);
+    (void)free_device(dval); (void)free_device(didx); (void)free_device(dbad);
     HIP_CHECK(err);
     return (int64_t)bad;
 }
 
 void tc_single_contraction(const double* L, double* D, int nb, int no, stream_t s) {
     const long total = (long)nb * nb * nb * nb;
-    PYMES_LAUNCH(tc_single_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, L, D, nb, no, total);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(tc_single_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, L, D, nb, no, total);
 }
 void tc_double_contraction(const double* L, double* S, int nb, int no, stream_t s) {
-    PYMES_LAUNCH(tc_double_kernel, dim3((nb * nb + 255) / 256), dim3(256), 0, (hipStream_t)s, L, S, nb, no);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(tc_double_kernel, dim3((nb * nb + 255) / 256), dim3(256), 0, (hipStream_t)s, L, S, nb, no);
 }
 double tc_triple_contraction(const double* L, int nb, int no, stream_t s) {
     double* out = nullptr;
     HIP_CHECK(hipMalloc(&out, sizeof(double)));
-    PYMES_LAUNCH(tc_triple_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, L, out, nb, no);
+    const hipError_t e1 = try_launch_kernel(tc_triple_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, L, out, nb, no);
     double h = 0.0;
-    const hipError_t e1 = hipGetLastError();
-    const hipError_t e2 = hipMemcpyAsync(&h, out, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)s);
-    (void)hipStreamSynchronize((hipStream_t)s);
-    (void)hipFree(out);
+    const hipError_t e2 = copy_async(&h, out, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)s);
+    (void)sync_stream((hipStream_t)s);
+    (void)free_device(out);
     HIP_CHECK(e1);
     HIP_CHECK(e2);
     return h;
@@ -5480,8 +5390,7 @@ double tc_triple_contraction(const double* L, int nb, int no, stream_t s) {
 
 void pairs_pack(const double* full, double* Xc, int no, int nv, int64_t r0, int64_t r1, stream_t s) {
     if (r1 <= r0) return;
-    PYMES_LAUNCH(pairs_pack_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, (hipStream_t)s, full, Xc, no, nv, (long)r0);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(pairs_pack_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, (hipStream_t)s, full, Xc, no, nv, (long)r0);
 }
 void energy_norms_pairs(const double* f, const double* t1, const double* tc, const double* Edir, const double* Eex,
                         const double* dtc, int no, int nv, int64_t r0, int64_t r1, bool with_t1, double out_host[6],
@@ -5491,13 +5400,11 @@ void energy_norms_pairs(const double* f, const double* t1, const double* tc, con
     ensure_dot_ws(dv);
     const long npairs = std::max<long>(0, (long)(r1 - r0));
     const int nb = (int)std::max<long>(1, std::min<long>(kDotBlocks, 2 * npairs));
-    PYMES_LAUNCH(energy_norms_pairs_kernel, dim3(nb), dim3(256), 0, st, f, t1, tc, Edir, Eex, dtc, no, nv, (long)r0,
+    launch_kernel(energy_norms_pairs_kernel, dim3(nb), dim3(256), 0, st, f, t1, tc, Edir, Eex, dtc, no, nv, (long)r0,
                        npairs, with_t1 ? 1 : 0, g_dot_ws[dv]);
-    HIP_CHECK(hipGetLastError());
     double* out_dev = g_dot_ws[dv] + 16 * kDotBlocks;
-    PYMES_LAUNCH(dots_stage2_kernel, dim3(6), dim3(256), 0, st, g_dot_ws[dv], nb, out_dev);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(g_dot_host[dv], out_dev, sizeof(double) * 6, hipMemcpyDeviceToHost, st));
+    launch_kernel(dots_stage2_kernel, dim3(6), dim3(256), 0, st, g_dot_ws[dv], nb, out_dev);
+    HIP_CHECK(copy_async(g_dot_host[dv], out_dev, sizeof(double) * 6, hipMemcpyDeviceToHost, st));
     wait_idle(st);
     for (int i = 0; i < 6; ++i) out_host[i] = g_dot_host[dv][i];
 }
@@ -5509,32 +5416,27 @@ void energy_norms_pairs_dev(const double* f, const double* t1, const double* tc,
     ensure_dot_ws(dv);
     const long npairs = std::max<long>(0, (long)(r1 - r0));
     const int nb = (int)std::max<long>(1, std::min<long>(kDotBlocks, 2 * npairs));
-    PYMES_LAUNCH(energy_norms_pairs_kernel, dim3(nb), dim3(256), 0, st, f, t1, tc, Edir, Eex, dtc, no, nv, (long)r0,
+    launch_kernel(energy_norms_pairs_kernel, dim3(nb), dim3(256), 0, st, f, t1, tc, Edir, Eex, dtc, no, nv, (long)r0,
                        npairs, with_t1 ? 1 : 0, g_dot_ws[dv]);
-    HIP_CHECK(hipGetLastError());
-    PYMES_LAUNCH(dots_stage2_kernel, dim3(6), dim3(256), 0, st, g_dot_ws[dv], nb, out_dev);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(dots_stage2_kernel, dim3(6), dim3(256), 0, st, g_dot_ws[dv], nb, out_dev);
 }
 void pairs_unpack(const double* Xc, double* full, int no, int nv, int64_t r0, int64_t r1, stream_t s) {
     if (r1 <= r0) return;
-    PYMES_LAUNCH(pairs_unpack_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, (hipStream_t)s, Xc, full, no, nv, (long)r0);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(pairs_unpack_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, (hipStream_t)s, Xc, full, no, nv, (long)r0);
 }
 void cc_update_pairs(double* tc, double* dtc, const double* rc, const double* eo, const double* ev, double shift,
                      double delta, int no, int nv, int64_t r0, int64_t r1, stream_t s) {
     if (r1 <= r0) return;
-    PYMES_LAUNCH(cc_update_pairs_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, (hipStream_t)s, tc, dtc, rc, eo, ev,
+    launch_kernel(cc_update_pairs_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, (hipStream_t)s, tc, dtc, rc, eo, ev,
                        shift, delta, no, (long)r0);
-    HIP_CHECK(hipGetLastError());
 }
 void residual_assemble_pairs(const double* V, const double* L, const double* Np, const double* D, const double* X,
                              double* Rc, int no, int nv, int64_t r0, int64_t r1, int a0, int nbp, stream_t s, double xd) {
     if (r1 <= r0) return;
     if (!fused_pair_kernels_ok(no)) throw std::runtime_error("residual_assemble_pairs: nocc too large for the LDS tile");
     const size_t lds = sizeof(double) * no * (no + 1);
-    PYMES_LAUNCH(residual_assemble_pairs_kernel, dim3((unsigned)(r1 - r0)), dim3(256), lds, (hipStream_t)s, V, L, Np,
+    launch_kernel(residual_assemble_pairs_kernel, dim3((unsigned)(r1 - r0)), dim3(256), lds, (hipStream_t)s, V, L, Np,
                        D, X, Rc, no, nv, (long)r0, a0, nbp, xd);
-    HIP_CHECK(hipGetLastError());
 }
 
 void rows_unpack(const double* Q, double* out, int64_t rows, int no, stream_t s) {
@@ -5550,8 +5452,7 @@ void rows_unpack(const double* Q, double* out, int64_t rows, int no, stream_t s)
         t.acc = 0;
         return;
     }
-    PYMES_LAUNCH(rows_unpack_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(rows_unpack_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, k);
 }
 
 bool fock_g12_ok(int nv) { return nv >= 1 && nv <= 1024 && !((nv & 1) && nv > 512); }
@@ -5585,11 +5486,9 @@ void fock_g12(const double* V, const double* t1, double* G1, double* G2, int no,
         phase_writes(u, {prange(G1, av), prange(G2, av)});
         return;
     }
-    if (vec2) PYMES_LAUNCH(fock_g12_kernel<2>, grid, block, lds, st, k);
-    else PYMES_LAUNCH(fock_g12_kernel<1>, grid, block, lds, st, k);
-    HIP_CHECK(hipGetLastError());
-    PYMES_LAUNCH(fock_g12_finish_kernel, dim3((unsigned)((av + 255) / 256)), dim3(256), 0, st, kf);
-    HIP_CHECK(hipGetLastError());
+    if (vec2) launch_kernel(fock_g12_kernel<2>, grid, block, lds, st, k);
+    else launch_kernel(fock_g12_kernel<1>, grid, block, lds, st, k);
+    launch_kernel(fock_g12_finish_kernel, dim3((unsigned)((av + 255) / 256)), dim3(256), 0, st, kf);
 }
 
 void fock_finish(const double* f, const double* t1, const double* W, double* fd, double* ft, int no, int nv, stream_t s) {
@@ -5605,10 +5504,8 @@ void fock_finish(const double* f, const double* t1, const double* W, double* fd,
         phase_writes(u, {prange(fd, n * n)});
         return;
     }
-    PYMES_LAUNCH(fock_ft_kernel, dim3((unsigned)((no * no + 3) / 4)), dim3(256), 0, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
-    PYMES_LAUNCH(fock_finish_kernel, dim3((unsigned)((n * n + 3) / 4)), dim3(256), 0, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(fock_ft_kernel, dim3((unsigned)((no * no + 3) / 4)), dim3(256), 0, (hipStream_t)s, k);
+    launch_kernel(fock_finish_kernel, dim3((unsigned)((n * n + 3) / 4)), dim3(256), 0, (hipStream_t)s, k);
 }
 
 void pair_traces(const double* M, int64_t ld, double alpha, double beta, double* out_vv, double* out_oo, int no, int nv,
@@ -5624,8 +5521,7 @@ void pair_traces(const double* M, int64_t ld, double alpha, double beta, double*
         phase_writes(t, {prange(out_vv, (long)nv * nv), prange(out_oo, (long)no * no)});
         return;
     }
-    PYMES_LAUNCH(pair_traces_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)s, k);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(pair_traces_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)s, k);
 }
 
 void ueg_two_body(const UegParams& prm, const int* k_int_dev, const int* index_map_dev, double* V_dev, stream_t s) {
@@ -5644,13 +5540,13 @@ void ueg_two_body(const UegParams& prm, const int* k_int_dev, const int* index_m
     if (prm.tab_array) {
         if (!prm.tab_scalar || prm.tab_len < 1) throw std::runtime_error("ueg: both correlator tables are needed");
         tabs = (double*)dmalloc(sizeof(double) * 2 * prm.tab_len);
-        HIP_CHECK(hipMemcpyAsync(tabs, prm.tab_scalar, sizeof(double) * prm.tab_len, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(tabs + prm.tab_len, prm.tab_array, sizeof(double) * prm.tab_len, hipMemcpyHostToDevice, st));
+        HIP_CHECK(copy_async(tabs, prm.tab_scalar, sizeof(double) * prm.tab_len, hipMemcpyHostToDevice, st));
+        HIP_CHECK(copy_async(tabs + prm.tab_len, prm.tab_array, sizeof(double) * prm.tab_len, hipMemcpyHostToDevice, st));
         u.tab_s = tabs; u.tab_a = tabs + prm.tab_len; u.tab_len = prm.tab_len;
     }
-    HIP_CHECK(hipMemsetAsync(V_dev, 0, sizeof(double) * n * n * n * n, st));
+    HIP_CHECK(set_async(V_dev, 0, sizeof(double) * n * n * n * n, st));
     std::vector<int> kint(3 * n);
-    HIP_CHECK(hipMemcpyAsync(kint.data(), k_int_dev, sizeof(int) * 3 * n, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(copy_async(kint.data(), k_int_dev, sizeof(int) * 3 * n, hipMemcpyDeviceToHost, st));
     wait_idle(st);
     double *umat = nullptr, *E = nullptr, *dk_dev = nullptr;
     int *uidx = nullptr, *dint_dev = nullptr;
@@ -5681,20 +5577,17 @@ void ueg_two_body(const UegParams& prm, const int* k_int_dev, const int* index_m
             dk_dev = (double*)dmalloc(sizeof(double) * 3 * nd);
             uidx = (int*)dmalloc(sizeof(int) * index.size());
             dint_dev = (int*)dmalloc(sizeof(int) * 3 * nd);
-            HIP_CHECK(hipMemcpyAsync(dint_dev, dints.data(), sizeof(int) * 3 * nd, hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(dk_dev, dks.data(), sizeof(double) * 3 * nd, hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(uidx, index.data(), sizeof(int) * index.size(), hipMemcpyHostToDevice, st));
-            PYMES_LAUNCH(ueg_nabla_kernel, dim3(nd), dim3(256), 0, st, u, dk_dev, dint_dev, umat);
-            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(copy_async(dint_dev, dints.data(), sizeof(int) * 3 * nd, hipMemcpyHostToDevice, st));
+            HIP_CHECK(copy_async(dk_dev, dks.data(), sizeof(double) * 3 * nd, hipMemcpyHostToDevice, st));
+            HIP_CHECK(copy_async(uidx, index.data(), sizeof(int) * index.size(), hipMemcpyHostToDevice, st));
+            launch_kernel(ueg_nabla_kernel, dim3(nd), dim3(256), 0, st, u, dk_dev, dint_dev, umat);
         } else if (prm.mode == 2) {
             E = (double*)dmalloc(sizeof(double) * n * n);
-            PYMES_LAUNCH(ueg_effective_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st, u, k_int_dev, E);
-            HIP_CHECK(hipGetLastError());
+            launch_kernel(ueg_effective_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st, u, k_int_dev, E);
         }
         const long total = n * n * n;
-        PYMES_LAUNCH(ueg_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, u, k_int_dev,
+        launch_kernel(ueg_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, u, k_int_dev,
                            index_map_dev, umat, uidx, E, V_dev);
-        HIP_CHECK(hipGetLastError());
         wait_idle(st);
     } catch (...) {
         dfree(umat); dfree(E); dfree(dk_dev); dfree(uidx); dfree(dint_dev); dfree(tabs);
@@ -5780,36 +5673,23 @@ bool gemv_dispatch(const dev::Gemm& g, long a_sm, long a_sk, long b_sk, long b_s
             gemv_batch_flush();              // this one runs on its own, behind the collected ones
         }
     }
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    if (g_prof.on) {
-        if (!g_prof.pool.empty()) { ev = g_prof.pool.back(); g_prof.pool.pop_back(); }
-        else { HIP_CHECK(hipEventCreate(&ev.first)); HIP_CHECK(hipEventCreate(&ev.second)); }
-        HIP_CHECK(hipEventRecord(ev.first, st));
-    }
+    ProfSpan span(st);
     if (cols) {
-        if (vec == 2) PYMES_LAUNCH(gemv_cols_kernel<2>, dim3((unsigned)cblocks, (unsigned)nchunk), dim3(256), 0, st, W, ld, x, xs, R, C, rchunk, g.splitk_ws);
-        else PYMES_LAUNCH(gemv_cols_kernel<1>, dim3((unsigned)cblocks, (unsigned)nchunk), dim3(256), 0, st, W, ld, x, xs, R, C, rchunk, g.splitk_ws);
-        HIP_CHECK(hipGetLastError());
-        PYMES_LAUNCH(gemv_finish_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, g.splitk_ws, (int)nchunk, C,
+        if (vec == 2) launch_kernel(gemv_cols_kernel<2>, dim3((unsigned)cblocks, (unsigned)nchunk), dim3(256), 0, st, W, ld, x, xs, R, C, rchunk, g.splitk_ws);
+        else launch_kernel(gemv_cols_kernel<1>, dim3((unsigned)cblocks, (unsigned)nchunk), dim3(256), 0, st, W, ld, x, xs, R, C, rchunk, g.splitk_ws);
+        launch_kernel(gemv_finish_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, g.splitk_ws, (int)nchunk, C,
                            g.alpha, g.beta, yin, g.C, ys);
     } else {
         const GemvRowsK rk{W, x, yin, g.C, ld, xs, R, C, ys, g.alpha, g.beta};
-        if (vec == 2) PYMES_LAUNCH(gemv_rows_kernel<2>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, rk);
-        else PYMES_LAUNCH(gemv_rows_kernel<1>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, rk);
+        if (vec == 2) launch_kernel(gemv_rows_kernel<2>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, rk);
+        else launch_kernel(gemv_rows_kernel<1>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, rk);
     }
-    HIP_CHECK(hipGetLastError());
     if (g_prof.on) {
-        HIP_CHECK(hipEventRecord(ev.second, st));
-        g_prof.ev.push_back(ev);
         const double fl = 2.0 * (double)g.M * (double)g.N * (double)g.K;
-        g_prof.flops += fl;
-        g_prof.fl.push_back(fl);
-        g_prof.klass.push_back(0);
-        g_prof.nk.push_back(1);
         char buf[256];
         snprintf(buf, sizeof buf, "M=%ld N=%ld K=%ld batch=1 gemv=%s vec=%d flops=%.4e", (long)g.M, (long)g.N, (long)g.K,
                  cols ? "cols" : "rows", vec, fl);
-        g_prof.what.push_back(buf);
+        span.finish(fl, 0, 1, buf);
     }
     return true;
 }
@@ -5927,11 +5807,9 @@ void triples_energy(const double* W, int64_t nt, int64_t t0, const double* Vijab
     const long npairs = (long)nv * (nv + 1) / 2;
     if (nt > 65535 || npairs > 0x7fffffffL) throw std::runtime_error("triples_energy: grid too large");
     hipStream_t st = (hipStream_t)s;
-    PYMES_LAUNCH(triples_orbit_kernel, dim3((unsigned)npairs, (unsigned)nt), dim3(64), 0, st, W, (long)t0, Vijab, t1, eps,
+    launch_kernel(triples_orbit_kernel, dim3((unsigned)npairs, (unsigned)nt), dim3(64), 0, st, W, (long)t0, Vijab, t1, eps,
                  partial, no, nv, npairs);
-    HIP_CHECK(hipGetLastError());
-    PYMES_LAUNCH(triples_sum_kernel, dim3((unsigned)nt), dim3(256), 0, st, (const double*)partial, (long)t0, npairs, out);
-    HIP_CHECK(hipGetLastError());
+    launch_kernel(triples_sum_kernel, dim3((unsigned)nt), dim3(256), 0, st, (const double*)partial, (long)t0, npairs, out);
 }
 
 }  // namespace dev
@@ -6086,13 +5964,11 @@ void fno_density(const double* Vijab, const double* eps_o, const double* eps_v, 
     if (p.ntp > 0x7fffffffL) throw std::runtime_error("fno_density: grid too large");
     double* epart = partial + p.nsplit * p.ntp * (kFnoT * kFnoT);
     hipStream_t st = (hipStream_t)s;
-    PYMES_LAUNCH(fno_density_kernel, dim3((unsigned)p.ntp, (unsigned)p.nsplit), dim3(256), 0, st, Vijab, eps_o, eps_v, no, nf,
+    launch_kernel(fno_density_kernel, dim3((unsigned)p.ntp, (unsigned)p.nsplit), dim3(256), 0, st, Vijab, eps_o, eps_v, no, nf,
                  nv, p.nt, p.nchunk, p.kc_per, p.kc_tot, partial, epart);
-    HIP_CHECK(hipGetLastError());
     const long nblk = ((long)nv * nv + 255) / 256;
-    PYMES_LAUNCH(fno_density_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, (const double*)partial,
+    launch_kernel(fno_density_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, (const double*)partial,
                  (const double*)epart, nv, p.nt, p.nsplit, D, e);
-    HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace dev

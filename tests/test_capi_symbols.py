@@ -36,3 +36,30 @@ def test_library_override(tmp_path):
     env = dict(os.environ, PYMES_AMD_LIBRARY=str(tmp_path / "other_build.so"), PYTHONPATH=ROOT)
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "refused" in out.stdout, out.stderr
+
+
+def test_unrecorded_stream_work_goes_through_the_ordered_layer():
+    """kernels.hip defers launches in the phase queue; whatever is not recorded there must launch the queue first.  The ten
+    runtime calls that do so are poisoned below their wrappers (the compiler refuses a bypass); a raw kernel launch cannot be
+    poisoned, so it is looked for here: only phase_flush (the flush itself) and try_launch_kernel may hold one, and nothing
+    above the poison but the wrappers may name a poisoned call."""
+    src = open(os.path.join(ROOT, "pymes_amd", "csrc", "kernels.hip")).read()
+    src = re.sub(r"//[^\n]*|/\*.*?\*/", "", src, flags=re.S)
+    assert not re.search(r"#\s*define\s+hip", src)
+    poisoned = re.findall(r"#pragma GCC poison ([^\n]+)", src)
+    names = " ".join(poisoned).split()
+    assert sorted(names) == sorted(["hipMemcpyAsync", "hipMemsetAsync", "hipMemcpy", "hipStreamSynchronize", "hipEventRecord",
+                                    "hipStreamWaitEvent", "hipGraphLaunch", "hipStreamBeginCapture", "hipStreamEndCapture",
+                                    "hipFree"])
+    above = src[:src.index("#pragma GCC poison")]
+    for name in names:
+        assert len(re.findall(r"\b%s\b" % name, above)) == 1, name         # its wrapper
+    # raw launches: split the file at the top-level function headers that may hold one
+    raw = r"hipLaunchKernelGGL|<<<|hipLaunchKernel\b|hipModuleLaunchKernel|hipExtLaunchKernel"
+    allowed = 0
+    for m in re.finditer(raw, src):
+        head = src[:m.start()]
+        owner = re.findall(r"\n(?:void|hipError_t) (\w+)\([^;{]*\) \{\n", head)[-1]
+        assert owner in ("phase_flush", "try_launch_kernel"), (owner, src[m.start():m.start() + 80])
+        allowed += 1
+    assert allowed == 3

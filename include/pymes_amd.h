@@ -610,6 +610,55 @@ int pymes_eom_diagonals(pymes_ctx* ctx, const double* f_host, const double* t2_d
 /* releases the engine's pooled scratch that is not in use (the temporaries / hoisted arrays of destroyed EOM handles) */
 int pymes_scratch_trim(pymes_ctx* ctx);
 int pymes_eom_sigma_destroy(pymes_eom* h);
+
+/* ---- IP- and EA-EOM-CCSD: ionisation and attachment energies (closed shell, doublet final states, right eigenvectors) ----------
+ * The operator is the EE sigma above restricted to the sector with one extra orbital x that interacts with nothing: with x a
+ * virtual, u1[x,i] = r1[i], u2[x,b,i,j] = u2[b,x,j,i] = r2[i,j,b] gives the IP operator plus eps_x; with x an occupied,
+ * u1[a,x] = r1[a], u2[a,b,x,j] = u2[b,a,j,x] = r2[a,b,j] gives the EA operator minus eps_x.  Eigenvalues: E(N-1) - E(N) (IP),
+ * E(N+1) - E(N) (EA).  With f the T1-dressed Fock matrix, V the T1-dressed blocks, t = T2 [a,b,i,j] and
+ *   L_oo[l,i] = f_li + (2 V_klcd - V_kldc) t_cdki,  L_vv[a,d] = f_ad - (2 V_klcd t_cakl - V_klcd t_ackl),  W_klij = V_klij + V_klcd t_cdij,
+ *   M1 = V_iabj[k,a,c,i] + V_klcd (2 t_caki - t_acki),  M_C = V_kldc t_caki,  M_D = V_kldc t_acki,  U = V_iajb[k,a,i,c]  as [(a,i),(d,l)],
+ *   PA = 2 M1 + M_D - 2 M_C - U,  PB = M_C - M1,  MDU = M_D - U,   rt = 2 r2 - (r2 with its first two indices exchanged):
+ * IP, r1[i], r2[i,j,b]:
+ *   s1[i]     = f_jb rt[i,j,b] - L_oo[k,i] r1[k] - V_ijka[j,k,i,b] rt[j,k,b]
+ *   s2[i,j,b] = -L_oo[l,i] r2[l,j,b] - L_oo[l,j] r2[i,l,b] + L_vv[b,d] r2[i,j,d] + W_klij r2[k,l,b] + t_cbij Y_c + A[l,i,j,b] r1[l]
+ *               + PA[(b,j),(d,l)] r2[i,l,d] + PB[(b,j),(d,l)] r2[l,i,d] + MDU[(b,i),(d,l)] r2[l,j,d] - (r1[l] V_iabc[l,b,c,d]) t_cdij
+ *   Y_c = -V_lkcd rt[l,k,d],   A[l,i,j,b] = -2 V_ijak[k,l,c,i] t_cbkj + V_ijka[k,l,i,c] t_cbkj + V_ijak[k,l,d,i] t_bdkj
+ *                                           + V_ijka[k,l,j,d] t_bdki - V_iajk[l,b,i,j] - f_lc t_cbij
+ * EA, r1[a], r2[a,b,j]:
+ *   s1[a]     = f_jb rt[a,b,j] + L_vv[a,b] r1[b] + V_iabc[j,a,b,c] rt[c,b,j]
+ *   s2[a,b,j] = L_vv[a,d] r2[d,b,j] + L_vv[b,c] r2[a,c,j] - L_oo[k,j] r2[a,b,k] + V_abcd r2[c,d,j]
+ *               + t_abkl (V_kldc r2[d,c,j] + V_ijka[l,k,j,d] r1[d]) - t_abkj (V_kldc rt[d,c,l] + f_kd r1[d])
+ *               + PA[(b,j),(d,l)] r2[a,d,l] + PB[(b,j),(d,l)] r2[d,a,l] + MDU[(a,j),(d,l)] r2[d,b,l]
+ *               + Q[k,a,c] (2 t_cbkj - t_bckj) - Q'[k,a,c] t_cbkj - Q'[k,b,c] t_ackj + V_abic[b,a,j,c] r1[c],
+ *   Q[k,a,c] = V_iabc[k,a,c,d] r1[d],  Q'[k,a,c] = V_iabc[k,a,d,c] r1[d]
+ * (the 7 + 32 terms per operator that the restriction of eom_ccsd.py:268-385 leaves, factorised).  The operator needs
+ * V_pqrs = V_qpsr on the blocks it reads and T_abij = T_baji: pymes_ipea_sigma_prepare tests both once and refuses, naming the
+ * missing symmetry.  Hermiticity is not needed (transcorrelated integrals).  Blocks read — IP: ijab iabj iajb ijka ijak iabc iajk
+ * klij (no abcd: works on an integral-sharded context); EA: ijab iabj iajb ijka iabc abic abcd (refuses a sharded context).
+ *   f_host   T1-dressed Fock matrix [n,n] (host);   t2_dev   CCSD doubles [v,v,o,o], alive and unchanged until _destroy
+ *   dressed  != 0: read the context's T1-dressed blocks (pymes_ccsd_dress_V), else the blocks as set
+ *   _flags       bit 0: kind, bit 1: dressed
+ *   _apply       sigma of k trial vectors (device): s1[z] [n1], s2[z] [n2]; n1 = o, n2 = o o v (IP) / n1 = v, n2 = v v o (EA).
+ *                All k vectors go through every product as one GEMM: each hoisted operand and integral block is read once
+ *   _diagonals   d1 = -L_ii (IP) / L_aa (EA);  d2 = L_bb - L_ii - L_jj (IP) / L_aa + L_bb - L_jj (EA)
+ *   _correction  n roots in one launch over flat vectors [r1 (n1) | zero pad | r2 (n2)] of len doubles, the doubles at off2, d in
+ *                the same layout: q_n = (s_n - w_n r_n) / (w_n - d + shift) written (zero in the pad), norms_host[2 n] =
+ *                |s_n - w_n r_n|^2, norms_host[2 n + 1] = |r_n|^2 (fixed summation order; ONE synchronisation)
+ * Every entry refuses a context that records a launch graph and a missing block by name; a refusal leaves no allocation behind.
+ * A handle dies with its context (pymes_ctx_destroy invalidates it; _destroy then frees its shell). */
+#define PYMES_IPEA_IP 0
+#define PYMES_IPEA_EA 1
+typedef struct pymes_ipea pymes_ipea;
+int pymes_ipea_sigma_prepare(pymes_ctx* ctx, const double* f_host, const double* t2_dev, int dressed, int kind, pymes_ipea** out);
+int pymes_ipea_sigma_flags(pymes_ipea* h, int* flags);
+int pymes_ipea_sigma_apply(pymes_ipea* h, int k, const double* const* r1_dev, const double* const* r2_dev, double* const* s1_dev,
+                           double* const* s2_dev);
+int pymes_ipea_sigma_diagonals(pymes_ipea* h, double* d1_dev, double* d2_dev);
+int pymes_ipea_sigma_correction(pymes_ipea* h, int n, const double* const* s_dev, const double* const* r_dev, const double* w_host,
+                                const double* d_dev, double shift, double* const* q_dev, int64_t off2, int64_t len,
+                                double* norms_host);
+int pymes_ipea_sigma_destroy(pymes_ipea* h);
 /* (mr + i mi)[e] = 1 / ((zr + i zi) - (hr + i hi) d[e] + shift), e < n: the FEAST preconditioner 1 / (z - diag + 0.01)
  * (feast_eom_ccsd.py:342; hs = 1j dt for the real-time form :276-278) from the device-resident diagonal */
 int pymes_cshift_inv(pymes_ctx* ctx, const double* d_dev, double zr, double zi, double hr, double hi, double shift,

@@ -167,6 +167,13 @@ SIGNATURES = {
     "pymes_eom_diagonals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pymes_scratch_trim": (C.c_int, [C.c_void_p]),
     "pymes_eom_sigma_destroy": (C.c_int, [C.c_void_p]),
+    "pymes_ipea_sigma_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "pymes_ipea_sigma_flags": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pymes_ipea_sigma_apply": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    "pymes_ipea_sigma_diagonals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pymes_ipea_sigma_correction": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                              C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "pymes_ipea_sigma_destroy": (C.c_int, [C.c_void_p]),
     "pymes_diis_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_pp, c_pp, c_i64_p, c_pp, c_pp]),
     "pymes_diis_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "pymes_diis_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_pp, c_pp, c_i64_p, C.c_int, C.c_int, C.c_int]),

@@ -26,6 +26,10 @@ struct pymes_eom {
     pymes::EomSigma* s;
     pymes_ctx* ctx;
 };
+struct pymes_ipea {
+    pymes::IpEaSigma* s;
+    pymes_ctx* ctx;
+};
 
 namespace {
 thread_local std::string g_err;
@@ -33,6 +37,7 @@ thread_local std::string g_err;
 // it (their hoisted arrays live in the engine's scratch pool); a later pymes_eom_sigma_destroy then only frees the host shell
 std::mutex g_eom_mu;
 std::set<pymes_eom*> g_eom_live;
+std::set<pymes_ipea*> g_ipea_live;          // (the IP / EA handles, same rule, same mutex)
 
 template <class F>
 int guarded(F&& f) {
@@ -71,6 +76,12 @@ pymes::EomSigma& S(pymes_eom* h) {
     E(h->ctx);                           // the context's device; queued grouped products first
     return *h->s;
 }
+pymes::IpEaSigma& SI(pymes_ipea* h, const char* who) {
+    if (!h || !h->s || !h->ctx) throw pymes::Error(std::string(who) + ": null or destroyed IP / EA handle");
+    Engine& e = E(h->ctx);
+    if (e.capturing()) throw pymes::Error(std::string(who) + " while a launch graph is being recorded");
+    return *h->s;
+}
 TView view_of(const double* p, const char* labels, const int64_t* dim, const int64_t* stride) {
     need(p, "tensor data");
     need(labels, "labels");
@@ -99,6 +110,13 @@ int pymes_ctx_destroy(pymes_ctx* ctx) {
             std::lock_guard<std::mutex> lock(g_eom_mu);
             for (pymes_eom* h : g_eom_live)
                 if (h->ctx == ctx) {                 // the handle outlives its context: invalidate it while the engine is alive
+                    if (ctx->e) dev::set_device(ctx->e->device);
+                    delete h->s;
+                    h->s = nullptr;
+                    h->ctx = nullptr;
+                }
+            for (pymes_ipea* h : g_ipea_live)
+                if (h->ctx == ctx) {
                     if (ctx->e) dev::set_device(ctx->e->device);
                     delete h->s;
                     h->s = nullptr;
@@ -980,6 +998,65 @@ int pymes_eom_sigma_destroy(pymes_eom* h) {
         {
             std::lock_guard<std::mutex> lock(g_eom_mu);
             g_eom_live.erase(h);
+        }
+        if (h->ctx && h->ctx->e) dev::set_device(h->ctx->e->device);
+        delete h->s;                         // (null when the context went first: pymes_ctx_destroy)
+        delete h;
+    });
+}
+
+// ---- IP- / EA-EOM-CCSD sigma (eom.cpp, IpEaSigma) -------------------------------------------------------------------------------
+int pymes_ipea_sigma_prepare(pymes_ctx* ctx, const double* f_host, const double* t2, int dressed, int kind, pymes_ipea** out) {
+    return guarded([&] {
+        need(out, "out");
+        *out = nullptr;
+        need(f_host, "f_host"); need(t2, "t2");
+        if (kind != PYMES_IPEA_IP && kind != PYMES_IPEA_EA) throw pymes::Error("ipea_sigma_prepare: kind must be PYMES_IPEA_IP or PYMES_IPEA_EA");
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("ipea_sigma_prepare while a launch graph is being recorded");
+        pymes::IpEaSigma* s = new pymes::IpEaSigma(e, kind == PYMES_IPEA_EA ? pymes::IpEaSigma::EA : pymes::IpEaSigma::IP, f_host,
+                                                   t2, dressed != 0);
+        *out = new pymes_ipea{s, ctx};
+        std::lock_guard<std::mutex> lock(g_eom_mu);
+        g_ipea_live.insert(*out);
+    });
+}
+int pymes_ipea_sigma_flags(pymes_ipea* h, int* flags) {
+    return guarded([&] {
+        need(flags, "flags");
+        *flags = SI(h, "ipea_sigma_flags").flags();
+    });
+}
+int pymes_ipea_sigma_apply(pymes_ipea* h, int k, const double* const* r1, const double* const* r2, double* const* s1,
+                           double* const* s2) {
+    return guarded([&] {
+        need(r1, "r1"); need(r2, "r2"); need(s1, "s1"); need(s2, "s2");
+        if (k < 0 || k > 4096) throw pymes::Error("ipea_sigma_apply: 0 <= k <= 4096");
+        for (int z = 0; z < k; ++z)
+            if (r2[z] == s2[z] || r1[z] == s1[z]) throw pymes::Error("ipea_sigma_apply: output aliases input");
+        SI(h, "ipea_sigma_apply").apply(k, r1, r2, s1, s2);
+    });
+}
+int pymes_ipea_sigma_diagonals(pymes_ipea* h, double* d1, double* d2) {
+    return guarded([&] {
+        need(d1, "d1"); need(d2, "d2");
+        SI(h, "ipea_sigma_diagonals").diagonals(d1, d2);
+    });
+}
+int pymes_ipea_sigma_correction(pymes_ipea* h, int n, const double* const* s, const double* const* r, const double* w_host,
+                                const double* d, double shift, double* const* q, int64_t off2, int64_t len, double* norms_host) {
+    return guarded([&] {
+        need(s, "s"); need(r, "r"); need(w_host, "w"); need(d, "d"); need(q, "q"); need(norms_host, "norms");
+        if (n < 0 || n > 4096) throw pymes::Error("ipea_sigma_correction: 0 <= n <= 4096");
+        SI(h, "ipea_sigma_correction").correction(n, s, r, w_host, d, shift, q, off2, len, norms_host);
+    });
+}
+int pymes_ipea_sigma_destroy(pymes_ipea* h) {
+    return guarded([&] {
+        if (!h) return;
+        {
+            std::lock_guard<std::mutex> lock(g_eom_mu);
+            g_ipea_live.erase(h);
         }
         if (h->ctx && h->ctx->e) dev::set_device(h->ctx->e->device);
         delete h->s;                         // (null when the context went first: pymes_ctx_destroy)

@@ -302,6 +302,28 @@ void ring_operands(const double* Viabj, const double* Viajb, double* M, double* 
 void pair_traces(const double* M, int64_t ld, double alpha, double beta, double* out_vv, double* out_oo, int no, int nv,
                  stream_t s, const double* M2 = nullptr, double alpha2 = 0.0);
 
+// ---- IP- / EA-EOM-CCSD (eom.cpp, IpEaSigma).  Doubles vectors r2[x,y,w], x, y < P, w < S (IP: P = no, S = nv;
+// EA: P = nv, S = no), k <= 16 vectors per call.  The product library only (the host simulator has no definition: weak ones in
+// the engine throw).
+// Operand packing, one pass over the k trial vectors: U1[z][n1] = r1_z;  R[z,x,y,w] = r2_z[x,y,w];  Rx[z,x,y,w] = r2_z[y,x,w];
+// Rt = 2 R - Rx;  Rn[x,y,z,w] = r2_z[x,y,w] (may be null) — every GEMM operand of one sigma build.
+void ipea_pack(int k, const double* const* r1, const double* const* r2, int P, int S, int n1, double* U1, double* R, double* Rx,
+               double* Rt, double* Rn, stream_t s);
+// Assembly, one pass over the partial results: s2_z[x,y,w] = D[z,x,y,w] + E[z,y,x,w] + L[x,y,z,w] (L may be null);
+// s1_z = S1[z][n1]
+void ipea_assemble(int k, const double* D, const double* E, const double* L, const double* S1, int P, int S, int n1,
+                   double* const* s1, double* const* s2, stream_t s);
+// Diagonals from L_oo [no,no] and L_vv [nv,nv] (only their diagonals are read).  kind 0 (IP): d1[i] = -L_ii,
+// d2[i,j,b] = L_bb - L_ii - L_jj;  kind 1 (EA): d1[a] = L_aa, d2[a,b,j] = L_aa + L_bb - L_jj
+void ipea_diagonals(const double* Loo, const double* Lvv, int kind, int no, int nv, double* d1, double* d2, stream_t s);
+// Davidson correction of n <= 16 roots in one launch over flat vectors of `len` doubles ([0,n1) singles, [n1,off2) pad,
+// [off2,len) doubles): q_n[e] = (s_n[e] - w[n] r_n[e]) / (w[n] - d[e] + shift), zero in the pad; out[2 n] = |s_n - w_n r_n|^2,
+// out[2 n + 1] = |r_n|^2, summed in a fixed order (block partials in ws, then one block), left in out_dev[2 n] (device) for
+// readback_start.  ws: ipea_correction_ws_doubles(n, len) doubles.
+int64_t ipea_correction_ws_doubles(int n, int64_t len);
+void ipea_correction(int n, const double* const* sv, const double* const* rv, const double* w_host, const double* d, double shift,
+                     double* const* q, int64_t n1, int64_t off2, int64_t len, double* ws, double* out_dev, stream_t s);
+
 // ---- Hartree-Fock matrix from the packed blocks (pymes/mean_field/hf.py:14-18); dir[tp*2+tq] = block (tp,o,tq,o),
 // exc[tp*2+tq] = block (tp,o,o,tq), tp/tq = 1 for a virtual index; h and f are [n,n] on the device
 void hf_fock(const double* const dir[4], const double* const exc[4], const double* h_dev, double* f_dev, int no, int nv,

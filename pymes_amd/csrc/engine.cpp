@@ -799,4 +799,21 @@ __attribute__((weak)) void fno_density(const double*, const double*, const doubl
                                        stream_t) {
     throw std::runtime_error("fno_density: not available in this backend");
 }
+// ... and without the IP- / EA-EOM-CCSD kernels
+__attribute__((weak)) void ipea_pack(int, const double* const*, const double* const*, int, int, int, double*, double*, double*,
+                                     double*, double*, stream_t) {
+    throw std::runtime_error("ipea_pack: not available in this backend");
+}
+__attribute__((weak)) void ipea_assemble(int, const double*, const double*, const double*, const double*, int, int, int,
+                                         double* const*, double* const*, stream_t) {
+    throw std::runtime_error("ipea_assemble: not available in this backend");
+}
+__attribute__((weak)) void ipea_diagonals(const double*, const double*, int, int, int, double*, double*, stream_t) {
+    throw std::runtime_error("ipea_diagonals: not available in this backend");
+}
+__attribute__((weak)) int64_t ipea_correction_ws_doubles(int, int64_t) { return 1; }
+__attribute__((weak)) void ipea_correction(int, const double* const*, const double* const*, const double*, const double*, double,
+                                           double* const*, int64_t, int64_t, int64_t, double*, double*, stream_t) {
+    throw std::runtime_error("ipea_correction: not available in this backend");
+}
 }  // namespace dev

@@ -617,4 +617,278 @@ void eom_diagonals(Engine& e, const double* f_host, const double* t2, bool dress
                        e.stream);
 }
 
+// ==== IP- / EA-EOM-CCSD (eom.h, IpEaSigma) =============================================================================
+// The 7 + 32 terms per operator that the EE sigma above leaves in the sector with one non-interacting orbital (tables in
+// include/pymes_amd.h), factorised.  With R[z,x,y,w] = r2_z[x,y,w], Rx its (x,y) transpose and Rt = 2 R - Rx every term lands
+// either in D[z,x,y,w] or in the transposed partial E[z,y,x,w]; the assembly kernel adds the two (and the abcd product of EA).
+double* IpEaSigma::keep(int64_t doubles) {
+    double* p = e.scratch_get(doubles);
+    owned_.push_back(p);
+    return p;
+}
+struct IpEaSigma::Tmp {
+    Engine& e;
+    double* p;
+    Tmp(IpEaSigma& s, int64_t n) : e(s.e), p(s.e.scratch_get(std::max<int64_t>(n, 1))) {}
+    ~Tmp() { e.scratch_put(p); }
+    Tmp(const Tmp&) = delete;
+    Tmp& operator=(const Tmp&) = delete;
+    operator double*() const { return p; }
+};
+
+TView IpEaSigma::V(const char* name) const { return e.block(pattern_of_name(name), dressed); }
+
+const std::vector<const char*>& IpEaSigma::blocks(Kind kind) {
+    static const std::vector<const char*> ip{"ijab", "iabj", "iajb", "ijka", "ijak", "iabc", "iajk", "klij"};
+    static const std::vector<const char*> ea{"ijab", "iabj", "iajb", "ijka", "iabc", "abic", "abcd"};
+    return kind == IP ? ip : ea;
+}
+
+IpEaSigma::~IpEaSigma() {
+    for (double* p : owned_) e.scratch_put(p);
+}
+
+IpEaSigma::IpEaSigma(Engine& eng, Kind kind_, const double* f_host, const double* t2, bool dressed_)
+    : e(eng), kind(kind_), no(eng.no), nv(eng.nv), dressed(dressed_), T(t2) {
+    if (!f_host || !t2) throw Error("ip/ea sigma: null Fock matrix / amplitudes");
+    const char* who = kind == IP ? "IP-EOM-CCSD sigma" : "EA-EOM-CCSD sigma";
+    if (kind == EA) e.refuse_if_sharded(who);
+    for (const char* name : blocks(kind))
+        if (!e.has_block(pattern_of_name(name), dressed))
+            throw Error(std::string(who) + ": the " + (dressed ? "dressed " : "") + "block '" + name + "' is missing");
+    // the symmetries the restricted operator needs (without them it is not even exchange-symmetric): once per prepare
+    auto asym = [&](const double* A, const double* B, int64_t d0, int64_t d1, int64_t d2, int64_t d3) {
+        const int64_t d[4] = {d0, d1, d2, d3};
+        double out[2] = {0.0, 0.0};
+        dev::exchange_asymmetry(A, B, d, out, e.stream);
+        return std::isfinite(out[1]) && out[0] <= 1e-12 * std::max(1.0, out[1]);
+    };
+    const int64_t o = no, v = nv;
+    bool v_ok = asym(V("ijab").p, V("ijab").p, o, o, v, v);
+    if (kind == IP) v_ok = v_ok && asym(V("klij").p, V("klij").p, o, o, o, o) && asym(V("ijka").p, V("ijak").p, o, o, o, v);
+    else v_ok = v_ok && asym(V("abcd").p, V("abcd").p, v, v, v, v);
+    if (!v_ok) throw Error(std::string(who) + ": the integrals lack the exchange symmetry V_pqrs = V_qpsr");
+    if (!asym(T, T, v, v, o, o)) throw Error(std::string(who) + ": the amplitudes lack the exchange symmetry T_abij = T_baji");
+    try {
+        hoist(f_host);
+    } catch (...) {
+        for (double* p : owned_) e.scratch_put(p);
+        owned_.clear();
+        throw;
+    }
+}
+
+void IpEaSigma::hoist(const double* f_host) {
+    const int64_t o = no, v = nv, n = o + v, ov = o * v, ov2 = ov * ov;
+    const Ops q{e};
+    std::vector<double> h(static_cast<size_t>(std::max(v * v, std::max(o * v, o * o))));
+    auto upload = [&](int64_t r0, int64_t nr, int64_t c0, int64_t nc, bool transposed = false) {
+        for (int64_t r = 0; r < nr; ++r)
+            for (int64_t c = 0; c < nc; ++c) h[transposed ? c * nr + r : r * nc + c] = f_host[(r0 + r) * n + c0 + c];
+        double* d = keep(nr * nc);
+        dev::memcpy_h2d(d, h.data(), sizeof(double) * nr * nc, e.stream);
+        dev::stream_sync(e.stream);            // (h is reused)
+        return d;
+    };
+    const TView Vijab = V("ijab"), Viabj = V("iabj"), Viajb = V("iajb"), Vijka = V("ijka");
+    const TView T4 = mv(T, {v, v, o, o});
+    // L_oo[l,i] = f_oo + (2 V_klcd - V_kldc) t_cdki,   L_vv[a,d] = f_vv - (2 V_klcd t_cakl - V_klcd t_ackl)
+    Loo = upload(0, o, 0, o);
+    Lvv = upload(o, v, o, v);
+    fov = upload(0, o, o, v);
+    fovT = upload(0, o, o, v, true);
+    q.C(2.0, Vijab, "klcd", T4, "cdki", 1.0, mv(Loo, {o, o}), "li");
+    q.C(-1.0, Vijab, "kldc", T4, "cdki", 1.0, mv(Loo, {o, o}), "li");
+    q.C(-2.0, Vijab, "klcd", T4, "cakl", 1.0, mv(Lvv, {v, v}), "ad");
+    q.C(1.0, Vijab, "klcd", T4, "ackl", 1.0, mv(Lvv, {v, v}), "ad");
+    // the (ov) x (ov) pair matrices of EomSigma (M1, M_C, M_D, U there), combined for the three products of one build:
+    //   PA = 2 M1 + M2 = 2 M1 + M_D - 2 M_C - U,   PB = M_C - M1,   MDU = M_D - U        as [(a,i),(d,l)]
+    PA = keep(ov2);
+    PB = keep(ov2);
+    MDU = keep(ov2);
+    auto P4 = [&](double* p) { return mv(p, {v, o, v, o}); };
+    {
+        Tmp M1(*this, ov2), MC(*this, ov2), MD(*this, ov2), Ud(*this, ov2);
+        {
+            Tmp Vd(*this, ov2), Vx(*this, ov2), Tdl(*this, ov2), Txl(*this, ov2), TAB(*this, ov2);
+            q.P(1.0, T4, "abij", 0.0, P4(Tdl), "aibj");
+            q.P(1.0, T4, "abij", 0.0, P4(Txl), "ajbi");
+            q.P(1.0, Vijab, "klcd", 0.0, P4(Vd), "ckdl");
+            q.P(1.0, Vijab, "klcd", 0.0, P4(Vx), "cldk");
+            q.P(2.0, P4(Tdl), "ckai", 0.0, P4(TAB), "aick");                     // 2 T[c,a,k,i] - T[a,c,k,i] as [(a,i),(c,k)]
+            q.P(-1.0, P4(Txl), "aick", 1.0, P4(TAB), "aick");
+            q.P(1.0, Viabj, "kaci", 0.0, P4(M1), "aick");
+            q.C(1.0, P4(TAB), "aick", P4(Vd), "ckdl", 1.0, P4(M1), "aidl");
+            q.C(1.0, P4(Tdl), "ckai", P4(Vx), "dlck", 0.0, P4(MC), "aidl");
+            q.C(1.0, P4(Txl), "aick", P4(Vx), "dlck", 0.0, P4(MD), "aidl");
+            q.P(1.0, Viajb, "kaic", 0.0, P4(Ud), "aick");
+        }
+        if (kind == EA) {
+            q.L(PA, {M1.p, MD.p, MC.p, Ud.p}, {2.0, 1.0, -2.0, -1.0}, ov2);
+            q.L(PB, {MC.p, M1.p}, {1.0, -1.0}, ov2);
+            q.L(MDU, {MD.p, Ud.p}, {1.0, -1.0}, ov2);
+        } else {                     // IP: pair index (i,a), the order of r2[.,i,a]
+            Tmp X(*this, ov2);
+            auto P4o = [&](double* p) { return mv(p, {o, v, o, v}); };
+            q.L(X, {M1.p, MD.p, MC.p, Ud.p}, {2.0, 1.0, -2.0, -1.0}, ov2);
+            q.P(1.0, P4(X), "aidl", 0.0, P4o(PA), "iald");
+            q.L(X, {MC.p, M1.p}, {1.0, -1.0}, ov2);
+            q.P(1.0, P4(X), "aidl", 0.0, P4o(PB), "iald");
+            q.L(X, {MD.p, Ud.p}, {1.0, -1.0}, ov2);
+            q.P(1.0, P4(X), "aidl", 0.0, P4o(MDU), "iald");
+        }
+    }
+    if (kind == IP) {
+        const TView Vijak = V("ijak"), Viajk = V("iajk"), Vklij = V("klij");
+        B2 = keep(o * o * o * o);                                               // W_klij = V_klij + V_klcd t_cdij
+        q.P(1.0, Vklij, "klij", 0.0, mv(B2, {o, o, o, o}), "klij");
+        q.C(1.0, Vijab, "klcd", T4, "cdij", 1.0, mv(B2, {o, o, o, o}), "klij");
+        // TA[(c | l),i,j,b]: rows c: t[c,b,i,j] (for Y_c, below); rows l: everything r1_l multiplies except the V_lacd.t term,
+        //   A[l,i,j,b] = (-2 V_klci t_cbkj + V_klic t_cbkj + V_kldi t_bdkj) + V_klid t_adkj|(j,b,i) - V_iajk[l,b,i,j] - f_lc t_cbij
+        TA = keep((v + o) * o * o * v);
+        const TView TAv = mv(TA, {v + o, o, o, v});
+        const TView At = slice(TAv, 0, 0, v), Al = slice(TAv, 0, v, v + o);
+        q.P(1.0, T4, "cbij", 0.0, At, "cijb");
+        Tmp A3(*this, o * o * v * o), A4(*this, o * o * v * o);
+        q.C(-2.0, Vijak, "klci", T4, "cbkj", 0.0, mv(A3, {o, o, v, o}), "libj");
+        q.C(1.0, Vijka, "klic", T4, "cbkj", 1.0, mv(A3, {o, o, v, o}), "libj");
+        q.C(1.0, Vijak, "kldi", T4, "bdkj", 1.0, mv(A3, {o, o, v, o}), "libj");
+        q.C(1.0, Vijka, "klid", T4, "adkj", 0.0, mv(A4, {o, o, v, o}), "liaj");
+        q.P(1.0, mv(A3, {o, o, v, o}), "libj", 0.0, Al, "lijb");
+        q.P(1.0, mv(A4, {o, o, v, o}), "ljbi", 1.0, Al, "lijb");
+        q.P(-1.0, Viajk, "lbij", 1.0, Al, "lijb");
+        q.C(-1.0, mv(fov, {o, v}), "lc", T4, "cbij", 1.0, Al, "lijb");
+        // BB[(l,k,d),(c | i)] = [-V_lkcd | -V_ijka[l,k,i,d]]: Y_c and the singles term from ONE pass over Rt
+        BB = keep(o * o * v * (v + o));
+        const TView BBv = mv(BB, {o, o, v, v + o});
+        q.P(-1.0, Vijab, "lkcd", 0.0, slice(BBv, 3, 0, v), "lkdc");
+        q.P(-1.0, Vijka, "lkid", 0.0, slice(BBv, 3, v, v + o), "lkdi");
+    } else {
+        // pair layouts of T on [(c,k),(b,j)]: Td = t[c,b,k,j], Tx = t[b,c,k,j], TT = 2 Td - Tx
+        Td = keep(ov2);
+        Tx = keep(ov2);
+        TT = keep(ov2);
+        q.P(1.0, T4, "cbkj", 0.0, P4(Td), "ckbj");
+        q.P(1.0, T4, "bckj", 0.0, P4(Tx), "ckbj");
+        q.L(TT, {Td, Tx}, {2.0, -1.0}, ov2);
+    }
+}
+
+int IpEaSigma::stack_limit() const {
+    const double free_b = static_cast<double>(dev::mem_free_bytes()) + static_cast<double>(e.scratch_free_bytes());
+    const double per_vector = 8.0 * (12.0 * static_cast<double>(n2()) + static_cast<double>(nv) * nv * nv);
+    return static_cast<int>(std::max(1.0, std::min(16.0, std::floor(free_b / 2.0 / std::max(per_vector, 1.0)))));
+}
+
+void IpEaSigma::apply(int k, const double* const* r1, const double* const* r2, double* const* s1, double* const* s2) {
+    if (k < 1) return;
+    for (int z = 0; z < k; ++z)
+        if (!r1[z] || !r2[z] || !s1[z] || !s2[z]) throw Error("ip/ea sigma: null vector");
+    const int step = stack_limit();
+    for (int lo = 0; lo < k; lo += step) {
+        const int g = std::min(k - lo, step);
+        if (kind == IP) apply_ip(g, r1 + lo, r2 + lo, s1 + lo, s2 + lo);
+        else apply_ea(g, r1 + lo, r2 + lo, s1 + lo, s2 + lo);
+    }
+}
+
+void IpEaSigma::apply_ip(int k, const double* const* r1, const double* const* r2, double* const* s1, double* const* s2) {
+    const int64_t o = no, v = nv, K = k, n2 = o * o * v;
+    const Ops q{e};
+    Tmp U1(*this, K * o), R(*this, K * n2), Rx(*this, K * n2), Rt(*this, K * n2), D(*this, K * n2), E(*this, K * n2),
+        S1(*this, K * o), YS(*this, K * (v + o)), XU(*this, K * (v + o)), Z(*this, K * v * v * v);
+    dev::ipea_pack(k, r1, r2, no, nv, no, U1, R, Rx, Rt, nullptr, e.stream);
+    const TView U1v = mv(U1, {K, o}), Rv = mv(R, {K, o, o, v}), Rxv = mv(Rx, {K, o, o, v}), Rtv = mv(Rt, {K, o, o, v}),
+                Dv = mv(D, {K, o, o, v}), Ev = mv(E, {K, o, o, v}), S1v = mv(S1, {K, o}), YSv = mv(YS, {K, v + o}),
+                XUv = mv(XU, {K, v + o}), Zv = mv(Z, {K, v, v, v});
+    const TView LooV = mv(Loo, {o, o}), LvvV = mv(Lvv, {v, v}), T4 = mv(T, {v, v, o, o});
+    // the ring-type terms: s2[j,i,a] += PA[(i,a),(l,d)] r2[j,l,d] + PB[(i,a),(l,d)] r2[l,j,d];  s2[j,i,a] += MDU[(j,a),(l,d)] r2[l,i,d]
+    q.C(1.0, Rv, "zjld", mv(PA, {o, v, o, v}), "iald", 0.0, Dv, "zjia");
+    q.C(1.0, Rxv, "zjld", mv(PB, {o, v, o, v}), "iald", 1.0, Dv, "zjia");
+    q.C(1.0, Rxv, "zild", mv(MDU, {o, v, o, v}), "jald", 0.0, Ev, "zija");
+    // Y_c = -V_lkcd (2 r2[l,k,d] - r2[k,l,d]) and the singles term -V_ijka[j,k,i,b] Rt[j,k,b] from one pass over Rt
+    q.C(1.0, Rtv, "zlkd", mv(BB, {o, o, v, v + o}), "lkdn", 0.0, YSv, "zn");
+    q.C(1.0, Rtv, "zijb", mv(fov, {o, v}), "jb", 0.0, S1v, "zi");
+    q.C(-1.0, U1v, "zk", LooV, "ki", 1.0, S1v, "zi");
+    e.axpby(1.0, slice(YSv, 1, v, v + o), 1.0, S1v);
+    // one-index dressings and the hole ladder
+    q.C(-1.0, LooV, "li", Rv, "zljb", 1.0, Dv, "zijb", "z");
+    q.C(-1.0, LooV, "lj", Rv, "zilb", 1.0, Dv, "zijb", "zi");
+    q.C(1.0, Rv, "zijd", LvvV, "bd", 1.0, Dv, "zijb");
+    q.C(1.0, mv(B2, {o, o, o, o}), "klij", Rv, "zklb", 1.0, Dv, "zijb", "z");
+    // D += [Y | r1] . [t ; A]
+    e.copy(slice(YSv, 1, 0, v), slice(XUv, 1, 0, v));
+    e.copy(U1v, slice(XUv, 1, v, v + o));
+    q.C(1.0, XUv, "zn", mv(TA, {v + o, o, o, v}), "nijb", 1.0, Dv, "zijb");
+    // -V_lacd t_cdji r1_l on the fly: (sum_l r1_l V_lacd) . t — no o^3 v block of it is stored
+    q.C(1.0, U1v, "zl", V("iabc"), "lacd", 0.0, Zv, "zacd");
+    q.C(-1.0, Zv, "zacd", T4, "cdji", 1.0, Ev, "zija");
+    dev::ipea_assemble(k, D, E, nullptr, S1, no, nv, no, s1, s2, e.stream);
+}
+
+void IpEaSigma::apply_ea(int k, const double* const* r1, const double* const* r2, double* const* s1, double* const* s2) {
+    const int64_t o = no, v = nv, K = k, n2 = v * v * o;
+    const Ops q{e};
+    Tmp U1(*this, K * v), R(*this, K * n2), Rx(*this, K * n2), Rt(*this, K * n2), Rn(*this, K * n2), D(*this, K * n2),
+        E(*this, K * n2), L(*this, K * n2), S1(*this, K * v), XX(*this, K * o * o * o), yy(*this, K * o), Q(*this, K * o * v * v),
+        Qp(*this, K * o * v * v);
+    dev::ipea_pack(k, r1, r2, nv, no, nv, U1, R, Rx, Rt, Rn, e.stream);
+    const TView U1v = mv(U1, {K, v}), Rv = mv(R, {K, v, v, o}), Rxv = mv(Rx, {K, v, v, o}), Rtv = mv(Rt, {K, v, v, o}),
+                Dv = mv(D, {K, v, v, o}), Ev = mv(E, {K, v, v, o}), S1v = mv(S1, {K, v}), XXv = mv(XX, {K, o, o, o}),
+                yyv = mv(yy, {K, o}), Qv = mv(Q, {K, o, v, v}), Qpv = mv(Qp, {o, v, v, K});
+    const TView LooV = mv(Loo, {o, o}), LvvV = mv(Lvv, {v, v}), T4 = mv(T, {v, v, o, o}), FOV = mv(fov, {o, v});
+    const TView Vijab = V("ijab"), Viabc = V("iabc");
+    auto P4 = [&](double* p) { return mv(p, {v, o, v, o}); };
+    // the ring-type terms: s2[b,a,i] += PA[(a,i),(d,l)] r2[b,d,l] + PB[(a,i),(d,l)] r2[d,b,l];  s2[b,a,i] += MDU[(b,i),(d,l)] r2[d,a,l]
+    q.C(1.0, Rv, "zbdl", P4(PA), "aidl", 0.0, Dv, "zbai");
+    q.C(1.0, Rxv, "zbdl", P4(PB), "aidl", 1.0, Dv, "zbai");
+    q.C(1.0, Rxv, "zadl", P4(MDU), "bidl", 0.0, Ev, "zabi");
+    // singles
+    q.C(1.0, Rtv, "zabj", mv(fovT, {v, o}), "bj", 0.0, S1v, "za");
+    q.C(1.0, U1v, "zb", LvvV, "ab", 1.0, S1v, "za");
+    q.C(1.0, Viabc, "jabc", Rtv, "zcbj", 1.0, S1v, "za");
+    // one-index dressings
+    q.C(1.0, LvvV, "ad", Rv, "zdbj", 1.0, Dv, "zabj", "z");
+    q.C(1.0, LvvV, "bc", Rv, "zacj", 1.0, Dv, "zabj", "za");
+    q.C(-1.0, Rv, "zabk", LooV, "kj", 1.0, Dv, "zabj");
+    // t[a,b,k,l] XX[k,l,j] + t[a,b,k,j] y_k:  XX = V_kldc r2[d,c,j] + V_ijka[l,k,j,d] r1_d,  y_k = -V_kldc Rt[d,c,l] - f_kd r1_d
+    q.C(1.0, Vijab, "kldc", Rv, "zdcj", 0.0, XXv, "zklj", "z");
+    q.C(1.0, V("ijka"), "lkjd", U1v, "zd", 1.0, XXv, "zklj");
+    q.C(-1.0, Vijab, "kldc", Rtv, "zdcl", 0.0, yyv, "zk");
+    q.C(-1.0, FOV, "kd", U1v, "zd", 1.0, yyv, "zk");
+    q.C(1.0, T4, "abkl", XXv, "zklj", 1.0, Dv, "zabj", "z");
+    q.C(1.0, T4, "abkj", yyv, "zk", 1.0, Dv, "zabj");
+    // the V_kacd t r1 terms on the fly: Q[k,a,c] = V_kacd r1_d, Q'[k,a,c] = V_kadc r1_d — no v^3 o block of them is stored
+    q.C(1.0, Viabc, "kacd", U1v, "zd", 0.0, Qv, "zkac");
+    q.C(1.0, Viabc, "kadc", U1v, "zd", 0.0, Qpv, "kacz", "ka");
+    q.C(1.0, Qv, "zkac", P4(TT), "ckbj", 1.0, Dv, "zabj");
+    q.C(-1.0, Qpv, "kacz", P4(Td), "ckbj", 1.0, Dv, "zabj");
+    q.C(-1.0, Qpv, "kbcz", P4(Tx), "ckaj", 1.0, Ev, "zbaj");
+    q.C(1.0, V("abic"), "bajc", U1v, "zc", 1.0, Ev, "zbaj");
+    // the particle ladder of all k vectors: ONE product over V_abcd, r2 in its natural [(c,d),(z,j)] layout
+    q.C(1.0, V("abcd"), "abcd", mv(Rn, {v, v, K, o}), "cdzj", 0.0, mv(L, {v, v, K, o}), "abzj");
+    dev::ipea_assemble(k, D, E, L, S1, nv, no, nv, s1, s2, e.stream);
+}
+
+void IpEaSigma::diagonals(double* d1, double* d2) {
+    if (!d1 || !d2) throw Error("ip/ea diagonals: null argument");
+    dev::ipea_diagonals(Loo, Lvv, kind == EA ? 1 : 0, no, nv, d1, d2, e.stream);
+}
+
+void IpEaSigma::correction(int n, const double* const* s, const double* const* r, const double* w_host, const double* d,
+                           double shift, double* const* q, int64_t off2, int64_t len, double* norms_host) {
+    if (n < 1) return;
+    if (!s || !r || !w_host || !d || !q || !norms_host) throw Error("ip/ea correction: null argument");
+    if (off2 < n1() || len != off2 + n2()) throw Error("ip/ea correction: the flat layout does not match the operator");
+    for (int z = 0; z < n; ++z)
+        if (!s[z] || !r[z] || !q[z]) throw Error("ip/ea correction: null vector");
+    for (int lo = 0; lo < n; lo += 16) {
+        const int g = std::min(16, n - lo);
+        Tmp ws(*this, dev::ipea_correction_ws_doubles(g, len)), out(*this, 32);
+        dev::ipea_correction(g, s + lo, r + lo, w_host + lo, d, shift, q + lo, n1(), off2, len, ws, out, e.stream);
+        const int slot = dev::readback_start(out, 2 * g, e.stream);
+        dev::readback_wait(slot, norms_host + 2 * lo, 2 * g);
+    }
+}
+
 }  // namespace pymes

@@ -59,4 +59,58 @@ class EomSigma {
 // dressed Fock matrix [n,n], t2 [v,v,o,o] on the device, blocks read dressed or as set
 void eom_diagonals(Engine& e, const double* f_host, const double* t2, bool dressed, double* d1, double* d2);
 
+// IP- and EA-EOM-CCSD sigma builds (formulas in include/pymes_amd.h): the EE operator above restricted to the sector
+// with one non-interacting orbital.  Vectors: IP r1[i], r2[i,j,b]; EA r1[a], r2[a,b,j] — below r2[x,y,w] with x, y over P
+// (no for IP, nv for EA) and w over S (nv for IP, no for EA).  Same life cycle as EomSigma: the constructor hoists what does
+// not depend on the trial vector, apply() builds sigma for k stacked vectors (every hoisted operand and every integral block
+// read once per call), diagonals() fills the preconditioner, correction() the Davidson expansion vectors of all roots.
+class IpEaSigma {
+  public:
+    enum Kind { IP = 0, EA = 1 };
+    // f_host: the T1-dressed Fock matrix [n,n] (host); t2: the CCSD doubles [v,v,o,o] (device; must outlive the object).
+    // Throws, naming the symmetry, unless V_pqrs = V_qpsr on the blocks read and T_abij = T_baji.
+    IpEaSigma(Engine& eng, Kind kind, const double* f_host, const double* t2, bool dressed);
+    ~IpEaSigma();
+    IpEaSigma(const IpEaSigma&) = delete;
+    IpEaSigma& operator=(const IpEaSigma&) = delete;
+
+    // the names of the dressed blocks the operator reads
+    static const std::vector<const char*>& blocks(Kind kind);
+    // bit 0: kind (0 IP, 1 EA); bit 1: the blocks are read dressed
+    int flags() const { return (kind == EA ? 1 : 0) | (dressed ? 2 : 0); }
+    int64_t n1() const { return kind == IP ? no : nv; }
+    int64_t n2() const { return kind == IP ? static_cast<int64_t>(no) * no * nv : static_cast<int64_t>(nv) * nv * no; }
+    // sigma for k trial vectors (device arrays): s1[z] [n1], s2[z] [n2] written
+    void apply(int k, const double* const* r1, const double* const* r2, double* const* s1, double* const* s2);
+    // d1 [n1] = -L_ii (IP) / L_aa (EA); d2 [n2] = L_bb - L_ii - L_jj (IP) / L_aa + L_bb - L_jj (EA): the dressed one-body part
+    void diagonals(double* d1, double* d2);
+    // For n roots (flat vectors of `len` doubles: [r1 (n1) | zero pad | r2 (n2)], the doubles part at `off2`; d the flat
+    // diagonals in the same layout): q_n = (s_n - w_n r_n) / (w_n - d + shift) written (zero in the pad) and
+    // norms[2 n] = |s_n - w_n r_n|^2, norms[2 n + 1] = |r_n|^2 returned (one synchronisation, fixed summation order)
+    void correction(int n, const double* const* s, const double* const* r, const double* w_host, const double* d, double shift,
+                    double* const* q, int64_t off2, int64_t len, double* norms_host);
+    Engine& engine() { return e; }
+    void trim() { e.scratch_trim(); }
+
+  private:
+    Engine& e;
+    const Kind kind;
+    const int no, nv;
+    const bool dressed;
+    const double* T;
+    std::vector<double*> owned_;
+    double* keep(int64_t doubles);
+    struct Tmp;
+    TView V(const char* name) const;
+    void hoist(const double* f_host);
+    void apply_ip(int k, const double* const* r1, const double* const* r2, double* const* s1, double* const* s2);
+    void apply_ea(int k, const double* const* r1, const double* const* r2, double* const* s1, double* const* s2);
+    int stack_limit() const;
+    // hoisted: L_oo [o,o], L_vv [v,v], f_ov [o,v] and its transpose; the (ov) x (ov) pair matrices PA = 2 M1 + M2,
+    // PB = M_C - M1, MDU = M_D - U (names of EomSigma), pair index (a,i) for EA and (i,a) for IP; IP: W_klij, TA [(c | l),i,j,b],
+    // BB [(l,k,d),(c | i)]; EA: the pair layouts of T
+    double *Loo = nullptr, *Lvv = nullptr, *fov = nullptr, *fovT = nullptr, *PA = nullptr, *PB = nullptr, *MDU = nullptr,
+           *B2 = nullptr, *TA = nullptr, *BB = nullptr, *TT = nullptr, *Td = nullptr, *Tx = nullptr;
+};
+
 }  // namespace pymes

@@ -5972,3 +5972,229 @@ void fno_density(const double* Vijab, const double* eps_o, const double* eps_v, 
 }
 
 }  // namespace dev
+
+// ==== IP- / EA-EOM-CCSD (device_api.h; eom.cpp, IpEaSigma) ==============================================================
+namespace {
+
+constexpr int kIpeaMax = 16;
+struct IpeaIn {          // the k <= 16 vectors of one call, by value
+    const double* a[kIpeaMax];
+    const double* b[kIpeaMax];
+};
+struct IpeaOut {
+    double* a[kIpeaMax];
+    double* b[kIpeaMax];
+};
+
+// Operand packing: block (bx, y, z) handles the plane y of vector z and a tile of 8 x by 32 w.  The direct element r2[x,y,w]
+// and its exchange partner r2[y,x,w] are both read along w (rows of S doubles) and every output is written along w, so both
+// sides are coalesced without a transposing stage; the LDS tile only carries the partner rows so that each is read once for
+// the two outputs that need it.  in.a = r1_z, in.b = r2_z.
+__global__ void __launch_bounds__(256) ipea_pack_kernel(IpeaIn in, int P, int S, int n1, int k, double* __restrict__ U1,
+                                                        double* __restrict__ R, double* __restrict__ Rx, double* __restrict__ Rt,
+                                                        double* __restrict__ Rn) {
+    __shared__ double sB[8][33];
+    const int z = blockIdx.z, y = blockIdx.y;
+    const int nwt = (S + 31) / 32;
+    const int xt = blockIdx.x / nwt, wt = blockIdx.x - xt * nwt;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int x = xt * 8 + ty, w = wt * 32 + tx;
+    const double* __restrict__ r2 = in.b[z];
+    const long PS = (long)P * S, n2 = PS * P;
+    const bool ok = x < P && w < S;
+    double a = 0.0;
+    if (ok) {
+        a = r2[(long)x * PS + (long)y * S + w];
+        sB[ty][tx] = r2[(long)y * PS + (long)x * S + w];
+    }
+    __syncthreads();
+    if (ok) {
+        const double b = sB[ty][tx];
+        const long o = (long)z * n2 + (long)x * PS + (long)y * S + w;
+        R[o] = a;
+        Rx[o] = b;
+        Rt[o] = 2.0 * a - b;
+        if (Rn) Rn[((long)x * P + y) * ((long)k * S) + (long)z * S + w] = a;
+    }
+    if (blockIdx.x == 0 && y == 0) {
+        const double* __restrict__ r1 = in.a[z];
+        for (int p = threadIdx.x; p < n1; p += 256) U1[(long)z * n1 + p] = r1[p];
+    }
+}
+
+// Assembly: s2_z[x,y,w] = D[z,x,y,w] + E[z,y,x,w] + L[x,y,z,w]; all three read along w.  out.a = s1_z, out.b = s2_z.
+__global__ void __launch_bounds__(256) ipea_assemble_kernel(IpeaOut out, int P, int S, int n1, int k, const double* __restrict__ D,
+                                                            const double* __restrict__ E, const double* __restrict__ L,
+                                                            const double* __restrict__ S1) {
+    const int z = blockIdx.z, y = blockIdx.y;
+    const int nwt = (S + 31) / 32;
+    const int xt = blockIdx.x / nwt, wt = blockIdx.x - xt * nwt;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int x = xt * 8 + ty, w = wt * 32 + tx;
+    const long PS = (long)P * S, n2 = PS * P;
+    if (x < P && w < S) {
+        const long o = (long)x * PS + (long)y * S + w;
+        double s = D[(long)z * n2 + o] + E[(long)z * n2 + (long)y * PS + (long)x * S + w];
+        if (L) s += L[((long)x * P + y) * ((long)k * S) + (long)z * S + w];
+        out.b[z][o] = s;
+    }
+    if (blockIdx.x == 0 && y == 0) {
+        double* __restrict__ s1 = out.a[z];
+        for (int p = threadIdx.x; p < n1; p += 256) s1[p] = S1[(long)z * n1 + p];
+    }
+}
+
+__global__ void __launch_bounds__(256) ipea_diagonals_kernel(const double* __restrict__ Loo, const double* __restrict__ Lvv, int kind,
+                                                             int no, int nv, double* __restrict__ d1, double* __restrict__ d2,
+                                                             long total) {
+    const int P = kind ? nv : no, S = kind ? no : nv;
+    const double* __restrict__ LP = kind ? Lvv : Loo;
+    const double* __restrict__ LS = kind ? Loo : Lvv;
+    const double sp = kind ? 1.0 : -1.0;        // IP: L_bb - L_ii - L_jj;  EA: L_aa + L_bb - L_jj
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int w = (int)(idx % S);
+        const long xy = idx / S;
+        const int y = (int)(xy % P), x = (int)(xy / P);
+        d2[idx] = sp * (LP[(long)x * (P + 1)] + LP[(long)y * (P + 1)]) - sp * LS[(long)w * (S + 1)];
+        if (idx < P) d1[idx] = sp * LP[idx * (P + 1)];
+    }
+}
+
+// Davidson correction, stage 1: block (bx, n) owns the elements [bx * kIpeaChunk, (bx + 1) * kIpeaChunk) of root n; its threads
+// stride through them, then the 256 partial sums are added pairwise in a fixed tree.  in.a = s_n, in.b = r_n, out.a = q_n.
+constexpr long kIpeaChunk = 256 * 16;
+struct IpeaW {
+    double w[kIpeaMax];
+};
+__global__ void __launch_bounds__(256) ipea_correction_kernel(IpeaIn in, IpeaOut out, IpeaW ww, const double* __restrict__ d,
+                                                              double shift, long n1, long off2, long len, long nblk,
+                                                              double* __restrict__ ws) {
+    __shared__ double sr[256], sn[256];
+    const int n = blockIdx.y, t = threadIdx.x;
+    const double* __restrict__ s = in.a[n];
+    const double* __restrict__ r = in.b[n];
+    double* __restrict__ q = out.a[n];
+    const double w = ww.w[n];
+    const long e0 = (long)blockIdx.x * kIpeaChunk, e1 = min(len, e0 + kIpeaChunk);
+    double res = 0.0, nrm = 0.0;
+    for (long e = e0 + t; e < e1; e += 256) {
+        if (e >= n1 && e < off2) {
+            q[e] = 0.0;
+            continue;
+        }
+        const double re = r[e], x = s[e] - w * re;
+        res += x * x;
+        nrm += re * re;
+        q[e] = x / (w - d[e] + shift);
+    }
+    sr[t] = res;
+    sn[t] = nrm;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) {
+            sr[t] += sr[t + h];
+            sn[t] += sn[t + h];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        ws[((long)n * nblk + blockIdx.x) * 2] = sr[0];
+        ws[((long)n * nblk + blockIdx.x) * 2 + 1] = sn[0];
+    }
+}
+// stage 2: one block per root; thread t sums the block partials t, t + 256, ... in order, then the same fixed tree
+__global__ void __launch_bounds__(256) ipea_correction_final_kernel(const double* __restrict__ ws, long nblk, double* __restrict__ out) {
+    __shared__ double sr[256], sn[256];
+    const int n = blockIdx.x, t = threadIdx.x;
+    double res = 0.0, nrm = 0.0;
+    for (long b = t; b < nblk; b += 256) {
+        res += ws[((long)n * nblk + b) * 2];
+        nrm += ws[((long)n * nblk + b) * 2 + 1];
+    }
+    sr[t] = res;
+    sn[t] = nrm;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) {
+            sr[t] += sr[t + h];
+            sn[t] += sn[t + h];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out[2 * n] = sr[0];
+        out[2 * n + 1] = sn[0];
+    }
+}
+
+void ipea_check(const char* who, int k, int P, int S) {
+    if (k < 1 || k > kIpeaMax) throw std::runtime_error(std::string(who) + ": 1 <= k <= 16 vectors per call");
+    if (P < 1 || S < 1 || P > 65535) throw std::runtime_error(std::string(who) + ": bad shape");
+    const long nx = (long)((P + 7) / 8) * ((S + 31) / 32);
+    if (nx > 0x7fffffffL) throw std::runtime_error(std::string(who) + ": grid too large");
+}
+
+}  // namespace
+
+namespace dev {
+
+void ipea_pack(int k, const double* const* r1, const double* const* r2, int P, int S, int n1, double* U1, double* R, double* Rx,
+               double* Rt, double* Rn, stream_t s) {
+    ipea_check("ipea_pack", k, P, S);
+    if (!r1 || !r2 || !U1 || !R || !Rx || !Rt) throw std::runtime_error("ipea_pack: null operand");
+    IpeaIn in{};
+    for (int z = 0; z < k; ++z) {
+        in.a[z] = r1[z];
+        in.b[z] = r2[z];
+    }
+    const unsigned nx = (unsigned)(((P + 7) / 8) * ((S + 31) / 32));
+    launch_kernel(ipea_pack_kernel, dim3(nx, (unsigned)P, (unsigned)k), dim3(256), 0, (hipStream_t)s, in, P, S, n1, k, U1, R, Rx, Rt,
+                  Rn);
+}
+
+void ipea_assemble(int k, const double* D, const double* E, const double* L, const double* S1, int P, int S, int n1,
+                   double* const* s1, double* const* s2, stream_t s) {
+    ipea_check("ipea_assemble", k, P, S);
+    if (!D || !E || !S1 || !s1 || !s2) throw std::runtime_error("ipea_assemble: null operand");
+    IpeaOut out{};
+    for (int z = 0; z < k; ++z) {
+        out.a[z] = s1[z];
+        out.b[z] = s2[z];
+    }
+    const unsigned nx = (unsigned)(((P + 7) / 8) * ((S + 31) / 32));
+    launch_kernel(ipea_assemble_kernel, dim3(nx, (unsigned)P, (unsigned)k), dim3(256), 0, (hipStream_t)s, out, P, S, n1, k, D, E, L,
+                  S1);
+}
+
+void ipea_diagonals(const double* Loo, const double* Lvv, int kind, int no, int nv, double* d1, double* d2, stream_t s) {
+    if (!Loo || !Lvv || !d1 || !d2 || no < 1 || nv < 1) throw std::runtime_error("ipea_diagonals: bad argument");
+    const long total = kind ? (long)nv * nv * no : (long)no * no * nv;
+    launch_kernel(ipea_diagonals_kernel, dim3(grid_for(total, 256, 256 * 64)), dim3(256), 0, (hipStream_t)s, Loo, Lvv, kind, no, nv,
+                  d1, d2, total);
+}
+
+int64_t ipea_correction_ws_doubles(int n, int64_t len) { return 2 * (int64_t)n * ((len + kIpeaChunk - 1) / kIpeaChunk); }
+
+void ipea_correction(int n, const double* const* sv, const double* const* rv, const double* w_host, const double* d, double shift,
+                     double* const* q, int64_t n1, int64_t off2, int64_t len, double* ws, double* out_dev, stream_t s) {
+    if (n < 1 || n > kIpeaMax) throw std::runtime_error("ipea_correction: 1 <= n <= 16 roots per call");
+    if (!sv || !rv || !w_host || !d || !q || !ws || !out_dev || len < 1 || n1 < 0 || off2 < n1 || off2 > len)
+        throw std::runtime_error("ipea_correction: bad argument");
+    const long nblk = (long)((len + kIpeaChunk - 1) / kIpeaChunk);
+    if (nblk > 0x7fffffffL) throw std::runtime_error("ipea_correction: grid too large");
+    IpeaIn in{};
+    IpeaOut out{};
+    IpeaW ww{};
+    for (int z = 0; z < n; ++z) {
+        in.a[z] = sv[z];
+        in.b[z] = rv[z];
+        out.a[z] = q[z];
+        ww.w[z] = w_host[z];
+    }
+    hipStream_t st = (hipStream_t)s;
+    launch_kernel(ipea_correction_kernel, dim3((unsigned)nblk, (unsigned)n), dim3(256), 0, st, in, out, ww, d, shift, (long)n1,
+                  (long)off2, (long)len, nblk, ws);
+    launch_kernel(ipea_correction_final_kernel, dim3((unsigned)n), dim3(256), 0, st, (const double*)ws, nblk, out_dev);
+}
+
+}  // namespace dev

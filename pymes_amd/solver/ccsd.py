@@ -493,6 +493,12 @@ class CCSD(ccd.CCD):
             if self.is_dcd:
                 raise ValueError("triples=True: (T) is defined for CCSD amplitudes, not for DCSD")
             ccsd_t.check_canonical(self.no, t_fock_pq, kwargs.get("canonical_tol", 1e-6))
+        # ip_roots=k / ea_roots=m (opt-in): the k lowest ionisation potentials / m lowest electron affinities of the converged
+        # state (pymes_amd/solver/eom_ip_ea.py); with frozen_core / fno_* they are those of the correlated space
+        # (ip_ea_r_epsilon=x: the relative residual norm at which both Davidson runs stop, default 1e-6)
+        ip_roots, ea_roots = int(kwargs.get("ip_roots", 0) or 0), int(kwargs.get("ea_roots", 0) or 0)
+        if (ip_roots or ea_roots) and self.is_dcd:
+            raise ValueError("ip_roots / ea_roots: the IP / EA operators are the CCSD similarity transform, not defined for DCSD")
         ints, own = self._integrals(t_fock_pq, t_V_pqrs)
         ctx = ints.ctx
         st = None
@@ -542,6 +548,10 @@ class CCSD(ccd.CCD):
                 e_t = ccsd_t.get_triples_energy(self.no, t_fock_pq, ints, st["t1"], st["t2"],
                                                 canonical_tol=kwargs.get("canonical_tol", 1e-6))
                 print_logging_info("(T) correction = {:.12f} ({:.3f} seconds)".format(e_t, time.time() - time_t), level=1)
+            e_ip = e_ea = None
+            if ip_roots or ea_roots:
+                e_ip, e_ea = self._ip_ea_roots(t_fock_pq, ints, st["t1"], st["t2"], ip_roots, ea_roots,
+                                               kwargs.get("ip_ea_r_epsilon"))
             if kwargs.get("device_amplitudes"):
                 # device-resident hand-over to the callers of the solution (EOM-CCSD / FEAST: get_T1_dressed_V on the same
                 # DeviceIntegrals, EOM_CCSD.solve on the result): "t1" / "t2" are DeviceArrays of the integrals' context —
@@ -563,6 +573,12 @@ class CCSD(ccd.CCD):
             if triples:
                 res["(t) e"] = e_t
                 res["ccsd(t) e"] = e_ccsd + e_t
+            if e_ip is not None:
+                res["ip e"] = e_ip
+            if e_ea is not None:
+                res["ea e"] = e_ea
+            if e_ip is not None and e_ea is not None:
+                res["qp gap"] = float(e_ip[0] + e_ea[0])      # the quasi-particle gap: lowest IP + lowest EA
             return res
         finally:
             collector.__exit__()
@@ -570,6 +586,29 @@ class CCSD(ccd.CCD):
                 ctx.close()      # (a DIIS history kept in this context is parked on the host on the way: Context.on_close)
             elif ctx.handle:
                 ccd.destroy_graphs(ctx, st)
+
+    def _ip_ea_roots(self, t_fock_pq, ints, t1, t2, ip_roots, ea_roots, r_epsilon=None):
+        """The lowest IP / EA roots of the converged amplitudes on the integrals' context (device hand-over: the Fock matrix
+        and the blocks each operator reads are T1-dressed in HBM; a sharded context is never asked to dress abcd)."""
+        from pymes_amd.solver.eom_ip_ea import EA_EOM_CCSD, IP_EOM_CCSD
+        f = t_fock_pq.get() if isinstance(t_fock_pq, DeviceArray) else np.asarray(t_fock_pq, dtype=np.float64)
+        fd = self.get_T1_dressed_fock(f, t1, ints)
+        out = []
+        for cls, n_roots in ((IP_EOM_CCSD, ip_roots), (EA_EOM_CCSD, ea_roots)):
+            if not n_roots:
+                out.append(None)
+                continue
+            solver = cls(self.no, n_roots=n_roots, device=self.device)
+            if r_epsilon is not None:                    # (ip_ea_r_epsilon=: the stopping test of both solvers)
+                solver.r_epsilon = float(r_epsilon)
+            solver.check_context(ints.ctx)               # (EA: refuses a sharded context before anything is dressed)
+            dressed = self.get_T1_dressed_V(t1, ints, solver.BLOCKS)
+            out.append(np.array(solver.solve(fd, dressed, t2)))
+            if cls is IP_EOM_CCSD:
+                self.ip_solver = solver                  # (residual norms, singles weights, history of the last solve)
+            else:
+                self.ea_solver = solver
+        return out
 
     def _solve_fno(self, t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv, **kwargs):
         from pymes_amd.solver import fno

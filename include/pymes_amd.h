@@ -313,7 +313,12 @@ int pymes_residual_slab(pymes_ctx* ctx, const double* f_dev, const double* t2_de
 /* P_dev (optional, amplitude-side mode only): the slab's small replicated intermediates — w Tt_cdil V_lkdc (the V.T part
  * of X_ki, ccd.py:215-220) and the pair-packed 2 V_klcd T_cdij of the hole ladder (:180) — as produced by
  * pymes_slab_prepare (every rank sums over its chunk of c / of the pairs (c,d)) and all-reduced by the caller;
- * pymes_slab_prepare_ws doubles.  NULL: the slab forms them itself. */
+ * pymes_slab_prepare_ws doubles.  NULL: the slab forms them itself.
+ * One rank with all columns and P_dev == NULL: the rows of ETd / ETx also carry X_ac T_cbij - X_ki T_abkj (ccd.py:231-232),
+ * added through the operands of the ring products; the context remembers (t2_dev, ETd_dev) until its next
+ * pymes_residual_slab call that does not skip the rings, and pymes_residual_finish[_pairs] ON THE SAME CONTEXT with that
+ * t2_dev and that ETd_dev does not add X_ac T again.  Such rows must be finished by the context that made them
+ * (PYMES_RING_FOLD=0: the separate products, rows as before). */
 int pymes_slab_prepare_ws(pymes_ctx* ctx, int64_t* n_doubles);
 int pymes_slab_prepare(pymes_ctx* ctx, const double* t2_dev, double* P_dev, int rank, int world, uint32_t flags);
 int pymes_residual_finish(pymes_ctx* ctx, const double* f_dev, const double* t2_dev, const double* ETd_dev,

@@ -232,20 +232,28 @@ void Engine::ensure_xs() {
     if (!xs_vv_) xs_vv_ = static_cast<double*>(dev::dmalloc(sizeof(double) * nv * nv));
 }
 
+bool Engine::ring_fold_enabled() {
+    if (const char* e = getenv("PYMES_RING_FOLD")) return atoi(e) != 0;
+    return true;
+}
+
 // The three pair layouts of T2 (Td, Tx, Tt_d) in the engine's persistent buffers
-void Engine::pair_layouts_of(const double* t2) {
+void Engine::pair_layouts_of(const double* t2, bool want_td) {
     const int64_t o = no, v = nv, ov = o * v;
-    for (auto& p : lay_)
-        if (!p) p = static_cast<double*>(dev::dmalloc(sizeof(double) * ov * ov));
+    for (int i = want_td ? 0 : 1; i < 3; ++i)
+        if (!lay_[i]) {
+            if (capturing_) throw Error("pair_layouts_of: the pair layouts must exist before a launch graph is recorded (run one eager pass first)");
+            lay_[i] = static_cast<double*>(dev::dmalloc(sizeof(double) * ov * ov));
+        }
     lay_t2_ = nullptr;
     if (dev::fused_pair_kernels_ok(no)) {
-        dev::t2_layouts(t2, lay_[0], lay_[1], lay_[2], no, nv, stream);
+        dev::t2_layouts(t2, want_td ? lay_[0] : nullptr, lay_[1], lay_[2], no, nv, stream);
         stats.permute_calls++;
-        stats.permute_bytes += 8.0 * 5.0 * double(ov * ov);
+        stats.permute_bytes += 8.0 * (want_td ? 5.0 : 4.0) * double(ov * ov);      // T twice, two or three layouts out
     } else {
         TView T = make_view(const_cast<double*>(t2), {v, v, o, o});
         TView t4 = make_view(lay_[0], {v, o, v, o});
-        permute(1.0, T, "abij", 0.0, t4, "aibj");
+        if (want_td) permute(1.0, T, "abij", 0.0, t4, "aibj");
         t4.p = lay_[1];
         permute(1.0, T, "abij", 0.0, t4, "ajbi");
         t4.p = lay_[2];
@@ -283,6 +291,7 @@ void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, dou
         }
     }
     if (skip_rings) return;
+    ring_fold_.clear();            // whatever this call writes into ETd / ETx, an earlier folded slab is no longer what they hold
     int64_t c0, c1;
     chunk(ov, c0, c1);
     const int64_t nc = c1 - c0;
@@ -292,7 +301,16 @@ void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, dou
     ArenaScope scope(arena);
     auto pairm = [&](double* p) { return make_view(p, {ov, ov}); };
     auto slab = [&]() { return make_view(arena.alloc(ov * nc), {ov, nc}); };
-    pair_layouts_of(t2);
+    // Ring fold (one rank, all columns, the V.T sums as traces of the builds): X_ac and X_ki are complete before the two
+    // applications, and with the sparse pair matrix  Dx[(c,k),(b,j)] = X_bc d_kj - d_cb X_kj
+    //     M -> M + Dx / 2,  N1 -> N1 + Dx / 2     (paired form: M_h = M / 2 -> M_h + Dx / 4)
+    // the assembly Ex_d + Ex_d^T + Ex_x(ajbi) + Ex_x(biaj) gains exactly X_ac T_cbij + X_bc T_acij - X_ki T_abkj - X_kj T_abik
+    // (ccd.py:231-232 after symmetrisation; the unwanted index placements of the two halves cancel, which needs the equal
+    // weights).  v^2 o + v o^2 entries per operand instead of two streaming products over (ov)^2 arrays: no X_ki product,
+    // no Td, and the finish does not form X_ac T (ring_fold_).  tests/test_ring_fold.py pins the identity.
+    const bool traces = !P && nc == ov;      // the small V.T sums as partial traces of the builds (below; one rank only)
+    const bool fold = traces && ring_fold_enabled();
+    pair_layouts_of(t2, !fold);
     TView Td = pairm(lay_[0]), Tx = pairm(lay_[1]), Ttd = pairm(lay_[2]);
     TView ETd = slice(pairm(ETd_p), 0, c0, c1), ETx = slice(pairm(ETx_p), 0, c0, c1);
     auto cols = [&](const TView& m) { return slice(m, 1, c0, c1); };
@@ -320,7 +338,6 @@ void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, dou
     // golden solve pins the result).  DCSD keeps ccd.py:202-204 only: 2 Wd - Ud^T + Vd Tt_d in the D-term, no build in the
     // C-term.  Column slab [c0,c1): both builds are restricted to the rank's columns n, the applications give rows n.
     const bool row_form = nc != ov;
-    const bool traces = !P && nc == ov;      // the small V.T sums as partial traces of the builds (below; one rank only)
     if (row_form) {
         // Several ranks: the slab in its TRANSPOSED form from the start.  MT[(b,j),(c,k)] / N1T hold the rank's columns as
         // ROWS; Tt_d, Tx, Ld, Vx, Vd are symmetric pair matrices, so
@@ -424,6 +441,25 @@ void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, dou
         xs_oo_tag_.set(t2, 0, 1);
         xs_vv_tag_.set(t2, 0, 1);
     }
+    if (fold) {
+        // X_ki = f_ki + w S_ki (:215-220), X_ac = f_ac - w S_ac (:206-212), then Dx into both operands as two strided
+        // accumulations each: m[(c,k),(b,k)] += wgt X_bc (X broadcast along k) and m[(c,k),(c,j)] -= wgt X_kj (along c)
+        TView Xoo = make_view(arena.alloc(o * o), {o, o}), Xvv = make_view(arena.alloc(v * v), {v, v});
+        copy(slice(slice(F, 0, 0, o), 1, 0, o), Xoo);
+        axpby(w, make_view(xs_oo_, {o, o}), 1.0, Xoo);
+        copy(slice(slice(F, 0, o, nn), 1, o, nn), Xvv);
+        axpby(-w, make_view(xs_vv_, {v, v}), 1.0, Xvv);
+        auto add_Dx = [&](const TView& m, double wgt) {
+            const int64_t ld = m.st[0];
+            const int64_t dv[3] = {v, v, o}, sv_in[3] = {1, v, 0}, sv_out[3] = {o * ld, o, ld + 1};            // (c, b, k)
+            axpby(wgt, make_view(Xvv.p, 3, dv, sv_in), 1.0, make_view(m.p, 3, dv, sv_out));
+            const int64_t dn[3] = {v, o, o}, so_in[3] = {0, o, 1}, so_out[3] = {o * ld + o, ld, 1};           // (c, k, j)
+            axpby(-wgt, make_view(Xoo.p, 3, dn, so_in), 1.0, make_view(m.p, 3, dn, so_out));
+        };
+        add_Dx(M, paired ? 0.25 : 0.5);
+        add_Dx(N1, 0.5);
+        ring_fold_.set(t2, ETd_p);
+    }
     if (paired) {
         pair_gemm(1.0, Tx.p, Ttd.p, N1.p, M.p, 0.0, ETx.p, ETd.p);                           // Ex_x = -Xc,  D = Tt_d M_h
     } else if (nc == ov) {
@@ -438,7 +474,7 @@ void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, dou
         contract(0.5, M, "kn", Ttd, "mk", 0.5, ETd, "nm", "", &ETx);                         // (Ex_d)^T
     }
     }
-    {
+    if (!fold) {
         // :232  Ex[a,b,i,j] -= X_ki T[a,b,k,j]  ->  ET[(b,j),(a,i)] -= sum_k Td[(b,j),(a,k)] X_ki   (Td symmetric)
         ArenaScope s2(arena);
         TView Foo = slice(slice(F, 0, 0, o), 1, 0, o);
@@ -555,30 +591,40 @@ void Engine::residual_finish(const double* f, const double* t2, const double* ET
     // X_ac = f_ac - w sum Tt[a,d,k,l] V[l,k,d,c]  (:206-221);  Ex += X_ac T[c,b,i,j]  (:231)
     const bool reuse = (flags & PYMES_REUSE_LAYOUTS) && lay_t2_ == t2 && lay_[2];     // Tt_d of the preceding residual_slab on this t2
     const bool have_sum = (flags & PYMES_REUSE_LAYOUTS) && xs_vv_tag_.is(t2, 0, 1);   // ... and its S_ac (all columns on this rank)
-    TView Xvv = make_view(arena.alloc(v * v), {v, v});
-    copy(Fvv, Xvv);
+    // ... unless the ring operands of the slab of this t2 carried X_ac already (residual_slab, ring fold): Exn then holds
+    // only the amplitude-side dressing, or nothing
+    const bool folded = ring_fold_.is(t2, ETd_p);
     TView Exn;
-    if (have_sum) {
-        axpby(-w, make_view(xs_vv_, {v, v}), 1.0, Xvv);
-        Exn = make_view(arena.alloc(o * o * v * v), {v, v, o, o});
-    } else {
-        TView Ttd = make_view(reuse ? lay_[2] : arena.alloc(o * o * v * v), {v, o, v, o});
-        if (!reuse) {
-            permute(2.0, T, "abij", 0.0, Ttd, "aibj");
-            permute(-1.0, T, "baij", 1.0, Ttd, "aibj");
+    if (!folded) {
+        TView Xvv = make_view(arena.alloc(v * v), {v, v});
+        copy(Fvv, Xvv);
+        if (have_sum) {
+            axpby(-w, make_view(xs_vv_, {v, v}), 1.0, Xvv);
+            Exn = make_view(arena.alloc(o * o * v * v), {v, v, o, o});
+        } else {
+            TView Ttd = make_view(reuse ? lay_[2] : arena.alloc(o * o * v * v), {v, o, v, o});
+            if (!reuse) {
+                permute(2.0, T, "abij", 0.0, Ttd, "aibj");
+                permute(-1.0, T, "baij", 1.0, Ttd, "aibj");
+            }
+            contract(-w, Ttd, "akdl", make_view(get_static("Vk"), {o, v, o, v}), "kdlc", 1.0, Xvv, "ac");
+            // a private Tt_d is dead after X_ac and lends its storage to Exn; the kept one must survive
+            Exn = make_view(reuse ? arena.alloc(o * o * v * v) : Ttd.p, {v, v, o, o});
         }
-        contract(-w, Ttd, "akdl", make_view(get_static("Vk"), {o, v, o, v}), "kdlc", 1.0, Xvv, "ac");
-        // a private Tt_d is dead after X_ac and lends its storage to Exn; the kept one must survive
-        Exn = make_view(reuse ? arena.alloc(o * o * v * v) : Ttd.p, {v, v, o, o});
+        contract(1.0, Xvv, "ac", T, "cbij", 0.0, Exn, "abij");
     }
     xs_oo_tag_.clear();                                               // last reader of the iteration
     xs_vv_tag_.clear();
-    contract(1.0, Xvv, "ac", T, "cbij", 0.0, Exn, "abij");
     if (amp_side) {
         if (!QK) throw Error("residual_finish: QK buffer missing");
-        amplitude_side_abij(t1, QK, Exn, 0, nv, nv, false);
+        if (folded) Exn = make_view(arena.alloc(o * o * v * v), {v, v, o, o});
+        amplitude_side_abij(t1, QK, Exn, 0, nv, nv, false, folded ? 0.0 : 1.0);     // (folded: its first product opens Exn)
     }
     if (fused) {
+        if (!Exn.p) {                                                 // folded and nothing dressed: the assembly reads zeros
+            Exn = make_view(arena.alloc(o * o * v * v), {v, v, o, o});
+            zero(Exn);
+        }
         // R = V~_abij (or what R holds already) + ladders + Ex + Ex^T in one pass              (:185-187, :249-252)
         dev::residual_assemble(packed ? Vabij_src.p : r2, packed ? L : nullptr, Exn.p, ETd_p, ETx_p, r2, no,
                                nv, stream, ring_xd_);
@@ -586,8 +632,10 @@ void Engine::residual_finish(const double* f, const double* t2, const double* ET
         stats.permute_bytes += 8.0 * 5.5 * double(o * o * v * v);
         return;
     }
-    permute(1.0, Exn, "abij", 1.0, R, "abij");
-    permute(1.0, Exn, "baji", 1.0, R, "abij");
+    if (Exn.p) {
+        permute(1.0, Exn, "abij", 1.0, R, "abij");
+        permute(1.0, Exn, "baji", 1.0, R, "abij");
+    }
     TView ETd = make_view(const_cast<double*>(ETd_p), {v, o, v, o}), ETx = make_view(const_cast<double*>(ETx_p), {v, o, v, o});
     permute(1.0, ETd, "aibj", 1.0, R, "abij");                                              // Ex + Ex^T (:249-252)
     permute(1.0, ETd, "bjai", 1.0, R, "abij");
@@ -625,12 +673,12 @@ void Engine::hf_fock_matrix(const double* h_host, double* f_host) {
 // partner V_abid t_dj = (V_abcj t_ci)_baji are the (c,j)/(i,d) kets of the bra (a,b).  Together with the undressed
 // V_abij in the assembly and the (k,l) bra inside the hole ladder this is all of V~_abij (ccsd.py:322-343).
 void Engine::amplitude_side_abij(const double* t1, const double* QK, const TView& N, int64_t a0, int64_t a1,
-                                 int64_t b1, bool with_partner) {
+                                 int64_t b1, bool with_partner, double beta) {
     // N is [a1 - a0][b1][o][o]: rows a in [a0,a1), columns b in [0,b1)
     const int64_t o = no, v = nv;
     TView t = make_view(const_cast<double*>(t1), {v, o});
     TView Qf = make_view(const_cast<double*>(QK), {o, v, o, o});        // Q + W, rows (k,b) plain [i][j] (ladder_t1)
-    contract(-1.0, slice(t, 0, a0, a1), "ak", slice(Qf, 1, 0, b1), "kbij", 1.0, N, "abij");
+    contract(-1.0, slice(t, 0, a0, a1), "ak", slice(Qf, 1, 0, b1), "kbij", beta, N, "abij");
     if (!with_partner) {
         // N is symmetrised by the caller (N_abij + N_baji, residual_assemble): instead of V_abcj t_ci, whose result has the
         // contracted operand's index in the middle (a transposed temporary and an accumulating permutation, 2.4 GB per
@@ -685,9 +733,11 @@ void Engine::residual_finish_pairs(const double* f, const double* t2, const doub
     TView F = make_view(const_cast<double*>(f), {nn, nn});
     TView Fvv = slice(slice(F, 0, o, nn), 1, o, nn);
     ArenaScope scope(arena);
+    // a one-rank slab without P whose ring operands carried X_ac already (residual_slab, ring fold): no X_ac, no X_ac T
+    const bool folded = ring_fold_.is(t2, ETd_p);
     // X_ac = f_ac - w sum Tt[a,d,k,l] V[l,k,d,c]  (ccd.py:206-221): given (all-reduced xvv_partial) or formed here
     TView Xvv = Xvv_in ? make_view(const_cast<double*>(Xvv_in), {v, v}) : make_view(arena.alloc(v * v), {v, v});
-    if (!Xvv_in) {
+    if (!Xvv_in && !folded) {
         ArenaScope s2(arena);
         TView Ttd = make_view(arena.alloc(o * o * v * v), {v, o, v, o});
         permute(2.0, T, "abij", 0.0, Ttd, "aibj");
@@ -701,8 +751,12 @@ void Engine::residual_finish_pairs(const double* f, const double* t2, const doub
     // only the columns b < a1 are needed (b <= a for every pair of the rank): [na][a1] tiles instead of [na][v]
     const int64_t nb = a1;
     TView Np = make_view(arena.alloc(na * nb * o * o), {na, nb, o, o});
-    contract(1.0, slice(Xvv, 0, a0, a1), "ac", slice(T, 1, 0, nb), "cbij", 0.0, Np, "abij");
-    contract(1.0, slice(Xvv, 0, 0, nb), "bc", slice(T, 1, a0, a1), "caji", 1.0, Np, "abij");
+    if (folded) {
+        zero(Np);
+    } else {
+        contract(1.0, slice(Xvv, 0, a0, a1), "ac", slice(T, 1, 0, nb), "cbij", 0.0, Np, "abij");
+        contract(1.0, slice(Xvv, 0, 0, nb), "bc", slice(T, 1, a0, a1), "caji", 1.0, Np, "abij");
+    }
     if (t1) amplitude_side_abij(t1, QK, Np, a0, a1, nb, true);
     // V_abij is read undressed in the amplitude-side mode (CCSD); CCD/DCD have nothing to dress
     const TView Vabij = block(P_abij, t1 ? false : dressed);

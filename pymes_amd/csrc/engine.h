@@ -219,8 +219,9 @@ class Engine {
                                double* Rc, unsigned flags, const double* t1, const double* QK, int rank, int world,
                                const double* Xvv_in = nullptr);
     void pair_chunk(int rank, int world, int64_t& r0, int64_t& r1) const;
+    // beta = 0: N holds nothing yet, the first product overwrites it
     void amplitude_side_abij(const double* t1, const double* QK, const TView& N, int64_t a0, int64_t a1, int64_t b1,
-                             bool with_partner);
+                             bool with_partner, double beta = 1.0);
     // rows [row0,row1) of the pair-packed ladders and rows [q0,q1) of QK[(k,b)] = sum_cd V_kbcd tau_cdij, all
     // from UNDRESSED, statically packed integrals; tau = T + t1 t1
     void ladder_t1(const double* t1, const double* t2, double* L, int64_t row0, int64_t row1, double* QK, int64_t q0,
@@ -326,7 +327,21 @@ class Engine {
     // that read them again (singles residual, residual_finish): persistent buffers, valid for the t2 pointer recorded
     double* lay_[3] = {nullptr, nullptr, nullptr};
     const double* lay_t2_ = nullptr;
-    void pair_layouts_of(const double* t2);
+    // (Td only on request: its one reader, the X_ki product of residual_slab, is gone where the ring fold applies)
+    void pair_layouts_of(const double* t2, bool want_td);
+    // Ring fold (cc.cpp, residual_slab): the t2 and the ETd buffer of the slab that already carries X_ac T_cbij - X_ki T_abkj
+    // through the ring operands, so that a finish of THAT slab must not add X_ac T again (a finish handed the same t2 with
+    // another ETd forms it as before).  A property of the slab's data: every residual_slab that does not skip the rings
+    // clears it first and sets it when it folds; the finishes only read it (a second finish of the same slab stays right).
+    // PYMES_RING_FOLD=0 selects the separate products.
+    struct FoldTag {
+        const double* t2 = nullptr;
+        const double* etd = nullptr;
+        bool is(const double* t, const double* e) const { return t2 && t2 == t && etd == e; }
+        void set(const double* t, const double* e) { t2 = t; etd = e; }
+        void clear() { t2 = etd = nullptr; }
+    } ring_fold_;
+    static bool ring_fold_enabled();
     // S_ki = sum_cdl Tt[c,d,i,l] V[l,k,d,c] and S_ac = sum_dkl Tt[a,d,k,l] V[l,k,d,c] (ccd.py:213-220), or this rank's partial
     // sums of them: X_ki, X_ac AND the singles residual (ccsd.py:434, :436 are the same sums for exchange-symmetric V, T)
     // read them; valid for the t2 pointer recorded, from the producer (residual_slab / slab_prepare / xvv_partial) to the

@@ -664,6 +664,43 @@ int pymes_ipea_sigma_correction(pymes_ipea* h, int n, const double* const* s_dev
                                 const double* d_dev, double shift, double* const* q_dev, int64_t off2, int64_t len,
                                 double* norms_host);
 int pymes_ipea_sigma_destroy(pymes_ipea* h);
+/* ---- CCSD Lambda equations and the one-particle density -----------------------------------------------------
+ * Vectors are pairs (x1 [v,o], x2 [v,v,o,o]) with x2_abij = x2_baji; <x, y> is the plain sum over all elements of both arrays.
+ * A is the EE-EOM-CCSD sigma of pymes_eom_sigma_apply (eom_ccsd.py:268-385), f~ / V the dressed Fock matrix and blocks of the
+ * handle, t = T2.
+ *   left sigma  A^T: <A^T l, u> = <l, A u> for all exchange-symmetric u, l.  Term by term it is the table of the sigma build
+ *               with the trial vector and the output swapped: a row  c . einsum("X,Y,U->S", x, y, u)  becomes
+ *               c . einsum("X,Y,S->U", x, y, l');  l' = l2 + l2^T(baji) for the rows under P(ijab,jiba) (:332-373), l2 for the
+ *               four unpermuted ones (:380-383), l1 for the singles rows; the doubles result is symmetrised, (x + x^T(baji)) / 2.
+ *               The hoisted V.T intermediates of the handle are read through transposed views; the particle ladder adjoint
+ *               sum_ab V_abcd l2_abij runs pair-packed on the rows V+ / V- of the right build read transposed ((V^T)+- =
+ *               (V+-)^T whenever V_abcd = V_badc: no hermiticity needed, dressed and transcorrelated blocks included).
+ *   Lambda      eta1[a,i] = 2 f~_ov[i,a],  eta2[a,b,i,j] = 2 V_ijab[i,j,a,b] - V_ijab[i,j,b,a];  A^T lambda + eta = 0.
+ *               pymes_lambda_step: res = eta + A^T lam;  out = lam - res / d;  err = -err_scale res / d;  *norm_host = |res|;
+ *               d1 = eps_v[a] - eps_o[i] - shift,  d2 = eps_v[a] + eps_v[b] - eps_o[i] - eps_o[j] - shift  (the denominators
+ *               of the CCSD update with their sign turned).  err is the error vector for a DIIS mixer: pymes_diis_step tests
+ *               linear dependence with an ABSOLUTE 1e-12 on the overlaps, which plain updates pass below |res| ~ 1e-6; a
+ *               fixed err_scale (the Python driver: 1e5) keeps the extrapolation alive down to |res| ~ 1e-11.  start != 0: lam is taken as zero and not read (it may be NULL), out = -eta / d.
+ *               sym != 0: the caller knows that lam2 has the exchange symmetry (else tested: one more synchronisation).
+ *   density     L(f) = E(f) + <lam1, R1(f)> + <lam2, R2(f)> with the CCSD energy expression and residuals at (t1, t2) is
+ *               linear in the Fock matrix; gamma_pq = dL / df_pq (occupied orbitals first, not symmetric):
+ *                 Xvv[a,c] = sum l2[a,b,i,j] t[c,b,i,j],  Xoo[k,i] = sum l2[a,b,i,j] t[a,b,k,j],
+ *                 Xov[j,b] = sum l1[a,i] (2 t[a,b,i,j] - t[a,b,j,i])
+ *                 gamma_vo[a,i] = l1[a,i]                      gamma_oo[j,i] = -2 Xoo[j,i] - sum_a t1[a,j] l1[a,i]
+ *                 gamma_vv[a,b] = 2 Xvv[a,b] + sum_i l1[a,i] t1[b,i]
+ *                 gamma_ov[j,b] = Xov[j,b] + 2 t1[b,j] + sum_i gamma_oo[j,i] t1[b,i] - 2 sum_a t1[a,j] Xvv[a,b]
+ *               pymes_rdm1 writes gamma + ref on the occupied diagonal (ref = 2: the trace is the electron count) to
+ *               gamma_host [n,n]; it reads no integral block.
+ * All three refuse a context that is recording a launch graph; the first two refuse left doubles without the exchange
+ * symmetry and (through the handle's prepare) an integral-sharded context and a missing block, by name.  Identical calls
+ * give identical bits (no atomics, fixed summation order). */
+int pymes_eom_sigma_apply_left(pymes_eom* h, int k, const double* const* l1_dev, const double* const* l2_dev, const int* sym,
+                               double* const* o1_dev, double* const* o2_dev);
+int pymes_lambda_step(pymes_eom* h, const double* lam1_dev, const double* lam2_dev, const double* eps_o_host,
+                      const double* eps_v_host, double shift, double err_scale, int start, int sym, double* out1_dev, double* out2_dev,
+                      double* err1_dev, double* err2_dev, double* norm_host);
+int pymes_rdm1(pymes_ctx* ctx, const double* t1_dev, const double* t2_dev, const double* lam1_dev, const double* lam2_dev,
+               double ref, double* gamma_host);
 /* (mr + i mi)[e] = 1 / ((zr + i zi) - (hr + i hi) d[e] + shift), e < n: the FEAST preconditioner 1 / (z - diag + 0.01)
  * (feast_eom_ccsd.py:342; hs = 1j dt for the real-time form :276-278) from the device-resident diagonal */
 int pymes_cshift_inv(pymes_ctx* ctx, const double* d_dev, double zr, double zi, double hr, double hi, double shift,

@@ -76,6 +76,13 @@ pymes::EomSigma& S(pymes_eom* h) {
     E(h->ctx);                           // the context's device; queued grouped products first
     return *h->s;
 }
+pymes::EomSigma& SL(pymes_eom* h, const char* who) {
+    if (!h || !h->s || !h->ctx) throw pymes::Error(std::string(who) + ": null or destroyed EOM handle");
+    Engine& e = E(h->ctx);
+    e.refuse_if_sharded(who);
+    if (e.capturing()) throw pymes::Error(std::string(who) + " while a launch graph is being recorded");
+    return *h->s;
+}
 pymes::IpEaSigma& SI(pymes_ipea* h, const char* who) {
     if (!h || !h->s || !h->ctx) throw pymes::Error(std::string(who) + ": null or destroyed IP / EA handle");
     Engine& e = E(h->ctx);
@@ -1002,6 +1009,40 @@ int pymes_eom_sigma_destroy(pymes_eom* h) {
         if (h->ctx && h->ctx->e) dev::set_device(h->ctx->e->device);
         delete h->s;                         // (null when the context went first: pymes_ctx_destroy)
         delete h;
+    });
+}
+
+// ---- left sigma, Lambda step, one-particle density (eom.cpp) -----------------------------------------------------------
+int pymes_eom_sigma_apply_left(pymes_eom* h, int k, const double* const* l1, const double* const* l2, const int* sym,
+                               double* const* o1, double* const* o2) {
+    return guarded([&] {
+        need(l1, "l1"); need(l2, "l2"); need(o1, "o1"); need(o2, "o2");
+        if (k < 0 || k > 4096) throw pymes::Error("eom_sigma_apply_left: 0 <= k <= 4096");
+        for (int z = 0; z < k; ++z)
+            if (l2[z] == o2[z] || l1[z] == o1[z]) throw pymes::Error("eom_sigma_apply_left: output aliases input");
+        SL(h, "eom_sigma_apply_left").apply_left(k, l1, l2, sym, o1, o2);
+    });
+}
+int pymes_lambda_step(pymes_eom* h, const double* lam1, const double* lam2, const double* eps_o_host, const double* eps_v_host,
+                      double shift, double err_scale, int start, int sym, double* out1, double* out2, double* err1, double* err2, double* norm_host) {
+    return guarded([&] {
+        need(eps_o_host, "eps_o"); need(eps_v_host, "eps_v"); need(out1, "out1"); need(out2, "out2"); need(err1, "err1");
+        need(err2, "err2"); need(norm_host, "norm");
+        if (!start) { need(lam1, "lam1"); need(lam2, "lam2"); }
+        if (err1 == out1 || err2 == out2 || (!start && (err1 == lam1 || err2 == lam2)))
+            throw pymes::Error("lambda_step: the error vector aliases lambda");
+        *norm_host = SL(h, "lambda_step").lambda_step(lam1, lam2, eps_o_host, eps_v_host, shift, err_scale, start != 0, sym != 0, out1,
+                                                      out2,
+                                                      err1, err2);
+    });
+}
+int pymes_rdm1(pymes_ctx* ctx, const double* t1, const double* t2, const double* lam1, const double* lam2, double ref,
+               double* gamma_host) {
+    return guarded([&] {
+        need(t1, "t1"); need(t2, "t2"); need(lam1, "lam1"); need(lam2, "lam2"); need(gamma_host, "gamma");
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("rdm1 while a launch graph is being recorded");
+        pymes::lambda_rdm1(e, t1, t2, lam1, lam2, ref, gamma_host);
     });
 }
 

@@ -938,6 +938,40 @@ void Engine::ladder_sym_multi(const double* const* xs, int k, double* L_all, boo
     }
 }
 
+void Engine::ladder_sym_adjoint(const double* x, double* LSp, double* LAp, bool dressed) {
+    refuse_if_sharded("ladder_sym_adjoint");
+    const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opp = o * (o + 1) / 2,
+                  opm = o * (o - 1) / 2;
+    if (!(lpack_.valid && lpack_.dressed == dressed && lpack_.row0 == 0 && lpack_.row1 == npp)) {
+        if (!lpack_.Vp || lpack_.row1 - lpack_.row0 != npp) {
+            dev::stream_sync(stream);
+            dev::dfree(lpack_.Vp);
+            dev::dfree(lpack_.Vm);
+            lpack_.Vp = lpack_.Vm = nullptr;
+            lpack_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * npp * lpitch(npp)));
+            lpack_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * npp * lpitch(std::max<int64_t>(npm, 1))));
+        }
+        dev::ladder_pack_V(block(P_abcd, dressed).p, lpack_.Vp, lpack_.Vm, nv, nv, 0, npp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
+        stats.permute_calls++;
+        stats.permute_bytes += 8.0 * 2.0 * double(npp) * double(v * v);
+        lpack_.row0 = 0; lpack_.row1 = npp; lpack_.dressed = dressed; lpack_.valid = true;
+    }
+    ArenaScope scope(arena);
+    const int64_t ldp = opp + (opp & 1), ldm = std::max<int64_t>(opm + (opm & 1), 2);
+    // the summed pair (a,b) is the ROW index of V+ / V-: the antisymmetric half of x is packed by the same pairs P(a,b)
+    // (PACK_AM_PROWS; the rows of diagonal pairs are zero, as the rows of V- are)
+    double* Sp = arena.alloc(npp * ldp);
+    double* Am = arena.alloc(npp * ldm);
+    dev::ladder_pack_T(x, nullptr, Sp, Am, no, nv, dev::PACK_ROW_HALF | dev::PACK_AM_PROWS, ldp, ldm, stream);
+    stats.permute_calls++;
+    stats.permute_bytes += 8.0 * 2.0 * double(v * v * o * o);
+    auto pitched = [&](double* p, int64_t r, int64_t c, int64_t ld) { return slice(make_view(p, {r, ld}), 1, 0, c); };
+    contract(1.0, packed_rows(lpack_.Vp, npp, npp), "kr", pitched(Sp, npp, opp, ldp), "kn", 0.0,
+             slice(make_view(LSp, {npp, o * o}), 1, 0, opp), "rn");
+    if (opm > 0 && npm > 0)
+        contract(1.0, packed_rows(lpack_.Vm, npp, npm), "kr", pitched(Am, npp, opm, ldm), "kn", 0.0, make_view(LAp, {npm, opm}), "rn");
+}
+
 // A hole-ladder-shaped term sum_kl I_klij X_abkl in the pair-packed rows of L (added to what the rows hold), for
 // I_klij = I_lkji and X_abkl = X_balk: the (k,l) part of ladder_sym for a caller-supplied I (EOM-CCSD: eom_ccsd.py:380-382
 // — u2 against V_klij + V_klcd T_cdij, T against V_kldc u2_dcij), 1/4 of the flops of the plain v^2 o^4 product.  With y

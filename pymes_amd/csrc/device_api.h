@@ -324,6 +324,35 @@ int64_t ipea_correction_ws_doubles(int n, int64_t len);
 void ipea_correction(int n, const double* const* sv, const double* const* rv, const double* w_host, const double* d, double shift,
                      double* const* q, int64_t n1, int64_t off2, int64_t len, double* ws, double* out_dev, stream_t s);
 
+// ---- CCSD Lambda equations and the one-particle density (eom.cpp, EomSigma::apply_left / lambda_step, lambda_rdm1).
+// The product library only (the host simulator has no definition: weak ones in the engine throw).
+// Assembly of the left sigma from its partial results, one pass, one launch (one block per virtual pair a >= b and one for the
+// singles; o (o + 1) + 256 doubles of LDS, refused beyond 64 KB; no atomics, fixed summation order).  With raw_abij = D_abij + cd Pd[(a,i),(b,j)] + Px[(a,j),(b,i)] + cx Pd[(a,j),(b,i)]
+// (D [v,v,o,o]; Pd, Px [ov,ov]; all null: zero) and the pair-packed ladder halves (Engine::ladder_sym_adjoint; may be null): Lp
+// rows P(a,b) of length o^2 with LS in the first o(o+1)/2 columns, La [v(v-1)/2][o(o-1)/2] by strictly-lower pairs:
+//   s2_abij = (raw_abij + raw_baji) / 2 + LS[P(ab)][P(ij)] + sgn(a-b) sgn(i-j) LA[Q(ab)][Q(ij)],   s1 = S1 [v,o]
+// Vijab == null: out1 = s1, out2 = s2.  Otherwise the Lambda update with eta2_abij = 2 V_ijab[i,j,a,b] - V_ijab[i,j,b,a] read
+// from the stored [o,o,v,v] block and eta1 [v,o]:  res = eta + s;  out = lam - res / d (out may alias lam; lam1 = lam2 = null: zero);  err = -err_scale res / d,
+// d1 = ev[a] - eo[i] - shift, d2 = ev[a] + ev[b] - eo[i] - eo[j] - shift;  norm_dev[0] = |res|^2 over singles and doubles (block
+// sums in ws, lambda_assemble_ws_doubles(nv) doubles, then one block; left on the device for readback_start).
+struct LambdaParts {
+    const double* D = nullptr; const double* Pd = nullptr; const double* Px = nullptr; const double* Lp = nullptr;
+    const double* La = nullptr; const double* S1 = nullptr;
+    double cd = 1.0, cx = 0.0;
+    const double* Vijab = nullptr; const double* eta1 = nullptr; const double* eo = nullptr; const double* ev = nullptr;
+    double shift = 0.0, err_scale = 1.0;
+    const double* lam1 = nullptr; const double* lam2 = nullptr;
+    double* out1 = nullptr; double* out2 = nullptr; double* err1 = nullptr; double* err2 = nullptr;
+    double* ws = nullptr; double* norm_dev = nullptr;
+};
+int64_t lambda_assemble_ws_doubles(int nv);
+void lambda_assemble(const LambdaParts& q, int no, int nv, stream_t s);
+// gamma [n,n] (n = no + nv, occupied first; device) from Xvv[a,c] = sum l2[a,b,i,j] t2[c,b,i,j], Xoo[k,i] = sum l2[a,b,i,j]
+// t2[a,b,k,j], Xov[j,b] = sum l1[a,i] (2 t2[a,b,i,j] - t2[a,b,j,i]) and l1, t1 [v,o], including the back-transformation with
+// t1 (formulas: include/pymes_amd.h, pymes_rdm1); ref is added on the occupied diagonal.  One launch.
+void rdm1_assemble(const double* Xvv, const double* Xoo, const double* Xov, const double* l1, const double* t1, int no, int nv,
+                   double ref, double* g, stream_t s);
+
 // ---- Hartree-Fock matrix from the packed blocks (pymes/mean_field/hf.py:14-18); dir[tp*2+tq] = block (tp,o,tq,o),
 // exc[tp*2+tq] = block (tp,o,o,tq), tp/tq = 1 for a virtual index; h and f are [n,n] on the device
 void hf_fock(const double* const dir[4], const double* const exc[4], const double* h_dev, double* f_dev, int no, int nv,

@@ -816,4 +816,13 @@ __attribute__((weak)) void ipea_correction(int, const double* const*, const doub
                                            double* const*, int64_t, int64_t, int64_t, double*, double*, stream_t) {
     throw std::runtime_error("ipea_correction: not available in this backend");
 }
+// ... and without the Lambda / density kernels
+__attribute__((weak)) int64_t lambda_assemble_ws_doubles(int) { return 1; }
+__attribute__((weak)) void lambda_assemble(const LambdaParts&, int, int, stream_t) {
+    throw std::runtime_error("lambda_assemble: not available in this backend");
+}
+__attribute__((weak)) void rdm1_assemble(const double*, const double*, const double*, const double*, const double*, int, int,
+                                         double, double*, stream_t) {
+    throw std::runtime_error("rdm1_assemble: not available in this backend");
+}
 }  // namespace dev

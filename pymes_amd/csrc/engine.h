@@ -198,6 +198,14 @@ class Engine {
     // the particle ladder of k exchange-symmetric vectors x_z [v,v,o,o] at once: L_all[z] (k consecutive [v(v+1)/2][o*o]
     // arrays) = pair-packed V_abcd . x_z, one batched launch per half (S / A) over all k vectors
     void ladder_sym_multi(const double* const* xs, int k, double* L_all, bool dressed);
+    // the ADJOINT of the particle ladder for an exchange-symmetric x: M_cdij = sum_ab V_abcd x_abij, pair-packed.  With
+    // V_abcd = V_badc alone (no hermiticity) the packed rows of V^T are the packed rows of V transposed,
+    //   (V^T)+[(cd),(ab)] = V_abcd + V_bacd = V+[(ab),(cd)],   (V^T)-[(cd),(ab)] = V-[(ab),(cd)],
+    // so these are the two products of ladder_sym with the cached V+ / V- read through a transposed view: a quarter of the
+    // flops of the plain product whatever the integrals.  LS: rows P(c,d) of length o*o, the symmetric half in the first
+    // o(o+1)/2 columns (the layout of ladder_sym; the rest of a row is not written); LA [v(v-1)/2][o(o-1)/2]: the
+    // antisymmetric half by strictly-lower pairs Q(c,d).
+    void ladder_sym_adjoint(const double* x, double* LS, double* LA, bool dressed);
     void hole_ladder_packed_multi(const double* const* xs, const double* const* Is, const double* const* ys, int k, double* L_all);
     void hole_ladder_packed(const double* x, const double* I, double* L, int64_t row0, int64_t row1,
                             const double* y = nullptr);

@@ -591,6 +591,177 @@ void EomSigma::apply(int k, const double* const* u1, const double* const* u2, co
     }
 }
 
+// ==== the adjoint of the sigma build: left vectors, the Lambda equations, the one-particle density ====================
+// apply() on an exchange-symmetric u2 is a chain of linear steps (the u2_sym branches of singles() / doubles()); A^T l runs that
+// chain backwards with every product transposed — the same hoisted operands through transposed views, no new intermediate of
+// V and T.  The steps under the permutation P(ijab,jiba) (:377) see l2 + l2^T = 2 l2, the unpermuted ones (:380-383) l2; the
+// result is projected back onto the symmetric subspace by the assembly kernel.
+struct EomSigma::LeftParts {
+    Tmp S1, D, Pd, Px, Lp, La;
+    bool packed;
+    LeftParts(EomSigma& s, bool build)
+        : S1(s, build ? static_cast<int64_t>(s.nv) * s.no : 1), D(s, build ? static_cast<int64_t>(s.nv) * s.nv * s.no * s.no : 1),
+          Pd(s, build ? static_cast<int64_t>(s.nv) * s.nv * s.no * s.no : 1),
+          Px(s, build ? static_cast<int64_t>(s.nv) * s.nv * s.no * s.no : 1),
+          Lp(s, build && s.v_sym ? static_cast<int64_t>(s.nv) * (s.nv + 1) / 2 * s.no * s.no : 1),
+          La(s, build && s.v_sym ? std::max<int64_t>(static_cast<int64_t>(s.nv) * (s.nv - 1) / 2 * (s.no * (s.no - 1) / 2), 1) : 1),
+          packed(build && s.v_sym) {}
+    void fill(dev::LambdaParts& q) const {
+        q.D = D; q.Pd = Pd; q.Px = Px; q.S1 = S1;
+        q.Lp = packed ? Lp.p : nullptr;
+        q.La = packed ? La.p : nullptr;
+    }
+};
+
+void EomSigma::left_prepare() {
+    if (left_ready) return;
+    if (!fused_ok) throw Error("eom sigma apply_left: nocc too large for the fused pair kernels");
+    const int64_t o = no, v = nv;
+    const Ops q{e};
+    if (!eta1) eta1 = keep(v * o);
+    q.P(2.0, mv(fov, {o, v}), "ia", 0.0, mv(eta1, {v, o}), "ai");
+    left_ready = true;
+}
+
+void EomSigma::left_partials(const double* l1, const double* l2, LeftParts& w) {
+    const int64_t o = no, v = nv, ov = o * v, ov2 = ov * ov;
+    const Ops q{e};
+    const TView L1 = mv(l1, {v, o}), L2 = mv(l2, {v, v, o, o}), T4 = mv(T, {v, v, o, o});
+    const TView Vijab = V("ijab"), Vijka = V("ijka"), Vijak = V("ijak"), Viabc = V("iabc");
+    const TView S = mv(w.S1, {v, o}), D = mv(w.D, {v, v, o, o}), FOV = mv(fov, {o, v});
+    auto P4 = [&](const double* p) { return mv(p, {v, o, v, o}); };
+    // ---- singles() backwards: the l1 row of A^T ------------------------------------------------------------------------------------
+    q.C(1.0, mv(W1, {v, o, v, o}), "ckai", L1, "ai", 0.0, S, "ck");
+    q.C(1.0, mv(Gvv_s, {v, v}), "ac", L1, "ai", 1.0, S, "ci");
+    q.C(1.0, L1, "ai", mv(Goo_s, {o, o}), "ki", 1.0, S, "ak");
+    {
+        // the adjoint of ut = 2 u2 - u2^(ab): utb collects what singles() contracts ut with, then D = 2 utb - utb^(ab)
+        Tmp utb(*this, v * v * o * o);
+        const TView Ub = mv(utb, {v, v, o, o});
+        q.C(1.0, mv(fov, {o, v, 1}), "jbx", mv(l1, {1, v, o}), "xai", 0.0, Ub, "baji");          // (an outer product: K = 1)
+        q.C(-1.0, Vijka, "jkib", L1, "ai", 1.0, Ub, "abjk");
+        q.C(1.0, Viabc, "jabc", L1, "ai", 1.0, Ub, "bcji");
+        q.P(2.0, Ub, "abij", 0.0, D, "abij");
+        q.P(-1.0, Ub, "baij", 1.0, D, "abij");
+    }
+    // ---- doubles() backwards.  Pair layouts of l2 in one pass: ld[(a,i),(b,j)] = lx[(a,j),(b,i)] = l2_abij, and Q = ld + 2 lx as
+    // matrices — what Dx receives: 2 lx where it enters D, ld / 2 . 2 through the half of it that Dd carries ---------------------
+    Tmp ld(*this, ov2), lx(*this, ov2), Q(*this, ov2);
+    dev::t2_layouts(l2, ld, lx, Q, no, nv, e.stream, 1.0, 2.0);
+    Tmp Xoo(*this, o * o), Xvv(*this, v * v), Bn(*this, o * o * o * o);
+    const TView XooV = mv(Xoo, {o, o}), XvvV = mv(Xvv, {v, v}), BnV = mv(Bn, {o, o, o, o});
+    // the terms that wrote D (:334-361): their operand against 2 l2
+    q.C(2.0, L2, "abij", T4, "cbij", 0.0, XvvV, "ac");
+    q.C(2.0, mv(WW, {v, v, o, v}), "abid", L2, "abij", 1.0, S, "dj");
+    q.C(2.0, mv(Gvv, {v, v}), "ad", L2, "abij", 1.0, D, "dbij");
+    q.C(2.0, mv(Goo, {o, o}), "li", L2, "abij", 1.0, D, "ablj", "ab");
+    q.C(2.0, L2, "abij", mv(A3, {o, o, v, o}), "libj", 1.0, S, "al");
+    q.C(2.0, L2, "abij", mv(A4, {o, o, v, o}), "liaj", 1.0, S, "bl");
+    q.C(-2.0, L2, "abij", mv(A6, {o, v, o, o}), "laji", 1.0, S, "bl");
+    q.C(-2.0, L2, "abij", V("iajk"), "kbij", 1.0, S, "ak");
+    // T . B5 (:338) and T . Bn (:381) share Bn^ = T^T l2
+    q.C(1.0, T4, "abkl", L2, "abij", 0.0, BnV, "klij");
+    q.C(2.0, Vijka, "klid", BnV, "klij", 1.0, S, "dj");
+    // the two (ov)^3 products, transposed: Pd = M12^T ld (the adjoint of utd, which enters as 2 Pd - Pd^(ab): cd, cx of the
+    // assembly), Px = MDU^T Q
+    q.C(1.0, P4(M12), "aidl", P4(ld), "aibj", 0.0, P4(w.Pd), "dlbj");
+    q.C(2.0, P4(Td), "akbj", P4(ld), "aibj", 0.0, XooV, "ki");
+    q.C(1.0, P4(MDU), "ajdl", P4(Q), "ajbi", 0.0, P4(w.Px), "dlbi");
+    // one-index dressings backwards
+    q.C(-2.0, Vijka, "klid", XooV, "ki", 1.0, S, "dl");
+    q.C(1.0, Vijak, "kldi", XooV, "ki", 1.0, S, "dl");
+    q.C(-1.0, FOV, "kd", XooV, "ki", 1.0, S, "di");
+    q.C(1.0, mv(Aoo, {o, v, o, v}), "kdlc", XooV, "ki", 1.0, P4(w.Px), "dlci");
+    q.C(2.0, Viabc, "ladc", XvvV, "ac", 1.0, S, "dl");
+    q.C(-1.0, Viabc, "lacd", XvvV, "ac", 1.0, S, "dl");
+    q.C(-1.0, XvvV, "ac", FOV, "lc", 1.0, S, "al");
+    q.C(1.0, XvvV, "ac", slice(mv(BB, {o, v, o, v + o}), 3, 0, v), "kdlc", 1.0, P4(w.Px), "akdl");
+    // ---- the unpermuted terms (:380-383) against l2 ----------------------------------------------------------------------------------
+    q.C(1.0, L2, "abij", mv(B2, {o, o, o, o}), "klij", 1.0, D, "abkl");
+    q.C(1.0, Vijab, "kldc", BnV, "klij", 1.0, D, "dcij");
+    // the particle ladder backwards: sum_ab V_abcd l2_abij.  With V_abcd = V_badc (every Hamiltonian the package is fed; no
+    // hermiticity needed) the packed rows V+ / V- of the right build are read in the other orientation — a quarter of the flops
+    // of the plain product, for dressed and transcorrelated blocks alike
+    if (w.packed) e.ladder_sym_adjoint(l2, w.Lp, w.La, dressed);
+    else q.C(1.0, V("abcd"), "abcd", L2, "abij", 1.0, D, "cdij");
+}
+
+void EomSigma::apply_left(int k, const double* const* l1, const double* const* l2, const int* sym, double* const* o1,
+                          double* const* o2) {
+    if (k < 1) return;
+    for (int z = 0; z < k; ++z)
+        if (!l1[z] || !l2[z] || !o1[z] || !o2[z]) throw Error("eom sigma apply_left: null vector");
+    for (int z = 0; z < k; ++z)            // (refusals first: nothing is allocated for a call that is refused)
+        if (!(sym && sym[z]) && !exchange_symmetric(l2[z], nv, no))
+            throw Error("eom sigma apply_left: the left doubles do not have the exchange symmetry l2_abij = l2_baji");
+    left_prepare();
+    for (int z = 0; z < k; ++z) {
+        LeftParts w(*this, true);
+        left_partials(l1[z], l2[z], w);
+        dev::LambdaParts q;
+        w.fill(q);
+        q.cd = 2.0; q.cx = -1.0;
+        q.out1 = o1[z]; q.out2 = o2[z];
+        dev::lambda_assemble(q, no, nv, e.stream);
+    }
+}
+
+double EomSigma::lambda_step(const double* lam1, const double* lam2, const double* eo_host, const double* ev_host, double shift,
+                             double err_scale, bool start, bool known_sym, double* out1, double* out2, double* err1, double* err2) {
+    if (!eo_host || !ev_host || !out1 || !out2 || !err1 || !err2) throw Error("lambda_step: null argument");
+    if (!start && (!lam1 || !lam2)) throw Error("lambda_step: null lambda");
+    if (!start && !known_sym && !exchange_symmetric(lam2, nv, no))
+        throw Error("lambda_step: lambda2 does not have the exchange symmetry l2_abij = l2_baji");
+    left_prepare();
+    const int64_t n = static_cast<int64_t>(no) + nv;
+    std::vector<double> eps(static_cast<size_t>(n));
+    for (int64_t i = 0; i < no; ++i) eps[i] = eo_host[i];
+    for (int64_t a = 0; a < nv; ++a) eps[no + a] = ev_host[a];
+    if (!eps_dev || eps != eps_host_) {
+        if (!eps_dev) eps_dev = keep(n);
+        dev::memcpy_h2d(eps_dev, eps.data(), sizeof(double) * n, e.stream);
+        dev::stream_sync(e.stream);
+        eps_host_ = eps;
+    }
+    LeftParts w(*this, !start);
+    if (!start) left_partials(lam1, lam2, w);
+    Tmp ws(*this, dev::lambda_assemble_ws_doubles(nv)), nrm(*this, 32);
+    dev::LambdaParts q;
+    if (!start) {                          // (start: lambda = 0, no partial results: out = -eta / d, nothing is read)
+        w.fill(q);
+        q.lam1 = lam1; q.lam2 = lam2;
+    }
+    q.cd = 2.0; q.cx = -1.0;
+    q.Vijab = V("ijab").p; q.eta1 = eta1; q.eo = eps_dev; q.ev = eps_dev + no; q.shift = shift; q.err_scale = err_scale;
+    q.out1 = out1; q.out2 = out2; q.err1 = err1; q.err2 = err2; q.ws = ws; q.norm_dev = nrm;
+    dev::lambda_assemble(q, no, nv, e.stream);
+    double r = 0.0;
+    const int slot = dev::readback_start(nrm, 1, e.stream);
+    dev::readback_wait(slot, &r, 1);
+    return std::sqrt(r);
+}
+
+void lambda_rdm1(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2, double ref,
+                 double* gamma_host) {
+    if (!t1 || !t2 || !lam1 || !lam2 || !gamma_host) throw Error("rdm1: null argument");
+    const int64_t o = e.no, v = e.nv, n = o + v;
+    struct Buf {
+        Engine& e;
+        double* p;
+        Buf(Engine& e_, int64_t m) : e(e_), p(e_.scratch_get(m)) {}
+        ~Buf() { e.scratch_put(p); }
+    } Xvv(e, v * v), Xoo(e, o * o), Xov(e, o * v), G(e, n * n);
+    const TView L1 = mv(lam1, {v, o}), L2 = mv(lam2, {v, v, o, o}), T4 = mv(t2, {v, v, o, o});
+    // the lambda2 . t2 contractions: K = v o o and v v o, the engine's split-K products
+    e.contract(1.0, L2, "abij", T4, "cbij", 0.0, mv(Xvv.p, {v, v}), "ac");
+    e.contract(1.0, L2, "abij", T4, "abkj", 0.0, mv(Xoo.p, {o, o}), "ki");
+    e.contract(2.0, L1, "ai", T4, "abij", 0.0, mv(Xov.p, {o, v}), "jb");
+    e.contract(-1.0, L1, "ai", T4, "abji", 1.0, mv(Xov.p, {o, v}), "jb");
+    dev::rdm1_assemble(Xvv.p, Xoo.p, Xov.p, lam1, t1, e.no, e.nv, ref, G.p, e.stream);
+    dev::memcpy_d2h(gamma_host, G.p, sizeof(double) * n * n, e.stream);
+    dev::stream_sync(e.stream);
+}
+
 // ---- eom_ccsd.py:169-198 (singles) and :200-266 (doubles) on the device ---------------------------------------------------------
 void eom_diagonals(Engine& e, const double* f_host, const double* t2, bool dressed, double* d1, double* d2) {
     if (!f_host || !t2 || !d1 || !d2) throw Error("eom diagonals: null argument");

@@ -29,6 +29,20 @@ class EomSigma {
     Engine& engine() { return e; }
     void trim();                      // release the pooled temporaries
 
+    // ---- the adjoint build: o = A^T l for the sigma A of apply() under the plain inner product over both arrays, on
+    // the exchange-symmetric subspace, from the SAME hoisted intermediates read through transposed operand views.  l2[z] must
+    // have the exchange symmetry (sym[z] != 0: the caller knows; else tested here, one reduction and a synchronisation; refused
+    // by name otherwise); the vectors are handled one by one.  apply() is not affected: nothing it reads is written.
+    void apply_left(int k, const double* const* l1, const double* const* l2, const int* sym, double* const* o1,
+                    double* const* o2);
+    // One Lambda iteration for eta1[a,i] = 2 f_ov[i,a], eta2[a,b,i,j] = 2 V_ijab[i,j,a,b] - V_ijab[i,j,b,a] (read from the block):
+    //   res = eta + A^T lam;  out = lam - res / d;  err = -err_scale res / d;  returns |res| (one synchronisation)
+    // d1 = ev[a] - eo[i] - shift, d2 = ev[a] + ev[b] - eo[i] - eo[j] - shift (eo, ev on the host).  start: lam is taken as zero
+    // and not read (out = -eta / d, the start vector; |eta| is returned); lam1 / lam2 may then be null.  known_sym: the caller
+    // knows that lam2_abij = lam2_baji (the output of an earlier step, or a combination of such); else tested here.
+    double lambda_step(const double* lam1, const double* lam2, const double* eo_host, const double* ev_host, double shift,
+                       double err_scale, bool start, bool known_sym, double* out1, double* out2, double* err1, double* err2);
+
   private:
     Engine& e;
     const int no, nv;
@@ -45,6 +59,13 @@ class EomSigma {
            *M1 = nullptr, *Ud = nullptr, *M2 = nullptr, *M12 = nullptr, *MDU = nullptr, *WA = nullptr, *W3 = nullptr, *A3 = nullptr,
            *A4 = nullptr, *A6 = nullptr, *Gvv = nullptr, *Goo = nullptr, *B2 = nullptr, *L = nullptr, *WW = nullptr, *BB = nullptr,
            *Aoo = nullptr, *A346 = nullptr, *TA = nullptr, *LK3 = nullptr, *LK2 = nullptr;
+    // the adjoint build: eta1, once per handle on first use; the partial results of one vector
+    double *eta1 = nullptr, *eps_dev = nullptr;
+    std::vector<double> eps_host_;
+    bool left_ready = false;
+    void left_prepare();
+    struct LeftParts;
+    void left_partials(const double* l1, const double* l2, LeftParts& w);
     void general_operands();          // LK3, LK2 (trial vectors without exchange symmetry), on first use
     bool v_sym = false, t_sym = false, hole_sym = false, fused_ok = false, many_ok = false;
     TView V(const char* name) const;
@@ -58,6 +79,12 @@ class EomSigma {
 // eom_ccsd.py:169-198 (get_diag_singles) / :200-266 (get_diag_doubles): d1 [v,o], d2 [v,v,o,o] (device, written); f_host the
 // dressed Fock matrix [n,n], t2 [v,v,o,o] on the device, blocks read dressed or as set
 void eom_diagonals(Engine& e, const double* f_host, const double* t2, bool dressed, double* d1, double* d2);
+
+// The one-particle response density of the CCSD Lagrangian (formulas in include/pymes_amd.h, pymes_rdm1): gamma_host
+// [n,n], occupied orbitals first, from t1, lam1 [v,o] and t2, lam2 [v,v,o,o] on the device; ref is added on the occupied
+// diagonal (2.0: the matrix whose trace is the electron count).  Reads no integral block.
+void lambda_rdm1(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2, double ref,
+                 double* gamma_host);
 
 // IP- and EA-EOM-CCSD sigma builds (formulas in include/pymes_amd.h): the EE operator above restricted to the sector
 // with one non-interacting orbital.  Vectors: IP r1[i], r2[i,j,b]; EA r1[a], r2[a,b,j] — below r2[x,y,w] with x, y over P

@@ -6198,3 +6198,212 @@ void ipea_correction(int n, const double* const* sv, const double* const* rv, co
 }
 
 }  // namespace dev
+
+// ==== CCSD Lambda equations and the one-particle density (device_api.h; eom.cpp, EomSigma::apply_left) =================
+namespace {
+
+// One block per virtual pair a >= b (the tiling of residual_assemble: every source is read with the thread index along its
+// fastest index, the o x o tile in LDS carries the transposition), one extra block for the singles.  With
+//   raw_abij = D_abij + cd Pd[(a,i),(b,j)] + Px[(a,j),(b,i)] + cx Pd[(a,j),(b,i)]
+// the left sigma is  s2_abij = (raw_abij + raw_baji) / 2 + LS[P(ab)][P(ij)] + sgn(a-b) sgn(i-j) LA[Q(ab)][Q(ij)],  s1 = S1 (LS in
+// the rows Lp of length o^2, LA dense by strictly-lower pairs: the two halves of the packed ladder adjoint).  Without V_ijab that is what is written
+// (out1, out2).  With it the block goes on to the Lambda update: eta2_abij = 2 V[i,j,a,b] - V[i,j,b,a] read from the stored
+// [o,o,v,v] block (a strided gather of two numbers per element, both index orders from the same two loads),
+//   res = eta + s,  out = lam - res / d,  err = -es res / d,  d2 = ev[a] + ev[b] - eo[i] - eo[j] - shift,  d1 = ev[a] - eo[i] - shift
+// and ws[block] = sum of res^2 over the block's elements, added pairwise in a fixed tree.  Null partials and a null lam count as zero
+// (the start lambda = -eta / d).
+struct LambdaK {
+    const double* D; const double* Pd; const double* Px; const double* Lp; const double* La; const double* S1;
+    const double* Vijab; const double* eta1; const double* eo; const double* ev;
+    const double* lam1; const double* lam2;
+    double* out1; double* out2; double* err1; double* err2; double* ws;
+    double cd, cx, shift, es;
+    int no, nv;
+};
+
+__device__ __forceinline__ double lambda_block_sum(double x, double* sr) {
+    const int t = threadIdx.x;
+    sr[t] = x;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) sr[t] += sr[t + h];
+        __syncthreads();
+    }
+    return sr[0];
+}
+
+__global__ void __launch_bounds__(256) lambda_assemble_kernel(const LambdaK k) {
+    extern __shared__ double S[];             // [no][no + 1]
+    double* sr = S + (long)k.no * (k.no + 1);         // [256], behind the tile
+    const int no = k.no, nv = k.nv;
+    const bool update = k.Vijab != nullptr;
+    const long npairs = (long)nv * (nv + 1) / 2;
+    double acc = 0.0;
+    if ((long)blockIdx.x == npairs) {         // the singles
+        const long n1 = (long)nv * no;
+        for (long e = threadIdx.x; e < n1; e += 256) {
+            const double s = k.S1 ? k.S1[e] : 0.0;
+            if (!update) {
+                k.out1[e] = s;
+                continue;
+            }
+            const int a = (int)(e / no), i = (int)(e - (long)a * no);
+            const double res = k.eta1[e] + s, dl = -res / (k.ev[a] - k.eo[i] - k.shift);
+            acc += res * res;
+            k.err1[e] = k.es * dl;
+            k.out1[e] = (k.lam1 ? k.lam1[e] : 0.0) + dl;
+        }
+        if (update) {
+            const double tot = lambda_block_sum(acc, sr);
+            if (threadIdx.x == 0) k.ws[npairs] = tot;
+        }
+        return;
+    }
+    const double* __restrict__ D = k.D;
+    const double* __restrict__ Pd = k.Pd;
+    const double* __restrict__ Px = k.Px;
+    const double cd = k.cd, cx = k.cx;
+    int a, b;
+    unrank_pair(blockIdx.x, a, b);
+    const int p = no + 1;
+    const long o2 = (long)no * no, ov = (long)no * nv, opp = (long)no * (no + 1) / 2;
+    const long ab = ((long)a * nv + b) * o2, ba = ((long)b * nv + a) * o2;
+    const long tab = (long)a * no * ov + (long)b * no, tba = (long)b * no * ov + (long)a * no;
+    for (int e = threadIdx.x; e < o2; e += 256) {             // sources read in (i,j) order
+        const int i = e / no, j = e - i * no;
+        double v = 0.0;
+        if (D) {
+            const long x = tab + (long)i * ov + j, y = tba + (long)i * ov + j;
+            v = D[ab + e] + cd * Pd[x] + Px[y] + cx * Pd[y];
+        }
+        S[i * p + j] = v;
+    }
+    __syncthreads();
+    if (D) {
+        for (int e = threadIdx.x; e < o2; e += 256) {         // sources read in (j,i) order
+            const int j = e / no, i = e - j * no;
+            const long x = tba + (long)j * ov + i, y = tab + (long)j * ov + i;
+            S[i * p + j] += D[ba + e] + cd * Pd[x] + Px[y] + cx * Pd[y];
+        }
+    }
+    __syncthreads();
+    const long opm = o2 - opp;
+    const double* __restrict__ row = k.Lp ? k.Lp + ((long)a * (a + 1) / 2 + b) * o2 : nullptr;
+    const double* __restrict__ rowa = (k.La && a != b) ? k.La + ((long)a * (a - 1) / 2 + b) * opm : nullptr;
+    const double ea = update ? k.ev[a] + k.ev[b] - k.shift : 0.0;
+    for (int e = threadIdx.x; e < o2; e += 256) {
+        const int i = e / no, j = e - i * no;
+        const int ih = max(i, j), il = min(i, j);
+        double ls = 0.0, la = 0.0;
+        if (row) {
+            ls = row[(long)ih * (ih + 1) / 2 + il];
+            if (rowa && i != j) la = rowa[(long)ih * (ih - 1) / 2 + il];
+        }
+        const double sgn = i > j ? 1.0 : -1.0;
+        const double sab = 0.5 * S[i * p + j] + ls + sgn * la, sba = 0.5 * S[j * p + i] + ls - sgn * la;
+        if (!update) {
+            k.out2[ab + e] = sab;
+            if (a != b) k.out2[ba + e] = sba;
+            continue;
+        }
+        const long vo = (long)e * nv * nv;                    // V_ijab[i,j,:,:]
+        const double vab = k.Vijab[vo + (long)a * nv + b], vba = k.Vijab[vo + (long)b * nv + a];
+        const double d = ea - k.eo[i] - k.eo[j];
+        const double r1 = 2.0 * vab - vba + sab, d1 = -r1 / d;
+        acc += r1 * r1;
+        k.err2[ab + e] = k.es * d1;
+        k.out2[ab + e] = (k.lam2 ? k.lam2[ab + e] : 0.0) + d1;
+        if (a != b) {
+            const double r2 = 2.0 * vba - vab + sba, d2 = -r2 / d;
+            acc += r2 * r2;
+            k.err2[ba + e] = k.es * d2;
+            k.out2[ba + e] = (k.lam2 ? k.lam2[ba + e] : 0.0) + d2;
+        }
+    }
+    if (update) {
+        const double tot = lambda_block_sum(acc, sr);
+        if (threadIdx.x == 0) k.ws[blockIdx.x] = tot;
+    }
+}
+// ... and one block adds the block sums: thread t takes t, t + 256, ... in order, then the same fixed tree
+__global__ void __launch_bounds__(256) lambda_norm_kernel(const double* __restrict__ ws, long nblk, double* __restrict__ out) {
+    __shared__ double sr[256];        // (a kernel of its own: no tile to share the LDS with)
+    double x = 0.0;
+    for (long b = threadIdx.x; b < nblk; b += 256) x += ws[b];
+    const double tot = lambda_block_sum(x, sr);
+    if (threadIdx.x == 0) out[0] = tot;
+}
+
+// gamma [n,n] (n = no + nv, occupied first) from Xvv[a,c] = sum l2[a,b,i,j] t2[c,b,i,j], Xoo[k,i] = sum l2[a,b,i,j] t2[a,b,k,j],
+// Xov[j,b] = sum l1[a,i] (2 t2[a,b,i,j] - t2[a,b,j,i]) and l1, t1 [v,o]; one block per row of gamma:
+//   g_oo[j,i] = -2 Xoo[j,i] - sum_a t1[a,j] l1[a,i] (+ ref on the diagonal)   g_ov[j,b] = Xov[j,b] + 2 t1[b,j] + sum_i g'_oo[j,i] t1[b,i] - 2 sum_a t1[a,j] Xvv[a,b]
+//   g_vo[a,i] = l1[a,i]                                                        g_vv[a,b] = 2 Xvv[a,b] + sum_i l1[a,i] t1[b,i]
+// (g'_oo without the reference term; the row of it is staged in LDS).  Every element is one thread's sum in a fixed order.
+__global__ void __launch_bounds__(256) rdm1_assemble_kernel(const double* __restrict__ Xvv, const double* __restrict__ Xoo,
+                                                            const double* __restrict__ Xov, const double* __restrict__ l1,
+                                                            const double* __restrict__ t1, int no, int nv, double ref,
+                                                            double* __restrict__ g) {
+    extern __shared__ double row[];           // [no]
+    const int n = no + nv, r = blockIdx.x, t = threadIdx.x;
+    double* __restrict__ out = g + (long)r * n;
+    if (r < no) {
+        const int j = r;
+        for (int i = t; i < no; i += 256) {
+            double s = -2.0 * Xoo[(long)j * no + i];
+            for (int a = 0; a < nv; ++a) s -= t1[(long)a * no + j] * l1[(long)a * no + i];
+            row[i] = s;
+            out[i] = s + (i == j ? ref : 0.0);
+        }
+        __syncthreads();
+        for (int b = t; b < nv; b += 256) {
+            double s = Xov[(long)j * nv + b] + 2.0 * t1[(long)b * no + j];
+            for (int i = 0; i < no; ++i) s += row[i] * t1[(long)b * no + i];
+            for (int a = 0; a < nv; ++a) s -= 2.0 * t1[(long)a * no + j] * Xvv[(long)a * nv + b];
+            out[no + b] = s;
+        }
+        return;
+    }
+    const int a = r - no;
+    for (int i = t; i < no; i += 256) out[i] = l1[(long)a * no + i];
+    for (int b = t; b < nv; b += 256) {
+        double s = 2.0 * Xvv[(long)a * nv + b];
+        for (int i = 0; i < no; ++i) s += l1[(long)a * no + i] * t1[(long)b * no + i];
+        out[no + b] = s;
+    }
+}
+
+}  // namespace
+
+namespace dev {
+
+int64_t lambda_assemble_ws_doubles(int nv) { return (int64_t)nv * (nv + 1) / 2 + 1; }
+
+void lambda_assemble(const LambdaParts& q, int no, int nv, stream_t s) {
+    if (no < 1 || nv < 1) throw std::runtime_error("lambda_assemble: bad shape");
+    const size_t lds = sizeof(double) * ((size_t)no * (no + 1) + 256);      // the tile and the 256 partial sums behind it
+    if (!fused_pair_kernels_ok(no) || lds > 64 * 1024) throw std::runtime_error("lambda_assemble: nocc too large for the LDS tile");
+    if (!q.out1 || !q.out2) throw std::runtime_error("lambda_assemble: null output");
+    if (q.D && (!q.Pd || !q.Px || !q.S1)) throw std::runtime_error("lambda_assemble: incomplete partial results");
+    if (!q.D && (q.Pd || q.Px || q.S1 || q.Lp || q.La)) throw std::runtime_error("lambda_assemble: partial results without the direct one");
+    const bool update = q.Vijab != nullptr;
+    if ((q.La && !q.Lp) || (!q.lam1 != !q.lam2)) throw std::runtime_error("lambda_assemble: inconsistent operands");
+    if (update && (!q.eta1 || !q.eo || !q.ev || !q.err1 || !q.err2 || !q.ws || !q.norm_dev))
+        throw std::runtime_error("lambda_assemble: null operand of the update");
+    const long npairs = (long)nv * (nv + 1) / 2;
+    if (npairs + 1 > 0x7fffffffL) throw std::runtime_error("lambda_assemble: grid too large");
+    const LambdaK k{q.D, q.Pd, q.Px, q.Lp, q.La, q.S1, q.Vijab, q.eta1, q.eo, q.ev, q.lam1, q.lam2, q.out1, q.out2, q.err1, q.err2,
+                    q.ws, q.cd, q.cx, q.shift, q.err_scale, no, nv};
+    hipStream_t st = (hipStream_t)s;
+    launch_kernel(lambda_assemble_kernel, dim3((unsigned)(npairs + 1)), dim3(256), lds, st, k);
+    if (update) launch_kernel(lambda_norm_kernel, dim3(1), dim3(256), 0, st, (const double*)q.ws, npairs + 1, q.norm_dev);
+}
+
+void rdm1_assemble(const double* Xvv, const double* Xoo, const double* Xov, const double* l1, const double* t1, int no, int nv,
+                   double ref, double* g, stream_t s) {
+    if (!Xvv || !Xoo || !Xov || !l1 || !t1 || !g) throw std::runtime_error("rdm1_assemble: null operand");
+    if (no < 1 || nv < 1 || (size_t)no * sizeof(double) > 64 * 1024) throw std::runtime_error("rdm1_assemble: bad shape");
+    launch_kernel(rdm1_assemble_kernel, dim3((unsigned)(no + nv)), dim3(256), sizeof(double) * no, (hipStream_t)s, Xvv, Xoo, Xov,
+                  l1, t1, no, nv, ref, g);
+}
+
+}  // namespace dev

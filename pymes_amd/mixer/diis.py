@@ -55,6 +55,24 @@ class DIIS:
         self.error_list, self.amplitude_list, self.L = [], [], np.zeros((1, 1))
         self._state, self._stale = None, False
 
+    def restart(self, release=None):
+        """Start an empty subspace: the stored vectors are handed to ``release`` (a caller-side pool) and forgotten.  A device
+        state array of a live context is kept and rewritten in place, so that restarting does not allocate."""
+        for lst in (self.error_list, self.amplitude_list):
+            for vec in lst:
+                for arr in vec:
+                    if release is not None and not isinstance(arr, np.ndarray):
+                        release(arr)
+        self.error_list, self.amplitude_list, self.L = [], [], np.zeros((1, 1))
+        self._log_slot, self._log_pending, self._stale = None, False, False
+        st = getattr(self, "_state", None)
+        if st is not None and st.ctx.handle is not None:
+            buf = np.zeros(96)
+            buf[0] = 1
+            st.set(buf)
+        else:
+            self._state = None
+
     # -- the small algebra on the device (pymes_diis_step): L and the coefficients live in a 96-double device array; the
     # host copies (self.L, self.last_coefficients) are refreshed only when somebody asks (logging, parking)
     def _device_state(self, ctx):

@@ -478,8 +478,18 @@ class CCSD(ccd.CCD):
         orbitals with at least that MP2 occupation / the first ``fno_nv`` of them (pymes_amd/solver/fno.py).  With any of
         the three the solve runs in that space: "ccsd e", "(t) e", "t1", "t2", "hole e" and "particle e" are those of the
         correlated space (new orbitals), "fno nv" is its number of virtuals and "fno dmp2 e" the MP2 energy of the dropped
-        virtuals (0.0 with the core frozen only); the total is "ccsd(t) e" + "fno dmp2 e".  Sources: a host V_pqrs or
+        virtuals (0.0 with the core frozen only); the total is "ccsd(t) e" + "fno dmp2 e".  ``density=True`` adds "lambda1",
+        "lambda2" (the solution of the Lambda equations), "rdm1" (the one-particle response density plus 2 on the occupied
+        diagonal, [n,n], not symmetric) and "natural occupations" (eigenvalues of its symmetric part, descending), of the
+        correlated space; ``lambda_r_epsilon`` is the residual norm at which the Lambda iteration stops.  Sources: a host V_pqrs or
         replicated DeviceIntegrals; for density-fitting factors call fno.truncate and solve on its result."""
+        if kwargs.get("density"):          # refused by name before anything is truncated, uploaded or dressed
+            if self.is_dcd:
+                raise ValueError("density=True: the Lambda equations are those of the CCSD similarity transform, not defined "
+                                 "for DCSD")
+            if self.shard_integrals:
+                raise ValueError("density=True with shard_integrals=True: the left sigma reads the whole V_abcd, which an "
+                                 "integral-sharded context does not hold")
         if frozen_core or fno_occ_threshold is not None or fno_nv is not None:
             return self._solve_fno(t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv,
                                    **kwargs)
@@ -499,11 +509,18 @@ class CCSD(ccd.CCD):
         ip_roots, ea_roots = int(kwargs.get("ip_roots", 0) or 0), int(kwargs.get("ea_roots", 0) or 0)
         if (ip_roots or ea_roots) and self.is_dcd:
             raise ValueError("ip_roots / ea_roots: the IP / EA operators are the CCSD similarity transform, not defined for DCSD")
+        # density=True (opt-in): the Lambda equations of the converged state and its one-particle density
+        # (pymes_amd/solver/lambda_ccsd.py); with frozen_core / fno_* they are those of the correlated space
+        # (lambda_r_epsilon=x: the residual norm at which the Lambda iteration stops, default 1e-8)
+        density = bool(kwargs.get("density", False))
         ints, own = self._integrals(t_fock_pq, t_V_pqrs)
         ctx = ints.ctx
         st = None
         collector = ccd.quiet_collector().__enter__()      # no 40-ms generation-2 collection in the middle of an iteration
         try:
+            if density:
+                from pymes_amd.solver import lambda_ccsd
+                lambda_ccsd.check_context(ctx)             # (a sharded DeviceIntegrals of the caller: before anything is dressed)
             print_logging_info(algo_name)
             print_logging_info("Using dcsd: ", self.is_dcd, level=1)
             print_logging_info("Solving doubles amplitude equation", level=1)
@@ -552,6 +569,7 @@ class CCSD(ccd.CCD):
             if ip_roots or ea_roots:
                 e_ip, e_ea = self._ip_ea_roots(t_fock_pq, ints, st["t1"], st["t2"], ip_roots, ea_roots,
                                                kwargs.get("ip_ea_r_epsilon"))
+            lam = self._lambda_density(t_fock_pq, ints, st, kwargs.get("lambda_r_epsilon")) if density else None
             if kwargs.get("device_amplitudes"):
                 # device-resident hand-over to the callers of the solution (EOM-CCSD / FEAST: get_T1_dressed_V on the same
                 # DeviceIntegrals, EOM_CCSD.solve on the result): "t1" / "t2" are DeviceArrays of the integrals' context —
@@ -579,6 +597,8 @@ class CCSD(ccd.CCD):
                 res["ea e"] = e_ea
             if e_ip is not None and e_ea is not None:
                 res["qp gap"] = float(e_ip[0] + e_ea[0])      # the quasi-particle gap: lowest IP + lowest EA
+            if lam is not None:
+                res.update(lam)
             return res
         finally:
             collector.__exit__()
@@ -609,6 +629,25 @@ class CCSD(ccd.CCD):
             else:
                 self.ea_solver = solver
         return out
+
+    def _lambda_density(self, t_fock_pq, ints, st, r_epsilon=None):
+        """Lambda and the one-particle density of the converged amplitudes on the integrals' context (device hand-over: the
+        Fock matrix and the ten blocks of the sigma build are T1-dressed in HBM), with the orbital energies and the level
+        shift of the amplitude update."""
+        from pymes_amd.solver import lambda_ccsd
+        f = t_fock_pq.get() if isinstance(t_fock_pq, DeviceArray) else np.asarray(t_fock_pq, dtype=np.float64)
+        t1, t2 = st["t1"], st["t2"]
+        fd = self.get_T1_dressed_fock(f, t1, ints)
+        solver = lambda_ccsd.Lambda_CCSD(self.no, device=self.device)
+        if r_epsilon is not None:
+            solver.r_epsilon = float(r_epsilon)
+        dressed = self.get_T1_dressed_V(t1, ints, solver.BLOCKS)
+        out = solver.solve(fd, dressed, t2, eps=(st["eps_i"], st["eps_a"]), level_shift=st["level_shift"])
+        self.lambda_solver = solver                      # (residual norm, history, expectation() of the last solve)
+        rdm1 = solver.rdm1(t1, ctx=ints.ctx)
+        solver.t2 = None                                 # (the solver's T2 buffer goes back to the pool; the results are host arrays)
+        return {"lambda1": out["lambda1"], "lambda2": out["lambda2"], "rdm1": rdm1,
+                "natural occupations": lambda_ccsd.natural_occupations(rdm1)}
 
     def _solve_fno(self, t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv, **kwargs):
         from pymes_amd.solver import fno

@@ -1,0 +1,241 @@
+"""CCSD Lambda equations and the one-particle response density on the MI355X engine.
+
+``Lambda_CCSD(no).solve(f_dressed, dict_or_DressedDeviceIntegrals, t2)`` solves ``A^T lambda + eta = 0`` for the left-hand
+ground state of a converged CCSD solution: ``A`` is the EE-EOM-CCSD sigma (eom_ccsd.py:268-385), ``A^T`` its adjoint under the
+plain inner product on the exchange-symmetric vectors, ``eta1[a,i] = 2 f~_ov[i,a]``, ``eta2[a,b,i,j] = 2 V_ijab[i,j,a,b] -
+V_ijab[i,j,b,a]`` (formulas and caveats: include/pymes_amd.h, ``pymes_lambda_step``).  The adjoint build runs in
+the engine on the handle of the sigma build (csrc/eom.cpp, ``EomSigma::apply_left``): the same hoisted V.T intermediates read
+through transposed views.  The iteration is ``lambda <- lambda - (eta + A^T lambda) / d`` with the orbital-energy denominators
+of the CCSD update and the device DIIS; one library call and one synchronisation (the residual norm) per iteration.
+
+``rdm1(t1)`` is the one-particle response density ``gamma_pq = dL/df_pq`` of the CCSD Lagrangian plus 2 on the occupied diagonal
+(its trace is the electron count), ``expectation(O)`` the correlation part ``sum gamma_pq O_pq`` of a one-body expectation value.
+Nothing is assumed hermitian: for transcorrelated integrals the left state is not the transpose of the right one.
+"""
+import ctypes as C
+import time
+
+import numpy as np
+
+from pymes_amd import _lib
+from pymes_amd.device import Context, DeviceArray, PymesError
+from pymes_amd.integral.device import DressedDeviceIntegrals
+from pymes_amd.log import print_logging_info, print_title
+from pymes_amd.mixer.diis import DIIS
+from pymes_amd.solver.eom_ccsd import _Sigma
+
+
+# The DIIS error vector is ERR_SCALE x the update: the mixer tests linear dependence of its subspace with an ABSOLUTE 1e-12 on the
+# overlaps (the reference's bookkeeping, mixer/diis.py), which plain updates pass below a residual of 1e-6 — the extrapolation
+# then degenerates and the iteration creeps.  A fixed factor leaves the coefficients unchanged and moves that point to 1e-11.
+ERR_SCALE = 1.0e5
+
+
+def check_context(ctx):
+    """The adjoint build reads the whole V_abcd: a context that shards its integrals is refused, by the name of the mode."""
+    if getattr(ctx, "shard", None) is not None:
+        raise PymesError("Lambda_CCSD: not available with integral sharding (shard=%s): the left sigma reads the whole V_abcd"
+                         % (ctx.shard,))
+
+
+class LeftSigma(_Sigma):
+    """The handle of the sigma build with its adjoint (``pymes_eom_sigma_apply_left``) and the Lambda step on it."""
+
+    def _handle(self):
+        if self._h is None:
+            raise PymesError("the EOM sigma handle has been destroyed (its context was closed)")
+        return self._h
+
+    def apply_left_many(self, l1s, l2s, syms=None, out1=None, out2=None):
+        """[(A^T l)_1, (A^T l)_2] for the left vectors (l1s[z], l2s[z]), device arrays; l2 must be exchange-symmetric."""
+        h, c, k = self._handle(), self.ctx, len(l1s)
+        o1 = [out1[z] if out1 is not None else c.empty((self.nv, self.no)) for z in range(k)]
+        o2 = [out2[z] if out2 is not None else c.empty((self.nv, self.nv, self.no, self.no)) for z in range(k)]
+        sym = None if syms is None else (C.c_int * max(k, 1))(*[int(bool(x)) for x in syms])
+        c.lib.call("pymes_eom_sigma_apply_left", h, k, _lib.ptr_array([u.ptr for u in l1s]), _lib.ptr_array([u.ptr for u in l2s]),
+                   sym, _lib.ptr_array([x.ptr for x in o1]), _lib.ptr_array([x.ptr for x in o2]))
+        return list(zip(o1, o2))
+
+    def apply_left(self, l1, l2, l2_sym=None):
+        return self.apply_left_many([l1], [l2], None if l2_sym is None else [l2_sym])[0]
+
+    def lambda_step(self, lam, eps_o, eps_v, shift, out, err, start=False, sym=False, err_scale=1.0):
+        """One iteration (``pymes_lambda_step``): out = lam - (eta + A^T lam) / d, err = err_scale (out - lam); returns
+        |eta + A^T lam|."""
+        eo = np.ascontiguousarray(eps_o, dtype=np.float64)
+        ev = np.ascontiguousarray(eps_v, dtype=np.float64)
+        if eo.shape != (self.no,) or ev.shape != (self.nv,):
+            raise ValueError("lambda_step: eps_o / eps_v must be [no] / [nv]")
+        norm = np.zeros(1)
+        l1, l2 = (None, None) if start else (C.c_void_p(lam[0].ptr), C.c_void_p(lam[1].ptr))
+        self.ctx.lib.call("pymes_lambda_step", self._handle(), l1, l2, _lib.host_ptr(eo), _lib.host_ptr(ev), float(shift),
+                          float(err_scale), int(bool(start)), int(bool(sym)), C.c_void_p(out[0].ptr), C.c_void_p(out[1].ptr),
+                          C.c_void_p(err[0].ptr), C.c_void_p(err[1].ptr), _lib.host_ptr(norm))
+        return float(norm[0])
+
+
+def device_rdm1(ctx, t1, t2, lam1, lam2, ref=2.0):
+    """gamma + ref on the occupied diagonal as a host [n,n] array (``pymes_rdm1``); all four inputs device arrays of ctx."""
+    out = np.zeros((ctx.n, ctx.n))
+    ctx.lib.call("pymes_rdm1", ctx.handle, C.c_void_p(t1.ptr), C.c_void_p(t2.ptr), C.c_void_p(lam1.ptr), C.c_void_p(lam2.ptr),
+                 float(ref), _lib.host_ptr(out))
+    return out
+
+
+class Lambda_CCSD:
+    BLOCKS = _Sigma.BLOCKS
+
+    def __init__(self, no, r_epsilon=1.e-8, max_iter=100, device=0, diis_dim=6):
+        self.algo_name = "Lambda-CCSD"
+        self.no = no
+        self.r_epsilon = float(r_epsilon)
+        self.max_iter = int(max_iter)
+        self.device = device
+        self.diis_dim = int(diis_dim)
+        self.lambda1 = self.lambda2 = self.t2 = None
+        self.residual_norm, self.iterations, self.converged, self.history = np.inf, 0, False, []
+
+    def _open(self, f, V, t2):
+        """(ctx, handle, owns the context) for the two call forms of ``EOM_CCSD.solve``."""
+        if isinstance(f, DeviceArray):
+            f = f.get()
+        f = np.asarray(f, dtype=np.float64)
+        nv = f.shape[0] - self.no
+        if isinstance(V, DressedDeviceIntegrals):
+            ctx = V.ctx
+            check_context(ctx)
+            if ctx.no != self.no or ctx.nv != nv:
+                raise ValueError("the integrals' context does not match (no, nv) of the Fock matrix")
+            if isinstance(t2, DeviceArray) and t2.ctx is not ctx:
+                raise ValueError("t2 lives in another context than the dressed integrals")
+            V.require(self.BLOCKS)
+            t2d = t2 if isinstance(t2, DeviceArray) else ctx.array(np.asarray(t2, dtype=np.float64))
+            return f, ctx, LeftSigma(ctx, f, t2d, dressed=True), False
+        ctx = Context(self.no, nv, device=self.device)
+        try:
+            for name in self.BLOCKS:
+                blk = V.get(name)
+                if blk is None:
+                    raise KeyError("%s: the dressed block '%s' is missing from the dictionary" % (self.algo_name, name))
+                ctx.set_V_block(name, np.ascontiguousarray(blk, dtype=np.float64))
+            return f, ctx, LeftSigma(ctx, f, ctx.array(np.asarray(t2, dtype=np.float64)), dressed=False), True
+        except Exception:
+            ctx.close()
+            raise
+
+    def apply_left(self, f_dressed, V_dressed, t2, l1, l2):
+        """One adjoint build for host arrays: ((A^T l)_1, (A^T l)_2)."""
+        _, ctx, sig, own = self._open(f_dressed, V_dressed, t2)
+        try:
+            o1, o2 = sig.apply_left(ctx.array(np.asarray(l1, dtype=np.float64)), ctx.array(np.asarray(l2, dtype=np.float64)))
+            return o1.get(), o2.get()
+        finally:
+            sig.close()
+            if own:
+                ctx.close()
+
+    def solve(self, f_dressed, V_dressed, t2, eps=None, level_shift=0.0):
+        """Solve the Lambda equations.  Call forms as ``EOM_CCSD.solve``: (dressed Fock matrix, dictionary of dressed host
+        blocks, host T2) — a context is built and dies with the call — or the device-resident hand-over of a CCSD solve
+        (``DressedDeviceIntegrals``, T2 a host array or a DeviceArray of the same context).  ``eps = (eps_o, eps_v)`` and
+        ``level_shift`` are the orbital energies and the shift of the denominators (default: the diagonal of the dressed
+        Fock matrix, no shift; ``CCSD.solve(density=True)`` passes those of its own update).  Returns a dictionary with
+        "lambda1" [v,o], "lambda2" [v,v,o,o] (host), "residual norm" (|eta + A^T lambda|), "iterations", "converged"."""
+        print_title("Lambda-CCSD Solver", )
+        t_init = time.time()
+        f, ctx, sig, own = self._open(f_dressed, V_dressed, t2)
+        no, nv = self.no, ctx.nv
+        eps_o, eps_v = (f.diagonal()[:no].copy(), f.diagonal()[no:].copy()) if eps is None else eps
+        mixer = DIIS(dim_space=self.diis_dim)
+        s1, s2 = (nv, no), (nv, nv, no, no)
+        new = lambda: (ctx.pool_get(s1), ctx.pool_get(s2))
+        self.history, self.converged = [], False
+        held = []
+        try:
+            lam, err = new(), new()
+            sig.lambda_step(None, eps_o, eps_v, level_shift, lam, err, start=True)          # lambda = -eta / d
+            for arr in err:
+                ctx.pool_put(arr)
+            norm, it = np.inf, 0
+            for it in range(1, self.max_iter + 1):
+                out, err = new(), new()
+                norm = sig.lambda_step(lam, eps_o, eps_v, level_shift, out, err, sym=True, err_scale=ERR_SCALE)
+                self.history.append(norm)
+                print_logging_info("Iteration = ", it, level=1)
+                print_logging_info("Norm Residual = {:.6e}".format(norm), level=2)
+                if not np.isfinite(norm):
+                    raise np.linalg.LinAlgError("Lambda-CCSD: the residual norm is not finite")
+                self.converged = norm < self.r_epsilon
+                if self.converged or it == self.max_iter:
+                    # the norm is that of `lam`, which therefore is what is returned — converged or not
+                    for arr in out + err:
+                        ctx.pool_put(arr)
+                    break
+                if len(mixer.error_list) == mixer.dim_space:
+                    # a full subspace is dropped, not shifted: the mixer reproduces the reference's bookkeeping, whose shifted
+                    # copy of the overlap matrix leaves out the second-newest vector (mixer/diis.py) and stalls this iteration
+                    mixer.restart(release=ctx.pool_put)
+                mixed = mixer.mix(list(err), list(out), release=ctx.pool_put, on_device=True)
+                for arr in lam:                          # (the history keeps `out` and `err`, never the extrapolated vector)
+                    ctx.pool_put(arr)
+                lam = tuple(mixed)
+            self.iterations, self.residual_norm = it, norm
+            self.lambda1, self.lambda2 = lam[0].get(), lam[1].get()
+            held = list(lam)
+            self.t2 = sig.T.get() if own else sig.T
+            if not self.converged:
+                print_logging_info("A converged solution is not found!", level=1)
+            print_logging_info("{:.3f} seconds spent on Lambda-CCSD".format(time.time() - t_init), level=1)
+            return {"lambda1": self.lambda1, "lambda2": self.lambda2, "residual norm": norm, "iterations": it,
+                    "converged": self.converged}
+        finally:
+            alive = not own and ctx.handle is not None
+            mixer.restart(release=ctx.pool_put if alive else None)
+            sig.close()
+            if own:
+                ctx.close()
+            elif alive:
+                for arr in held:
+                    ctx.pool_put(arr)
+
+    def rdm1(self, t1, ctx=None):
+        """The one-particle density [n,n] (occupied orbitals first) of the last solve: the response density plus 2 on the
+        occupied diagonal.  Not symmetric, and not symmetrised.  ``ctx``: a live context to run on (default: a small one of
+        its own; the density reads no integrals)."""
+        if self.lambda1 is None:
+            raise RuntimeError("rdm1: needs a finished solve()")
+        if self.t2 is None:
+            raise RuntimeError("rdm1: the amplitudes of the solve are no longer held (CCSD.solve(density=True) returns \"rdm1\")")
+        if ctx is None and isinstance(self.t2, DeviceArray) and self.t2.ctx.handle is not None:
+            ctx = self.t2.ctx
+        own = ctx is None
+        if own:
+            ctx = Context(self.no, self.lambda1.shape[0], device=self.device)
+
+        def on_ctx(x):
+            if isinstance(x, DeviceArray):
+                return x if x.ctx is ctx else ctx.array(x.get())
+            return ctx.array(np.ascontiguousarray(x, dtype=np.float64))
+        try:
+            g = device_rdm1(ctx, on_ctx(t1), on_ctx(self.t2), on_ctx(self.lambda1), on_ctx(self.lambda2))
+        finally:
+            if own:
+                ctx.close()
+        self.gamma = g
+        return g
+
+    def expectation(self, O, t1=None):
+        """sum gamma_pq O_pq: the correlation part of the expectation value of the one-body operator O (orbital basis of f).
+        Uses the density of the last ``rdm1`` call (``t1`` given: computes it first)."""
+        if t1 is not None:
+            self.rdm1(t1)
+        if getattr(self, "gamma", None) is None:
+            raise RuntimeError("expectation: call rdm1(t1) first")
+        g = self.gamma.copy()
+        g[np.arange(self.no), np.arange(self.no)] -= 2.0
+        return float((g * np.asarray(O, dtype=np.float64)).sum())
+
+
+def natural_occupations(rdm1):
+    """Eigenvalues of the symmetrised density, descending."""
+    return np.linalg.eigvalsh(0.5 * (rdm1 + rdm1.T))[::-1].copy()

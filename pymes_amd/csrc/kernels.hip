@@ -3793,6 +3793,15 @@ void launch_gemm_glds(const GemmK& k, long nblocks, hipStream_t st) {
 // register-staged kernel wins)
 inline long dma_min_k() { return 384L; }
 
+// The k-cut of a launch: `ktiles` k-tiles in `want` equal runs of whole k-tiles.  Returns the number of cuts that results
+// (fewer than `want` when the last runs come out empty) and, given a block, sets its kchunk / nsplit to it.
+inline long cut_k(long ktiles, long want, GemmK* k = nullptr) {
+    const long kt_per = (ktiles + want - 1) / want;
+    const long nsplit = std::max<long>(1, (ktiles + kt_per - 1) / std::max<long>(kt_per, 1));
+    if (k) { k->kchunk = (int)std::max<long>(kt_per * BK, BK); k->nsplit = (int)nsplit; }
+    return nsplit;
+}
+
 // ---- launch plan of the LDS-DMA kernel -------------------------------------------------------------------------------
 // A CU turns out one tile per tile-time tau whether it holds one block or two (two resident blocks share its MFMA pipes),
 // and the hardware hands the next block of the grid to whichever CU frees a slot: a launch costs about (work of the
@@ -3819,8 +3828,7 @@ inline DmaPlan plan_dma(long tiles, long ktiles, long ws_tiles) {
         const long smax = std::max<long>(1, std::min<long>(std::min<long>(cap, max_cuts), ws_tiles / tail));
         double best_cost = 1e300;
         for (long sp = 1; sp <= smax; ++sp) {
-            const long kt_per = (ktiles + sp - 1) / sp, ns = (ktiles + kt_per - 1) / kt_per;       // the cuts that result
-            if (ns != sp) continue;
+            if (cut_k(ktiles, sp) != sp) continue;
             double c = (double)((tail * sp + 255) / 256) / (double)sp + (double)sp * 3.0 / tau;
             if (sp > 1) c += (5.0 + 0.0437 * (double)tail * (double)(sp + 1)) / tau;
             if (c < best_cost - 1e-9) { best_cost = c; best = DmaPlan{whole, tail, (int)sp}; }
@@ -3872,10 +3880,87 @@ bool dispatch_layout(const GemmK& k, bool akc, bool bkc, int vec, long nblocks, 
 inline bool even(long x) { return (x & 1) == 0; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- one product, described once -------------------------------------------------------------------------------------
+// What dev::gemm works out about a product before it chooses a launch form; every form (a launch of its own, the two
+// halves of the open group, a task of the open phase, the matrix-vector kernels) reads this and nothing else.
+struct GemmProduct {
+    const dev::Gemm& g;
+    long a_sm, a_sk, b_sk, b_sn;       // strides with an extent-1 dimension normalised to the unit-stride role
+    bool akc, bkc;                     // A / B contiguous along K
+    long a_ld, b_ld;                   // pitch of the other dimension
+    long nbatch, ktiles;
+    int Mc, Nc;                        // GemmK::Mc / Nc
+    int vec;                           // 2: 16-byte global loads
+    double flops;
+};
+inline double gemm_flops(const dev::Gemm& g) {
+    return 2.0 * (double)g.M * (double)g.N * (double)g.K * (double)(g.nb1 * g.nb2);
+}
+inline GemmProduct describe_product(const dev::Gemm& g, long a_sm, long a_sk, long b_sk, long b_sn) {
+    GemmProduct p{g, a_sm, a_sk, b_sk, b_sn, a_sk == 1, b_sk == 1};
+    p.a_ld = p.akc ? a_sm : a_sk;
+    p.b_ld = p.bkc ? b_sn : b_sk;
+    p.nbatch = g.nb1 * g.nb2;
+    p.ktiles = (g.K + BK - 1) / BK;
+    // ---- 16-byte global loads need even strides/extents and aligned bases --------------
+    // An odd M (N) of an M- (N-)contiguous operand is fine when the pitch has room for one more element: the
+    // pair load at the edge then reads a pad element that only feeds a row (column) of C which is never stored.
+    p.Mc = (int)g.M; p.Nc = (int)g.N;
+    if (!p.akc && (g.M & 1) && p.a_ld > g.M) p.Mc = (int)g.M + 1;
+    if (!p.bkc && (g.N & 1) && p.b_ld > g.N) p.Nc = (int)g.N + 1;
+    const long a_contig_extent = p.akc ? g.K : p.Mc, b_contig_extent = p.bkc ? g.K : p.Nc;
+    p.vec = even(p.a_ld) && even(p.b_ld) && even(a_contig_extent) && even(b_contig_extent) && aligned16(g.A) && aligned16(g.B) &&
+            even(g.a_b1) && even(g.a_b2) && even(g.b_b1) && even(g.b_b2) ? 2 : 1;
+    p.flops = gemm_flops(g);
+    return p;
+}
+// layout of a product as the grouped kernel and the phase kernel switch on it
+inline int layout_variant(const GemmProduct& p) { return (p.akc ? 4 : 0) | (p.bkc ? 2 : 0) | (p.vec == 2 ? 1 : 0); }
+
+// The argument block of a product on BM x BN tiles: everything the kernel reads except the cut (kchunk / nsplit: cut_k; the
+// workspace of the partial tiles; tile_begin and the mixed plan where a launch covers part of the tiles).
+inline GemmK make_gemmk(const GemmProduct& p, int BM, int BN) {
+    const dev::Gemm& g = p.g;
+    GemmK k;
+    k.A = g.A; k.B = g.B; k.C = g.C;
+    k.Cin = g.Cin ? g.Cin : g.C;
+    k.a_ld = p.a_ld; k.b_ld = p.b_ld; k.ldc = g.ldc;
+    k.M = (int)g.M; k.N = (int)g.N; k.K = (int)g.K;
+    k.Mc = p.Mc; k.Nc = p.Nc;
+    k.alpha = g.alpha; k.beta = g.beta;
+    k.tiles_m = (int)((g.M + BM - 1) / BM);
+    k.tiles_n = (int)((g.N + BN - 1) / BN);
+    k.tile_begin = 0;
+    k.nb2 = g.nb2;
+    k.a_b1 = g.a_b1; k.a_b2 = g.a_b2; k.b_b1 = g.b_b1; k.b_b2 = g.b_b2; k.c_b1 = g.c_b1; k.c_b2 = g.c_b2;
+    k.ws = nullptr;
+    return k;
+}
+
+// k-split of the last, partially filled round of tiles (all of them for a small output).  Tiles all cost the same, so a
+// launch takes ceil(tiles / slots) tile-times; cutting the K range of the remainder tiles s ways over the idle CUs makes the
+// last round ceil(rem s / slots) rounds of 1/s tile-time each.  Few remainder tiles may be cut finer (huge K, tiny output);
+// every cut keeps min_kt k-tiles and the partial tiles fit ws_tiles.
+struct TailSplit { long main_tiles, tail_tiles; int split; };
+inline TailSplit plan_tail(long tiles, long ktiles, long slots, long min_kt, long ws_tiles) {
+    const long rem = tiles % slots;
+    if (ktiles < 16 || rem == 0) return {tiles, 0, 1};
+    long best = 1;
+    double best_cost = 1.0;
+    long smax = std::min<long>(512, std::max<long>(8, 2048 / rem));
+    smax = std::min<long>(smax, ktiles / min_kt);
+    smax = std::min<long>(smax, ws_tiles / rem);
+    for (long sp = 2; sp <= smax; ++sp) {
+        const double cost = (double)((rem * sp + slots - 1) / slots) / (double)sp + 1e-5 * sp;
+        if (cost < best_cost - 1e-9) { best_cost = cost; best = sp; }
+    }
+    if (best >= 2 && best_cost < 0.8) return {tiles - rem, rem, (int)best};        // worth it below 0.8 of a tile-time
+    return {tiles, 0, 1};
+}
 
 // M = 1 or N = 1 (no batch): matrix-vector product on the streaming kernels above.  Returns false when the shape does not
 // qualify (then the MFMA GEMM handles it).  Timed under the same profiling events as a GEMM call (class 0).
-bool gemv_dispatch(const dev::Gemm& g, long a_sm, long a_sk, long b_sk, long b_sn, hipStream_t st);
+bool gemv_dispatch(const GemmProduct& p, hipStream_t st);
 
 // dev::gemv_batch_begin/end: weighted-column-sum products with beta == 0 issued in between are collected and launched
 // together; any other launch that could read their results (permute, a GEMM of another kind) flushes them first, so the
@@ -4009,12 +4094,7 @@ void gemm_group_launch(bool dma) {
         GemmK& k = ks[i];
         long sp = std::max<long>(1, std::min<long>(std::min<long>(want, max_cuts), ktiles[i] / min_ktiles));
         while (sp > 1 && ws_used + tiles[i] * sp * tile_doubles > q.ws_doubles) --sp;
-        const long kt_per = (ktiles[i] + sp - 1) / sp;
-        k.kchunk = (int)std::max<long>(kt_per * BK, BK);
-        k.nsplit = (int)std::max<long>(1, (ktiles[i] + kt_per - 1) / std::max<long>(kt_per, 1));
-        k.tile_begin = 0;
-        k.ws = nullptr;
-        if (k.nsplit > 1) {
+        if (cut_k(ktiles[i], sp, &k) > 1) {
             k.ws = q.ws + ws_used;
             ws_used += tiles[i] * k.nsplit * tile_doubles;
             red.g[red.n] = k;
@@ -4220,62 +4300,41 @@ void prof_query(int kernel_class, long* calls, long* kernel_launches, double* ms
 namespace {
 // Queue a mid-size product in the LDS-DMA layout for the grouped 128 x 128 launch of the open group (tried before the open
 // phase gets the product: deep products belong on the LDS-DMA kernel, not on the 64 x 64 tiles of a phase).
-bool gemm_group_take_dma(const Gemm& g, bool a_kcontig, bool b_kcontig, int64_t a_sm, int64_t a_sk, int64_t b_sk, int64_t b_sn,
-                         hipStream_t st) {
+bool gemm_group_take_dma(const GemmProduct& p, hipStream_t st) {
+    const Gemm& g = p.g;
     GemmGroup& q = g_group;
     if (q.st != st) return false;
-    const long nbatch = g.nb1 * g.nb2;
-    const long t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128) * nbatch;
-    const long ktiles = (g.K + BK - 1) / BK;
-    if (t128 >= 256 && ktiles * BK >= 256) return false;
-    {
-        const long a_ld = a_kcontig ? a_sm : a_sk, b_ld = b_kcontig ? b_sn : b_sk;
-        const bool vec2 = even(a_ld) && even(b_ld) && even(g.K) && (even(g.N) || b_ld > g.N) && aligned16(g.A) && aligned16(g.B) &&
-                          even(g.a_b1) && even(g.a_b2) && even(g.b_b1) && even(g.b_b2);
-        const bool off32 = 128 * a_ld * 8 + 4096 < (1L << 32) && 16 * b_ld * 8 + 4096 < (1L << 32);
-        // (enough blocks of >= dma_min_k depth for half the chip, else the 64 x 64 group fills it better)
-        const bool fills = t128 * std::min<long>(16, g.K / dma_min_k()) >= 128;
-        if (a_kcontig && !b_kcontig && vec2 && off32 && g.M > 64 && g.N > 64 && g.K >= 2 * dma_min_k() && g.splitk_ws && fills &&
-            t128 <= 0x3fffffffL / 64) {
-            if (q.nd == kGroupMax) gemm_group_flush_dma();
-            GemmK k;
-            k.A = g.A; k.B = g.B; k.C = g.C;
-            k.Cin = g.Cin ? g.Cin : g.C;
-            k.a_ld = a_ld; k.b_ld = b_ld; k.ldc = g.ldc;
-            k.M = (int)g.M; k.N = (int)g.N; k.K = (int)g.K;
-            k.Mc = k.M;
-            k.Nc = ((g.N & 1) && b_ld > g.N) ? k.N + 1 : k.N;
-            k.alpha = g.alpha; k.beta = g.beta;
-            k.nb2 = g.nb2;
-            k.a_b1 = g.a_b1; k.a_b2 = g.a_b2; k.b_b1 = g.b_b1; k.b_b2 = g.b_b2; k.c_b1 = g.c_b1; k.c_b2 = g.c_b2;
-            k.ws = nullptr;
-            k.tiles_m = (int)((g.M + 127) / 128);
-            k.tiles_n = (int)((g.N + 127) / 128);
-            const int i = q.nd++;
-            q.kd[i] = k;
-            q.tiles_d[i] = t128;
-            q.ktiles_d[i] = ktiles;
-            q.flops_d[i] = 2.0 * (double)g.M * (double)g.N * (double)g.K * (double)nbatch;
-            q.ws = g.splitk_ws;
-            q.ws_doubles = g.splitk_ws_doubles;
-            ++q.products;
-            return true;
-        }
-    }
-    return false;
+    const long t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128) * p.nbatch;
+    if (t128 >= 256 && p.ktiles * BK >= 256) return false;
+    const bool off32 = 128 * p.a_ld * 8 + 4096 < (1L << 32) && 16 * p.b_ld * 8 + 4096 < (1L << 32);
+    // (enough blocks of >= dma_min_k depth for half the chip, else the 64 x 64 group fills it better)
+    const bool fills = t128 * std::min<long>(16, g.K / dma_min_k()) >= 128;
+    // (p.vec at akc && !bkc: even pitches and K, aligned bases, even batch strides, and N even or b_ld > N — Nc even)
+    if (!(p.akc && !p.bkc && p.vec == 2 && off32 && g.M > 64 && g.N > 64 && g.K >= 2 * dma_min_k() && g.splitk_ws && fills &&
+          t128 <= 0x3fffffffL / 64))
+        return false;
+    if (q.nd == kGroupMax) gemm_group_flush_dma();
+    const int i = q.nd++;
+    q.kd[i] = make_gemmk(p, 128, 128);
+    q.tiles_d[i] = t128;
+    q.ktiles_d[i] = p.ktiles;
+    q.flops_d[i] = p.flops;
+    q.ws = g.splitk_ws;
+    q.ws_doubles = g.splitk_ws_doubles;
+    ++q.products;
+    return true;
 }
 // Queue a product for the open group.  false: not a small product (it runs as its own launch, after the queue).
-bool gemm_group_take(const Gemm& g, bool a_kcontig, bool b_kcontig, int64_t a_sm, int64_t a_sk, int64_t b_sk, int64_t b_sn,
-                     hipStream_t st) {
+bool gemm_group_take(const GemmProduct& p, hipStream_t st) {
+    const Gemm& g = p.g;
     GemmGroup& q = g_group;
     if (q.st != st) return false;
-    const long nbatch = g.nb1 * g.nb2;
-    const long t64 = ((g.M + 63) / 64) * ((g.N + 63) / 64) * nbatch, t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128) * nbatch;
-    const long ktiles = (g.K + BK - 1) / BK;
+    const long ktiles = p.ktiles;
+    const long t64 = ((g.M + 63) / 64) * ((g.N + 63) / 64) * p.nbatch, t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128) * p.nbatch;
     // big products keep their own launches: enough 128 x 128 tiles for the chip, or deep enough for the LDS-DMA kernel's
     // k-split; and so do the long streaming products (one pass over a multi-GB block: the single-buffer kernel moves more)
     if (t128 >= 256 && ktiles * BK >= 256) return false;
-    if (gemm_group_take_dma(g, a_kcontig, b_kcontig, a_sm, a_sk, b_sk, b_sn, st)) return true;
+    if (gemm_group_take_dma(p, st)) return true;
     if (t128 < 256 && g.K / std::max<long>(1, (512 + t128 - 1) / t128) >= dma_min_k() && g.M > 64 && g.N > 64) return false;
     if (t64 * ktiles > 400000 || t64 > 0x3fffffffL / 16) return false;
     // streaming shapes (short K against a skinny side; tiny outputs over a huge K): one pass over a big operand, bound by the
@@ -4283,38 +4342,17 @@ bool gemm_group_take(const Gemm& g, bool a_kcontig, bool b_kcontig, int64_t a_sm
     // (from a few rounds of blocks on: tiny ones lose nothing in a group)
     if (t64 * ktiles >= 4096 && ((g.K <= 256 && std::min(g.M, g.N) <= 256) || (g.M <= 256 && g.N <= 256 && g.K >= 65536)))
         return false;
-    GemmK k;
-    k.A = g.A; k.B = g.B; k.C = g.C;
-    k.Cin = g.Cin ? g.Cin : g.C;
-    k.a_ld = a_kcontig ? a_sm : a_sk;
-    k.b_ld = b_kcontig ? b_sn : b_sk;
-    k.ldc = g.ldc;
-    k.M = (int)g.M; k.N = (int)g.N; k.K = (int)g.K;
-    k.alpha = g.alpha; k.beta = g.beta;
-    k.nb2 = g.nb2;
-    k.a_b1 = g.a_b1; k.a_b2 = g.a_b2; k.b_b1 = g.b_b1; k.b_b2 = g.b_b2; k.c_b1 = g.c_b1; k.c_b2 = g.c_b2;
-    k.ws = nullptr;
-    k.tiles_m = (int)((g.M + 63) / 64);
-    k.tiles_n = (int)((g.N + 63) / 64);
-    int vec = 2;
-    k.Mc = k.M; k.Nc = k.N;
-    if (!a_kcontig && (g.M & 1) && k.a_ld > g.M) k.Mc = k.M + 1;
-    if (!b_kcontig && (g.N & 1) && k.b_ld > g.N) k.Nc = k.N + 1;
-    const long a_contig_extent = a_kcontig ? g.K : k.Mc, b_contig_extent = b_kcontig ? g.K : k.Nc;
-    if (!even(k.a_ld) || !even(k.b_ld) || !even(a_contig_extent) || !even(b_contig_extent) || !aligned16(g.A) || !aligned16(g.B) ||
-        !even(g.a_b1) || !even(g.a_b2) || !even(g.b_b1) || !even(g.b_b2))
-        vec = 1;
     if (q.n == kGroupMax) gemm_group_flush();
     // the grid of a group is one int: flush early when the running block count would not fit comfortably
     long queued = 0;
     for (int i = 0; i < q.n; ++i) queued += q.tiles[i];
     if (queued + t64 > 0x3fffffffL / 16) gemm_group_flush();
     const int i = q.n++;
-    q.k[i] = k;
-    q.variant[i] = (a_kcontig ? 4 : 0) | (b_kcontig ? 2 : 0) | (vec == 2 ? 1 : 0);
+    q.k[i] = make_gemmk(p, 64, 64);
+    q.variant[i] = layout_variant(p);
     q.tiles[i] = t64;
     q.ktiles[i] = ktiles;
-    q.flops[i] = 2.0 * (double)g.M * (double)g.N * (double)g.K * (double)nbatch;
+    q.flops[i] = p.flops;
     q.ws = g.splitk_ws;
     q.ws_doubles = g.splitk_ws ? g.splitk_ws_doubles : 0;
     ++q.products;
@@ -4326,72 +4364,34 @@ namespace {
 // A small product as tasks of the open phase: 64 x 64 tiles (64 x 32 / 32 x 64 when a side is at most 32), the k-split rule of
 // the register-staged launches of dev::gemm, its partial tiles in a slice of the workspace and their reduction as a task
 // of the next level.  false: not small (or no phase open) — the caller goes on with the launches of its own.
-bool phase_gemm(const Gemm& g, bool akc, bool bkc, int64_t a_sm, int64_t a_sk, int64_t b_sk, int64_t b_sn, hipStream_t st) {
+bool phase_gemm(const GemmProduct& p, hipStream_t st) {
     if (!phase_open(st)) return false;
-    const long nbatch = g.nb1 * g.nb2;
-    const double dM = (double)g.M, dN = (double)g.N, dK = (double)g.K, dB = (double)nbatch;
+    const Gemm& g = p.g;
+    const long ktiles = p.ktiles;
+    const double dM = (double)g.M, dN = (double)g.N, dK = (double)g.K, dB = (double)p.nbatch;
     const double cost = 2.0 * dM * dN * dK * dB / 4.0e7 + 8.0 * (dM * dK + dK * dN + (g.beta != 0.0 ? 2.0 : 1.0) * dM * dN) * dB / 4.0e6;
     if (!phase_small(cost)) return false;
     if (g.splitk_ws) { g_phase.ws = g.splitk_ws; g_phase.ws_doubles = g.splitk_ws_doubles; }     // (of THIS phase's engine: cleared by the flush)
     // deep products with enough 128 x 128 tiles for the LDS-DMA kernel (k-split over the chip) belong there, small as they may be
     {
-        const long t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128) * nbatch;
+        const long t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128) * p.nbatch;
         if (g.M > 64 && g.N > 64 && g.K >= 2 * dma_min_k() && t128 * std::min<long>(16, g.K / dma_min_k()) >= 128) return false;
     }
     int BM = 64, BN = 64;
     if (g.N <= 32) BN = 32;
     else if (g.M <= 32) BM = 32;
-    GemmK k;
-    k.A = g.A; k.B = g.B; k.C = g.C;
-    k.Cin = g.Cin ? g.Cin : g.C;
-    k.a_ld = akc ? a_sm : a_sk;
-    k.b_ld = bkc ? b_sn : b_sk;
-    k.ldc = g.ldc;
-    k.M = (int)g.M; k.N = (int)g.N; k.K = (int)g.K;
-    k.alpha = g.alpha; k.beta = g.beta;
-    k.nb2 = g.nb2;
-    k.a_b1 = g.a_b1; k.a_b2 = g.a_b2; k.b_b1 = g.b_b1; k.b_b2 = g.b_b2; k.c_b1 = g.c_b1; k.c_b2 = g.c_b2;
-    k.ws = nullptr;
-    k.tiles_m = (int)((g.M + BM - 1) / BM);
-    k.tiles_n = (int)((g.N + BN - 1) / BN);
-    const long tiles = (long)k.tiles_m * k.tiles_n * nbatch;
+    GemmK k = make_gemmk(p, BM, BN);
+    const long tiles = (long)k.tiles_m * k.tiles_n * p.nbatch;
     if (tiles > 0x3fffffffL / 16) return false;
-    int vec = 2;
-    k.Mc = k.M; k.Nc = k.N;
-    if (!akc && (g.M & 1) && k.a_ld > g.M) k.Mc = k.M + 1;
-    if (!bkc && (g.N & 1) && k.b_ld > g.N) k.Nc = k.N + 1;
-    {
-        const long ace = akc ? g.K : k.Mc, bce = bkc ? g.K : k.Nc;
-        if (!even(k.a_ld) || !even(k.b_ld) || !even(ace) || !even(bce) || !aligned16(g.A) || !aligned16(g.B) || !even(g.a_b1) ||
-            !even(g.a_b2) || !even(g.b_b1) || !even(g.b_b2))
-            vec = 1;
-    }
-    const long ktiles = (g.K + BK - 1) / BK;
-    // k-split of the last, partially filled round of blocks (all of them for a small output), as dev::gemm does it
-    const long slots = 1024;
+    // k-split of the last, partially filled round of blocks (all of them for a small output): four co-resident blocks per CU
     const long ws_cap = g.splitk_ws ? g.splitk_ws_doubles / ((long)BM * BN) : 0;
-    long main_tiles = tiles, tail_tiles = 0;
-    int tail_split = 1;
-    if (ktiles >= 16) {
-        const long rem = tiles % slots;
-        if (rem > 0) {
-            long best = 1;
-            double best_cost = 1.0;
-            long smax = std::min<long>(512, std::max<long>(8, 2048 / rem));
-            smax = std::min<long>(smax, ktiles / 8);
-            smax = std::min<long>(smax, ws_cap / rem);
-            for (long sp = 2; sp <= smax; ++sp) {
-                const double c = (double)((rem * sp + slots - 1) / slots) / (double)sp + 1e-5 * sp;
-                if (c < best_cost - 1e-9) { best_cost = c; best = sp; }
-            }
-            if (best >= 2 && best_cost < 0.8) { tail_tiles = rem; main_tiles = tiles - rem; tail_split = (int)best; }
-        }
-    }
-    const unsigned short sub = (unsigned short)((BM == 64 && BN == 64 ? 0 : (BN == 32 ? 1 : 2)) * 8 + (akc ? 4 : 0) + (bkc ? 2 : 0) + (vec == 2 ? 1 : 0));
-    const int a_t = akc ? (BK + 2) * BM : (BM + 16) * BK, b_t = bkc ? (BK + 2) * BN : (BN + 16) * BK;
+    const TailSplit ts = plan_tail(tiles, ktiles, 1024, 8, ws_cap);
+    const long main_tiles = ts.main_tiles, tail_tiles = ts.tail_tiles;
+    const unsigned short sub = (unsigned short)((BM == 64 && BN == 64 ? 0 : (BN == 32 ? 1 : 2)) * 8 + layout_variant(p));
+    const int a_t = p.akc ? (BK + 2) * BM : (BM + 16) * BK, b_t = p.bkc ? (BK + 2) * BN : (BN + 16) * BK;
     const int lds = 2 * (a_t + b_t) * (int)sizeof(double);
-    const PhaseRange rA = pbox(g.A, {{g.M, a_sm}, {g.K, a_sk}, {g.nb1, g.a_b1}, {g.nb2, g.a_b2}}, 1);
-    const PhaseRange rB = pbox(g.B, {{g.K, b_sk}, {g.N, b_sn}, {g.nb1, g.b_b1}, {g.nb2, g.b_b2}}, 1);
+    const PhaseRange rA = pbox(g.A, {{g.M, p.a_sm}, {g.K, p.a_sk}, {g.nb1, g.a_b1}, {g.nb2, g.a_b2}}, 1);
+    const PhaseRange rB = pbox(g.B, {{g.K, p.b_sk}, {g.N, p.b_sn}, {g.nb1, g.b_b1}, {g.nb2, g.b_b2}}, 1);
     const PhaseRange rC = pbox(g.C, {{g.M, g.ldc}, {g.N, 1}, {g.nb1, g.c_b1}, {g.nb2, g.c_b2}});
     const PhaseRange rCin = (g.beta != 0.0 && k.Cin != g.C) ? pbox(k.Cin, {{g.M, g.ldc}, {g.N, 1}, {g.nb1, g.c_b1}, {g.nb2, g.c_b2}})
                                                            : PhaseRange{0, 0};
@@ -4401,12 +4401,9 @@ bool phase_gemm(const Gemm& g, bool akc, bool bkc, int64_t a_sm, int64_t a_sk, i
     const bool whole_dense = dense_c && (main_tiles == 0 || tail_tiles == 0) && (g.beta == 0.0 || (g.beta == 1.0 && k.Cin == g.C));
     const signed char acc = g.beta == 1.0 ? 1 : 0;
     auto add = [&](long tile_begin, long ntiles, int nsplit, double share) {
-        const long kt_per = (ktiles + nsplit - 1) / nsplit;
-        k.kchunk = (int)std::max<long>(kt_per * BK, BK);
-        k.nsplit = (int)std::max<long>(1, (ktiles + kt_per - 1) / std::max<long>(kt_per, 1));
         k.tile_begin = tile_begin;
         k.ws = nullptr;
-        if (k.nsplit > 1) {
+        if (cut_k(ktiles, nsplit, &k) > 1) {
             k.ws = phase_ws(g.splitk_ws, g.splitk_ws_doubles, ntiles * k.nsplit * (long)BM * BN);
             if (!k.ws) { k.nsplit = 1; k.kchunk = (int)(ktiles * BK); }
         }
@@ -4428,7 +4425,7 @@ bool phase_gemm(const Gemm& g, bool akc, bool bkc, int64_t a_sm, int64_t a_sk, i
     };
     const double fmain = tiles > 0 ? (double)main_tiles / (double)tiles : 1.0;
     if (main_tiles > 0) add(0, main_tiles, 1, fmain);
-    if (tail_tiles > 0) add(main_tiles, tail_tiles, tail_split, 1.0 - fmain);
+    if (tail_tiles > 0) add(main_tiles, tail_tiles, ts.split, 1.0 - fmain);
     return true;
 }
 }  // namespace
@@ -4500,32 +4497,20 @@ void gemm(const Gemm& g, stream_t s) {
     if (b_sk != 1 && b_sn != 1) { if (g.K == 1) b_sk = 1; else if (g.N == 1) b_sn = 1; }
     if (!(a_sk == 1 || a_sm == 1)) throw std::runtime_error("gemm: A has no unit stride");
     if (!(b_sk == 1 || b_sn == 1)) throw std::runtime_error("gemm: B has no unit stride");
-    const bool a_kcontig = (a_sk == 1);
-    const bool b_kcontig = (b_sk == 1);
-    if (gemv_dispatch(g, a_sm, a_sk, b_sk, b_sn, st)) return;
+    const GemmProduct p = describe_product(g, a_sm, a_sk, b_sk, b_sn);
+    if (gemv_dispatch(p, st)) return;
     gemv_batch_flush();          // (not flush_deferred: the product may yet join the open group or the open phase)
-    if (g_group.active && gemm_group_take_dma(g, a_kcontig, b_kcontig, a_sm, a_sk, b_sk, b_sn, st)) return;
-    if (phase_gemm(g, a_kcontig, b_kcontig, a_sm, a_sk, b_sk, b_sn, st)) return;
-    if (g_group.active && gemm_group_take(g, a_kcontig, b_kcontig, a_sm, a_sk, b_sk, b_sn, st)) return;
+    if (g_group.active && gemm_group_take_dma(p, st)) return;
+    if (phase_gemm(p, st)) return;
+    if (g_group.active && gemm_group_take(p, st)) return;
     gemm_group_flush();          // (a product that is launched on its own keeps its place in the order of effects)
-    GemmK k;
-    k.A = g.A; k.B = g.B; k.C = g.C;
-    k.Cin = g.Cin ? g.Cin : g.C;
-    k.a_ld = a_kcontig ? a_sm : a_sk;
-    k.b_ld = b_kcontig ? b_sn : b_sk;
-    k.ldc = g.ldc;
-    k.M = (int)g.M; k.N = (int)g.N; k.K = (int)g.K;
-    k.alpha = g.alpha; k.beta = g.beta;
-    k.nb2 = g.nb2;
-    k.a_b1 = g.a_b1; k.a_b2 = g.a_b2; k.b_b1 = g.b_b1; k.b_b2 = g.b_b2; k.c_b1 = g.c_b1; k.c_b2 = g.c_b2;
-    k.ws = nullptr;
+    const long ktiles = p.ktiles;
 
     // ---- tile shape: 128x128 unless a dimension is small -----------------------------
     int BM = 128, BN = 128;
     if (g.N <= 64) BN = 64;
     if (g.M <= 64) BM = 64;
-    const long nbatch = g.nb1 * g.nb2;
-    auto ntiles = [&](int bm, int bn) { return ((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * nbatch; };
+    auto ntiles = [&](int bm, int bn) { return ((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * p.nbatch; };
     // under-filled chip (<1 block per CU at 128x128): 64x64 tiles give 4x the blocks — unless K is deep enough to fill
     // the chip by k-splitting with >= 1024 per split, which keeps the (faster) 128x128 LDS-DMA kernel
     if (BM == 128 && BN == 128 && ntiles(128, 128) < 256) {
@@ -4551,86 +4536,41 @@ void gemm(const Gemm& g, stream_t s) {
         if (g.N <= 32) BN = 32;
         else if (g.M <= 32) BM = 32;
     }
-    k.tiles_m = (int)((g.M + BM - 1) / BM);
-    k.tiles_n = (int)((g.N + BN - 1) / BN);
-    const long tiles = (long)k.tiles_m * k.tiles_n * nbatch;
-
-    // ---- 16-byte global loads need even strides/extents and aligned bases --------------
-    // An odd M (N) of an M- (N-)contiguous operand is fine when the pitch has room for one more element: the
-    // pair load at the edge then reads a pad element that only feeds a row (column) of C which is never stored.
-    int vec = 2;
-    k.Mc = k.M; k.Nc = k.N;
-    if (!a_kcontig && (g.M & 1) && k.a_ld > g.M) k.Mc = k.M + 1;
-    if (!b_kcontig && (g.N & 1) && k.b_ld > g.N) k.Nc = k.N + 1;
-    {
-        const long a_contig_extent = a_kcontig ? g.K : k.Mc;
-        const long b_contig_extent = b_kcontig ? g.K : k.Nc;
-        if (!even(k.a_ld) || !even(k.b_ld) || !even(a_contig_extent) || !even(b_contig_extent) ||
-            !aligned16(g.A) || !aligned16(g.B) || !even(g.a_b1) || !even(g.a_b2) || !even(g.b_b1) ||
-            !even(g.b_b2))
-            vec = 1;
-    }
+    GemmK k = make_gemmk(p, BM, BN);
+    const long tiles = (long)k.tiles_m * k.tiles_n * p.nbatch;
     if (tiles > 0x7fffffffL) throw std::runtime_error("gemm: grid too large");
 
     // ---- k-splitting.  (1) whole problem when the output has too few tiles to fill the chip;
-    // (2) only the LAST, partially filled wave of tiles otherwise: tiles all cost the same, so a
-    // launch takes ceil(tiles/slots) tile-times; splitting the K range of the remainder tiles over
-    // the idle CUs turns that last wave into a fraction of a tile-time.
-    const long ktiles = (g.K + BK - 1) / BK;
+    // (2) only the LAST, partially filled wave of tiles otherwise: plan_tail, or plan_dma for the LDS-DMA kernel.
     // Blocks that share a CU time-share its MFMA pipes, so what has to balance is the number of tiles per CU:
     // a launch costs about ceil(tiles / 256) tile-times (64x64 tiles need 4 co-resident blocks to fill a CU).
     const long slots = (BM <= 64 && BN <= 64) ? 1024 : 256;
     const long ws_tiles = g.splitk_ws ? g.splitk_ws_doubles / ((long)BM * BN) : 0;
-    long main_tiles = tiles, tail_tiles = 0;
-    int main_split = 1, tail_split = 1;
     // the LDS-DMA kernel (128 x 128, 16-byte loads, 32-bit lane offsets, K range per block >= dma_min_k) plans its own
     // launch: whole tiles + a cut tail in ONE grid (plan_dma)
-    const bool dma_ok = BM == 128 && BN == 128 && vec == 2 && g.K >= dma_min_k() &&
-                        (a_kcontig ? 128 : 16) * k.a_ld * 8 + 4096 < (1L << 32) &&
-                        (b_kcontig ? 128 : 16) * k.b_ld * 8 + 4096 < (1L << 32);
+    const bool dma_ok = BM == 128 && BN == 128 && p.vec == 2 && g.K >= dma_min_k() &&
+                        (p.akc ? 128 : 16) * k.a_ld * 8 + 4096 < (1L << 32) &&
+                        (p.bkc ? 128 : 16) * k.b_ld * 8 + 4096 < (1L << 32);
     DmaPlan plan{tiles, 0, 1};
     if (dma_ok) plan = plan_dma(tiles, ktiles, ws_tiles);
-    else if (ktiles >= 16) {
-        // The last, partially filled round of tiles (all of them for a small output) is split s ways along K:
-        // ceil(rem s / slots) rounds of 1/s tile-time each.  Few remainder tiles may be split finer (huge K, tiny output).
-        const long rem = tiles % slots;
-        if (rem > 0) {
-            long best = 1;
-            double best_cost = 1.0;
-            long smax = std::min<long>(512, std::max<long>(8, 2048 / rem));
-            const long min_kt = (BM == 128 && BN == 128) ? 16 : 8;       // per split: >= 256 (128x128) / 128 (smaller tiles) deep
-            smax = std::min<long>(smax, ktiles / min_kt);
-            smax = std::min<long>(smax, ws_tiles / rem);
-            for (long sp = 2; sp <= smax; ++sp) {
-                const double cost = (double)((rem * sp + slots - 1) / slots) / (double)sp + 1e-5 * sp;
-                if (cost < best_cost - 1e-9) { best_cost = cost; best = sp; }
-            }
-            if (best >= 2 && best_cost < 0.8) {        // worth it below 0.8 of a tile-time
-                tail_tiles = rem;
-                main_tiles = tiles - rem;
-                tail_split = (int)best;
-            }
-        }
-    }
+    // (per cut >= 256 deep on 128 x 128 tiles, 128 on smaller ones)
+    const TailSplit ts = dma_ok ? TailSplit{tiles, 0, 1} : plan_tail(tiles, ktiles, slots, (BM == 128 && BN == 128) ? 16 : 8, ws_tiles);
 
     ProfSpan span(st);
     bool used_dma = false;
     int n_kernels = 0;
     g_stream64 = stream && BM <= 64 && BN <= 64;
     auto launch = [&](long tile_begin, long ntiles, int nsplit) {
-        const long kt_per = (ktiles + nsplit - 1) / nsplit;
-        k.kchunk = (int)std::max<long>(kt_per * BK, BK);
-        k.nsplit = (int)std::max<long>(1, (ktiles + kt_per - 1) / std::max<long>(kt_per, 1));
         k.tile_begin = tile_begin;
-        k.ws = k.nsplit > 1 ? g.splitk_ws : nullptr;
+        k.ws = cut_k(ktiles, nsplit, &k) > 1 ? g.splitk_ws : nullptr;
         const long nblocks = ntiles * k.nsplit;
         ++n_kernels;
-        if (BM == 128 && BN == 128) dispatch_layout<128, 128>(k, a_kcontig, b_kcontig, vec, nblocks, st);
-        else if (BM == 128 && BN == 64) dispatch_layout<128, 64>(k, a_kcontig, b_kcontig, vec, nblocks, st);
-        else if (BM == 64 && BN == 128) dispatch_layout<64, 128>(k, a_kcontig, b_kcontig, vec, nblocks, st);
-        else if (BM == 64 && BN == 32) dispatch_layout<64, 32>(k, a_kcontig, b_kcontig, vec, nblocks, st);
-        else if (BM == 32 && BN == 64) dispatch_layout<32, 64>(k, a_kcontig, b_kcontig, vec, nblocks, st);
-        else dispatch_layout<64, 64>(k, a_kcontig, b_kcontig, vec, nblocks, st);
+        if (BM == 128 && BN == 128) dispatch_layout<128, 128>(k, p.akc, p.bkc, p.vec, nblocks, st);
+        else if (BM == 128 && BN == 64) dispatch_layout<128, 64>(k, p.akc, p.bkc, p.vec, nblocks, st);
+        else if (BM == 64 && BN == 128) dispatch_layout<64, 128>(k, p.akc, p.bkc, p.vec, nblocks, st);
+        else if (BM == 64 && BN == 32) dispatch_layout<64, 32>(k, p.akc, p.bkc, p.vec, nblocks, st);
+        else if (BM == 32 && BN == 64) dispatch_layout<32, 64>(k, p.akc, p.bkc, p.vec, nblocks, st);
+        else dispatch_layout<64, 64>(k, p.akc, p.bkc, p.vec, nblocks, st);
         if (k.nsplit > 1) {
             launch_kernel(splitk_reduce_kernel, dim3((unsigned)ntiles, (unsigned)(BM * BN / 256)), dim3(256), 0, st, k, BM, BN);
         }
@@ -4639,20 +4579,16 @@ void gemm(const Gemm& g, stream_t s) {
     int nsplit = 1;
     if (dma_ok) {
         // one grid: plan.whole whole tiles, then plan.tail tiles cut plan.s ways (ks-major); one reduction over the tail tiles
-        const long kt_per = (ktiles + plan.s - 1) / plan.s;
-        k.kchunk = (int)std::max<long>(kt_per * BK, BK);
-        k.nsplit = (int)std::max<long>(1, (ktiles + kt_per - 1) / std::max<long>(kt_per, 1));
-        if (k.nsplit == 1) { plan.whole = tiles; plan.tail = 0; }
-        k.tile_begin = 0;
+        if (cut_k(ktiles, plan.s, &k) == 1) { plan.whole = tiles; plan.tail = 0; }
         k.mixed = 1;
         k.whole = plan.whole;
         k.tail = plan.tail;
         k.ws = plan.tail > 0 ? g.splitk_ws : nullptr;
         const long nblocks = plan.whole + plan.tail * k.nsplit;
         if (nblocks > 0x7fffffffL) throw std::runtime_error("gemm: grid too large");
-        if (a_kcontig && b_kcontig) launch_gemm_glds<true, true>(k, nblocks, st);
-        else if (a_kcontig) launch_gemm_glds<true, false>(k, nblocks, st);
-        else if (b_kcontig) launch_gemm_glds<false, true>(k, nblocks, st);
+        if (p.akc && p.bkc) launch_gemm_glds<true, true>(k, nblocks, st);
+        else if (p.akc) launch_gemm_glds<true, false>(k, nblocks, st);
+        else if (p.bkc) launch_gemm_glds<false, true>(k, nblocks, st);
         else launch_gemm_glds<false, false>(k, nblocks, st);
         used_dma = true;
         n_kernels = 1;
@@ -4664,18 +4600,17 @@ void gemm(const Gemm& g, stream_t s) {
             nsplit = -k.nsplit;            // logged as a negative split
         }
     } else {
-        nsplit = main_tiles > 0 ? launch(0, main_tiles, main_split) : 1;
-        if (tail_tiles > 0) nsplit = -launch(main_tiles, tail_tiles, tail_split);   // logged as a negative split
+        nsplit = ts.main_tiles > 0 ? launch(0, ts.main_tiles, 1) : 1;
+        if (ts.tail_tiles > 0) nsplit = -launch(ts.main_tiles, ts.tail_tiles, ts.split);   // logged as a negative split
     }
     if (g_prof.on) {
-        const double fl = 2.0 * (double)g.M * (double)g.N * (double)g.K * (double)nbatch;
         char buf[256];
         int len = snprintf(buf, sizeof buf, "M=%ld N=%ld K=%ld batch=%ld tile=%dx%d%s akc=%d bkc=%d vec=%d dma=%d split=%d flops=%.4e",
-                           (long)g.M, (long)g.N, (long)g.K, (long)nbatch, BM, BN, g_stream64 ? "s" : "", (int)a_kcontig,
-                           (int)b_kcontig, vec, (int)used_dma, nsplit, fl);
+                           (long)g.M, (long)g.N, (long)g.K, (long)p.nbatch, BM, BN, g_stream64 ? "s" : "", (int)p.akc,
+                           (int)p.bkc, p.vec, (int)used_dma, nsplit, p.flops);
         if (used_dma && len > 0 && len < (int)sizeof buf)
             snprintf(buf + len, sizeof buf - len, " plan=%ld+%ld/%d", plan.whole, plan.tail, plan.tail ? k.nsplit : 1);
-        span.finish(fl, used_dma ? 1 : 0, n_kernels, buf);
+        span.finish(p.flops, used_dma ? 1 : 0, n_kernels, buf);
     }
 }
 
@@ -5600,58 +5535,60 @@ void ueg_two_body(const UegParams& prm, const int* k_int_dev, const int* index_m
 
 namespace {
 
-bool gemv_dispatch(const dev::Gemm& g, long a_sm, long a_sk, long b_sk, long b_sn, hipStream_t st) {
+bool gemv_dispatch(const GemmProduct& p, hipStream_t st) {
+    const dev::Gemm& g = p.g;
     if (g.nb1 != 1 || g.nb2 != 1 || g.K < 256) return false;
-    const double* W; const double* x; long ld, xs, R, C, ys; bool cols;
+    GemvItem it;                                 // y = alpha W x (+ beta yin): W is R x C with pitch ld
+    bool cols;
     if (g.M == 1 && g.N >= 64) {                 // y[n] = sum_k A(0,k) B(k,n)
-        x = g.A; xs = a_sk; W = g.B; ys = 1;
-        if (b_sn == 1) { cols = true; R = g.K; C = g.N; ld = b_sk; }          // B[k][n]: weighted column sums
-        else { cols = false; R = g.N; C = g.K; ld = b_sn; }                    // B[n][k]: one dot per row
+        it.x = g.A; it.xs = p.a_sk; it.W = g.B; it.ys = 1;
+        if (p.b_sn == 1) { cols = true; it.R = g.K; it.C = g.N; it.ld = p.b_sk; }          // B[k][n]: weighted column sums
+        else { cols = false; it.R = g.N; it.C = g.K; it.ld = p.b_sn; }                    // B[n][k]: one dot per row
     } else if (g.N == 1 && g.M >= 64) {          // y[m] = sum_k A(m,k) B(k,0)
-        x = g.B; xs = b_sk; W = g.A; ys = g.ldc;
-        if (a_sk == 1) { cols = false; R = g.M; C = g.K; ld = a_sm; }
-        else { cols = true; R = g.K; C = g.M; ld = a_sk; }
+        it.x = g.B; it.xs = p.b_sk; it.W = g.A; it.ys = g.ldc;
+        if (p.a_sk == 1) { cols = false; it.R = g.M; it.C = g.K; it.ld = p.a_sm; }
+        else { cols = true; it.R = g.K; it.C = g.M; it.ld = p.a_sk; }
     } else {
         return false;
     }
+    const long R = it.R, C = it.C;
     if (!cols && R < 512) return false;          // too few rows to fill the chip with one wave per row
     const double* yin = g.Cin ? g.Cin : g.C;
-    const int vec = (even(ld) && even(C) && aligned16(W)) ? 2 : 1;
+    const int vec = (even(it.ld) && even(C) && aligned16(it.W)) ? 2 : 1;
     const long cblocks = (C + 256L * vec - 1) / (256L * vec);
-    long nchunk = 1, rchunk = R;
+    long nchunk = 1;
+    it.rchunk = R;
     if (cols) {        // row chunks so that about 2048 blocks are in flight; their partial sums go through the workspace
         if (!g.splitk_ws || C > g.splitk_ws_doubles) return false;
         nchunk = std::max<long>(1, std::min<long>((2048 + cblocks - 1) / cblocks, R / 32));
         nchunk = std::min<long>(nchunk, g.splitk_ws_doubles / C);
-        rchunk = (R + nchunk - 1) / nchunk;
-        nchunk = (R + rchunk - 1) / rchunk;
+        it.rchunk = (R + nchunk - 1) / nchunk;
+        nchunk = (R + it.rchunk - 1) / it.rchunk;
     }
+    it.y = g.C; it.ws_off = 0; it.alpha = g.alpha; it.nchunk = (int)nchunk; it.cblocks = (int)cblocks; it.vec = vec;
+    it.blk0 = it.out0 = 0;
+    const GemvRowsK rk{it.W, it.x, yin, g.C, it.ld, it.xs, R, C, it.ys, g.alpha, g.beta};       // (the one-dot-per-row form)
     if (phase_open(st)) {
         const double cost = 8.0 * (double)R * (double)C / 4.0e6;
         if (phase_small(cost)) {
-            const PhaseRange rW = pbox(W, {{R, ld}, {C, 1}}, 1);
+            const PhaseRange rW = pbox(it.W, {{R, it.ld}, {C, 1}}, 1);
             if (cols) {
                 double* part = phase_ws(g.splitk_ws, g.splitk_ws_doubles, nchunk * C);
                 if (part) {
-                    GemvTaskK t;
-                    t.it.W = W; t.it.x = x; t.it.y = g.C; t.it.ld = ld; t.it.xs = xs; t.it.R = R; t.it.C = C; t.it.rchunk = rchunk;
-                    t.it.ys = ys; t.it.ws_off = 0; t.it.alpha = g.alpha; t.it.nchunk = (int)nchunk; t.it.cblocks = (int)cblocks;
-                    t.it.vec = vec; t.it.blk0 = t.it.out0 = 0;
-                    t.ws = part; t.yin = yin; t.beta = g.beta;
+                    const GemvTaskK t{it, part, yin, g.beta};
                     const PhaseRange rP = prange(part, nchunk * C);
                     PhaseRec& a = phase_push(PK_GEMV_COLS, 0, cblocks * nchunk, 0, cost, t);
-                    phase_reads(a, {rW, pbox(x, {{R, xs}})});
+                    phase_reads(a, {rW, pbox(it.x, {{R, it.xs}})});
                     phase_writes(a, {rP});
                     PhaseRec& f = phase_push(PK_GEMV_FINISH, 0, (C + 255) / 256, 0, 1.0, t);
-                    phase_reads(f, {rP, g.beta != 0.0 ? pbox(yin, {{C, ys}}) : PhaseRange{0, 0}});
-                    phase_writes(f, {pbox(g.C, {{C, ys}})});
+                    phase_reads(f, {rP, g.beta != 0.0 ? pbox(yin, {{C, it.ys}}) : PhaseRange{0, 0}});
+                    phase_writes(f, {pbox(g.C, {{C, it.ys}})});
                     return true;
                 }
             } else {
-                GemvRowsK t{W, x, yin, g.C, ld, xs, R, C, ys, g.alpha, g.beta};
-                PhaseRec& a = phase_push(PK_GEMV_ROWS, vec == 2 ? 1 : 0, (R + 3) / 4, 0, cost, t);
-                phase_reads(a, {rW, pbox(x, {{C, xs}}), g.beta != 0.0 ? pbox(yin, {{R, ys}}) : PhaseRange{0, 0}});
-                phase_writes(a, {pbox(g.C, {{R, ys}})});
+                PhaseRec& a = phase_push(PK_GEMV_ROWS, vec == 2 ? 1 : 0, (R + 3) / 4, 0, cost, rk);
+                phase_reads(a, {rW, pbox(it.x, {{C, it.xs}}), g.beta != 0.0 ? pbox(yin, {{R, it.ys}}) : PhaseRange{0, 0}});
+                phase_writes(a, {pbox(g.C, {{R, it.ys}})});
                 return true;
             }
         }
@@ -5661,10 +5598,8 @@ bool gemv_dispatch(const dev::Gemm& g, long a_sm, long a_sk, long b_sk, long b_s
         if (b.active && !g_prof.on) {        // (per-call event timing wants every product on its own)
             const bool same = b.tab.n == 0 || (b.ws == g.splitk_ws && b.st == st);
             if (cols && g.beta == 0.0 && same && b.tab.n < kGemvBatchMax && b.ws_used + nchunk * C <= g.splitk_ws_doubles) {
-                GemvItem& it = b.tab.it[b.tab.n++];
-                it.W = W; it.x = x; it.y = g.C; it.ld = ld; it.xs = xs; it.R = R; it.C = C; it.rchunk = rchunk; it.ys = ys;
-                it.ws_off = b.ws_used; it.alpha = g.alpha; it.nchunk = (int)nchunk; it.cblocks = (int)cblocks; it.vec = vec;
-                it.blk0 = it.out0 = 0;
+                it.ws_off = b.ws_used;
+                b.tab.it[b.tab.n++] = it;
                 b.ws_used += nchunk * C;
                 b.ws = g.splitk_ws;
                 b.st = st;
@@ -5675,21 +5610,20 @@ bool gemv_dispatch(const dev::Gemm& g, long a_sm, long a_sk, long b_sk, long b_s
     }
     ProfSpan span(st);
     if (cols) {
-        if (vec == 2) launch_kernel(gemv_cols_kernel<2>, dim3((unsigned)cblocks, (unsigned)nchunk), dim3(256), 0, st, W, ld, x, xs, R, C, rchunk, g.splitk_ws);
-        else launch_kernel(gemv_cols_kernel<1>, dim3((unsigned)cblocks, (unsigned)nchunk), dim3(256), 0, st, W, ld, x, xs, R, C, rchunk, g.splitk_ws);
+        const dim3 grid((unsigned)cblocks, (unsigned)nchunk);
+        if (vec == 2) launch_kernel(gemv_cols_kernel<2>, grid, dim3(256), 0, st, it.W, it.ld, it.x, it.xs, R, C, it.rchunk, g.splitk_ws);
+        else launch_kernel(gemv_cols_kernel<1>, grid, dim3(256), 0, st, it.W, it.ld, it.x, it.xs, R, C, it.rchunk, g.splitk_ws);
         launch_kernel(gemv_finish_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, g.splitk_ws, (int)nchunk, C,
-                           g.alpha, g.beta, yin, g.C, ys);
+                           g.alpha, g.beta, yin, g.C, it.ys);
     } else {
-        const GemvRowsK rk{W, x, yin, g.C, ld, xs, R, C, ys, g.alpha, g.beta};
         if (vec == 2) launch_kernel(gemv_rows_kernel<2>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, rk);
         else launch_kernel(gemv_rows_kernel<1>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, rk);
     }
     if (g_prof.on) {
-        const double fl = 2.0 * (double)g.M * (double)g.N * (double)g.K;
         char buf[256];
         snprintf(buf, sizeof buf, "M=%ld N=%ld K=%ld batch=1 gemv=%s vec=%d flops=%.4e", (long)g.M, (long)g.N, (long)g.K,
-                 cols ? "cols" : "rows", vec, fl);
-        span.finish(fl, 0, 1, buf);
+                 cols ? "cols" : "rows", vec, p.flops);
+        span.finish(p.flops, 0, 1, buf);
     }
     return true;
 }

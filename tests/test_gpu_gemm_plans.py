@@ -11,8 +11,12 @@ from pymes_amd.device import Context
 
 pytestmark = pytest.mark.gpu
 
-# (M, N, K): 128 x 128 tiles, K >= 384 so that the LDS-DMA kernel is taken
+# (M, N, K), K >= 384.  (Fewer than 256 tiles of 128 x 128 and K / ceil(512 / tiles) < 384: dev::gemm runs these on 64 x 64 tiles,
+# tools/gemm_route_dump.py shows it, and PYMES_GEMM_PLAN has no effect on them.)
 SHAPES = [(1250, 1100, 900), (384, 640, 2000), (777, 300, 1601), (129, 129, 4100), (2000, 1600, 400)]
+# ... and the ones that do reach the LDS-DMA kernel, which the test asserts: 256 whole tiles + 16 for the tail, 4 tiles over a
+# K deep enough to cut 128 ways, exactly 256 whole tiles
+DMA_SHAPES = [(2176, 2048, 800), (256, 256, 49152), (2048, 2048, 400)]
 PLANS = [None, "0,1", "0,2", "0,3", "8,2", "16,3", "64,2", "88,2", "200,1", "8,1"]
 
 
@@ -45,19 +49,25 @@ def run_case(ctx, rng, M, N, K, a_kc, b_kc, alpha, beta, plan, nb=1):
     return err
 
 
-@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("shape", SHAPES + DMA_SHAPES)
 def test_launch_plans_agree_with_numpy(gpu_lib, shape):
     M, N, K = shape
     rng = np.random.default_rng(M + 7 * N + 13 * K)
     ctx = Context(4, 4, workspace_bytes=1 << 28, lib=gpu_lib)
+    on_dma = shape in DMA_SHAPES
     try:
+        ctx.prof_enable(on_dma)          # (per-call events: what prof_query counts; the other shapes keep their default route)
         for plan in PLANS:
             a_kc, b_kc = bool(rng.integers(2)), bool(rng.integers(2))
             alpha = float(rng.choice([1.0, -0.5, 2.0]))
             beta = float(rng.choice([0.0, 1.0, 0.25]))
+            ctx.prof_reset()
             err = run_case(ctx, rng, M, N, K, a_kc, b_kc, alpha, beta, plan)
             assert err < 1e-13 * K ** 0.5, dict(shape=shape, plan=plan, a_kc=a_kc, b_kc=b_kc, alpha=alpha, beta=beta, err=err)
+            if on_dma:
+                assert ctx.prof_query(kernel_class=1)["launches"] == 1, dict(shape=shape, plan=plan)
     finally:
+        ctx.prof_enable(False)
         ctx.close()
 
 

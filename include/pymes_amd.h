@@ -701,6 +701,40 @@ int pymes_lambda_step(pymes_eom* h, const double* lam1_dev, const double* lam2_d
                       double* err1_dev, double* err2_dev, double* norm_host);
 int pymes_rdm1(pymes_ctx* ctx, const double* t1_dev, const double* t2_dev, const double* lam1_dev, const double* lam2_dev,
                double ref, double* gamma_host);
+/* ---- left EOM-CCSD eigenvectors and transition densities ------------------------------------------------------
+ * Conventions of the block above.  For root k: A r_k = w_k r_k, A^T l_k = w_k l_k (pymes_eom_sigma_apply / _apply_left; with
+ * k > 1 the left build sends all vectors through its large products as one GEMM each), <l_j, r_k> = delta_jk,
+ * r0_k = -<lambda, r_k>; the left state has no reference component.  R1(f), R2(f): the CCSD residuals at (t1, t2) with the
+ * integrals set to zero; A(f): the sigma with the T1-dressed f and all V blocks zero.  Everything is linear in f:
+ *   gammaL_k[p,q] = d/df_pq ( <l1_k, R1(f)> + <l2_k, R2(f)> )
+ *   gammaR_k[p,q] = d/df_pq ( 2 sum f~_ov[i,a] r1_k[a,i] + <lambda, A(f) r_k> + 2 sum lambda2[a,b,i,j] r1_k[a,i] R1(f)[b,j]
+ *                             - <lambda, r_k> ( <lambda1, R1(f)> + <lambda2, R2(f)> ) )
+ *   S_k(O) = (sum gammaL_k O) (sum gammaR_k O);  oscillator strength (2/3) w_k sum_x S_k(mu_x).
+ * Written out, with C the coefficients of the dressed Fock matrix f~ and the dressing undone at the end (t = T2):
+ *   X(l1, l2):  Xvv[a,c] = sum l2[a,b,i,j] t[c,b,i,j],  Xoo[k,i] = sum l2[a,b,i,j] t[a,b,k,j],
+ *               Xov[j,b] = sum l1[a,i] (2 t[a,b,i,j] - t[a,b,j,i])
+ *   left:   C_vo = l1,  C_oo = -2 Xoo(l),  C_vv = 2 Xvv(l),  C_ov = Xov(l)          (pymes_rdm1 without ref and without 2 t1)
+ *   right:  s = <lambda, r>,  Y = X(lambda1, lambda2),  Z = X(lambda1, lambda2) with r2 in the place of t,
+ *           Le[b,j] = 2 sum lambda2[a,b,i,j] r1[a,i],  Eov = Xov(Le)
+ *           C_vo = Le - s lambda1
+ *           C_oo[j,i] = -sum_a r1[a,j] lambda1[a,i] - 2 Zoo[j,i] + 2 s Yoo[j,i]
+ *           C_vv[a,b] = sum_i lambda1[a,i] r1[b,i] + 2 Zvv[a,b] - 2 s Yvv[a,b]
+ *           C_ov[j,b] = 2 r1[b,j] + Zov[j,b] + Eov[j,b] - s Yov[j,b] - 2 sum_i Yoo[j,i] r1[b,i] - 2 sum_a Yvv[a,b] r1[a,j]
+ *   gamma_vo = C_vo,  gamma_oo[j,i] = C_oo[j,i] - sum_a t1[a,j] C_vo[a,i],  gamma_vv[a,b] = C_vv[a,b] + sum_i C_vo[a,i] t1[b,i],
+ *   gamma_ov[j,b] = C_ov[j,b] + sum_i gamma_oo[j,i] t1[b,i] - sum_a t1[a,j] C_vv[a,b]
+ * pymes_tdm1: gammaL_host, gammaR_host [k,n,n] (occupied orbitals first) and r0_host [k] for k <= 64 roots given as device
+ * vectors (l1[z], l2[z]), (r1[z], r2[z]); linear in every vector (the biorthogonal normalisation is the caller's).  The
+ * contracted intermediates are engine products with the k vectors stacked, the rest one assembly launch.  It reads no integral
+ * block; identical calls give identical bits (no atomics, fixed summation order).
+ * pymes_eom_correction: the Davidson correction of pymes_ipea_sigma_correction for the EE vectors of the context's (no, nv):
+ * flat vectors [x1 (v o) | zero pad | x2 (v v o o)] of len doubles, the doubles at off2, d_dev the diagonals of
+ * pymes_eom_diagonals in the same layout (the same kernel; one launch and ONE synchronisation per sixteen roots).
+ * Both refuse a context that is recording a launch graph. */
+int pymes_tdm1(pymes_ctx* ctx, const double* t1_dev, const double* t2_dev, const double* lam1_dev, const double* lam2_dev, int k,
+               const double* const* l1_dev, const double* const* l2_dev, const double* const* r1_dev, const double* const* r2_dev,
+               double* gammaL_host, double* gammaR_host, double* r0_host);
+int pymes_eom_correction(pymes_ctx* ctx, int n, const double* const* s_dev, const double* const* r_dev, const double* w_host,
+                         const double* d_dev, double shift, double* const* q_dev, int64_t off2, int64_t len, double* norms_host);
 /* (mr + i mi)[e] = 1 / ((zr + i zi) - (hr + i hi) d[e] + shift), e < n: the FEAST preconditioner 1 / (z - diag + 0.01)
  * (feast_eom_ccsd.py:342; hs = 1j dt for the real-time form :276-278) from the device-resident diagonal */
 int pymes_cshift_inv(pymes_ctx* ctx, const double* d_dev, double zr, double zi, double hr, double hi, double shift,

@@ -177,6 +177,9 @@ SIGNATURES = {
     "pymes_ipea_sigma_correction": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                               C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "pymes_ipea_sigma_destroy": (C.c_int, [C.c_void_p]),
+    "pymes_tdm1": (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 7),
+    "pymes_eom_correction": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                       C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "pymes_diis_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_pp, c_pp, c_i64_p, c_pp, c_pp]),
     "pymes_diis_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "pymes_diis_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_pp, c_pp, c_i64_p, C.c_int, C.c_int, C.c_int]),

@@ -1046,6 +1046,32 @@ int pymes_rdm1(pymes_ctx* ctx, const double* t1, const double* t2, const double*
     });
 }
 
+int pymes_tdm1(pymes_ctx* ctx, const double* t1, const double* t2, const double* lam1, const double* lam2, int k,
+               const double* const* l1, const double* const* l2, const double* const* r1, const double* const* r2,
+               double* gl_host, double* gr_host, double* r0_host) {
+    return guarded([&] {
+        need(t1, "t1"); need(t2, "t2"); need(lam1, "lam1"); need(lam2, "lam2"); need(l1, "l1"); need(l2, "l2"); need(r1, "r1");
+        need(r2, "r2"); need(gl_host, "gammaL"); need(gr_host, "gammaR"); need(r0_host, "r0");
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("tdm1 while a launch graph is being recorded");
+        pymes::transition_densities(e, t1, t2, lam1, lam2, k, l1, l2, r1, r2, gl_host, gr_host, r0_host);
+    });
+}
+int pymes_eom_correction(pymes_ctx* ctx, int n, const double* const* s, const double* const* r, const double* w_host,
+                         const double* d, double shift, double* const* q, int64_t off2, int64_t len, double* norms_host) {
+    return guarded([&] {
+        need(s, "s"); need(r, "r"); need(w_host, "w"); need(d, "d"); need(q, "q"); need(norms_host, "norms");
+        if (n < 0 || n > 4096) throw pymes::Error("eom_correction: 0 <= n <= 4096");
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("eom_correction while a launch graph is being recorded");
+        const int64_t n1 = static_cast<int64_t>(e.nv) * e.no;
+        if (off2 < n1 || len != off2 + n1 * n1) throw pymes::Error("eom_correction: the flat layout does not match (no, nv)");
+        for (int z = 0; z < n; ++z)
+            if (!s[z] || !r[z] || !q[z]) throw pymes::Error("eom_correction: null vector");
+        pymes::davidson_correction(e, n, s, r, w_host, d, shift, q, n1, off2, len, norms_host);
+    });
+}
+
 // ---- IP- / EA-EOM-CCSD sigma (eom.cpp, IpEaSigma) -------------------------------------------------------------------------------
 int pymes_ipea_sigma_prepare(pymes_ctx* ctx, const double* f_host, const double* t2, int dressed, int kind, pymes_ipea** out) {
     return guarded([&] {

@@ -972,6 +972,43 @@ void Engine::ladder_sym_adjoint(const double* x, double* LSp, double* LAp, bool 
         contract(1.0, packed_rows(lpack_.Vm, npp, npm), "kr", pitched(Am, npp, opm, ldm), "kn", 0.0, make_view(LAp, {npm, opm}), "rn");
 }
 
+void Engine::ladder_sym_adjoint_multi(const double* const* xs, int k, double* LSp, double* LAp, bool dressed) {
+    refuse_if_sharded("ladder_sym_adjoint_multi");
+    if (k < 1) return;
+    const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opm = o * (o - 1) / 2, K = k;
+    if (!(lpack_.valid && lpack_.dressed == dressed && lpack_.row0 == 0 && lpack_.row1 == npp)) {
+        if (!lpack_.Vp || lpack_.row1 - lpack_.row0 != npp) {
+            dev::stream_sync(stream);
+            dev::dfree(lpack_.Vp);
+            dev::dfree(lpack_.Vm);
+            lpack_.Vp = lpack_.Vm = nullptr;
+            lpack_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * npp * lpitch(npp)));
+            lpack_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * npp * lpitch(std::max<int64_t>(npm, 1))));
+        }
+        dev::ladder_pack_V(block(P_abcd, dressed).p, lpack_.Vp, lpack_.Vm, nv, nv, 0, npp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
+        stats.permute_calls++;
+        stats.permute_bytes += 8.0 * 2.0 * double(npp) * double(v * v);
+        lpack_.row0 = 0; lpack_.row1 = npp; lpack_.dressed = dressed; lpack_.valid = true;
+    }
+    ArenaScope scope(arena);
+    const int64_t ldp = ladder_adjoint_pitch(true), ldm = ladder_adjoint_pitch(false);
+    // the packed halves of vector z in the columns [z ld, (z + 1) ld) of rows of pitch k ld (the pad columns zeroed: they go
+    // through the product as columns of their own)
+    double* Sp = arena.alloc(npp * K * ldp);
+    double* Am = arena.alloc(npp * K * ldm);
+    zero(make_view(Sp, {npp * K * ldp}));
+    zero(make_view(Am, {npp * K * ldm}));
+    for (int z = 0; z < k; ++z)
+        dev::ladder_pack_T(xs[z], nullptr, Sp + z * ldp, Am + z * ldm, no, nv, dev::PACK_ROW_HALF | dev::PACK_AM_PROWS, K * ldp,
+                           K * ldm, stream);
+    stats.permute_calls += k;
+    stats.permute_bytes += 8.0 * 2.0 * double(k) * double(v * v * o * o);
+    contract(1.0, packed_rows(lpack_.Vp, npp, npp), "kr", make_view(Sp, {npp, K * ldp}), "kn", 0.0, make_view(LSp, {npp, K * ldp}), "rn");
+    if (opm > 0 && npm > 0)
+        contract(1.0, packed_rows(lpack_.Vm, npp, npm), "kr", make_view(Am, {npp, K * ldm}), "kn", 0.0,
+                 make_view(LAp, {npm, K * ldm}), "rn");
+}
+
 // A hole-ladder-shaped term sum_kl I_klij X_abkl in the pair-packed rows of L (added to what the rows hold), for
 // I_klij = I_lkji and X_abkl = X_balk: the (k,l) part of ladder_sym for a caller-supplied I (EOM-CCSD: eom_ccsd.py:380-382
 // — u2 against V_klij + V_klcd T_cdij, T against V_kldc u2_dcij), 1/4 of the flops of the plain v^2 o^4 product.  With y

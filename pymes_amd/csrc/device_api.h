@@ -344,6 +344,7 @@ struct LambdaParts {
     const double* lam1 = nullptr; const double* lam2 = nullptr;
     double* out1 = nullptr; double* out2 = nullptr; double* err1 = nullptr; double* err2 = nullptr;
     double* ws = nullptr; double* norm_dev = nullptr;
+    int64_t lp_ld = 0, la_ld = 0;      // row pitches of Lp / La (0: o^2 and o (o - 1) / 2); the stacked left build passes k vectors' halves side by side
 };
 int64_t lambda_assemble_ws_doubles(int nv);
 void lambda_assemble(const LambdaParts& q, int no, int nv, stream_t s);
@@ -352,6 +353,20 @@ void lambda_assemble(const LambdaParts& q, int no, int nv, stream_t s);
 // t1 (formulas: include/pymes_amd.h, pymes_rdm1); ref is added on the occupied diagonal.  One launch.
 void rdm1_assemble(const double* Xvv, const double* Xoo, const double* Xov, const double* l1, const double* t1, int no, int nv,
                    double ref, double* g, stream_t s);
+// Transition densities of k EE-EOM-CCSD roots (eom.cpp, transition_densities; formulas: include/pymes_amd.h,
+// pymes_tdm1): gl, gr [k,n,n] and r0 [k] (device) from t1, lam1 [v,o], the stacked singles L1, R1 [k,v,o] and the contracted
+// intermediates — X: l2_z . t2 and l1_z . (2 t - t^(ij)), Y: the same of lambda, Z: lambda2 . r2_z and lambda1 . (2 r2_z -
+// r2_z^(ij)), Le[z,b,j] = 2 sum lambda2[a,b,i,j] r1_z[a,i], E: Le_z . (2 t - t^(ij)); vv blocks [v,v], oo [o,o], ov [o,v], with a
+// leading root index where they depend on the root.  One launch, no atomics, fixed summation order.
+struct Tdm1Parts {
+    const double* t1 = nullptr; const double* lam1 = nullptr; const double* L1 = nullptr; const double* R1 = nullptr;
+    const double* Xvv = nullptr; const double* Xoo = nullptr; const double* Xov = nullptr;
+    const double* Yvv = nullptr; const double* Yoo = nullptr; const double* Yov = nullptr;
+    const double* Zvv = nullptr; const double* Zoo = nullptr; const double* Zov = nullptr;
+    const double* Le = nullptr; const double* Eov = nullptr;
+    double* gl = nullptr; double* gr = nullptr; double* r0 = nullptr;
+};
+void tdm1_assemble(const Tdm1Parts& q, int k, int no, int nv, stream_t s);
 
 // ---- Hartree-Fock matrix from the packed blocks (pymes/mean_field/hf.py:14-18); dir[tp*2+tq] = block (tp,o,tq,o),
 // exc[tp*2+tq] = block (tp,o,o,tq), tp/tq = 1 for a virtual index; h and f are [n,n] on the device

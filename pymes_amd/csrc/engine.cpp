@@ -825,4 +825,7 @@ __attribute__((weak)) void rdm1_assemble(const double*, const double*, const dou
                                          double, double*, stream_t) {
     throw std::runtime_error("rdm1_assemble: not available in this backend");
 }
+__attribute__((weak)) void tdm1_assemble(const Tdm1Parts&, int, int, int, stream_t) {
+    throw std::runtime_error("tdm1_assemble: not available in this backend");
+}
 }  // namespace dev

@@ -206,6 +206,16 @@ class Engine {
     // o(o+1)/2 columns (the layout of ladder_sym; the rest of a row is not written); LA [v(v-1)/2][o(o-1)/2]: the
     // antisymmetric half by strictly-lower pairs Q(c,d).
     void ladder_sym_adjoint(const double* x, double* LS, double* LA, bool dressed);
+    // ... for k vectors through ONE product per half: the packed operands side by side, vector z in the columns [z ldp, z ldp +
+    // opp) of rows of pitch k ldp (ldp = ladder_adjoint_pitch(true); the antisymmetric half alike with ldm).  LS [npp][k ldp],
+    // LA [max(npm,1)][k ldm]: the row of pair r for vector z starts at LS + r k ldp + z ldp
+    void ladder_sym_adjoint_multi(const double* const* xs, int k, double* LS, double* LA, bool dressed);
+    int64_t ladder_adjoint_pitch(bool symmetric_half) const {
+        const int64_t o = no, opp = o * (o + 1) / 2, opm = o * (o - 1) / 2;
+        // even and with at least one pad column: ladder_pack_T zeroes the column behind the packed ones whenever the pitch it
+        // is given exceeds them, and here the pitch is k of these
+        return ((symmetric_half ? opp : opm) + 2) & ~int64_t(1);
+    }
     void hole_ladder_packed_multi(const double* const* xs, const double* const* Is, const double* const* ys, int k, double* L_all);
     void hole_ladder_packed(const double* x, const double* I, double* L, int64_t row0, int64_t row1,
                             const double* y = nullptr);

@@ -695,7 +695,7 @@ void EomSigma::apply_left(int k, const double* const* l1, const double* const* l
         if (!(sym && sym[z]) && !exchange_symmetric(l2[z], nv, no))
             throw Error("eom sigma apply_left: the left doubles do not have the exchange symmetry l2_abij = l2_baji");
     left_prepare();
-    for (int z = 0; z < k; ++z) {
+    auto one = [&](int z) {
         LeftParts w(*this, true);
         left_partials(l1[z], l2[z], w);
         dev::LambdaParts q;
@@ -703,6 +703,97 @@ void EomSigma::apply_left(int k, const double* const* l1, const double* const* l
         q.cd = 2.0; q.cx = -1.0;
         q.out1 = o1[z]; q.out2 = o2[z];
         dev::lambda_assemble(q, no, nv, e.stream);
+    };
+    if (k < 2) { one(0); return; }
+    const int step = stack_limit();
+    for (int lo = 0; lo < k; lo += step) {
+        const int hi = std::min(k, lo + step);
+        if (hi - lo < 2) { one(lo); continue; }
+        try {
+            left_stack(hi - lo, l1 + lo, l2 + lo, o1 + lo, o2 + lo);
+        } catch (const Error& err) {
+            if (std::string(err.what()).find("memory") == std::string::npos) throw;
+            trim();                    // out of device memory in the middle of a stacked build: one vector at a time
+            for (int z = lo; z < hi; ++z) one(z);
+        }
+    }
+}
+
+// ---- A^T l for k left vectors at once: left_partials() with a leading vector index on every vector-dependent operand, so that
+// every hoisted operand and every V+ / V- row is read once per call.  The two (ov)^3 products run transposed — PdT[z] = ld_z M12,
+// PxT[z] = Q_z MDU with the k symmetric pair matrices stacked along the rows: ONE GEMM each — which the assembly does not see:
+// it reads Pd and Px only through raw_abij + raw_baji, the sum of an element and its transpose.  The packed ladder halves of the
+// k vectors lie side by side in the columns of one product per half (Engine::ladder_sym_adjoint_multi).
+void EomSigma::left_stack(int k, const double* const* l1, const double* const* l2, double* const* o1, double* const* o2) {
+    const int64_t o = no, v = nv, ov = o * v, ov2 = ov * ov, K = k, n1 = v * o, n2 = v * v * o * o;
+    const Ops q{e};
+    Tmp L1S(*this, K * n1), L2S(*this, K * n2), S1(*this, K * n1), Dd(*this, K * n2), Pd(*this, K * ov2), Px(*this, K * ov2);
+    Tmp ld(*this, K * ov2), lx(*this, K * ov2), Q(*this, K * ov2);
+    for (int z = 0; z < k; ++z) {
+        dev::memcpy_d2d(L1S.p + z * n1, l1[z], sizeof(double) * n1, e.stream);
+        dev::memcpy_d2d(L2S.p + z * n2, l2[z], sizeof(double) * n2, e.stream);
+        dev::t2_layouts(l2[z], ld.p + z * ov2, lx.p + z * ov2, Q.p + z * ov2, no, nv, e.stream, 1.0, 2.0);
+    }
+    const TView L1 = mv(L1S, {K, v, o}), L2 = mv(L2S, {K, v, v, o, o}), T4 = mv(T, {v, v, o, o});
+    const TView Vijab = V("ijab"), Vijka = V("ijka"), Vijak = V("ijak"), Viabc = V("iabc");
+    const TView S = mv(S1, {K, v, o}), D = mv(Dd, {K, v, v, o, o}), FOV = mv(fov, {o, v});
+    auto P4 = [&](const double* p) { return mv(p, {v, o, v, o}); };
+    auto P5 = [&](const double* p) { return mv(p, {K, v, o, v, o}); };
+    // ---- singles() backwards ------------------------------------------------------------------------------------------------------
+    q.C(1.0, mv(W1, {v, o, v, o}), "ckai", L1, "zai", 0.0, S, "zck");
+    q.C(1.0, mv(Gvv_s, {v, v}), "ac", L1, "zai", 1.0, S, "zci");
+    q.C(1.0, L1, "zai", mv(Goo_s, {o, o}), "ki", 1.0, S, "zak");
+    {
+        Tmp utb(*this, K * n2);
+        const TView Ub = mv(utb, {K, v, v, o, o});
+        q.C(1.0, mv(fov, {o, v, 1}), "jbx", mv(L1S, {K, 1, v, o}), "zxai", 0.0, Ub, "zbaji");
+        q.C(-1.0, Vijka, "jkib", L1, "zai", 1.0, Ub, "zabjk");
+        q.C(1.0, Viabc, "jabc", L1, "zai", 1.0, Ub, "zbcji");
+        q.P(2.0, Ub, "zabij", 0.0, D, "zabij");
+        q.P(-1.0, Ub, "zbaij", 1.0, D, "zabij");
+    }
+    // ---- doubles() backwards --------------------------------------------------------------------------------------------------------
+    Tmp Xoo(*this, K * o * o), Xvv(*this, K * v * v), Bn(*this, K * o * o * o * o);
+    const TView XooV = mv(Xoo, {K, o, o}), XvvV = mv(Xvv, {K, v, v}), BnV = mv(Bn, {K, o, o, o, o});
+    q.C(2.0, L2, "zabij", T4, "cbij", 0.0, XvvV, "zac");
+    q.C(2.0, mv(WW, {v, v, o, v}), "abid", L2, "zabij", 1.0, S, "zdj");
+    q.C(2.0, mv(Gvv, {v, v}), "ad", L2, "zabij", 1.0, D, "zdbij", "z");
+    q.C(2.0, mv(Goo, {o, o}), "li", L2, "zabij", 1.0, D, "zablj", "zab");
+    q.C(2.0, L2, "zabij", mv(A3, {o, o, v, o}), "libj", 1.0, S, "zal");
+    q.C(2.0, L2, "zabij", mv(A4, {o, o, v, o}), "liaj", 1.0, S, "zbl");
+    q.C(-2.0, L2, "zabij", mv(A6, {o, v, o, o}), "laji", 1.0, S, "zbl");
+    q.C(-2.0, L2, "zabij", V("iajk"), "kbij", 1.0, S, "zak");
+    q.C(1.0, T4, "abkl", L2, "zabij", 0.0, BnV, "zklij");
+    q.C(2.0, Vijka, "klid", BnV, "zklij", 1.0, S, "zdj");
+    q.C(1.0, P5(ld), "zbjai", P4(M12), "aidl", 0.0, P5(Pd), "zbjdl");                   // (M12^T ld_z)^T, all z: one GEMM
+    q.C(2.0, P4(Td), "akbj", P5(ld), "zaibj", 0.0, XooV, "zki");
+    q.C(1.0, P5(Q), "zbiaj", P4(MDU), "ajdl", 0.0, P5(Px), "zbidl");                    // (MDU^T Q_z)^T, all z: one GEMM
+    q.C(-2.0, Vijka, "klid", XooV, "zki", 1.0, S, "zdl");
+    q.C(1.0, Vijak, "kldi", XooV, "zki", 1.0, S, "zdl");
+    q.C(-1.0, FOV, "kd", XooV, "zki", 1.0, S, "zdi");
+    q.C(1.0, mv(Aoo, {o, v, o, v}), "kdlc", XooV, "zki", 1.0, P5(Px), "zcidl");         // (into the transposed Px)
+    q.C(2.0, Viabc, "ladc", XvvV, "zac", 1.0, S, "zdl");
+    q.C(-1.0, Viabc, "lacd", XvvV, "zac", 1.0, S, "zdl");
+    q.C(-1.0, XvvV, "zac", FOV, "lc", 1.0, S, "zal");
+    q.C(1.0, XvvV, "zac", slice(mv(BB, {o, v, o, v + o}), 3, 0, v), "kdlc", 1.0, P5(Px), "zdlak");
+    q.C(1.0, L2, "zabij", mv(B2, {o, o, o, o}), "klij", 1.0, D, "zabkl");
+    q.C(1.0, Vijab, "kldc", BnV, "zklij", 1.0, D, "zdcij");
+    const int64_t npp = v * (v + 1) / 2, npm = std::max<int64_t>(v * (v - 1) / 2, 1);
+    const int64_t ldp = e.ladder_adjoint_pitch(true), ldm = e.ladder_adjoint_pitch(false);
+    const bool la = v_sym && o > 1 && v > 1;
+    Tmp Lp(*this, v_sym ? npp * K * ldp : 1), La(*this, la ? npm * K * ldm : 1);
+    if (v_sym) e.ladder_sym_adjoint_multi(l2, k, Lp, La, dressed);
+    else q.C(1.0, V("abcd"), "abcd", L2, "zabij", 1.0, D, "zcdij");
+    for (int z = 0; z < k; ++z) {
+        dev::LambdaParts w;
+        w.D = Dd.p + z * n2; w.Pd = Pd.p + z * ov2; w.Px = Px.p + z * ov2; w.S1 = S1.p + z * n1;
+        if (v_sym) {
+            w.Lp = Lp.p + z * ldp; w.lp_ld = K * ldp;
+            if (la) { w.La = La.p + z * ldm; w.la_ld = K * ldm; }
+        }
+        w.cd = 2.0; w.cx = -1.0;
+        w.out1 = o1[z]; w.out2 = o2[z];
+        dev::lambda_assemble(w, no, nv, e.stream);
     }
 }
 
@@ -760,6 +851,83 @@ void lambda_rdm1(Engine& e, const double* t1, const double* t2, const double* la
     dev::rdm1_assemble(Xvv.p, Xoo.p, Xov.p, lam1, t1, e.no, e.nv, ref, G.p, e.stream);
     dev::memcpy_d2h(gamma_host, G.p, sizeof(double) * n * n, e.stream);
     dev::stream_sync(e.stream);
+}
+
+// ---- transition densities of k roots (eom.h): the v o o / v v o-contracted intermediates as engine products with the
+// k vectors stacked (one GEMM per product), then one assembly launch for both densities of all roots ---------------------------
+void transition_densities(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2, int k,
+                          const double* const* l1, const double* const* l2, const double* const* r1, const double* const* r2,
+                          double* gl_host, double* gr_host, double* r0_host) {
+    if (!t1 || !t2 || !lam1 || !lam2 || !l1 || !l2 || !r1 || !r2 || !gl_host || !gr_host || !r0_host)
+        throw Error("tdm1: null argument");
+    if (k < 1 || k > 64) throw Error("tdm1: 1 <= k <= 64 roots per call");
+    for (int z = 0; z < k; ++z)
+        if (!l1[z] || !l2[z] || !r1[z] || !r2[z]) throw Error("tdm1: null vector");
+    const int64_t o = e.no, v = e.nv, n = o + v, K = k, n1 = v * o, n2 = v * v * o * o;
+    struct Buf {
+        Engine& e;
+        double* p;
+        Buf(Engine& e_, int64_t m) : e(e_), p(e_.scratch_get(m)) {}
+        ~Buf() { e.scratch_put(p); }
+    } L1(e, K * n1), R1(e, K * n1), L2(e, K * n2), R2(e, K * n2), Xvv(e, K * v * v), Xoo(e, K * o * o), Xov(e, K * n1),
+        Yvv(e, v * v), Yoo(e, o * o), Yov(e, n1), Zvv(e, K * v * v), Zoo(e, K * o * o), Zov(e, K * n1), Le(e, K * n1),
+        Eov(e, K * n1), G(e, 2 * K * n * n + K);
+    for (int z = 0; z < k; ++z) {
+        dev::memcpy_d2d(L1.p + z * n1, l1[z], sizeof(double) * n1, e.stream);
+        dev::memcpy_d2d(R1.p + z * n1, r1[z], sizeof(double) * n1, e.stream);
+        dev::memcpy_d2d(L2.p + z * n2, l2[z], sizeof(double) * n2, e.stream);
+        dev::memcpy_d2d(R2.p + z * n2, r2[z], sizeof(double) * n2, e.stream);
+    }
+    const TView T4 = mv(t2, {v, v, o, o}), LAM1 = mv(lam1, {v, o}), LAM2 = mv(lam2, {v, v, o, o});
+    const TView L1v = mv(L1.p, {K, v, o}), R1v = mv(R1.p, {K, v, o}), L2v = mv(L2.p, {K, v, v, o, o}), R2v = mv(R2.p, {K, v, v, o, o});
+    auto vv = [&](double* p) { return mv(p, {K, v, v}); };
+    auto oo = [&](double* p) { return mv(p, {K, o, o}); };
+    auto ov = [&](double* p) { return mv(p, {K, o, v}); };
+    // l_z . t
+    e.contract(1.0, L2v, "zabij", T4, "cbij", 0.0, vv(Xvv.p), "zac");
+    e.contract(1.0, L2v, "zabij", T4, "abkj", 0.0, oo(Xoo.p), "zki");
+    e.contract(2.0, L1v, "zai", T4, "abij", 0.0, ov(Xov.p), "zjb");
+    e.contract(-1.0, L1v, "zai", T4, "abji", 1.0, ov(Xov.p), "zjb");
+    // lambda . t
+    e.contract(1.0, LAM2, "abij", T4, "cbij", 0.0, mv(Yvv.p, {v, v}), "ac");
+    e.contract(1.0, LAM2, "abij", T4, "abkj", 0.0, mv(Yoo.p, {o, o}), "ki");
+    e.contract(2.0, LAM1, "ai", T4, "abij", 0.0, mv(Yov.p, {o, v}), "jb");
+    e.contract(-1.0, LAM1, "ai", T4, "abji", 1.0, mv(Yov.p, {o, v}), "jb");
+    // lambda . r_z
+    e.contract(1.0, LAM2, "abij", R2v, "zcbij", 0.0, vv(Zvv.p), "zac");
+    e.contract(1.0, LAM2, "abij", R2v, "zabkj", 0.0, oo(Zoo.p), "zki");
+    e.contract(2.0, LAM1, "ai", R2v, "zabij", 0.0, ov(Zov.p), "zjb");
+    e.contract(-1.0, LAM1, "ai", R2v, "zabji", 1.0, ov(Zov.p), "zjb");
+    e.contract(2.0, LAM2, "abij", R1v, "zai", 0.0, mv(Le.p, {K, v, o}), "zbj");
+    e.contract(2.0, mv(Le.p, {K, v, o}), "zai", T4, "abij", 0.0, ov(Eov.p), "zjb");
+    e.contract(-1.0, mv(Le.p, {K, v, o}), "zai", T4, "abji", 1.0, ov(Eov.p), "zjb");
+    dev::Tdm1Parts q;
+    q.t1 = t1; q.lam1 = lam1; q.L1 = L1.p; q.R1 = R1.p;
+    q.Xvv = Xvv.p; q.Xoo = Xoo.p; q.Xov = Xov.p; q.Yvv = Yvv.p; q.Yoo = Yoo.p; q.Yov = Yov.p;
+    q.Zvv = Zvv.p; q.Zoo = Zoo.p; q.Zov = Zov.p; q.Le = Le.p; q.Eov = Eov.p;
+    q.gl = G.p; q.gr = G.p + K * n * n; q.r0 = G.p + 2 * K * n * n;
+    dev::tdm1_assemble(q, k, e.no, e.nv, e.stream);
+    dev::memcpy_d2h(gl_host, q.gl, sizeof(double) * K * n * n, e.stream);
+    dev::memcpy_d2h(gr_host, q.gr, sizeof(double) * K * n * n, e.stream);
+    dev::memcpy_d2h(r0_host, q.r0, sizeof(double) * K, e.stream);
+    dev::stream_sync(e.stream);
+}
+
+// ---- the Davidson correction of n roots over flat vectors (eom.h), sixteen roots per launch ----------------------------------------
+void davidson_correction(Engine& e, int n, const double* const* s, const double* const* r, const double* w_host, const double* d,
+                         double shift, double* const* q, int64_t n1, int64_t off2, int64_t len, double* norms_host) {
+    for (int lo = 0; lo < n; lo += 16) {
+        const int g = std::min(16, n - lo);
+        struct Buf {
+            Engine& e;
+            double* p;
+            Buf(Engine& e_, int64_t m) : e(e_), p(e_.scratch_get(std::max<int64_t>(m, 1))) {}
+            ~Buf() { e.scratch_put(p); }
+        } ws(e, dev::ipea_correction_ws_doubles(g, len)), out(e, 32);
+        dev::ipea_correction(g, s + lo, r + lo, w_host + lo, d, shift, q + lo, n1, off2, len, ws.p, out.p, e.stream);
+        const int slot = dev::readback_start(out.p, 2 * g, e.stream);
+        dev::readback_wait(slot, norms_host + 2 * lo, 2 * g);
+    }
 }
 
 // ---- eom_ccsd.py:169-198 (singles) and :200-266 (doubles) on the device ---------------------------------------------------------
@@ -1053,13 +1221,7 @@ void IpEaSigma::correction(int n, const double* const* s, const double* const* r
     if (off2 < n1() || len != off2 + n2()) throw Error("ip/ea correction: the flat layout does not match the operator");
     for (int z = 0; z < n; ++z)
         if (!s[z] || !r[z] || !q[z]) throw Error("ip/ea correction: null vector");
-    for (int lo = 0; lo < n; lo += 16) {
-        const int g = std::min(16, n - lo);
-        Tmp ws(*this, dev::ipea_correction_ws_doubles(g, len)), out(*this, 32);
-        dev::ipea_correction(g, s + lo, r + lo, w_host + lo, d, shift, q + lo, n1(), off2, len, ws, out, e.stream);
-        const int slot = dev::readback_start(out, 2 * g, e.stream);
-        dev::readback_wait(slot, norms_host + 2 * lo, 2 * g);
-    }
+    davidson_correction(e, n, s, r, w_host, d, shift, q, n1(), off2, len, norms_host);
 }
 
 }  // namespace pymes

@@ -32,7 +32,8 @@ class EomSigma {
     // ---- the adjoint build: o = A^T l for the sigma A of apply() under the plain inner product over both arrays, on
     // the exchange-symmetric subspace, from the SAME hoisted intermediates read through transposed operand views.  l2[z] must
     // have the exchange symmetry (sym[z] != 0: the caller knows; else tested here, one reduction and a synchronisation; refused
-    // by name otherwise); the vectors are handled one by one.  apply() is not affected: nothing it reads is written.
+    // by name otherwise).  k > 1 vectors go through every product stacked (left_stack: one GEMM per large product), k = 1 through
+    // the single-vector path.  apply() is not affected: nothing it reads is written.
     void apply_left(int k, const double* const* l1, const double* const* l2, const int* sym, double* const* o1,
                     double* const* o2);
     // One Lambda iteration for eta1[a,i] = 2 f_ov[i,a], eta2[a,b,i,j] = 2 V_ijab[i,j,a,b] - V_ijab[i,j,b,a] (read from the block):
@@ -66,6 +67,7 @@ class EomSigma {
     void left_prepare();
     struct LeftParts;
     void left_partials(const double* l1, const double* l2, LeftParts& w);
+    void left_stack(int k, const double* const* l1, const double* const* l2, double* const* o1, double* const* o2);
     void general_operands();          // LK3, LK2 (trial vectors without exchange symmetry), on first use
     bool v_sym = false, t_sym = false, hole_sym = false, fused_ok = false, many_ok = false;
     TView V(const char* name) const;
@@ -85,6 +87,20 @@ void eom_diagonals(Engine& e, const double* f_host, const double* t2, bool dress
 // diagonal (2.0: the matrix whose trace is the electron count).  Reads no integral block.
 void lambda_rdm1(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2, double ref,
                  double* gamma_host);
+
+// The transition densities of k EE-EOM-CCSD roots (formulas in include/pymes_amd.h, pymes_tdm1): gammaL, gammaR
+// [k,n,n] and r0 [k] on the host from t1, lam1 [v,o], t2, lam2 [v,v,o,o] and the left / right vectors (l1[z], l2[z]), (r1[z],
+// r2[z]) on the device.  Linear in every vector: normalisation is the caller's.  Reads no integral block.
+void transition_densities(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2, int k,
+                          const double* const* l1, const double* const* l2, const double* const* r1, const double* const* r2,
+                          double* gl_host, double* gr_host, double* r0_host);
+
+// For n roots over flat vectors of `len` doubles ([0,n1) singles, [n1,off2) zero pad, [off2,len) doubles; d the diagonal in the
+// same layout): q_n = (s_n - w_n r_n) / (w_n - d + shift) written (zero in the pad), norms[2 n] = |s_n - w_n r_n|^2,
+// norms[2 n + 1] = |r_n|^2 (one launch and one synchronisation per sixteen roots, fixed summation order).  The kernel of the
+// IP / EA driver; the EE drivers (right and left) use it with the diagonals of eom_diagonals.
+void davidson_correction(Engine& e, int n, const double* const* s, const double* const* r, const double* w_host, const double* d,
+                         double shift, double* const* q, int64_t n1, int64_t off2, int64_t len, double* norms_host);
 
 // IP- and EA-EOM-CCSD sigma builds (formulas in include/pymes_amd.h): the EE operator above restricted to the sector
 // with one non-interacting orbital.  Vectors: IP r1[i], r2[i,j,b]; EA r1[a], r2[a,b,j] — below r2[x,y,w] with x, y over P

@@ -6152,6 +6152,7 @@ struct LambdaK {
     const double* lam1; const double* lam2;
     double* out1; double* out2; double* err1; double* err2; double* ws;
     double cd, cx, shift, es;
+    long lp_ld, la_ld;          // row pitches of Lp / La (o^2 and o (o - 1) / 2 unless the ladder halves of k vectors lie side by side)
     int no, nv;
 };
 
@@ -6200,7 +6201,7 @@ __global__ void __launch_bounds__(256) lambda_assemble_kernel(const LambdaK k) {
     int a, b;
     unrank_pair(blockIdx.x, a, b);
     const int p = no + 1;
-    const long o2 = (long)no * no, ov = (long)no * nv, opp = (long)no * (no + 1) / 2;
+    const long o2 = (long)no * no, ov = (long)no * nv;
     const long ab = ((long)a * nv + b) * o2, ba = ((long)b * nv + a) * o2;
     const long tab = (long)a * no * ov + (long)b * no, tba = (long)b * no * ov + (long)a * no;
     for (int e = threadIdx.x; e < o2; e += 256) {             // sources read in (i,j) order
@@ -6221,9 +6222,8 @@ __global__ void __launch_bounds__(256) lambda_assemble_kernel(const LambdaK k) {
         }
     }
     __syncthreads();
-    const long opm = o2 - opp;
-    const double* __restrict__ row = k.Lp ? k.Lp + ((long)a * (a + 1) / 2 + b) * o2 : nullptr;
-    const double* __restrict__ rowa = (k.La && a != b) ? k.La + ((long)a * (a - 1) / 2 + b) * opm : nullptr;
+    const double* __restrict__ row = k.Lp ? k.Lp + ((long)a * (a + 1) / 2 + b) * k.lp_ld : nullptr;
+    const double* __restrict__ rowa = (k.La && a != b) ? k.La + ((long)a * (a - 1) / 2 + b) * k.la_ld : nullptr;
     const double ea = update ? k.ev[a] + k.ev[b] - k.shift : 0.0;
     for (int e = threadIdx.x; e < o2; e += 256) {
         const int i = e / no, j = e - i * no;
@@ -6306,6 +6306,115 @@ __global__ void __launch_bounds__(256) rdm1_assemble_kernel(const double* __rest
     }
 }
 
+// ==== transition densities of the EE-EOM-CCSD roots (device_api.h, tdm1_assemble) =====================================
+// grid (n, k, 2): row r of gammaL (blockIdx.z == 0) or gammaR (1) of root z, occupied rows first.  Both sides are the coefficients
+// C of the T1-dressed Fock matrix followed by the back-transformation of rdm1_assemble:
+//   g_oo[j,i] = C_oo[j,i] - sum_a t1[a,j] C_vo[a,i]      g_ov[j,b] = C_ov[j,b] + sum_i g_oo[j,i] t1[b,i] - sum_a t1[a,j] C_vv[a,b]
+//   g_vo[a,i] = C_vo[a,i]                                 g_vv[a,b] = C_vv[a,b] + sum_i C_vo[a,i] t1[b,i]
+// left:  C_vo = l1, C_oo = -2 Xoo, C_vv = 2 Xvv, C_ov = Xov.
+// right, s = <lambda, r> = sum lam1 r1 + trace Zvv (every block adds it up in the same fixed order):
+//   C_vo = Le - s lam1                                    C_oo[j,i] = -sum_a r1[a,j] lam1[a,i] - 2 Zoo[j,i] + 2 s Yoo[j,i]
+//   C_vv[a,b] = sum_i lam1[a,i] r1[b,i] + 2 Zvv[a,b] - 2 s Yvv[a,b]
+//   C_ov[j,b] = 2 r1[b,j] + Zov[j,b] + Eov[j,b] - s Yov[j,b] - 2 sum_i Yoo[j,i] r1[b,i] - 2 sum_a Yvv[a,b] r1[a,j]
+// Every element is one thread's sum in a fixed order; the block of row 0 of the right side writes r0[z] = -s.
+struct Tdm1K {
+    dev::Tdm1Parts q;
+    int no, nv;
+};
+
+__global__ void __launch_bounds__(256) tdm1_assemble_kernel(const Tdm1K k) {
+    extern __shared__ double S[];             // row [no], row2 [no], the 256 partial sums
+    const int no = k.no, nv = k.nv, n = no + nv, r = blockIdx.x, z = blockIdx.y, t = threadIdx.x;
+    double* row = S;
+    double* row2 = S + no;
+    double* sr = S + 2 * no;
+    const long n1 = (long)nv * no;
+    const double* __restrict__ t1 = k.q.t1;
+    if (blockIdx.z == 0) {
+        const double* __restrict__ l1 = k.q.L1 + (long)z * n1;
+        const double* __restrict__ Xvv = k.q.Xvv + (long)z * nv * nv;
+        const double* __restrict__ Xoo = k.q.Xoo + (long)z * no * no;
+        const double* __restrict__ Xov = k.q.Xov + (long)z * n1;
+        double* __restrict__ out = k.q.gl + ((long)z * n + r) * n;
+        if (r < no) {
+            const int j = r;
+            for (int i = t; i < no; i += 256) {
+                double s = -2.0 * Xoo[(long)j * no + i];
+                for (int a = 0; a < nv; ++a) s -= t1[(long)a * no + j] * l1[(long)a * no + i];
+                row[i] = s;
+                out[i] = s;
+            }
+            __syncthreads();
+            for (int b = t; b < nv; b += 256) {
+                double s = Xov[(long)j * nv + b];
+                for (int i = 0; i < no; ++i) s += row[i] * t1[(long)b * no + i];
+                for (int a = 0; a < nv; ++a) s -= 2.0 * t1[(long)a * no + j] * Xvv[(long)a * nv + b];
+                out[no + b] = s;
+            }
+            return;
+        }
+        const int a = r - no;
+        for (int i = t; i < no; i += 256) out[i] = l1[(long)a * no + i];
+        for (int b = t; b < nv; b += 256) {
+            double s = 2.0 * Xvv[(long)a * nv + b];
+            for (int i = 0; i < no; ++i) s += l1[(long)a * no + i] * t1[(long)b * no + i];
+            out[no + b] = s;
+        }
+        return;
+    }
+    const double* __restrict__ lam1 = k.q.lam1;
+    const double* __restrict__ r1 = k.q.R1 + (long)z * n1;
+    const double* __restrict__ Le = k.q.Le + (long)z * n1;
+    const double* __restrict__ Zvv = k.q.Zvv + (long)z * nv * nv;
+    const double* __restrict__ Zoo = k.q.Zoo + (long)z * no * no;
+    const double* __restrict__ Zov = k.q.Zov + (long)z * n1;
+    const double* __restrict__ Eov = k.q.Eov + (long)z * n1;
+    const double* __restrict__ Yvv = k.q.Yvv;
+    const double* __restrict__ Yoo = k.q.Yoo;
+    const double* __restrict__ Yov = k.q.Yov;
+    double* __restrict__ out = k.q.gr + ((long)z * n + r) * n;
+    double acc = 0.0;
+    for (long e = t; e < n1; e += 256) acc += lam1[e] * r1[e];
+    for (int a = t; a < nv; a += 256) acc += Zvv[(long)a * nv + a];
+    const double s = lambda_block_sum(acc, sr);
+    if (r == 0 && t == 0) k.q.r0[z] = -s;
+    if (r < no) {
+        const int j = r;
+        for (int i = t; i < no; i += 256) {
+            double c = -2.0 * Zoo[(long)j * no + i] + 2.0 * s * Yoo[(long)j * no + i], w = 0.0;
+            for (int a = 0; a < nv; ++a) {
+                const double la = lam1[(long)a * no + i], ta = t1[(long)a * no + j];
+                c -= r1[(long)a * no + j] * la + ta * (Le[(long)a * no + i] - s * la);
+                w += ta * la;
+            }
+            row[i] = c;
+            row2[i] = w;
+            out[i] = c;
+        }
+        __syncthreads();
+        for (int b = t; b < nv; b += 256) {
+            double c = 2.0 * r1[(long)b * no + j] + Zov[(long)j * nv + b] + Eov[(long)j * nv + b] - s * Yov[(long)j * nv + b];
+            for (int i = 0; i < no; ++i)
+                c += row[i] * t1[(long)b * no + i] - (2.0 * Yoo[(long)j * no + i] + row2[i]) * r1[(long)b * no + i];
+            for (int a = 0; a < nv; ++a)
+                c -= 2.0 * Yvv[(long)a * nv + b] * r1[(long)a * no + j]
+                     + 2.0 * t1[(long)a * no + j] * (Zvv[(long)a * nv + b] - s * Yvv[(long)a * nv + b]);
+            out[no + b] = c;
+        }
+        return;
+    }
+    const int a = r - no;
+    for (int i = t; i < no; i += 256) out[i] = Le[(long)a * no + i] - s * lam1[(long)a * no + i];
+    for (int b = t; b < nv; b += 256) {
+        double c = 2.0 * (Zvv[(long)a * nv + b] - s * Yvv[(long)a * nv + b]);
+        for (int i = 0; i < no; ++i) {
+            const double la = lam1[(long)a * no + i];
+            c += la * r1[(long)b * no + i] + (Le[(long)a * no + i] - s * la) * t1[(long)b * no + i];
+        }
+        out[no + b] = c;
+    }
+}
+
 }  // namespace
 
 namespace dev {
@@ -6319,6 +6428,8 @@ void lambda_assemble(const LambdaParts& q, int no, int nv, stream_t s) {
     if (!q.out1 || !q.out2) throw std::runtime_error("lambda_assemble: null output");
     if (q.D && (!q.Pd || !q.Px || !q.S1)) throw std::runtime_error("lambda_assemble: incomplete partial results");
     if (!q.D && (q.Pd || q.Px || q.S1 || q.Lp || q.La)) throw std::runtime_error("lambda_assemble: partial results without the direct one");
+    if (q.lp_ld < 0 || q.la_ld < 0 || (q.lp_ld && q.lp_ld < (int64_t)no * (no + 1) / 2) || (q.la_ld && q.la_ld < (int64_t)no * (no - 1) / 2))
+        throw std::runtime_error("lambda_assemble: bad row pitch of the ladder halves");
     const bool update = q.Vijab != nullptr;
     if ((q.La && !q.Lp) || (!q.lam1 != !q.lam2)) throw std::runtime_error("lambda_assemble: inconsistent operands");
     if (update && (!q.eta1 || !q.eo || !q.ev || !q.err1 || !q.err2 || !q.ws || !q.norm_dev))
@@ -6326,7 +6437,8 @@ void lambda_assemble(const LambdaParts& q, int no, int nv, stream_t s) {
     const long npairs = (long)nv * (nv + 1) / 2;
     if (npairs + 1 > 0x7fffffffL) throw std::runtime_error("lambda_assemble: grid too large");
     const LambdaK k{q.D, q.Pd, q.Px, q.Lp, q.La, q.S1, q.Vijab, q.eta1, q.eo, q.ev, q.lam1, q.lam2, q.out1, q.out2, q.err1, q.err2,
-                    q.ws, q.cd, q.cx, q.shift, q.err_scale, no, nv};
+                    q.ws, q.cd, q.cx, q.shift, q.err_scale, q.lp_ld ? (long)q.lp_ld : (long)no * no,
+                    q.la_ld ? (long)q.la_ld : (long)no * (no - 1) / 2, no, nv};
     hipStream_t st = (hipStream_t)s;
     launch_kernel(lambda_assemble_kernel, dim3((unsigned)(npairs + 1)), dim3(256), lds, st, k);
     if (update) launch_kernel(lambda_norm_kernel, dim3(1), dim3(256), 0, st, (const double*)q.ws, npairs + 1, q.norm_dev);
@@ -6338,6 +6450,17 @@ void rdm1_assemble(const double* Xvv, const double* Xoo, const double* Xov, cons
     if (no < 1 || nv < 1 || (size_t)no * sizeof(double) > 64 * 1024) throw std::runtime_error("rdm1_assemble: bad shape");
     launch_kernel(rdm1_assemble_kernel, dim3((unsigned)(no + nv)), dim3(256), sizeof(double) * no, (hipStream_t)s, Xvv, Xoo, Xov,
                   l1, t1, no, nv, ref, g);
+}
+
+void tdm1_assemble(const Tdm1Parts& q, int k, int no, int nv, stream_t s) {
+    if (no < 1 || nv < 1 || k < 1 || k > 65535) throw std::runtime_error("tdm1_assemble: bad shape");
+    const size_t lds = sizeof(double) * (2 * (size_t)no + 256);
+    if (lds > 64 * 1024) throw std::runtime_error("tdm1_assemble: nocc too large for the LDS rows");
+    if (!q.t1 || !q.lam1 || !q.L1 || !q.R1 || !q.Xvv || !q.Xoo || !q.Xov || !q.Yvv || !q.Yoo || !q.Yov || !q.Zvv || !q.Zoo ||
+        !q.Zov || !q.Le || !q.Eov || !q.gl || !q.gr || !q.r0)
+        throw std::runtime_error("tdm1_assemble: null operand");
+    const Tdm1K kk{q, no, nv};
+    launch_kernel(tdm1_assemble_kernel, dim3((unsigned)(no + nv), (unsigned)k, 2u), dim3(256), lds, (hipStream_t)s, kk);
 }
 
 }  // namespace dev

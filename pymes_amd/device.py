@@ -653,15 +653,20 @@ class Context:
         return np.array(out[:])
 
     # ---- launch graphs ----------------------------------------------------------------
+    recording = False      # between graph_begin and graph_end / graph_abort (solvers refuse by name before they allocate)
+
     def graph_begin(self):
         self.lib.call("pymes_graph_begin", self.handle)
+        self.recording = True
 
     def graph_end(self):
         g = C.c_void_p()
+        self.recording = False
         self.lib.call("pymes_graph_end", self.handle, C.byref(g))
         return g
 
     def graph_abort(self):
+        self.recording = False
         self.lib.call("pymes_graph_abort", self.handle)
 
     def graph_launch(self, g):

@@ -490,6 +490,13 @@ class CCSD(ccd.CCD):
             if self.shard_integrals:
                 raise ValueError("density=True with shard_integrals=True: the left sigma reads the whole V_abcd, which an "
                                  "integral-sharded context does not hold")
+        if kwargs.get("ee_roots"):         # likewise
+            if self.is_dcd:
+                raise ValueError("ee_roots: the EOM-CCSD operator and its left vectors are those of the CCSD similarity "
+                                 "transform, not defined for DCSD")
+            if self.shard_integrals:
+                raise ValueError("ee_roots with shard_integrals=True: the left sigma reads the whole V_abcd, which an "
+                                 "integral-sharded context does not hold")
         if frozen_core or fno_occ_threshold is not None or fno_nv is not None:
             return self._solve_fno(t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv,
                                    **kwargs)
@@ -513,6 +520,11 @@ class CCSD(ccd.CCD):
         # (pymes_amd/solver/lambda_ccsd.py); with frozen_core / fno_* they are those of the correlated space
         # (lambda_r_epsilon=x: the residual norm at which the Lambda iteration stops, default 1e-8)
         density = bool(kwargs.get("density", False))
+        # ee_roots=k (opt-in): the k lowest excitation energies with their left vectors and transition densities
+        # (pymes_amd/solver/eom_transitions.py): "ee e", "ee tdm left", "ee tdm right" [k,n,n], "ee residuals"; with
+        # frozen_core / fno_* those of the correlated space; with density=True Lambda is solved once (ee_r_epsilon=x: the
+        # relative residual norm at which both Davidson runs stop, default 1e-8)
+        ee_roots = int(kwargs.get("ee_roots", 0) or 0)
         ints, own = self._integrals(t_fock_pq, t_V_pqrs)
         ctx = ints.ctx
         st = None
@@ -521,6 +533,9 @@ class CCSD(ccd.CCD):
             if density:
                 from pymes_amd.solver import lambda_ccsd
                 lambda_ccsd.check_context(ctx)             # (a sharded DeviceIntegrals of the caller: before anything is dressed)
+            if ee_roots:
+                from pymes_amd.solver import eom_transitions
+                eom_transitions.check_context(ctx, self.no)
             print_logging_info(algo_name)
             print_logging_info("Using dcsd: ", self.is_dcd, level=1)
             print_logging_info("Solving doubles amplitude equation", level=1)
@@ -570,6 +585,7 @@ class CCSD(ccd.CCD):
                 e_ip, e_ea = self._ip_ea_roots(t_fock_pq, ints, st["t1"], st["t2"], ip_roots, ea_roots,
                                                kwargs.get("ip_ea_r_epsilon"))
             lam = self._lambda_density(t_fock_pq, ints, st, kwargs.get("lambda_r_epsilon")) if density else None
+            ee = self._ee_transitions(t_fock_pq, ints, st, ee_roots, kwargs.get("ee_r_epsilon"), lam) if ee_roots else None
             if kwargs.get("device_amplitudes"):
                 # device-resident hand-over to the callers of the solution (EOM-CCSD / FEAST: get_T1_dressed_V on the same
                 # DeviceIntegrals, EOM_CCSD.solve on the result): "t1" / "t2" are DeviceArrays of the integrals' context —
@@ -599,6 +615,8 @@ class CCSD(ccd.CCD):
                 res["qp gap"] = float(e_ip[0] + e_ea[0])      # the quasi-particle gap: lowest IP + lowest EA
             if lam is not None:
                 res.update(lam)
+            if ee is not None:
+                res.update(ee)
             return res
         finally:
             collector.__exit__()
@@ -648,6 +666,23 @@ class CCSD(ccd.CCD):
         solver.t2 = None                                 # (the solver's T2 buffer goes back to the pool; the results are host arrays)
         return {"lambda1": out["lambda1"], "lambda2": out["lambda2"], "rdm1": rdm1,
                 "natural occupations": lambda_ccsd.natural_occupations(rdm1)}
+
+    def _ee_transitions(self, t_fock_pq, ints, st, n_roots, r_epsilon=None, lam=None):
+        """The lowest excitation energies, left vectors and transition densities of the converged amplitudes on the
+        integrals' context (device hand-over as ``_lambda_density``; ``lam``: its result, so that Lambda is solved once)."""
+        from pymes_amd.solver.eom_transitions import EOM_CCSD_Transitions
+        f = t_fock_pq.get() if isinstance(t_fock_pq, DeviceArray) else np.asarray(t_fock_pq, dtype=np.float64)
+        t1, t2 = st["t1"], st["t2"]
+        fd = self.get_T1_dressed_fock(f, t1, ints)
+        solver = EOM_CCSD_Transitions(self.no, n_excit=n_roots, device=self.device)
+        if r_epsilon is not None:
+            solver.r_epsilon = float(r_epsilon)
+        dressed = self.get_T1_dressed_V(t1, ints, solver.BLOCKS)
+        out = solver.solve(fd, dressed, t2, t1, lam=None if lam is None else (lam["lambda1"], lam["lambda2"]),
+                           eps=(st["eps_i"], st["eps_a"]), level_shift=st["level_shift"])
+        self.ee_solver = solver                          # (vectors, r0, biorthogonality, strengths() of the last solve)
+        return {"ee e": out["e"], "ee tdm left": out["tdm left"], "ee tdm right": out["tdm right"],
+                "ee residuals": {"right": out["right residual"], "left": out["left residual"]}}
 
     def _solve_fno(self, t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv, **kwargs):
         from pymes_amd.solver import fno

@@ -134,16 +134,21 @@ class Lambda_CCSD:
             if own:
                 ctx.close()
 
-    def solve(self, f_dressed, V_dressed, t2, eps=None, level_shift=0.0):
+    def solve(self, f_dressed, V_dressed, t2, eps=None, level_shift=0.0, handle=None):
         """Solve the Lambda equations.  Call forms as ``EOM_CCSD.solve``: (dressed Fock matrix, dictionary of dressed host
         blocks, host T2) — a context is built and dies with the call — or the device-resident hand-over of a CCSD solve
         (``DressedDeviceIntegrals``, T2 a host array or a DeviceArray of the same context).  ``eps = (eps_o, eps_v)`` and
         ``level_shift`` are the orbital energies and the shift of the denominators (default: the diagonal of the dressed
         Fock matrix, no shift; ``CCSD.solve(density=True)`` passes those of its own update).  Returns a dictionary with
-        "lambda1" [v,o], "lambda2" [v,v,o,o] (host), "residual norm" (|eta + A^T lambda|), "iterations", "converged"."""
+        "lambda1" [v,o], "lambda2" [v,v,o,o] (host), "residual norm" (|eta + A^T lambda|), "iterations", "converged".
+        ``handle = (ctx, LeftSigma)``: iterate on a handle the caller has hoisted from the same (f, V, t2) and keeps (the
+        transition solver: one hoist for the right, the Lambda and the left solve); it is not closed here."""
         print_title("Lambda-CCSD Solver", )
         t_init = time.time()
-        f, ctx, sig, own = self._open(f_dressed, V_dressed, t2)
+        if handle is None:
+            f, ctx, sig, own = self._open(f_dressed, V_dressed, t2)
+        else:
+            f, (ctx, sig), own = np.asarray(f_dressed, dtype=np.float64), handle, False
         no, nv = self.no, ctx.nv
         eps_o, eps_v = (f.diagonal()[:no].copy(), f.diagonal()[no:].copy()) if eps is None else eps
         mixer = DIIS(dim_space=self.diis_dim)
@@ -191,7 +196,8 @@ class Lambda_CCSD:
         finally:
             alive = not own and ctx.handle is not None
             mixer.restart(release=ctx.pool_put if alive else None)
-            sig.close()
+            if handle is None:
+                sig.close()
             if own:
                 ctx.close()
             elif alive:

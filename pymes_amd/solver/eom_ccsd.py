@@ -19,14 +19,16 @@ import time
 import numpy as np
 
 from pymes_amd import _lib
-from pymes_amd.device import Context, DeviceArray, PymesError
+from pymes_amd.device import Context, DeviceArray
 from pymes_amd.integral.device import DressedDeviceIntegrals
 from pymes_amd.integral.partition import BLOCK_NAMES
 from pymes_amd.log import print_logging_info, print_title
 from pymes_amd.mixer.diis import _single_threaded_blas
+from pymes_amd.solver import subspace
+from pymes_amd.solver.subspace import FlatLayout, extend_subspace, orthonormalise_block
 
 
-class _Sigma:
+class _Sigma(subspace.LibraryHandle):
     """Device-resident H-bar . u (eom_ccsd.py:268-385): a handle of the engine's EOM sigma build (csrc/eom.cpp,
     ``pymes_eom_sigma_prepare / _apply``).  Every V.T product that does not depend on the trial vector is hoisted once per solve;
     one ``apply_many`` call builds sigma for any number of trial vectors — exchange-symmetric ones stacked, so that every shared
@@ -34,6 +36,7 @@ class _Sigma:
 
     # the blocks a sigma build reads (eom_ccsd.py:268-385)
     BLOCKS = ("ijab", "iabj", "iajb", "ijka", "ijak", "iabc", "iajk", "abic", "klij", "abcd")
+    DESTROY, NOUN = "pymes_eom_sigma_destroy", "EOM sigma"
 
     def __init__(self, ctx, f, t2, dressed=False):
         """``dressed``: read the context's T1-DRESSED blocks (the context of a CCSD solve whose integrals were dressed in
@@ -48,30 +51,12 @@ class _Sigma:
         h = C.c_void_p()
         ctx.lib.call("pymes_eom_sigma_prepare", ctx.handle, _lib.host_ptr(self._f), C.c_void_p(t2.ptr), int(self.dressed),
                      C.byref(h))
-        self._h = h
-        ctx.on_close(self._ctx_closing)               # the handle dies before its context
+        self._bind(h)
         flags = C.c_int()
         ctx.lib.call("pymes_eom_sigma_flags", self._h, C.byref(flags))
         fl = flags.value
         self.v_sym, self.t_sym, self.hole_sym = bool(fl & 1), bool(fl & 2), bool(fl & 4)
         self.fused_ok, self.many_ok = bool(fl & 8), bool(fl & 16)
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h is not None:        # (also after the context has gone: the library invalidated the handle then, this frees its shell)
-            self.ctx.lib.call("pymes_eom_sigma_destroy", h)
-
-    def _ctx_closing(self, ctx):
-        try:
-            self.close()
-        except Exception:
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def exchange_symmetric(self, u2):
         return self.ctx.exchange_symmetric(u2)      # one reduction kernel, no temporary
@@ -80,14 +65,15 @@ class _Sigma:
         """[(sigma1_z, sigma2_z)] for the trial vectors (u1s[z], u2s[z]).  ``syms[z]``: the caller's knowledge that u2_z has
         the exchange symmetry u2_abij = u2_baji (tested on the device when ``syms`` is None); ``out1`` / ``out2``: device
         arrays that receive sigma1_z / sigma2_z (e.g. the two parts of a flat subspace vector) instead of fresh ones."""
-        if self._h is None:
-            raise PymesError("the EOM sigma handle has been destroyed (its context was closed)")
-        k = len(u1s)
+        return self._apply("pymes_eom_sigma_apply", u1s, u2s, syms, out1, out2)
+
+    def _apply(self, entry, u1s, u2s, syms, out1, out2):
+        h, k = self._handle(), len(u1s)
         c, no, nv = self.ctx, self.no, self.nv
         s1 = [out1[z] if out1 is not None else c.empty((nv, no)) for z in range(k)]
         s2 = [out2[z] if out2 is not None else c.empty((nv, nv, no, no)) for z in range(k)]
         sym = None if syms is None else (C.c_int * max(k, 1))(*[int(bool(x)) for x in syms])
-        c.lib.call("pymes_eom_sigma_apply", self._h, k, _lib.ptr_array([u.ptr for u in u1s]), _lib.ptr_array([u.ptr for u in u2s]),
+        c.lib.call(entry, h, k, _lib.ptr_array([u.ptr for u in u1s]), _lib.ptr_array([u.ptr for u in u2s]),
                    sym, _lib.ptr_array([x.ptr for x in s1]), _lib.ptr_array([x.ptr for x in s2]))
         return list(zip(s1, s2))
 
@@ -135,18 +121,14 @@ class EOM_CCSD:
         f = t_fock_dressed_pq.get() if isinstance(t_fock_dressed_pq, DeviceArray) else np.asarray(t_fock_dressed_pq, dtype=np.float64)
         t2 = t_T_abij if isinstance(t_T_abij, DeviceArray) else ctx.array(t_T_abij)
         us, v, e = self._ritz
-        lay = self._layout(self.no, ctx.nv)
-        nflat = lay[2]
+        lay = self._layout(ctx)
         sig = _Sigma(ctx, f, t2, dressed=True)
-        rz = [ctx.empty((nflat,)) for _ in range(self.n_excit)]
+        rz = [lay.empty() for _ in range(self.n_excit)]
         ctx.lincomb_multi(rz, us, v)
-        wz = [self._zero_pad(ctx, ctx.empty((nflat,)), lay) for _ in rz]
-        u2s = [self._u2(ctx, r, lay) for r in rz]
-        sig.apply_many([self._u1(ctx, r, lay) for r in rz], u2s, [sig.exchange_symmetric(u2) for u2 in u2s],
-                       out1=[self._u1(ctx, w, lay) for w in wz], out2=[self._u2(ctx, w, lay) for w in wz])
+        wz = subspace.apply_flat(lay, sig.apply_many, rz, [sig.exchange_symmetric(lay.part2(r)) for r in rz])
         out = []
         for n in range(self.n_excit):        # the residual vector itself (its norm from the three inner products cancels at 1e-8)
-            z = ctx.empty((nflat,))
+            z = lay.empty()
             ctx.lincomb_multi([z], [wz[n], rz[n]], np.array([[1.0], [-e[n]]]))
             out.append(float(np.sqrt(ctx.gram([z], [z])[0, 0] / ctx.gram([rz[n]], [rz[n]])[0, 0])))
         return out
@@ -219,17 +201,8 @@ class EOM_CCSD:
             sig = _Sigma(ctx, f, t2, dressed=device_form)
             t0 = lap("hoist_s", t0)
             print_logging_info("Initialising u tensors...", level=1)
-            lay = self._layout(no, nv)
-            n1, off2, nflat = lay
-            # (a combination of vectors with a zero pad has a zero pad; a sigma vector gets its parts written one by one)
-            fresh = lambda: ctx.empty((nflat,))
-            new = []                                  # raw new trial vectors of this pass [u1 | pad | u2], flat
-            for i in range(self.n_excit):
-                vec = ctx.zeros((nflat,))
-                one = np.zeros(n1)
-                one[lowest_ex_ind_init[i]] = 1.0
-                self._u1(ctx, vec, lay).set(one.reshape(nv, no))
-                new.append(vec)
+            lay = self._layout(ctx)
+            new = [lay.unit(p) for p in lowest_ex_ind_init]      # raw new trial vectors of this pass [u1 | pad | u2], flat
             us, ws, B = [], [], np.zeros((0, 0))      # orthonormal basis, its sigma vectors, U^T W
             # exchange symmetry u2_abij = u2_baji: the start vectors have it (zero doubles), and the stacked sigma build,
             # the projections and the expansions keep it exactly — tested only where that chain is broken
@@ -246,23 +219,14 @@ class EOM_CCSD:
                 if not reuse and us:                                                 # the reference's schedule: everything anew
                     new, us, ws, B = us + new, [], [], np.zeros((0, 0))
                 if new:
-                    new = self._orthonormalise_block(ctx, us, new, lay)              # :91
+                    new = orthonormalise_block(ctx, lay, us, new)                    # :91
                     t0 = lap("orth_s", t0)
-                    u2s = [self._u2(ctx, u, lay) for u in new]
-                    sym = [True] * len(new) if all_sym else [sig.exchange_symmetric(u2) for u2 in u2s]
-                    wn = [self._zero_pad(ctx, fresh(), lay) for _ in new]
-                    sig.apply_many([self._u1(ctx, u, lay) for u in new], u2s, sym,                  # :95-101, new vectors only
-                                   out1=[self._u1(ctx, w, lay) for w in wn], out2=[self._u2(ctx, w, lay) for w in wn])
+                    sym = [True] * len(new) if all_sym else [sig.exchange_symmetric(lay.part2(u)) for u in new]
+                    wn = subspace.apply_flat(lay, sig.apply_many, new, sym)          # :95-101, new vectors only
                     tm["sigma_vectors"] += len(new)
                     t0 = lap("sigma_s", t0)
-                    d0 = len(us)
-                    us, ws = us + new, ws + wn
-                    Bn = np.zeros((len(us), len(us)))                                # :103-109, the new rows and columns
-                    Bn[:d0, :d0] = B
-                    Bn[:, d0:] = ctx.gram(us, wn)
-                    if d0:
-                        Bn[d0:, :d0] = ctx.gram(new, ws[:d0])
-                    B, new = Bn, []
+                    us, ws, B = extend_subspace(ctx, us, ws, B, new, wn)             # :103-109, the new rows and columns
+                    new = []
                 dim = len(us)
                 e_old = self.e_excit                                                 # :110 (every pass, so the collapse
                 with _single_threaded_blas():                                        # (a <= 12 x 12 matrix: no thread pool)
@@ -281,14 +245,14 @@ class EOM_CCSD:
                     with _single_threaded_blas():
                         Rc = np.linalg.cholesky(v.T @ v).T
                         cmat = v @ np.linalg.inv(Rc)
-                    cu = [fresh() for _ in range(self.n_excit)]
-                    cw = [fresh() for _ in range(self.n_excit)]
+                    cu = [lay.empty() for _ in range(self.n_excit)]
+                    cw = [lay.empty() for _ in range(self.n_excit)]
                     ctx.lincomb_multi(cu, us, cmat)
                     ctx.lincomb_multi(cw, ws, cmat)
                     B = cmat.T @ B @ cmat
                     G = ctx.gram(cu, cu)
                     if np.abs(G - np.eye(self.n_excit)).max() > self.ORTH_TOL:       # (nearly parallel Ritz vectors)
-                        cu, cw = self._orthonormalise_block(ctx, [], cu, lay, shadows=cw)
+                        cu, cw = orthonormalise_block(ctx, lay, [], cu, shadows=cw)
                         B = ctx.gram(cu, cw)
                     us, ws = cu, cw
                     self.e_excit = e_old
@@ -298,7 +262,7 @@ class EOM_CCSD:
                         den = e[n] - D_ai[lowest_ex_ind_init[n]] + 1e-5
                         coef[:dim, n] = v[:, n] / den
                         coef[dim:, n] = -e[n] * v[:, n] / den
-                    new = [fresh() for _ in range(self.n_excit)]
+                    new = [lay.empty() for _ in range(self.n_excit)]
                     ctx.lincomb_multi(new, ws + us, coef)
                     e_old = self.e_excit
                     diff_e_norm = np.linalg.norm(self.e_excit - e)
@@ -328,8 +292,8 @@ class EOM_CCSD:
             # (as in the reference the attributes hold the trial space as the loop left it: basis first, then the expansion
             # vectors; in the device form they stay device arrays of the caller's context)
             keep = (us + new)[:self.n_excit]
-            self.u_singles = [self._u1(ctx, u, lay) for u in keep]
-            self.u_doubles = [self._u2(ctx, u, lay) for u in keep]
+            self.u_singles = [lay.part1(u) for u in keep]
+            self.u_doubles = [lay.part2(u) for u in keep]
             if not device_form:
                 self.u_singles = [x.get() for x in self.u_singles]
                 self.u_doubles = [x.get() for x in self.u_doubles]
@@ -339,109 +303,13 @@ class EOM_CCSD:
             if not device_form:
                 ctx.close()
 
-    @staticmethod
-    def _part(ctx, vec, offset, shape):
-        return DeviceArray(ctx, vec.ptr + 8 * offset, shape, owned=False, keepalive=vec)
-
-    # ---- flat subspace vectors [u1 (nv no) | zero pad | u2 (nv^2 no^2)], the doubles on a 256-byte boundary ----------------
-    @staticmethod
-    def _layout(no, nv):
-        n1 = nv * no
-        off2 = -(-n1 // 32) * 32
-        return n1, off2, off2 + nv * nv * no * no
-
-    def _u1(self, ctx, vec, lay):
-        return self._part(ctx, vec, 0, (ctx.nv, ctx.no))
-
-    def _u2(self, ctx, vec, lay):
-        return self._part(ctx, vec, lay[1], (ctx.nv, ctx.nv, ctx.no, ctx.no))
-
-    def _orthonormalise_block(self, ctx, us, ys, lay, shadows=None):
-        """EOM_CCSD.QR (eom_ccsd.py:512-541) for a trial space [us | ys] whose leading vectors ``us`` are orthonormal already
-        (Householder QR leaves those as they are, up to a sign the Rayleigh-Ritz step does not see): the block ``ys`` is
-        projected against ``us`` and orthonormalised in itself by rounds of block Gram-Schmidt in its Pythagorean form
-        — ONE Gram product [us | ys]^T ys (every vector read once), the Cholesky factor of ys^T ys - P^T P on the host, ONE
-        multi-output combination (ys - us P) R^-1 — so a round costs two passes over the subspace instead of a dot product
-        and an update per pair of vectors; a round is repeated only when the check of the result asks for it.  Returns the
-        new orthonormal block; with ``shadows`` (vectors that any linear map of ``ys`` must follow, e.g. their sigma vectors;
-        only for an empty ``us``) returns (block, mapped shadows)."""
-        assert shadows is None or not us
-        k, d, nflat = len(ys), len(us), lay[2]
-        eye = np.vstack([np.zeros((d, k)), np.eye(k)])
-        for rnd in range(4):
-            G = ctx.gram(us + ys, ys)
-            # a-posteriori check = the Gram product the next round needs anyway: expansion vectors are residuals, orthogonal
-            # to the basis up to rounding (U^T (W v - e U v) = B v - e v), and one round brings them to the unit matrix
-            if rnd > 0 and np.abs(G - eye).max() <= self.ORTH_TOL:
-                break
-            P, S = G[:d], G[d:] - G[:d].T @ G[:d]
-            S = 0.5 * (S + S.T)
-            scale = np.sqrt(np.abs(np.diag(S)))
-            ok = bool(np.all(np.isfinite(scale)) and np.all(scale > 0.0) and np.all(np.diag(S) > 0.0))
-            if ok:
-                try:
-                    with _single_threaded_blas():
-                        Lc = np.linalg.cholesky(S / np.outer(scale, scale))          # equilibrated: S = D L L^T D
-                        ok = bool(np.diag(Lc).min() > 1e-7)                          # (condition number of ys below ~1e7)
-                        Rinv = np.linalg.inv(Lc.T * scale[None, :]) if ok else None  # R = L^T D, ys_new = ys' R^-1
-                except np.linalg.LinAlgError:
-                    ok = False
-            if not ok or rnd == 3:       # (numerically) dependent new vectors: vector by vector, null vectors replaced
-                return self._orthonormalise_sequential(ctx, us, ys, lay, shadows)
-            coef = np.vstack([-P @ Rinv, Rinv])
-            out = [ctx.empty((nflat,)) for _ in range(k)]
-            ctx.lincomb_multi(out, us + ys, coef)
-            if shadows is not None:
-                sh = [ctx.empty((nflat,)) for _ in range(k)]
-                ctx.lincomb_multi(sh, shadows, Rinv)
-                shadows = sh
-            ys = out
-        return ys if shadows is None else (ys, shadows)
-
-    ORTH_TOL = 1e-13       # max |U^T U - 1| accepted for the trial space (numpy's Householder QR: ~1e-15)
+    _part = staticmethod(subspace.view)        # (a non-owning view into a flat vector; the FEAST driver has a layout of its own)
+    ORTH_TOL = subspace.ORTH_TOL
 
     @staticmethod
-    def _zero_pad(ctx, vec, lay):
-        if lay[1] > lay[0]:
-            DeviceArray(ctx, vec.ptr + 8 * lay[0], (lay[1] - lay[0],), owned=False, keepalive=vec).zero_()
-        return vec
-
-    def _orthonormalise_sequential(self, ctx, us, ys, lay, shadows=None):
-        """The fall-back of ``_orthonormalise_block``: modified Gram-Schmidt with re-orthogonalisation, one vector at a time
-        (one Gram product and one combination per sweep).  A vector that vanishes against the others — the reference's
-        Householder QR would return an arbitrary unit vector orthogonal to them — is replaced by a seeded random,
-        exchange-symmetric direction."""
-        done, sh_done = list(us), []
-        n1, off2, nflat = lay
-        rng = np.random.default_rng(len(us) + 1000 * len(ys))
-        for z, y in enumerate(ys):
-            q = ctx.empty((nflat,)).copy_from(y)
-            sh = None if shadows is None else ctx.empty((nflat,)).copy_from(shadows[z])
-            for attempt in range(3):
-                nrm0 = np.sqrt(ctx.gram([q], [q])[0, 0])
-                for _ in range(2):
-                    if done:
-                        proj = ctx.gram(done, [q])[:, 0]
-                        ctx.lincomb_multi([q], done, -proj[:, None], beta=[1.0])
-                        if sh is not None:
-                            ctx.lincomb_multi([sh], sh_done, -proj[len(us):, None], beta=[1.0])
-                nrm = np.sqrt(ctx.gram([q], [q])[0, 0])
-                if np.isfinite(nrm) and nrm > 1e-12 * max(nrm0, 1e-300) and nrm > 0.0:
-                    break
-                if shadows is not None:
-                    raise np.linalg.LinAlgError("linearly dependent Ritz vectors in the Davidson collapse")
-                r1 = rng.standard_normal((ctx.nv, ctx.no))
-                r2 = rng.standard_normal((ctx.nv, ctx.nv, ctx.no, ctx.no))
-                q.zero_()
-                self._u1(ctx, q, lay).set(r1)
-                self._u2(ctx, q, lay).set(r2 + r2.transpose(1, 0, 3, 2))
-            ctx.lincomb_multi([q], [], np.zeros((0, 1)), beta=[1.0 / nrm])
-            if sh is not None:
-                ctx.lincomb_multi([sh], [], np.zeros((0, 1)), beta=[1.0 / nrm])
-                sh_done.append(sh)
-            done.append(q)
-        block = done[len(us):]
-        return block if shadows is None else (block, sh_done)
+    def _layout(ctx):
+        """Flat subspace vectors [u1 (nv no) | zero pad | u2 (nv^2 no^2)]."""
+        return FlatLayout(ctx, (ctx.nv, ctx.no), (ctx.nv, ctx.nv, ctx.no, ctx.no))
 
     # ---- the reference's host-array call forms (eom_ccsd.py:268-385) ---------------------------
     def _host_sigma(self, t_fock_pq, dict_t_V, t_u_ai, t_u_abij, t_T_abij, which):

@@ -9,8 +9,8 @@ and written-out formulas in include/pymes_amd.h):
   gammaL_k = d/df ( <l1_k, R1(f)> + <l2_k, R2(f)> ),   gammaR_k = d/df <0|(1 + Lambda) f~ (r0_k + R_k)|0>,   r0_k = -<lambda, r_k>,
   S_k(O) = (sum gammaL_k O) (sum gammaR_k O),   oscillator strength (2/3) w_k sum_x S_k(mu_x).
 
-Both eigenproblems run through one block Davidson on flat vectors [x1 | zero pad | x2] (the layout and the subspace tools of
-``EOM_CCSD``): sigma of the NEW vectors of a pass in one stacked library call (``pymes_eom_sigma_apply`` /
+Both eigenproblems run through the block Davidson of ``subspace.py`` on flat vectors [x1 | zero pad | x2] (``FlatLayout``):
+sigma of the NEW vectors of a pass in one stacked library call (``pymes_eom_sigma_apply`` /
 ``pymes_eom_sigma_apply_left``), the corrections ``(s - w x) / (w - d + shift)`` of all roots and their residual norms from one
 launch and one synchronisation (``pymes_eom_correction``, d from ``pymes_eom_diagonals``), collapse to the Ritz vectors at
 ``max_dim``.  The right run starts from unit vectors on the smallest singles diagonals and takes the lowest roots; the left run
@@ -26,8 +26,7 @@ from pymes_amd import _lib
 from pymes_amd.device import DeviceArray, PymesError
 from pymes_amd.log import print_logging_info, print_title
 from pymes_amd.mixer.diis import _single_threaded_blas
-from pymes_amd.solver import lambda_ccsd
-from pymes_amd.solver.eom_ccsd import EOM_CCSD
+from pymes_amd.solver import lambda_ccsd, subspace
 
 LDS_BYTES = 64 * 1024
 
@@ -59,7 +58,7 @@ def device_tdm1(ctx, t1, t2, lam1, lam2, l1s, l2s, r1s, r2s):
     return gl, gr, r0
 
 
-class EOM_CCSD_Transitions(EOM_CCSD):
+class EOM_CCSD_Transitions:
     BLOCKS = lambda_ccsd.Lambda_CCSD.BLOCKS
 
     def __init__(self, no, n_excit=3, r_epsilon=1.e-8, max_iter=200, device=0):
@@ -74,74 +73,6 @@ class EOM_CCSD_Transitions(EOM_CCSD):
         self.lambda_r_epsilon = None                  # (default: r_epsilon)
         self.result = None
         self.lambda_solver = None
-
-    # ---- one block Davidson for both sides --------------------------------------------------------------------------------------
-    def _davidson(self, ctx, lay, apply_flat, d, start, targets, side):
-        """(w [k], Ritz vectors, relative residuals [k], passes).  ``targets`` None: the k lowest roots, residuals with the Ritz
-        values; else the Ritz pair nearest each target, residuals and corrections with the target itself."""
-        nr, nflat = self.n_excit, lay[2]
-        fresh = lambda: ctx.empty((nflat,))
-        us, ws, B, new = [], [], np.zeros((0, 0)), list(start)
-        rel, rz, w, complex_passes = np.full(nr, np.inf), [], np.zeros(nr), 0
-        for it in range(self.max_iter):
-            new = self._orthonormalise_block(ctx, us, new, lay) if new else []
-            if new:
-                wn = apply_flat(new)                                        # sigma of the new vectors only, one stacked call
-                d0 = len(us)
-                us, ws = us + new, ws + wn
-                Bn = np.zeros((len(us), len(us)))
-                Bn[:d0, :d0] = B
-                Bn[:, d0:] = ctx.gram(us, wn)
-                if d0:
-                    Bn[d0:, :d0] = ctx.gram(new, ws[:d0])
-                B = Bn
-            elif it > 0:
-                break                                                       # (the subspace is invariant)
-            with _single_threaded_blas():
-                lam, vec = np.linalg.eig(B)
-            if targets is None:
-                pick = np.argsort(lam.real, kind="stable")[:nr]
-            else:
-                pick, left = [], list(range(len(lam)))
-                for t in targets:                                           # nearest Ritz value, each taken once
-                    p = min(left, key=lambda q: abs(lam[q] - t))
-                    pick.append(p)
-                    left.remove(p)
-                pick = np.array(pick)
-            theta, imag = np.real(lam[pick]), np.imag(lam[pick])
-            complex_passes = complex_passes + 1 if np.abs(imag).max() > self.r_epsilon else 0
-            if complex_passes >= 3:
-                bad = int(np.argmax(np.abs(imag)))
-                raise PymesError("EOM_CCSD_Transitions: root %d of the %s problem has a complex Ritz value (%.6f %+.3ej): a "
-                                 "complex-conjugate pair has no real eigenvector" % (bad, side, theta[bad], imag[bad]))
-            v = np.real(vec[:, pick])
-            v = v / np.linalg.norm(v, axis=0)[None, :]
-            w = theta if targets is None else np.asarray(targets, dtype=np.float64)
-            rz, sz, qs = [fresh() for _ in range(nr)], [fresh() for _ in range(nr)], [fresh() for _ in range(nr)]
-            ctx.lincomb_multi(rz, us, v)
-            ctx.lincomb_multi(sz, ws, v)
-            res, nrm = self._correction(ctx, lay, sz, rz, w, d, qs)
-            rel = np.sqrt(res / nrm)
-            print_logging_info("%s pass %d" % (side, it), level=1)
-            for r in range(nr):
-                print_logging_info("Root {:d} energy = {:.12f}  |residual| / |x| = {:.3e}".format(r, theta[r], rel[r]), level=2)
-            if np.all(rel < self.r_epsilon) and complex_passes == 0:
-                return theta if targets is None else w, rz, rel, it + 1
-            todo = [n for n in range(nr) if not rel[n] < self.r_epsilon]
-            if len(us) + len(todo) > self.max_dim:                          # collapse to the Ritz vectors
-                us, ws = self._orthonormalise_block(ctx, [], rz, lay, shadows=sz)
-                B = ctx.gram(us, ws)
-            new = [qs[n] for n in todo]
-        return (w if targets is not None else theta), rz, rel, self.max_iter
-
-    def _correction(self, ctx, lay, ss, rs, w, d, qs):
-        n = len(rs)
-        ww = np.ascontiguousarray(w, dtype=np.float64)
-        out = np.zeros(2 * max(n, 1))
-        ctx.lib.call("pymes_eom_correction", ctx.handle, n, _lib.ptr_array([x.ptr for x in ss]), _lib.ptr_array([x.ptr for x in rs]),
-                     _lib.host_ptr(ww), C.c_void_p(d.ptr), float(self.shift), _lib.ptr_array([x.ptr for x in qs]), lay[1], lay[2],
-                     _lib.host_ptr(out))
-        return out[0:2 * n:2].copy(), out[1:2 * n:2].copy()
 
     # ---- the solve ------------------------------------------------------------------------------------------------------------------
     def solve(self, f_dressed, V_dressed, t2, t1, lam=None, eps=None, level_shift=0.0):
@@ -160,40 +91,35 @@ class EOM_CCSD_Transitions(EOM_CCSD):
             check_context(V_dressed.ctx, self.no)
         else:
             check_occupied(self.no)
-        opener = lambda_ccsd.Lambda_CCSD(self.no, device=self.device)
-        opener.algo_name = self.algo_name
-        f, ctx, sig, own = opener._open(f_dressed, V_dressed, t2)
+        f, ctx, sig, own = subspace.open_handle(self.no, self.device, f_dressed, V_dressed, t2, self.BLOCKS, lambda_ccsd.LeftSigma,
+                                                self.algo_name)
         collector = quiet_collector().__enter__()
         nr, no, nv = self.n_excit, self.no, ctx.nv
         try:
             if nr < 1 or nr > no * nv:
                 raise ValueError("EOM_CCSD_Transitions: 1 <= n_excit <= %d (the number of singles)" % (no * nv))
-            lay = self._layout(no, nv)
-            n1, off2, nflat = lay
-            part1 = lambda x: self._u1(ctx, x, lay)
-            part2 = lambda x: self._u2(ctx, x, lay)
-
-            def flat_apply(fn):
-                def run(vecs):
-                    outs = [self._zero_pad(ctx, ctx.empty((nflat,)), lay) for _ in vecs]
-                    fn([part1(u) for u in vecs], [part2(u) for u in vecs], [True] * len(vecs),
-                       out1=[part1(x) for x in outs], out2=[part2(x) for x in outs])
-                    return outs
-                return run
-            right, left = flat_apply(sig.apply_many), flat_apply(sig.apply_left_many)
-            d = ctx.zeros((nflat,))
+            lay = subspace.FlatLayout(ctx, (nv, no), (nv, nv, no, no))
+            part1, part2, off2 = lay.part1, lay.part2, lay.off2
+            right = lambda vecs: subspace.apply_flat(lay, sig.apply_many, vecs, [True] * len(vecs))
+            left = lambda vecs: subspace.apply_flat(lay, sig.apply_left_many, vecs, [True] * len(vecs))
+            d = ctx.zeros((lay.nflat,))
             ctx.lib.call("pymes_eom_diagonals", ctx.handle, _lib.host_ptr(np.ascontiguousarray(f)), C.c_void_p(sig.T.ptr),
                          int(sig.dressed), C.c_void_p(d.ptr), C.c_void_p(d.ptr + 8 * off2))
             d1 = part1(d).get().ravel()
-            start = []
-            for p in np.argsort(d1, kind="stable")[:nr]:
-                vec = ctx.zeros((nflat,))
-                one = np.zeros(n1)
-                one[p] = 1.0
-                part1(vec).set(one.reshape(nv, no))
-                start.append(vec)
+            start = [lay.unit(p) for p in np.argsort(d1, kind="stable")[:nr]]
+
+            def correction(ss, rs, w, d, shift, qs):
+                return subspace.correction(ctx.lib, "pymes_eom_correction", ctx.handle, lay, ss, rs, w, d, shift, qs)
+
+            def davidson(apply, start, targets, side):
+                """(w, Ritz vectors, passes): a root whose Ritz value keeps an imaginary part is refused by name.  (As before the
+                move, a run that ends without converging — no new direction left included — reports max_iter passes.)"""
+                dav = subspace.block_davidson(ctx, lay, apply, correction, d, start, nr, self.max_dim, self.max_iter, self.r_epsilon,
+                                              self.shift, targets=targets, label=side,
+                                              refuse_complex="EOM_CCSD_Transitions: root %d of the " + side + " problem")
+                return dav.w, dav.rz, dav.passes if dav.converged else self.max_iter
             # ---- right vectors, unit norm, ascending ---------------------------------------------------------------------------
-            w, rz, _, it_r = self._davidson(ctx, lay, right, d, start, None, "right")
+            w, rz, it_r = davidson(right, start, None, "right")
             order = np.argsort(w, kind="stable")
             w, rz = w[order], [rz[n] for n in order]
             nrm = np.sqrt(np.diag(ctx.gram(rz, rz)))
@@ -209,18 +135,18 @@ class EOM_CCSD_Transitions(EOM_CCSD):
             else:
                 lam, lam_ok = (np.asarray(lam[0], dtype=np.float64), np.asarray(lam[1], dtype=np.float64)), True
             # ---- left vectors: from the right ones, the Ritz pair nearest each w_k ----------------------------------------------
-            start = [ctx.empty((nflat,)).copy_from(x) for x in rz]
-            _, lz, _, it_l = self._davidson(ctx, lay, left, d, start, w, "left")
+            start = [lay.empty().copy_from(x) for x in rz]
+            _, lz, it_l = davidson(left, start, w, "left")
             G = ctx.gram(lz, rz)                                            # G_jk = <l_j, r_k>
             with _single_threaded_blas():
                 Gi = np.linalg.inv(G)
-            ln = [ctx.empty((nflat,)) for _ in range(nr)]
+            ln = [lay.empty() for _ in range(nr)]
             ctx.lincomb_multi(ln, lz, Gi.T)                                 # l_j <- sum_m (G^-1)_jm l_m
             lz = ln
             # ---- certificates from one fresh stacked build per side -----------------------------------------------------------------
-            scratch = [ctx.empty((nflat,)) for _ in range(nr)]
-            res_r, nrm_r = self._correction(ctx, lay, right(rz), rz, w, d, scratch)
-            res_l, nrm_l = self._correction(ctx, lay, left(lz), lz, w, d, scratch)
+            scratch = [lay.empty() for _ in range(nr)]
+            res_r, nrm_r = correction(right(rz), rz, w, d, self.shift, scratch)
+            res_l, nrm_l = correction(left(lz), lz, w, d, self.shift, scratch)
             rel_r, rel_l = np.sqrt(res_r / nrm_r), np.sqrt(res_l / nrm_l)
             bio = float(np.abs(ctx.gram(lz, rz) - np.eye(nr)).max())
             # ---- densities -------------------------------------------------------------------------------------------------------------

@@ -19,10 +19,10 @@ import numpy as np
 
 from pymes_amd import _lib
 from pymes_amd.device import Context, DeviceArray, PymesError
-from pymes_amd.integral.device import DressedDeviceIntegrals
 from pymes_amd.log import print_logging_info, print_title
 from pymes_amd.mixer.diis import DIIS
 from pymes_amd.solver.eom_ccsd import _Sigma
+from pymes_amd.solver.subspace import open_handle
 
 
 # The DIIS error vector is ERR_SCALE x the update: the mixer tests linear dependence of its subspace with an ABSOLUTE 1e-12 on the
@@ -41,20 +41,9 @@ def check_context(ctx):
 class LeftSigma(_Sigma):
     """The handle of the sigma build with its adjoint (``pymes_eom_sigma_apply_left``) and the Lambda step on it."""
 
-    def _handle(self):
-        if self._h is None:
-            raise PymesError("the EOM sigma handle has been destroyed (its context was closed)")
-        return self._h
-
     def apply_left_many(self, l1s, l2s, syms=None, out1=None, out2=None):
         """[(A^T l)_1, (A^T l)_2] for the left vectors (l1s[z], l2s[z]), device arrays; l2 must be exchange-symmetric."""
-        h, c, k = self._handle(), self.ctx, len(l1s)
-        o1 = [out1[z] if out1 is not None else c.empty((self.nv, self.no)) for z in range(k)]
-        o2 = [out2[z] if out2 is not None else c.empty((self.nv, self.nv, self.no, self.no)) for z in range(k)]
-        sym = None if syms is None else (C.c_int * max(k, 1))(*[int(bool(x)) for x in syms])
-        c.lib.call("pymes_eom_sigma_apply_left", h, k, _lib.ptr_array([u.ptr for u in l1s]), _lib.ptr_array([u.ptr for u in l2s]),
-                   sym, _lib.ptr_array([x.ptr for x in o1]), _lib.ptr_array([x.ptr for x in o2]))
-        return list(zip(o1, o2))
+        return self._apply("pymes_eom_sigma_apply_left", l1s, l2s, syms, out1, out2)
 
     def apply_left(self, l1, l2, l2_sym=None):
         return self.apply_left_many([l1], [l2], None if l2_sym is None else [l2_sym])[0]
@@ -95,37 +84,10 @@ class Lambda_CCSD:
         self.lambda1 = self.lambda2 = self.t2 = None
         self.residual_norm, self.iterations, self.converged, self.history = np.inf, 0, False, []
 
-    def _open(self, f, V, t2):
-        """(ctx, handle, owns the context) for the two call forms of ``EOM_CCSD.solve``."""
-        if isinstance(f, DeviceArray):
-            f = f.get()
-        f = np.asarray(f, dtype=np.float64)
-        nv = f.shape[0] - self.no
-        if isinstance(V, DressedDeviceIntegrals):
-            ctx = V.ctx
-            check_context(ctx)
-            if ctx.no != self.no or ctx.nv != nv:
-                raise ValueError("the integrals' context does not match (no, nv) of the Fock matrix")
-            if isinstance(t2, DeviceArray) and t2.ctx is not ctx:
-                raise ValueError("t2 lives in another context than the dressed integrals")
-            V.require(self.BLOCKS)
-            t2d = t2 if isinstance(t2, DeviceArray) else ctx.array(np.asarray(t2, dtype=np.float64))
-            return f, ctx, LeftSigma(ctx, f, t2d, dressed=True), False
-        ctx = Context(self.no, nv, device=self.device)
-        try:
-            for name in self.BLOCKS:
-                blk = V.get(name)
-                if blk is None:
-                    raise KeyError("%s: the dressed block '%s' is missing from the dictionary" % (self.algo_name, name))
-                ctx.set_V_block(name, np.ascontiguousarray(blk, dtype=np.float64))
-            return f, ctx, LeftSigma(ctx, f, ctx.array(np.asarray(t2, dtype=np.float64)), dressed=False), True
-        except Exception:
-            ctx.close()
-            raise
-
     def apply_left(self, f_dressed, V_dressed, t2, l1, l2):
         """One adjoint build for host arrays: ((A^T l)_1, (A^T l)_2)."""
-        _, ctx, sig, own = self._open(f_dressed, V_dressed, t2)
+        _, ctx, sig, own = open_handle(self.no, self.device, f_dressed, V_dressed, t2, self.BLOCKS, LeftSigma, self.algo_name,
+                                       check_context)
         try:
             o1, o2 = sig.apply_left(ctx.array(np.asarray(l1, dtype=np.float64)), ctx.array(np.asarray(l2, dtype=np.float64)))
             return o1.get(), o2.get()
@@ -146,7 +108,8 @@ class Lambda_CCSD:
         print_title("Lambda-CCSD Solver", )
         t_init = time.time()
         if handle is None:
-            f, ctx, sig, own = self._open(f_dressed, V_dressed, t2)
+            f, ctx, sig, own = open_handle(self.no, self.device, f_dressed, V_dressed, t2, self.BLOCKS, LeftSigma, self.algo_name,
+                                           check_context)
         else:
             f, (ctx, sig), own = np.asarray(f_dressed, dtype=np.float64), handle, False
         no, nv = self.no, ctx.nv

@@ -664,6 +664,41 @@ int pymes_ipea_sigma_correction(pymes_ipea* h, int n, const double* const* s_dev
                                 const double* d_dev, double shift, double* const* q_dev, int64_t off2, int64_t len,
                                 double* norms_host);
 int pymes_ipea_sigma_destroy(pymes_ipea* h);
+/* ---- left IP / EA vectors, Dyson amplitudes and pole strengths ---------------------------------------------------
+ * H is the operator of pymes_ipea_sigma_apply on the compact vectors (r1, r2), <x, y> the plain sum over both arrays.
+ * pymes_ipea_sigma_apply_left: o_z = H^T l_z for k vectors, stacked like _apply.  With U1, R, Rx, Rt (and Rn for EA) the packed
+ * operands of the right build and D, E, L, S1 its partial results (s2[x,y,w] = D[x,y,w] + E[y,x,w] + L[x,y,w], s1 = S1):
+ *   dD = l2,  dE = l2 with its first two indices exchanged,  dL = l2,  dS1 = l1      (the packing of the left vector)
+ *   every product  C += alpha A . B  of the right build with the trial-vector operand A:  dA += alpha dC . B, the same hoisted
+ *   operand or integral block B read through the same view (V_iabc in place, the EA ladder ONE product over V_abcd for all k)
+ *   o2[x,y,w] = dR[x,y,w] + dRx[y,x,w] + 2 dRt[x,y,w] - dRt[y,x,w] (+ dRn[x,y,w]),  o1 = dU1   (the adjoint of the packing)
+ * Left eigenvectors H^T l_k = w_k l_k are normalised <l_j, r_k> = delta_jk by the caller.
+ * Dyson amplitudes.  Take the EE transition densities of pymes_tdm1 for the problem with the extra orbital x, T and Lambda
+ * zero in x.  b_p: the restriction to the sector (one copy: [x,b,i,j] -> [i,j,b] for IP, [a,b,x,j] -> [a,b,j] for EA) of
+ * d(R1, R2)/df_xp (IP) or d(R1, R2)/df_px (EA);  e_q: ONE HALF of the functional r -> gammaR[q,x] (IP) / gammaR[x,q] (EA) on the
+ * embedded exchange-symmetric vector;  psiL_k(p) = <l_k, b_p>,  psiR_k(q) = <e_q, r_k>.  Written out (t = T2, Yoo[k,i] = sum
+ * lam2[a,b,i,j] t[a,b,k,j], Yvv[a,c] = sum lam2[a,b,i,j] t[c,b,i,j]):
+ * IP, l1[i], l2[i,j,b], r1[i], r2[i,j,b]:
+ *   psiL(i) = l1[i]                              psiL(a) = sum_i l1[i] t1[a,i] + sum l2[i,j,b] t[a,b,i,j]
+ *   psiR(a) = sum_i lam1[a,i] r1[i] / 2 + sum lam2[a,b,i,j] r2[i,j,b]
+ *   psiR(j) = r1[j] + sum lam1[a,i] (2 r2[j,i,a] - r2[i,j,a]) / 2 - sum_i Yoo[j,i] r1[i] - sum_a t1[a,j] psiR(a)
+ *   i.e. b_i = the unit single i,  b_a = (t1[a,:], t[a,b,i,j])
+ * EA, l1[a], l2[a,b,j], r1[a], r2[a,b,j]:
+ *   psiL(a) = l1[a]                              psiL(k) = -sum_a t1[a,k] l1[a] - sum l2[a,b,j] t[a,b,k,j]
+ *   psiR(i) = -sum_a r1[a] lam1[a,i] / 2 - sum lam2[a,b,i,j] r2[a,b,j]
+ *   psiR(b) = r1[b] + sum lam1[a,i] (2 r2[b,a,i] - r2[a,b,i]) / 2 - sum_a r1[a] Yvv[a,b] + sum_i psiR(i) t1[b,i]
+ *   i.e. b_a = the unit single a,  b_k = -(t1[:,k], t[a,b,k,j])
+ * Residue Z_k[q,p] = psiR_k(q) psiL_k(p), pole strength P_k = sum_p psiR_k(p) psiL_k(p); with V = 0 every Koopmans root has
+ * P = 1.  Sum rules (identities in t, lambda): sum_c e_q[c] b_p[c] = rdm1[q,p] / 2 (IP), delta_qp - rdm1[p,q] / 2 (EA).
+ * pymes_ipea_dyson: psiL_host, psiR_host [k,n] (occupied orbitals first) for k roots given as device vectors of the handle's
+ * kind; t2 is the handle's.  Yoo, Yvv are built once per call, the root-dependent contractions are engine products with the k
+ * vectors stacked, the rest one assembly launch.  Linear in every vector; reads no integral block; identical calls give
+ * identical bits (no atomics, fixed summation order).  Both entries refuse a context that is recording a launch graph. */
+int pymes_ipea_sigma_apply_left(pymes_ipea* h, int k, const double* const* l1_dev, const double* const* l2_dev,
+                                double* const* o1_dev, double* const* o2_dev);
+int pymes_ipea_dyson(pymes_ipea* h, const double* t1_dev, const double* lam1_dev, const double* lam2_dev, int k,
+                     const double* const* l1_dev, const double* const* l2_dev, const double* const* r1_dev,
+                     const double* const* r2_dev, double* psiL_host, double* psiR_host);
 /* ---- CCSD Lambda equations and the one-particle density -----------------------------------------------------
  * Vectors are pairs (x1 [v,o], x2 [v,v,o,o]) with x2_abij = x2_baji; <x, y> is the plain sum over all elements of both arrays.
  * A is the EE-EOM-CCSD sigma of pymes_eom_sigma_apply (eom_ccsd.py:268-385), f~ / V the dressed Fock matrix and blocks of the

@@ -173,6 +173,8 @@ SIGNATURES = {
     "pymes_ipea_sigma_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "pymes_ipea_sigma_flags": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pymes_ipea_sigma_apply": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    "pymes_ipea_sigma_apply_left": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    "pymes_ipea_dyson": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 6),
     "pymes_ipea_sigma_diagonals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pymes_ipea_sigma_correction": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                               C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),

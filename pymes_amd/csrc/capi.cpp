@@ -1104,6 +1104,27 @@ int pymes_ipea_sigma_apply(pymes_ipea* h, int k, const double* const* r1, const 
         SI(h, "ipea_sigma_apply").apply(k, r1, r2, s1, s2);
     });
 }
+int pymes_ipea_sigma_apply_left(pymes_ipea* h, int k, const double* const* l1, const double* const* l2, double* const* o1,
+                                double* const* o2) {
+    return guarded([&] {
+        need(l1, "l1"); need(l2, "l2"); need(o1, "o1"); need(o2, "o2");
+        if (k < 0 || k > 4096) throw pymes::Error("ipea_sigma_apply_left: 0 <= k <= 4096");
+        for (int z = 0; z < k; ++z)
+            if (l2[z] == o2[z] || l1[z] == o1[z]) throw pymes::Error("ipea_sigma_apply_left: output aliases input");
+        SI(h, "ipea_sigma_apply_left").apply_left(k, l1, l2, o1, o2);
+    });
+}
+int pymes_ipea_dyson(pymes_ipea* h, const double* t1, const double* lam1, const double* lam2, int k, const double* const* l1,
+                     const double* const* l2, const double* const* r1, const double* const* r2, double* psiL_host,
+                     double* psiR_host) {
+    return guarded([&] {
+        need(t1, "t1"); need(lam1, "lam1"); need(lam2, "lam2"); need(l1, "l1"); need(l2, "l2"); need(r1, "r1"); need(r2, "r2");
+        need(psiL_host, "psiL"); need(psiR_host, "psiR");
+        if (k < 1 || k > 4096) throw pymes::Error("ipea_dyson: 1 <= k <= 4096");
+        pymes::IpEaSigma& s = SI(h, "ipea_dyson");
+        pymes::ipea_dyson(s.engine(), s.which(), t1, s.amplitudes(), lam1, lam2, k, l1, l2, r1, r2, psiL_host, psiR_host);
+    });
+}
 int pymes_ipea_sigma_diagonals(pymes_ipea* h, double* d1, double* d2) {
     return guarded([&] {
         need(d1, "d1"); need(d2, "d2");

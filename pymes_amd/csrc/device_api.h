@@ -313,6 +313,23 @@ void ipea_pack(int k, const double* const* r1, const double* const* r2, int P, i
 // s1_z = S1[z][n1]
 void ipea_assemble(int k, const double* D, const double* E, const double* L, const double* S1, int P, int S, int n1,
                    double* const* s1, double* const* s2, stream_t s);
+// The adjoint of ipea_pack, one pass over the partial results of the left build (eom.cpp, IpEaSigma::apply_left):
+// o2_z[x,y,w] = dR[z,x,y,w] + dRx[z,y,x,w] + 2 dRt[z,x,y,w] - dRt[z,y,x,w] + dRn[x,y,z,w] (dRn may be null);  o1_z = dU1[z][n1].
+// Rows along w on both sides, every output element written once, no atomics.
+void ipea_unpack(int k, const double* dU1, const double* dR, const double* dRx, const double* dRt, const double* dRn, int P, int S,
+                 int n1, double* const* o1, double* const* o2, stream_t s);
+// Dyson amplitudes of k IP (kind 0) / EA (kind 1) roots (eom.cpp, ipea_dyson; formulas: include/pymes_amd.h, pymes_ipea_dyson):
+// psiL, psiR [k,n] (device, occupied orbitals first) from t1, lam1 [v,o], Yoo[k,i] = sum lam2[a,b,i,j] t2[a,b,k,j], Yvv[a,c] = sum
+// lam2[a,b,i,j] t2[c,b,i,j], the stacked singles L1, R1 [k,n1] and, with m = nv (IP) / no (EA), A [k,m] = lam2 . r2_z,
+// B [k,m] = l2_z . t2, C [k,n1] = lam1 . (2 r2_z - r2_z^(xy)).  One launch, one block per root, no atomics, fixed summation order;
+// reads no integral block.
+struct DysonParts {
+    const double* t1 = nullptr; const double* lam1 = nullptr; const double* Yoo = nullptr; const double* Yvv = nullptr;
+    const double* L1 = nullptr; const double* R1 = nullptr; const double* A = nullptr; const double* B = nullptr;
+    const double* C = nullptr;
+    double* psiL = nullptr; double* psiR = nullptr;
+};
+void ipea_dyson_assemble(const DysonParts& q, int k, int kind, int no, int nv, stream_t s);
 // Diagonals from L_oo [no,no] and L_vv [nv,nv] (only their diagonals are read).  kind 0 (IP): d1[i] = -L_ii,
 // d2[i,j,b] = L_bb - L_ii - L_jj;  kind 1 (EA): d1[a] = L_aa, d2[a,b,j] = L_aa + L_bb - L_jj
 void ipea_diagonals(const double* Loo, const double* Lvv, int kind, int no, int nv, double* d1, double* d2, stream_t s);

@@ -808,6 +808,13 @@ __attribute__((weak)) void ipea_assemble(int, const double*, const double*, cons
                                          double* const*, double* const*, stream_t) {
     throw std::runtime_error("ipea_assemble: not available in this backend");
 }
+__attribute__((weak)) void ipea_unpack(int, const double*, const double*, const double*, const double*, const double*, int, int, int,
+                                       double* const*, double* const*, stream_t) {
+    throw std::runtime_error("ipea_unpack: not available in this backend");
+}
+__attribute__((weak)) void ipea_dyson_assemble(const DysonParts&, int, int, int, int, stream_t) {
+    throw std::runtime_error("ipea_dyson_assemble: not available in this backend");
+}
 __attribute__((weak)) void ipea_diagonals(const double*, const double*, int, int, int, double*, double*, stream_t) {
     throw std::runtime_error("ipea_diagonals: not available in this backend");
 }

@@ -1209,6 +1209,97 @@ void IpEaSigma::apply_ea(int k, const double* const* r1, const double* const* r2
     dev::ipea_assemble(k, D, E, L, S1, nv, no, nv, s1, s2, e.stream);
 }
 
+// ---- the adjoint build (eom.h): each product of apply_ip / apply_ea once, trial-vector operand and output exchanged ----------------
+void IpEaSigma::apply_left(int k, const double* const* l1, const double* const* l2, double* const* o1, double* const* o2) {
+    if (k < 1) return;
+    for (int z = 0; z < k; ++z)
+        if (!l1[z] || !l2[z] || !o1[z] || !o2[z]) throw Error("ip/ea left sigma: null vector");
+    const int step = stack_limit();
+    for (int lo = 0; lo < k; lo += step) {
+        const int g = std::min(k - lo, step);
+        if (kind == IP) left_ip(g, l1 + lo, l2 + lo, o1 + lo, o2 + lo);
+        else left_ea(g, l1 + lo, l2 + lo, o1 + lo, o2 + lo);
+    }
+}
+
+void IpEaSigma::left_ip(int k, const double* const* l1, const double* const* l2, double* const* o1, double* const* o2) {
+    const int64_t o = no, v = nv, K = k, n2 = o * o * v;
+    const Ops q{e};
+    // dS1, dD, dE: U1, R, Rx of the left vector (Rt of it is not read);  gU, gR, gX, gT: the derivatives with respect to U1, R, Rx, Rt
+    Tmp dS1(*this, K * o), dD(*this, K * n2), dE(*this, K * n2), Ru(*this, K * n2), gU(*this, K * o), gR(*this, K * n2),
+        gX(*this, K * n2), gT(*this, K * n2), dYS(*this, K * (v + o)), dXU(*this, K * (v + o)), dZ(*this, K * v * v * v);
+    dev::ipea_pack(k, l1, l2, no, nv, no, dS1, dD, dE, Ru, nullptr, e.stream);
+    const TView dS1v = mv(dS1, {K, o}), dDv = mv(dD, {K, o, o, v}), dEv = mv(dE, {K, o, o, v}), gUv = mv(gU, {K, o}),
+                gRv = mv(gR, {K, o, o, v}), gXv = mv(gX, {K, o, o, v}), gTv = mv(gT, {K, o, o, v}), dYSv = mv(dYS, {K, v + o}),
+                dXUv = mv(dXU, {K, v + o}), dZv = mv(dZ, {K, v, v, v});
+    const TView LooV = mv(Loo, {o, o}), LvvV = mv(Lvv, {v, v}), T4 = mv(T, {v, v, o, o});
+    // the ring-type terms
+    q.C(1.0, dDv, "zjia", mv(PA, {o, v, o, v}), "iald", 0.0, gRv, "zjld");
+    q.C(1.0, dDv, "zjia", mv(PB, {o, v, o, v}), "iald", 0.0, gXv, "zjld");
+    q.C(1.0, dEv, "zija", mv(MDU, {o, v, o, v}), "jald", 1.0, gXv, "zild");
+    // D += [Y | r1] . [t ; A] backwards, then dYS = [dXU_c | dS1] (the singles read YS_i directly)
+    q.C(1.0, dDv, "zijb", mv(TA, {v + o, o, o, v}), "nijb", 0.0, dXUv, "zn");
+    e.copy(slice(dXUv, 1, 0, v), slice(dYSv, 1, 0, v));
+    e.copy(dS1v, slice(dYSv, 1, v, v + o));
+    q.C(1.0, dYSv, "zn", mv(BB, {o, o, v, v + o}), "lkdn", 0.0, gTv, "zlkd");
+    q.C(1.0, mv(dS1, {K, 1, o}), "zxi", mv(fov, {o, v, 1}), "jbx", 1.0, gTv, "zijb");
+    q.C(-1.0, dS1v, "zi", LooV, "ki", 0.0, gUv, "zk");
+    e.axpby(1.0, slice(dXUv, 1, v, v + o), 1.0, gUv);
+    // one-index dressings and the hole ladder
+    q.C(-1.0, LooV, "li", dDv, "zijb", 1.0, gRv, "zljb", "z");
+    q.C(-1.0, LooV, "lj", dDv, "zijb", 1.0, gRv, "zilb", "zi");
+    q.C(1.0, dDv, "zijb", LvvV, "bd", 1.0, gRv, "zijd");
+    q.C(1.0, mv(B2, {o, o, o, o}), "klij", dDv, "zijb", 1.0, gRv, "zklb", "z");
+    // -V_lacd t_cdji r1_l backwards: dZ = -dE . t, then against V_lacd read in place
+    q.C(-1.0, dEv, "zija", T4, "cdji", 0.0, dZv, "zacd");
+    q.C(1.0, dZv, "zacd", V("iabc"), "lacd", 1.0, gUv, "zl");
+    dev::ipea_unpack(k, gU, gR, gX, gT, nullptr, no, nv, no, o1, o2, e.stream);
+}
+
+void IpEaSigma::left_ea(int k, const double* const* l1, const double* const* l2, double* const* o1, double* const* o2) {
+    const int64_t o = no, v = nv, K = k, n2 = v * v * o;
+    const Ops q{e};
+    Tmp dS1(*this, K * v), dD(*this, K * n2), dE(*this, K * n2), Ru(*this, K * n2), dL(*this, K * n2), gU(*this, K * v),
+        gR(*this, K * n2), gX(*this, K * n2), gT(*this, K * n2), gN(*this, K * n2), dXX(*this, K * o * o * o), dyy(*this, K * o),
+        dQ(*this, K * o * v * v), dQp(*this, K * o * v * v);
+    dev::ipea_pack(k, l1, l2, nv, no, nv, dS1, dD, dE, Ru, dL, e.stream);
+    const TView dS1v = mv(dS1, {K, v}), dDv = mv(dD, {K, v, v, o}), dEv = mv(dE, {K, v, v, o}), gUv = mv(gU, {K, v}),
+                gRv = mv(gR, {K, v, v, o}), gXv = mv(gX, {K, v, v, o}), gTv = mv(gT, {K, v, v, o}), dXXv = mv(dXX, {K, o, o, o}),
+                dyyv = mv(dyy, {K, o}), dQv = mv(dQ, {K, o, v, v}), dQpv = mv(dQp, {o, v, v, K});
+    const TView LooV = mv(Loo, {o, o}), LvvV = mv(Lvv, {v, v}), T4 = mv(T, {v, v, o, o}), FOV = mv(fov, {o, v});
+    const TView Vijab = V("ijab"), Viabc = V("iabc");
+    auto P4 = [&](double* p) { return mv(p, {v, o, v, o}); };
+    // the ring-type terms
+    q.C(1.0, dDv, "zbai", P4(PA), "aidl", 0.0, gRv, "zbdl");
+    q.C(1.0, dDv, "zbai", P4(PB), "aidl", 0.0, gXv, "zbdl");
+    q.C(1.0, dEv, "zabi", P4(MDU), "bidl", 1.0, gXv, "zadl");
+    // singles
+    q.C(1.0, mv(dS1, {K, 1, v}), "zxa", mv(fovT, {v, o, 1}), "bjx", 0.0, gTv, "zabj");
+    q.C(1.0, dS1v, "za", LvvV, "ab", 0.0, gUv, "zb");
+    q.C(1.0, Viabc, "jabc", dS1v, "za", 1.0, gTv, "zcbj");
+    // one-index dressings
+    q.C(1.0, LvvV, "ad", dDv, "zabj", 1.0, gRv, "zdbj", "z");
+    q.C(1.0, LvvV, "bc", dDv, "zabj", 1.0, gRv, "zacj", "za");
+    q.C(-1.0, dDv, "zabj", LooV, "kj", 1.0, gRv, "zabk");
+    // t XX and t y backwards
+    q.C(1.0, T4, "abkl", dDv, "zabj", 0.0, dXXv, "zklj", "z");
+    q.C(1.0, T4, "abkj", dDv, "zabj", 0.0, dyyv, "zk");
+    q.C(1.0, Vijab, "kldc", dXXv, "zklj", 1.0, gRv, "zdcj", "z");
+    q.C(1.0, V("ijka"), "lkjd", dXXv, "zklj", 1.0, gUv, "zd");
+    q.C(-1.0, Vijab, "kldc", dyyv, "zk", 1.0, gTv, "zdcl");
+    q.C(-1.0, FOV, "kd", dyyv, "zk", 1.0, gUv, "zd");
+    // the V_kacd t r1 terms backwards: dQ, dQ' of o v^2 per vector, then against V_kacd read in place
+    q.C(1.0, dDv, "zabj", P4(TT), "ckbj", 0.0, dQv, "zkac");
+    q.C(-1.0, dDv, "zabj", P4(Td), "ckbj", 0.0, dQpv, "kacz");
+    q.C(-1.0, dEv, "zbaj", P4(Tx), "ckaj", 1.0, dQpv, "kbcz");
+    q.C(1.0, Viabc, "kacd", dQv, "zkac", 1.0, gUv, "zd");
+    q.C(1.0, Viabc, "kadc", dQpv, "kacz", 1.0, gUv, "zd");
+    q.C(1.0, V("abic"), "bajc", dEv, "zbaj", 1.0, gUv, "zc");
+    // the particle ladder of all k vectors backwards: ONE product over V_abcd
+    q.C(1.0, V("abcd"), "abcd", mv(dL, {v, v, K, o}), "abzj", 0.0, mv(gN, {v, v, K, o}), "cdzj");
+    dev::ipea_unpack(k, gU, gR, gX, gT, gN, nv, no, nv, o1, o2, e.stream);
+}
+
 void IpEaSigma::diagonals(double* d1, double* d2) {
     if (!d1 || !d2) throw Error("ip/ea diagonals: null argument");
     dev::ipea_diagonals(Loo, Lvv, kind == EA ? 1 : 0, no, nv, d1, d2, e.stream);
@@ -1222,6 +1313,54 @@ void IpEaSigma::correction(int n, const double* const* s, const double* const* r
     for (int z = 0; z < n; ++z)
         if (!s[z] || !r[z] || !q[z]) throw Error("ip/ea correction: null vector");
     davidson_correction(e, n, s, r, w_host, d, shift, q, n1(), off2, len, norms_host);
+}
+
+// ---- Dyson amplitudes (eom.h; formulas in include/pymes_amd.h, pymes_ipea_dyson) ------------------------------------------------------
+void ipea_dyson(Engine& e, IpEaSigma::Kind kind, const double* t1, const double* t2, const double* lam1, const double* lam2, int k,
+                const double* const* l1, const double* const* l2, const double* const* r1, const double* const* r2,
+                double* psiL_host, double* psiR_host) {
+    if (!t1 || !t2 || !lam1 || !lam2 || !l1 || !l2 || !r1 || !r2 || !psiL_host || !psiR_host) throw Error("ipea_dyson: null argument");
+    if (k < 1) throw Error("ipea_dyson: needs at least one root");
+    for (int z = 0; z < k; ++z)
+        if (!l1[z] || !l2[z] || !r1[z] || !r2[z]) throw Error("ipea_dyson: null vector");
+    const bool ip = kind == IpEaSigma::IP;
+    const int64_t o = e.no, v = e.nv, n = o + v, P = ip ? o : v, S = ip ? v : o, m = S, n2 = P * P * S;
+    struct Buf {
+        Engine& e;
+        double* p;
+        Buf(Engine& e_, int64_t d) : e(e_), p(e_.scratch_get(std::max<int64_t>(d, 1))) {}
+        ~Buf() { e.scratch_put(p); }
+    };
+    const TView T4 = mv(t2, {v, v, o, o}), LAM1 = mv(lam1, {v, o}), LAM2 = mv(lam2, {v, v, o, o});
+    // lambda . t, once per call
+    Buf Yoo(e, o * o), Yvv(e, v * v);
+    e.contract(1.0, LAM2, "abij", T4, "abkj", 0.0, mv(Yoo.p, {o, o}), "ki");
+    e.contract(1.0, LAM2, "abij", T4, "cbij", 0.0, mv(Yvv.p, {v, v}), "ac");
+    for (int lo = 0; lo < k; lo += 16) {
+        const int g = std::min(16, k - lo);
+        const int64_t K = g;
+        Buf L1(e, K * P), R1(e, K * P), Lr(e, K * n2), Rr(e, K * n2), Xx(e, K * n2), Rt(e, K * n2), A(e, K * m), B(e, K * m),
+            Cc(e, K * P), G(e, 2 * K * n);
+        dev::ipea_pack(g, l1 + lo, l2 + lo, (int)P, (int)S, (int)P, L1.p, Lr.p, Xx.p, Rt.p, nullptr, e.stream);
+        dev::ipea_pack(g, r1 + lo, r2 + lo, (int)P, (int)S, (int)P, R1.p, Rr.p, Xx.p, Rt.p, nullptr, e.stream);
+        const TView Am = mv(A.p, {K, m}), Bm = mv(B.p, {K, m}), Cm = mv(Cc.p, {K, P});
+        if (ip) {
+            e.contract(1.0, mv(Rr.p, {K, o, o, v}), "zijb", LAM2, "abij", 0.0, Am, "za");
+            e.contract(1.0, mv(Lr.p, {K, o, o, v}), "zijb", T4, "abij", 0.0, Bm, "za");
+            e.contract(1.0, mv(Rt.p, {K, o, o, v}), "zjia", LAM1, "ai", 0.0, Cm, "zj");
+        } else {
+            e.contract(1.0, mv(Rr.p, {K, v, v, o}), "zabj", LAM2, "abij", 0.0, Am, "zi");
+            e.contract(1.0, mv(Lr.p, {K, v, v, o}), "zabj", T4, "abkj", 0.0, Bm, "zk");
+            e.contract(1.0, mv(Rt.p, {K, v, v, o}), "zbai", LAM1, "ai", 0.0, Cm, "zb");
+        }
+        dev::DysonParts q;
+        q.t1 = t1; q.lam1 = lam1; q.Yoo = Yoo.p; q.Yvv = Yvv.p; q.L1 = L1.p; q.R1 = R1.p; q.A = A.p; q.B = B.p; q.C = Cc.p;
+        q.psiL = G.p; q.psiR = G.p + K * n;
+        dev::ipea_dyson_assemble(q, g, ip ? 0 : 1, e.no, e.nv, e.stream);
+        dev::memcpy_d2h(psiL_host + lo * n, q.psiL, sizeof(double) * K * n, e.stream);
+        dev::memcpy_d2h(psiR_host + lo * n, q.psiR, sizeof(double) * K * n, e.stream);
+        dev::stream_sync(e.stream);
+    }
 }
 
 }  // namespace pymes

@@ -125,6 +125,12 @@ class IpEaSigma {
     int64_t n2() const { return kind == IP ? static_cast<int64_t>(no) * no * nv : static_cast<int64_t>(nv) * nv * no; }
     // sigma for k trial vectors (device arrays): s1[z] [n1], s2[z] [n2] written
     void apply(int k, const double* const* r1, const double* const* r2, double* const* s1, double* const* s2);
+    // The adjoint build: o = H^T l for the sigma H of apply() under the plain inner product over the compact vectors,
+    // k stacked vectors per call under the same stack_limit().  ipea_pack of the left vector IS the adjoint of the assembly (R, Rx,
+    // Rn, U1 of l are the derivatives with respect to D, E, L, S1); every product of apply_ip / apply_ea then runs once with its
+    // trial-vector operand and its output exchanged, from the same hoisted operands and the same blocks read in place; ipea_unpack
+    // (the adjoint of the packing) adds the four partial results.  apply() is not affected: nothing it reads is written.
+    void apply_left(int k, const double* const* l1, const double* const* l2, double* const* o1, double* const* o2);
     // d1 [n1] = -L_ii (IP) / L_aa (EA); d2 [n2] = L_bb - L_ii - L_jj (IP) / L_aa + L_bb - L_jj (EA): the dressed one-body part
     void diagonals(double* d1, double* d2);
     // For n roots (flat vectors of `len` doubles: [r1 (n1) | zero pad | r2 (n2)], the doubles part at `off2`; d the flat
@@ -133,6 +139,8 @@ class IpEaSigma {
     void correction(int n, const double* const* s, const double* const* r, const double* w_host, const double* d, double shift,
                     double* const* q, int64_t off2, int64_t len, double* norms_host);
     Engine& engine() { return e; }
+    Kind which() const { return kind; }
+    const double* amplitudes() const { return T; }
     void trim() { e.scratch_trim(); }
 
   private:
@@ -148,6 +156,8 @@ class IpEaSigma {
     void hoist(const double* f_host);
     void apply_ip(int k, const double* const* r1, const double* const* r2, double* const* s1, double* const* s2);
     void apply_ea(int k, const double* const* r1, const double* const* r2, double* const* s1, double* const* s2);
+    void left_ip(int k, const double* const* l1, const double* const* l2, double* const* o1, double* const* o2);
+    void left_ea(int k, const double* const* l1, const double* const* l2, double* const* o1, double* const* o2);
     int stack_limit() const;
     // hoisted: L_oo [o,o], L_vv [v,v], f_ov [o,v] and its transpose; the (ov) x (ov) pair matrices PA = 2 M1 + M2,
     // PB = M_C - M1, MDU = M_D - U (names of EomSigma), pair index (a,i) for EA and (i,a) for IP; IP: W_klij, TA [(c | l),i,j,b],
@@ -155,5 +165,13 @@ class IpEaSigma {
     double *Loo = nullptr, *Lvv = nullptr, *fov = nullptr, *fovT = nullptr, *PA = nullptr, *PB = nullptr, *MDU = nullptr,
            *B2 = nullptr, *TA = nullptr, *BB = nullptr, *TT = nullptr, *Td = nullptr, *Tx = nullptr;
 };
+
+// The Dyson amplitudes of k IP / EA roots (definitions and written-out formulas in include/pymes_amd.h,
+// pymes_ipea_dyson): psiL_host, psiR_host [k,n] (occupied orbitals first) from t1, lam1 [v,o], t2, lam2 [v,v,o,o] and the left /
+// right vectors (l1[z], l2[z]), (r1[z], r2[z]) on the device (compact: IP [o], [o,o,v]; EA [v], [v,v,o]).  Linear in every vector:
+// normalisation is the caller's.  Reads no integral block.
+void ipea_dyson(Engine& e, IpEaSigma::Kind kind, const double* t1, const double* t2, const double* lam1, const double* lam2, int k,
+                const double* const* l1, const double* const* l2, const double* const* r1, const double* const* r2,
+                double* psiL_host, double* psiR_host);
 
 }  // namespace pymes

@@ -6061,6 +6061,93 @@ __global__ void __launch_bounds__(256) ipea_correction_final_kernel(const double
     }
 }
 
+// The adjoint of the operand packing: o2_z[x,y,w] = dR[z,x,y,w] + dRx[z,y,x,w] + 2 dRt[z,x,y,w] - dRt[z,y,x,w] + dRn[x,y,z,w]
+// (dRn may be null), o1_z = dU1[z].  Same tiling as the assembly: block (bx, y, z) owns the plane y of vector z and 8 x by 32 w;
+// the direct rows [z,x,y,:] and the partner rows [z,y,x,:] are both read along w and the output is written along w, so nothing
+// is transposed through LDS and no element is written twice.  out.a = o1_z, out.b = o2_z.
+__global__ void __launch_bounds__(256) ipea_unpack_kernel(IpeaOut out, int P, int S, int n1, int k, const double* __restrict__ dU1,
+                                                          const double* __restrict__ dR, const double* __restrict__ dRx,
+                                                          const double* __restrict__ dRt, const double* __restrict__ dRn) {
+    const int z = blockIdx.z, y = blockIdx.y;
+    const int nwt = (S + 31) / 32;
+    const int xt = blockIdx.x / nwt, wt = blockIdx.x - xt * nwt;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int x = xt * 8 + ty, w = wt * 32 + tx;
+    const long PS = (long)P * S, n2 = PS * P;
+    if (x < P && w < S) {
+        const long o = (long)x * PS + (long)y * S + w, p = (long)z * n2 + (long)y * PS + (long)x * S + w;
+        double s = dR[(long)z * n2 + o] + dRx[p] + 2.0 * dRt[(long)z * n2 + o] - dRt[p];
+        if (dRn) s += dRn[((long)x * P + y) * ((long)k * S) + (long)z * S + w];
+        out.b[z][o] = s;
+    }
+    if (blockIdx.x == 0 && y == 0) {
+        double* __restrict__ o1 = out.a[z];
+        for (int p = threadIdx.x; p < n1; p += 256) o1[p] = dU1[(long)z * n1 + p];
+    }
+}
+
+// Dyson amplitudes of k IP / EA roots (device_api.h, ipea_dyson_assemble): block z owns root z.  Stage 1 fills the
+// amplitudes over the orbitals of the OTHER kind than the singles (IP: virtuals, EA: occupied) and keeps the right one in LDS;
+// stage 2 reads it back for the T1 back-transformation of the singles' own orbitals.  Every element is one thread's sum in a
+// fixed order.
+struct DysonK {
+    dev::DysonParts q;
+    int no, nv, kind;
+};
+__global__ void __launch_bounds__(256) ipea_dyson_kernel(const DysonK k) {
+    extern __shared__ double S[];             // the stage-1 right amplitudes [nv] (IP) / [no] (EA)
+    const int no = k.no, nv = k.nv, n = no + nv, z = blockIdx.x, t = threadIdx.x;
+    const double* __restrict__ t1 = k.q.t1;
+    const double* __restrict__ lam1 = k.q.lam1;
+    double* __restrict__ pl = k.q.psiL + (long)z * n;
+    double* __restrict__ pr = k.q.psiR + (long)z * n;
+    if (k.kind == 0) {
+        const double* __restrict__ l1 = k.q.L1 + (long)z * no;
+        const double* __restrict__ r1 = k.q.R1 + (long)z * no;
+        for (int a = t; a < nv; a += 256) {
+            double sl = k.q.B[(long)z * nv + a], sr = 0.0;
+            for (int i = 0; i < no; ++i) {
+                sl += l1[i] * t1[(long)a * no + i];
+                sr += lam1[(long)a * no + i] * r1[i];
+            }
+            sr = 0.5 * sr + k.q.A[(long)z * nv + a];
+            S[a] = sr;
+            pl[no + a] = sl;
+            pr[no + a] = sr;
+        }
+        __syncthreads();
+        for (int j = t; j < no; j += 256) {
+            double sr = r1[j] + 0.5 * k.q.C[(long)z * no + j];
+            for (int i = 0; i < no; ++i) sr -= k.q.Yoo[(long)j * no + i] * r1[i];
+            for (int a = 0; a < nv; ++a) sr -= t1[(long)a * no + j] * S[a];
+            pl[j] = l1[j];
+            pr[j] = sr;
+        }
+        return;
+    }
+    const double* __restrict__ l1 = k.q.L1 + (long)z * nv;
+    const double* __restrict__ r1 = k.q.R1 + (long)z * nv;
+    for (int i = t; i < no; i += 256) {
+        double sl = -k.q.B[(long)z * no + i], sr = 0.0;
+        for (int a = 0; a < nv; ++a) {
+            sl -= t1[(long)a * no + i] * l1[a];
+            sr += r1[a] * lam1[(long)a * no + i];
+        }
+        sr = -0.5 * sr - k.q.A[(long)z * no + i];
+        S[i] = sr;
+        pl[i] = sl;
+        pr[i] = sr;
+    }
+    __syncthreads();
+    for (int b = t; b < nv; b += 256) {
+        double sr = r1[b] + 0.5 * k.q.C[(long)z * nv + b];
+        for (int a = 0; a < nv; ++a) sr -= r1[a] * k.q.Yvv[(long)a * nv + b];
+        for (int i = 0; i < no; ++i) sr += S[i] * t1[(long)b * no + i];
+        pl[no + b] = l1[b];
+        pr[no + b] = sr;
+    }
+}
+
 void ipea_check(const char* who, int k, int P, int S) {
     if (k < 1 || k > kIpeaMax) throw std::runtime_error(std::string(who) + ": 1 <= k <= 16 vectors per call");
     if (P < 1 || S < 1 || P > 65535) throw std::runtime_error(std::string(who) + ": bad shape");
@@ -6098,6 +6185,31 @@ void ipea_assemble(int k, const double* D, const double* E, const double* L, con
     const unsigned nx = (unsigned)(((P + 7) / 8) * ((S + 31) / 32));
     launch_kernel(ipea_assemble_kernel, dim3(nx, (unsigned)P, (unsigned)k), dim3(256), 0, (hipStream_t)s, out, P, S, n1, k, D, E, L,
                   S1);
+}
+
+void ipea_unpack(int k, const double* dU1, const double* dR, const double* dRx, const double* dRt, const double* dRn, int P, int S,
+                 int n1, double* const* o1, double* const* o2, stream_t s) {
+    ipea_check("ipea_unpack", k, P, S);
+    if (!dU1 || !dR || !dRx || !dRt || !o1 || !o2) throw std::runtime_error("ipea_unpack: null operand");
+    IpeaOut out{};
+    for (int z = 0; z < k; ++z) {
+        if (!o1[z] || !o2[z]) throw std::runtime_error("ipea_unpack: null output");
+        out.a[z] = o1[z];
+        out.b[z] = o2[z];
+    }
+    const unsigned nx = (unsigned)(((P + 7) / 8) * ((S + 31) / 32));
+    launch_kernel(ipea_unpack_kernel, dim3(nx, (unsigned)P, (unsigned)k), dim3(256), 0, (hipStream_t)s, out, P, S, n1, k, dU1, dR,
+                  dRx, dRt, dRn);
+}
+
+void ipea_dyson_assemble(const DysonParts& q, int k, int kind, int no, int nv, stream_t s) {
+    if (no < 1 || nv < 1 || k < 1 || (kind != 0 && kind != 1)) throw std::runtime_error("ipea_dyson_assemble: bad shape");
+    const size_t lds = sizeof(double) * (size_t)(kind ? no : nv);
+    if (lds > 64 * 1024) throw std::runtime_error("ipea_dyson_assemble: too many orbitals for the LDS row");
+    if (!q.t1 || !q.lam1 || !q.Yoo || !q.Yvv || !q.L1 || !q.R1 || !q.A || !q.B || !q.C || !q.psiL || !q.psiR)
+        throw std::runtime_error("ipea_dyson_assemble: null operand");
+    const DysonK kk{q, no, nv, kind};
+    launch_kernel(ipea_dyson_kernel, dim3((unsigned)k), dim3(256), lds, (hipStream_t)s, kk);
 }
 
 void ipea_diagonals(const double* Loo, const double* Lvv, int kind, int no, int nv, double* d1, double* d2, stream_t s) {

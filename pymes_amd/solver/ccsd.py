@@ -497,6 +497,15 @@ class CCSD(ccd.CCD):
             if self.shard_integrals:
                 raise ValueError("ee_roots with shard_integrals=True: the left sigma reads the whole V_abcd, which an "
                                  "integral-sharded context does not hold")
+        if kwargs.get("dyson"):            # likewise
+            if not (kwargs.get("ip_roots") or kwargs.get("ea_roots")):
+                raise ValueError("dyson=True needs ip_roots and / or ea_roots: the amplitudes are those of the IP / EA roots")
+            if self.is_dcd:
+                raise ValueError("dyson=True: the IP / EA operators, their left vectors and the Lambda equations are those of "
+                                 "the CCSD similarity transform, not defined for DCSD")
+            if self.shard_integrals:
+                raise ValueError("dyson=True with shard_integrals=True: the Lambda equations read the whole V_abcd, which an "
+                                 "integral-sharded context does not hold")
         if frozen_core or fno_occ_threshold is not None or fno_nv is not None:
             return self._solve_fno(t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv,
                                    **kwargs)
@@ -525,6 +534,11 @@ class CCSD(ccd.CCD):
         # frozen_core / fno_* those of the correlated space; with density=True Lambda is solved once (ee_r_epsilon=x: the
         # relative residual norm at which both Davidson runs stop, default 1e-8)
         ee_roots = int(kwargs.get("ee_roots", 0) or 0)
+        # dyson=True (opt-in, with ip_roots / ea_roots): the left vectors of those roots, their Dyson amplitudes "ip dyson left",
+        # "ip dyson right" [k,n] and "ip pole strengths" [k] (and the "ea" counterparts; pymes_amd/solver/eom_dyson.py); with
+        # frozen_core / fno_* those of the correlated space; with density=True Lambda is solved once (dyson_r_epsilon=x: the
+        # relative residual norm at which the Davidson runs stop, default 1e-8)
+        dyson = bool(kwargs.get("dyson", False))
         ints, own = self._integrals(t_fock_pq, t_V_pqrs)
         ctx = ints.ctx
         st = None
@@ -536,6 +550,11 @@ class CCSD(ccd.CCD):
             if ee_roots:
                 from pymes_amd.solver import eom_transitions
                 eom_transitions.check_context(ctx, self.no)
+            if dyson:
+                from pymes_amd.solver import eom_dyson
+                for cls, n_roots in ((eom_dyson.IP_EOM_CCSD_Dyson, ip_roots), (eom_dyson.EA_EOM_CCSD_Dyson, ea_roots)):
+                    if n_roots:
+                        cls(self.no, n_roots=n_roots, device=self.device).check_context(ctx, False)
             print_logging_info(algo_name)
             print_logging_info("Using dcsd: ", self.is_dcd, level=1)
             print_logging_info("Solving doubles amplitude equation", level=1)
@@ -586,6 +605,7 @@ class CCSD(ccd.CCD):
                                                kwargs.get("ip_ea_r_epsilon"))
             lam = self._lambda_density(t_fock_pq, ints, st, kwargs.get("lambda_r_epsilon")) if density else None
             ee = self._ee_transitions(t_fock_pq, ints, st, ee_roots, kwargs.get("ee_r_epsilon"), lam) if ee_roots else None
+            dy = self._dyson(t_fock_pq, ints, st, ip_roots, ea_roots, kwargs.get("dyson_r_epsilon"), lam) if dyson else None
             if kwargs.get("device_amplitudes"):
                 # device-resident hand-over to the callers of the solution (EOM-CCSD / FEAST: get_T1_dressed_V on the same
                 # DeviceIntegrals, EOM_CCSD.solve on the result): "t1" / "t2" are DeviceArrays of the integrals' context —
@@ -617,6 +637,8 @@ class CCSD(ccd.CCD):
                 res.update(lam)
             if ee is not None:
                 res.update(ee)
+            if dy is not None:
+                res.update(dy)
             return res
         finally:
             collector.__exit__()
@@ -683,6 +705,29 @@ class CCSD(ccd.CCD):
         self.ee_solver = solver                          # (vectors, r0, biorthogonality, strengths() of the last solve)
         return {"ee e": out["e"], "ee tdm left": out["tdm left"], "ee tdm right": out["tdm right"],
                 "ee residuals": {"right": out["right residual"], "left": out["left residual"]}}
+
+    def _dyson(self, t_fock_pq, ints, st, ip_roots, ea_roots, r_epsilon=None, lam=None):
+        """The left vectors, Dyson amplitudes and pole strengths of the lowest IP / EA roots of the converged amplitudes on the
+        integrals' context (device hand-over as ``_lambda_density``; ``lam``: its result; Lambda is solved at most once)."""
+        from pymes_amd.solver.eom_dyson import EA_EOM_CCSD_Dyson, IP_EOM_CCSD_Dyson
+        f = t_fock_pq.get() if isinstance(t_fock_pq, DeviceArray) else np.asarray(t_fock_pq, dtype=np.float64)
+        t1, t2 = st["t1"], st["t2"]
+        fd = self.get_T1_dressed_fock(f, t1, ints)
+        lam = None if lam is None else (lam["lambda1"], lam["lambda2"])
+        res = {}
+        for cls, n_roots, tag in ((IP_EOM_CCSD_Dyson, ip_roots, "ip"), (EA_EOM_CCSD_Dyson, ea_roots, "ea")):
+            if not n_roots:
+                continue
+            solver = cls(self.no, n_roots=n_roots, device=self.device)
+            if r_epsilon is not None:
+                solver.r_epsilon = float(r_epsilon)
+            dressed = self.get_T1_dressed_V(t1, ints, solver.blocks(lam is None))
+            out = solver.solve(fd, dressed, t2, t1, lam=lam, eps=(st["eps_i"], st["eps_a"]), level_shift=st["level_shift"])
+            lam = (out["lambda1"], out["lambda2"])
+            setattr(self, tag + "_dyson_solver", solver)         # (vectors, residuals, residues(), spectral_function() of the last solve)
+            res.update({tag + " dyson left": out["dyson left"], tag + " dyson right": out["dyson right"],
+                        tag + " pole strengths": out["pole strengths"]})
+        return res
 
     def _solve_fno(self, t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv, **kwargs):
         from pymes_amd.solver import fno

@@ -59,6 +59,26 @@ class IPEASigma(subspace.LibraryHandle):
                    _lib.ptr_array([x.ptr for x in s1]), _lib.ptr_array([x.ptr for x in s2]))
         return list(zip(s1, s2))
 
+    def apply_left_many(self, l1s, l2s, out1=None, out2=None):
+        """[((H^T l_z)_1, (H^T l_z)_2)] for the left vectors (l1s[z], l2s[z]), device arrays; one library call
+        (``pymes_ipea_sigma_apply_left``: the products of ``apply_many`` once each, trial-vector operand and output exchanged)."""
+        h, c, k = self._handle(), self.ctx, len(l1s)
+        o1 = [out1[z] if out1 is not None else c.empty(self.shape1) for z in range(k)]
+        o2 = [out2[z] if out2 is not None else c.empty(self.shape2) for z in range(k)]
+        c.lib.call("pymes_ipea_sigma_apply_left", h, k, _lib.ptr_array([u.ptr for u in l1s]), _lib.ptr_array([u.ptr for u in l2s]),
+                   _lib.ptr_array([x.ptr for x in o1]), _lib.ptr_array([x.ptr for x in o2]))
+        return list(zip(o1, o2))
+
+    def dyson(self, t1, lam1, lam2, l1s, l2s, r1s, r2s):
+        """(psiL [k,n], psiR [k,n]) as host arrays (``pymes_ipea_dyson``); every input a device array of the handle's context."""
+        k, n = len(l1s), self.ctx.n
+        pl, pr = np.zeros((k, n)), np.zeros((k, n))
+        self.ctx.lib.call("pymes_ipea_dyson", self._handle(), C.c_void_p(t1.ptr), C.c_void_p(lam1.ptr), C.c_void_p(lam2.ptr), k,
+                          _lib.ptr_array([x.ptr for x in l1s]), _lib.ptr_array([x.ptr for x in l2s]),
+                          _lib.ptr_array([x.ptr for x in r1s]), _lib.ptr_array([x.ptr for x in r2s]), _lib.host_ptr(pl),
+                          _lib.host_ptr(pr))
+        return pl, pr
+
     def diagonals(self):
         """The flat diagonal [d1 | 0 | d2] (device)."""
         h = self._handle()
@@ -112,6 +132,21 @@ class _IPEA_EOM_CCSD:
         try:
             out = sig.apply_many([ctx.array(np.asarray(x, dtype=np.float64).reshape(sig.shape1)) for x in r1s],
                                  [ctx.array(np.asarray(x, dtype=np.float64).reshape(sig.shape2)) for x in r2s])
+            out = [(a.get(), b.get()) for a, b in out]
+            return out if many else out[0]
+        finally:
+            sig.close()
+            if own:
+                ctx.close()
+
+    def apply_left(self, f_dressed, V_dressed, t2, l1, l2):
+        """One adjoint build for host arrays: (H^T l)_1, (H^T l)_2 of (l1, l2), or lists of them for lists (stacked build)."""
+        many = isinstance(l1, (list, tuple))
+        l1s, l2s = (list(l1), list(l2)) if many else ([l1], [l2])
+        ctx, sig, own = self._sigma(f_dressed, V_dressed, t2)
+        try:
+            out = sig.apply_left_many([ctx.array(np.asarray(x, dtype=np.float64).reshape(sig.shape1)) for x in l1s],
+                                      [ctx.array(np.asarray(x, dtype=np.float64).reshape(sig.shape2)) for x in l2s])
             out = [(a.get(), b.get()) for a, b in out]
             return out if many else out[0]
         finally:

@@ -551,6 +551,35 @@ int pymes_diis_step(pymes_ctx* ctx, double* state_dev, int npairs, const double*
 int pymes_diis_solve(double* state_host, const double* overlaps_host, int ntypes, int m, int was_full);
 int pymes_lincomb_dev(pymes_ctx* ctx, double* out_dev, int nx, const double* const* x_dev, const double* coeff_dev,
                       int64_t n);
+/* ---- The amplitude tail of the single-rank loop on EXCHANGE-SYMMETRIC amplitudes.  In that loop every [v,v,o,o] array of
+ * the update, the mixer and the energy pass has X_abij == X_baji (T2, dT2, each stored DIIS vector, V_ijab): the calls below
+ * are those above with the caller's DECLARATION of that symmetry — never inferred from a shape.  Each pair of tiles (a,b),
+ * (b,a) is then read once: the reductions sum the tiles a >= b and count the off-diagonal ones twice; the element-wise
+ * steps compute tile (a,b) exactly as the plain call does and store it as (a,b) and, transposed, as (b,a), so their outputs
+ * are exchange-symmetric bit for bit (the plain call evaluates tile (b,a) on its own: the two agree to the rounding of the
+ * denominator eo_i + eo_j - ev_a - ev_b, whose value can depend on the order of a and b in the last bit).  Storage, shapes
+ * and results otherwise as in the plain calls.  The forms run when pymes_sym_tail answers 1 — the o x o tile fits the LDS
+ * (pymes_pair_fused_ok), the build has them, the environment does not say PYMES_SYM_TAIL=0 — and the call is too large to be
+ * a task of a phase launch (PYMES_PHASE_MAX_US; small problems keep the plain forms whether phases are on or off, so that the
+ * bits of a solve do not depend on the phase switches); otherwise they ARE the plain calls.  Not for EOM, Lambda or (T) vectors and not for the pair-compact arrays of the sharded loop.
+ * pymes_dots_sym: sym[p] != 0 marks the pairs of symmetric [v,v,o,o] operands (n[p] = v*v*o*o), the others as pymes_dots_var.
+ * pymes_diis_mix_sym: sym_types[t] != 0 marks the amplitude types whose vectors are such arrays.
+ * pymes_pair_layouts_sym: pymes_pair_layouts (2 X_abij - X_baij with X_baij taken from the tile of X_ab).
+ * Flag PYMES_SYM_TAIL of pymes_ccsd_residuals and pymes_doubles_residual (with PYMES_SYM_RINGS): the same declaration for
+ * t2 — the pair layouts inside are formed that way; pymes_ccsd_iterate declares all of it itself. */
+#define PYMES_SYM_TAIL (1u << 22)
+int pymes_sym_tail(pymes_ctx* ctx, int* yes);
+int pymes_cc_update_to_sym(pymes_ctx* ctx, double* t_out_dev, double* dt_dev, const double* t_in_dev, const double* r_dev,
+                           double level_shift, double delta);                       /* rank 4; t_out may be t_in */
+int pymes_dots_sym(pymes_ctx* ctx, int npairs, const double* const* x_dev, const double* const* y_dev, const int64_t* n,
+                   const int* sym, double* out_host);
+int pymes_lincomb_sym(pymes_ctx* ctx, double* out_dev, int nx, const double* const* x_dev, const double* c_host, int64_t n);
+int pymes_diis_mix_sym(pymes_ctx* ctx, double* state_host, int ntypes, int m, int was_full, const double* const* err_hist_dev,
+                       const double* const* err_new_dev, const int64_t* sizes, const double* const* amp_hist_dev,
+                       double* const* out_dev, const int* sym_types);
+int pymes_energy_norms_start_sym(pymes_ctx* ctx, const double* f_dev, const double* t1_dev, const double* t2_dev,
+                                 const double* dt2_dev, int* slot);
+int pymes_pair_layouts_sym(pymes_ctx* ctx, const double* x_dev, double* Xd_dev, double* Xx_dev, double* Xt_dev);
 /* (yr + i yi)[e] = (mr + i mi)[e] (xr + i xi)[e], e < n: a complex diagonal applied to a complex vector held as two real
  * arrays (y may alias x) — the preconditioner 1 / (z - diag + 0.01) of the FEAST linear solves, feast_eom_ccsd.py:342-343. */
 int pymes_cmul(pymes_ctx* ctx, const double* mr_dev, const double* mi_dev, const double* xr_dev, const double* xi_dev,

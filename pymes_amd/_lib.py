@@ -190,6 +190,15 @@ SIGNATURES = {
     "pymes_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_pp, c_pp, C.c_int64, c_double_p]),
     "pymes_lincomb_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_pp, C.c_void_p, C.c_void_p, c_pp, C.c_int64]),
     "pymes_lincomb_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_pp, C.c_void_p, C.c_int64]),
+    "pymes_sym_tail": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "pymes_cc_update_to_sym": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
+    "pymes_dots_sym": (C.c_int, [C.c_void_p, C.c_int, c_pp, c_pp, c_i64_p, C.POINTER(C.c_int), c_double_p]),
+    "pymes_lincomb_sym": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_pp, c_double_p, C.c_int64]),
+    "pymes_diis_mix_sym": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_pp, c_pp, c_i64_p, c_pp, c_pp,
+                                     C.POINTER(C.c_int)]),
+    "pymes_energy_norms_start_sym": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(C.c_int)]),
+    "pymes_pair_layouts_sym": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pymes_stats": (C.c_int, [C.c_void_p, C.c_int, c_i64_p, c_double_p, c_i64_p, c_double_p]),
     "pymes_prof_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "pymes_prof_reset": (C.c_int, [C.c_void_p]),
@@ -200,6 +209,7 @@ PYMES_DCD, PYMES_USE_DRESSED, PYMES_SKIP_LADDER, PYMES_SYM_LADDER, PYMES_SYM_RIN
 PYMES_OWNER_TILES = 1 << 21
 PYMES_REUSE_LAYOUTS = 32
 PYMES_T1_ZERO = 1 << 20
+PYMES_SYM_TAIL = 1 << 22
 PYMES_SLAB_RINGS_ONLY, PYMES_SLAB_LADDERS_ONLY = 64, 128
 PYMES_DRESS_ABIJ_REDUCED = 1 << 16
 

@@ -399,8 +399,10 @@ int pymes_ccsd_residuals(pymes_ctx* ctx, const double* f, const double* t1, cons
                          double* r2) {
     return guarded([&] {
         need(f, "f"); need(t1, "t1"); need(t2, "t2"); need(r1, "r1"); need(r2, "r2");
-        if (flags & ~(PYMES_DCD | PYMES_T1_ZERO)) throw pymes::Error("ccsd_residuals: flags are PYMES_DCD | PYMES_T1_ZERO");
-        E(ctx).ccsd_residuals(f, t1, t2, (flags & PYMES_DCD) | ((flags & PYMES_T1_ZERO) ? Engine::kT1Zero : 0u), r1, r2);
+        if (flags & ~(PYMES_DCD | PYMES_T1_ZERO | PYMES_SYM_TAIL))
+            throw pymes::Error("ccsd_residuals: flags are PYMES_DCD | PYMES_T1_ZERO | PYMES_SYM_TAIL");
+        E(ctx).ccsd_residuals(f, t1, t2, (flags & PYMES_DCD) | ((flags & PYMES_T1_ZERO) ? Engine::kT1Zero : 0u) |
+                                             ((flags & PYMES_SYM_TAIL) ? Engine::kSymTail : 0u), r1, r2);
     });
 }
 int pymes_ccsd_iterate(pymes_ctx* ctx, const double* f, double* t1, double* t2, uint32_t flags, double level_shift, double delta,
@@ -656,6 +658,36 @@ int pymes_energy_norms_start(pymes_ctx* ctx, const double* f, const double* t1, 
         *slot = E(ctx).energy_norms_start(f, t1, t2, dt2);
     });
 }
+int pymes_sym_tail(pymes_ctx* ctx, int* yes) {
+    return guarded([&] {
+        need(yes, "yes");
+        *yes = Eq(ctx).sym_tail() ? 1 : 0;
+    });
+}
+int pymes_cc_update_to_sym(pymes_ctx* ctx, double* t_out, double* dt, const double* t_in, const double* r, double shift,
+                           double delta) {
+    return guarded([&] {
+        need(t_out, "t_out"); need(dt, "dt"); need(t_in, "t_in"); need(r, "r");
+        E(ctx).cc_update_to(t_out, dt, t_in, r, shift, delta, 4, true);
+    });
+}
+int pymes_energy_norms_start_sym(pymes_ctx* ctx, const double* f, const double* t1, const double* t2, const double* dt2,
+                                 int* slot) {
+    return guarded([&] {
+        need(t2, "t2"); need(slot, "slot");
+        if ((f == nullptr) != (t1 == nullptr)) throw pymes::Error("f and t1 must be given together");
+        *slot = E(ctx).energy_norms_start(f, t1, t2, dt2, true);
+    });
+}
+int pymes_pair_layouts_sym(pymes_ctx* ctx, const double* x, double* Xd, double* Xx, double* Xt) {
+    return guarded([&] {
+        need(x, "x"); need(Xx, "Xx"); need(Xt, "Xt");
+        Engine& e = E(ctx);
+        if (!dev::fused_pair_kernels_ok(e.no)) throw pymes::Error("pair_layouts: nocc too large for the LDS tile");
+        if (e.sym_tail()) dev::t2_layouts_sym(x, Xd, Xx, Xt, e.no, e.nv, e.stream);
+        else dev::t2_layouts(x, Xd, Xx, Xt, e.no, e.nv, e.stream);
+    });
+}
 int pymes_energy_norms_wait(pymes_ctx* ctx, int slot, double* out) {
     return guarded([&] {
         need(out, "out");
@@ -857,6 +889,20 @@ int pymes_dots_var(pymes_ctx* ctx, int npairs, const double* const* x, const dou
         dev::dots(npairs, x, y, n, out, E(ctx).stream);
     });
 }
+int pymes_dots_sym(pymes_ctx* ctx, int npairs, const double* const* x, const double* const* y, const int64_t* n, const int* sym,
+                   double* out) {
+    return guarded([&] {
+        need(x, "x"); need(y, "y"); need(n, "n"); need(sym, "sym"); need(out, "out");
+        if (npairs < 0 || npairs > 16) throw pymes::Error("dots: 0..16 pairs");
+        E(ctx).dots(npairs, x, y, n, sym, out);
+    });
+}
+int pymes_lincomb_sym(pymes_ctx* ctx, double* out, int nx, const double* const* x, const double* c, int64_t n) {
+    return guarded([&] {
+        need(out, "out"); need(x, "x"); need(c, "c");
+        E(ctx).lincomb(out, nx, x, c, n, true);
+    });
+}
 int pymes_lincomb(pymes_ctx* ctx, double* out, int nx, const double* const* x, const double* c, int64_t n) {
     return guarded([&] {
         need(out, "out"); need(x, "x"); need(c, "c");
@@ -912,28 +958,44 @@ int pymes_diis_solve(double* state_host, const double* overlaps_host, int ntypes
         diis_small::step(state_host, overlaps_host, ntypes, m, was_full);
     });
 }
+// sym_types[t] != 0: the vectors of amplitude type t are exchange-symmetric [v,v,o,o] arrays (the caller's declaration)
+static void diis_mix_impl(pymes_ctx* ctx, double* state_host, int ntypes, int m, int was_full, const double* const* err_hist,
+                          const double* const* err_new, const int64_t* sizes, const double* const* amp_hist, double* const* out,
+                          const int* sym_types) {
+    need(state_host, "state"); need(err_hist, "err_hist"); need(err_new, "err_new"); need(sizes, "sizes");
+    need(amp_hist, "amp_hist"); need(out, "out");
+    if (ntypes < 1 || m < 1 || m > 8 || ntypes * m > 16) throw pymes::Error("diis_mix: need ntypes * m <= 16, m <= 8");
+    Engine& e = E(ctx);
+    const double* x[16];
+    const double* y[16];
+    int64_t n[16];
+    for (int t = 0; t < ntypes; ++t)
+        for (int i = 0; i < m; ++i) {
+            x[t * m + i] = err_hist[t * m + i];
+            y[t * m + i] = err_new[t];
+            n[t * m + i] = sizes[t];
+        }
+    int sym[16];
+    for (int t = 0; t < ntypes; ++t)
+        for (int i = 0; i < m; ++i) sym[t * m + i] = sym_types ? sym_types[t] : 0;
+    double ov[16];
+    e.dots(ntypes * m, x, y, n, sym, ov);                              // one launch pair, one synchronisation
+    diis_small::step(state_host, ov, ntypes, m, was_full);             // (m+1) x (m+1) algebra on this host thread
+    if (state_host[91] == 2.0)      // singular or non-finite subspace matrix: the reference's numpy.linalg raises here too
+        throw pymes::Error("DIIS: the subspace matrix is singular or not finite (numpy.linalg.LinAlgError in pymes/mixer/diis.py:85-95)");
+    for (int t = 0; t < ntypes; ++t)
+        e.lincomb(out[t], m, amp_hist + t * m, state_host + 82, sizes[t], sym_types && sym_types[t]);
+}
 int pymes_diis_mix(pymes_ctx* ctx, double* state_host, int ntypes, int m, int was_full, const double* const* err_hist,
                    const double* const* err_new, const int64_t* sizes, const double* const* amp_hist, double* const* out) {
+    return guarded([&] { diis_mix_impl(ctx, state_host, ntypes, m, was_full, err_hist, err_new, sizes, amp_hist, out, nullptr); });
+}
+int pymes_diis_mix_sym(pymes_ctx* ctx, double* state_host, int ntypes, int m, int was_full, const double* const* err_hist,
+                       const double* const* err_new, const int64_t* sizes, const double* const* amp_hist, double* const* out,
+                       const int* sym_types) {
     return guarded([&] {
-        need(state_host, "state"); need(err_hist, "err_hist"); need(err_new, "err_new"); need(sizes, "sizes");
-        need(amp_hist, "amp_hist"); need(out, "out");
-        if (ntypes < 1 || m < 1 || m > 8 || ntypes * m > 16) throw pymes::Error("diis_mix: need ntypes * m <= 16, m <= 8");
-        Engine& e = E(ctx);
-        const double* x[16];
-        const double* y[16];
-        int64_t n[16];
-        for (int t = 0; t < ntypes; ++t)
-            for (int i = 0; i < m; ++i) {
-                x[t * m + i] = err_hist[t * m + i];
-                y[t * m + i] = err_new[t];
-                n[t * m + i] = sizes[t];
-            }
-        double ov[16];
-        dev::dots(ntypes * m, x, y, n, ov, e.stream);                      // one launch pair, one synchronisation
-        diis_small::step(state_host, ov, ntypes, m, was_full);             // (m+1) x (m+1) algebra on this host thread
-        if (state_host[91] == 2.0)      // singular or non-finite subspace matrix: the reference's numpy.linalg raises here too
-            throw pymes::Error("DIIS: the subspace matrix is singular or not finite (numpy.linalg.LinAlgError in pymes/mixer/diis.py:85-95)");
-        for (int t = 0; t < ntypes; ++t) dev::lincomb(out[t], m, amp_hist + t * m, state_host + 82, sizes[t], e.stream);
+        need(sym_types, "sym_types");
+        diis_mix_impl(ctx, state_host, ntypes, m, was_full, err_hist, err_new, sizes, amp_hist, out, sym_types);
     });
 }
 int pymes_lincomb_dev(pymes_ctx* ctx, double* out, int nx, const double* const* x, const double* coeff_dev, int64_t n) {

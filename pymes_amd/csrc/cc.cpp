@@ -238,7 +238,13 @@ bool Engine::ring_fold_enabled() {
 }
 
 // The three pair layouts of T2 (Td, Tx, Tt_d) in the engine's persistent buffers
-void Engine::pair_layouts_of(const double* t2, bool want_td) {
+bool Engine::sym_tail() const {
+    if (const char* e = getenv("PYMES_SYM_TAIL"))
+        if (atoi(e) == 0) return false;
+    return dev::sym_tail_ok() && dev::fused_pair_kernels_ok(no);
+}
+
+void Engine::pair_layouts_of(const double* t2, bool want_td, bool sym) {
     const int64_t o = no, v = nv, ov = o * v;
     for (int i = want_td ? 0 : 1; i < 3; ++i)
         if (!lay_[i]) {
@@ -247,7 +253,8 @@ void Engine::pair_layouts_of(const double* t2, bool want_td) {
         }
     lay_t2_ = nullptr;
     if (dev::fused_pair_kernels_ok(no)) {
-        dev::t2_layouts(t2, want_td ? lay_[0] : nullptr, lay_[1], lay_[2], no, nv, stream);
+        if (sym && sym_tail()) dev::t2_layouts_sym(t2, want_td ? lay_[0] : nullptr, lay_[1], lay_[2], no, nv, stream);
+        else dev::t2_layouts(t2, want_td ? lay_[0] : nullptr, lay_[1], lay_[2], no, nv, stream);
         stats.permute_calls++;
         stats.permute_bytes += 8.0 * (want_td ? 5.0 : 4.0) * double(ov * ov);      // T twice, two or three layouts out
     } else {
@@ -310,7 +317,7 @@ void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, dou
     // no Td, and the finish does not form X_ac T (ring_fold_).  tests/test_ring_fold.py pins the identity.
     const bool traces = !P && nc == ov;      // the small V.T sums as partial traces of the builds (below; one rank only)
     const bool fold = traces && ring_fold_enabled();
-    pair_layouts_of(t2, !fold);
+    pair_layouts_of(t2, !fold, flags & kSymTail);
     TView Td = pairm(lay_[0]), Tx = pairm(lay_[1]), Ttd = pairm(lay_[2]);
     TView ETd = slice(pairm(ETd_p), 0, c0, c1), ETx = slice(pairm(ETx_p), 0, c0, c1);
     auto cols = [&](const TView& m) { return slice(m, 1, c0, c1); };
@@ -1702,9 +1709,9 @@ void Engine::ccsd_residuals(const double* f, const double* t1, const double* t2,
         res_fd_ = got[0]; res_ETd_ = got[1]; res_ETx_ = got[2]; res_L_ = got[3]; res_QK_ = got[4];
     }
     const unsigned dcd = flags & PYMES_DCD;
-    const unsigned sym = PYMES_SYM_LADDER | PYMES_SYM_RINGS;
+    const unsigned sym = PYMES_SYM_LADDER | PYMES_SYM_RINGS, tail = flags & kSymTail;
     if (flags & PYMES_T1_ZERO) {
-        residual_slab(f, t2, res_ETd_, res_ETx_, res_L_, 0, 1, dcd | sym);                                     // :171
+        residual_slab(f, t2, res_ETd_, res_ETx_, res_L_, 0, 1, dcd | sym | tail);                              // :171
         singles_residual_partial(f, t1, t2, r1, 0, 1, true);                                                   // :167
         residual_finish(f, t2, res_ETd_, res_ETx_, res_L_, r2, dcd | sym | PYMES_REUSE_LAYOUTS);
         return;
@@ -1713,7 +1720,7 @@ void Engine::ccsd_residuals(const double* f, const double* t1, const double* t2,
     // V_abcd is never dressed: its T1 dressing (:165, ccsd.py:414-419) is carried by tau = T2 + T1 T1 inside the ladders,
     // that of V_abij by Q_kb and two small products inside the finish; only V~_klij, V~_iajb, V~_iabj are formed
     dress_V(t1, (1u << pattern_of_name("klij")) | (1u << pattern_of_name("iajb")) | (1u << pattern_of_name("iabj")));
-    residual_slab(res_fd_, t2, res_ETd_, res_ETx_, res_L_, 0, 1, dcd | sym | PYMES_USE_DRESSED, t1, res_QK_);  // :171
+    residual_slab(res_fd_, t2, res_ETd_, res_ETx_, res_L_, 0, 1, dcd | sym | tail | PYMES_USE_DRESSED, t1, res_QK_);  // :171
     singles_residual_partial(res_fd_, t1, t2, r1, 0, 1, true);                                                 // :167
     residual_finish(res_fd_, t2, res_ETd_, res_ETx_, res_L_, r2, dcd | sym | PYMES_USE_DRESSED | PYMES_REUSE_LAYOUTS, t1, res_QK_);
 }
@@ -1733,10 +1740,11 @@ void Engine::ccsd_iterate(const double* f, double* t1, double* t2, unsigned flag
         }
         res_r1_ = r1;
     }
-    ccsd_residuals(f, t1, t2, flags, res_r1_, res_r2_);                       // ccsd.py:161-171
+    // (the symmetry-reduced residual is this step's precondition already: T2, R2, dT2 are exchange-symmetric)
+    ccsd_residuals(f, t1, t2, flags | kSymTail, res_r1_, res_r2_);            // ccsd.py:161-171
     cc_update_to(t1, dt1, t1, res_r1_, shift, delta, 2);                      // :176-179
-    cc_update_to(t2, dt2, t2, res_r2_, shift, delta, 4);
-    energy_norms(f, t1, t2, dt2, out);                                        // :189-197
+    cc_update_to(t2, dt2, t2, res_r2_, shift, delta, 4, true);
+    energy_norms(f, t1, t2, dt2, out, true);                                  // :189-197
 }
 
 // ---- one process per GPU with the host program's collectives (engine.h; include/pymes_amd.h, pymes_collectives) -----------------
@@ -2033,13 +2041,28 @@ void Engine::release_residual_buffers() {
 }
 
 void Engine::cc_update_to(double* t_out, double* dt, const double* t_in, const double* r, double shift, double delta,
-                          int rank) {
+                          int rank, bool sym) {
     if (rank != 2 && rank != 4) throw Error("cc_update: rank must be 2 (T1) or 4 (T2)");
     need_eps("cc_update");
-    dev::cc_update_to(t_out, dt, t_in, r, eps_o, eps_v, shift, delta, no, nv, rank, stream);
+    if (sym && rank == 4 && sym_tail()) dev::cc_update_to_sym(t_out, dt, t_in, r, eps_o, eps_v, shift, delta, no, nv, stream);
+    else dev::cc_update_to(t_out, dt, t_in, r, eps_o, eps_v, shift, delta, no, nv, rank, stream);
 }
 
-int Engine::energy_norms_start(const double* f, const double* t1, const double* t2, const double* dt2) {
+void Engine::dots(int npairs, const double* const* x, const double* const* y, const int64_t* n, const int* sym, double* out) {
+    bool any = false;
+    for (int i = 0; sym && i < npairs && i < 16; ++i) any = any || sym[i];
+    if (any && sym_tail()) dev::dots_sym(npairs, x, y, n, sym, no, nv, out, stream);
+    else dev::dots(npairs, x, y, n, out, stream);
+}
+
+void Engine::lincomb(double* out, int nx, const double* const* x, const double* c, int64_t n, bool sym) {
+    if (sym && n != (int64_t)nv * nv * no * no) throw Error("lincomb: a symmetric vector must be a [v,v,o,o] array");
+    if (sym && sym_tail()) dev::lincomb_sym(out, nx, x, c, no, nv, stream);
+    else dev::lincomb(out, nx, x, c, n, stream);
+}
+
+int Engine::energy_norms_start(const double* f, const double* t1, const double* t2, const double* dt2, bool sym) {
+    if (sym && sym_tail()) return dev::energy_norms_start_sym(f, t1, t2, get_static("Edir"), get_static("Eex"), dt2, no, nv, stream);
     return dev::energy_norms_start(f, t1, t2, get_static("Edir"), get_static("Eex"), dt2, no, nv, stream);
 }
 void Engine::energy_norms_wait(int slot, double out[6]) {
@@ -2053,7 +2076,8 @@ void Engine::energy_norms_wait(int slot, double out[6]) {
     out[5] = r[5];
 }
 
-void Engine::energy_norms(const double* f, const double* t1, const double* t2, const double* dt2, double out[6]) {
+void Engine::energy_norms(const double* f, const double* t1, const double* t2, const double* dt2, double out[6], bool sym) {
+    if (sym && sym_tail()) return energy_norms_wait(energy_norms_start(f, t1, t2, dt2, true), out);
     double r[6];
     dev::energy_norms(f, t1, t2, get_static("Edir"), get_static("Eex"), dt2, no, nv, r, stream);
     out[0] = 2.0 * r[0];      // ccsd.py:465

@@ -175,6 +175,24 @@ void cc_update_to(double* t_out, double* dt, const double* t_in, const double* r
                   double shift, double delta, int no, int nv, int rank, stream_t s);
 // out = sum_k c[k] * x_k   (k < nx <= 8)
 void lincomb(double* out, int nx, const double* const* x, const double* c, int64_t n, stream_t s);
+// ---- the amplitude tail on exchange-symmetric amplitudes: the caller DECLARES that every [nv,nv,no,no] array of the call
+// has X[a,b,i,j] == X[b,a,j,i] (never inferred from a shape); each pair of tiles is then read once, as (a, b <= a).  The
+// element-wise forms compute tile (a,b) as their full-read forms do and store it as (a,b) and, transposed, as (b,a): their
+// outputs are exchange-symmetric bit for bit.  The reductions count the off-diagonal tiles twice.  All need
+// fused_pair_kernels_ok(no); a call small enough to be a task of a phase (whether phases are on or not) runs the full-read
+// form, so that the bits of a solve do not depend on the phase switches.  sym_tail_ok(): the
+// backend has these forms (the host simulator does not: the callers then use the forms above).
+bool sym_tail_ok();
+void cc_update_to_sym(double* t_out, double* dt, const double* t_in, const double* r, const double* eo, const double* ev,
+                      double shift, double delta, int no, int nv, stream_t s);                     // rank 4
+void lincomb_sym(double* out, int nx, const double* const* x, const double* c, int no, int nv, stream_t s);
+// dots with sym[p] != 0 for the pairs of symmetric [nv,nv,no,no] operands (n[p] must be their size); the others as in dots
+void dots_sym(int npairs, const double* const* x, const double* const* y, const int64_t* n, const int* sym, int no, int nv,
+              double* out_host, stream_t s);
+int energy_norms_start_sym(const double* f, const double* t1, const double* t2, const double* Edir, const double* Eex,
+                           const double* dt2, int no, int nv, stream_t s);                          // t2, Edir, Eex, dt2 symmetric
+// t2_layouts with (ca, cb) = (2, -1) for a symmetric T: T_baij is taken from the staged tile of T_ab
+void t2_layouts_sym(const double* T, double* Td, double* Tx, double* Ttd, int no, int nv, stream_t s);
 // ---- tall-skinny subspace algebra of the Davidson / FEAST drivers (eom_ccsd.py:91-147, :512-541): every vector is read ONCE
 // per call, whatever the number of inner products / combinations it enters ------------------------------------------------
 // out_host[i * n + j] = <x_i, y_j> for i < m, j < n over vectors of `len` doubles (m, n <= 64); deterministic two-stage

@@ -835,4 +835,24 @@ __attribute__((weak)) void rdm1_assemble(const double*, const double*, const dou
 __attribute__((weak)) void tdm1_assemble(const Tdm1Parts&, int, int, int, stream_t) {
     throw std::runtime_error("tdm1_assemble: not available in this backend");
 }
+// ... and without the read-each-pair-once forms of the amplitude tail: the callers keep the full-read forms
+__attribute__((weak)) bool sym_tail_ok() { return false; }
+__attribute__((weak)) void cc_update_to_sym(double*, double*, const double*, const double*, const double*, const double*, double,
+                                            double, int, int, stream_t) {
+    throw std::runtime_error("cc_update_to_sym: not available in this backend");
+}
+__attribute__((weak)) void lincomb_sym(double*, int, const double* const*, const double*, int, int, stream_t) {
+    throw std::runtime_error("lincomb_sym: not available in this backend");
+}
+__attribute__((weak)) void dots_sym(int, const double* const*, const double* const*, const int64_t*, const int*, int, int, double*,
+                                    stream_t) {
+    throw std::runtime_error("dots_sym: not available in this backend");
+}
+__attribute__((weak)) int energy_norms_start_sym(const double*, const double*, const double*, const double*, const double*,
+                                                 const double*, int, int, stream_t) {
+    throw std::runtime_error("energy_norms_start_sym: not available in this backend");
+}
+__attribute__((weak)) void t2_layouts_sym(const double*, double*, double*, double*, int, int, stream_t) {
+    throw std::runtime_error("t2_layouts_sym: not available in this backend");
+}
 }  // namespace dev

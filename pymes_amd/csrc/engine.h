@@ -252,6 +252,13 @@ class Engine {
     // t1 == 0 exactly (the MP2 start, a momentum-conserving system): exp(-T1) H exp(T1) = H, residuals from the undressed f, V.
     // Only enqueues kernels on buffers the engine holds (replayable as a launch graph).
     static constexpr unsigned kT1Zero = 1u << 20;
+    // bit `kSymTail` (PYMES_SYM_TAIL; ccsd_residuals, doubles_residual with PYMES_SYM_RINGS): the caller runs the amplitude
+    // tail on exchange-symmetric arrays — the pair layouts of t2 take T_baij from the tile of T_ab (dev::t2_layouts_sym).
+    // sym_tail(): the forms of that tail which read each exchange pair once are available and wanted — the backend has them
+    // (dev::sym_tail_ok), the o x o tile fits the LDS, PYMES_SYM_TAIL is not 0.  The `sym` arguments below are the caller's
+    // declaration that every [v,v,o,o] array of the call has X_abij == X_baji; without sym_tail() they change nothing.
+    static constexpr unsigned kSymTail = 1u << 22;
+    bool sym_tail() const;
     void ccsd_residuals(const double* f, const double* t1, const double* t2, unsigned flags, double* r1, double* r2);
     // ... and one fixed-point pass without a mixer (ccsd.py:159-197 with is_diis = False): residuals, dT = R / (D + shift),
     // T += delta dT in place, then the energies and norms of the updated amplitudes: out = {one-body, direct, exchange,
@@ -261,15 +268,19 @@ class Engine {
                       double* dt2, double out[6]);
     void release_residual_buffers();
     void cc_update(double* t, double* dt, const double* r, double shift, double delta, int rank);  // ccsd.py:176-179
-    void cc_update_to(double* t_out, double* dt, const double* t_in, const double* r, double shift, double delta, int rank);
+    void cc_update_to(double* t_out, double* dt, const double* t_in, const double* r, double shift, double delta, int rank,
+                      bool sym = false);
+    // out[p] = <x_p, y_p> / out = sum_k c[k] x_k with the declaration above (sym[p]: per pair; lincomb: [v,v,o,o] arrays)
+    void dots(int npairs, const double* const* x, const double* const* y, const int64_t* n, const int* sym, double* out);
+    void lincomb(double* out, int nx, const double* const* x, const double* c, int64_t n, bool sym);
     void ccsd_energy(const double* f, const double* t1, const double* t2, double out[3]);     // ccsd.py:458-466
     void ccd_energy(const double* t2, double out[2]);                                         // ccd.py:256-262
     // energies (ccsd.py:458-466 / ccd.py:256-262 when f, t1 are null) and the squared norms of t2 and dt2
     // (ccsd.py:196-197) in one pass: out = {one-body, direct, exchange, |t2|^2, |dt2|^2, |t1|^2}
-    void energy_norms(const double* f, const double* t1, const double* t2, const double* dt2, double out[6]);
+    void energy_norms(const double* f, const double* t1, const double* t2, const double* dt2, double out[6], bool sym = false);
     // the same in two halves: enqueue (returns a read-back slot) / wait for that read-back only — the stream goes on with what
     // was enqueued in between (the next iteration's residual kernels)
-    int energy_norms_start(const double* f, const double* t1, const double* t2, const double* dt2);
+    int energy_norms_start(const double* f, const double* t1, const double* t2, const double* dt2, bool sym = false);
     void energy_norms_wait(int slot, double out[6]);
     void energy_norms_pairs(const double* f, const double* t1, const double* tc, const double* dtc, int rank, int world,
                             double out[6]);
@@ -346,7 +357,7 @@ class Engine {
     double* lay_[3] = {nullptr, nullptr, nullptr};
     const double* lay_t2_ = nullptr;
     // (Td only on request: its one reader, the X_ki product of residual_slab, is gone where the ring fold applies)
-    void pair_layouts_of(const double* t2, bool want_td);
+    void pair_layouts_of(const double* t2, bool want_td, bool sym = false);
     // Ring fold (cc.cpp, residual_slab): the t2 and the ETd buffer of the slab that already carries X_ac T_cbij - X_ki T_abkj
     // through the ring operands, so that a finish of THAT slab must not add X_ac T again (a finish handed the same t2 with
     // another ETd forms it as before).  A property of the slab's data: every residual_slab that does not skip the rings

@@ -2407,6 +2407,247 @@ __device__ __forceinline__ void residual_assemble_body(const AssembleK& k, const
 }
 __global__ void __launch_bounds__(256) residual_assemble_kernel(const AssembleK k) { residual_assemble_body(k, blockIdx.x); }
 
+// ---- the amplitude tail of the single-rank loop on exchange-symmetric [v,v,o,o] arrays, X[a,b,i,j] == X[b,a,j,i] (the
+// caller's declaration, device_api.h sym_tail_ok): every pair of tiles is READ once, as tile (a, b <= a).  The element-wise
+// kernels take one block per pair a >= b (the tiling of residual_assemble), compute the tile with the expressions of their
+// full-read forms and store it twice — as (a,b) and, through the o x (o + 1) LDS tile, transposed as (b,a) — so what they
+// write is exchange-symmetric bit for bit.  The reductions walk the tiles (a, b <= a), v contiguous runs of the array, and
+// count the off-diagonal ones twice (an exact doubling of their partial sum).  Launches only, and only for calls too
+// large to be a task of the phase union kernel (phase_small): a small call keeps the full-read form whether phases are
+// on or off, so that a solve gives the same bits with PYMES_PHASE=0, =serial and recorded.
+__global__ void __launch_bounds__(256) cc_update_sym_kernel(const CcUpdateK k) {
+    double* t = k.t;                          // may alias t_in: a block reads and writes tile (a,b), and writes (b,a), alone
+    double* __restrict__ dt = k.dt;
+    const double* t_in = k.t_in;
+    const double* __restrict__ r_ = k.r;
+    const double* __restrict__ eo = k.eo;
+    const double* __restrict__ ev = k.ev;
+    const double shift = k.shift, delta = k.delta;
+    const int no = k.no, nv = k.nv;
+    extern __shared__ double tile[];          // [no][no + 1]
+    int a, b;
+    unrank_pair(blockIdx.x, a, b);
+    const int p = no + 1, o2 = no * no;
+    const long ab = ((long)a * nv + b) * o2, ba = ((long)b * nv + a) * o2;
+    const double eva = ev[a], evb = ev[b];
+    for (int e = threadIdx.x; e < o2; e += blockDim.x) {
+        const int i = e / no, j = e - i * no;
+        const double d = eo[i] + eo[j] - eva - evb;
+        const double inv = 1.0 / (d + shift);
+        const double x = r_[ab + e] * inv;
+        dt[ab + e] = x;
+        tile[i * p + j] = x;
+    }
+    __syncthreads();
+    if (a != b)
+        for (int e = threadIdx.x; e < o2; e += blockDim.x) {
+            const int j = e / no, i = e - j * no;
+            dt[ba + e] = tile[i * p + j];
+        }
+    __syncthreads();
+    for (int e = threadIdx.x; e < o2; e += blockDim.x) {      // (a thread meets its own elements of the first loop again)
+        const int i = e / no, j = e - i * no;
+        const double x = tile[i * p + j];
+        const double y = t_in[ab + e] + delta * x;
+        t[ab + e] = y;
+        tile[i * p + j] = y;
+    }
+    __syncthreads();
+    if (a != b)
+        for (int e = threadIdx.x; e < o2; e += blockDim.x) {
+            const int j = e / no, i = e - j * no;
+            t[ba + e] = tile[i * p + j];
+        }
+}
+
+struct LinSymK {
+    double* out;
+    LinPtrs p;
+    int nx, no, nv;
+};
+__global__ void __launch_bounds__(256) lincomb_sym_kernel(const LinSymK k) {
+    double* out = k.out;                      // may be one of the inputs: tile (a,b) is read before it is written, (b,a) never
+    const int nx = k.nx, no = k.no, nv = k.nv;
+    extern __shared__ double tile[];          // [no][no + 1]
+    int a, b;
+    unrank_pair(blockIdx.x, a, b);
+    const int p = no + 1, o2 = no * no;
+    const long ab = ((long)a * nv + b) * o2, ba = ((long)b * nv + a) * o2;
+    for (int e = threadIdx.x; e < o2; e += blockDim.x) {
+        const int i = e / no, j = e - i * no;
+        double s = 0.0;
+        for (int q = 0; q < nx; ++q) s += k.p.x[q][ab + e] * k.p.c[q];
+        out[ab + e] = s;
+        tile[i * p + j] = s;
+    }
+    if (a == b) return;                       // (block-uniform)
+    __syncthreads();
+    for (int e = threadIdx.x; e < o2; e += blockDim.x) {
+        const int j = e / no, i = e - j * no;
+        out[ba + e] = tile[i * p + j];
+    }
+}
+
+// t2_layouts<true> with T_ba[i][j] taken from the staged tile as T_ab[j][i] instead of a second read of T
+__global__ void __launch_bounds__(256) t2_layouts_sym_kernel(const LayoutsK k) {
+    const double* __restrict__ T = k.T;
+    double* __restrict__ Td = k.Td;
+    double* __restrict__ Tx = k.Tx;
+    double* __restrict__ Ttd = k.Ttd;
+    const int no = k.no, nv = k.nv;
+    extern __shared__ double tile[];          // [no][no + 1]
+    const int a = blockIdx.x / nv, b = blockIdx.x - a * nv;
+    const int p = no + 1, o2 = no * no;
+    const long ov = (long)no * nv;
+    const double* __restrict__ Tab = T + ((long)a * nv + b) * o2;
+    const long base = (long)a * no * ov + (long)b * no;       // element [(a,0),(b,0)] of a pair matrix
+    for (int e = threadIdx.x; e < o2; e += blockDim.x) {
+        const int i = e / no, j = e - i * no;
+        const double x = Tab[e];
+        tile[i * p + j] = x;
+        if (Td) Td[base + (long)i * ov + j] = x;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < o2; e += blockDim.x) {
+        const int i = e / no, j = e - i * no;
+        Ttd[base + (long)i * ov + j] = 2.0 * tile[i * p + j] - tile[j * p + i];
+    }
+    for (int e = threadIdx.x; e < o2; e += blockDim.x) {
+        const int j = e / no, i = e - j * no;                   // Tx tile row j, column i
+        Tx[base + (long)j * ov + i] = tile[i * p + j];
+    }
+}
+
+// dots_stage1 with the pairs of `symmask` summed over their tiles (a, b <= a): chunk `b` of the nb chunks of a pair takes
+// the tiles b, b + nb, ... in rank order (the chunks of different pairs still meet in the same tiles of a shared operand,
+// see DotsK); the other pairs (T1-sized vectors) keep the plain form.
+struct DotsSymK {
+    DotsK d;
+    unsigned symmask;
+    int o2, nv;
+};
+template <int VEC, int SVEC>      // VEC: the plain pairs, as dots_stage1_kernel<VEC> (bit for bit); SVEC: the loads within a tile
+__global__ void __launch_bounds__(256) dots_stage1_sym_kernel(const DotsSymK k) {
+    __shared__ double sh[4];
+    const int nb = k.d.nb, npairs = k.d.npairs;
+    const int lin = blockIdx.x;
+    int pair, b;
+    if ((nb & 7) == 0) { const int q = lin >> 3; pair = q % npairs; b = (q / npairs) * 8 + (lin & 7); }
+    else { pair = lin / nb; b = lin - pair * nb; }
+    if (!((k.symmask >> pair) & 1u)) {        // (block-uniform)
+        dots_stage1_body<VEC>(k.d, blockIdx.x, sh);
+        return;
+    }
+    const double* __restrict__ x = k.d.p.x[pair];
+    const double* __restrict__ y = k.d.p.y[pair];
+    const int o2 = k.o2, nv = k.nv;
+    const long npp = (long)nv * (nv + 1) / 2;
+    double off = 0.0, dia = 0.0;
+    for (long t = b; t < npp; t += nb) {
+        int va, vb;
+        unrank_pair(t, va, vb);
+        const long base = ((long)va * nv + vb) * o2;
+        double s = 0.0;
+        if (SVEC == 2) {                      // o2 even: every tile starts on a 16-byte boundary
+            const double2* __restrict__ x2 = reinterpret_cast<const double2*>(x + base);
+            const double2* __restrict__ y2 = reinterpret_cast<const double2*>(y + base);
+            double s1 = 0.0;
+#pragma unroll 4
+            for (int i = threadIdx.x; i < (o2 >> 1); i += 256) {
+                const double2 u = x2[i], w = y2[i];
+                s += u.x * w.x;
+                s1 += u.y * w.y;
+            }
+            s += s1;
+        } else {
+#pragma unroll 4
+            for (int i = threadIdx.x; i < o2; i += 256) s += x[base + i] * y[base + i];
+        }
+        if (va == vb) dia += s;
+        else off += s;
+    }
+    const double r_off = block_sum(off, sh), r_dia = block_sum(dia, sh);
+    if (threadIdx.x == 0) k.d.partial[pair * kDotBlocks + b] = 2.0 * r_off + r_dia;
+}
+
+// energy_norms over the tiles (a, b <= a) of t2, Edir, Eex, dt2 (tau = t2 + t1 t1 has the symmetry too); block vb of the
+// grid takes the tiles vb, vb + grid, ...; the T1 sums as in the full-read form
+template <int VEC>
+__global__ void __launch_bounds__(256) energy_norms_sym_kernel(const EnergyK k) {
+    __shared__ double sh[4];
+    const double* __restrict__ f = k.f;
+    const double* __restrict__ t1 = k.t1;
+    const double* __restrict__ t2 = k.t2;
+    const double* __restrict__ Edir = k.Edir;
+    const double* __restrict__ Eex = k.Eex;
+    const double* __restrict__ dt2 = k.dt2;
+    double* __restrict__ partial = k.partial;
+    const int no = k.no, nv = k.nv;
+    const unsigned vb = blockIdx.x, vgrid = gridDim.x;
+    const int noV = no / VEC, o2V = no * noV;       // j digit and tile length in units of VEC elements
+    const int sj = 256 % noV, si = 256 / noV;
+    const long npp = (long)nv * (nv + 1) / 2;
+    double s0 = 0.0, s5 = 0.0;
+    double o1 = 0.0, o2 = 0.0, o3 = 0.0, o4 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0, d4 = 0.0;
+    for (long t = vb; t < npp; t += vgrid) {
+        int a, b;
+        unrank_pair(t, a, b);
+        const long base = ((long)a * nv + b) * no * no;
+        double s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
+        int i = (int)threadIdx.x / noV, j = (int)threadIdx.x - i * noV;
+#pragma unroll 2
+        for (int e = threadIdx.x; e < o2V; e += 256) {
+            if (VEC == 2) {
+                const double2 x = reinterpret_cast<const double2*>(t2 + base)[e];
+                const double2 ed = reinterpret_cast<const double2*>(Edir + base)[e], ex = reinterpret_cast<const double2*>(Eex + base)[e];
+                double tx = x.x, ty = x.y;
+                if (t1) {
+                    const double ta = t1[a * no + i];
+                    tx += ta * t1[b * no + 2 * j];
+                    ty += ta * t1[b * no + 2 * j + 1];
+                }
+                s1 += tx * ed.x + ty * ed.y;
+                s2 += tx * ex.x + ty * ex.y;
+                s3 += x.x * x.x + x.y * x.y;
+                if (dt2) { const double2 d = reinterpret_cast<const double2*>(dt2 + base)[e]; s4 += d.x * d.x + d.y * d.y; }
+            } else {
+                const double x = t2[base + e];
+                double tau = x;
+                if (t1) tau += t1[a * no + i] * t1[b * no + j];
+                s1 += tau * Edir[base + e];
+                s2 += tau * Eex[base + e];
+                s3 += x * x;
+                if (dt2) { const double d = dt2[base + e]; s4 += d * d; }
+            }
+            j += sj;
+            const int c = j >= noV; j -= c ? noV : 0;
+            i += si + c;
+        }
+        if (a == b) { d1 += s1; d2 += s2; d3 += s3; d4 += s4; }     // (block-uniform)
+        else { o1 += s1; o2 += s2; o3 += s3; o4 += s4; }
+    }
+    if (t1 && f) {
+        const long n = no + nv, ov = (long)no * nv;
+        for (long e = vb * (long)blockDim.x + threadIdx.x; e < ov; e += (long)vgrid * blockDim.x) {
+            const long a = e / no, i = e - a * no;
+            const double y = t1[e];
+            s0 += f[i * n + no + a] * y;
+            s5 += y * y;
+        }
+    }
+    const double r0 = block_sum(s0, sh), r5 = block_sum(s5, sh);
+    const double r1 = 2.0 * block_sum(o1, sh) + block_sum(d1, sh), r2 = 2.0 * block_sum(o2, sh) + block_sum(d2, sh),
+                 r3 = 2.0 * block_sum(o3, sh) + block_sum(d3, sh), r4 = 2.0 * block_sum(o4, sh) + block_sum(d4, sh);
+    if (threadIdx.x == 0) {
+        partial[5 * kDotBlocks + vb] = r5;
+        partial[0 * kDotBlocks + vb] = r0;
+        partial[1 * kDotBlocks + vb] = r1;
+        partial[2 * kDotBlocks + vb] = r2;
+        partial[3 * kDotBlocks + vb] = r3;
+        partial[4 * kDotBlocks + vb] = r4;
+    }
+}
+
 // ---- pair-sharded tail of the iteration (one process per GPU): a rank owns the virtual pairs P(a,b) in [r0,r1), a >= b,
 // and keeps the tiles X[a,b,:,:] and X[b,a,:,:] of every amplitude-sized quantity in the compact layout
 // Xc[P - r0][2][o*o] (tile 1 is zero for a == b, so that dot products over Xc equal those over the full array) -----
@@ -4726,10 +4967,25 @@ void cc_update(double* t, double* dt, const double* r, const double* eo, const d
                double delta, int no, int nv, int rank, stream_t s) {
     cc_update_to(t, dt, t, r, eo, ev, shift, delta, no, nv, rank, s);
 }
+void cc_update_to_sym(double* t_out, double* dt, const double* t_in, const double* r, const double* eo, const double* ev,
+                      double shift, double delta, int no, int nv, stream_t s) {
+    if (!fused_pair_kernels_ok(no)) throw std::runtime_error("cc_update_to_sym: nocc too large for the LDS tile");
+    const long total = (long)nv * nv * no * no;
+    if (!total) return;
+    phase_open((hipStream_t)s);                                    // (arms the switches phase_small reads)
+    if (phase_small(32.0 * (double)total / 4.0e6)) {               // a small call: the full-read form, task or launch
+        cc_update_to(t_out, dt, t_in, r, eo, ev, shift, delta, no, nv, 4, s);
+        return;
+    }
+    const CcUpdateK k{t_out, dt, t_in, r, eo, ev, shift, delta, no, nv, 4, total};
+    launch_kernel(cc_update_sym_kernel, dim3((unsigned)((long)nv * (nv + 1) / 2)), dim3(256), sizeof(double) * no * (no + 1),
+                  (hipStream_t)s, k);
+}
 
 // stage 1 of a batch of dot products: 16-byte loads when every operand allows them; returns the number of chunks per pair
+// symmask: the pairs whose operands are exchange-symmetric [nv,nv,no,no] arrays, to be summed over the tiles (a, b <= a)
 static int launch_dots_stage1(int npairs, const double* const* x, const double* const* y, const int64_t* n, double* ws,
-                              hipStream_t st) {
+                              hipStream_t st, unsigned symmask = 0u, int no = 0, int nv = 0) {
     DotPtrs p;
     long nmax = 0;
     bool vec = true;
@@ -4755,6 +5011,13 @@ static int launch_dots_stage1(int npairs, const double* const* x, const double* 
             }
         phase_reads(t, {PhaseRange{lo, hi}});
         phase_writes(t, {prange(ws, 16L * kDotBlocks)});
+        return nb;
+    }
+    if (symmask && !phase_small(bytes / 4.0e6)) {          // (a small call keeps the full-read form, task or launch)
+        const DotsSymK ks{k, symmask, no * no, nv};
+        if (vec && even((long)no * no)) launch_kernel(dots_stage1_sym_kernel<2, 2>, dim3(nb * npairs), dim3(256), 0, st, ks);
+        else if (vec) launch_kernel(dots_stage1_sym_kernel<2, 1>, dim3(nb * npairs), dim3(256), 0, st, ks);
+        else launch_kernel(dots_stage1_sym_kernel<1, 1>, dim3(nb * npairs), dim3(256), 0, st, ks);
         return nb;
     }
     if (vec) launch_kernel(dots_stage1_kernel<2>, dim3(nb * npairs), dim3(256), 0, st, k);
@@ -4789,13 +5052,14 @@ static void launch_dots_final(DotsFinalK k, double* ws, hipStream_t st) {
     launch_kernel(dots_final_kernel, dim3(k.npairs), dim3(256), 0, st, k);
 }
 
-void dots(int npairs, const double* const* x, const double* const* y, const int64_t* n, double* out_host, stream_t s) {
+static void dots_impl(int npairs, const double* const* x, const double* const* y, const int64_t* n, unsigned symmask, int no,
+                      int nv, double* out_host, stream_t s) {
     if (npairs <= 0) return;
     if (npairs > 16) throw std::runtime_error("dots: at most 16 pairs per call");
     hipStream_t st = (hipStream_t)s;
     const int dv = current_device();
     ensure_dot_ws(dv);
-    const int nb = launch_dots_stage1(npairs, x, y, n, g_dot_ws[dv], st);
+    const int nb = launch_dots_stage1(npairs, x, y, n, g_dot_ws[dv], st, symmask, no, nv);
     // results and a sequence word straight into pinned memory, polled for (no copy, no stream synchronisation)
     void* hd = nullptr;
     HIP_CHECK(hipHostGetDevicePointer(&hd, g_dot_host[dv], 0));
@@ -4806,6 +5070,20 @@ void dots(int npairs, const double* const* x, const double* const* y, const int6
     phase_flush();
     if (!poll_flag(reinterpret_cast<const long*>(g_dot_host[dv] + 16), seq, st)) throw std::runtime_error("dots: the device never delivered the result");
     for (int i = 0; i < npairs; ++i) out_host[i] = g_dot_host[dv][i];
+}
+void dots(int npairs, const double* const* x, const double* const* y, const int64_t* n, double* out_host, stream_t s) {
+    dots_impl(npairs, x, y, n, 0u, 0, 0, out_host, s);
+}
+bool sym_tail_ok() { return true; }
+void dots_sym(int npairs, const double* const* x, const double* const* y, const int64_t* n, const int* sym, int no, int nv,
+              double* out_host, stream_t s) {
+    unsigned mask = 0u;
+    for (int i = 0; i < npairs && i < 16; ++i)
+        if (sym[i]) {
+            if (n[i] != (int64_t)nv * nv * no * no) throw std::runtime_error("dots_sym: a symmetric pair is not [nv,nv,no,no]");
+            mask |= 1u << i;
+        }
+    dots_impl(npairs, x, y, n, mask, no, nv, out_host, s);
 }
 
 void diis_step(double* state, int npairs, const double* const* x, const double* const* y, const int64_t* n, int ntypes, int m,
@@ -4829,8 +5107,8 @@ void lincomb_dev(double* out, int nx, const double* const* x, const double* coef
     launch_kernel(lincomb_dev_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, out, p, coeff_dev, nx, (long)n);
 }
 
-int energy_norms_start(const double* f, const double* t1, const double* t2, const double* Edir, const double* Eex,
-                       const double* dt2, int no, int nv, stream_t s) {
+static int energy_norms_start_impl(const double* f, const double* t1, const double* t2, const double* Edir, const double* Eex,
+                                   const double* dt2, int no, int nv, bool sym, stream_t s) {
     gemm_group_flush();
     hipStream_t st = (hipStream_t)s;
     const int dv = current_device();
@@ -4847,6 +5125,9 @@ int energy_norms_start(const double* f, const double* t1, const double* t2, cons
         phase_reads(t, {prange(t2, total), prange(Edir, total), prange(Eex, total), prange(dt2, dt2 ? total : 0),
                         prange(t1, t1 ? (long)no * nv : 0), prange(f, (t1 && f) ? n * n : 0)});
         phase_writes(t, {prange(g_dot_ws[dv], 16L * kDotBlocks)});
+    } else if (sym && total && !phase_small(cost)) {
+        if (vec) launch_kernel(energy_norms_sym_kernel<2>, dim3(nb), dim3(256), 0, st, k);
+        else launch_kernel(energy_norms_sym_kernel<1>, dim3(nb), dim3(256), 0, st, k);
     } else {
         if (vec) launch_kernel(energy_norms_kernel<2>, dim3(nb), dim3(256), 0, st, k);
         else launch_kernel(energy_norms_kernel<1>, dim3(nb), dim3(256), 0, st, k);
@@ -4859,6 +5140,14 @@ int energy_norms_start(const double* f, const double* t1, const double* t2, cons
     launch_dots_final(DotsFinalK{g_dot_ws[dv], out_pin, flag, nullptr, 0u, seq, nb, 6}, g_dot_ws[dv], st);
     phase_flush();
     return ticket;
+}
+int energy_norms_start(const double* f, const double* t1, const double* t2, const double* Edir, const double* Eex,
+                       const double* dt2, int no, int nv, stream_t s) {
+    return energy_norms_start_impl(f, t1, t2, Edir, Eex, dt2, no, nv, false, s);
+}
+int energy_norms_start_sym(const double* f, const double* t1, const double* t2, const double* Edir, const double* Eex,
+                           const double* dt2, int no, int nv, stream_t s) {
+    return energy_norms_start_impl(f, t1, t2, Edir, Eex, dt2, no, nv, true, s);
 }
 void energy_norms(const double* f, const double* t1, const double* t2, const double* Edir, const double* Eex,
                   const double* dt2, int no, int nv, double out_host[6], stream_t s) {
@@ -4909,6 +5198,22 @@ void lincomb(double* out, int nx, const double* const* x, const double* c, int64
         return;
     }
     launch_kernel(lincomb_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, k);
+}
+void lincomb_sym(double* out, int nx, const double* const* x, const double* c, int no, int nv, stream_t s) {
+    if (nx < 0 || nx > 8) throw std::runtime_error("lincomb: at most 8 terms");
+    if (!fused_pair_kernels_ok(no)) throw std::runtime_error("lincomb_sym: nocc too large for the LDS tile");
+    const long n = (long)nv * nv * no * no;
+    if (n <= 0) return;
+    phase_open((hipStream_t)s);
+    if (phase_small(8.0 * (double)(nx + 1) * (double)n / 4.0e6)) {     // a small call: the full-read form, task or launch
+        lincomb(out, nx, x, c, n, s);
+        return;
+    }
+    LinPtrs p;
+    for (int i = 0; i < 8; ++i) { p.x[i] = i < nx ? x[i] : nullptr; p.c[i] = i < nx ? c[i] : 0.0; }
+    const LinSymK k{out, p, nx, no, nv};
+    launch_kernel(lincomb_sym_kernel, dim3((unsigned)((long)nv * (nv + 1) / 2)), dim3(256), sizeof(double) * no * (no + 1),
+                  (hipStream_t)s, k);
 }
 
 namespace {
@@ -5230,6 +5535,18 @@ void t2_layouts(const double* T, double* Td, double* Tx, double* Ttd, int no, in
     }
     if (res) launch_kernel(t2_layouts_kernel<true>, dim3((unsigned)(nv * nv)), dim3(256), lds, (hipStream_t)s, k);
     else launch_kernel(t2_layouts_kernel<false>, dim3((unsigned)(nv * nv)), dim3(256), lds, (hipStream_t)s, k);
+}
+void t2_layouts_sym(const double* T, double* Td, double* Tx, double* Ttd, int no, int nv, stream_t s) {
+    if (!fused_pair_kernels_ok(no)) throw std::runtime_error("t2_layouts: nocc too large for the LDS tile");
+    const long n4 = (long)nv * nv * no * no;
+    phase_open((hipStream_t)s);
+    if (phase_small(40.0 * (double)n4 / 4.0e6)) {                  // a small call: the full-read form, task or launch
+        t2_layouts(T, Td, Tx, Ttd, no, nv, s);
+        return;
+    }
+    if (!n4) return;
+    const LayoutsK k{T, Td, Tx, Ttd, 2.0, -1.0, no, nv};
+    launch_kernel(t2_layouts_sym_kernel, dim3((unsigned)(nv * nv)), dim3(256), sizeof(double) * no * (no + 1), (hipStream_t)s, k);
 }
 
 void residual_assemble(const double* V, const double* L, const double* N, const double* D, const double* X, double* R,

@@ -414,11 +414,19 @@ class Context:
         else:
             self.lib.call("pymes_ccsd_dress_V", self.handle, C.c_void_p(t1.ptr), mask)
 
-    def ccsd_residuals(self, f, t1, t2, r1, r2, is_dcd=False, t1_zero=False):
-        """ccsd.py:161-171 in one call (symmetry-reduced form, one rank; include/pymes_amd.h): R1, R2 from (f, t1, t2)."""
+    def ccsd_residuals(self, f, t1, t2, r1, r2, is_dcd=False, t1_zero=False, sym_tail=False):
+        """ccsd.py:161-171 in one call (symmetry-reduced form, one rank; include/pymes_amd.h): R1, R2 from (f, t1, t2).
+        ``sym_tail``: the caller runs the amplitude tail on exchange-symmetric arrays (PYMES_SYM_TAIL)."""
         self.lib.call("pymes_ccsd_residuals", self.handle, C.c_void_p(f.ptr), C.c_void_p(t1.ptr), C.c_void_p(t2.ptr),
-                      (_lib.PYMES_DCD if is_dcd else 0) | (_lib.PYMES_T1_ZERO if t1_zero else 0), C.c_void_p(r1.ptr),
-                      C.c_void_p(r2.ptr))
+                      (_lib.PYMES_DCD if is_dcd else 0) | (_lib.PYMES_T1_ZERO if t1_zero else 0) |
+                      (_lib.PYMES_SYM_TAIL if sym_tail else 0), C.c_void_p(r1.ptr), C.c_void_p(r2.ptr))
+
+    def sym_tail(self):
+        """Do the calls that declare exchange-symmetric amplitudes (``sym=...``) read each exchange pair once here?
+        (include/pymes_amd.h, pymes_sym_tail; they are the plain calls otherwise.)"""
+        yes = C.c_int()
+        self.lib.call("pymes_sym_tail", self.handle, C.byref(yes))
+        return bool(yes.value)
 
     def ccsd_iterate(self, f, t1, t2, dt1, dt2, level_shift=0.0, delta=1.0, is_dcd=False, t1_zero=False):
         """One fixed-point pass without a mixer (ccsd.py:159-197, is_diis = False): (e_1b, e_dir, e_ex, |t2|^2, |dt2|^2, |t1|^2)."""
@@ -446,13 +454,13 @@ class Context:
         return out
 
     def doubles_residual(self, f, t2, out, is_dcd=False, dressed=False, skip_ladder=False, sym_ladder=False,
-                         sym_rings=None):
+                         sym_rings=None, sym_tail=False):
         """``sym_ladder`` / ``sym_rings``: T_abij = T_baji and V_pqrs = V_qpsr hold, use the symmetry-reduced
         forms (pair-packed ladder, merged ring products); ``sym_rings`` defaults to ``sym_ladder``."""
         sym_rings = sym_ladder if sym_rings is None else sym_rings
         flags = (_lib.PYMES_DCD if is_dcd else 0) | (_lib.PYMES_USE_DRESSED if dressed else 0) | \
                 (_lib.PYMES_SKIP_LADDER if skip_ladder else 0) | (_lib.PYMES_SYM_LADDER if sym_ladder else 0) | \
-                (_lib.PYMES_SYM_RINGS if sym_rings else 0)
+                (_lib.PYMES_SYM_RINGS if sym_rings else 0) | (_lib.PYMES_SYM_TAIL if sym_tail and sym_rings else 0)
         self.lib.call("pymes_doubles_residual", self.handle, C.c_void_p(f.ptr), C.c_void_p(t2.ptr),
                       C.c_void_p(out.ptr), flags)
         return out
@@ -567,9 +575,10 @@ class Context:
                       C.c_void_p(W.ptr), int(ld), int(r0), int(r1), int(minus_half))
         return W
 
-    def pair_layouts(self, x, Xx, Xt, Xd=None):
-        """Xx[(a,j),(b,i)] = x_abij, Xt[(a,i),(b,j)] = 2 x_abij - x_baij (and Xd[(a,i),(b,j)] = x_abij) in one pass."""
-        self.lib.call("pymes_pair_layouts", self.handle, C.c_void_p(x.ptr), C.c_void_p(Xd.ptr if Xd is not None else 0),
+    def pair_layouts(self, x, Xx, Xt, Xd=None, sym=False):
+        """Xx[(a,j),(b,i)] = x_abij, Xt[(a,i),(b,j)] = 2 x_abij - x_baij (and Xd[(a,i),(b,j)] = x_abij) in one pass.
+        ``sym``: the caller declares x_abij == x_baji."""
+        self.lib.call("pymes_pair_layouts_sym" if sym else "pymes_pair_layouts", self.handle, C.c_void_p(x.ptr), C.c_void_p(Xd.ptr if Xd is not None else 0),
                       C.c_void_p(Xx.ptr), C.c_void_p(Xt.ptr))
 
     def symmetrised_assemble(self, N, D, X, out, V=None, L=None):
@@ -600,28 +609,38 @@ class Context:
         self.lib.call("pymes_ladder_sym_unpack", self.handle, C.c_void_p(L.ptr), C.c_void_p(out.ptr), float(beta))
         return out
 
-    def cc_update(self, t, dt, r, level_shift=0.0, delta=1.0):
+    def cc_update(self, t, dt, r, level_shift=0.0, delta=1.0, sym=False):
         rank = len(t.shape)
+        if sym and rank == 4:
+            return self.cc_update_to(t, dt, t, r, level_shift, delta, sym=True)
         self.lib.call("pymes_cc_update", self.handle, C.c_void_p(t.ptr), C.c_void_p(dt.ptr), C.c_void_p(r.ptr),
                       float(level_shift), float(delta), rank)
 
-    def cc_update_to(self, t_out, dt, t_in, r, level_shift=0.0, delta=1.0):
-        """dt = r/(D+shift), t_out = t_in + delta*dt (t_out may be t_in)."""
+    def cc_update_to(self, t_out, dt, t_in, r, level_shift=0.0, delta=1.0, sym=False):
+        """dt = r/(D+shift), t_out = t_in + delta*dt (t_out may be t_in).  ``sym`` (rank 4): the caller declares r and t_in
+        exchange-symmetric, X_abij == X_baji (include/pymes_amd.h, pymes_cc_update_to_sym)."""
+        if sym and len(t_in.shape) == 4:
+            self.lib.call("pymes_cc_update_to_sym", self.handle, C.c_void_p(t_out.ptr), C.c_void_p(dt.ptr),
+                          C.c_void_p(t_in.ptr), C.c_void_p(r.ptr), float(level_shift), float(delta))
+            return
         self.lib.call("pymes_cc_update_to", self.handle, C.c_void_p(t_out.ptr), C.c_void_p(dt.ptr), C.c_void_p(t_in.ptr),
                       C.c_void_p(r.ptr), float(level_shift), float(delta), len(t_in.shape))
 
-    def energy_norms(self, f, t1, t2, dt2=None):
-        """(one-body, direct, exchange, |t2|^2, |dt2|^2, |t1|^2) in one pass and one synchronisation; f/t1 None for CCD."""
+    def energy_norms(self, f, t1, t2, dt2=None, sym=False):
+        """(one-body, direct, exchange, |t2|^2, |dt2|^2, |t1|^2) in one pass and one synchronisation; f/t1 None for CCD.
+        ``sym``: the caller declares t2 and dt2 exchange-symmetric."""
+        if sym:
+            return self.energy_norms_wait(self.energy_norms_start(f, t1, t2, dt2, sym=True))
         out = (C.c_double * 6)()
         self.lib.call("pymes_energy_norms", self.handle, C.c_void_p(f.ptr if f is not None else 0),
                       C.c_void_p(t1.ptr if t1 is not None else 0), C.c_void_p(t2.ptr),
                       C.c_void_p(dt2.ptr if dt2 is not None else 0), out)
         return tuple(out[:])
 
-    def energy_norms_start(self, f, t1, t2, dt2=None):
+    def energy_norms_start(self, f, t1, t2, dt2=None, sym=False):
         """``energy_norms`` enqueued only: returns a read-back slot for ``energy_norms_wait`` (include/pymes_amd.h)."""
         slot = C.c_int()
-        self.lib.call("pymes_energy_norms_start", self.handle, C.c_void_p(f.ptr if f is not None else 0),
+        self.lib.call("pymes_energy_norms_start_sym" if sym else "pymes_energy_norms_start", self.handle, C.c_void_p(f.ptr if f is not None else 0),
                       C.c_void_p(t1.ptr if t1 is not None else 0), C.c_void_p(t2.ptr),
                       C.c_void_p(dt2.ptr if dt2 is not None else 0), C.byref(slot))
         return slot.value
@@ -689,13 +708,20 @@ class Context:
         return e[0], e[1]
 
     # ---- vector helpers ---------------------------------------------------------------
-    def dots(self, xs, ys):
-        """out[p] = <xs[p], ys[p]>; the pairs may differ in length (T1 and T2 overlaps in one launch)."""
+    def dots(self, xs, ys, sym=None):
+        """out[p] = <xs[p], ys[p]>; the pairs may differ in length (T1 and T2 overlaps in one launch).  ``sym``: one flag per
+        pair — the caller declares both operands exchange-symmetric [v,v,o,o] amplitudes (pymes_dots_sym)."""
         assert len(xs) == len(ys) and all(x.size == y.size for x, y in zip(xs, ys))
         out = np.empty(len(xs))
         for lo in range(0, len(xs), 16):
             hi = min(len(xs), lo + 16)
             buf = (C.c_double * (hi - lo))()
+            if sym is not None and any(sym[lo:hi]):
+                self.lib.call("pymes_dots_sym", self.handle, hi - lo, ptr_array([x.ptr for x in xs[lo:hi]]),
+                              ptr_array([y.ptr for y in ys[lo:hi]]), i64_array([x.size for x in xs[lo:hi]]),
+                              (C.c_int * (hi - lo))(*[int(bool(f)) for f in sym[lo:hi]]), buf)
+                out[lo:hi] = buf[:]
+                continue
             self.lib.call("pymes_dots_var", self.handle, hi - lo, ptr_array([x.ptr for x in xs[lo:hi]]),
                           ptr_array([y.ptr for y in ys[lo:hi]]), i64_array([x.size for x in xs[lo:hi]]), buf)
             out[lo:hi] = buf[:]
@@ -704,7 +730,8 @@ class Context:
     def norm(self, x):
         return float(np.sqrt(self.dots([x], [x])[0]))
 
-    def lincomb(self, out, xs, coeffs):
+    def lincomb(self, out, xs, coeffs, sym=False):
+        """out = sum_k coeffs[k] xs[k].  ``sym``: the caller declares every xs[k] an exchange-symmetric [v,v,o,o] array."""
         assert len(xs) == len(coeffs) and all(x.size == out.size for x in xs)
         first = True
         for lo in range(0, len(xs), 7):
@@ -712,7 +739,7 @@ class Context:
             if not first:
                 chunk, cc = [out] + chunk, [1.0] + cc
             cbuf = (C.c_double * len(cc))(*cc)
-            self.lib.call("pymes_lincomb", self.handle, C.c_void_p(out.ptr), len(chunk),
+            self.lib.call("pymes_lincomb_sym" if sym else "pymes_lincomb", self.handle, C.c_void_p(out.ptr), len(chunk),
                           ptr_array([x.ptr for x in chunk]), cbuf, out.size)
             first = False
         return out
@@ -775,11 +802,20 @@ class Context:
                               _lib.host_ptr(bb) if bb is not None else None, ptr_array([y.ptr for y in oj]), size)
         return outs
 
-    def diis_mix(self, state_host, err_hist, err_new, amp_hist, outs, m, was_full):
+    def diis_mix(self, state_host, err_hist, err_new, amp_hist, outs, m, was_full, sym_types=None):
         """One DIIS step in one library call (include/pymes_amd.h, pymes_diis_mix): ``err_hist`` / ``amp_hist`` are the
-        stored vectors type-major ([t][i]), ``state_host`` a float64 numpy array of 96 (L and the coefficients)."""
+        stored vectors type-major ([t][i]), ``state_host`` a float64 numpy array of 96 (L and the coefficients).
+        ``sym_types``: one flag per amplitude type — its vectors are exchange-symmetric [v,v,o,o] arrays, the caller's
+        declaration (pymes_diis_mix_sym)."""
         ntypes = len(err_new)
         assert len(err_hist) == len(amp_hist) == ntypes * m and len(outs) == ntypes and state_host.size >= 96
+        if sym_types is not None and any(sym_types):
+            assert len(sym_types) == ntypes
+            self.lib.call("pymes_diis_mix_sym", self.handle, _lib.host_ptr(state_host), ntypes, int(m), int(bool(was_full)),
+                          ptr_array([x.ptr for x in err_hist]), ptr_array([x.ptr for x in err_new]),
+                          i64_array([x.size for x in err_new]), ptr_array([x.ptr for x in amp_hist]),
+                          ptr_array([x.ptr for x in outs]), (C.c_int * ntypes)(*[int(bool(f)) for f in sym_types]))
+            return
         self.lib.call("pymes_diis_mix", self.handle, _lib.host_ptr(state_host), ntypes, int(m), int(bool(was_full)),
                       ptr_array([x.ptr for x in err_hist]), ptr_array([x.ptr for x in err_new]),
                       i64_array([x.size for x in err_new]), ptr_array([x.ptr for x in amp_hist]),

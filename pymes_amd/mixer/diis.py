@@ -191,7 +191,7 @@ class DIIS:
         return np.linalg.inv(self.L).dot(unit)
 
     def mix(self, error, amplitude, release=None, sharded=(), allreduce=None, out=None, mark=None, on_device=False,
-            defer_log=False, native=False):
+            defer_log=False, native=False, sym=()):
         """error / amplitude: lists of DeviceArray (one entry per amplitude type).
         Returns freshly allocated DeviceArrays with the extrapolated amplitudes.  The
         mixer keeps references to the arrays passed in (like the reference): the caller must
@@ -200,7 +200,10 @@ class DIIS:
         this process holds only its share (one process per GPU); their overlaps are summed over the ranks with
         ``allreduce`` (a callable on a small numpy vector), the extrapolation itself is local.  ``out``: arrays to
         write the extrapolated amplitudes into instead of fresh ones (the solvers keep T1/T2 in fixed buffers so that
-        their loop body can be replayed as a launch graph); they must not be among the stored vectors."""
+        their loop body can be replayed as a launch graph); they must not be among the stored vectors.  ``sym``: indices of
+        the amplitude types whose vectors — every stored one included — are exchange-symmetric [v,v,o,o] arrays, the
+        caller's declaration (the single-rank loops; include/pymes_amd.h, pymes_diis_mix_sym).  The whole-step form on the
+        device (``on_device``) does not take it."""
         self._adopt(error[0].ctx, error)
         was_full = len(self.error_list) == self.dim_space
         if was_full:
@@ -240,7 +243,8 @@ class DIIS:
             buf[1:82] = pad.ravel()
             res = [out[nt] if out is not None else ctx.pool_get(amplitude[nt].shape) for nt in range(ntypes)]
             ctx.diis_mix(buf, [self.error_list[i][nt] for nt in range(ntypes) for i in range(m)], list(error),
-                         [self.amplitude_list[a][nt] for nt in range(ntypes) for a in range(m)], res, m, was_full)
+                         [self.amplitude_list[a][nt] for nt in range(ntypes) for a in range(m)], res, m, was_full,
+                         sym_types=[nt in sym for nt in range(ntypes)] if sym and not sharded else None)
             n1 = int(buf[0])
             self.L = buf[1:82].reshape(9, 9)[:n1, :n1].copy()
             self.last_coefficients = buf[82:82 + n1].copy()
@@ -256,7 +260,8 @@ class DIIS:
         # all <e_i, e_new> of all amplitude types in one launch and one synchronisation; summed per type on the host
         # in the order of the reference's loop (diis.py:65-78)
         parts = ctx.dots([self.error_list[i][nt] for nt in range(ntypes) for i in range(m)],
-                         [error[nt] for nt in range(ntypes) for _ in range(m)])
+                         [error[nt] for nt in range(ntypes) for _ in range(m)],
+                         sym=[nt in sym for nt in range(ntypes) for _ in range(m)] if sym and not sharded else None)
         for nt in range(ntypes):
             part = parts[nt * m:(nt + 1) * m]
             overlaps += allreduce(part) if nt in sharded else part
@@ -289,7 +294,7 @@ class DIIS:
         res = []
         for nt in range(ntypes):
             dst = out[nt] if out is not None else ctx.pool_get(amplitude[nt].shape)
-            ctx.lincomb(dst, [self.amplitude_list[a][nt] for a in range(m)], c[:m])
+            ctx.lincomb(dst, [self.amplitude_list[a][nt] for a in range(m)], c[:m], sym=bool(nt in sym and not sharded))
             res.append(dst)
         out = res
         if defer_log:           # the caller prints these lines (log_last) once its next kernels are on their way

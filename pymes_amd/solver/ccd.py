@@ -187,21 +187,21 @@ class CCD:
                     e_dir_ccd, e_ex_ccd, nt, nr = self._sharded_iteration(ctx, shard, f_dev, t2, level_shift, delta)  # :132
                 else:
                     run_replayable(ctx, st, lambda: ctx.doubles_residual(f_dev, t2, r2, is_dcd=self.is_dcd,
-                                                                         sym_ladder=sym))     # ccd.py:100-102
+                                                                         sym_ladder=sym, sym_tail=sym))     # ccd.py:100-102
                     if self.is_diis:
                         t2n, dt2 = ctx.pool_get(t2.shape), ctx.pool_get(t2.shape)
-                        ctx.cc_update_to(t2n, dt2, t2, r2, level_shift, delta)        # :123-124
+                        ctx.cc_update_to(t2n, dt2, t2, r2, level_shift, delta, sym=sym)        # :123-124
                     else:
                         t2n, dt2 = t2, dt_fixed
-                        ctx.cc_update(t2, dt2, r2, level_shift, delta)
+                        ctx.cc_update(t2, dt2, r2, level_shift, delta, sym=sym)
                     if first and amps is not None:
                         np.copyto(amps, t2n.get())    # the reference updates the caller's array in place (:124)
                     first = False
                     if self.is_diis:
                         self.mixer.mix([dt2], [t2n], release=ctx.pool_put, out=[t2], defer_log=True,   # :126-127
                                        on_device=bool(os.environ.get("PYMES_DEVICE_DIIS")),
-                           native=not os.environ.get("PYMES_NUMPY_DIIS"))
-                    _, e_dir_ccd, e_ex_ccd, nt2, nr2, _ = ctx.energy_norms(None, None, t2, dt2)   # :132 + norms, one pass
+                           native=not os.environ.get("PYMES_NUMPY_DIIS"), sym=(0,) if sym else ())
+                    _, e_dir_ccd, e_ex_ccd, nt2, nr2, _ = ctx.energy_norms(None, None, t2, dt2, sym=sym)   # :132 + norms, one pass
                     if self.is_diis:
                         self.mixer.log_last()
                     nt, nr = np.sqrt(nt2), np.sqrt(nr2)

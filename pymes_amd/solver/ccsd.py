@@ -168,7 +168,7 @@ class CCSD(ccd.CCD):
             # products inside the finish (include/pymes_amd.h, pymes_residual_slab).  T1 = 0 exactly (the MP2 start; every
             # iteration of a momentum-conserving system such as the UEG): exp(-T1) H exp(T1) = H, :163 and :165 are
             # identities — the residuals straight from the undressed f and V
-            ctx.ccsd_residuals(st["f"], t1, t2, r1, r2, is_dcd=self.is_dcd, t1_zero=st["t1_zero"])
+            ctx.ccsd_residuals(st["f"], t1, t2, r1, r2, is_dcd=self.is_dcd, t1_zero=st["t1_zero"], sym_tail=True)
         else:
             # general path (amplitudes or integrals without the exchange symmetry): explicitly dressed blocks
             ctx.dress_fock(st["f"], t1, st["fd"])                                     # :163
@@ -189,6 +189,9 @@ class CCSD(ccd.CCD):
         the last.  At (20,80) that round trip (read-back, interpreter, graph launch) was 85 us of a 2.1-ms iteration."""
         ctx, t1, t2, r1, r2 = st["ctx"], st["t1"], st["t2"], st["r1"], st["r2"]
         shift = st["level_shift"]
+        # the symmetry-reduced solve keeps T2, R2, dT2 and every stored DIIS vector exchange-symmetric: update, mixer and
+        # energy pass are told so and read each exchange pair once (include/pymes_amd.h, pymes_sym_tail)
+        sym = bool(st["sym"])
         mark = pdist.trace.mark          # device and host time per phase when bench.py asks for it (no-ops otherwise)
         mark("begin")
         if not st.pop("residuals_in_flight", False):
@@ -203,11 +206,11 @@ class CCSD(ccd.CCD):
                 t1n, t2n, dt1, dt2 = (ctx.pool_get(t1.shape), ctx.pool_get(t2.shape), ctx.pool_get(t1.shape),
                                       ctx.pool_get(t2.shape))
                 ctx.cc_update_to(t1n, dt1, t1, r1, shift, self.delta)                     # :176-179
-                ctx.cc_update_to(t2n, dt2, t2, r2, shift, self.delta)
+                ctx.cc_update_to(t2n, dt2, t2, r2, shift, self.delta, sym=sym)
             else:
                 t1n, t2n, dt1, dt2 = t1, t2, st["dt1"], st["dt2"]
                 ctx.cc_update(t1, dt1, r1, shift, self.delta)
-                ctx.cc_update(t2, dt2, r2, shift, self.delta)
+                ctx.cc_update(t2, dt2, r2, shift, self.delta, sym=sym)
             if st["first"] and st["amps"] is not None:
                 np.copyto(st["amps"][0], t1n.get())     # the reference updates the caller's arrays in place
                 np.copyto(st["amps"][1], t2n.get())
@@ -223,9 +226,9 @@ class CCSD(ccd.CCD):
                 # (20,80), round 4).  PYMES_NUMPY_DIIS=1: numpy.linalg as the reference.
                 self.mixer.mix([dt1, dt2], [t1n, t2n], release=ctx.pool_put, out=[t1, t2], mark=mark, defer_log=True,
                                on_device=bool(os.environ.get("PYMES_DEVICE_DIIS")),
-                               native=not os.environ.get("PYMES_NUMPY_DIIS"))
+                               native=not os.environ.get("PYMES_NUMPY_DIIS"), sym=(1,) if sym else ())
             mark("DIIS extrapolation")
-            slot = ctx.energy_norms_start(st["f"], t1, t2, dt2)                            # :189-197, one pass, enqueued
+            slot = ctx.energy_norms_start(st["f"], t1, t2, dt2, sym=sym)                            # :189-197, one pass, enqueued
         # the next pass's residuals, behind the energy reduction: same variant as this pass's (T1 = 0 only ever changes after
         # the first pass from MP2, or never: a momentum-conserving system); recorded launch graphs only — the eager first
         # passes of a variant do their per-solve set-up work and stay where they were

@@ -76,7 +76,7 @@ EomSigma::EomSigma(Engine& eng, const double* f_host, const double* t2, bool dre
     const int64_t o = no, v = nv, n = o + v, ov = o * v, ov2 = ov * ov;
     const Ops q{e};
     try {
-        std::vector<double> h(static_cast<size_t>(std::max(v * v, o * v)));
+        std::vector<double> h(static_cast<size_t>(std::max(v * v, std::max(o * v, o * o))));     // (f_oo is the largest when no > nv)
         auto upload = [&](int64_t r0, int64_t nr, int64_t c0, int64_t nc, double sign, bool transposed = false) {
             for (int64_t r = 0; r < nr; ++r)
                 for (int64_t c = 0; c < nc; ++c)

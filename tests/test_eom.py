@@ -181,6 +181,12 @@ def test_apply_many_host_logic(hostsim_lib, monkeypatch):
     check_apply_many(hostsim_lib, monkeypatch, 3, 5, 3, 1e-11)
 
 
+def test_apply_many_more_occupied_than_virtual_host_logic(hostsim_lib, monkeypatch):
+    """no > nv: f_oo is the largest block of the Fock matrix that the handle stages on the host (its staging buffer was sized by
+    f_vv and f_ov alone; tests/hostsim/run_sanitized.sh sees such an overrun, a plain run need not)."""
+    check_apply_many(hostsim_lib, monkeypatch, 3, 2, 2, 1e-11)
+
+
 @pytest.mark.gpu
 def test_apply_many_gpu(gpu_lib, monkeypatch):
     check_apply_many(gpu_lib, monkeypatch, 3, 5, 3, 1e-11)

@@ -7,7 +7,9 @@ phases on or off), and at these sizes every call is that small.  ``forced`` ther
 PYMES_PHASE_MAX_US=0 (nothing is small).
 
 Shapes (no, nv): (1,2) and (6,1) the smallest / a diagonal pair only; (2,3) even nocc (16-byte loads); (3,4), (5,3) odd nocc
-(scalar loads); (16,5), (17,4) o^2 = 256 and 289 against the 256-thread block loop."""
+(scalar loads); (16,5), (17,4) o^2 = 256 and 289 against the 256-thread block loop; (24,3), (32,2) the 16-byte form past one
+trip of that loop: o^2 / 2 = 288 and 512 double2 per tile, at no = 24 the (i, j) digits advance by (21, 4) per trip and carry on
+the second one, at no = 32 by (16, 0) without a carry."""
 import contextlib
 import io
 import json
@@ -24,7 +26,7 @@ from pymes_amd.mixer.diis import DIIS
 from pymes_amd.solver import ccd, ccsd
 
 pytestmark = pytest.mark.gpu
-SHAPES = [(1, 2), (2, 3), (3, 4), (5, 3), (16, 5), (17, 4), (6, 1)]
+SHAPES = [(1, 2), (2, 3), (3, 4), (5, 3), (16, 5), (17, 4), (24, 3), (32, 2), (6, 1)]
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 EPS = 2.0 ** -53
 

@@ -28,6 +28,20 @@ extern "C" {
 
 typedef struct pymes_ctx pymes_ctx;
 
+/* ---- limits on nocc.  Three kernel families stage occupied-index tiles in the 64 KB of LDS a workgroup is given, and each has
+ * its own largest nocc; everything else has none.
+ *   PYMES_NOCC_MAX_FUSED   the fused pair kernels (one nocc x (nocc + 1) tile of doubles: pymes_pair_layouts[_sym],
+ *                          pymes_symmetrised_assemble, the pair-sharded tail, the read-once amplitude tail): 90 x 91 x 8 = 65 520 B.
+ *                          pymes_pairs_supported / pymes_sym_tail answer 0 above it; the residual and the right EOM sigma then
+ *                          run their unfused forms (same results), the entry points named here and pymes_eom_sigma_apply_left
+ *                          refuse.
+ *   PYMES_NOCC_MAX_LAMBDA  the left assembly (that tile + 256 partial sums: pymes_eom_sigma_apply_left, pymes_lambda_step and the
+ *                          solvers on them): 88 x 89 x 8 + 2048 = 64 704 B.  Refused above it before anything is allocated.
+ *   PYMES_NOCC_MAX_BRA_DRESS  pymes_ladder_dress (the instantiated MFMA step counts); the CCSD step falls back to its Q_kb form. */
+#define PYMES_NOCC_MAX_FUSED 90
+#define PYMES_NOCC_MAX_LAMBDA 88
+#define PYMES_NOCC_MAX_BRA_DRESS 80
+
 /* ---- library / context ------------------------------------------------------- */
 const char* pymes_last_error(void);
 const char* pymes_backend(void);                 /* "hip-gfx950" for the product library */
@@ -247,7 +261,7 @@ int pymes_ladder_sym_multi(pymes_ctx* ctx, const double* const* x_dev, int k, do
  * packed, pitch ld = a multiple of 16 doubles), Pk_dev [v*o][ld] the rows x*o + k of V_kxcd packed the same way (x slow), t1_dev [v,o]:
  *   W[P(a,b)] = V[P(a,b)] - sum_k t1[a,k] Pk[(b,k)] -+ sum_k t1[b,k] Pk[(a,k)]
  * ("-" for the symmetric half V_abcd + V_abdc, "+" with minus_half = 1 for V_abcd - V_abdc, whose rows a == b stay zero).
- * nocc <= 64; the packed rows of 16 consecutive a within 2 GB (nvirt up to ~320). */
+ * nocc <= PYMES_NOCC_MAX_BRA_DRESS; the packed rows of 16 consecutive a within 2 GB (nvirt up to ~320). */
 int pymes_ladder_dress(pymes_ctx* ctx, const double* V_dev, const double* Pk_dev, const double* t1_dev, double* W_dev,
                        int64_t ld, int64_t r0, int64_t r1, int minus_half);
 /* The three pair layouts of an amplitude-like array X [v,v,o,o] in one pass: Xd[(a,i),(b,j)] = X_abij,

@@ -383,6 +383,7 @@ struct LambdaParts {
 };
 int64_t lambda_assemble_ws_doubles(int nv);
 void lambda_assemble(const LambdaParts& q, int no, int nv, stream_t s);
+bool lambda_assemble_ok(int no);       // the tile and the partial sums fit the LDS: no <= PYMES_NOCC_MAX_LAMBDA
 // gamma [n,n] (n = no + nv, occupied first; device) from Xvv[a,c] = sum l2[a,b,i,j] t2[c,b,i,j], Xoo[k,i] = sum l2[a,b,i,j]
 // t2[a,b,k,j], Xov[j,b] = sum l1[a,i] (2 t2[a,b,i,j] - t2[a,b,j,i]) and l1, t1 [v,o], including the back-transformation with
 // t1 (formulas: include/pymes_amd.h, pymes_rdm1); ref is added on the occupied diagonal.  One launch.

@@ -825,6 +825,7 @@ __attribute__((weak)) void ipea_correction(int, const double* const*, const doub
 }
 // ... and without the Lambda / density kernels
 __attribute__((weak)) int64_t lambda_assemble_ws_doubles(int) { return 1; }
+__attribute__((weak)) bool lambda_assemble_ok(int) { return true; }          // (the stub below refuses by name)
 __attribute__((weak)) void lambda_assemble(const LambdaParts&, int, int, stream_t) {
     throw std::runtime_error("lambda_assemble: not available in this backend");
 }

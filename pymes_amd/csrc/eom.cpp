@@ -3,6 +3,8 @@
 // reference lines.  Pair layouts (ov x ov matrices): Xd[(a,i),(b,j)] = X[a,b,i,j], Xx[(a,j),(b,i)] = X[a,b,i,j].
 #include "eom.h"
 
+#include "../../include/pymes_amd.h"
+
 #include <algorithm>
 #include <cmath>
 #include <initializer_list>
@@ -613,9 +615,17 @@ struct EomSigma::LeftParts {
     }
 };
 
-void EomSigma::left_prepare() {
-    if (left_ready) return;
+// The refusals of the left build that the shape alone decides: before anything is tested, hoisted or allocated
+void EomSigma::left_check() const {
     if (!fused_ok) throw Error("eom sigma apply_left: nocc too large for the fused pair kernels");
+    if (!dev::lambda_assemble_ok(no))
+        throw Error("lambda_assemble: nocc = " + std::to_string(no) + " is too large for the LDS tile (o (o + 1) + 256 doubles in 64 KB: nocc <= " +
+                    std::to_string(PYMES_NOCC_MAX_LAMBDA) + ")");
+}
+
+void EomSigma::left_prepare() {
+    left_check();
+    if (left_ready) return;
     const int64_t o = no, v = nv;
     const Ops q{e};
     if (!eta1) eta1 = keep(v * o);
@@ -689,6 +699,7 @@ void EomSigma::left_partials(const double* l1, const double* l2, LeftParts& w) {
 void EomSigma::apply_left(int k, const double* const* l1, const double* const* l2, const int* sym, double* const* o1,
                           double* const* o2) {
     if (k < 1) return;
+    left_check();
     for (int z = 0; z < k; ++z)
         if (!l1[z] || !l2[z] || !o1[z] || !o2[z]) throw Error("eom sigma apply_left: null vector");
     for (int z = 0; z < k; ++z)            // (refusals first: nothing is allocated for a call that is refused)
@@ -799,6 +810,7 @@ void EomSigma::left_stack(int k, const double* const* l1, const double* const* l
 
 double EomSigma::lambda_step(const double* lam1, const double* lam2, const double* eo_host, const double* ev_host, double shift,
                              double err_scale, bool start, bool known_sym, double* out1, double* out2, double* err1, double* err2) {
+    left_check();
     if (!eo_host || !ev_host || !out1 || !out2 || !err1 || !err2) throw Error("lambda_step: null argument");
     if (!start && (!lam1 || !lam2)) throw Error("lambda_step: null lambda");
     if (!start && !known_sym && !exchange_symmetric(lam2, nv, no))

@@ -64,6 +64,7 @@ class EomSigma {
     double *eta1 = nullptr, *eps_dev = nullptr;
     std::vector<double> eps_host_;
     bool left_ready = false;
+    void left_check() const;
     void left_prepare();
     struct LeftParts;
     void left_partials(const double* l1, const double* l2, LeftParts& w);

@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/pymes_amd.h"      // the PYMES_NOCC_MAX_* limits
 #include "device_api.h"
 #include "diis_small.h"
 
@@ -5430,14 +5431,14 @@ void ladder_pack_V_factors(const double* B, double* Vp, double* Vm, int naux, in
 // below the 2-GB record count of the buffer resources
 bool ladder_dress_ok(int no, int nv) {
     const double ld = (double)((((long)nv * (nv + 1) / 2) + 15) & ~15L);
-    return no >= 1 && no <= 80 && nv >= 1 && 8.0 * ld * (15.0 * nv + 137.0) < 2147483648.0;
+    return no >= 1 && no <= PYMES_NOCC_MAX_BRA_DRESS && nv >= 1 && 8.0 * ld * (15.0 * nv + 137.0) < 2147483648.0;
 }
 
 int64_t ladder_dress_ws_doubles(int no, int nv) { return (int64_t)((nv + 15) / 16) * ((no + 3) / 4) * 64; }
 
 void ladder_dress(const double* V, const double* Pk, const double* t1, double* W, int no, int nv, int64_t ld, int64_t row0,
                   int64_t row1, double sgn, double* ws, stream_t s) {
-    if (!ladder_dress_ok(no, nv)) throw std::runtime_error("ladder_dress: nocc outside 1..80 or tile extents beyond 2 GB");
+    if (!ladder_dress_ok(no, nv)) throw std::runtime_error("ladder_dress: nocc outside 1.." + std::to_string(PYMES_NOCC_MAX_BRA_DRESS) + " or tile extents beyond 2 GB");
     if (ld <= 0 || (ld & 15)) throw std::runtime_error("ladder_dress: the row pitch must be a multiple of 16 doubles");
     if ((reinterpret_cast<uintptr_t>(V) | reinterpret_cast<uintptr_t>(Pk) | reinterpret_cast<uintptr_t>(W)) & 127)
         throw std::runtime_error("ladder_dress: operands must be 128-byte aligned");
@@ -5501,7 +5502,13 @@ void ladder_unpack(const double* L, double* R, double beta, int no, int nv, stre
     launch_kernel(ladder_unpack_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, k);
 }
 
-bool fused_pair_kernels_ok(int no) { return (size_t)no * (no + 1) * sizeof(double) <= 64 * 1024; }
+// (the tile alone: the phase union kernel adds 32 B of static LDS to a task's tile, 65 552 B at no = 90 — within the 160 KB a
+// workgroup may have on gfx950; the 64 KB here is the budget the kernels were written for, not the hardware's limit)
+constexpr size_t kPairTileBudget = 64 * 1024;
+constexpr size_t pair_tile_bytes(size_t no) { return no * (no + 1) * sizeof(double); }
+static_assert(pair_tile_bytes(PYMES_NOCC_MAX_FUSED) <= kPairTileBudget && pair_tile_bytes(PYMES_NOCC_MAX_FUSED + 1) > kPairTileBudget,
+              "PYMES_NOCC_MAX_FUSED is the largest nocc whose tile fits the budget");
+bool fused_pair_kernels_ok(int no) { return no <= PYMES_NOCC_MAX_FUSED; }
 
 void ring_operands(const double* Viabj, const double* Viajb, double* M, double* N1, double a1, double a2, int no, int nv,
                    stream_t s) {
@@ -6850,10 +6857,15 @@ namespace dev {
 
 int64_t lambda_assemble_ws_doubles(int nv) { return (int64_t)nv * (nv + 1) / 2 + 1; }
 
+constexpr size_t lambda_assemble_lds(size_t no) { return sizeof(double) * (no * (no + 1) + 256); }   // the tile, 256 partial sums behind it
+static_assert(lambda_assemble_lds(PYMES_NOCC_MAX_LAMBDA) <= 64 * 1024 && lambda_assemble_lds(PYMES_NOCC_MAX_LAMBDA + 1) > 64 * 1024 &&
+              PYMES_NOCC_MAX_LAMBDA <= PYMES_NOCC_MAX_FUSED, "PYMES_NOCC_MAX_LAMBDA is the largest nocc whose tile and partial sums fit 64 KB");
+bool lambda_assemble_ok(int no) { return no >= 1 && no <= PYMES_NOCC_MAX_LAMBDA; }
+
 void lambda_assemble(const LambdaParts& q, int no, int nv, stream_t s) {
     if (no < 1 || nv < 1) throw std::runtime_error("lambda_assemble: bad shape");
-    const size_t lds = sizeof(double) * ((size_t)no * (no + 1) + 256);      // the tile and the 256 partial sums behind it
-    if (!fused_pair_kernels_ok(no) || lds > 64 * 1024) throw std::runtime_error("lambda_assemble: nocc too large for the LDS tile");
+    const size_t lds = lambda_assemble_lds(no);
+    if (!lambda_assemble_ok(no)) throw std::runtime_error("lambda_assemble: nocc too large for the LDS tile");
     if (!q.out1 || !q.out2) throw std::runtime_error("lambda_assemble: null output");
     if (q.D && (!q.Pd || !q.Px || !q.S1)) throw std::runtime_error("lambda_assemble: incomplete partial results");
     if (!q.D && (q.Pd || q.Px || q.S1 || q.Lp || q.La)) throw std::runtime_error("lambda_assemble: partial results without the direct one");

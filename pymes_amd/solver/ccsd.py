@@ -542,6 +542,9 @@ class CCSD(ccd.CCD):
         # frozen_core / fno_* those of the correlated space; with density=True Lambda is solved once (dyson_r_epsilon=x: the
         # relative residual norm at which the Davidson runs stop, default 1e-8)
         dyson = bool(kwargs.get("dyson", False))
+        if density or ee_roots or dyson:                   # (the left assembly's cap on nocc: before a context exists)
+            from pymes_amd.solver import lambda_ccsd
+            lambda_ccsd.check_occupied(self.no, "EOM_CCSD_Transitions" if ee_roots and not density else "Lambda_CCSD")
         ints, own = self._integrals(t_fock_pq, t_V_pqrs)
         ctx = ints.ctx
         st = None

@@ -87,6 +87,8 @@ class _IPEA_Dyson:
         t_start = time.time()
         from pymes_amd.integral.device import DressedDeviceIntegrals
         from pymes_amd.solver.ccd import quiet_collector
+        if lam is None:                        # Lambda is solved here: its cap on nocc, before a context or a handle exists
+            lambda_ccsd.check_occupied(self.no, self.NAME)
         if isinstance(V_dressed, DressedDeviceIntegrals):
             self.check_context(V_dressed.ctx, lam is not None)
         make = lambda ctx, f, t2, dressed: IPEASigma(ctx, self.KIND, f, t2, dressed)

@@ -28,9 +28,6 @@ from pymes_amd.log import print_logging_info, print_title
 from pymes_amd.mixer.diis import _single_threaded_blas
 from pymes_amd.solver import lambda_ccsd, subspace
 
-LDS_BYTES = 64 * 1024
-
-
 def check_context(ctx, no):
     """The refusals that need no allocation: integral sharding, a launch graph being recorded, an o too large for the LDS tile
     of the left assembly (o (o + 1) + 256 doubles)."""
@@ -43,9 +40,7 @@ def check_context(ctx, no):
 
 
 def check_occupied(no):
-    if 8 * (no * (no + 1) + 256) > LDS_BYTES:
-        raise PymesError("EOM_CCSD_Transitions: nocc = %d is too large for the LDS tile of lambda_assemble (o (o + 1) + 256 doubles "
-                         "in 64 KB)" % no)
+    lambda_ccsd.check_occupied(no, "EOM_CCSD_Transitions")
 
 
 def device_tdm1(ctx, t1, t2, lam1, lam2, l1s, l2s, r1s, r2s):

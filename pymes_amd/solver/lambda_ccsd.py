@@ -31,6 +31,17 @@ from pymes_amd.solver.subspace import open_handle
 ERR_SCALE = 1.0e5
 
 
+NOCC_MAX = 88          # PYMES_NOCC_MAX_LAMBDA (include/pymes_amd.h): o (o + 1) + 256 doubles of LDS in 64 KB
+
+
+def check_occupied(no, name="Lambda_CCSD"):
+    """The left assembly stages an o x (o + 1) tile and 256 partial sums in LDS: refused here, before a context, a handle or a
+    vector exists (the library refuses the same shapes at the head of ``pymes_eom_sigma_apply_left`` / ``pymes_lambda_step``)."""
+    if no > NOCC_MAX:
+        raise PymesError("%s: nocc = %d is too large for the LDS tile of lambda_assemble (o (o + 1) + 256 doubles in 64 KB: "
+                         "nocc <= %d)" % (name, no, NOCC_MAX))
+
+
 def check_context(ctx):
     """The adjoint build reads the whole V_abcd: a context that shards its integrals is refused, by the name of the mode."""
     if getattr(ctx, "shard", None) is not None:
@@ -86,6 +97,7 @@ class Lambda_CCSD:
 
     def apply_left(self, f_dressed, V_dressed, t2, l1, l2):
         """One adjoint build for host arrays: ((A^T l)_1, (A^T l)_2)."""
+        check_occupied(self.no)
         _, ctx, sig, own = open_handle(self.no, self.device, f_dressed, V_dressed, t2, self.BLOCKS, LeftSigma, self.algo_name,
                                        check_context)
         try:
@@ -105,6 +117,7 @@ class Lambda_CCSD:
         "lambda1" [v,o], "lambda2" [v,v,o,o] (host), "residual norm" (|eta + A^T lambda|), "iterations", "converged".
         ``handle = (ctx, LeftSigma)``: iterate on a handle the caller has hoisted from the same (f, V, t2) and keeps (the
         transition solver: one hoist for the right, the Lambda and the left solve); it is not closed here."""
+        check_occupied(self.no)
         print_title("Lambda-CCSD Solver", )
         t_init = time.time()
         if handle is None:

@@ -225,14 +225,26 @@ def _bitsym_V(no, nv, seed):
     return np.ascontiguousarray(V + V.transpose(1, 0, 3, 2))
 
 
+def set_whole_V(ctx, no, nv, seed):
+    """All of a random V_pqrs == V_qpsr (bit for bit) on the context; returns its block V_ijab [o,o,v,v]."""
+    V = _bitsym_V(no, nv, seed)
+    ctx.set_V_pqrs(V)
+    return V[:no, :no, no:, no:]
+
+
 @pytest.mark.parametrize("with_t1", [False, True])
 @pytest.mark.parametrize("with_dt2", [False, True])
 def test_energy_norms(case, with_t1, with_dt2):
+    check_energy_norms(case, with_t1, with_dt2)
+
+
+def check_energy_norms(case, with_t1, with_dt2, set_V=set_whole_V):
+    """``set_V(ctx, no, nv, seed)`` puts the integrals on the context and returns V_ijab (tests/test_gpu_nocc_cap.py uploads
+    that block alone: (no + nv)^4 doubles are 0.6 GB at no = 90)."""
     ctx, no, nv = case
     rng = np.random.default_rng(23 * no + nv)
     n = no + nv
-    V = _bitsym_V(no, nv, 29 * no + nv)
-    ctx.set_V_pqrs(V)
+    Vijab = set_V(ctx, no, nv, 29 * no + nv)
     f = rng.standard_normal((n, n))
     t1 = rng.standard_normal((nv, no))
     T, dT = sym4(rng, no, nv), sym4(rng, no, nv)
@@ -243,8 +255,8 @@ def test_energy_norms(case, with_t1, with_dt2):
     with full_read(ctx):
         old, plain = np.array(ctx.energy_norms(*args, sym=True)), np.array(ctx.energy_norms(*args))
     assert np.array_equal(old, plain)
-    Edir = V[:no, :no, no:, no:].transpose(2, 3, 0, 1)
-    Eex = V[:no, :no, no:, no:].transpose(3, 2, 0, 1)
+    Edir = Vijab.transpose(2, 3, 0, 1)
+    Eex = Vijab.transpose(3, 2, 0, 1)
     tau = T + (np.einsum("ai,bj->abij", t1, t1) if with_t1 else 0.0)
     ref = np.array([2.0 * (f[:no, no:].T * t1).sum() if with_t1 else 0.0, 2.0 * (tau * Edir).sum(), -(tau * Eex).sum(),
                     (T * T).sum(), (dT * dT).sum() if with_dt2 else 0.0, (t1 * t1).sum() if with_t1 else 0.0])

@@ -1,6 +1,6 @@
 // Device abstraction used by the host engine (engine.cpp).
 //
-// Product build: implemented by kernels.hip (hand-written gfx950 kernels).
+// Product build: implemented by kernels.hip, kernels_post.hip and kernels_integrals.hip (hand-written gfx950 kernels).
 // tests/hostsim/ implements the same functions with plain CPU loops so that the
 // HOST logic (contraction planner, CC term sequencing, C-ABI plumbing) can be
 // exercised under `pytest -m "not gpu"`, valgrind and ASan.  The host simulator is

@@ -782,7 +782,7 @@ void Engine::set_V_from_factors(const double* B_host, int naux) {
 }  // namespace pymes
 
 namespace dev {
-// Backends without the factor kernel (the host simulator): the product library's strong definition (kernels.hip) replaces it.
+// Backends without the factor kernel (the host simulator): the product library's strong definition (kernels.hip; kernels_post.hip for the post-CCSD ones) replaces it.
 __attribute__((weak)) void ladder_pack_V_factors(const double*, double*, double*, int, int, int, int64_t, int64_t, stream_t,
                                                  int64_t, int64_t) {
     throw std::runtime_error("ladder_pack_V_factors: not available in this backend");

@@ -39,27 +39,46 @@ def test_library_override(tmp_path):
 
 
 def test_unrecorded_stream_work_goes_through_the_ordered_layer():
-    """kernels.hip defers launches in the phase queue; whatever is not recorded there must launch the queue first.  The ten
-    runtime calls that do so are poisoned below their wrappers (the compiler refuses a bypass); a raw kernel launch cannot be
-    poisoned, so it is looked for here: only phase_flush (the flush itself) and try_launch_kernel may hold one, and nothing
-    above the poison but the wrappers may name a poisoned call."""
-    src = open(os.path.join(ROOT, "pymes_amd", "csrc", "kernels.hip")).read()
-    src = re.sub(r"//[^\n]*|/\*.*?\*/", "", src, flags=re.S)
-    assert not re.search(r"#\s*define\s+hip", src)
-    poisoned = re.findall(r"#pragma GCC poison ([^\n]+)", src)
+    """kernels.hip defers launches in the phase queue; whatever is not recorded there, in any HIP unit, must launch the queue
+    first.  The ten runtime calls that do so are poisoned below their wrappers in launch.h (the compiler refuses a bypass in
+    every unit that includes it); a raw kernel launch cannot be poisoned, so it is looked for here, over launch.h and every
+    unit together: only phase_flush (the flush itself) and try_launch_kernel may hold one, nothing above the poison but the
+    wrappers may name a poisoned call, and no unit names one at all."""
+    csrc = os.path.join(ROOT, "pymes_amd", "csrc")
+
+    def read(name):
+        return re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(csrc, name)).read(), flags=re.S)
+
+    units = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert "kernels.hip" in units
+    others = units + sorted(f for f in os.listdir(csrc) if f.endswith(".h") and f != "launch.h")
+    srcs = {f: read(f) for f in ["launch.h"] + others}
+    for f, src in srcs.items():
+        assert not re.search(r"#\s*define\s+hip", src), f
+    layer = srcs["launch.h"]
+    poisoned = re.findall(r"#pragma GCC poison ([^\n]+)", layer)
     names = " ".join(poisoned).split()
     assert sorted(names) == sorted(["hipMemcpyAsync", "hipMemsetAsync", "hipMemcpy", "hipStreamSynchronize", "hipEventRecord",
                                     "hipStreamWaitEvent", "hipGraphLaunch", "hipStreamBeginCapture", "hipStreamEndCapture",
                                     "hipFree"])
-    above = src[:src.index("#pragma GCC poison")]
+    above = layer[:layer.index("#pragma GCC poison")]
     for name in names:
         assert len(re.findall(r"\b%s\b" % name, above)) == 1, name         # its wrapper
-    # raw launches: split the file at the top-level function headers that may hold one
+        for f in others:
+            assert not re.search(r"\b%s\b" % name, srcs[f]), (f, name)
+            assert "#pragma GCC poison" not in srcs[f], f
+    # every unit is under the poison before it defines anything
+    for f in units:
+        inc = re.search(r'#include "launch\.h"', srcs[f])
+        body = re.search(r"\{", srcs[f])
+        assert inc and body and inc.start() < body.start(), f
+    # raw launches: split each file at the top-level function headers that may hold one
     raw = r"hipLaunchKernelGGL|<<<|hipLaunchKernel\b|hipModuleLaunchKernel|hipExtLaunchKernel"
-    allowed = 0
-    for m in re.finditer(raw, src):
-        head = src[:m.start()]
-        owner = re.findall(r"\n(?:void|hipError_t) (\w+)\([^;{]*\) \{\n", head)[-1]
-        assert owner in ("phase_flush", "try_launch_kernel"), (owner, src[m.start():m.start() + 80])
-        allowed += 1
-    assert allowed == 3
+    owners = []
+    for f, src in srcs.items():
+        for m in re.finditer(raw, src):
+            head = src[:m.start()]
+            found = re.findall(r"\n(?:void|hipError_t) (\w+)\([^;{]*\) \{\n", head)
+            assert found and found[-1] in ("phase_flush", "try_launch_kernel"), (f, found[-1:], src[m.start():m.start() + 80])
+            owners.append((f, found[-1]))
+    assert sorted(owners) == [("kernels.hip", "phase_flush"), ("kernels.hip", "phase_flush"), ("launch.h", "try_launch_kernel")]

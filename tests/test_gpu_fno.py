@@ -271,7 +271,7 @@ def test_two_ranks_one_gpu(gpu_lib):
 
 
 def fno_plan(noa, nv):
-    """fno_plan of kernels.hip (64-wide tiles, 32-wide c chunks, about 1024 blocks): (nt, nchunk, kc_tot, want, nsplit)."""
+    """fno_plan of kernels_post.hip (64-wide tiles, 32-wide c chunks, about 1024 blocks): (nt, nchunk, kc_tot, want, nsplit)."""
     nt, nchunk = -(-nv // 64), -(-nv // 32)
     ntp, kc_tot = nt * (nt + 1) // 2, noa * noa * nchunk
     want = max(1, min(-(-1024 // ntp), kc_tot, 65535))

@@ -1,4 +1,4 @@
-"""GPU: the post-CCSD assembly kernels past one trip of their block loops (csrc/kernels.hip: ipea_correction / _final,
+"""GPU: the post-CCSD assembly kernels past one trip of their block loops (csrc/kernels_post.hip: ipea_correction / _final,
 ipea_diagonals, ipea_pack / _assemble / _unpack, ipea_dyson, lambda_assemble, rdm1_assemble, tdm1_assemble).  Each of them runs one
 block per virtual pair, row or root and strides ``for (e = threadIdx.x; e < extent; e += 256)`` over o^2, nv, no nv or a chunk of
 4096 elements, often with an LDS tile or row between two such loops; the sibling modules compare them with numpy where every such

@@ -1,6 +1,6 @@
 """GPU: the kernels that stage one nocc x (nocc + 1) tile of doubles in LDS, up to the cap on nocc and past it
 (include/pymes_amd.h, PYMES_NOCC_MAX_FUSED = 90 / PYMES_NOCC_MAX_LAMBDA = 88; csrc/kernels.hip: t2_layouts (both template
-forms), t2_layouts_sym, residual_assemble, residual_assemble_pairs, cc_update_sym, lincomb_sym, lambda_assemble).  The sibling
+forms), t2_layouts_sym, residual_assemble, residual_assemble_pairs, cc_update_sym, lincomb_sym; csrc/kernels_post.hip: lambda_assemble).  The sibling
 modules stop at nocc = 32 (test_gpu_sym_tail.py), 23 for Lambda and 40 for IP / EA (test_gpu_loop_edges.py); whole solves reach 50.
 
 Shapes (no, nv), nvirt tiny so that every array is at most 9 x 8100 doubles:

@@ -738,7 +738,7 @@ int pymes_shard_buffer_sizes(pymes_ctx* ctx, int world, int64_t* sizes) {
         if (world < 1) throw pymes::Error("world must be >= 1");
         pymes::Engine& e = E(ctx);
         const int64_t o = e.no, v = e.nv, ov = o * v, npp = v * (v + 1) / 2;
-        auto padded = [&](int64_t n) { return (n + world - 1) / world * world; };
+        auto padded = [&](int64_t n) { int64_t lo, hi; return pymes::chunk(n, 0, world, lo, hi) * world; };
         sizes[0] = sizes[1] = padded(ov) * ov;
         sizes[2] = padded(npp) * o * o;
         sizes[3] = padded(ov) * o * o;

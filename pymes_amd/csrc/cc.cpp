@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <optional>
 #include <vector>
 
 #include "../../include/pymes_amd.h"
@@ -26,10 +27,11 @@ static_assert(Engine::kT1Zero == PYMES_T1_ZERO && Engine::kOwnerTiles == PYMES_O
               "the engine's flag bits are the public ones");
 
 namespace {
-// Row pitch of the pair-packed integrals V^+- (the K-contiguous left operand of the ladder GEMMs): a multiple of 16 doubles,
-// so that every 128-byte piece the LDS-DMA fetches is one cache line (v(v+1)/2 = 20100 is not: two lines per piece).
-inline int64_t lpitch(int64_t n) { return (n + 15) & ~int64_t(15); }
+// `rows` rows of pair-packed integrals V^+- at their pitch (PairDims::lpitch), `cols` of them defined
+inline int64_t lpitch(int64_t n) { return PairDims::lpitch(n); }
 inline TView packed_rows(double* p, int64_t rows, int64_t cols) { return slice(make_view(p, {rows, lpitch(cols)}), 1, 0, cols); }
+// r rows of pitch ld, the first c columns of each
+inline TView pitched(double* p, int64_t r, int64_t c, int64_t ld) { return slice(make_view(p, {r, ld}), 1, 0, c); }
 constexpr int P_klij = 0, P_ijka = 1, P_ijak = 2, P_ijab = 3, P_iajk = 4, P_iajb = 5, P_iabj = 6, P_iabc = 7,
               P_aibc = 11, P_abij = 12, P_abic = 13, P_abci = 14, P_abcd = 15;
 }
@@ -270,115 +272,62 @@ void Engine::pair_layouts_of(const double* t2, bool want_td, bool sym) {
     lay_t2_ = t2;
 }
 
-void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, double* ETx_p, double* L, int rank,
-                           int world, unsigned flags, const double* t1, double* QK, const double* P) {
-    const bool dcd = flags & PYMES_DCD, dressed = flags & PYMES_USE_DRESSED,
-               skip_ladder = flags & (PYMES_SKIP_LADDER | PYMES_SLAB_RINGS_ONLY), skip_rings = flags & PYMES_SLAB_LADDERS_ONLY;
-    const bool quad = !dcd;
-    const int64_t o = no, v = nv, nn = n, ov = o * v;
-    if (world < 1 || rank < 0 || rank >= world) throw Error("residual_slab: bad rank/world");
-    if (L && !skip_ladder) check_shard_rank("residual_slab", rank, world);
-    const double w = quad ? 1.0 : 0.5;
-    TView F = make_view(const_cast<double*>(f), {nn, nn});
-    auto chunk = [&](int64_t rows, int64_t& lo, int64_t& hi) {
-        const int64_t c = (rows + world - 1) / world;
-        lo = std::min<int64_t>(rank * c, rows);
-        hi = std::min<int64_t>(lo + c, rows);
-    };
-    if (L && !skip_ladder) {
-        int64_t r0, r1;
-        chunk(v * (v + 1) / 2, r0, r1);
-        if (t1) {
-            if (!QK) throw Error("residual_slab: QK buffer missing");
-            int64_t q0, q1;
-            chunk(o * v, q0, q1);
-            ladder_t1(t1, t2, L, r0, r1, QK, q0, q1, dcd, P ? P + o * o : nullptr);
-        } else {
-            ladder_sym(t2, L, r0, r1, dressed, quad ? 1 : 2);  // particle AND hole ladder rows of this rank
-        }
+// The three parts of residual_slab.  The ladder half: this rank's rows of the pair-packed ladders (and of QK with t1).
+void Engine::slab_ladders(const double* t2, double* L, int rank, int world, unsigned flags, const double* t1, double* QK,
+                          const double* P) {
+    const bool dcd = flags & PYMES_DCD, dressed = flags & PYMES_USE_DRESSED;
+    const int64_t o = no, v = nv;
+    int64_t r0, r1;
+    chunk(pair_dims().npp, rank, world, r0, r1);
+    if (t1) {
+        if (!QK) throw Error("residual_slab: QK buffer missing");
+        int64_t q0, q1;
+        chunk(o * v, rank, world, q0, q1);
+        ladder_t1(t1, t2, L, r0, r1, QK, q0, q1, dcd, P ? P + o * o : nullptr);
+    } else {
+        ladder_sym(t2, L, r0, r1, dressed, dcd ? 2 : 1);   // particle AND hole ladder rows of this rank
     }
-    if (skip_rings) return;
-    ring_fold_.clear();            // whatever this call writes into ETd / ETx, an earlier folded slab is no longer what they hold
-    int64_t c0, c1;
-    chunk(ov, c0, c1);
-    const int64_t nc = c1 - c0;
-    if (nc <= 0) return;           // a rank without columns never touches (or needs) the dressed ov blocks
-    TView Viajb = block(P_iajb, dressed), Viabj = block(P_iabj, dressed);
+}
 
-    ArenaScope scope(arena);
+// The ring half of a rank that holds some of the columns.
+void Engine::slab_rings_rows(const RingSlab& s) {
+    const int64_t ov = static_cast<int64_t>(no) * nv, c0 = s.c0, c1 = s.c1, nc = c1 - c0;
+    const bool quad = s.quad;
+    const TView &Tx = s.Tx, &Ttd = s.Ttd, &ETd = s.ETd, &ETx = s.ETx;
+    auto pairm = [&](double* p) { return make_view(p, {ov, ov}); };
+    // Several ranks: the slab in its TRANSPOSED form from the start.  MT[(b,j),(c,k)] / N1T hold the rank's columns as
+    // ROWS; Tt_d, Tx, Ld, Vx, Vd are symmetric pair matrices, so
+    //     MT += rows(Tt_d) Ld / 2,  N1T += rows(Tx) Vx / 2,  ET_x = N1T Tx,  ET_d = MT Tt_d / 2 + ET_x / 2
+    // are all products with a K-contiguous left and an N-contiguous right operand — the LDS-DMA variant that runs at 93 %
+    // of peak on one rank (the column form needed the <false,true> variant for its applications: 85.5 % at N = 8,
+    // profiles/r03/stub_rank0_of8.json) — and their outputs ARE the contiguous row blocks of ETd / ETx that are exchanged.
+    auto slabT = [&]() { return make_view(arena.alloc(nc * ov), {nc, ov}); };
+    TView MT = slabT(), N1T = slabT();
+    s.load_rows(2.0, s.Viabj, "kbcj", MT);                                               // MT = (2 Wd)^T
+    s.load_rows(-1.0, s.Viajb, "kbjc", N1T);                                             // N1T = -(UdT)^T
+    axpby(1.0, N1T, 1.0, MT);
+    ring_xd_ = 0.0;
+    auto rowsOf = [&](const TView& m) { return slice(m, 0, c0, c1); };
+    if (quad) {
+        contract(0.5, rowsOf(Ttd), "ny", pairm(get_static("Ld")), "yx", 1.0, MT, "nx");
+        contract(0.5, rowsOf(Tx), "ny", pairm(get_static("Vx")), "yx", 1.0, N1T, "nx");
+    } else {
+        contract(1.0, rowsOf(Ttd), "ny", pairm(get_static("Vd")), "yx", 1.0, MT, "nx");
+    }
+    contract(1.0, N1T, "nk", Tx, "km", 0.0, ETx, "nm");                                  // (Ex_x)^T, rows = this rank's columns
+    contract(0.5, MT, "nk", Ttd, "km", 0.5, ETd, "nm", "", &ETx);                        // (Ex_d)^T
+}
+
+// The ring half of the one rank that holds all columns.
+void Engine::slab_rings_cols(const RingSlab& s) {
+    const int64_t o = no, v = nv, nn = n, ov = o * v, c0 = s.c0, c1 = s.c1, nc = c1 - c0;
+    const bool quad = s.quad, traces = s.traces, fold = s.fold;
+    const double w = quad ? 1.0 : 0.5;
+    const double* t2 = s.t2;
+    const TView &F = s.F, &Viajb = s.Viajb, &Viabj = s.Viabj, &Tx = s.Tx, &Ttd = s.Ttd, &ETd = s.ETd, &ETx = s.ETx;
     auto pairm = [&](double* p) { return make_view(p, {ov, ov}); };
     auto slab = [&]() { return make_view(arena.alloc(ov * nc), {ov, nc}); };
-    // Ring fold (one rank, all columns, the V.T sums as traces of the builds): X_ac and X_ki are complete before the two
-    // applications, and with the sparse pair matrix  Dx[(c,k),(b,j)] = X_bc d_kj - d_cb X_kj
-    //     M -> M + Dx / 2,  N1 -> N1 + Dx / 2     (paired form: M_h = M / 2 -> M_h + Dx / 4)
-    // the assembly Ex_d + Ex_d^T + Ex_x(ajbi) + Ex_x(biaj) gains exactly X_ac T_cbij + X_bc T_acij - X_ki T_abkj - X_kj T_abik
-    // (ccd.py:231-232 after symmetrisation; the unwanted index placements of the two halves cancel, which needs the equal
-    // weights).  v^2 o + v o^2 entries per operand instead of two streaming products over (ov)^2 arrays: no X_ki product,
-    // no Td, and the finish does not form X_ac T (ring_fold_).  tests/test_ring_fold.py pins the identity.
-    const bool traces = !P && nc == ov;      // the small V.T sums as partial traces of the builds (below; one rank only)
-    const bool fold = traces && ring_fold_enabled();
-    pair_layouts_of(t2, !fold, flags & kSymTail);
-    TView Td = pairm(lay_[0]), Tx = pairm(lay_[1]), Ttd = pairm(lay_[2]);
-    TView ETd = slice(pairm(ETd_p), 0, c0, c1), ETx = slice(pairm(ETx_p), 0, c0, c1);
     auto cols = [&](const TView& m) { return slice(m, 1, c0, c1); };
-    // column slabs (b,j) in [c0,c1) of the static / dressed right-hand factors, straight from the 4-index blocks:
-    //   Wd[(c,k),(b,j)] = V_iabj[k,b,c,j],   UdT[(c,k),(b,j)] = V_iajb[k,b,j,c]
-    const int64_t b0 = c0 / o, b1 = (c1 + o - 1) / o;
-    auto load_cols = [&](double alpha, const TView& blk, const char* spec, const TView& dst) {
-        TView src = slice(blk, 1, b0, b1);                       // only the b values the slab touches
-        if (b0 * o == c0 && b1 * o == c1) {
-            permute(alpha, src, spec, 0.0, make_view(dst.p, {v, o, b1 - b0, o}), "ckbj");
-        } else {
-            ArenaScope s2(arena);
-            TView tmp = make_view(arena.alloc(ov * (b1 - b0) * o), {ov, (b1 - b0) * o});
-            permute(alpha, src, spec, 0.0, make_view(tmp.p, {v, o, b1 - b0, o}), "ckbj");
-            copy(slice(tmp, 1, c0 - b0 * o, c1 - b0 * o), dst);
-        }
-    };
-    // ---- the o^3 v^3 terms in four products (three for DCSD).  With pair matrices on (a,i) = a*o + i, all symmetric,
-    //   Wd[(c,k),(b,j)] = V~_iabj[k,b,c,j],  Ud^T[(c,k),(b,j)] = V~_iajb[k,b,j,c],  Ld = 2 Vd - Vx  (L_ldkc = 2 g_ldkc - g_lckd)
-    // the ten ring products of ccd.py:190-191, :199-204, :233-240 are, for V_pqrs = V_qpsr and T_abij = T_baji, exactly
-    //   D-term:  Ex_d  = 1/2 Tt_d (2 Wd - Ud^T + 1/2 Ld Tt_d)            (one build, one application)
-    //   C-term:  Xc    = Tx (Ud^T - 1/2 Vx Tx),   Ex_d -= 1/2 Xc,   Ex_x = -Xc     (one build, ONE application, used in both
-    //            index placements — the (1/2 + P_ij) of the closed-shell CCSD doubles equations in their C / D form)
-    // (numerically identical to the reference's sequence to rounding: tests/test_host_round2.py pins the identity and every
-    // golden solve pins the result).  DCSD keeps ccd.py:202-204 only: 2 Wd - Ud^T + Vd Tt_d in the D-term, no build in the
-    // C-term.  Column slab [c0,c1): both builds are restricted to the rank's columns n, the applications give rows n.
-    const bool row_form = nc != ov;
-    if (row_form) {
-        // Several ranks: the slab in its TRANSPOSED form from the start.  MT[(b,j),(c,k)] / N1T hold the rank's columns as
-        // ROWS; Tt_d, Tx, Ld, Vx, Vd are symmetric pair matrices, so
-        //     MT += rows(Tt_d) Ld / 2,  N1T += rows(Tx) Vx / 2,  ET_x = N1T Tx,  ET_d = MT Tt_d / 2 + ET_x / 2
-        // are all products with a K-contiguous left and an N-contiguous right operand — the LDS-DMA variant that runs at 93 %
-        // of peak on one rank (the column form needed the <false,true> variant for its applications: 85.5 % at N = 8,
-        // profiles/r03/stub_rank0_of8.json) — and their outputs ARE the contiguous row blocks of ETd / ETx that are exchanged.
-        auto slabT = [&]() { return make_view(arena.alloc(nc * ov), {nc, ov}); };
-        TView MT = slabT(), N1T = slabT();
-        auto load_rows = [&](double alpha, const TView& blk, const char* spec, const TView& dst) {
-            TView src = slice(blk, 1, b0, b1);                       // only the b values the slab touches
-            if (b0 * o == c0 && b1 * o == c1) {
-                permute(alpha, src, spec, 0.0, make_view(dst.p, {b1 - b0, o, v, o}), "bjck");
-            } else {
-                ArenaScope s2(arena);
-                TView tmp = make_view(arena.alloc((b1 - b0) * o * ov), {(b1 - b0) * o, ov});
-                permute(alpha, src, spec, 0.0, make_view(tmp.p, {b1 - b0, o, v, o}), "bjck");
-                copy(slice(tmp, 0, c0 - b0 * o, c1 - b0 * o), dst);
-            }
-        };
-        load_rows(2.0, Viabj, "kbcj", MT);                                                   // MT = (2 Wd)^T
-        load_rows(-1.0, Viajb, "kbjc", N1T);                                                 // N1T = -(UdT)^T
-        axpby(1.0, N1T, 1.0, MT);
-        ring_xd_ = 0.0;
-        auto rowsOf = [&](const TView& m) { return slice(m, 0, c0, c1); };
-        if (quad) {
-            contract(0.5, rowsOf(Ttd), "ny", pairm(get_static("Ld")), "yx", 1.0, MT, "nx");
-            contract(0.5, rowsOf(Tx), "ny", pairm(get_static("Vx")), "yx", 1.0, N1T, "nx");
-        } else {
-            contract(1.0, rowsOf(Ttd), "ny", pairm(get_static("Vd")), "yx", 1.0, MT, "nx");
-        }
-        contract(1.0, N1T, "nk", Tx, "km", 0.0, ETx, "nm");                                  // (Ex_x)^T, rows = this rank's columns
-        contract(0.5, MT, "nk", Ttd, "km", 0.5, ETd, "nm", "", &ETx);                        // (Ex_d)^T
-    } else {
     TView M = slab(), N1 = slab();
     // One rank with all columns: the two builds are independent, and so are the two applications once the D-term no longer
     // carries the half of the C-term (Ex_d = D + Ex_x / 2: the assembly reads Ex_x in both placements, `ring_xd_`) — each pair
@@ -389,7 +338,7 @@ void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, dou
     // Only where a single product under-fills the chip (< 512 tiles of 128 x 128): a big product loses nothing on its own,
     // and the assembly's two extra reads of Ex_x (1.6 GB at (50,200)) would be paid for nothing.
     const int64_t ring_tiles = ((ov + 127) / 128) * ((ov + 127) / 128);
-    const bool paired = nc == ov && ring_tiles < 512;
+    const bool paired = ring_tiles < 512;
     ring_xd_ = paired ? 0.5 : 0.0;
     auto pair_gemm = [&](double alpha, const double* A0, const double* A1, const double* B0, const double* B1, double beta,
                          double* C0, double* C1) {
@@ -415,14 +364,14 @@ void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, dou
         for (int i = t.rank - 1; i >= 0; --i) { if (t.st[i] != st) return false; st *= t.dim[i]; }
         return true;
     };
-    if (nc == ov && dense(Viabj) && dense(Viajb) && (size_t)no * 33 * sizeof(double) <= 64 * 1024) {
+    if (dense(Viabj) && dense(Viajb) && (size_t)no * 33 * sizeof(double) <= 64 * 1024) {
         // both operands in one pass over the two blocks (two permutations and an axpby before: 5 reads / 3 writes of (ov)^2)
         dev::ring_operands(Viabj.p, Viajb.p, M.p, N1.p, paired ? 1.0 : 2.0, paired ? 0.5 : 1.0, no, nv, stream);
         stats.permute_calls++;
         stats.permute_bytes += 8.0 * 4.0 * double(ov) * double(ov);
     } else {
-        load_cols(paired ? 1.0 : 2.0, Viabj, "kbcj", M);                                      // M = 2 Wd  (paired: Wd)
-        load_cols(-1.0, Viajb, "kbjc", N1);                                                   // N1 = -UdT
+        s.load_cols(paired ? 1.0 : 2.0, Viabj, "kbcj", M);                                      // M = 2 Wd  (paired: Wd)
+        s.load_cols(-1.0, Viajb, "kbjc", N1);                                                   // N1 = -UdT
         axpby(paired ? 0.5 : 1.0, N1, 1.0, M);                                               // M = 2 Wd - UdT  (paired: half of it)
     }
     // The small V.T sums S_ac = sum_dkl Tt_adkl V_lkdc, S_ki = sum_cdl Tt_cdil V_lkdc (X_ac, X_ki, ccsd.py:434 / :436) are
@@ -465,22 +414,90 @@ void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, dou
         };
         add_Dx(M, paired ? 0.25 : 0.5);
         add_Dx(N1, 0.5);
-        ring_fold_.set(t2, ETd_p);
+        ring_fold_.set(t2, s.ETd_p);
     }
     if (paired) {
         pair_gemm(1.0, Tx.p, Ttd.p, N1.p, M.p, 0.0, ETx.p, ETd.p);                           // Ex_x = -Xc,  D = Tt_d M_h
-    } else if (nc == ov) {
+    } else {
         // all columns on this rank: nothing is exchanged, and since only Ex + Ex^T enters R (residual_assemble) the slab
         // need not be transposed — Ex_x = Tx N1 and Ex_d = Tt_d M / 2 + Ex_x / 2 with the K-contiguous symmetric amplitudes
         // on the left: the same operand layout as the two builds (the LDS-DMA variant with the better L2 reuse: 6.4 GB of
         // fetches per launch against 13.6 GB for the transposed form, profiles/r02/bench_c3_pmc_hbm_traffic.csv)
         contract(1.0, Tx, "mk", N1, "kn", 0.0, ETx, "mn");                                   // Ex_x = -Xc
         contract(0.5, Ttd, "mk", M, "kn", 0.5, ETd, "mn", "", &ETx);                         // Ex_d = D-term - Xc / 2
-    } else {
-        contract(1.0, N1, "kn", Tx, "mk", 0.0, ETx, "nm");                                   // (Ex_x)^T, rows = this rank's columns
-        contract(0.5, M, "kn", Ttd, "mk", 0.5, ETd, "nm", "", &ETx);                         // (Ex_d)^T
     }
-    }
+}
+
+void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, double* ETx_p, double* L, int rank,
+                           int world, unsigned flags, const double* t1, double* QK, const double* P) {
+    const bool dcd = flags & PYMES_DCD, dressed = flags & PYMES_USE_DRESSED,
+               skip_ladder = flags & (PYMES_SKIP_LADDER | PYMES_SLAB_RINGS_ONLY), skip_rings = flags & PYMES_SLAB_LADDERS_ONLY;
+    const bool quad = !dcd;
+    const int64_t o = no, v = nv, nn = n, ov = o * v;
+    if (world < 1 || rank < 0 || rank >= world) throw Error("residual_slab: bad rank/world");
+    if (L && !skip_ladder) check_shard_rank("residual_slab", rank, world);
+    const double w = quad ? 1.0 : 0.5;
+    TView F = make_view(const_cast<double*>(f), {nn, nn});
+    if (L && !skip_ladder) slab_ladders(t2, L, rank, world, flags, t1, QK, P);
+    if (skip_rings) return;
+    ring_fold_.clear();            // whatever this call writes into ETd / ETx, an earlier folded slab is no longer what they hold
+    int64_t c0, c1;
+    chunk(ov, rank, world, c0, c1);
+    const int64_t nc = c1 - c0;
+    if (nc <= 0) return;           // a rank without columns never touches (or needs) the dressed ov blocks
+    TView Viajb = block(P_iajb, dressed), Viabj = block(P_iabj, dressed);
+
+    ArenaScope scope(arena);
+    auto pairm = [&](double* p) { return make_view(p, {ov, ov}); };
+    // Ring fold (one rank, all columns, the V.T sums as traces of the builds): X_ac and X_ki are complete before the two
+    // applications, and with the sparse pair matrix  Dx[(c,k),(b,j)] = X_bc d_kj - d_cb X_kj
+    //     M -> M + Dx / 2,  N1 -> N1 + Dx / 2     (paired form: M_h = M / 2 -> M_h + Dx / 4)
+    // the assembly Ex_d + Ex_d^T + Ex_x(ajbi) + Ex_x(biaj) gains exactly X_ac T_cbij + X_bc T_acij - X_ki T_abkj - X_kj T_abik
+    // (ccd.py:231-232 after symmetrisation; the unwanted index placements of the two halves cancel, which needs the equal
+    // weights).  v^2 o + v o^2 entries per operand instead of two streaming products over (ov)^2 arrays: no X_ki product,
+    // no Td, and the finish does not form X_ac T (ring_fold_).  tests/test_ring_fold.py pins the identity.
+    const bool traces = !P && nc == ov;      // the small V.T sums as partial traces of the builds (below; one rank only)
+    const bool fold = traces && ring_fold_enabled();
+    pair_layouts_of(t2, !fold, flags & kSymTail);
+    TView Td = pairm(lay_[0]), Tx = pairm(lay_[1]), Ttd = pairm(lay_[2]);
+    TView ETd = slice(pairm(ETd_p), 0, c0, c1), ETx = slice(pairm(ETx_p), 0, c0, c1);
+    // column slabs (b,j) in [c0,c1) of the static / dressed right-hand factors, straight from the 4-index blocks:
+    //   Wd[(c,k),(b,j)] = V_iabj[k,b,c,j],   UdT[(c,k),(b,j)] = V_iajb[k,b,j,c]
+    const int64_t b0 = c0 / o, b1 = (c1 + o - 1) / o;
+    auto load_cols = [&](double alpha, const TView& blk, const char* spec, const TView& dst) {
+        TView src = slice(blk, 1, b0, b1);                       // only the b values the slab touches
+        if (b0 * o == c0 && b1 * o == c1) {
+            permute(alpha, src, spec, 0.0, make_view(dst.p, {v, o, b1 - b0, o}), "ckbj");
+        } else {
+            ArenaScope s2(arena);
+            TView tmp = make_view(arena.alloc(ov * (b1 - b0) * o), {ov, (b1 - b0) * o});
+            permute(alpha, src, spec, 0.0, make_view(tmp.p, {v, o, b1 - b0, o}), "ckbj");
+            copy(slice(tmp, 1, c0 - b0 * o, c1 - b0 * o), dst);
+        }
+    };
+    // ---- the o^3 v^3 terms in four products (three for DCSD).  With pair matrices on (a,i) = a*o + i, all symmetric,
+    //   Wd[(c,k),(b,j)] = V~_iabj[k,b,c,j],  Ud^T[(c,k),(b,j)] = V~_iajb[k,b,j,c],  Ld = 2 Vd - Vx  (L_ldkc = 2 g_ldkc - g_lckd)
+    // the ten ring products of ccd.py:190-191, :199-204, :233-240 are, for V_pqrs = V_qpsr and T_abij = T_baji, exactly
+    //   D-term:  Ex_d  = 1/2 Tt_d (2 Wd - Ud^T + 1/2 Ld Tt_d)            (one build, one application)
+    //   C-term:  Xc    = Tx (Ud^T - 1/2 Vx Tx),   Ex_d -= 1/2 Xc,   Ex_x = -Xc     (one build, ONE application, used in both
+    //            index placements — the (1/2 + P_ij) of the closed-shell CCSD doubles equations in their C / D form)
+    // (numerically identical to the reference's sequence to rounding: tests/test_host_round2.py pins the identity and every
+    // golden solve pins the result).  DCSD keeps ccd.py:202-204 only: 2 Wd - Ud^T + Vd Tt_d in the D-term, no build in the
+    // C-term.  Column slab [c0,c1): both builds are restricted to the rank's columns n, the applications give rows n.
+    auto load_rows = [&](double alpha, const TView& blk, const char* spec, const TView& dst) {
+        TView src = slice(blk, 1, b0, b1);                       // only the b values the slab touches
+        if (b0 * o == c0 && b1 * o == c1) {
+            permute(alpha, src, spec, 0.0, make_view(dst.p, {b1 - b0, o, v, o}), "bjck");
+        } else {
+            ArenaScope s2(arena);
+            TView tmp = make_view(arena.alloc((b1 - b0) * o * ov), {(b1 - b0) * o, ov});
+            permute(alpha, src, spec, 0.0, make_view(tmp.p, {b1 - b0, o, v, o}), "bjck");
+            copy(slice(tmp, 0, c0 - b0 * o, c1 - b0 * o), dst);
+        }
+    };
+    const RingSlab rs{t2, ETd_p, quad, traces, fold, c0, c1, F, Viajb, Viabj, Tx, Ttd, ETd, ETx, load_cols, load_rows};
+    if (nc != ov) slab_rings_rows(rs);
+    else slab_rings_cols(rs);
     if (!fold) {
         // :232  Ex[a,b,i,j] -= X_ki T[a,b,k,j]  ->  ET[(b,j),(a,i)] -= sum_k Td[(b,j),(a,k)] X_ki   (Td symmetric)
         ArenaScope s2(arena);
@@ -506,15 +523,14 @@ void Engine::residual_slab(const double* f, const double* t2, double* ETd_p, dou
 //   P = [ X'_ki = w sum_{cdl} Tt[c,d,i,l] V[l,k,d,c]  (o x o;  c in the rank's chunk)
 //       | Jp, Jm = 2 V_klcd T_cdij pair-packed       (opp x ldp, opp x ldm;  pairs (c,d) in the rank's chunk) ]
 int64_t Engine::slab_prepare_ws_doubles() const {
-    const int64_t o = no, opp = o * (o + 1) / 2, opm = o * (o - 1) / 2;
-    const int64_t ldp = opp + (opp & 1), ldm = std::max<int64_t>(opm + (opm & 1), 2);
-    return o * o + opp * ldp + opp * ldm;
+    const PairDims d = pair_dims();
+    return static_cast<int64_t>(no) * no + d.opp * d.ldp + d.opp * d.ldm;
 }
 
 void Engine::slab_prepare(const double* t2, double* P, int rank, int world, unsigned flags) {
     const bool dcd = flags & PYMES_DCD;
-    const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opp = o * (o + 1) / 2, opm = o * (o - 1) / 2;
-    const int64_t ldp = opp + (opp & 1), ldm = std::max<int64_t>(opm + (opm & 1), 2);
+    const PairDims d = pair_dims();
+    const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm, ldp = d.ldp, ldm = d.ldm;
     if (world < 1 || rank < 0 || rank >= world) throw Error("slab_prepare: bad rank/world");
     dev::memset_zero(P, sizeof(double) * slab_prepare_ws_doubles(), stream);
     TView T = make_view(const_cast<double*>(t2), {v, v, o, o});
@@ -523,7 +539,8 @@ void Engine::slab_prepare(const double* t2, double* P, int rank, int world, unsi
     xs_oo_tag_.clear();
     {
         // X'_ki over c in [c0,c1)
-        const int64_t cc = (v + world - 1) / world, c0 = std::min<int64_t>(rank * cc, v), c1 = std::min<int64_t>(c0 + cc, v);
+        int64_t c0, c1;
+        chunk(v, rank, world, c0, c1);
         if (c1 > c0) {
             ArenaScope s2(arena);
             TView Tc = slice(T, 0, c0, c1);                                       // T[c,d,i,l]
@@ -538,30 +555,20 @@ void Engine::slab_prepare(const double* t2, double* P, int rank, int world, unsi
         }
         xs_oo_tag_.set(t2, rank, world);       // this rank's partial sum: the singles residual takes ccsd.py:434 from it
     }
-    if (!static_.count("VpIjab")) {
-        double* vp = new_static("VpIjab", opp * lpitch(npp));
-        double* vm = new_static("VmIjab", opp * lpitch(std::max<int64_t>(npm, 1)));
-        dev::ladder_pack_V(block(P_ijab).p, vp, vm, no, nv, 0, opp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
-    }
+    const PackedV Vij = ijab_pack();
     {
         // J over the packed pairs P(c,d) in the rank's chunk (Q(c,d) for the antisymmetric part)
         double* Sp = arena.alloc(npp * ldp);
         double* Am = arena.alloc(std::max<int64_t>(npm * ldm, 1));
         dev::ladder_pack_T(t2, nullptr, Sp, Am, no, nv, dev::PACK_ROW_HALF, ldp, ldm, stream);
-        auto pitched = [&](double* p, int64_t r, int64_t c, int64_t ld) { return slice(make_view(p, {r, ld}), 1, 0, c); };
-        auto cut = [&](int64_t n, int64_t& k0, int64_t& k1) {
-            const int64_t c = (n + world - 1) / world;
-            k0 = std::min<int64_t>(rank * c, n);
-            k1 = std::min<int64_t>(k0 + c, n);
-        };
         int64_t k0, k1;
-        cut(npp, k0, k1);
+        chunk(npp, rank, world, k0, k1);
         if (k1 > k0)
-            contract(2.0, slice(packed_rows(static_["VpIjab"], opp, npp), 1, k0, k1), "rk",
+            contract(2.0, slice(packed_rows(Vij.Vp, opp, npp), 1, k0, k1), "rk",
                      slice(pitched(Sp, npp, opp, ldp), 0, k0, k1), "kn", 0.0, pitched(P + o * o, opp, opp, ldp), "rn");
-        cut(npm, k0, k1);
+        chunk(npm, rank, world, k0, k1);
         if (opm > 0 && k1 > k0)
-            contract(2.0, slice(packed_rows(static_["VmIjab"], opp, npm), 1, k0, k1), "rk",
+            contract(2.0, slice(packed_rows(Vij.Vm, opp, npm), 1, k0, k1), "rk",
                      slice(pitched(Am, npm, opm, ldm), 0, k0, k1), "kn", 0.0, pitched(P + o * o + opp * ldp, opp, opm, ldm), "rn");
     }
 }
@@ -703,9 +710,7 @@ void Engine::amplitude_side_abij(const double* t1, const double* QK, const TView
 
 void Engine::pair_chunk(int rank, int world, int64_t& r0, int64_t& r1) const {
     if (world < 1 || rank < 0 || rank >= world) throw Error("pair_chunk: bad rank/world");
-    const int64_t npp = static_cast<int64_t>(nv) * (nv + 1) / 2, c = (npp + world - 1) / world;
-    r0 = std::min<int64_t>(rank * c, npp);
-    r1 = std::min<int64_t>(r0 + c, npp);
+    chunk(pair_dims().npp, rank, world, r0, r1);
 }
 
 static int a_of_pair_row(int64_t r) {
@@ -813,37 +818,60 @@ void Engine::ladder(const double* t2, double* r2, int a0, int a1, bool dressed, 
     contract(1.0, Vs, "abcd", T, "cdij", beta, R, "abij");                                   // ccd.py:187
 }
 
+bool Engine::ensure_ladder_pack(int64_t row0, int64_t row1, bool dressed) {
+    if (lpack_.valid && lpack_.dressed == dressed && lpack_.row0 == row0 && lpack_.row1 == row1) return false;
+    const PairDims d = pair_dims();
+    const int64_t rows = row1 - row0;
+    if (!lpack_.Vp || lpack_.row1 - lpack_.row0 != rows) {
+        dev::stream_sync(stream);
+        dev::dfree(lpack_.Vp);
+        dev::dfree(lpack_.Vm);
+        lpack_.Vp = lpack_.Vm = nullptr;
+        lpack_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * d.vlp));
+        lpack_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * d.vlm));
+    }
+    dev::ladder_pack_V(block(P_abcd, dressed).p, lpack_.Vp, lpack_.Vm, nv, nv, row0, row1, stream, d.vlp, d.vlm);
+    lpack_.row0 = row0; lpack_.row1 = row1; lpack_.dressed = dressed; lpack_.valid = true;
+    return true;
+}
+
+Engine::PackedV Engine::ladder_rows(const char* who, int64_t row0, int64_t row1, bool dressed) {
+    if (shard_on_) {
+        check_shard_rows(who, row0, row1, dressed);
+        return {srows_.Vp, srows_.Vm, false};
+    }
+    const bool packed = ensure_ladder_pack(row0, row1, dressed);
+    return {lpack_.Vp, lpack_.Vm, packed};
+}
+
+Engine::PackedV Engine::ijab_pack() {
+    const bool packed = !static_.count("VpIjab");
+    if (packed) {
+        const PairDims d = pair_dims();
+        double* vp = new_static("VpIjab", d.opp * d.vlp);
+        double* vm = new_static("VmIjab", d.opp * d.vlm);
+        dev::ladder_pack_V(block(P_ijab).p, vp, vm, no, nv, 0, d.opp, stream, d.vlp, d.vlm);
+    }
+    return {static_["VpIjab"], static_["VmIjab"], packed};
+}
+
 // Pair-packed ladder.  With V_abcd = V_badc (electron exchange) and T_cdij = T_dcji:
 //   L_abij = LS_(ab)(ij) + sgn(a-b) sgn(i-j) LA_(ab)(ij),
 //   LS = sum_{c>=d} (V_abcd + V_abdc) f_cd (T_cdij + T_dcij)/2,   LA = sum_{c>d} (V_abcd - V_abdc) (T_cdij - T_dcij)/2
 // for a >= b, i >= j only: two GEMMs of v(v+1)/2 x v(v+-1)/2 x o(o+-1)/2 = 1/4 of the flops of ccd.py:187.
 void Engine::ladder_sym(const double* t2, double* L, int64_t row0, int64_t row1, bool dressed, int hole) {
-    const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opp = o * (o + 1) / 2,
-                  opm = o * (o - 1) / 2;
+    const PairDims d = pair_dims();
+    const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm, ldp = d.ldp, ldm = d.ldm;
     if (row0 < 0 || row1 > npp || row0 > row1) throw Error("ladder_sym: bad pair-row range");
     if (hole < 0 || hole > 2) throw Error("ladder_sym: hole must be 0, 1 (CCSD) or 2 (DCSD)");
     if (row0 == row1) return;
     const int64_t rows = row1 - row0;
-    if (shard_on_) check_shard_rows("ladder_sym", row0, row1, dressed);
-    else if (!(lpack_.valid && lpack_.dressed == dressed && lpack_.row0 == row0 && lpack_.row1 == row1)) {
-        if (!lpack_.Vp || lpack_.row1 - lpack_.row0 != rows) {
-            dev::stream_sync(stream);
-            dev::dfree(lpack_.Vp);
-            dev::dfree(lpack_.Vm);
-            lpack_.Vp = lpack_.Vm = nullptr;
-            lpack_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * lpitch(npp)));
-            lpack_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * lpitch(std::max<int64_t>(npm, 1))));
-        }
-        dev::ladder_pack_V(block(P_abcd, dressed).p, lpack_.Vp, lpack_.Vm, nv, nv, row0, row1, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
+    const PackedV V = ladder_rows("ladder_sym", row0, row1, dressed);
+    if (V.packed) {
         stats.permute_calls++;
         stats.permute_bytes += 8.0 * 2.0 * double(rows) * double(v * v);
-        lpack_.row0 = row0; lpack_.row1 = row1; lpack_.dressed = dressed; lpack_.valid = true;
     }
     ArenaScope scope(arena);
-    // even pitches (zero pad column / pad row where the pair index is a GEMM K index): every operand qualifies for
-    // 16-byte loads and the LDS-DMA kernel also when o(o+1)/2 is odd — (30,120): 465, (50,200): 1275
-    const int64_t ldp = opp + (opp & 1), ldm = std::max<int64_t>(opm + (opm & 1), 2);
-    auto pitched = [&](double* p, int64_t r, int64_t c, int64_t ld) { return slice(make_view(p, {r, ld}), 1, 0, c); };
     double* Sp = arena.alloc(npp * ldp);
     double* Am = arena.alloc(std::max<int64_t>(npm * ldm, 1));
     dev::ladder_pack_T(t2, nullptr, Sp, Am, no, nv, dev::PACK_ROW_HALF, ldp, ldm, stream);
@@ -852,50 +880,17 @@ void Engine::ladder_sym(const double* t2, double* L, int64_t row0, int64_t row1,
     // L rows [row0,row1): [ LS (opp) | LA (opm) ], row length o*o
     TView Lrows = make_view(L + row0 * o * o, {rows, o * o});
     TView LS = slice(Lrows, 1, 0, opp), LA = slice(Lrows, 1, opp, o * o);
-    TView SpT = pitched(Sp, npp, opp, ldp), AmT = pitched(Am, npm, opm, ldm);
-    double* Vp = shard_on_ ? srows_.Vp : lpack_.Vp;        // integral sharding: the stored rows are the only copy
-    double* Vm = shard_on_ ? srows_.Vm : lpack_.Vm;
-    contract(1.0, packed_rows(Vp, rows, npp), "rk", SpT, "kn", 0.0, LS, "rn");
+    contract(1.0, packed_rows(V.Vp, rows, npp), "rk", pitched(Sp, npp, opp, ldp), "kn", 0.0, LS, "rn");
     if (opm > 0) {
-        if (npm > 0) contract(1.0, packed_rows(Vm, rows, npm), "rk", AmT, "kn", 0.0, LA, "rn");
+        if (npm > 0) contract(1.0, packed_rows(V.Vm, rows, npm), "rk", pitched(Am, npm, opm, ldm), "kn", 0.0, LA, "rn");
         else zero(LA);
     }
     if (!hole) return;
-    // ---- hole ladder (ccd.py:175-186) in the same pair-packed rows:  HL_abij = sum_kl I_klij T_abkl,
-    // I = V~_klij (+ sum_cd V_klcd T_cdij for CCSD).  I_klij = I_lkji, so with S/A = (T_abkl +- T_bakl)/2:
-    //   HLS[(a>=b),(i>=j)] = sum_{k>=l} g_kl S_abkl (I_klij + I_lkij),  HLA[(a>b),(i>j)] = sum_{k>l} A_abkl (I_klij - I_lkij)
-    // and (I_klij +- I_lkij)/2 = pack(V~_klij) + sum_{c>=d} (V_klcd +- V_kldc) (f_cd S | A)_cdij.
-    double* Ip = arena.alloc(ldp * ldp);
-    double* Im = arena.alloc(ldp * ldm);
-    if (ldp > opp) {
-        dev::memset_zero(Ip + opp * ldp, sizeof(double) * ldp, stream);
-        dev::memset_zero(Im + opp * ldm, sizeof(double) * ldm, stream);
-    }
-    dev::ladder_pack_T(block(P_klij, dressed).p, nullptr, Ip, Im, no, no, dev::PACK_AM_PROWS, ldp, ldm, stream);
-    TView Ipv = pitched(Ip, opp, opp, ldp), Imv = pitched(Im, opp, opm, ldm);        // the defined part
-    TView IpK = pitched(Ip, ldp, opp, ldp), ImK = pitched(Im, ldp, opm, ldm);        // with the zero pad row
-    if (hole == 1) {
-        if (!static_.count("VpIjab")) {      // static per solve: dressed ijab == undressed ijab
-            double* vp = new_static("VpIjab", opp * lpitch(npp));
-            double* vm = new_static("VmIjab", opp * lpitch(std::max<int64_t>(npm, 1)));
-            dev::ladder_pack_V(block(P_ijab).p, vp, vm, no, nv, 0, opp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
-        }
-        contract(2.0, packed_rows(static_["VpIjab"], opp, npp), "rk", SpT, "kn", 2.0, Ipv, "rn");
-        if (opm > 0 && npm > 0) contract(2.0, packed_rows(static_["VmIjab"], opp, npm), "rk", AmT, "kn", 2.0, Imv, "rn");
-        else if (opm > 0) axpby(2.0, Imv, 0.0, Imv);
-    } else {
-        axpby(2.0, Ipv, 0.0, Ipv);
-        if (opm > 0) axpby(2.0, Imv, 0.0, Imv);
-    }
-    double* SpR = arena.alloc(npp * ldp);
-    double* AmR = arena.alloc(npp * ldp);
-    dev::ladder_pack_T(t2, nullptr, SpR, AmR, no, nv, dev::PACK_COL_HALF | dev::PACK_AM_PROWS | dev::PACK_AM_PCOLS, ldp, ldp, stream,
-                       row0, row1);                   // only the rows this call multiplies
+    // the hole ladder (ccd.py:175-186) in the same rows: I = V~_klij (+ sum_cd V_klcd T_cdij for CCSD, from the halves of T
+    // packed above)
+    hole_ladder_rows(t2, block(P_klij, dressed).p, L, row0, row1, nullptr, hole == 1 ? Sp : nullptr, hole == 1 ? Am : nullptr);
     stats.permute_calls += 2;
     stats.permute_bytes += 8.0 * 2.0 * double(v * v * o * o);
-    // the (k,l) pair is the GEMM K index: it runs over the padded pitch (zero pad column in the rows of T, zero pad row in I)
-    contract(1.0, slice(make_view(SpR, {npp, ldp}), 0, row0, row1), "rk", IpK, "kn", 1.0, LS, "rn");
-    if (opm > 0) contract(1.0, slice(make_view(AmR, {npp, ldp}), 0, row0, row1), "rk", ImK, "kn", 1.0, LA, "rn");
 }
 
 // The particle ladder (ladder_sym without the hole part) for k vectors in ONE batched launch per half: the packed
@@ -904,25 +899,14 @@ void Engine::ladder_sym(const double* t2, double* L, int64_t row0, int64_t row1,
 // vector is 228 tiles on 256 CUs, k vectors are k x 228 tiles with a k-split tail.
 void Engine::ladder_sym_multi(const double* const* xs, int k, double* L_all, bool dressed) {
     refuse_if_sharded("ladder_sym_multi");
-    const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opp = o * (o + 1) / 2,
-                  opm = o * (o - 1) / 2;
+    const PairDims d = pair_dims();
+    const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm, ldp = d.ldp, ldm = d.ldm;
     if (k < 1) return;
-    if (!(lpack_.valid && lpack_.dressed == dressed && lpack_.row0 == 0 && lpack_.row1 == npp)) {
-        if (!lpack_.Vp || lpack_.row1 - lpack_.row0 != npp) {
-            dev::stream_sync(stream);
-            dev::dfree(lpack_.Vp);
-            dev::dfree(lpack_.Vm);
-            lpack_.Vp = lpack_.Vm = nullptr;
-            lpack_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * npp * lpitch(npp)));
-            lpack_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * npp * lpitch(std::max<int64_t>(npm, 1))));
-        }
-        dev::ladder_pack_V(block(P_abcd, dressed).p, lpack_.Vp, lpack_.Vm, nv, nv, 0, npp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
+    if (ensure_ladder_pack(0, npp, dressed)) {
         stats.permute_calls++;
         stats.permute_bytes += 8.0 * 2.0 * double(npp) * double(v * v);
-        lpack_.row0 = 0; lpack_.row1 = npp; lpack_.dressed = dressed; lpack_.valid = true;
     }
     ArenaScope scope(arena);
-    const int64_t ldp = opp + (opp & 1), ldm = std::max<int64_t>(opm + (opm & 1), 2);
     const int64_t sp_sz = npp * ldp, am_sz = std::max<int64_t>(npm * ldm, 2);
     double* Sp = arena.alloc(k * sp_sz);
     double* Am = arena.alloc(k * am_sz);
@@ -947,24 +931,13 @@ void Engine::ladder_sym_multi(const double* const* xs, int k, double* L_all, boo
 
 void Engine::ladder_sym_adjoint(const double* x, double* LSp, double* LAp, bool dressed) {
     refuse_if_sharded("ladder_sym_adjoint");
-    const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opp = o * (o + 1) / 2,
-                  opm = o * (o - 1) / 2;
-    if (!(lpack_.valid && lpack_.dressed == dressed && lpack_.row0 == 0 && lpack_.row1 == npp)) {
-        if (!lpack_.Vp || lpack_.row1 - lpack_.row0 != npp) {
-            dev::stream_sync(stream);
-            dev::dfree(lpack_.Vp);
-            dev::dfree(lpack_.Vm);
-            lpack_.Vp = lpack_.Vm = nullptr;
-            lpack_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * npp * lpitch(npp)));
-            lpack_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * npp * lpitch(std::max<int64_t>(npm, 1))));
-        }
-        dev::ladder_pack_V(block(P_abcd, dressed).p, lpack_.Vp, lpack_.Vm, nv, nv, 0, npp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
+    const PairDims d = pair_dims();
+    const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm, ldp = d.ldp, ldm = d.ldm;
+    if (ensure_ladder_pack(0, npp, dressed)) {
         stats.permute_calls++;
         stats.permute_bytes += 8.0 * 2.0 * double(npp) * double(v * v);
-        lpack_.row0 = 0; lpack_.row1 = npp; lpack_.dressed = dressed; lpack_.valid = true;
     }
     ArenaScope scope(arena);
-    const int64_t ldp = opp + (opp & 1), ldm = std::max<int64_t>(opm + (opm & 1), 2);
     // the summed pair (a,b) is the ROW index of V+ / V-: the antisymmetric half of x is packed by the same pairs P(a,b)
     // (PACK_AM_PROWS; the rows of diagonal pairs are zero, as the rows of V- are)
     double* Sp = arena.alloc(npp * ldp);
@@ -972,7 +945,6 @@ void Engine::ladder_sym_adjoint(const double* x, double* LSp, double* LAp, bool 
     dev::ladder_pack_T(x, nullptr, Sp, Am, no, nv, dev::PACK_ROW_HALF | dev::PACK_AM_PROWS, ldp, ldm, stream);
     stats.permute_calls++;
     stats.permute_bytes += 8.0 * 2.0 * double(v * v * o * o);
-    auto pitched = [&](double* p, int64_t r, int64_t c, int64_t ld) { return slice(make_view(p, {r, ld}), 1, 0, c); };
     contract(1.0, packed_rows(lpack_.Vp, npp, npp), "kr", pitched(Sp, npp, opp, ldp), "kn", 0.0,
              slice(make_view(LSp, {npp, o * o}), 1, 0, opp), "rn");
     if (opm > 0 && npm > 0)
@@ -982,23 +954,13 @@ void Engine::ladder_sym_adjoint(const double* x, double* LSp, double* LAp, bool 
 void Engine::ladder_sym_adjoint_multi(const double* const* xs, int k, double* LSp, double* LAp, bool dressed) {
     refuse_if_sharded("ladder_sym_adjoint_multi");
     if (k < 1) return;
-    const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opm = o * (o - 1) / 2, K = k;
-    if (!(lpack_.valid && lpack_.dressed == dressed && lpack_.row0 == 0 && lpack_.row1 == npp)) {
-        if (!lpack_.Vp || lpack_.row1 - lpack_.row0 != npp) {
-            dev::stream_sync(stream);
-            dev::dfree(lpack_.Vp);
-            dev::dfree(lpack_.Vm);
-            lpack_.Vp = lpack_.Vm = nullptr;
-            lpack_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * npp * lpitch(npp)));
-            lpack_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * npp * lpitch(std::max<int64_t>(npm, 1))));
-        }
-        dev::ladder_pack_V(block(P_abcd, dressed).p, lpack_.Vp, lpack_.Vm, nv, nv, 0, npp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
+    const PairDims d = pair_dims();
+    const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opm = d.opm, ldp = d.adj_ldp, ldm = d.adj_ldm, K = k;
+    if (ensure_ladder_pack(0, npp, dressed)) {
         stats.permute_calls++;
         stats.permute_bytes += 8.0 * 2.0 * double(npp) * double(v * v);
-        lpack_.row0 = 0; lpack_.row1 = npp; lpack_.dressed = dressed; lpack_.valid = true;
     }
     ArenaScope scope(arena);
-    const int64_t ldp = ladder_adjoint_pitch(true), ldm = ladder_adjoint_pitch(false);
     // the packed halves of vector z in the columns [z ld, (z + 1) ld) of rows of pitch k ld (the pad columns zeroed: they go
     // through the product as columns of their own)
     double* Sp = arena.alloc(npp * K * ldp);
@@ -1016,56 +978,84 @@ void Engine::ladder_sym_adjoint_multi(const double* const* xs, int k, double* LS
                  make_view(LAp, {npm, K * ldm}), "rn");
 }
 
+// ---- the hole-ladder steps.  HL_abij = sum_kl I_klij X_abkl for I_klij = I_lkji, X_abkl = X_balk, in the pair-packed rows:
+// with S/A = (X_abkl +- X_bakl)/2
+//   HLS[(a>=b),(i>=j)] = sum_{k>=l} g_kl S_abkl (I_klij + I_lkij),  HLA[(a>b),(i>j)] = sum_{k>l} A_abkl (I_klij - I_lkij)
+// and, where I carries a V.T part, (I_klij +- I_lkij)/2 = pack(I) + sum_{c>=d} (V_klcd +- V_kldc) (f_cd S | A)_cdij.
+void Engine::hole_operand_pack(const double* I, const HoleOperand& h) {
+    const PairDims d = pair_dims();
+    if (d.ldp > d.opp) {       // the zero pad row of the K range
+        dev::memset_zero(h.Ip + d.opp * d.ldp, sizeof(double) * d.ldp, stream);
+        dev::memset_zero(h.Im + d.opp * d.ldm, sizeof(double) * d.ldm, stream);
+    }
+    dev::ladder_pack_T(I, nullptr, h.Ip, h.Im, no, no, dev::PACK_AM_PROWS, d.ldp, d.ldm, stream);
+}
+
+Engine::HoleOperand Engine::hole_operand(const double* I) {
+    const PairDims d = pair_dims();
+    HoleOperand h;
+    h.Ip = arena.alloc(d.ldp * d.ldp);
+    h.Im = arena.alloc(d.ldp * d.ldm);
+    hole_operand_pack(I, h);
+    return h;
+}
+
+void Engine::hole_operand_add(const HoleOperand& h, const double* Sp, const double* Am, double beta, bool grouped) {
+    const PairDims d = pair_dims();
+    TView Ipv = pitched(h.Ip, d.opp, d.opp, d.ldp), Imv = pitched(h.Im, d.opp, d.opm, d.ldm);        // the defined part
+    if (!Sp) {
+        axpby(2.0, Ipv, 0.0, Ipv);
+        if (d.opm > 0) axpby(2.0, Imv, 0.0, Imv);
+        return;
+    }
+    // [opp x npp] . [npp x opp] instead of the o^2 x v^2 x o^2 product of ccd.py:180
+    const PackedV V = ijab_pack();
+    std::optional<GemmGroupScope> grp;
+    if (grouped) grp.emplace(stream);
+    contract(2.0, packed_rows(V.Vp, d.opp, d.npp), "rk", pitched(const_cast<double*>(Sp), d.npp, d.opp, d.ldp), "kn", beta, Ipv, "rn");
+    if (d.opm > 0 && d.npm > 0)
+        contract(2.0, packed_rows(V.Vm, d.opp, d.npm), "rk", pitched(const_cast<double*>(Am), d.npm, d.opm, d.ldm), "kn", beta, Imv, "rn");
+    if (grp) grp->close();
+    if (d.opm > 0 && d.npm <= 0 && beta != 1.0) axpby(beta, Imv, 0.0, Imv);       // nv = 1: no (c,d) pair in the A half
+}
+
+void Engine::hole_ladder_rows(const double* x, const double* I, double* L, int64_t row0, int64_t row1, const double* y,
+                              const double* ySp, const double* yAm) {
+    const PairDims d = pair_dims();
+    const int64_t o = no, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm, ldp = d.ldp, ldm = d.ldm;
+    TView Lrows = make_view(L + row0 * o * o, {row1 - row0, o * o});
+    TView LS = slice(Lrows, 1, 0, opp), LA = slice(Lrows, 1, opp, o * o);
+    const HoleOperand h = hole_operand(I);
+    if (y) {
+        ijab_pack();           // (a first use packs V_klcd ahead of y)
+        ArenaScope s2(arena);
+        double* Sp = arena.alloc(npp * ldp);
+        double* Am = arena.alloc(std::max<int64_t>(npm * ldm, 1));
+        dev::ladder_pack_T(y, nullptr, Sp, Am, no, nv, dev::PACK_ROW_HALF, ldp, ldm, stream);
+        hole_operand_add(h, Sp, Am, 2.0);
+    } else {
+        hole_operand_add(h, ySp, yAm, 2.0);
+    }
+    double* SpR = arena.alloc(npp * ldp);
+    double* AmR = arena.alloc(npp * ldp);
+    dev::ladder_pack_T(x, nullptr, SpR, AmR, no, nv, dev::PACK_COL_HALF | dev::PACK_AM_PROWS | dev::PACK_AM_PCOLS, ldp, ldp, stream,
+                       row0, row1);                   // only the rows this call multiplies
+    // the (k,l) pair is the GEMM K index: it runs over the padded pitch (zero pad column in the rows of x, zero pad row in I)
+    contract(1.0, slice(make_view(SpR, {npp, ldp}), 0, row0, row1), "rk", pitched(h.Ip, ldp, opp, ldp), "kn", 1.0, LS, "rn");
+    if (opm > 0) contract(1.0, slice(make_view(AmR, {npp, ldp}), 0, row0, row1), "rk", pitched(h.Im, ldp, opm, ldm), "kn", 1.0, LA, "rn");
+}
+
 // A hole-ladder-shaped term sum_kl I_klij X_abkl in the pair-packed rows of L (added to what the rows hold), for
 // I_klij = I_lkji and X_abkl = X_balk: the (k,l) part of ladder_sym for a caller-supplied I (EOM-CCSD: eom_ccsd.py:380-382
 // — u2 against V_klij + V_klcd T_cdij, T against V_kldc u2_dcij), 1/4 of the flops of the plain v^2 o^4 product.  With y
 // (exchange-symmetric, [v,v,o,o]) the term sum_cd V_klcd y_cdij is added to I on the way, pair-packed too.
 void Engine::hole_ladder_packed(const double* x, const double* I, double* L, int64_t row0, int64_t row1, const double* y) {
-    const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opp = o * (o + 1) / 2, opm = o * (o - 1) / 2;
-    if (row0 < 0 || row1 > npp || row0 > row1) throw Error("hole_ladder_packed: bad pair-row range");
+    if (row0 < 0 || row1 > pair_dims().npp || row0 > row1) throw Error("hole_ladder_packed: bad pair-row range");
     if (row0 == row1) return;
-    const int64_t rows = row1 - row0;
-    const int64_t ldp = opp + (opp & 1), ldm = std::max<int64_t>(opm + (opm & 1), 2);
     ArenaScope scope(arena);
-    auto pitched = [&](double* p, int64_t r, int64_t c, int64_t ld) { return slice(make_view(p, {r, ld}), 1, 0, c); };
-    TView Lrows = make_view(L + row0 * o * o, {rows, o * o});
-    TView LS = slice(Lrows, 1, 0, opp), LA = slice(Lrows, 1, opp, o * o);
-    double* Ip = arena.alloc(ldp * ldp);
-    double* Im = arena.alloc(ldp * ldm);
-    if (ldp > opp) {
-        dev::memset_zero(Ip + opp * ldp, sizeof(double) * ldp, stream);
-        dev::memset_zero(Im + opp * ldm, sizeof(double) * ldm, stream);
-    }
-    dev::ladder_pack_T(I, nullptr, Ip, Im, no, no, dev::PACK_AM_PROWS, ldp, ldm, stream);
-    TView Ipv = pitched(Ip, opp, opp, ldp), Imv = pitched(Im, opp, opm, ldm);
-    if (y) {
-        // I += sum_cd V_klcd y_cdij, formed pair-packed as well (the V.T part of the CCSD hole ladder, ccd.py:180, with y
-        // in the place of T): [opp x npp] . [npp x opp] instead of the o^2 x v^2 x o^2 product
-        if (!static_.count("VpIjab")) {
-            double* vp = new_static("VpIjab", opp * lpitch(npp));
-            double* vm = new_static("VmIjab", opp * lpitch(std::max<int64_t>(npm, 1)));
-            dev::ladder_pack_V(block(P_ijab).p, vp, vm, no, nv, 0, opp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
-        }
-        ArenaScope s2(arena);
-        double* Sp = arena.alloc(npp * ldp);
-        double* Am = arena.alloc(std::max<int64_t>(npm * ldm, 1));
-        dev::ladder_pack_T(y, nullptr, Sp, Am, no, nv, dev::PACK_ROW_HALF, ldp, ldm, stream);
-        contract(2.0, packed_rows(static_["VpIjab"], opp, npp), "rk", pitched(Sp, npp, opp, ldp), "kn", 2.0, Ipv, "rn");
-        if (opm > 0 && npm > 0)
-            contract(2.0, packed_rows(static_["VmIjab"], opp, npm), "rk", pitched(Am, npm, opm, ldm), "kn", 2.0, Imv, "rn");
-        else if (opm > 0) axpby(2.0, Imv, 0.0, Imv);
-    } else {
-        axpby(2.0, Ipv, 0.0, Ipv);
-        if (opm > 0) axpby(2.0, Imv, 0.0, Imv);
-    }
-    double* SpR = arena.alloc(npp * ldp);
-    double* AmR = arena.alloc(npp * ldp);
-    dev::ladder_pack_T(x, nullptr, SpR, AmR, no, nv, dev::PACK_COL_HALF | dev::PACK_AM_PROWS | dev::PACK_AM_PCOLS, ldp, ldp, stream,
-                       row0, row1);
+    hole_ladder_rows(x, I, L, row0, row1, y);
     stats.permute_calls++;
-    stats.permute_bytes += 8.0 * 2.0 * double(rows) * 2.0 * double(o * o);
-    contract(1.0, slice(make_view(SpR, {npp, ldp}), 0, row0, row1), "rk", pitched(Ip, ldp, opp, ldp), "kn", 1.0, LS, "rn");
-    if (opm > 0) contract(1.0, slice(make_view(AmR, {npp, ldp}), 0, row0, row1), "rk", pitched(Im, ldp, opm, ldm), "kn", 1.0, LA, "rn");
+    stats.permute_bytes += 8.0 * 2.0 * double(row1 - row0) * 2.0 * double(static_cast<int64_t>(no) * no);
 }
 
 // hole_ladder_packed for k vectors in batched launches: L_z += rows(x_z) . (2 pack(I_z) [+ 2 V_klcd y_z, pair-packed]), all
@@ -1074,9 +1064,9 @@ void Engine::hole_ladder_packed(const double* x, const double* I, double* L, int
 // V_kldc u2_z (:381): the shared side is packed once and enters the batched GEMM with batch stride 0.
 void Engine::hole_ladder_packed_multi(const double* const* xs, const double* const* Is, const double* const* ys, int k,
                                       double* L_all) {
-    const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opp = o * (o + 1) / 2, opm = o * (o - 1) / 2;
+    const PairDims d = pair_dims();
+    const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm, ldp = d.ldp, ldm = d.ldm;
     if (k < 1) return;
-    const int64_t ldp = opp + (opp & 1), ldm = std::max<int64_t>(opm + (opm & 1), 2);
     bool same_x = true, same_I = true;
     for (int z = 1; z < k; ++z) { same_x = same_x && xs[z] == xs[0]; same_I = same_I && Is[z] == Is[0]; }
     if (ys) same_I = false;
@@ -1085,21 +1075,11 @@ void Engine::hole_ladder_packed_multi(const double* const* xs, const double* con
     const int64_t ip_sz = ldp * ldp, im_sz = ldp * ldm;
     double* Ip = arena.alloc(ki * ip_sz);
     double* Im = arena.alloc(ki * im_sz);
-    for (int z = 0; z < ki; ++z) {
-        if (ldp > opp) {       // the zero pad row of the K range
-            dev::memset_zero(Ip + z * ip_sz + opp * ldp, sizeof(double) * ldp, stream);
-            dev::memset_zero(Im + z * im_sz + opp * ldm, sizeof(double) * ldm, stream);
-        }
-        dev::ladder_pack_T(Is[z], nullptr, Ip + z * ip_sz, Im + z * im_sz, no, no, dev::PACK_AM_PROWS, ldp, ldm, stream);
-    }
+    for (int z = 0; z < ki; ++z) hole_operand_pack(Is[z], {Ip + z * ip_sz, Im + z * im_sz});
     int64_t id[3] = {ki, opp, opp}, is_[3] = {ip_sz, ldp, 1}, md[3] = {ki, opp, std::max<int64_t>(opm, 1)}, ms[3] = {im_sz, ldm, 1};
     TView Ipv = make_view(Ip, 3, id, is_), Imv = make_view(Im, 3, md, ms);
     if (ys) {
-        if (!static_.count("VpIjab")) {
-            double* vp = new_static("VpIjab", opp * lpitch(npp));
-            double* vm = new_static("VmIjab", opp * lpitch(std::max<int64_t>(npm, 1)));
-            dev::ladder_pack_V(block(P_ijab).p, vp, vm, no, nv, 0, opp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
-        }
+        const PackedV Vij = ijab_pack();
         ArenaScope s2(arena);
         const int64_t sp_sz = npp * ldp, am_sz = std::max<int64_t>(npm * ldm, 2);
         double* Sp = arena.alloc(k * sp_sz);
@@ -1109,10 +1089,10 @@ void Engine::hole_ladder_packed_multi(const double* const* xs, const double* con
         stats.permute_calls += k;
         stats.permute_bytes += 8.0 * 2.0 * double(k) * double(v * v * o * o);
         int64_t bd[3] = {k, npp, opp}, bs[3] = {sp_sz, ldp, 1};
-        contract(2.0, packed_rows(static_["VpIjab"], opp, npp), "rk", make_view(Sp, 3, bd, bs), "zkn", 2.0, Ipv, "zrn", "z");
+        contract(2.0, packed_rows(Vij.Vp, opp, npp), "rk", make_view(Sp, 3, bd, bs), "zkn", 2.0, Ipv, "zrn", "z");
         if (opm > 0 && npm > 0) {
             int64_t bd2[3] = {k, npm, opm}, bs2[3] = {am_sz, ldm, 1};
-            contract(2.0, packed_rows(static_["VmIjab"], opp, npm), "rk", make_view(Am, 3, bd2, bs2), "zkn", 2.0, Imv, "zrn", "z");
+            contract(2.0, packed_rows(Vij.Vm, opp, npm), "rk", make_view(Am, 3, bd2, bs2), "zkn", 2.0, Imv, "zrn", "z");
         } else if (opm > 0) {
             axpby(2.0, Imv, 0.0, Imv);
         }
@@ -1160,7 +1140,8 @@ void Engine::hole_ladder_packed_multi(const double* const* xs, const double* con
 // costs shrink with the number of ranks alike: the dressing streams V in and W out (16 B per element) at ~4 TB/s
 // effective; the Q products run 2 ov (npp opp + npm opm) flops at ~70 TFLOP/s.  PYMES_LADDER_DRESS=0/1 overrides it.
 bool Engine::bra_dress_pays() const {
-    const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opp = o * (o + 1) / 2, opm = o * (o - 1) / 2;
+    const PairDims d = pair_dims();
+    const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm;
     if (!dev::ladder_dress_ok(no, nv) || dress_off_) return false;
     if (const char* e = getenv("PYMES_LADDER_DRESS")) return atoi(e) != 0;
     const double t_dress = 16.0 * double(npp) * double(npp + npm) / 4.0e12 + 20e-6;
@@ -1170,26 +1151,14 @@ bool Engine::bra_dress_pays() const {
 
 void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t row0, int64_t row1, double* QK,
                        int64_t q0, int64_t q1, bool dcd, const double* J) {
-    const int64_t o = no, v = nv, npp = v * (v + 1) / 2, npm = v * (v - 1) / 2, opp = o * (o + 1) / 2,
-                  opm = o * (o - 1) / 2, ov = o * v;
+    const PairDims d = pair_dims();
+    const int64_t o = no, v = nv, ov = o * v, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm, ldp = d.ldp, ldm = d.ldm;
     if (row0 < 0 || row1 > npp || row0 > row1) throw Error("ladder_t1: bad pair-row range");
     if (q0 < 0 || q1 > ov || q0 > q1) throw Error("ladder_t1: bad (k,b) row range");
     const int64_t rows = row1 - row0, qrows = q1 - q0;
-    const int64_t ldp = opp + (opp & 1), ldm = std::max<int64_t>(opm + (opm & 1), 2);   // even pitches: 16-byte loads
     // ---- static packs (once per solve) ---------------------------------------------------------
-    if (rows > 0 && shard_on_) check_shard_rows("ladder_t1", row0, row1, false);
-    else if (rows > 0 && !(lpack_.valid && !lpack_.dressed && lpack_.row0 == row0 && lpack_.row1 == row1)) {
-        if (!lpack_.Vp || lpack_.row1 - lpack_.row0 != rows) {
-            dev::stream_sync(stream);
-            dev::dfree(lpack_.Vp);
-            dev::dfree(lpack_.Vm);
-            lpack_.Vp = lpack_.Vm = nullptr;
-            lpack_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * lpitch(npp)));
-            lpack_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * lpitch(std::max<int64_t>(npm, 1))));
-        }
-        dev::ladder_pack_V(block(P_abcd).p, lpack_.Vp, lpack_.Vm, nv, nv, row0, row1, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
-        lpack_.row0 = row0; lpack_.row1 = row1; lpack_.dressed = false; lpack_.valid = true;
-    }
+    // (integral sharding: the stored rows take the place of the pack; the dressing writes to its own copy as ever)
+    const PackedV V = rows > 0 ? ladder_rows("ladder_t1", row0, row1, false) : PackedV{nullptr, nullptr, false};
     // Bra dressing of the rank's rows of the packed V_abcd instead of its share of the Q_kb products: the two rank-no updates of
     // dev::ladder_dress move 2 x 6.5 GB at (50,200) where Q_kbij = sum_cd V_kbcd tau_cdij costs 1.0e12 flops (13.9 ms);
     // the dressed copy W takes the place of V in the ladder product and QK carries the small brackets only.
@@ -1200,7 +1169,7 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
         // rows (x,k) of V_kxcd (x slow), pair-packed over (c,d): packed in the order of the block, rows transposed; and the
         // dressed copy W of this rank's rows.  Out of memory (2 x 1.6 GB + 2 x 1.6 GB of scratch + the size of the packed
         // rows at (50,200)): one rank falls back to the Q_kb form; among several ranks the choice must not diverge.
-        const int64_t lp = lpitch(npp), lm = lpitch(std::max<int64_t>(npm, 1));
+        const int64_t lp = d.vlp, lm = d.vlm;
         const bool need_p = !static_.count("VpKx");
         double *tp = nullptr, *tm = nullptr, *px = nullptr, *mx = nullptr, *wp = nullptr, *wm = nullptr;
         bool ok = true;
@@ -1232,17 +1201,12 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
         }
     }
     if (!dress && qrows > 0 && !static_.count("VpK" + kkey)) {
-        double* vp = new_static("VpK" + kkey, qrows * lpitch(npp));
-        double* vm = new_static("VmK" + kkey, qrows * lpitch(std::max<int64_t>(npm, 1)));
-        dev::ladder_pack_V(block(P_iabc).p, vp, vm, 0, nv, q0, q1, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));          // rows (k,b) of V_kbcd as they are
+        double* vp = new_static("VpK" + kkey, qrows * d.vlp);
+        double* vm = new_static("VmK" + kkey, qrows * d.vlm);
+        dev::ladder_pack_V(block(P_iabc).p, vp, vm, 0, nv, q0, q1, stream, d.vlp, d.vlm);          // rows (k,b) of V_kbcd as they are
     }
-    if (!static_.count("VpIjab")) {
-        double* vp = new_static("VpIjab", opp * lpitch(npp));
-        double* vm = new_static("VmIjab", opp * lpitch(std::max<int64_t>(npm, 1)));
-        dev::ladder_pack_V(block(P_ijab).p, vp, vm, no, nv, 0, opp, stream, lpitch(npp), lpitch(std::max<int64_t>(npm, 1)));
-    }
+    ijab_pack();               // (with the other static packs, also where J makes this call do without it)
     ArenaScope scope(arena);
-    auto pitched = [&](double* p, int64_t r, int64_t c, int64_t ld) { return slice(make_view(p, {r, ld}), 1, 0, c); };
     TView Lrows = make_view(L + row0 * o * o, {rows, o * o});
     TView LS = slice(Lrows, 1, 0, opp), LA = slice(Lrows, 1, opp, o * o);
     {
@@ -1254,15 +1218,14 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
         stats.permute_calls++;
         stats.permute_bytes += 8.0 * 2.0 * double(v * v * o * o);
         TView SpT = pitched(Sp, npp, opp, ldp), AmT = pitched(Am, npm, opm, ldm);
-        // (integral sharding: the stored rows take the place of the pack; the dressing writes to its own copy as ever)
-        const double* Ap = shard_on_ ? srows_.Vp : lpack_.Vp;
-        const double* Am_ = shard_on_ ? srows_.Vm : lpack_.Vm;
+        const double* Ap = V.Vp;
+        const double* Am_ = V.Vm;
         if (dress && rows > 0) {
             ArenaScope s3(arena);
             double* ws = arena.alloc(dev::ladder_dress_ws_doubles(no, nv));
-            dev::ladder_dress(Ap, static_["VpKx"], t1, static_["VpDress" + rkey], no, nv, lpitch(npp), row0, row1, -1.0, ws, stream);
+            dev::ladder_dress(Ap, static_["VpKx"], t1, static_["VpDress" + rkey], no, nv, d.vlp, row0, row1, -1.0, ws, stream);
             if (npm > 0)
-                dev::ladder_dress(Am_, static_["VmKx"], t1, static_["VmDress" + rkey], no, nv, lpitch(npm), row0, row1, 1.0, ws, stream);
+                dev::ladder_dress(Am_, static_["VmKx"], t1, static_["VmDress" + rkey], no, nv, d.vlm, row0, row1, 1.0, ws, stream);
             Ap = static_["VpDress" + rkey];
             Am_ = static_["VmDress" + rkey];
         }
@@ -1311,15 +1274,9 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
     // ---- hole ladder rows.  Ifull = V~_klij + V_klcd T_cdij (pair-packed, doubled as in ladder_sym) ------
     // The (k,l) pair is the GEMM K index here: it runs over the padded pitch ldp (zero pad column in the rows of
     // T / tau, zero pad row in I) so that both operands qualify for 16-byte loads.
-    double* Ip = arena.alloc(ldp * ldp);
-    double* Im = arena.alloc(ldp * ldm);
-    if (ldp > opp) {
-        dev::memset_zero(Ip + opp * ldp, sizeof(double) * ldp, stream);
-        dev::memset_zero(Im + opp * ldm, sizeof(double) * ldm, stream);
-    }
-    dev::ladder_pack_T(block(P_klij, true).p, nullptr, Ip, Im, no, no, dev::PACK_AM_PROWS, ldp, ldm, stream);
-    TView Ipv = pitched(Ip, opp, opp, ldp), Imv = pitched(Im, opp, opm, ldm);        // the defined part
-    TView IpK = pitched(Ip, ldp, opp, ldp), ImK = pitched(Im, ldp, opm, ldm);        // with the zero pad row
+    const HoleOperand h = hole_operand(block(P_klij, true).p);
+    TView Ipv = pitched(h.Ip, opp, opp, ldp), Imv = pitched(h.Im, opp, opm, ldm);        // the defined part
+    TView IpK = pitched(h.Ip, ldp, opp, ldp), ImK = pitched(h.Im, ldp, opm, ldm);        // with the zero pad row
     double* SpR = arena.alloc(npp * ldp);
     double* AmR = arena.alloc(npp * ldp);
     const int rflags = dev::PACK_COL_HALF | dev::PACK_AM_PROWS | dev::PACK_AM_PCOLS;
@@ -1327,8 +1284,7 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
     auto rowsA = [&]() { return slice(make_view(AmR, {npp, ldp}), 0, row0, row1); };
     if (dcd) {
         // DCSD keeps only V~_klij in the hole ladder proper (ccd.py:178), but the (k,l)-bra part still sees Ifull
-        axpby(2.0, Ipv, 0.0, Ipv);
-        if (opm > 0) axpby(2.0, Imv, 0.0, Imv);
+        hole_operand_add(h, nullptr, nullptr, 2.0);
         dev::ladder_pack_T(t2, nullptr, SpR, AmR, no, nv, rflags, ldp, ldp, stream, row0, row1);
         contract(1.0, rowsS(), "rk", IpK, "kn", 1.0, LS, "rn");
         if (opm > 0) contract(1.0, rowsA(), "rk", ImK, "kn", 1.0, LA, "rn");
@@ -1343,12 +1299,7 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
         double* Sp = arena.alloc(npp * ldp);
         double* Am = arena.alloc(std::max<int64_t>(npm * ldm, 1));
         dev::ladder_pack_T(t2, nullptr, Sp, Am, no, nv, dev::PACK_ROW_HALF, ldp, ldm, stream);
-        GemmGroupScope grp(stream);
-        contract(2.0, packed_rows(static_["VpIjab"], opp, npp), "rk", pitched(Sp, npp, opp, ldp), "kn", bI, Ipv, "rn");
-        if (opm > 0 && npm > 0)
-            contract(2.0, packed_rows(static_["VmIjab"], opp, npm), "rk", pitched(Am, npm, opm, ldm), "kn", bI, Imv, "rn");
-        grp.close();
-        if (opm > 0 && npm <= 0 && !dcd) axpby(2.0, Imv, 0.0, Imv);
+        hole_operand_add(h, Sp, Am, bI, true);
     }
     // CCSD: rows of tau against Ifull;  DCSD: rows of t1 t1 against Ifull (rows of T were taken above)
     dev::ladder_pack_T(dcd ? nullptr : t2, t1, SpR, AmR, no, nv, rflags, ldp, ldp, stream, row0, row1);   // this rank's rows
@@ -1391,7 +1342,8 @@ int64_t Engine::dress_fock_ws_doubles() const {
 void Engine::dress_fock_partial(const double* t1, double* W, int rank, int world) {
     const int64_t o = no, v = nv;
     if (world < 1 || rank < 0 || rank >= world) throw Error("dress_fock_partial: bad rank/world");
-    const int64_t c = (o + world - 1) / world, j0 = std::min<int64_t>(rank * c, o), j1 = std::min<int64_t>(j0 + c, o);
+    int64_t j0, j1;
+    chunk(o, rank, world, j0, j1);
     TView G1 = make_view(W, {v, v}), G2 = make_view(G1.p + v * v, {v, v}), J1 = make_view(G2.p + v * v, {o, v}),
           J2 = make_view(J1.p + o * v, {o, v}), L1 = make_view(J2.p + o * v, {o, o}), L2 = make_view(L1.p + o * o, {o, o}),
           K1 = make_view(L2.p + o * o, {o, v}), K2 = make_view(K1.p + o * v, {v, o});
@@ -1452,7 +1404,8 @@ void Engine::xvv_partial(const double* f, const double* t2, double* Xvv_p, int r
     const bool dcd = flags & PYMES_DCD;
     const int64_t o = no, v = nv, nn = n;
     if (world < 1 || rank < 0 || rank >= world) throw Error("xvv_partial: bad rank/world");
-    const int64_t c = (o + world - 1) / world, k0 = std::min<int64_t>(rank * c, o), k1 = std::min<int64_t>(k0 + c, o);
+    int64_t k0, k1;
+    chunk(o, rank, world, k0, k1);
     TView Xvv = make_view(Xvv_p, {v, v});
     TView F = make_view(const_cast<double*>(f), {nn, nn});
     if (rank == 0) copy(slice(slice(F, 0, o, nn), 1, o, nn), Xvv);
@@ -1625,7 +1578,8 @@ void Engine::singles_residual_partial(const double* fd, const double* t1, const 
                                       bool reuse_layouts) {
     const int64_t o = no, v = nv, nn = n;
     if (world < 1 || rank < 0 || rank >= world) throw Error("singles_residual_partial: bad rank/world");
-    const int64_t c = (o + world - 1) / world, j0 = std::min<int64_t>(rank * c, o), j1 = std::min<int64_t>(j0 + c, o);
+    int64_t j0, j1;
+    chunk(o, rank, world, j0, j1);
     const int64_t nj = j1 - j0;
     TView D = make_view(const_cast<double*>(fd), {nn, nn});
     TView Dov = slice(slice(D, 0, 0, o), 1, o, nn), Dvo = slice(slice(D, 0, o, nn), 1, 0, o);
@@ -1798,7 +1752,7 @@ struct Hooks {
         }
     }
 };
-int64_t chunk_of(int64_t n, int world) { return (n + world - 1) / world; }
+int64_t chunk_of(int64_t n, int world) { int64_t lo, hi; return chunk(n, 0, world, lo, hi); }
 }  // namespace
 
 // ---- owner tiles: what rank `to` reads of the rows of a ring-product matrix that rank `from` computed (pymes_amd/dist.py,
@@ -1808,16 +1762,11 @@ std::vector<Engine::Rect> Engine::owner_tile_rects(int from, int to, int world) 
     std::vector<Rect> out;
     if (from == to) return out;
     const int64_t o = no, ov = o * nv, npp = static_cast<int64_t>(nv) * (nv + 1) / 2;
-    auto slab = [&](int64_t n, int r, int64_t& lo, int64_t& hi) {
-        const int64_t c = (n + world - 1) / world;
-        lo = std::min<int64_t>(r * c, n);
-        hi = std::min<int64_t>(lo + c, n);
-    };
     int64_t q0, q1, r0, r1;
-    slab(npp, to, q0, q1);
+    chunk(npp, to, world, q0, q1);
     if (q1 <= q0) return out;
     const int64_t A0 = static_cast<int64_t>(a_of_pair_row(q0)) * o, A1 = static_cast<int64_t>(a_of_pair_row(q1 - 1) + 1) * o;
-    slab(ov, from, r0, r1);
+    chunk(ov, from, world, r0, r1);
     if (std::min(r1, A1) > r0) out.push_back(Rect{r0, std::min(r1, A1), A0, A1});
     if (A0 > 0 && std::min(r1, A1) > std::max(r0, A0)) out.push_back(Rect{std::max(r0, A0), std::min(r1, A1), 0, A0});
     return out;
@@ -1901,7 +1850,8 @@ void Engine::ccsd_sharded_residuals(const double* f, double* fd, const double* t
     {
         // V~_iajb / V~_iabj only for the second-index range that this rank's column slab reads (:165); V~_klij rides in the
         // same call and shares its V_klcd t_dj intermediate with V~_iabj
-        const int64_t cc = chunk_of(ov, world), c0 = std::min<int64_t>(rank * cc, ov), c1 = std::min<int64_t>(c0 + cc, ov);
+        int64_t c0, c1;
+        chunk(ov, rank, world, c0, c1);
         if (c1 > c0) {
             const int64_t cut[4] = {0, 0, c0 / o, (c1 + o - 1) / o};
             dress_V(t1, (1u << P_klij) | (1u << P_iajb) | (1u << P_iabj), cut);
@@ -2171,24 +2121,23 @@ void Engine::check_shard_rows(const char* who, int64_t row0, int64_t row1, bool 
 void Engine::shard_rows(const double** vp, const double** vm, int64_t* row0, int64_t* row1, int64_t* ldp, int64_t* ldm) const {
     if (!shard_on_) throw Error("pymes_shard_rows_ptr: the context does not shard its integrals");
     if (!srows_.set) throw Error("pymes_shard_rows_ptr: the rows of V_abcd have not been set");
-    const int64_t v = nv;
     *vp = srows_.Vp;
     *vm = srows_.Vm;
     *row0 = srows_.row0;
     *row1 = srows_.row1;
-    *ldp = lpitch(v * (v + 1) / 2);
-    *ldm = lpitch(std::max<int64_t>(v * (v - 1) / 2, 1));
+    *ldp = pair_dims().vlp;
+    *ldm = pair_dims().vlm;
 }
 
 void Engine::shard_rows_alloc() {
-    const int64_t v = nv, rows = srows_.row1 - srows_.row0;
+    const int64_t rows = srows_.row1 - srows_.row0;
     if (srows_.Vp || rows <= 0) return;
-    srows_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * lpitch(v * (v + 1) / 2)));
-    srows_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * lpitch(std::max<int64_t>(v * (v - 1) / 2, 1))));
+    srows_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * pair_dims().vlp));
+    srows_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * rows * pair_dims().vlm));
 }
 
 int64_t Engine::integral_bytes() const {
-    const int64_t v = nv, lp = lpitch(v * (v + 1) / 2), lm = lpitch(std::max<int64_t>(v * (v - 1) / 2, 1));
+    const int64_t lp = pair_dims().vlp, lm = pair_dims().vlm;
     int64_t d = 0;
     for (int p = 0; p < 16; ++p) d += (V_[p] ? block_size(p) : 0) + (Vd_[p] ? block_size(p) : 0);
     for (auto& kv : static_doubles_) d += kv.second;
@@ -2202,7 +2151,7 @@ int64_t Engine::integral_bytes() const {
 // ladder_pack_V in its nr == 0 form (the rows of the chunk are consecutive planes).
 void Engine::shard_rows_from(const double* V0, const int64_t st[4], bool on_device) {
     shard_rows_alloc();
-    const int64_t v = nv, plane = v * v, lp = lpitch(v * (v + 1) / 2), lm = lpitch(std::max<int64_t>(v * (v - 1) / 2, 1));
+    const int64_t v = nv, plane = v * v, lp = pair_dims().vlp, lm = pair_dims().vlm;
     const int64_t r0 = srows_.row0, r1 = srows_.row1;
     srows_.set = false;
     if (r1 > r0) {
@@ -2253,7 +2202,7 @@ void Engine::shard_rows_from(const double* V0, const int64_t st[4], bool on_devi
 
 void Engine::shard_rows_from_factors(const double* Bd, int naux) {
     shard_rows_alloc();
-    const int64_t v = nv, lp = lpitch(v * (v + 1) / 2), lm = lpitch(std::max<int64_t>(v * (v - 1) / 2, 1));
+    const int64_t lp = pair_dims().vlp, lm = pair_dims().vlm;
     srows_.set = false;
     if (srows_.row1 > srows_.row0)
         dev::ladder_pack_V_factors(Bd, srows_.Vp, srows_.Vm, naux, n, no, srows_.row0, srows_.row1, stream, lp, lm);

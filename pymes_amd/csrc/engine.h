@@ -6,7 +6,9 @@
 // (pymes/solver/ccsd.py:11, mp2.py:5; historically ctf.einsum, pymes/__init__.py:3)
 // plus the solver methods that call it.
 #pragma once
+#include <algorithm>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <set>
 #include <stdexcept>
@@ -91,6 +93,38 @@ struct ContractStats {
     long gemm_calls = 0, permute_calls = 0;
     double gemm_flops = 0.0;       // executed 2*M*N*K*batch
     double permute_bytes = 0.0;    // bytes moved by explicit copies (read + write)
+};
+
+// Rank `rank` of `world` owns the items [lo,hi) of n: chunks of c = ceil(n / world), the last ones short or empty — the one
+// rule of every sharded sum and slab (pymes_amd/pdist.py, slab_rows, cuts the same way).  Returns c.
+inline int64_t chunk(int64_t n, int rank, int world, int64_t& lo, int64_t& hi) {
+    const int64_t c = (n + world - 1) / world;
+    lo = std::min<int64_t>(rank * c, n);
+    hi = std::min<int64_t>(lo + c, n);
+    return c;
+}
+
+// Sizes and pitches of the pair-packed ladder family (cc.cpp) for (no, nv): pairs c >= d / c > d of virtual (npp / npm) and
+// of occupied (opp / opm) indices.
+struct PairDims {
+    int64_t npp, npm, opp, opm;
+    // rows of packed amplitudes [.][opp | opm]: even pitches (zero pad column / pad row where the pair index is a GEMM K
+    // index), so that every operand qualifies for 16-byte loads and the LDS-DMA kernel also when o(o+1)/2 is odd —
+    // (30,120): 465, (50,200): 1275
+    int64_t ldp, ldm;
+    // rows of the packed integrals V^+ / V^- (the K-contiguous left operand of the ladder GEMMs): see lpitch
+    int64_t vlp, vlm;
+    // the k-vector operands of ladder_sym_adjoint_multi: even and with at least one pad column — ladder_pack_T zeroes the
+    // column behind the packed ones whenever the pitch it is given exceeds them, and there the pitch is k of these
+    int64_t adj_ldp, adj_ldm;
+    PairDims(int64_t o, int64_t v)
+        : npp(v * (v + 1) / 2), npm(v * (v - 1) / 2), opp(o * (o + 1) / 2), opm(o * (o - 1) / 2), ldp(opp + (opp & 1)),
+          ldm(std::max<int64_t>(opm + (opm & 1), 2)), vlp(lpitch(npp)), vlm(lpitch(std::max<int64_t>(npm, 1))),
+          adj_ldp((opp + 2) & ~int64_t(1)), adj_ldm((opm + 2) & ~int64_t(1)) {}
+    // a multiple of 16 doubles, so that every 128-byte piece the LDS-DMA fetches is one cache line (v(v+1)/2 = 20100 is
+    // not: two lines per piece)
+    static int64_t lpitch(int64_t n) { return (n + 15) & ~int64_t(15); }
+    int64_t adjoint_pitch(bool symmetric_half) const { return symmetric_half ? adj_ldp : adj_ldm; }
 };
 
 // block pattern id: bit (3-pos) set when the index at `pos` is virtual
@@ -210,12 +244,8 @@ class Engine {
     // opp) of rows of pitch k ldp (ldp = ladder_adjoint_pitch(true); the antisymmetric half alike with ldm).  LS [npp][k ldp],
     // LA [max(npm,1)][k ldm]: the row of pair r for vector z starts at LS + r k ldp + z ldp
     void ladder_sym_adjoint_multi(const double* const* xs, int k, double* LS, double* LA, bool dressed);
-    int64_t ladder_adjoint_pitch(bool symmetric_half) const {
-        const int64_t o = no, opp = o * (o + 1) / 2, opm = o * (o - 1) / 2;
-        // even and with at least one pad column: ladder_pack_T zeroes the column behind the packed ones whenever the pitch it
-        // is given exceeds them, and here the pitch is k of these
-        return ((symmetric_half ? opp : opm) + 2) & ~int64_t(1);
-    }
+    PairDims pair_dims() const { return PairDims(no, nv); }
+    int64_t ladder_adjoint_pitch(bool symmetric_half) const { return pair_dims().adjoint_pitch(symmetric_half); }
     void hole_ladder_packed_multi(const double* const* xs, const double* const* Is, const double* const* ys, int k, double* L_all);
     void hole_ladder_packed(const double* x, const double* I, double* L, int64_t row0, int64_t row1,
                             const double* y = nullptr);
@@ -438,6 +468,49 @@ class Engine {
         int64_t row0 = 0, row1 = 0;
         bool dressed = false, valid = false;
     } lpack_;
+    // The cache holds the V^+ / V^- rows [row0,row1) of the (dressed) V_abcd afterwards; true when it had to pack them (the
+    // callers count that pass in `stats`, ladder_t1 does not).
+    bool ensure_ladder_pack(int64_t row0, int64_t row1, bool dressed);
+    struct PackedV {
+        double* Vp;
+        double* Vm;
+        bool packed;       // by this call
+    };
+    // The rows [row0,row1) to multiply with: the stored rows of an integral-sharded context (the only copy; checked against
+    // its (rank, world) and `dressed`), else the cache.
+    PackedV ladder_rows(const char* who, int64_t row0, int64_t row1, bool dressed);
+    // V_klcd with (k,l) and (c,d) pair-packed (rows P(k,l) at the pitch of the V rows), packed on first use; static per
+    // solve: dressed ijab == undressed ijab
+    PackedV ijab_pack();
+    // The right operand I' of a hole-ladder product in the arena: Ip [ldp][ldp], Im [ldp][ldm] = the pair-packed halves of
+    // an I_klij = I_lkji, rows P(k,l), with a zero pad row where opp is odd (the (k,l) pair is the GEMM K index).
+    struct HoleOperand {
+        double* Ip;
+        double* Im;
+    };
+    void hole_operand_pack(const double* I, const HoleOperand& h);
+    HoleOperand hole_operand(const double* I);
+    // I' <- beta I' + 2 V_klcd y from the packed halves (Sp, Am) of y (ladder_pack_T, PACK_ROW_HALF); without: I' <- 2 I'.
+    // grouped: the two products as one GemmGroupScope.
+    void hole_operand_add(const HoleOperand& h, const double* Sp, const double* Am, double beta, bool grouped = false);
+    // rows [row0,row1) of L += rows(x) . (2 pack(I) [+ 2 V_klcd y]); y as the array or as its packed halves (ySp, yAm).
+    // Allocates in the caller's ArenaScope and counts nothing in `stats`.
+    void hole_ladder_rows(const double* x, const double* I, double* L, int64_t row0, int64_t row1, const double* y,
+                          const double* ySp = nullptr, const double* yAm = nullptr);
+    // The ring half of residual_slab in its two forms (several ranks: the slab transposed from the start; one rank: all
+    // columns) and what residual_slab hands to them.
+    struct RingSlab {
+        const double* t2;
+        const double* ETd_p;
+        bool quad, traces, fold;
+        int64_t c0, c1;
+        TView F, Viajb, Viabj, Tx, Ttd, ETd, ETx;
+        std::function<void(double, const TView&, const char*, const TView&)> load_cols, load_rows;
+    };
+    void slab_ladders(const double* t2, double* L, int rank, int world, unsigned flags, const double* t1, double* QK,
+                      const double* P);
+    void slab_rings_rows(const RingSlab& s);
+    void slab_rings_cols(const RingSlab& s);
     bool bra_dress_pays() const;
     bool dress_off_ = false;     // the dressed copy did not fit the device memory once: Q_kb form from then on
     double* splitk_ws_ = nullptr;

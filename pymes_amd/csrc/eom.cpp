@@ -789,8 +789,8 @@ void EomSigma::left_stack(int k, const double* const* l1, const double* const* l
     q.C(1.0, XvvV, "zac", slice(mv(BB, {o, v, o, v + o}), 3, 0, v), "kdlc", 1.0, P5(Px), "zdlak");
     q.C(1.0, L2, "zabij", mv(B2, {o, o, o, o}), "klij", 1.0, D, "zabkl");
     q.C(1.0, Vijab, "kldc", BnV, "zklij", 1.0, D, "zdcij");
-    const int64_t npp = v * (v + 1) / 2, npm = std::max<int64_t>(v * (v - 1) / 2, 1);
-    const int64_t ldp = e.ladder_adjoint_pitch(true), ldm = e.ladder_adjoint_pitch(false);
+    const PairDims pd = e.pair_dims();
+    const int64_t npp = pd.npp, npm = std::max<int64_t>(pd.npm, 1), ldp = pd.adj_ldp, ldm = pd.adj_ldm;
     const bool la = v_sym && o > 1 && v > 1;
     Tmp Lp(*this, v_sym ? npp * K * ldp : 1), La(*this, la ? npm * K * ldm : 1);
     if (v_sym) e.ladder_sym_adjoint_multi(l2, k, Lp, La, dressed);

@@ -153,6 +153,22 @@ def test_pair_packed_ladder(gpu_lib, no, nv, seed):
         ctx.close()
 
 
+@pytest.mark.parametrize("no,nv,seed", [(1, 3, 21), (2, 1, 22), (3, 2, 23)])
+def test_hole_and_multi_ladders_degenerate_pair_shapes(gpu_lib, no, nv, seed):
+    """No antisymmetric virtual pair (nv = 1), none of occupied indices (no = 1), an odd number of occupied pairs (no = 2)."""
+    from tests.test_host_engine import hole_and_multi_check
+    hole_and_multi_check(gpu_lib, no, nv, seed, TOL)
+
+
+@pytest.mark.parametrize("dress", ["0", "1"])
+@pytest.mark.parametrize("no,nv,seed", [(1, 3, 21), (2, 1, 22), (3, 2, 23), (2, 4, 24)])
+def test_sharded_residual_degenerate_pair_shapes(gpu_lib, monkeypatch, no, nv, seed, dress):
+    """... and, with 3 ranks, more ranks than rows."""
+    from tests.test_host_engine import sharded_residual_check
+    monkeypatch.setenv("PYMES_LADDER_DRESS", dress)
+    sharded_residual_check(gpu_lib, [(no, nv, seed)], (1, 2, 3), 1e-11)
+
+
 def test_sharded_residual_simulated_ranks(gpu_lib):
     from tests.test_host_engine import sharded_residual_check
     sharded_residual_check(gpu_lib, [(3, 5, 2), (6, 17, 3), (8, 24, 4)], (1, 2, 8), 1e-11)

@@ -252,6 +252,59 @@ def test_sharded_residual_host_logic_bra_dressed(sim, monkeypatch):
     sharded_residual_check(sim, [(2, 3, 1), (3, 5, 2)], (1, 2, 3, 8), 1e-12)
 
 
+# The shapes at which the pair-packed ladder family degenerates: no antisymmetric virtual pair (nv = 1), no antisymmetric
+# occupied pair (no = 1), an odd number of occupied pairs with its pad row (no = 2) — and, with 3 ranks, more ranks than rows.
+DEGENERATE_PAIR_SHAPES = [(1, 3, 21), (2, 1, 22), (3, 2, 23), (2, 4, 24)]
+
+
+@pytest.mark.parametrize("dress", ["0", "1"])
+@pytest.mark.parametrize("no,nv,seed", DEGENERATE_PAIR_SHAPES)
+def test_sharded_residual_degenerate_pair_shapes(sim, monkeypatch, no, nv, seed, dress):
+    monkeypatch.setenv("PYMES_LADDER_DRESS", dress)
+    sharded_residual_check(sim, [(no, nv, seed)], (1, 2, 3), 1e-12)
+
+
+def hole_and_multi_check(lib, no, nv, seed, tol):
+    """hole_ladder_check, then the k = 3 entries with distinct vectors: hole_ladder_packed_multi with and without ys and
+    ladder_sym_multi, each unpacked and compared with the plain einsum."""
+    f, V, t1, t2 = random_case(no, nv, seed, symmetric=True)
+    Vb = oc.split_blocks(no, V)
+    rng = np.random.default_rng(seed)
+    sym = lambda a: 0.5 * (a + a.transpose(1, 0, 3, 2))
+    k, npp = 3, nv * (nv + 1) // 2
+    xs = [sym(rng.standard_normal(t2.shape)) for _ in range(k)]
+    ys = [sym(rng.standard_normal(t2.shape)) for _ in range(k)]
+    Is = [sym(rng.standard_normal((no,) * 4)) for _ in range(k)]
+    ctx = Context(no, nv, lib=lib)
+    try:
+        ctx.set_V_pqrs(V)
+        hole_ladder_check(ctx, no, nv, Vb, t2, tol)
+        dx, dy, dI = [ctx.array(a) for a in xs], [ctx.array(a) for a in ys], [ctx.array(a) for a in Is]
+
+        def unpacked(L_all, z):
+            Lz = DeviceArray(ctx, L_all.ptr + 8 * z * npp * no * no, (npp, no * no), owned=False, keepalive=L_all)
+            return ctx.ladder_sym_unpack(Lz, ctx.empty(t2.shape), beta=0.0).get()
+
+        def close(got, ref, what):
+            assert np.abs(got - ref).max() < tol * max(1.0, np.abs(ref).max()), (what, no, nv)
+
+        for with_y in (False, True):
+            L_all = ctx.hole_ladder_packed_multi(dx, dI, ctx.zeros((k, npp, no * no)), ys=dy if with_y else None)
+            for z in range(k):
+                I = Is[z] + (np.einsum("klcd,cdij->klij", Vb["ijab"], ys[z]) if with_y else 0.0)
+                close(unpacked(L_all, z), np.einsum("klij,abkl->abij", I, xs[z]), ("hole multi", with_y, z))
+        L_all = ctx.ladder_sym_multi(dx, ctx.zeros((k, npp, no * no)))
+        for z in range(k):
+            close(unpacked(L_all, z), np.einsum("abcd,cdij->abij", Vb["abcd"], xs[z]), ("ladder multi", z))
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("no,nv,seed", DEGENERATE_PAIR_SHAPES[:3])
+def test_hole_and_multi_ladders_degenerate_pair_shapes(sim, no, nv, seed):
+    hole_and_multi_check(sim, no, nv, seed, 1e-12)
+
+
 def _problem(tag):
     if tag.startswith("syn_"):
         no, nv = (int(x) for x in tag.split("_")[1:])

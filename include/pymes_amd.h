@@ -97,7 +97,19 @@ int pymes_memset_zero(pymes_ctx* ctx, void* dst_dev, uint64_t bytes);
 
 /* ---- generic tensor engine: the `einsum` seam (ccsd.py:11, mp2.py:5) ------------ */
 /* C[lc] = alpha * sum_{contracted} A[la] * B[lb] + beta * C[lc]; one-letter labels; strides
- * may be NULL (contiguous); `batch` lists free labels to run as GEMM batches ("" = none). */
+ * may be NULL (contiguous); `batch` lists free labels to run as GEMM batches ("" = none).
+ * Strides (here, in pymes_permute and in the device forms of pymes_set_V_pqrs / pymes_set_V_block; with on_device == 0 those
+ * two read a C-contiguous host array and neither use nor check `strides`) count ELEMENTS and are zero or positive, of
+ * tensors of rank 0..6:
+ *  - an INPUT axis may have stride 0 (the operand is shared along it); an output has neither a zero stride nor two index
+ *    tuples on one element;
+ *  - a negative stride is refused with an error that names the argument (the product kernels read a pitch as an unsigned
+ *    distance): pass a reversed copy;
+ *  - no alignment is asked of a base pointer or a pitch beyond 8 bytes; the 16-byte loads are chosen only where both allow;
+ *  - ONE-ELEMENT OVER-READ: a product may load the 8 bytes that follow the last element of A or B (the second half of a pair
+ *    load past an odd contiguous extent; its value reaches no stored element of C).  That double must lie inside the same
+ *    allocation: a view of an input must not end flush with the end of its allocation.  Nothing outside the view of C is
+ *    written, and with beta == 0 nothing of C is read. */
 int pymes_contract(pymes_ctx* ctx, double alpha,
                    const double* A_dev, const char* la, const int64_t* dimA, const int64_t* strideA,
                    const double* B_dev, const char* lb, const int64_t* dimB, const int64_t* strideB,

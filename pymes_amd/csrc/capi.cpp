@@ -89,11 +89,23 @@ pymes::IpEaSigma& SI(pymes_ipea* h, const char* who) {
     if (e.capturing()) throw pymes::Error(std::string(who) + " while a launch graph is being recorded");
     return *h->s;
 }
-TView view_of(const double* p, const char* labels, const int64_t* dim, const int64_t* stride) {
+// Element strides of this interface are zero or positive: the 32-bit lane offsets of the LDS-DMA product kernel and the
+// pad-element rule of describe_product (kernels.hip) read a pitch as an unsigned distance, so a negative one is refused here,
+// by the name of the argument, instead of reaching a kernel.
+void need_forward(const int64_t* stride, int rank, const char* what) {
+    if (!stride) return;
+    for (int i = 0; i < rank; ++i)
+        if (stride[i] < 0)
+            throw pymes::Error(std::string(what) + ": negative stride " + std::to_string(stride[i]) + " at axis " + std::to_string(i) +
+                               " (strides are zero or positive: pass a reversed copy)");
+}
+TView view_of(const double* p, const char* labels, const int64_t* dim, const int64_t* stride, const char* what) {
     need(p, "tensor data");
     need(labels, "labels");
     need(dim, "dims");
-    return pymes::make_view(const_cast<double*>(p), static_cast<int>(std::strlen(labels)), dim, stride);
+    const int rank = static_cast<int>(std::strlen(labels));
+    if (rank <= 6) need_forward(stride, rank, what);
+    return pymes::make_view(const_cast<double*>(p), rank, dim, stride);
 }
 }  // namespace
 
@@ -244,7 +256,8 @@ int pymes_contract(pymes_ctx* ctx, double alpha, const double* A, const char* la
                    double beta, double* C, const char* lc, const int64_t* dC, const int64_t* sC,
                    const char* batch) {
     return guarded([&] {
-        Eq(ctx).contract(alpha, view_of(A, la, dA, sA), la, view_of(B, lb, dB, sB), lb, beta, view_of(C, lc, dC, sC),
+        Eq(ctx).contract(alpha, view_of(A, la, dA, sA, "strideA"), la, view_of(B, lb, dB, sB, "strideB"), lb, beta,
+                        view_of(C, lc, dC, sC, "strideC"),
                         lc, batch ? batch : "");
     });
 }
@@ -253,7 +266,7 @@ int pymes_permute(pymes_ctx* ctx, double alpha, const double* in, const char* li
     return guarded([&] {
         need(li, "li");
         need(lo, "lo");
-        TView vin = view_of(in, li, dim_in, stride_in);
+        TView vin = view_of(in, li, dim_in, stride_in, "stride_in");
         const int r = vin.rank;
         if (static_cast<int>(std::strlen(lo)) != r) throw pymes::Error("permute: label strings differ in length");
         int64_t dout[6];
@@ -262,6 +275,7 @@ int pymes_permute(pymes_ctx* ctx, double alpha, const double* in, const char* li
             if (!f) throw pymes::Error("permute: output label missing from input");
             dout[i] = dim_in[f - li];
         }
+        need_forward(stride_out, r, "stride_out");
         TView vout = pymes::make_view(out, r, dout, stride_out);
         need(out, "out");
         E(ctx).permute(alpha, vin, li, beta, vout, lo);
@@ -288,6 +302,7 @@ int pymes_dgemm(pymes_ctx* ctx, int64_t M, int64_t N, int64_t K, double alpha, c
 int pymes_set_V_pqrs(pymes_ctx* ctx, const double* V, int on_device, const int64_t* strides) {
     return guarded([&] {
         need(V, "V");
+        if (on_device) need_forward(strides, 4, "strides");
         E(ctx).set_V_full(V, on_device != 0, strides);
     });
 }
@@ -302,6 +317,7 @@ int pymes_set_V_block(pymes_ctx* ctx, const char* name, const double* data, int6
         if (n_elements != want)
             throw pymes::Error(std::string("block '") + name + "' has " + std::to_string(want) + " elements for this context, got " +
                                std::to_string(n_elements));
+        if (on_device) need_forward(strides, 4, "strides");
         e.set_V_block(name, data, on_device != 0, strides);
     });
 }

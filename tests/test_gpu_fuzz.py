@@ -1,7 +1,8 @@
 """GPU: seeded random shapes through the two front ends every contraction of the CC path goes through — the fp64 MFMA
 GEMM (tile-choice rules, ragged extents, padded pitches, k-splits, the LDS-DMA kernel from K >= 384, the matrix-vector
-kernels) and the einsum-style planner (label classification, kept transposes, batch labels, alpha / beta) — against
-numpy.  The reference's seam for both is the module-level ``einsum`` callable (pymes/solver/ccsd.py:11)."""
+kernels) and the einsum-style planner (label classification, kept transposes, alpha / beta; contiguous operands of rank up
+to 4 without batch labels) — against numpy.  Batch labels, ranks 5 and 6 and strided, offset and stride-0 views go through
+tests/test_gpu_strided_abi.py.  The reference's seam for both is the module-level ``einsum`` callable (pymes/solver/ccsd.py:11)."""
 import numpy as np
 import pytest
 

@@ -181,6 +181,32 @@ int pymes_ccsd_t_triples(pymes_ctx* ctx, int64_t* n_triples);
 int pymes_ccsd_t(pymes_ctx* ctx, const double* eps_host, const double* t1_dev, const double* t2_dev, int64_t t_begin,
                  int64_t t_end, double* per_triple_dev, double* e_out_host);
 
+/* ---- Lambda-CCSD(T): the triples correction with Lambda as the left state (Kucharski-Bartlett, Taube-Bartlett) ---------------
+ * The triples correction for Hamiltonians without V_pqrs = V_rspq (transcorrelated integrals), which pymes_ccsd_t refuses; for
+ * Hermitian integrals the more robust one away from equilibrium.  Closed shell, canonical orbitals (the f_ov lam2 term of the
+ * general formula vanishes), notation as above.  lam1 [v,o], lam2 [v,v,o,o] are the library's Lambda (pymes_lambda_step:
+ * A^T lam + eta = 0, eta2 = 2 V_ijab - V_ijba, plain inner product), converted once per call:
+ *   L[a,b,i,j] = (2 lam2[a,b,i,j] + lam2[b,a,i,j]) / 3        l1[a,i] = lam1[a,i] / 2
+ * (in spin orbitals the doubles multiplier is 2L - L^x, the singles multiplier 2 l1).  For an occupied triple (i,j,k):
+ *   wR_ijk[a,b,c] = sum_f V_abic[a,b,i,f] T[c,f,k,j] - sum_m V_aijk[a,m,i,j] T[b,c,m,k]      (right: targets in the bra)
+ *   wL_ijk[a,b,c] = sum_f V_iabc[i,f,a,b] L[c,f,k,j] - sum_m V_ijak[i,j,a,m] L[b,c,m,k]      (left: w above, L for T)
+ *   WR, WL        = the six-permutation sums of wR, wL, as W_ijk above
+ *   YL[a,b,c]     = WL[abc] + V_ijab[j,k,b,c] l1[a,i] + V_ijab[i,k,a,c] l1[b,j] + V_ijab[i,j,a,b] l1[c,k]
+ *   S_ijk         = 1/3 sum_abc WR[abc] R(YL)[abc] / (eps_i + eps_j + eps_k - eps_a - eps_b - eps_c)
+ *   E_Lambda(T)   = sum_{i >= j >= k} m_ijk S_ijk
+ * t1 does not enter (the right triples are connected); lam1_dev may be NULL (CCD, electron gas).  The formula needs
+ * V_pqrs = V_qpsr, T_abij = T_baji and the same symmetry of lam2, nothing else.  Triple numbering, ranges, per_triple_dev and
+ * e_out_host as for pymes_ccsd_t.  Reads only the UNDRESSED blocks iabc, aibc, ijak, abic, aijk (ijab with lam1) and, for the
+ * symmetry check, their partners ijka, abci, iajk: valid after pymes_ccsd_dress_V and on a context with
+ * pymes_set_integral_shard (no V_abcd).  Refused: a missing block (named), a call while a launch graph is recorded, integrals
+ * without V_pqrs = V_qpsr on those blocks (above 1e-10 max |V|; the block pair is named).  There is no Hermiticity check.  WR
+ * and WL are each the twelve products of pymes_ccsd_t (the excitation-type blocks are copied once per call into the layouts
+ * of the de-excitation-type ones: two o v^3 arrays); both are held per batch, so the default batch is half of pymes_ccsd_t's
+ * (PYMES_TRIPLES_BATCH=<n> forces it).  Each per-triple value and the sum (fixed order) are the same whatever the batch.
+ * Synchronises; frees what it allocates before it returns. */
+int pymes_ccsd_t_lambda(pymes_ctx* ctx, const double* eps_host, const double* t2_dev, const double* lam1_dev,
+                        const double* lam2_dev, int64_t t_begin, int64_t t_end, double* per_triple_dev, double* e_out_host);
+
 /* ---- frozen natural orbitals (FNO) and frozen core (closed shell, canonical orbitals, Hermitian integrals) -----------------
  * Orbital window: the n_frozen lowest occupied orbitals are dropped, the active ones are [n_frozen, no), no' = no - n_frozen.
  * Amplitudes over the active occupied orbitals and all virtuals, eps = the context's orbital energies (pymes_set_orbital_energies):

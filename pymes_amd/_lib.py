@@ -69,6 +69,8 @@ SIGNATURES = {
     "pymes_ccsd_t_triples": (C.c_int, [C.c_void_p, c_i64_p]),
     "pymes_ccsd_t": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                c_double_p]),
+    "pymes_ccsd_t_lambda": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                      C.c_void_p, c_double_p]),
     "pymes_fno_density": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, c_double_p]),
     "pymes_derive_context": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "pymes_set_orbital_energies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -362,6 +362,13 @@ int pymes_ccsd_t(pymes_ctx* ctx, const double* eps_host, const double* t1_dev, c
         *e_out_host = E(ctx).ccsd_t(eps_host, t1_dev, t2_dev, t_begin, t_end, per_triple_dev);
     });
 }
+int pymes_ccsd_t_lambda(pymes_ctx* ctx, const double* eps_host, const double* t2_dev, const double* lam1_dev,
+                        const double* lam2_dev, int64_t t_begin, int64_t t_end, double* per_triple_dev, double* e_out_host) {
+    return guarded([&] {
+        need(eps_host, "eps"); need(t2_dev, "t2"); need(lam2_dev, "lam2"); need(e_out_host, "e_out");
+        *e_out_host = E(ctx).ccsd_t_lambda(eps_host, t2_dev, lam1_dev, lam2_dev, t_begin, t_end, per_triple_dev);
+    });
+}
 int pymes_fno_density(pymes_ctx* ctx, const double* v_ijab_dev, int n_frozen, double* D_host, double* e_mp2_host) {
     return guarded([&] {
         need(D_host, "D"); need(e_mp2_host, "e_mp2");

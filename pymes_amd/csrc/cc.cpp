@@ -2275,6 +2275,54 @@ void unrank_triple(int64_t t, int& i, int& j, int& k) {
     j = y;
     k = (int)(r - (int64_t)y * (y + 1) / 2);
 }
+// The operands of the twelve products of one W_ijk: X1[p][f][x][y] and its swapped pair X1s[f][p][x][y] = X1[p][f][y][x]
+// ([o,v,v,v], [v,o,v,v]), X2[p][q][x][m] ([o,o,v,o]) and the permuted amplitudes A2o[x][y][f][z] = A[z,f,x,y],
+// A2h[m][k][b][c] = A[b,c,m,k] ([o,o,v,v]).  (T) and the left triples of Lambda-CCSD(T): V_iabc, V_aibc, V_ijak; the right
+// triples: copies of V_abic and V_aijk in these layouts.
+struct TriplesOperands {
+    const double *X1, *X1s, *X2, *A2o, *A2h;
+};
+// Wq[a][b][c] = w_ijk[abc] + w_jik[bac] + w_ikj[acb] + w_kij[cab] + w_jki[bca] + w_kji[cba], each w_pqr[x,y,z] =
+//   sum_f X1[p,f,x,y] A2o[r][q][f][z] - sum_m X2[p,q,x,m] A2h[m][r][y][z]
+// written with the unit-stride index c as N: X1[p,f,y,x] = X1s[f,p,x,y] supplies the swapped pairs.  The same launches
+// whatever else the caller holds: every sum has one order.
+void triples_W(Engine& e, double* Wq, int i, int j, int k, const TriplesOperands& x) {
+    const int64_t o = e.no, v = e.nv, v2 = v * v, v3 = v2 * v;
+    const double *Viabc = x.X1, *Vaibc = x.X1s, *Vijak = x.X2, *T2o = x.A2o, *T2h = x.A2h;
+    auto mm = [&](double* C, int64_t M, int64_t N, int64_t K, double alpha, double beta, const double* A, int64_t a_sm,
+                  int64_t a_sk, const double* B, int64_t b_sk, int64_t b_sn, int64_t ldc, int64_t nb = 1, int64_t b_b = 0,
+                  int64_t c_b = 0) {
+        dev::Gemm g{};
+        g.M = M; g.N = N; g.K = K;
+        g.alpha = alpha; g.beta = beta;
+        g.A = A; g.a_sm = a_sm; g.a_sk = a_sk;
+        g.B = B; g.b_sk = b_sk; g.b_sn = b_sn;
+        g.C = C; g.ldc = ldc;
+        g.nb1 = nb; g.nb2 = 1;
+        g.a_b1 = 0; g.b_b1 = b_b; g.c_b1 = c_b;
+        g.a_b2 = g.b_b2 = g.c_b2 = 0;
+        g.splitk_ws = nullptr;          // no k-split: the order of every sum is that of the tile kernel alone
+        g.splitk_ws_doubles = 0;
+        dev::gemm(g, e.stream);
+        e.stats.gemm_calls++;
+        e.stats.gemm_flops += 2.0 * (double)M * (double)N * (double)K * (double)nb;
+    };
+    // (the names are those of (T): Viabc = X1, Vaibc = X1s, Vijak = X2, T2o / T2h = A2o / A2h)
+    // particle products (K = v)
+    mm(Wq, v2, v, v, 1.0, 0.0, Viabc + i * v3, 1, v2, T2o + (k * o + j) * v2, v, 1, v);                 // w_ijk[a,b,c]
+    mm(Wq, v2, v, v, 1.0, 1.0, Vaibc + j * v2, 1, o * v2, T2o + (k * o + i) * v2, v, 1, v);             // w_jik[b,a,c]
+    mm(Wq, v, v, v, 1.0, 1.0, T2o + (j * o + k) * v2, 1, v, Viabc + i * v3, v2, 1, v, v, v, v2);       // w_ikj[a,c,b]
+    mm(Wq, v, v, v, 1.0, 1.0, T2o + (j * o + i) * v2, 1, v, Vaibc + k * v2, o * v2, 1, v, v, v, v2);   // w_kij[c,a,b]
+    mm(Wq, v, v2, v, 1.0, 1.0, T2o + (i * o + k) * v2, 1, v, Viabc + j * v3, v2, 1, v2);               // w_jki[b,c,a]
+    mm(Wq, v, v2, v, 1.0, 1.0, T2o + (i * o + j) * v2, 1, v, Vaibc + k * v2, o * v2, 1, v2);           // w_kji[c,b,a]
+    // hole products (K = o)
+    mm(Wq, v, v2, o, -1.0, 1.0, Vijak + (i * o + j) * v * o, o, 1, T2h + k * v2, o * v2, 1, v2);       // w_ijk[a,b,c]
+    mm(Wq, v, v2, o, -1.0, 1.0, Vijak + (i * o + k) * v * o, o, 1, T2h + j * o * v2, v2, 1, v2);       // w_ikj[a,c,b]
+    mm(Wq, v, v, o, -1.0, 1.0, Vijak + (j * o + i) * v * o, o, 1, T2h + k * v2, o * v2, 1, v, v, v, v2);   // w_jik[b,a,c]
+    mm(Wq, v, v, o, -1.0, 1.0, Vijak + (j * o + k) * v * o, o, 1, T2h + i * o * v2, v2, 1, v, v, v, v2);   // w_jki[b,c,a]
+    mm(Wq, v2, v, o, -1.0, 1.0, T2h + j * v2, 1, o * v2, Vijak + (k * o + i) * v * o, 1, o, v);         // w_kij[c,a,b]
+    mm(Wq, v2, v, o, -1.0, 1.0, T2h + i * o * v2, 1, v2, Vijak + (k * o + j) * v * o, 1, o, v);         // w_kji[c,b,a]
+}
 }  // namespace
 
 void Engine::check_hermitian(const char* who, const char* why) {
@@ -2350,52 +2398,121 @@ double Engine::ccsd_t(const double* eps_host, const double* t1, const double* t2
     batch = std::min<int64_t>({batch, t_end - t_begin, 65535});
     double* W = bufs.get(batch * v3);
     double* partial = bufs.get(dev::triples_partial_doubles(nv, batch));
-    const double* Viabc = V_[P_iabc];
-    const double* Vaibc = V_[P_aibc];
-    const double* Vijak = V_[P_ijak];
-    auto mm = [&](double* C, int64_t M, int64_t N, int64_t K, double alpha, double beta, const double* A, int64_t a_sm,
-                  int64_t a_sk, const double* B, int64_t b_sk, int64_t b_sn, int64_t ldc, int64_t nb = 1, int64_t b_b = 0,
-                  int64_t c_b = 0) {
-        dev::Gemm g{};
-        g.M = M; g.N = N; g.K = K;
-        g.alpha = alpha; g.beta = beta;
-        g.A = A; g.a_sm = a_sm; g.a_sk = a_sk;
-        g.B = B; g.b_sk = b_sk; g.b_sn = b_sn;
-        g.C = C; g.ldc = ldc;
-        g.nb1 = nb; g.nb2 = 1;
-        g.a_b1 = 0; g.b_b1 = b_b; g.c_b1 = c_b;
-        g.a_b2 = g.b_b2 = g.c_b2 = 0;
-        g.splitk_ws = nullptr;          // no k-split: the order of every sum is that of the tile kernel alone
-        g.splitk_ws_doubles = 0;
-        dev::gemm(g, stream);
-        stats.gemm_calls++;
-        stats.gemm_flops += 2.0 * (double)M * (double)N * (double)K * (double)nb;
-    };
+    const TriplesOperands ops{V_[P_iabc], V_[P_aibc], V_[P_ijak], T2o, T2h};
     for (int64_t t0 = t_begin; t0 < t_end; t0 += batch) {
         const int64_t nt = std::min(batch, t_end - t0);
         for (int64_t q = 0; q < nt; ++q) {
             int i, j, k;
             unrank_triple(t0 + q, i, j, k);
-            double* Wq = W + q * v3;
-            // W[a][b][c] = w_ijk[abc] + w_jik[bac] + w_ikj[acb] + w_kij[cab] + w_jki[bca] + w_kji[cba], each w_pqr[x,y,z] =
-            //   sum_f V_iabc[p,f,x,y] T2o[r][q][f][z] - sum_m V_ijak[p,q,x,m] T2h[m][r][y][z]
-            // written with the unit-stride index c as N: V_iabc[p,f,y,x] = V_aibc[f,p,x,y] supplies the swapped pairs.
-            // particle products (K = v)
-            mm(Wq, v2, v, v, 1.0, 0.0, Viabc + i * v3, 1, v2, T2o + (k * o + j) * v2, v, 1, v);                 // w_ijk[a,b,c]
-            mm(Wq, v2, v, v, 1.0, 1.0, Vaibc + j * v2, 1, o * v2, T2o + (k * o + i) * v2, v, 1, v);             // w_jik[b,a,c]
-            mm(Wq, v, v, v, 1.0, 1.0, T2o + (j * o + k) * v2, 1, v, Viabc + i * v3, v2, 1, v, v, v, v2);       // w_ikj[a,c,b]
-            mm(Wq, v, v, v, 1.0, 1.0, T2o + (j * o + i) * v2, 1, v, Vaibc + k * v2, o * v2, 1, v, v, v, v2);   // w_kij[c,a,b]
-            mm(Wq, v, v2, v, 1.0, 1.0, T2o + (i * o + k) * v2, 1, v, Viabc + j * v3, v2, 1, v2);               // w_jki[b,c,a]
-            mm(Wq, v, v2, v, 1.0, 1.0, T2o + (i * o + j) * v2, 1, v, Vaibc + k * v2, o * v2, 1, v2);           // w_kji[c,b,a]
-            // hole products (K = o)
-            mm(Wq, v, v2, o, -1.0, 1.0, Vijak + (i * o + j) * v * o, o, 1, T2h + k * v2, o * v2, 1, v2);       // w_ijk[a,b,c]
-            mm(Wq, v, v2, o, -1.0, 1.0, Vijak + (i * o + k) * v * o, o, 1, T2h + j * o * v2, v2, 1, v2);       // w_ikj[a,c,b]
-            mm(Wq, v, v, o, -1.0, 1.0, Vijak + (j * o + i) * v * o, o, 1, T2h + k * v2, o * v2, 1, v, v, v, v2);   // w_jik[b,a,c]
-            mm(Wq, v, v, o, -1.0, 1.0, Vijak + (j * o + k) * v * o, o, 1, T2h + i * o * v2, v2, 1, v, v, v, v2);   // w_jki[b,c,a]
-            mm(Wq, v2, v, o, -1.0, 1.0, T2h + j * v2, 1, o * v2, Vijak + (k * o + i) * v * o, 1, o, v);         // w_kij[c,a,b]
-            mm(Wq, v2, v, o, -1.0, 1.0, T2h + i * o * v2, 1, v2, Vijak + (k * o + j) * v * o, 1, o, v);         // w_kji[c,b,a]
+            triples_W(*this, W + q * v3, i, j, k, ops);
         }
         dev::triples_energy(W, nt, t0, t1 ? V_[P_ijab] : nullptr, t1, eps, partial, out + (t0 - t_begin), no, nv, stream);
+    }
+    // the sum over the range in a fixed order (the same whatever the batch)
+    std::vector<double> h(t_end - t_begin);
+    dev::memcpy_d2h(h.data(), out, sizeof(double) * h.size(), stream);
+    dev::stream_sync(stream);
+    double e = 0.0;
+    for (double x : h) e += x;
+    return e;
+}
+
+// ---- Lambda-CCSD(T): include/pymes_amd.h, pymes_ccsd_t_lambda (the formulas there and in tests/_lambda_triples_reference.py) ----
+double Engine::ccsd_t_lambda(const double* eps_host, const double* t2, const double* lam1, const double* lam2, int64_t t_begin,
+                             int64_t t_end, double* per_triple) {
+    const char* who = "ccsd_t_lambda";
+    if (capturing_) throw Error("ccsd_t_lambda reads its energy back: not inside a launch graph");
+    if (!eps_host) throw Error("ccsd_t_lambda: null pointer: eps");
+    if (!t2) throw Error("ccsd_t_lambda: null pointer: t2");
+    if (!lam2) throw Error("ccsd_t_lambda: null pointer: lam2");
+    const int64_t ntot = triples_count(no);
+    if (t_begin < 0 || t_end < t_begin || t_end > ntot)
+        throw Error("ccsd_t_lambda: triple range [" + std::to_string(t_begin) + ", " + std::to_string(t_end) + ") outside [0, " +
+                    std::to_string(ntot) + ")");
+    constexpr int P_aijk = 8;
+    // the UNDRESSED blocks only: the five the products read, then their partners under (p,q,r,s) -> (q,p,s,r)
+    for (int pat : {P_iabc, P_aibc, P_ijak, P_abic, P_aijk, P_ijka, P_abci, P_iajk})
+        if (!V_[pat])
+            throw Error("ccsd_t_lambda needs the undressed integral block '" + canonical_name(pat) + "', which has not been set");
+    if (lam1 && !V_[P_ijab]) throw Error("ccsd_t_lambda needs the undressed integral block 'ijab', which has not been set");
+    const int64_t o = no, v = nv, v2 = v * v, v3 = v2 * v;
+    // V_pqrs = V_qpsr on what is read: the closed-shell formula rests on it (and on nothing else: no V_pqrs = V_rspq)
+    {
+        struct Pair { int a, b; int64_t d[4]; const char* what; };
+        const Pair pairs[] = {{P_iabc, P_aibc, {o, v, v, v}, "V_iabc[i,a,b,c] - V_aibc[a,i,c,b]"},
+                              {P_ijak, P_ijka, {o, o, v, o}, "V_ijak[i,j,a,k] - V_ijka[j,i,k,a]"},
+                              {P_abic, P_abci, {v, v, o, v}, "V_abic[a,b,i,c] - V_abci[b,a,c,i]"},
+                              {P_aijk, P_iajk, {v, o, o, o}, "V_aijk[a,i,j,k] - V_iajk[i,a,k,j]"},
+                              {P_ijab, P_ijab, {o, o, v, v}, "V_ijab[i,j,a,b] - V_ijab[j,i,b,a]"}};
+        for (const Pair& pr : pairs) {
+            if (pr.a == P_ijab && !lam1) continue;
+            double r[2];
+            dev::exchange_asymmetry(V_[pr.a], V_[pr.b], pr.d, r, stream);
+            if (!(r[0] <= 1e-10 * r[1])) {
+                char buf[400];
+                snprintf(buf, sizeof buf, "%s needs integrals with V_pqrs = V_qpsr: max |%s| = %.3e against max |V| = %.3e", who,
+                         pr.what, r[0], r[1]);
+                throw Error(buf);
+            }
+        }
+    }
+    if (t_end == t_begin) return 0.0;
+    DevBufs bufs;
+    // right amplitudes: T2o[x][y][f][z] = T[z,f,x,y], T2h[m][k][b][c] = T[b,c,m,k], as in ccsd_t
+    double* T2o = bufs.get(o * o * v2);
+    double* T2h = bufs.get(o * o * v2);
+    const TView Tv = make_view(t2, {v, v, o, o});
+    permute(1.0, Tv, "zfxy", 0.0, make_view(T2o, {o, o, v, v}), "xyfz");
+    permute(1.0, Tv, "bcmk", 0.0, make_view(T2h, {o, o, v, v}), "mkbc");
+    // left amplitudes in the same two layouts: L[a,b,i,j] = (2 lam2[a,b,i,j] + lam2[b,a,i,j]) / 3, l1 = lam1 / 2
+    double* L2o = bufs.get(o * o * v2);
+    double* L2h = bufs.get(o * o * v2);
+    const TView Lv = make_view(lam2, {v, v, o, o});
+    permute(2.0 / 3.0, Lv, "zfxy", 0.0, make_view(L2o, {o, o, v, v}), "xyfz");
+    permute(1.0 / 3.0, Lv, "fzxy", 1.0, make_view(L2o, {o, o, v, v}), "xyfz");
+    permute(2.0 / 3.0, Lv, "bcmk", 0.0, make_view(L2h, {o, o, v, v}), "mkbc");
+    permute(1.0 / 3.0, Lv, "cbmk", 1.0, make_view(L2h, {o, o, v, v}), "mkbc");
+    double* l1 = nullptr;
+    if (lam1) {
+        l1 = bufs.get(v * o);
+        permute(0.5, make_view(lam1, {v, o}), "ai", 0.0, make_view(l1, {v, o}), "ai");
+    }
+    // the excitation-type blocks in the layouts of the de-excitation-type ones, so that the right triples are the products of
+    // the left ones (and of ccsd_t), stride for stride: R1[i,f,a,b] = V_abic[a,b,i,f], R1s[f,i,a,b] = V_abic[b,a,i,f],
+    // R2[i,j,a,m] = V_aijk[a,m,i,j].  Two o v^3 copies per call (3.2 GB each at (50,200)), released on return.
+    double* R1 = bufs.get(o * v3);
+    double* R1s = bufs.get(o * v3);
+    double* R2 = bufs.get(o * o * o * v);
+    permute(1.0, block(P_abic), "abif", 0.0, make_view(R1, {o, v, v, v}), "ifab");
+    permute(1.0, block(P_abic), "baif", 0.0, make_view(R1s, {v, o, v, v}), "fiab");
+    permute(1.0, block(P_aijk), "amij", 0.0, make_view(R2, {o, o, v, o}), "ijam");
+    double* eps = bufs.get(n);
+    dev::memcpy_h2d(eps, eps_host, sizeof(double) * n, stream);
+    double* out = per_triple ? per_triple : bufs.get(t_end - t_begin);
+    // batch: WR and WL of that many triples are held, so the default is half of ccsd_t's for the same 128 MB; each array
+    // is built by products of its own triple alone (the per-triple values do not depend on the batch)
+    int64_t batch = 0;
+    if (const char* e = getenv("PYMES_TRIPLES_BATCH")) batch = atoll(e);
+    if (batch <= 0) {
+        const double budget = std::min(128.0 * (1 << 20), 0.25 * (double)dev::mem_free_bytes());
+        batch = std::max<int64_t>(1, (int64_t)(budget / (16.0 * (double)v3)));
+    }
+    batch = std::min<int64_t>({batch, t_end - t_begin, 65535});
+    double* WR = bufs.get(batch * v3);
+    double* WL = bufs.get(batch * v3);
+    double* partial = bufs.get(dev::triples_partial_doubles(nv, batch));
+    const TriplesOperands right{R1, R1s, R2, T2o, T2h};
+    const TriplesOperands left{V_[P_iabc], V_[P_aibc], V_[P_ijak], L2o, L2h};
+    for (int64_t t0 = t_begin; t0 < t_end; t0 += batch) {
+        const int64_t nt = std::min(batch, t_end - t0);
+        for (int64_t q = 0; q < nt; ++q) {
+            int i, j, k;
+            unrank_triple(t0 + q, i, j, k);
+            triples_W(*this, WR + q * v3, i, j, k, right);
+            triples_W(*this, WL + q * v3, i, j, k, left);
+        }
+        dev::lambda_triples_energy(WR, WL, nt, t0, l1 ? V_[P_ijab] : nullptr, l1, eps, partial, out + (t0 - t_begin), no, nv,
+                                   stream);
     }
     // the sum over the range in a fixed order (the same whatever the batch)
     std::vector<double> h(t_end - t_begin);

@@ -250,6 +250,12 @@ void ladder_pack_V_factors(const double* B, double* Vp, double* Vm, int naux, in
 int64_t triples_partial_doubles(int nv, int64_t nt);
 void triples_energy(const double* W, int64_t nt, int64_t t0, const double* Vijab, const double* t1, const double* eps,
                     double* partial, double* out, int no, int nv, stream_t s);
+// ---- Lambda-CCSD(T) (cc.cpp, Engine::ccsd_t_lambda): the same batch with two arrays.  WR [nt][v][v][v] holds the right
+// triples (from the excitation-type blocks and T), WL the left ones (from the de-excitation-type blocks and L); YL = WL + the
+// disconnected term with l1 [v,o] in place of t1 (null: YL = WL).  out[q] = m_ijk / 3 sum_abc WR R(YL) / D; scratch, limits and
+// the fixed summation order as for triples_energy.  The product library only (a weak definition in the engine throws).
+void lambda_triples_energy(const double* WR, const double* WL, int64_t nt, int64_t t0, const double* Vijab, const double* l1,
+                           const double* eps, double* partial, double* out, int no, int nv, stream_t s);
 // ---- frozen natural orbitals (cc.cpp, Engine::fno_density): over the occupied window [nf, no) and all nv virtuals, with
 // t[a,b,i,j] = V_ijab[i,j,a,b] / (eps_o[i] + eps_o[j] - eps_v[a] - eps_v[b]) formed on the fly (no amplitude array),
 //   D[a][b] = 2 sum_{c,i,j} (2 t[a,c,i,j] - t[c,a,i,j]) t[b,c,i,j]   (exactly symmetric),   e[0] = sum (2 t_abij - t_baij) V_ijab

@@ -793,6 +793,10 @@ __attribute__((weak)) void triples_energy(const double*, int64_t, int64_t, const
                                           double*, int, int, stream_t) {
     throw std::runtime_error("triples_energy: not available in this backend");
 }
+__attribute__((weak)) void lambda_triples_energy(const double*, const double*, int64_t, int64_t, const double*, const double*,
+                                                 const double*, double*, double*, int, int, stream_t) {
+    throw std::runtime_error("lambda_triples_energy: not available in this backend");
+}
 // ... and without the FNO density kernel
 __attribute__((weak)) int64_t fno_density_partial_doubles(int, int) { return 1; }
 __attribute__((weak)) void fno_density(const double*, const double*, const double*, int, int, int, double*, double*, double*,

@@ -365,6 +365,12 @@ class Engine {
     // m_ijk S_ijk of the range.  Synchronises the stream; everything it allocates is released on return.
     static int64_t triples_count(int no);
     double ccsd_t(const double* eps_host, const double* t1, const double* t2, int64_t t_begin, int64_t t_end, double* per_triple);
+    // Lambda-CCSD(T) (include/pymes_amd.h, pymes_ccsd_t_lambda): the same sum with the left triples from the blocks iabc, aibc,
+    // ijak and L, l1 (converted from the library's lam2 [v,v,o,o], lam1 [v,o]; lam1 may be null) and the right triples from
+    // abic, aijk and t2; the blocks ijka, abci, iajk (ijab with lam1) only for the check of V_pqrs = V_qpsr.  No V_abcd, no
+    // Hermiticity.  Synchronises the stream; everything it allocates is released on return.
+    double ccsd_t_lambda(const double* eps_host, const double* t2, const double* lam1, const double* lam2, int64_t t_begin,
+                         int64_t t_end, double* per_triple);
     // V_pqrs = V_rspq on the undressed blocks iabc / abic and ijak / aijk (throws, naming `who` and `why`, otherwise)
     void check_hermitian(const char* who, const char* why);
     // frozen natural orbitals (include/pymes_amd.h): pymes_fno_density (Vijab: device [no,no,nv,nv], null = the context's own

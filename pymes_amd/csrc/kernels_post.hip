@@ -94,6 +94,66 @@ __global__ void __launch_bounds__(64) triples_orbit_kernel(const double* __restr
     if (threadIdx.x == 0) partial[q * npairs + p] = acc;
 }
 
+// Lambda-CCSD(T) (cc.cpp, Engine::ccsd_t_lambda): the mapping of triples_orbit_kernel with two arrays.  The right triples w_k
+// come from WR, the left ones y_k = WL + the disconnected term of l1 (formed on the fly, as above with l1 for t1); the orbit
+// contributes sum_k wR_k R_k(yL) / D with the same parity-class form of R and the same multiplicities.
+__global__ void __launch_bounds__(64) lambda_triples_orbit_kernel(const double* __restrict__ WR, const double* __restrict__ WL,
+                                                                  long t0, const double* __restrict__ Vijab,
+                                                                  const double* __restrict__ l1, const double* __restrict__ eps,
+                                                                  double* __restrict__ partial, int no, int nv, long npairs) {
+    const long p = blockIdx.x;
+    const long q = blockIdx.y;
+    int a, b, i, j, k;
+    unrank_pair(p, a, b);
+    unrank_triple(t0 + q, i, j, k);
+    const long v = nv, v2 = v * v;
+    const double* __restrict__ Rq = WR + q * v2 * v;
+    const double* __restrict__ Lq = WL + q * v2 * v;
+    const double dab = eps[i] + eps[j] + eps[k] - eps[no + a] - eps[no + b];
+    const double* Vjk = nullptr;
+    const double* Vik = nullptr;
+    const double* Vij = nullptr;
+    double lai = 0.0, lbi = 0.0, laj = 0.0, lbj = 0.0, lak = 0.0, lbk = 0.0;
+    if (l1) {
+        Vjk = Vijab + ((long)j * no + k) * v2;
+        Vik = Vijab + ((long)i * no + k) * v2;
+        Vij = Vijab + ((long)i * no + j) * v2;
+        lai = l1[(long)a * no + i]; lbi = l1[(long)b * no + i];
+        laj = l1[(long)a * no + j]; lbj = l1[(long)b * no + j];
+        lak = l1[(long)a * no + k]; lbk = l1[(long)b * no + k];
+    }
+    double acc = 0.0;
+    for (int c = threadIdx.x; c <= b; c += 64) {
+        const long A = a, B = b, Cc = c;
+        const long x[6] = {A * v2 + B * v + Cc, B * v2 + Cc * v + A, Cc * v2 + A * v + B,
+                           Cc * v2 + B * v + A, A * v2 + Cc * v + B, B * v2 + A * v + Cc};
+        double w[6], y[6];
+#pragma unroll
+        for (int u = 0; u < 6; ++u) {
+            w[u] = Rq[x[u]];
+            y[u] = Lq[x[u]];
+        }
+        if (l1) {
+            const double lci = l1[Cc * no + i], lcj = l1[Cc * no + j], lck = l1[Cc * no + k];
+            // disc(x,y,z) = V_jk[y,z] l1[x,i] + V_ik[x,z] l1[y,j] + V_ij[x,y] l1[z,k]
+            y[0] += Vjk[B * v + Cc] * lai + Vik[A * v + Cc] * lbj + Vij[A * v + B] * lck;     // (a,b,c)
+            y[1] += Vjk[Cc * v + A] * lbi + Vik[B * v + A] * lcj + Vij[B * v + Cc] * lak;     // (b,c,a)
+            y[2] += Vjk[A * v + B] * lci + Vik[Cc * v + B] * laj + Vij[Cc * v + A] * lbk;     // (c,a,b)
+            y[3] += Vjk[B * v + A] * lci + Vik[Cc * v + A] * lbj + Vij[Cc * v + B] * lak;     // (c,b,a)
+            y[4] += Vjk[Cc * v + B] * lai + Vik[A * v + B] * lcj + Vij[A * v + Cc] * lbk;     // (a,c,b)
+            y[5] += Vjk[A * v + Cc] * lbi + Vik[B * v + Cc] * laj + Vij[B * v + A] * lck;     // (b,a,c)
+        }
+        const double se = y[0] + y[1] + y[2], so = y[3] + y[4] + y[5];
+        const double re = se - 2.0 * so, ro = so - 2.0 * se;
+        double s = w[0] * (3.0 * y[0] + re) + w[1] * (3.0 * y[1] + re) + w[2] * (3.0 * y[2] + re) +
+                   w[3] * (3.0 * y[3] + ro) + w[4] * (3.0 * y[4] + ro) + w[5] * (3.0 * y[5] + ro);
+        const double inv_mult = (a == b && b == c) ? (1.0 / 6.0) : ((a == b || b == c) ? 0.5 : 1.0);
+        acc += s * inv_mult / (dab - eps[no + c]);
+    }
+    acc = wave_sum(acc);
+    if (threadIdx.x == 0) partial[q * npairs + p] = acc;
+}
+
 // out[q] = m_ijk / 3 * sum_p partial[q][p], summed in a fixed order
 __global__ void __launch_bounds__(256) triples_sum_kernel(const double* __restrict__ partial, long t0, long npairs,
                                                           double* __restrict__ out) {
@@ -127,6 +187,21 @@ void triples_energy(const double* W, int64_t nt, int64_t t0, const double* Vijab
     hipStream_t st = (hipStream_t)s;
     launch_kernel(triples_orbit_kernel, dim3((unsigned)npairs, (unsigned)nt), dim3(64), 0, st, W, (long)t0, Vijab, t1, eps,
                  partial, no, nv, npairs);
+    launch_kernel(triples_sum_kernel, dim3((unsigned)nt), dim3(256), 0, st, (const double*)partial, (long)t0, npairs, out);
+}
+
+void lambda_triples_energy(const double* WR, const double* WL, int64_t nt, int64_t t0, const double* Vijab, const double* l1,
+                           const double* eps, double* partial, double* out, int no, int nv, stream_t s) {
+    if (nt <= 0) return;
+    if (!WR || !WL || !eps || !partial || !out || (l1 && !Vijab)) throw std::runtime_error("lambda_triples_energy: null operand");
+    const int64_t ntot = (int64_t)no * (no + 1) * (no + 2) / 6;
+    if (no < 1 || nv < 1 || t0 < 0 || t0 + nt > ntot)
+        throw std::runtime_error("lambda_triples_energy: bad shape or triple range");
+    const long npairs = (long)nv * (nv + 1) / 2;
+    if (nt > 65535 || npairs > 0x7fffffffL) throw std::runtime_error("lambda_triples_energy: grid too large");
+    hipStream_t st = (hipStream_t)s;
+    launch_kernel(lambda_triples_orbit_kernel, dim3((unsigned)npairs, (unsigned)nt), dim3(64), 0, st, WR, WL, (long)t0, Vijab, l1,
+                  eps, partial, no, nv, npairs);
     launch_kernel(triples_sum_kernel, dim3((unsigned)nt), dim3(256), 0, st, (const double*)partial, (long)t0, npairs, out);
 }
 

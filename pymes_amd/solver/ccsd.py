@@ -481,7 +481,9 @@ class CCSD(ccd.CCD):
         orbitals with at least that MP2 occupation / the first ``fno_nv`` of them (pymes_amd/solver/fno.py).  With any of
         the three the solve runs in that space: "ccsd e", "(t) e", "t1", "t2", "hole e" and "particle e" are those of the
         correlated space (new orbitals), "fno nv" is its number of virtuals and "fno dmp2 e" the MP2 energy of the dropped
-        virtuals (0.0 with the core frozen only); the total is "ccsd(t) e" + "fno dmp2 e".  ``density=True`` adds "lambda1",
+        virtuals (0.0 with the core frozen only); the total is "ccsd(t) e" + "fno dmp2 e".  ``triples="lambda"`` adds
+        "lambda (t) e", "ccsd(t)_lambda e" (Lambda-CCSD(T), pymes_amd/solver/ccsd_t.py: also for transcorrelated integrals,
+        which ``triples=True`` refuses), "lambda1" and "lambda2".  ``density=True`` adds "lambda1",
         "lambda2" (the solution of the Lambda equations), "rdm1" (the one-particle response density plus 2 on the occupied
         diagonal, [n,n], not symmetric) and "natural occupations" (eigenvalues of its symmetric part, descending), of the
         correlated space; ``lambda_r_epsilon`` is the residual norm at which the Lambda iteration stops.  Sources: a host V_pqrs or
@@ -509,6 +511,15 @@ class CCSD(ccd.CCD):
             if self.shard_integrals:
                 raise ValueError("dyson=True with shard_integrals=True: the Lambda equations read the whole V_abcd, which an "
                                  "integral-sharded context does not hold")
+        if isinstance(kwargs.get("triples"), str):          # likewise: triples="lambda" is Lambda-CCSD(T)
+            if kwargs["triples"] != "lambda":
+                raise ValueError("triples=%r: expected True ((T)), \"lambda\" (Lambda-CCSD(T)) or False" % (kwargs["triples"],))
+            if self.is_dcd:
+                raise ValueError("triples=\"lambda\": the Lambda equations are those of the CCSD similarity transform, not "
+                                 "defined for DCSD")
+            if self.shard_integrals:
+                raise ValueError("triples=\"lambda\" with shard_integrals=True: the Lambda equations read the whole V_abcd, "
+                                 "which an integral-sharded context does not hold")
         if frozen_core or fno_occ_threshold is not None or fno_nv is not None:
             return self._solve_fno(t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv,
                                    **kwargs)
@@ -517,10 +528,15 @@ class CCSD(ccd.CCD):
         max_iter = kwargs.get("max_iter", self.max_iter)
         delta_e = kwargs.get("delta_e", self.delta_e)
         # triples=True (opt-in): the (T) correction of the converged amplitudes (pymes_amd/solver/ccsd_t.py)
-        triples = bool(kwargs.get("triples", False))
+        # triples="lambda" (opt-in): Lambda-CCSD(T), the triples correction with Lambda as the left state — the one defined for
+        # transcorrelated integrals; Lambda is solved once and shared with density=True, ee_roots and dyson
+        lambda_t = isinstance(kwargs.get("triples"), str)
+        triples = bool(kwargs.get("triples", False)) and not lambda_t
         if triples:
             if self.is_dcd:
                 raise ValueError("triples=True: (T) is defined for CCSD amplitudes, not for DCSD")
+            ccsd_t.check_canonical(self.no, t_fock_pq, kwargs.get("canonical_tol", 1e-6))
+        if lambda_t:
             ccsd_t.check_canonical(self.no, t_fock_pq, kwargs.get("canonical_tol", 1e-6))
         # ip_roots=k / ea_roots=m (opt-in): the k lowest ionisation potentials / m lowest electron affinities of the converged
         # state (pymes_amd/solver/eom_ip_ea.py); with frozen_core / fno_* they are those of the correlated space
@@ -542,7 +558,7 @@ class CCSD(ccd.CCD):
         # frozen_core / fno_* those of the correlated space; with density=True Lambda is solved once (dyson_r_epsilon=x: the
         # relative residual norm at which the Davidson runs stop, default 1e-8)
         dyson = bool(kwargs.get("dyson", False))
-        if density or ee_roots or dyson:                   # (the left assembly's cap on nocc: before a context exists)
+        if density or ee_roots or dyson or lambda_t:       # (the left assembly's cap on nocc: before a context exists)
             from pymes_amd.solver import lambda_ccsd
             lambda_ccsd.check_occupied(self.no, "EOM_CCSD_Transitions" if ee_roots and not density else "Lambda_CCSD")
         ints, own = self._integrals(t_fock_pq, t_V_pqrs)
@@ -550,7 +566,7 @@ class CCSD(ccd.CCD):
         st = None
         collector = ccd.quiet_collector().__enter__()      # no 40-ms generation-2 collection in the middle of an iteration
         try:
-            if density:
+            if density or lambda_t:
                 from pymes_amd.solver import lambda_ccsd
                 lambda_ccsd.check_context(ctx)             # (a sharded DeviceIntegrals of the caller: before anything is dressed)
             if ee_roots:
@@ -609,7 +625,16 @@ class CCSD(ccd.CCD):
             if ip_roots or ea_roots:
                 e_ip, e_ea = self._ip_ea_roots(t_fock_pq, ints, st["t1"], st["t2"], ip_roots, ea_roots,
                                                kwargs.get("ip_ea_r_epsilon"))
-            lam = self._lambda_density(t_fock_pq, ints, st, kwargs.get("lambda_r_epsilon")) if density else None
+            lam = None
+            if density or lambda_t:
+                lam = self._lambda_density(t_fock_pq, ints, st, kwargs.get("lambda_r_epsilon"), with_density=density)
+            e_lt = None
+            if lambda_t:
+                time_t = time.time()
+                e_lt = ccsd_t.get_lambda_triples_energy(self.no, t_fock_pq, ints, st["t2"], lam["lambda1"], lam["lambda2"],
+                                                        canonical_tol=kwargs.get("canonical_tol", 1e-6))
+                print_logging_info("Lambda-(T) correction = {:.12f} ({:.3f} seconds)".format(e_lt, time.time() - time_t),
+                                   level=1)
             ee = self._ee_transitions(t_fock_pq, ints, st, ee_roots, kwargs.get("ee_r_epsilon"), lam) if ee_roots else None
             dy = self._dyson(t_fock_pq, ints, st, ip_roots, ea_roots, kwargs.get("dyson_r_epsilon"), lam) if dyson else None
             if kwargs.get("device_amplitudes"):
@@ -633,6 +658,9 @@ class CCSD(ccd.CCD):
             if triples:
                 res["(t) e"] = e_t
                 res["ccsd(t) e"] = e_ccsd + e_t
+            if lambda_t:
+                res["lambda (t) e"] = e_lt
+                res["ccsd(t)_lambda e"] = e_ccsd + e_lt
             if e_ip is not None:
                 res["ip e"] = e_ip
             if e_ea is not None:
@@ -676,10 +704,10 @@ class CCSD(ccd.CCD):
                 self.ea_solver = solver
         return out
 
-    def _lambda_density(self, t_fock_pq, ints, st, r_epsilon=None):
+    def _lambda_density(self, t_fock_pq, ints, st, r_epsilon=None, with_density=True):
         """Lambda and the one-particle density of the converged amplitudes on the integrals' context (device hand-over: the
         Fock matrix and the ten blocks of the sigma build are T1-dressed in HBM), with the orbital energies and the level
-        shift of the amplitude update."""
+        shift of the amplitude update.  ``with_density=False``: Lambda alone (triples="lambda" without density=True)."""
         from pymes_amd.solver import lambda_ccsd
         f = t_fock_pq.get() if isinstance(t_fock_pq, DeviceArray) else np.asarray(t_fock_pq, dtype=np.float64)
         t1, t2 = st["t1"], st["t2"]
@@ -690,6 +718,9 @@ class CCSD(ccd.CCD):
         dressed = self.get_T1_dressed_V(t1, ints, solver.BLOCKS)
         out = solver.solve(fd, dressed, t2, eps=(st["eps_i"], st["eps_a"]), level_shift=st["level_shift"])
         self.lambda_solver = solver                      # (residual norm, history, expectation() of the last solve)
+        if not with_density:
+            solver.t2 = None
+            return {"lambda1": out["lambda1"], "lambda2": out["lambda2"]}
         rdm1 = solver.rdm1(t1, ctx=ints.ctx)
         solver.t2 = None                                 # (the solver's T2 buffer goes back to the pool; the results are host arrays)
         return {"lambda1": out["lambda1"], "lambda2": out["lambda2"], "rdm1": rdm1,

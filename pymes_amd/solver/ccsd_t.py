@@ -3,7 +3,10 @@
 Closed shell, canonical orbitals: the energy is a sum over the o(o+1)(o+2)/6 unique occupied triples i >= j >= k of
 m_ijk S_ijk, each formed from the undressed integral blocks and the amplitudes in HBM (W_ijk by fp64 MFMA products, the
 energy of a batch of triples by one kernel).  With ``torch.distributed`` initialised (one process per GPU) every rank sums
-a contiguous chunk of the triples and one double is all-reduced."""
+a contiguous chunk of the triples and one double is all-reduced.
+
+``get_lambda_triples_energy`` is Lambda-CCSD(T) (pymes_ccsd_t_lambda): the same sum with Lambda as the left state, the
+triples correction that is defined for transcorrelated (non-Hermitian) integrals, which (T) refuses."""
 import ctypes as C
 
 import numpy as np
@@ -72,6 +75,35 @@ def triples_energy(ctx, eps, t1, t2, t_begin, t_end, per_triple=False):
     return float(e.value), vec
 
 
+def lambda_triples_energy(ctx, eps, t2, lam1, lam2, t_begin, t_end, per_triple=False):
+    """pymes_ccsd_t_lambda on a context, as ``triples_energy``.  t2 / lam1 / lam2 are DeviceArrays of ``ctx`` (lam1 may be
+    None); lam1, lam2 in the library's normalisation (``Lambda_CCSD.solve``)."""
+    eps = np.ascontiguousarray(eps, dtype=np.float64)
+    assert eps.shape == (ctx.n,)
+    out = ctx.empty((max(t_end - t_begin, 1),)) if per_triple else None
+    e = C.c_double()
+    try:
+        ctx.lib.call("pymes_ccsd_t_lambda", ctx.handle, _lib.host_ptr(eps), C.c_void_p(t2.ptr),
+                     C.c_void_p(lam1.ptr if lam1 is not None else None), C.c_void_p(lam2.ptr), int(t_begin), int(t_end),
+                     C.c_void_p(out.ptr if out is not None else None), C.byref(e))
+        vec = out.get()[:t_end - t_begin] if out is not None else None
+    finally:
+        if out is not None:
+            out.free()
+    return float(e.value), vec
+
+
+def _triple_chunk(no, triple_range):
+    """(begin, end, all-reduce afterwards?) of a call: the given range, or this rank's chunk of all triples."""
+    reduce = triple_range is None and pdist.sharded() and not pdist.stubbed()
+    if triple_range is None:
+        rank, world, _ = pdist.world()
+        lo, hi = rank_range(no, rank, world) if reduce else (0, n_triples(no))
+    else:
+        lo, hi = int(triple_range[0]), int(triple_range[1])
+    return lo, hi, reduce
+
+
 def get_triples_energy(no, t_fock_pq, ints_or_V_pqrs, t1, t2, device=0, triple_range=None, per_triple=False,
                        canonical_tol=1e-6):
     """E(T) for the amplitudes (t1 [v,o] or None for CCD amplitudes, t2 [v,v,o,o] with T_abij = T_baji) and canonical
@@ -95,13 +127,44 @@ def get_triples_energy(no, t_fock_pq, ints_or_V_pqrs, t1, t2, device=0, triple_r
             temps.append(tmp)
         d2, tmp = _on_device(ctx, t2, (nv, nv, no, no), "t2")
         temps.append(tmp)
-        reduce = triple_range is None and pdist.sharded() and not pdist.stubbed()
-        if triple_range is None:
-            rank, world, _ = pdist.world()
-            lo, hi = rank_range(no, rank, world) if reduce else (0, n_triples(no))
-        else:
-            lo, hi = int(triple_range[0]), int(triple_range[1])
+        lo, hi, reduce = _triple_chunk(no, triple_range)
         e, vec = triples_energy(ctx, np.diag(f), d1, d2, lo, hi, per_triple)
+        if reduce:
+            e = float(pdist.allreduce_sum([e])[0])
+        return (e, vec) if per_triple else e
+    finally:
+        for t in temps:
+            if t is not None:
+                t.free()
+        if own:
+            ctx.close()
+
+
+def get_lambda_triples_energy(no, t_fock_pq, ints_or_V_pqrs, t2, lam1, lam2, device=0, triple_range=None, per_triple=False,
+                              canonical_tol=1e-6):
+    """E_Lambda(T) of Lambda-CCSD(T) for the amplitudes t2 [v,v,o,o], the library's Lambda (lam1 [v,o] or None, lam2
+    [v,v,o,o]: ``Lambda_CCSD.solve`` / ``CCSD.solve(density=True)``) and canonical f = t_fock_pq.  t1 does not enter.  The
+    integrals need V_pqrs = V_qpsr only: transcorrelated ones are served.  Arguments, ranges, ranks and the return value as
+    ``get_triples_energy``."""
+    f = check_canonical(no, t_fock_pq, canonical_tol)
+    own = not isinstance(ints_or_V_pqrs, DeviceIntegrals)
+    ints = DeviceIntegrals.from_V_pqrs(no, ints_or_V_pqrs, device=device) if own else ints_or_V_pqrs
+    ctx = ints.ctx
+    temps = []
+    try:
+        if f.shape != (ctx.n, ctx.n) or ctx.no != no:
+            raise ValueError("the Fock matrix is %s, the integrals are for %d occupied of %d orbitals" % (f.shape, ctx.no, ctx.n))
+        nv = ctx.nv
+        dev = []
+        for x, shape, what in ((t2, (nv, nv, no, no), "t2"), (lam1, (nv, no), "lam1"), (lam2, (nv, nv, no, no), "lam2")):
+            if x is None and what == "lam1":
+                dev.append(None)
+                continue
+            d, tmp = _on_device(ctx, x, shape, what)
+            dev.append(d)
+            temps.append(tmp)
+        lo, hi, reduce = _triple_chunk(no, triple_range)
+        e, vec = lambda_triples_energy(ctx, np.diag(f), dev[0], dev[1], dev[2], lo, hi, per_triple)
         if reduce:
             e = float(pdist.allreduce_sum([e])[0])
         return (e, vec) if per_triple else e

@@ -817,6 +817,47 @@ int pymes_lambda_step(pymes_eom* h, const double* lam1_dev, const double* lam2_d
                       double* err1_dev, double* err2_dev, double* norm_host);
 int pymes_rdm1(pymes_ctx* ctx, const double* t1_dev, const double* t2_dev, const double* lam1_dev, const double* lam2_dev,
                double ref, double* gamma_host);
+/* ---- the two-particle response density ---------------------------------------------------------------------------
+ * L(f, V) = E(f, V) + <lam1, R1(f, V)> + <lam2, R2(f, V)> of the block above with the integrals switched on is linear and
+ * homogeneous in (f, V).  G_pqrs = dL / dV_pqrs (f held fixed, all n^4 entries of V independent) and
+ *   Gamma_pqrs = (G_pqrs + G_qpsr) / 2:   L(f, V) = sum gamma_pq f_pq + sum Gamma_pqrs V_pqrs  for every V with V_pqrs = V_qpsr
+ * (gamma without the reference term; no factor 1/2; not hermitian and not symmetrised: V_pqrs = V_rspq is never assumed).  A
+ * formula in (t1, t2, lam1, lam2): they need not solve anything.  G is the sum of (t = T2, tt = 2 t - t^(ab), tau = t + t1 t1):
+ *   1 the coefficients of the T1-dressed blocks in <lam2, R2>:
+ *       abij: l2      klij: B[k,l,i,j] = sum l2[a,b,i,j] t[a,b,k,l]      abcd: sum_ij l2[a,b,i,j] t[c,d,i,j]
+ *       iajb[k,a,i,c] = -2 sum l2[a,b,i,j] t[c,b,k,j] - 2 sum l2[b,a,i,j] t[b,c,k,j]      iabj[k,b,c,j] = 2 sum l2[a,b,i,j] tt[a,c,i,k]
+ *       ijab[k,l,c,d] = sum B[k,l,i,j] t[c,d,i,j] + sum l2[a,b,i,j] t[a,d,k,j] t[c,b,i,l] + sum l2[a,b,i,j] tt[a,c,i,k] tt[d,b,l,j]
+ *                       - sum gvv[a,d] tt[a,c,l,k] + sum goo[l,i] tt[d,c,i,k] + 2 sum l2[a,b,i,j] t[d,a,k,i] (t[b,c,l,j] - t[c,b,l,j])
+ *       (gvv = 2 Xvv, goo = -2 Xoo of pymes_rdm1);
+ *   2 their back-transformation, the adjoint of the T1 dressing: a virtual bra index a of a dressed block sends -t1[a,k] times its
+ *     coefficient to the occupied source index k, an occupied ket index i sends +t1[c,i] times it to the virtual source c — index
+ *     by index, every subset of the transformable positions once (the abcd coefficient enters as sum_ij l2 tau, never as a v^4
+ *     array unless the abcd block itself is asked for);
+ *   3 the dressed-Fock part: with C the response density gamma without the energy's 2 t1 and C' = C without Xov in its ov block,
+ *       V[j,p,b,q] += 2 t1[b,j] C'[p,q],   V[j,p,q,b] -= t1[b,j] C[p,q],   V_iabj[j,a,b,i] += 2 t1[b,j] Xov[i,a]
+ *     (the last one: the reference dresses f_ov[i,a] with V_iabj[j,a,b,i]);
+ *   4 the direct terms: V_aibc[a,j,b,c] += l1[a,i] tt[b,c,i,j];  V_ijka[j,k,i,b] -= l1[a,i] tt[a,b,j,k];
+ *       V_ijab[k,j,b,c] -= (sum_a l1[a,i] t1[a,k]) tt[b,c,i,j];  V_ijab[j,k,c,b] -= (sum_i l1[a,i] t1[c,i]) tt[a,b,j,k];
+ *       V_ijab[i,j,a,b] += 2 tau[a,b,i,j] - tau[b,a,i,j]  (the energy).
+ * The full spin-summed two-particle density of E = sum h D1 + 1/2 sum V D with f = h + sum_i (2 V_piqi - V_piiq) is
+ *   D_pqrs = D_HF + 2 (gamma_pr n_qs + n_pr gamma_qs) - (gamma_ps n_qr + n_ps gamma_qr) + 2 Gamma_pqrs,
+ *   D_HF = 4 n_pr n_qs - 2 n_ps n_qr,  n the unit matrix on the occupied block (the host helper full_rdm2 of the Python package).
+ * pymes_rdm2: writes the blocks named in mask (bit = 8 p + 4 q + 2 r + s of the pattern, 1 for a virtual position: klij 0,
+ * ijka 1, ijab 3, iajk 4, iajb 5, iabj 6, iabc 7, abij 12, abic 13, abcd 15) to out_dev[bit], device arrays of the block's
+ * shape.  A block and its image under (pq,rs) -> (qp,sr) hold the same numbers (Gamma_aibc[a,i,b,c] = Gamma_iabc[i,a,c,b], ...):
+ * the six images (ijak, aijk, aibj, aijb, aibc, abci) are refused by name.  It reads no integral block (an integral-sharded
+ * context is served).  abcd (v^4 doubles) is built only when its bit is set.
+ * pymes_rdm2_expectation: *value_host = sum Gamma_pqrs W_pqrs over all sixteen blocks for the operator W held as the context's
+ * undressed blocks (pymes_set_V_*); W_pqrs = W_qpsr is tested and refused by name otherwise, as is an integral-sharded context.
+ * The abcd density is never built: sum Gamma_abcd W_abcd = sum l2[a,b,i,j] (sum_cd W_abcd tau[c,d,i,j]) with the inner sum
+ * through the pair-packed ladder on W's packed V+ / V- rows.
+ * Both refuse, by name and before any allocation: nocc > PYMES_NOCC_MAX_LAMBDA, a launch graph being recorded, lam2 or t2 without
+ * the exchange symmetry x_abij = x_baji, (pymes_rdm2) outputs that alias inputs or each other.  Identical calls give identical
+ * bits (no atomics, fixed summation order). */
+int pymes_rdm2(pymes_ctx* ctx, const double* t1_dev, const double* t2_dev, const double* lam1_dev, const double* lam2_dev,
+               unsigned mask, double* const* out_dev);
+int pymes_rdm2_expectation(pymes_ctx* ctx, const double* t1_dev, const double* t2_dev, const double* lam1_dev,
+                           const double* lam2_dev, double* value_host);
 /* ---- left EOM-CCSD eigenvectors and transition densities ------------------------------------------------------
  * Conventions of the block above.  For root k: A r_k = w_k r_k, A^T l_k = w_k l_k (pymes_eom_sigma_apply / _apply_left; with
  * k > 1 the left build sends all vectors through its large products as one GEMM each), <l_j, r_k> = delta_jk,

@@ -172,6 +172,8 @@ SIGNATURES = {
     "pymes_eom_sigma_apply_left": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     "pymes_lambda_step": (C.c_int, [C.c_void_p] * 5 + [C.c_double, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 5),
     "pymes_rdm1": (C.c_int, [C.c_void_p] * 5 + [C.c_double, C.c_void_p]),
+    "pymes_rdm2": (C.c_int, [C.c_void_p] * 5 + [C.c_uint, C.c_void_p]),
+    "pymes_rdm2_expectation": (C.c_int, [C.c_void_p] * 6),
     "pymes_ipea_sigma_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "pymes_ipea_sigma_flags": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pymes_ipea_sigma_apply": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),

@@ -1131,6 +1131,26 @@ int pymes_rdm1(pymes_ctx* ctx, const double* t1, const double* t2, const double*
     });
 }
 
+// ---- the two-particle density (eom.cpp, lambda_rdm2) -------------------------------------------------------------------
+int pymes_rdm2(pymes_ctx* ctx, const double* t1, const double* t2, const double* lam1, const double* lam2, unsigned mask,
+               double* const* out) {
+    return guarded([&] {
+        need(t1, "t1"); need(t2, "t2"); need(lam1, "lam1"); need(lam2, "lam2"); need(out, "out");
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("rdm2 while a launch graph is being recorded");
+        pymes::lambda_rdm2(e, t1, t2, lam1, lam2, mask, out);
+    });
+}
+int pymes_rdm2_expectation(pymes_ctx* ctx, const double* t1, const double* t2, const double* lam1, const double* lam2,
+                           double* value_host) {
+    return guarded([&] {
+        need(t1, "t1"); need(t2, "t2"); need(lam1, "lam1"); need(lam2, "lam2"); need(value_host, "value");
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("rdm2_expectation while a launch graph is being recorded");
+        *value_host = pymes::lambda_rdm2_expectation(e, t1, t2, lam1, lam2);
+    });
+}
+
 int pymes_tdm1(pymes_ctx* ctx, const double* t1, const double* t2, const double* lam1, const double* lam2, int k,
                const double* const* l1, const double* const* l2, const double* const* r1, const double* const* r2,
                double* gl_host, double* gr_host, double* r0_host) {

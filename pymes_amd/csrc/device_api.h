@@ -410,6 +410,31 @@ struct Tdm1Parts {
 };
 void tdm1_assemble(const Tdm1Parts& q, int k, int no, int nv, stream_t s);
 
+// ---- the CCSD two-particle density (eom.cpp, lambda_rdm2 / lambda_rdm2_expectation).  The product library only
+// (the host simulator has no definition: weak ones in the engine throw, by name).
+// Gamma_ijab in the [v,v,o,o] layout from G [v,v,o,o] (G[a,b,i,j]: the sum of the products that multiply V_ijab[i,j,a,b]),
+// Tt = 2 T - T^(ab) (the energy term), t1 [v,o] and the [v,o] matrices D2[b,j] = 2 (C_ov[j,b] - Xov[j,b]), Cv[a,j] = C_ov[j,a] of the
+// dressed-Fock part (C: the response density without the energy's 2 t1):
+//   g[i,j,a,b] = G[a,b,i,j] + Tt[a,b,i,j] + t1[a,i] (2 t1[b,j] + D2[b,j]) - t1[b,i] (t1[a,j] + Cv[a,j])
+//   out[a,b,i,j] = out[b,a,j,i] = (g[i,j,a,b] + g[j,i,b,a]) / 2
+// One launch, one block per virtual pair a >= b, o (o + 1) doubles of LDS; no atomics, fixed summation order.
+struct Rdm2Parts {
+    const double* G = nullptr; const double* Tt = nullptr; const double* t1 = nullptr; const double* D2 = nullptr;
+    const double* Cv = nullptr;
+    double* out = nullptr;
+};
+bool rdm2_assemble_ok(int no);         // the tiles fit the LDS: no <= PYMES_NOCC_MAX_LAMBDA
+void rdm2_assemble(const Rdm2Parts& q, int no, int nv, stream_t s);
+// ws[0 .. rdm2_contract_sums(n)) = w x the sums of G[e] W[e] over consecutive chunks of the n elements (fixed tree) ...
+int64_t rdm2_contract_sums(int64_t n);
+void rdm2_contract(const double* G, const double* W, int64_t n, double w, double* ws, stream_t s);
+// ... the packed form, ws[0 .. v (v + 1) / 2): row P(a,b) of sum X[a,b,i,j] R[a,b,i,j] for an exchange-symmetric X [v,v,o,o] and R
+// pair-packed as Engine::ladder_sym leaves it (rows P(a,b), a >= b, of length o^2: [ LS (o (o + 1) / 2) | LA (o (o - 1) / 2) ],
+// R[a,b,i,j] = LS[P(ij)] + sgn(a-b) sgn(i-j) LA[Q(ij)]); off-diagonal pairs count twice ...
+void rdm2_contract_packed(const double* X, const double* L, int no, int nv, double* ws, stream_t s);
+// ... and out_dev[0] = the sum of the nsums partial sums, added in order by one block (the second pass of lambda_assemble's norm)
+void rdm2_contract_finish(const double* ws, int64_t nsums, double* out_dev, stream_t s);
+
 // ---- Hartree-Fock matrix from the packed blocks (pymes/mean_field/hf.py:14-18); dir[tp*2+tq] = block (tp,o,tq,o),
 // exc[tp*2+tq] = block (tp,o,o,tq), tp/tq = 1 for a virtual index; h and f are [n,n] on the device
 void hf_fock(const double* const dir[4], const double* const exc[4], const double* h_dev, double* f_dev, int no, int nv,

@@ -840,6 +840,22 @@ __attribute__((weak)) void rdm1_assemble(const double*, const double*, const dou
 __attribute__((weak)) void tdm1_assemble(const Tdm1Parts&, int, int, int, stream_t) {
     throw std::runtime_error("tdm1_assemble: not available in this backend");
 }
+// ... and without the two-particle density kernels (the products of lambda_rdm2 run; the assembly of ijab and the contractions
+// refuse by name)
+__attribute__((weak)) bool rdm2_assemble_ok(int) { return true; }            // (the stubs below refuse by name)
+__attribute__((weak)) void rdm2_assemble(const Rdm2Parts&, int, int, stream_t) {
+    throw std::runtime_error("rdm2_assemble: not available in this backend");
+}
+__attribute__((weak)) int64_t rdm2_contract_sums(int64_t) { return 1; }
+__attribute__((weak)) void rdm2_contract(const double*, const double*, int64_t, double, double*, stream_t) {
+    throw std::runtime_error("rdm2_contract: not available in this backend");
+}
+__attribute__((weak)) void rdm2_contract_packed(const double*, const double*, int, int, double*, stream_t) {
+    throw std::runtime_error("rdm2_contract_packed: not available in this backend");
+}
+__attribute__((weak)) void rdm2_contract_finish(const double*, int64_t, double*, stream_t) {
+    throw std::runtime_error("rdm2_contract_finish: not available in this backend");
+}
 // ... and without the read-each-pair-once forms of the amplitude tail: the callers keep the full-read forms
 __attribute__((weak)) bool sym_tail_ok() { return false; }
 __attribute__((weak)) void cc_update_to_sym(double*, double*, const double*, const double*, const double*, const double*, double,

@@ -865,6 +865,309 @@ void lambda_rdm1(Engine& e, const double* t1, const double* t2, const double* la
     dev::stream_sync(e.stream);
 }
 
+// ==== the two-particle density (eom.h; formulas in include/pymes_amd.h, pymes_rdm2) ====================================
+// G = dL/dV accumulates block by block in `raw` (one array per occupied / virtual pattern, allocated on first use), in four
+// parts: the densities of the six dressed blocks, their back-transformation through t1 (walk: the adjoint of Engine::dress_V,
+// index by index), the dressed-Fock part (outer products of t1 with the response density C) and the direct terms of the singles
+// residual and the energy.  The [o,o,v,v] pattern is kept as [v,v,o,o] — the layout rdm2_assemble reads, which also adds that
+// block's outer products and its energy term; every other stored block is (raw_pqrs + partner_qpsr) / 2 by one permute and
+// one axpby.  Nothing of size v^4 exists unless the abcd block itself is asked for, nothing of size n^4 ever.
+namespace {
+constexpr int kOOVV = 3, kVVVV = 15;
+inline int rdm2_partner(int pat) { return ((pat & 8) >> 1) | ((pat & 4) << 1) | ((pat & 2) >> 1) | ((pat & 1) << 1); }
+
+struct Rdm2Build {
+    Engine& e;
+    const int64_t o, v, n;
+    const double *t1, *t2, *l1, *l2;
+    double* raw[16] = {nullptr};
+    std::vector<double*> held;
+    Rdm2Build(Engine& e_, const double* t1_, const double* t2_, const double* l1_, const double* l2_)
+        : e(e_), o(e_.no), v(e_.nv), n(o + v), t1(t1_), t2(t2_), l1(l1_), l2(l2_) {}
+    ~Rdm2Build() {
+        for (double* p : held) e.scratch_put(p);
+    }
+    Rdm2Build(const Rdm2Build&) = delete;
+    Rdm2Build& operator=(const Rdm2Build&) = delete;
+    struct Buf {
+        Engine& e;
+        double* p;
+        Buf(Engine& e_, int64_t m) : e(e_), p(e_.scratch_get(std::max<int64_t>(m, 1))) {}
+        ~Buf() { e.scratch_put(p); }
+        Buf(const Buf&) = delete;
+        Buf& operator=(const Buf&) = delete;
+    };
+    double* get(int64_t m) {
+        double* p = e.scratch_get(std::max<int64_t>(m, 1));
+        held.push_back(p);
+        return p;
+    }
+    int64_t dim(int pat, int pos) const { return ((pat >> (3 - pos)) & 1) ? v : o; }
+    int64_t size(int pat) const { return dim(pat, 0) * dim(pat, 1) * dim(pat, 2) * dim(pat, 3); }
+    TView view(const double* p, int pat) const { return mv(p, {dim(pat, 0), dim(pat, 1), dim(pat, 2), dim(pat, 3)}); }
+    TView rawv(int pat) {
+        if (!raw[pat]) {
+            raw[pat] = get(size(pat));
+            e.zero(mv(raw[pat], {size(pat)}));
+        }
+        return pat == kOOVV ? mv(raw[pat], {v, v, o, o}) : view(raw[pat], pat);
+    }
+    // raw[pat][sc] += al * sum A[sa] B[sb]  (sc: the block's own index order)
+    void C(double al, const TView& A, const char* sa, const TView& B, const char* sb, int pat, const char* sc) {
+        const char t[5] = {sc[2], sc[3], sc[0], sc[1], 0};
+        e.contract(al, A, sa, B, sb, 1.0, rawv(pat), pat == kOOVV ? t : sc);
+    }
+    void add(int pat, const double* X) {
+        if (pat == kOOVV) e.permute(1.0, view(X, pat), "pqrs", 1.0, rawv(pat), "rspq");
+        else e.axpby(1.0, view(X, pat), 1.0, rawv(pat));
+    }
+    // X: the density of a (partly) dressed block of the pattern `pat`.  A virtual bra index sends -t1[a,k] X to the occupied source
+    // index k, an occupied ket index +t1[c,i] X to the virtual source c; the positions from `start` on, each subset once.
+    // no_vvvv (the walk of the abij density): the branch with both ket indices transformed is left out — it is lambda2 . t1 t1,
+    // which run() sends through the abcd family together with lambda2 . t2 as lambda2 . tau, never as a v^4 array.
+    void walk(int pat, const double* X, int start, bool no_vvvv = false) {
+        add(pat, X);
+        for (int pos = start; pos < 4; ++pos) {
+            const bool virt = (pat >> (3 - pos)) & 1;
+            if ((pos < 2) != virt) continue;
+            if (no_vvvv && pos == 3 && ((pat >> 1) & 1)) continue;
+            const int np = pat ^ (1 << (3 - pos));
+            char sx[5] = "pqrs", sy[5] = "pqrs", st[3] = {0, 0, 0};
+            sy[pos] = 'x';
+            st[0] = pos < 2 ? sx[pos] : 'x';
+            st[1] = pos < 2 ? 'x' : sx[pos];
+            Buf Y(e, size(np));
+            e.contract(pos < 2 ? -1.0 : 1.0, view(X, pat), sx, mv(t1, {v, o}), st, 0.0, view(Y.p, np), sy);
+            walk(np, Y.p, pos + 1, no_vvvv);
+        }
+    }
+    double *Tt = nullptr, *tau = nullptr, *Cm = nullptr, *gov = nullptr;
+    void run(bool want_abcd);
+    void project(int pat, double* out);
+    void finish_oovv(double* out_vvoo);
+};
+
+void Rdm2Build::run(bool want_abcd) {
+    const int64_t o2v2 = v * v * o * o, ov2 = o * v * o * v;
+    const TView L1 = mv(l1, {v, o}), L2 = mv(l2, {v, v, o, o}), T4 = mv(t2, {v, v, o, o}), T1 = mv(t1, {v, o});
+    Tt = get(o2v2);
+    tau = get(o2v2);
+    Cm = get(n * n);
+    gov = get(o * v);
+    const TView TtV = mv(Tt, {v, v, o, o}), TauV = mv(tau, {v, v, o, o}), GOV = mv(gov, {o, v});
+    e.permute(2.0, T4, "abij", 0.0, TtV, "abij");
+    e.permute(-1.0, T4, "baij", 1.0, TtV, "abij");
+    dev::tau_build(tau, t2, t1, e.no, e.nv, e.stream);
+    // ---- the one-body intermediates of lambda_rdm1 and C = the response density without the energy's 2 t1 ---------------------------
+    Buf gvv(e, v * v), goo(e, o * o), Bn(e, o * o * o * o), tl(e, o * o), lt(e, v * v);
+    const TView GVV = mv(gvv.p, {v, v}), GOO = mv(goo.p, {o, o}), BnV = mv(Bn.p, {o, o, o, o}), TL = mv(tl.p, {o, o}),
+                LT = mv(lt.p, {v, v});
+    e.contract(2.0, L2, "abij", T4, "cbij", 0.0, GVV, "ac");
+    e.contract(-2.0, L2, "abij", T4, "abkj", 0.0, GOO, "ki");
+    e.contract(1.0, L1, "ai", TtV, "abij", 0.0, GOV, "jb");
+    e.contract(1.0, L2, "abij", T4, "abkl", 0.0, BnV, "klij");
+    e.contract(1.0, T1, "ak", L1, "ai", 0.0, TL, "ki");               // (t1^T l1)[k,i]
+    e.contract(1.0, L1, "ai", T1, "ci", 0.0, LT, "ac");               // (l1 t1^T)[a,c]
+    const TView Cfull = mv(Cm, {n, n});
+    const TView Coo = slice(slice(Cfull, 0, 0, o), 1, 0, o), Cov = slice(slice(Cfull, 0, 0, o), 1, o, n),
+                Cvo = slice(slice(Cfull, 0, o, n), 1, 0, o), Cvv = slice(slice(Cfull, 0, o, n), 1, o, n);
+    e.axpby(1.0, L1, 0.0, Cvo);
+    e.axpby(1.0, GOO, 0.0, Coo);
+    e.axpby(-1.0, TL, 1.0, Coo);
+    e.axpby(1.0, GVV, 0.0, Cvv);
+    e.axpby(1.0, LT, 1.0, Cvv);
+    e.axpby(1.0, GOV, 0.0, Cov);
+    e.contract(1.0, Coo, "ji", T1, "bi", 1.0, Cov, "jb");             // (goo - t1^T l1) t1^T
+    e.contract(-1.0, T1, "aj", GVV, "ab", 1.0, Cov, "jb");            // - t1^T gvv
+    // ---- 1: densities of the dressed blocks.  ijab (dressed = undressed) goes straight into its raw array -------------------------
+    {
+        Buf X(e, ov2);
+        const TView XV = mv(X.p, {v, o, v, o});
+        C(1.0, BnV, "klij", T4, "cdij", kOOVV, "klcd");
+        e.contract(1.0, L2, "abij", T4, "adkj", 0.0, XV, "bidk");
+        C(1.0, XV, "bidk", T4, "cbil", kOOVV, "klcd");
+        e.contract(1.0, L2, "abij", TtV, "acik", 0.0, XV, "bjck");
+        C(1.0, XV, "bjck", TtV, "dblj", kOOVV, "klcd");
+        e.contract(1.0, L2, "abij", T4, "daki", 0.0, XV, "bjdk");
+        C(2.0, XV, "bjdk", T4, "bclj", kOOVV, "klcd");
+        C(-2.0, XV, "bjdk", T4, "cblj", kOOVV, "klcd");
+        C(-1.0, GVV, "ad", TtV, "aclk", kOOVV, "klcd");
+        C(1.0, GOO, "li", TtV, "dcik", kOOVV, "klcd");
+    }
+    // ---- 2: the back-transformations ----------------------------------------------------------------------------------------------
+    walk(pattern_of_name("abij"), l2, 0, true);
+    walk(pattern_of_name("klij"), Bn.p, 0);
+    {
+        Buf D(e, ov2);
+        const TView P = mv(D.p, {o, v, o, v});
+        e.contract(-2.0, L2, "abij", T4, "cbkj", 0.0, P, "kaic");
+        e.contract(-2.0, L2, "abij", T4, "ackj", 1.0, P, "kbic");
+        walk(pattern_of_name("iajb"), D.p, 0);
+        e.contract(2.0, L2, "abij", TtV, "acik", 0.0, mv(D.p, {o, v, v, o}), "kbcj");
+        walk(pattern_of_name("iabj"), D.p, 0);
+    }
+    {
+        // the abcd family, Z = lambda2 . tau: Z itself only on request; its images under one and two bra transformations from
+        // M1[k,b,i,j] = -sum_a t1[a,k] l2[a,b,i,j] (o v^3 o^2 and o^4 v^2 flops)
+        Buf M1(e, o * v * o * o), M2(e, o * o * o * o), Y(e, o * v * v * v);
+        const TView M1V = mv(M1.p, {o, v, o, o}), M2V = mv(M2.p, {o, o, o, o}), YV = mv(Y.p, {o, v, v, v});
+        e.contract(-1.0, T1, "ak", L2, "abij", 0.0, M1V, "kbij");
+        e.contract(-1.0, M1V, "kbij", T1, "bl", 0.0, M2V, "klij");
+        e.contract(1.0, M1V, "kbij", TauV, "cdij", 0.0, YV, "kbcd");
+        add(pattern_of_name("iabc"), Y.p);
+        e.permute(1.0, YV, "kbcd", 1.0, rawv(pattern_of_name("aibc")), "bkdc");
+        C(1.0, M2V, "klij", TauV, "cdij", kOOVV, "klcd");
+        if (want_abcd) C(1.0, L2, "abij", TauV, "cdij", kVVVV, "abcd");
+    }
+    // ---- 3: the dressed-Fock part, V[j,p,b,q] += 2 t1[b,j] C'[p,q], V[j,p,q,b] -= t1[b,j] C[p,q] (C' = C without Xov in its ov
+    // block, which the reference's f_ov dressing reads from V_iabj[j,a,b,i] instead: the last product).  The [o,o,v,v] parts are
+    // rdm2_assemble's ------------------------------------------------------------------------------------------------------------------
+    const TView T1x = mv(t1, {v, o, 1});
+    auto outer = [&](double al, const TView& blk, int pat, const char* sc) {
+        TView b3 = blk;                       // [p,q] -> [p,q,1]: the K = 1 form of an outer product
+        b3.rank = 3;
+        b3.dim[2] = 1;
+        b3.st[2] = 1;
+        C(al, T1x, "bjx", b3, "pqx", pat, sc);
+    };
+    outer(2.0, Coo, pattern_of_name("ijak"), "jpbq");
+    outer(2.0, Cvo, pattern_of_name("iabj"), "jpbq");
+    outer(2.0, Cvv, pattern_of_name("iabc"), "jpbq");
+    outer(-1.0, Coo, pattern_of_name("ijka"), "jpqb");
+    outer(-1.0, Cvo, pattern_of_name("iajb"), "jpqb");
+    outer(-1.0, Cvv, pattern_of_name("iabc"), "jpqb");
+    outer(2.0, GOV, pattern_of_name("iabj"), "jqbp");                 // 2 t1[b,j] Xov[i,a] at V_iabj[j,a,b,i]
+    // ---- 4: the direct V terms of the singles residual (those of the energy: rdm2_assemble) ----------------------------------------
+    C(1.0, L1, "ai", TtV, "bcij", pattern_of_name("aibc"), "ajbc");
+    C(-1.0, TL, "ki", TtV, "bcij", kOOVV, "kjbc");
+    C(-1.0, L1, "ai", TtV, "abjk", pattern_of_name("ijka"), "jkib");
+    C(-1.0, LT, "ac", TtV, "abjk", kOOVV, "jkcb");
+}
+
+// out[a,b,i,j] = Gamma_ijab[i,j,a,b]
+void Rdm2Build::finish_oovv(double* out_vvoo) {
+    Buf D2(e, v * o), Cv(e, v * o);
+    const TView Cfull = mv(Cm, {n, n});
+    const TView Cov = slice(slice(Cfull, 0, 0, o), 1, o, n);
+    e.permute(2.0, Cov, "jb", 0.0, mv(D2.p, {v, o}), "bj");
+    e.permute(-2.0, mv(gov, {o, v}), "jb", 1.0, mv(D2.p, {v, o}), "bj");
+    e.permute(1.0, Cov, "ja", 0.0, mv(Cv.p, {v, o}), "aj");
+    dev::Rdm2Parts q;
+    q.G = rawv(kOOVV).p; q.Tt = Tt; q.t1 = t1; q.D2 = D2.p; q.Cv = Cv.p; q.out = out_vvoo;
+    dev::rdm2_assemble(q, e.no, e.nv, e.stream);
+}
+
+// out = (raw[pat]_pqrs + raw[partner]_qpsr) / 2 for every pattern but [o,o,v,v]
+void Rdm2Build::project(int pat, double* out) {
+    const TView O = view(out, pat);
+    e.permute(0.5, rawv(rdm2_partner(pat)), "qpsr", 0.0, O, "pqrs");
+    e.axpby(0.5, rawv(pat), 1.0, O);
+}
+
+void rdm2_check(Engine& e, const char* who, const double* t1, const double* t2, const double* lam1, const double* lam2) {
+    if (!t1 || !t2 || !lam1 || !lam2) throw Error(std::string(who) + ": null argument");
+    if (!dev::rdm2_assemble_ok(e.no))
+        throw Error(std::string(who) + ": nocc = " + std::to_string(e.no) + " is too large for the LDS tile of rdm2_assemble (o (o + 1) + 256 "
+                    "doubles in 64 KB: nocc <= " + std::to_string(PYMES_NOCC_MAX_LAMBDA) + ")");
+    const int64_t d[4] = {e.nv, e.nv, e.no, e.no};
+    for (const double* x : {lam2, t2}) {
+        double out[2] = {0.0, 0.0};
+        dev::exchange_asymmetry(x, x, d, out, e.stream);
+        if (!(std::isfinite(out[1]) && out[0] <= 1e-13 * std::max(1.0, out[1])))
+            throw Error(std::string(who) + (x == lam2 ? ": lambda2 does not have the exchange symmetry l2_abij = l2_baji"
+                                                      : ": t2 does not have the exchange symmetry t2_abij = t2_baji"));
+    }
+}
+}  // namespace
+
+bool rdm2_stored(int pattern) { return pattern >= 0 && pattern < 16 && pattern <= rdm2_partner(pattern); }
+
+void lambda_rdm2(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2, unsigned mask,
+                 double* const out[16]) {
+    if (!out) throw Error("rdm2: null argument");
+    if (!(mask & 0xffffu) || (mask >> 16)) throw Error("rdm2: the block mask names no block (bits 0..15: the occupied / virtual patterns)");
+    for (int pat = 0; pat < 16; ++pat) {
+        if (!((mask >> pat) & 1)) continue;
+        if (!rdm2_stored(pat))
+            throw Error("rdm2: block '" + canonical_name(pat) + "' is the image of '" + canonical_name(rdm2_partner(pat)) +
+                        "' under (pq,rs) -> (qp,sr) and is not stored: ask for that one");
+        if (!out[pat]) throw Error("rdm2: null output for block '" + canonical_name(pat) + "'");
+        for (const double* in : {t1, t2, lam1, lam2})
+            if (in == out[pat]) throw Error("rdm2: output aliases input");
+        for (int q = 0; q < pat; ++q)
+            if (((mask >> q) & 1) && out[q] == out[pat]) throw Error("rdm2: two outputs are the same array");
+    }
+    rdm2_check(e, "rdm2", t1, t2, lam1, lam2);
+    const int64_t o = e.no, v = e.nv;
+    Rdm2Build w(e, t1, t2, lam1, lam2);
+    w.run((mask >> kVVVV) & 1);
+    for (int pat = 0; pat < 16; ++pat) {
+        if (!((mask >> pat) & 1)) continue;
+        if (pat == kOOVV) {
+            Rdm2Build::Buf S(e, v * v * o * o);
+            w.finish_oovv(S.p);
+            e.permute(1.0, mv(S.p, {v, v, o, o}), "abij", 0.0, mv(out[pat], {o, o, v, v}), "ijab");
+        } else {
+            w.project(pat, out[pat]);
+        }
+    }
+    dev::stream_sync(e.stream);
+}
+
+double lambda_rdm2_expectation(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2) {
+    e.refuse_if_sharded("rdm2_expectation");
+    for (int pat = 0; pat < 16; ++pat)
+        if (!e.has_block(pat)) throw Error("rdm2_expectation: the operator block '" + canonical_name(pat) + "' is not set");
+    rdm2_check(e, "rdm2_expectation", t1, t2, lam1, lam2);
+    {
+        double asym[2] = {0.0, 0.0};
+        e.exchange_asymmetry_V(asym);
+        if (!(std::isfinite(asym[1]) && asym[0] <= 1e-12 * std::max(1.0, asym[1])))
+            throw Error("rdm2_expectation: the operator does not have the symmetry W_pqrs = W_qpsr (max |W_pqrs - W_qpsr| = " +
+                        std::to_string(asym[0]) + ")");
+    }
+    const int64_t o = e.no, v = e.nv, npp = v * (v + 1) / 2;
+    int64_t nsums = npp, largest = 1;
+    for (int pat = 0; pat < kVVVV; ++pat) {
+        if (!rdm2_stored(pat)) continue;
+        int64_t sz = 1;
+        for (int pos = 0; pos < 4; ++pos) sz *= ((pat >> (3 - pos)) & 1) ? v : o;
+        nsums += dev::rdm2_contract_sums(sz);
+        largest = std::max(largest, sz);
+    }
+    Rdm2Build w(e, t1, t2, lam1, lam2);
+    w.run(false);
+    Rdm2Build::Buf ws(e, nsums + 1), G(e, largest);
+    int64_t at = 0;
+    for (int pat = 0; pat < kVVVV; ++pat) {
+        if (!rdm2_stored(pat)) continue;
+        const double wgt = rdm2_partner(pat) == pat ? 1.0 : 2.0;      // (a block and its image contribute the same sum)
+        const int64_t sz = w.size(pat);
+        if (pat == kOOVV) {
+            Rdm2Build::Buf S(e, sz);
+            w.finish_oovv(S.p);
+            e.permute(1.0, mv(S.p, {v, v, o, o}), "abij", 0.0, mv(G.p, {o, o, v, v}), "ijab");
+        } else {
+            w.project(pat, G.p);
+        }
+        dev::rdm2_contract(G.p, e.block(pat).p, sz, wgt, ws.p + at, e.stream);
+        at += dev::rdm2_contract_sums(sz);
+    }
+    {
+        // the abcd block never exists: sum Gamma_abcd W_abcd = sum_abij l2_abij (sum_cd W_abcd tau_cdij), the inner sum through the
+        // pair-packed ladder on W's V+ / V- packs (a quarter of the flops of the plain product), the outer one on the packed rows
+        Rdm2Build::Buf L(e, npp * o * o);
+        e.ladder_sym(w.tau, L.p, 0, npp, false);
+        dev::rdm2_contract_packed(lam2, L.p, e.no, e.nv, ws.p + at, e.stream);
+        at += npp;
+    }
+    dev::rdm2_contract_finish(ws.p, at, ws.p + nsums, e.stream);
+    double r = 0.0;
+    const int slot = dev::readback_start(ws.p + nsums, 1, e.stream);
+    dev::readback_wait(slot, &r, 1);
+    return r;
+}
+
 // ---- transition densities of k roots (eom.h): the v o o / v v o-contracted intermediates as engine products with the
 // k vectors stacked (one GEMM per product), then one assembly launch for both densities of all roots ---------------------------
 void transition_densities(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2, int k,

@@ -89,6 +89,20 @@ void eom_diagonals(Engine& e, const double* f_host, const double* t2, bool dress
 void lambda_rdm1(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2, double ref,
                  double* gamma_host);
 
+// The two-particle response density of the same Lagrangian (formulas in include/pymes_amd.h, pymes_rdm2):
+// Gamma_pqrs = (G_pqrs + G_qpsr) / 2 with G = dL/dV at fixed f, so that L(f, V) = sum gamma f + sum Gamma V for every V with
+// V_pqrs = V_qpsr.  Block by block: out[pattern] (device, written) for every pattern in `mask` (bit = the pattern number of
+// pattern_of_name).  A block and its image under (pq,rs) -> (qp,sr) are the same data; rdm2_stored(pattern) names the one of
+// each pair that can be asked for (klij, ijka, ijab, iajk, iajb, iabj, iabc, abij, abic, abcd).  Reads no integral block; t2 and
+// lam2 must have the exchange symmetry; refused by name beyond PYMES_NOCC_MAX_LAMBDA.  abcd (v^4) is built only when asked for.
+bool rdm2_stored(int pattern);
+void lambda_rdm2(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2, unsigned mask,
+                 double* const out[16]);
+// sum Gamma_pqrs W_pqrs over all sixteen blocks for the operator W held as the context's undressed blocks (W_pqrs = W_qpsr is
+// tested and refused by name otherwise).  The abcd density is never built: its part is sum l2_abij (W_abcd tau_cdij) through the
+// pair-packed ladder.  Deterministic: block sums in a fixed tree, added in order.  One synchronisation.
+double lambda_rdm2_expectation(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2);
+
 // The transition densities of k EE-EOM-CCSD roots (formulas in include/pymes_amd.h, pymes_tdm1): gammaL, gammaR
 // [k,n,n] and r0 [k] on the host from t1, lam1 [v,o], t2, lam2 [v,v,o,o] and the left / right vectors (l1[z], l2[z]), (r1[z],
 // r2[z]) on the device.  Linear in every vector: normalisation is the caller's.  Reads no integral block.

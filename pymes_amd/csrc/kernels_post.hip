@@ -1040,3 +1040,147 @@ void tdm1_assemble(const Tdm1Parts& q, int k, int no, int nv, stream_t s) {
 }
 
 }  // namespace dev
+
+// ==== the CCSD two-particle density (device_api.h, rdm2_assemble / rdm2_contract; eom.cpp, lambda_rdm2) ================
+namespace {
+
+// Gamma_ijab in the [v,v,o,o] layout, one block per virtual pair a >= b with the o x (o + 1) tile of lambda_assemble.  With
+//   g[i,j,a,b] = G[a,b,i,j] + Tt[a,b,i,j] + t[a,i] (2 t[b,j] + D2[b,j]) - t[b,i] (t[a,j] + Cv[a,j])
+// (the coefficient of V_ijab[i,j,a,b]: the sum of the products, the energy term, the outer products of the dressed-Fock part)
+// out[a,b,i,j] = out[b,a,j,i] = (g[i,j,a,b] + g[j,i,b,a]) / 2.  Pass 1 reads the tiles (a,b) of G and Tt in (i,j) order, pass 2
+// the tiles (b,a) in (j,i) order, pass 3 writes both tiles of the output along their fastest index; the LDS tile carries the
+// transposition.  Every element is one thread's sum in a fixed order.
+struct Rdm2K {
+    const double* G; const double* Tt; const double* t1; const double* D2; const double* Cv;
+    double* out;
+    int no, nv;
+};
+
+__global__ void __launch_bounds__(256) rdm2_assemble_kernel(const Rdm2K k) {
+    extern __shared__ double S[];             // [no][no + 1]
+    const int no = k.no, nv = k.nv;
+    int a, b;
+    unrank_pair(blockIdx.x, a, b);
+    const int p = no + 1;
+    const long o2 = (long)no * no;
+    const long ab = ((long)a * nv + b) * o2, ba = ((long)b * nv + a) * o2;
+    const double* __restrict__ G = k.G;
+    const double* __restrict__ Tt = k.Tt;
+    const double* __restrict__ ta = k.t1 + (long)a * no;
+    const double* __restrict__ tb = k.t1 + (long)b * no;
+    const double* __restrict__ da = k.D2 + (long)a * no;
+    const double* __restrict__ db = k.D2 + (long)b * no;
+    const double* __restrict__ ca = k.Cv + (long)a * no;
+    const double* __restrict__ cb = k.Cv + (long)b * no;
+    for (int e = threadIdx.x; e < o2; e += 256) {             // sources read in (i,j) order
+        const int i = e / no, j = e - i * no;
+        S[i * p + j] = G[ab + e] + Tt[ab + e] + ta[i] * (2.0 * tb[j] + db[j]) - tb[i] * (ta[j] + ca[j]);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < o2; e += 256) {             // sources read in (j,i) order
+        const int j = e / no, i = e - j * no;
+        S[i * p + j] += G[ba + e] + Tt[ba + e] + tb[j] * (2.0 * ta[i] + da[i]) - ta[j] * (tb[i] + cb[i]);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < o2; e += 256) {
+        const int r = e / no, c = e - r * no;
+        k.out[ab + e] = 0.5 * S[r * p + c];
+        if (a != b) k.out[ba + e] = 0.5 * S[c * p + r];
+    }
+}
+
+// ws[block] = w x the sum of G[e] W[e] over the block's 4096 consecutive elements: thread t takes t, t + 256, ... in order, then
+// the fixed tree of lambda_block_sum; rdm2_contract_finish (the second pass of lambda_norm) adds the block sums in order.
+constexpr int kRdm2Chunk = 4096;
+
+__global__ void __launch_bounds__(256) rdm2_contract_kernel(const double* __restrict__ G, const double* __restrict__ W, long n,
+                                                            double w, double* __restrict__ ws) {
+    __shared__ double sr[256];
+    const long base = (long)blockIdx.x * kRdm2Chunk;
+    double acc = 0.0;
+    for (int q = 0; q < kRdm2Chunk / 256; ++q) {
+        const long e = base + q * 256 + threadIdx.x;
+        if (e < n) acc += G[e] * W[e];
+    }
+    const double tot = lambda_block_sum(acc, sr);
+    if (threadIdx.x == 0) ws[blockIdx.x] = w * tot;
+}
+
+// The packed form: sum_abij X[a,b,i,j] R[a,b,i,j] for an exchange-symmetric X [v,v,o,o] and R given pair-packed as ladder_sym
+// leaves it — rows P(a,b), a >= b, of length o^2: LS[P(ij)] in the first o (o + 1) / 2 columns, LA[Q(ij)] behind them,
+// R[a,b,i,j] = LS + sgn(a-b) sgn(i-j) LA.  One block per row: the tile X[a,b,:,:] is staged in LDS (read along j), column P(i,j)
+// meets X_abij + X_abji and column Q(i,j) meets X_abij - X_abji; an off-diagonal pair counts twice (its tile (b,a) is the
+// transpose).  ws[row] = the row's sum, fixed tree.
+__global__ void __launch_bounds__(256) rdm2_contract_packed_kernel(const double* __restrict__ X, const double* __restrict__ L,
+                                                                   int no, int nv, double* __restrict__ ws) {
+    extern __shared__ double S[];             // [no][no + 1], the 256 partial sums behind it
+    const int p = no + 1;
+    double* sr = S + (long)no * p;
+    int a, b;
+    unrank_pair(blockIdx.x, a, b);
+    const long o2 = (long)no * no, opp = (long)no * (no + 1) / 2;
+    const double* __restrict__ x = X + ((long)a * nv + b) * o2;
+    const double* __restrict__ row = L + (long)blockIdx.x * o2;
+    for (int e = threadIdx.x; e < o2; e += 256) {
+        const int i = e / no, j = e - i * no;
+        S[i * p + j] = x[e];
+    }
+    __syncthreads();
+    double acc = 0.0;
+    for (int c = threadIdx.x; c < o2; c += 256) {
+        int i, j;
+        if (c < opp) {
+            unrank_pair(c, i, j);
+            acc += row[c] * (i == j ? S[i * p + i] : S[i * p + j] + S[j * p + i]);
+        } else if (a != b) {
+            unrank_pair(c - opp, i, j);       // Q(i', j) with i' = i + 1 > j
+            ++i;
+            acc += row[c] * (S[i * p + j] - S[j * p + i]);
+        }
+    }
+    const double tot = lambda_block_sum(acc, sr);
+    if (threadIdx.x == 0) ws[blockIdx.x] = (a == b ? 1.0 : 2.0) * tot;
+}
+
+}  // namespace
+
+namespace dev {
+
+constexpr size_t rdm2_tile_lds(size_t no) { return sizeof(double) * (no * (no + 1) + 256); }        // the largest of the two kernels
+static_assert(rdm2_tile_lds(PYMES_NOCC_MAX_LAMBDA) <= 64 * 1024, "the tile of rdm2_contract_packed fits 64 KB up to PYMES_NOCC_MAX_LAMBDA");
+bool rdm2_assemble_ok(int no) { return no >= 1 && no <= PYMES_NOCC_MAX_LAMBDA; }
+
+void rdm2_assemble(const Rdm2Parts& q, int no, int nv, stream_t s) {
+    if (no < 1 || nv < 1) throw std::runtime_error("rdm2_assemble: bad shape");
+    if (!rdm2_assemble_ok(no)) throw std::runtime_error("rdm2_assemble: nocc too large for the LDS tile");
+    if (!q.G || !q.Tt || !q.t1 || !q.D2 || !q.Cv || !q.out) throw std::runtime_error("rdm2_assemble: null operand");
+    if (q.out == q.G || q.out == q.Tt) throw std::runtime_error("rdm2_assemble: the output aliases an operand");
+    const long npairs = (long)nv * (nv + 1) / 2;
+    if (npairs > 0x7fffffffL) throw std::runtime_error("rdm2_assemble: grid too large");
+    const Rdm2K k{q.G, q.Tt, q.t1, q.D2, q.Cv, q.out, no, nv};
+    launch_kernel(rdm2_assemble_kernel, dim3((unsigned)npairs), dim3(256), sizeof(double) * no * (no + 1), (hipStream_t)s, k);
+}
+
+int64_t rdm2_contract_sums(int64_t n) { return (n + kRdm2Chunk - 1) / kRdm2Chunk; }
+
+void rdm2_contract(const double* G, const double* W, int64_t n, double w, double* ws, stream_t s) {
+    if (!G || !W || !ws || n < 1) throw std::runtime_error("rdm2_contract: bad argument");
+    const int64_t nblk = rdm2_contract_sums(n);
+    if (nblk > 0x7fffffffL) throw std::runtime_error("rdm2_contract: grid too large");
+    launch_kernel(rdm2_contract_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s, G, W, (long)n, w, ws);
+}
+
+void rdm2_contract_packed(const double* X, const double* L, int no, int nv, double* ws, stream_t s) {
+    if (!X || !L || !ws || no < 1 || nv < 1) throw std::runtime_error("rdm2_contract_packed: bad argument");
+    if (!rdm2_assemble_ok(no)) throw std::runtime_error("rdm2_contract_packed: nocc too large for the LDS tile");
+    const long npairs = (long)nv * (nv + 1) / 2;
+    if (npairs > 0x7fffffffL) throw std::runtime_error("rdm2_contract_packed: grid too large");
+    launch_kernel(rdm2_contract_packed_kernel, dim3((unsigned)npairs), dim3(256), rdm2_tile_lds(no), (hipStream_t)s, X, L, no, nv, ws);
+}
+
+void rdm2_contract_finish(const double* ws, int64_t nsums, double* out_dev, stream_t s) {
+    if (!ws || !out_dev || nsums < 1) throw std::runtime_error("rdm2_contract_finish: bad argument");
+    launch_kernel(lambda_norm_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, ws, (long)nsums, out_dev);
+}
+
+}  // namespace dev

@@ -486,8 +486,16 @@ class CCSD(ccd.CCD):
         which ``triples=True`` refuses), "lambda1" and "lambda2".  ``density=True`` adds "lambda1",
         "lambda2" (the solution of the Lambda equations), "rdm1" (the one-particle response density plus 2 on the occupied
         diagonal, [n,n], not symmetric) and "natural occupations" (eigenvalues of its symmetric part, descending), of the
-        correlated space; ``lambda_r_epsilon`` is the residual norm at which the Lambda iteration stops.  Sources: a host V_pqrs or
+        correlated space; ``lambda_r_epsilon`` is the residual norm at which the Lambda iteration stops.  ``rdm2=True`` (implies
+        ``density=True``) adds "rdm2 blocks" (the two-particle response density Gamma block by block, without abcd;
+        pymes_amd/solver/lambda_ccsd.py) and "density e" = sum gamma f + sum Gamma V, the correlation energy rebuilt from the
+        densities against the resident integrals.  Sources: a host V_pqrs or
         replicated DeviceIntegrals; for density-fitting factors call fno.truncate and solve on its result."""
+        if kwargs.get("rdm2"):             # the two-particle density is that of the Lambda state: rdm2=True implies density=True
+            if self.is_dcd:
+                raise ValueError("rdm2=True: the two-particle density is that of the CCSD Lagrangian and its Lambda equations, "
+                                 "not defined for DCSD")
+            kwargs["density"] = True
         if kwargs.get("density"):          # refused by name before anything is truncated, uploaded or dressed
             if self.is_dcd:
                 raise ValueError("density=True: the Lambda equations are those of the CCSD similarity transform, not defined "
@@ -627,7 +635,8 @@ class CCSD(ccd.CCD):
                                                kwargs.get("ip_ea_r_epsilon"))
             lam = None
             if density or lambda_t:
-                lam = self._lambda_density(t_fock_pq, ints, st, kwargs.get("lambda_r_epsilon"), with_density=density)
+                lam = self._lambda_density(t_fock_pq, ints, st, kwargs.get("lambda_r_epsilon"), with_density=density,
+                                           with_rdm2=bool(kwargs.get("rdm2", False)))
             e_lt = None
             if lambda_t:
                 time_t = time.time()
@@ -704,7 +713,7 @@ class CCSD(ccd.CCD):
                 self.ea_solver = solver
         return out
 
-    def _lambda_density(self, t_fock_pq, ints, st, r_epsilon=None, with_density=True):
+    def _lambda_density(self, t_fock_pq, ints, st, r_epsilon=None, with_density=True, with_rdm2=False):
         """Lambda and the one-particle density of the converged amplitudes on the integrals' context (device hand-over: the
         Fock matrix and the ten blocks of the sigma build are T1-dressed in HBM), with the orbital energies and the level
         shift of the amplitude update.  ``with_density=False``: Lambda alone (triples="lambda" without density=True)."""
@@ -722,9 +731,17 @@ class CCSD(ccd.CCD):
             solver.t2 = None
             return {"lambda1": out["lambda1"], "lambda2": out["lambda2"]}
         rdm1 = solver.rdm1(t1, ctx=ints.ctx)
+        res = {"lambda1": out["lambda1"], "lambda2": out["lambda2"], "rdm1": rdm1,
+               "natural occupations": lambda_ccsd.natural_occupations(rdm1)}
+        if with_rdm2:
+            # the two-particle density of the same Lambda, and L = sum gamma f + sum Gamma V against the resident undressed
+            # integrals (the abcd block is contracted through the packed ladder, never built)
+            res["rdm2 blocks"] = solver.rdm2(t1, ctx=ints.ctx)
+            gamma = rdm1.copy()
+            gamma[np.arange(self.no), np.arange(self.no)] -= 2.0
+            res["density e"] = float((gamma * f).sum()) + solver.expectation2(ints, t1=t1)
         solver.t2 = None                                 # (the solver's T2 buffer goes back to the pool; the results are host arrays)
-        return {"lambda1": out["lambda1"], "lambda2": out["lambda2"], "rdm1": rdm1,
-                "natural occupations": lambda_ccsd.natural_occupations(rdm1)}
+        return res
 
     def _ee_transitions(self, t_fock_pq, ints, st, n_roots, r_epsilon=None, lam=None):
         """The lowest excitation energies, left vectors and transition densities of the converged amplitudes on the

@@ -11,6 +11,11 @@ of the CCSD update and the device DIIS; one library call and one synchronisation
 ``rdm1(t1)`` is the one-particle response density ``gamma_pq = dL/df_pq`` of the CCSD Lagrangian plus 2 on the occupied diagonal
 (its trace is the electron count), ``expectation(O)`` the correlation part ``sum gamma_pq O_pq`` of a one-body expectation value.
 Nothing is assumed hermitian: for transcorrelated integrals the left state is not the transpose of the right one.
+
+``rdm2(t1)`` is the two-particle response density ``Gamma_pqrs = (dL/dV_pqrs + dL/dV_qpsr) / 2`` block by block and
+``expectation2(W)`` the two-body expectation value ``sum Gamma W`` — ``L(f, V) = sum gamma f + sum Gamma V`` for every V with
+V_pqrs = V_qpsr (gamma: ``rdm1`` without the 2 on the occupied diagonal; no factor 1/2; formulas: include/pymes_amd.h,
+``pymes_rdm2``).  ``full_rdm2`` assembles the spin-summed two-particle density matrix from them.
 """
 import ctypes as C
 import time
@@ -80,6 +85,80 @@ def device_rdm1(ctx, t1, t2, lam1, lam2, ref=2.0):
     ctx.lib.call("pymes_rdm1", ctx.handle, C.c_void_p(t1.ptr), C.c_void_p(t2.ptr), C.c_void_p(lam1.ptr), C.c_void_p(lam2.ptr),
                  float(ref), _lib.host_ptr(out))
     return out
+
+
+# ---- the two-particle density (include/pymes_amd.h, pymes_rdm2) ------------------------------------------------------
+RDM2_NAMES = ("klij", "ijka", "ijak", "ijab", "iajk", "iajb", "iabj", "iabc", "aijk", "aijb", "aibj", "aibc", "abij", "abic", "abci",
+              "abcd")                                  # by pattern number: 8 p + 4 q + 2 r + s, 1 for a virtual position
+# A block and its image under (pq,rs) -> (qp,sr) hold the same numbers: the library stores one of each pair
+RDM2_IMAGE = {"ijak": "ijka", "aijk": "iajk", "aibj": "iajb", "aijb": "iabj", "aibc": "iabc", "abci": "abic"}
+RDM2_STORED = tuple(nm for nm in RDM2_NAMES if nm not in RDM2_IMAGE)
+
+
+def _rdm2_names(blocks):
+    """The block names of a request, checked; default: all blocks except abcd."""
+    names = tuple(nm for nm in RDM2_NAMES if nm != "abcd") if blocks is None else tuple(blocks)
+    for nm in names:
+        if nm not in RDM2_NAMES:
+            raise ValueError("rdm2: unknown block %r (the sixteen names of split_blocks: %s)" % (nm, ", ".join(RDM2_NAMES)))
+    if not names:
+        raise ValueError("rdm2: no block requested")
+    return names
+
+
+def device_rdm2(ctx, t1, t2, lam1, lam2, blocks=None, out=None):
+    """The blocks of Gamma as device arrays (``pymes_rdm2``): a dictionary over the STORED names among ``blocks`` (default: all
+    but abcd) and the stored images of the others (RDM2_IMAGE: Gamma_aibc[a,i,b,c] = Gamma_iabc[i,a,c,b], ...).  All four inputs
+    device arrays of ctx; ``out``: a dictionary of device arrays to write into (default: new ones)."""
+    check_occupied(ctx.no, "rdm2")
+    stored = []
+    for nm in _rdm2_names(blocks):
+        nm = RDM2_IMAGE.get(nm, nm)
+        if nm not in stored:
+            stored.append(nm)
+    res = {nm: (out[nm] if out is not None and nm in out else ctx.empty(ctx.block_shape(nm))) for nm in stored}
+    ptrs = (C.c_void_p * 16)()
+    mask = 0
+    for nm, arr in res.items():
+        if tuple(arr.shape) != ctx.block_shape(nm):
+            raise ValueError("rdm2: the output for block %r must have shape %s" % (nm, ctx.block_shape(nm)))
+        k = RDM2_NAMES.index(nm)
+        ptrs[k] = arr.ptr
+        mask |= 1 << k
+    ctx.lib.call("pymes_rdm2", ctx.handle, C.c_void_p(t1.ptr), C.c_void_p(t2.ptr), C.c_void_p(lam1.ptr), C.c_void_p(lam2.ptr),
+                 mask, ptrs)
+    return res
+
+
+def device_expectation2(ctx, t1, t2, lam1, lam2):
+    """sum Gamma_pqrs W_pqrs for the operator W held as the undressed blocks of ctx (``pymes_rdm2_expectation``); the abcd
+    density is never built."""
+    check_occupied(ctx.no, "expectation2")
+    val = np.zeros(1)
+    ctx.lib.call("pymes_rdm2_expectation", ctx.handle, C.c_void_p(t1.ptr), C.c_void_p(t2.ptr), C.c_void_p(lam1.ptr),
+                 C.c_void_p(lam2.ptr), _lib.host_ptr(val))
+    return float(val[0])
+
+
+def full_rdm2(no, gamma, Gamma_blocks):
+    """The spin-summed two-particle density matrix [n,n,n,n] of E = sum h D1 + 1/2 sum V D with f = h + sum_i (2 V_piqi - V_piiq):
+    D = D_HF + 2 (gamma_pr n_qs + n_pr gamma_qs) - (gamma_ps n_qr + n_ps gamma_qr) + 2 Gamma, D_HF = 4 n_pr n_qs - 2 n_ps n_qr, n
+    the unit matrix on the occupied block.  ``gamma``: the response density [n,n] WITHOUT the reference term (``rdm1`` minus 2
+    on the occupied diagonal); ``Gamma_blocks``: a complete dictionary of the sixteen blocks (``rdm2`` with every name)."""
+    g = np.asarray(gamma, dtype=np.float64)
+    m = g.shape[0]
+    missing = [nm for nm in RDM2_NAMES if nm not in Gamma_blocks]
+    if missing:
+        raise ValueError("full_rdm2: needs all sixteen blocks; missing %s" % ", ".join(missing))
+    nocc = np.zeros((m, m))
+    nocc[np.arange(no), np.arange(no)] = 1.0
+    D = 4.0 * np.einsum("pr,qs->pqrs", nocc, nocc) - 2.0 * np.einsum("ps,qr->pqrs", nocc, nocc)
+    D += 2.0 * (np.einsum("pr,qs->pqrs", g, nocc) + np.einsum("pr,qs->pqrs", nocc, g))
+    D -= np.einsum("ps,qr->pqrs", g, nocc) + np.einsum("ps,qr->pqrs", nocc, g)
+    sl = {"o": slice(0, no), "v": slice(no, None)}
+    for nm in RDM2_NAMES:
+        D[tuple(sl["v" if ch in "abcd" else "o"] for ch in nm)] += 2.0 * np.asarray(Gamma_blocks[nm])
+    return D
 
 
 class Lambda_CCSD:
@@ -205,6 +284,92 @@ class Lambda_CCSD:
                 ctx.close()
         self.gamma = g
         return g
+
+    def _on_context(self, what, ctx):
+        """(ctx, own, on_ctx): the context a density call runs on and the function that brings an operand onto it."""
+        if self.lambda1 is None:
+            raise RuntimeError("%s: needs a finished solve()" % what)
+        if self.t2 is None:
+            raise RuntimeError("%s: the amplitudes of the solve are no longer held (CCSD.solve(density=True, rdm2=True) returns "
+                               "\"rdm2 blocks\")" % what)
+        if ctx is None and isinstance(self.t2, DeviceArray) and self.t2.ctx.handle is not None:
+            ctx = self.t2.ctx
+        own = ctx is None
+        if own:
+            ctx = Context(self.no, self.lambda1.shape[0], device=self.device)
+
+        def on_ctx(x):
+            if isinstance(x, DeviceArray):
+                return x if x.ctx is ctx else ctx.array(x.get())
+            return ctx.array(np.ascontiguousarray(x, dtype=np.float64))
+        return ctx, own, on_ctx
+
+    def rdm2(self, t1, blocks=None, ctx=None):
+        """The blocks of the two-particle response density Gamma of the last solve as a dictionary of host arrays, names and
+        shapes as ``split_blocks``.  ``blocks``: the names wanted (default: all except abcd, which is v^4 and returned only when
+        named).  Not hermitian, and not symmetrised.  ``ctx``: a live context to run on (default: a small one of its own; the
+        density reads no integrals)."""
+        names = _rdm2_names(blocks)
+        check_occupied(self.no, "rdm2")
+        ctx, own, on_ctx = self._on_context("rdm2", ctx)
+        try:
+            dev = device_rdm2(ctx, on_ctx(t1), on_ctx(self.t2), on_ctx(self.lambda1), on_ctx(self.lambda2), names)
+            host = {nm: arr.get() for nm, arr in dev.items()}
+            for arr in dev.values():
+                arr.free()
+        finally:
+            if own:
+                ctx.close()
+        return {nm: (np.ascontiguousarray(host[RDM2_IMAGE[nm]].transpose(1, 0, 3, 2)) if nm in RDM2_IMAGE else host[nm])
+                for nm in names}
+
+    def expectation2(self, W, O=None, t1=None):
+        """sum Gamma_pqrs W_pqrs (+ sum gamma_pq O_pq): the correlation part of the expectation value of the two-body operator W
+        (and the one-body operator O) in the orbital basis of the solve.  ``W``: a host [n,n,n,n] array, a dictionary of its
+        sixteen blocks or a ``DeviceIntegrals`` of the same shape; it must have W_pqrs = W_qpsr (tested once, refused by name
+        otherwise).  The contraction runs on the device, block by block; the abcd density is never built.  ``t1``: the singles of
+        the solve (needed unless ``rdm1(t1)`` / ``rdm2(t1)`` / a call with ``t1`` went before)."""
+        from pymes_amd.integral.device import DeviceIntegrals
+        if t1 is not None:
+            self.t1 = t1
+        if getattr(self, "t1", None) is None:
+            raise RuntimeError("expectation2: pass t1 (the singles amplitudes of the solve)")
+        check_occupied(self.no, "expectation2")
+        nv = self.lambda1.shape[0] if self.lambda1 is not None else 0
+        m = self.no + nv
+        own = not isinstance(W, DeviceIntegrals)
+        if own:
+            if self.lambda1 is None:
+                raise RuntimeError("expectation2: needs a finished solve()")
+            wctx = Context(self.no, nv, device=self.device)
+        else:
+            wctx = W.ctx
+        try:
+            if not own:
+                if tuple(W.shape) != (m,) * 4:
+                    raise ValueError("expectation2: W must have shape %s" % ((m,) * 4,))
+            elif isinstance(W, dict):
+                missing = [nm for nm in RDM2_NAMES if nm not in W]
+                if missing:
+                    raise ValueError("expectation2: W needs all sixteen blocks; missing %s" % ", ".join(missing))
+                for nm in RDM2_NAMES:
+                    wctx.set_V_block(nm, np.ascontiguousarray(W[nm], dtype=np.float64))
+            else:
+                W = np.asarray(W, dtype=np.float64)
+                if W.shape != (m,) * 4:
+                    raise ValueError("expectation2: W must have shape %s" % ((m,) * 4,))
+                wctx.set_V_pqrs(W)
+            if not wctx.V_exchange_symmetric():
+                raise PymesError("expectation2: the operator does not have the symmetry W_pqrs = W_qpsr (max |W_pqrs - W_qpsr| = "
+                                 "%.3e)" % wctx.V_exchange_asymmetry()[0])
+            _, _, on_ctx = self._on_context("expectation2", wctx)
+            val = device_expectation2(wctx, on_ctx(self.t1), on_ctx(self.t2), on_ctx(self.lambda1), on_ctx(self.lambda2))
+        finally:
+            if own:
+                wctx.close()
+        if O is not None:
+            val += self.expectation(O, t1=self.t1)
+        return val
 
     def expectation(self, O, t1=None):
         """sum gamma_pq O_pq: the correlation part of the expectation value of the one-body operator O (orbital basis of f).

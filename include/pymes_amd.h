@@ -150,6 +150,26 @@ int pymes_set_V_from_factors(pymes_ctx* ctx, const double* B_host, int naux);
  * pointer, set_V_block("abcd") from device memory, pymes_ladder, pymes_doubles_residual, pymes_ccsd_residuals /
  * _iterate, pymes_ccsd_dress_abcd_rows, dressed or other rows of pymes_ladder_sym, the EOM sigma). */
 int pymes_set_integral_shard(pymes_ctx* ctx, int rank, int world);
+/* Factor-direct particle ladder (opt-in; before any pymes_set_V_* call; not together with pymes_set_integral_shard): nothing of
+ * size v^4 is ever allocated.  Only pymes_set_V_from_factors sets the integrals of such a context (set_V_pqrs / set_V_block
+ * are refused: there are no factors): it forms the 15 other blocks as ever, keeps a compact device copy of the
+ * virtual-virtual factors B_vv (zero-padded [nv][naux up to 8][nv up to 64]) and allocates one pair of chunk buffers for V^+ /
+ * V^- rows at the ladder pitches, within chunk_bytes (0: the environment's PYMES_DIRECT_CHUNK_BYTES, default 1 GiB; at least
+ * one row).  The undressed pair-packed ladders (pymes_ladder_sym, the ladders inside pymes_ccsd_residuals / _iterate and the
+ * symmetric pymes_doubles_residual) rebuild their rows from B_vv chunk by chunk in every call: npp v^2 naux 2 flops per call in
+ * exchange for 8 v^4 (block) + 8 v^4 (packed rows) bytes.  The T1 dressing of the ladder rides on tau and the Q_kb products
+ * (PYMES_LADDER_DRESS=1 is an error here).  PYMES_DIRECT_BUILDER=gemm|fused selects the row builder: batched products into
+ * planes that dev ladder_pack_V packs (every backend), or one gfx950 kernel from B_vv straight into the rows (the default
+ * where the backend has it).  Everything
+ * that needs the full, dressed or stored V_abcd fails and names the mode: the block pointer, pymes_ladder, the general or
+ * dressed pymes_doubles_residual, pymes_ccsd_dress_abcd_rows, dressing abcd, dressed pymes_ladder_sym, pymes_ladder_sym_multi
+ * / _adjoint*, the EE / EA sigma, the EOM diagonals, pymes_rdm2_expectation, pymes_derive_context from or into it. */
+int pymes_set_integral_direct(pymes_ctx* ctx, int64_t chunk_bytes);
+/* info[5] = { naux, rows per chunk, bytes of B_vv, bytes of the chunk buffers, builder (0 gemm, 1 fused) } of such a context */
+int pymes_direct_info(pymes_ctx* ctx, int64_t* info);
+/* builds the rows [r0,r1) (at most one chunk) into the chunk buffers and returns them read-only (device pointers, row
+ * pitches; valid until the next ladder call): for tests */
+int pymes_direct_rows(pymes_ctx* ctx, int64_t r0, int64_t r1, const double** vp, const double** vm, int64_t* ldp, int64_t* ldm);
 /* bytes the context holds for integrals: undressed and dressed blocks, the stored / packed V_abcd rows, the static packs */
 int pymes_integral_bytes(pymes_ctx* ctx, int64_t* bytes);
 /* read-only view of the stored rows of a sharded context: device pointers, the pair-row range and the row pitches */

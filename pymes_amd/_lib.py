@@ -65,6 +65,10 @@ SIGNATURES = {
     "pymes_V_block_ptr": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, c_pp, c_i64_p]),
     "pymes_set_integral_shard": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pymes_integral_bytes": (C.c_int, [C.c_void_p, c_i64_p]),
+    # factor-direct particle ladder (include/pymes_amd.h): no V_abcd, rows rebuilt from the factors chunk by chunk
+    "pymes_set_integral_direct": (C.c_int, [C.c_void_p, C.c_int64]),
+    "pymes_direct_info": (C.c_int, [C.c_void_p, c_i64_p]),
+    "pymes_direct_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_pp, c_pp, c_i64_p, c_i64_p]),
     "pymes_shard_rows_ptr": (C.c_int, [C.c_void_p, c_pp, c_pp, c_i64_p, c_i64_p, c_i64_p, c_i64_p]),
     "pymes_ccsd_t_triples": (C.c_int, [C.c_void_p, c_i64_p]),
     "pymes_ccsd_t": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,

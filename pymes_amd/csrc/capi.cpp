@@ -80,6 +80,7 @@ pymes::EomSigma& SL(pymes_eom* h, const char* who) {
     if (!h || !h->s || !h->ctx) throw pymes::Error(std::string(who) + ": null or destroyed EOM handle");
     Engine& e = E(h->ctx);
     e.refuse_if_sharded(who);
+    e.refuse_if_direct(who);
     if (e.capturing()) throw pymes::Error(std::string(who) + " while a launch graph is being recorded");
     return *h->s;
 }
@@ -383,6 +384,21 @@ int pymes_derive_context(pymes_ctx* src, pymes_ctx* dst, int n_frozen, const dou
 }
 int pymes_set_integral_shard(pymes_ctx* ctx, int rank, int world) {
     return guarded([&] { E(ctx).set_integral_shard(rank, world); });
+}
+int pymes_set_integral_direct(pymes_ctx* ctx, int64_t chunk_bytes) {
+    return guarded([&] { E(ctx).set_integral_direct(chunk_bytes); });
+}
+int pymes_direct_info(pymes_ctx* ctx, int64_t* info) {
+    return guarded([&] {
+        need(info, "info");
+        E(ctx).direct_info(info);
+    });
+}
+int pymes_direct_rows(pymes_ctx* ctx, int64_t r0, int64_t r1, const double** vp, const double** vm, int64_t* ldp, int64_t* ldm) {
+    return guarded([&] {
+        need(vp, "vp"); need(vm, "vm"); need(ldp, "ldp"); need(ldm, "ldm");
+        E(ctx).direct_rows(r0, r1, vp, vm, ldp, ldm);
+    });
 }
 int pymes_integral_bytes(pymes_ctx* ctx, int64_t* bytes) {
     return guarded([&] {
@@ -1051,6 +1067,7 @@ int pymes_eom_sigma_prepare(pymes_ctx* ctx, const double* f_host, const double* 
         need(f_host, "f_host"); need(t2, "t2");
         Engine& e = E(ctx);
         e.refuse_if_sharded("EOM sigma");
+        e.refuse_if_direct("EOM sigma");
         if (e.capturing()) throw pymes::Error("eom_sigma_prepare while a launch graph is being recorded");
         pymes::EomSigma* s = new pymes::EomSigma(e, f_host, t2, dressed != 0);
         *out = new pymes_eom{s, ctx};
@@ -1078,6 +1095,7 @@ int pymes_eom_diagonals(pymes_ctx* ctx, const double* f_host, const double* t2, 
     return guarded([&] {
         need(f_host, "f_host"); need(t2, "t2"); need(d1, "d1"); need(d2, "d2");
         E(ctx).refuse_if_sharded("EOM diagonals");
+        E(ctx).refuse_if_direct("EOM diagonals");
         pymes::eom_diagonals(E(ctx), f_host, t2, dressed != 0, d1, d2);
     });
 }

@@ -97,6 +97,8 @@ void Engine::doubles_residual(const double* f, const double* t2, double* r2, uns
     refuse_if_sharded("doubles_residual");
     const bool dcd = flags & PYMES_DCD, dressed = flags & PYMES_USE_DRESSED, skip_ladder = flags & PYMES_SKIP_LADDER,
                sym_ladder = flags & PYMES_SYM_LADDER, sym_rings = flags & PYMES_SYM_RINGS;
+    // (factor-direct: the CCD / DCD loop runs here with the pair-packed undressed ladder; the forms that read V_abcd are refused)
+    if (!skip_ladder && (!sym_ladder || dressed)) refuse_if_direct("doubles_residual with the full or dressed V_abcd");
     const bool quad = !dcd;
     const int64_t o = no, v = nv, nn = n;
     if (sym_rings) {      // symmetry-reduced evaluation = the one-rank case of the sharded form
@@ -784,6 +786,7 @@ void Engine::residual_finish_pairs(const double* f, const double* t2, const doub
 // 32 rows with b < block end — 56 % of the traffic of the full rows at nv = 200.
 void Engine::dress_abcd_rows(const double* t1, int a0, int a1, bool lower_only) {
     refuse_if_sharded("dress_abcd_rows");
+    refuse_if_direct("dress_abcd_rows");
     if (a0 < 0 || a1 > nv || a0 > a1) throw Error("dress_abcd_rows: bad range");
     if (a0 == a1) return;
     TView t = make_view(const_cast<double*>(t1), {(int64_t)nv, (int64_t)no});
@@ -809,6 +812,7 @@ void Engine::dress_abcd_rows(const double* t1, int a0, int a1, bool lower_only) 
 
 void Engine::ladder(const double* t2, double* r2, int a0, int a1, bool dressed, double beta) {
     refuse_if_sharded("ladder");
+    refuse_if_direct("ladder");
     const int64_t o = no, v = nv;
     if (a0 < 0 || a1 > nv || a0 > a1) throw Error("ladder: bad a-range");
     if (a0 == a1) return;
@@ -836,6 +840,8 @@ bool Engine::ensure_ladder_pack(int64_t row0, int64_t row1, bool dressed) {
 }
 
 Engine::PackedV Engine::ladder_rows(const char* who, int64_t row0, int64_t row1, bool dressed) {
+    // (factor-direct: the undressed ladders never come here, they build their rows chunk by chunk)
+    if (direct_.on) refuse_if_direct(dressed ? (std::string(who) + " with the dressed V_abcd").c_str() : who);
     if (shard_on_) {
         check_shard_rows(who, row0, row1, dressed);
         return {srows_.Vp, srows_.Vm, false};
@@ -866,7 +872,8 @@ void Engine::ladder_sym(const double* t2, double* L, int64_t row0, int64_t row1,
     if (hole < 0 || hole > 2) throw Error("ladder_sym: hole must be 0, 1 (CCSD) or 2 (DCSD)");
     if (row0 == row1) return;
     const int64_t rows = row1 - row0;
-    const PackedV V = ladder_rows("ladder_sym", row0, row1, dressed);
+    const bool direct = direct_.on && !dressed;
+    const PackedV V = direct ? PackedV{nullptr, nullptr, false} : ladder_rows("ladder_sym", row0, row1, dressed);
     if (V.packed) {
         stats.permute_calls++;
         stats.permute_bytes += 8.0 * 2.0 * double(rows) * double(v * v);
@@ -880,10 +887,15 @@ void Engine::ladder_sym(const double* t2, double* L, int64_t row0, int64_t row1,
     // L rows [row0,row1): [ LS (opp) | LA (opm) ], row length o*o
     TView Lrows = make_view(L + row0 * o * o, {rows, o * o});
     TView LS = slice(Lrows, 1, 0, opp), LA = slice(Lrows, 1, opp, o * o);
-    contract(1.0, packed_rows(V.Vp, rows, npp), "rk", pitched(Sp, npp, opp, ldp), "kn", 0.0, LS, "rn");
-    if (opm > 0) {
-        if (npm > 0) contract(1.0, packed_rows(V.Vm, rows, npm), "rk", pitched(Am, npm, opm, ldm), "kn", 0.0, LA, "rn");
-        else zero(LA);
+    if (direct) {
+        direct_ladder_products(row0, row1, pitched(Sp, npp, opp, ldp), pitched(Am, npm, opm, ldm), LS, LA);
+        if (opm > 0 && npm <= 0) zero(LA);
+    } else {
+        contract(1.0, packed_rows(V.Vp, rows, npp), "rk", pitched(Sp, npp, opp, ldp), "kn", 0.0, LS, "rn");
+        if (opm > 0) {
+            if (npm > 0) contract(1.0, packed_rows(V.Vm, rows, npm), "rk", pitched(Am, npm, opm, ldm), "kn", 0.0, LA, "rn");
+            else zero(LA);
+        }
     }
     if (!hole) return;
     // the hole ladder (ccd.py:175-186) in the same rows: I = V~_klij (+ sum_cd V_klcd T_cdij for CCSD, from the halves of T
@@ -899,6 +911,7 @@ void Engine::ladder_sym(const double* t2, double* L, int64_t row0, int64_t row1,
 // vector is 228 tiles on 256 CUs, k vectors are k x 228 tiles with a k-split tail.
 void Engine::ladder_sym_multi(const double* const* xs, int k, double* L_all, bool dressed) {
     refuse_if_sharded("ladder_sym_multi");
+    refuse_if_direct("ladder_sym_multi");
     const PairDims d = pair_dims();
     const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm, ldp = d.ldp, ldm = d.ldm;
     if (k < 1) return;
@@ -931,6 +944,7 @@ void Engine::ladder_sym_multi(const double* const* xs, int k, double* L_all, boo
 
 void Engine::ladder_sym_adjoint(const double* x, double* LSp, double* LAp, bool dressed) {
     refuse_if_sharded("ladder_sym_adjoint");
+    refuse_if_direct("ladder_sym_adjoint");
     const PairDims d = pair_dims();
     const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm, ldp = d.ldp, ldm = d.ldm;
     if (ensure_ladder_pack(0, npp, dressed)) {
@@ -953,6 +967,7 @@ void Engine::ladder_sym_adjoint(const double* x, double* LSp, double* LAp, bool 
 
 void Engine::ladder_sym_adjoint_multi(const double* const* xs, int k, double* LSp, double* LAp, bool dressed) {
     refuse_if_sharded("ladder_sym_adjoint_multi");
+    refuse_if_direct("ladder_sym_adjoint_multi");
     if (k < 1) return;
     const PairDims d = pair_dims();
     const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opm = d.opm, ldp = d.adj_ldp, ldm = d.adj_ldm, K = k;
@@ -1142,6 +1157,12 @@ void Engine::hole_ladder_packed_multi(const double* const* xs, const double* con
 bool Engine::bra_dress_pays() const {
     const PairDims d = pair_dims();
     const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm;
+    if (direct_.on) {
+        // factor-direct: there are no stored rows to dress; the T1 dressing rides on tau and the Q_kb products
+        if (const char* e = getenv("PYMES_LADDER_DRESS"))
+            if (atoi(e) != 0) refuse_if_direct("PYMES_LADDER_DRESS=1 (the bra dressing of the stored rows)");
+        return false;
+    }
     if (!dev::ladder_dress_ok(no, nv) || dress_off_) return false;
     if (const char* e = getenv("PYMES_LADDER_DRESS")) return atoi(e) != 0;
     const double t_dress = 16.0 * double(npp) * double(npp + npm) / 4.0e12 + 20e-6;
@@ -1158,7 +1179,9 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
     const int64_t rows = row1 - row0, qrows = q1 - q0;
     // ---- static packs (once per solve) ---------------------------------------------------------
     // (integral sharding: the stored rows take the place of the pack; the dressing writes to its own copy as ever)
-    const PackedV V = rows > 0 ? ladder_rows("ladder_t1", row0, row1, false) : PackedV{nullptr, nullptr, false};
+    // (factor-direct: no rows are held; they are built chunk by chunk where the product is taken, below)
+    const bool direct = direct_.on;
+    const PackedV V = rows > 0 && !direct ? ladder_rows("ladder_t1", row0, row1, false) : PackedV{nullptr, nullptr, false};
     // Bra dressing of the rank's rows of the packed V_abcd instead of its share of the Q_kb products: the two rank-no updates of
     // dev::ladder_dress move 2 x 6.5 GB at (50,200) where Q_kbij = sum_cd V_kbcd tau_cdij costs 1.0e12 flops (13.9 ms);
     // the dressed copy W takes the place of V in the ladder product and QK carries the small brackets only.
@@ -1239,7 +1262,7 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
         }
         {
             GemmGroupScope grp(stream);
-            if (rows > 0) {
+            if (rows > 0 && !direct) {
                 contract(1.0, packed_rows(const_cast<double*>(Ap), rows, npp), "rk", SpT, "kn", 0.0, LS, "rn");
                 if (opm > 0 && npm > 0) contract(1.0, packed_rows(const_cast<double*>(Am_), rows, npm), "rk", AmT, "kn", 0.0, LA, "rn");
             }
@@ -1249,6 +1272,7 @@ void Engine::ladder_t1(const double* t1, const double* t2, double* L, int64_t ro
             }
             grp.close();
         }
+        if (rows > 0 && direct) direct_ladder_products(row0, row1, SpT, AmT, LS, LA);
         if (rows > 0 && opm > 0 && npm <= 0) zero(LA);
         if (qrows > 0 && dress) {
             // QK = W_kbij alone (ccsd.py:322-343, the (i,j)-, (c,j)- and (i,d)-ket parts of the bras (k,b))
@@ -2086,6 +2110,7 @@ int64_t shard_staging_bytes() {
 void Engine::set_integral_shard(int rank, int world) {
     if (world < 1 || rank < 0 || rank >= world) throw Error("integral shard: need 0 <= rank < world");
     if (shard_on_) throw Error("the context already shards its integrals");
+    refuse_if_direct("pymes_set_integral_shard");
     for (int p = 0; p < 16; ++p)
         if (V_[p] || Vd_[p]) throw Error("pymes_set_integral_shard must be called before any pymes_set_V_* call");
     shard_on_ = true;
@@ -2143,7 +2168,148 @@ int64_t Engine::integral_bytes() const {
     for (auto& kv : static_doubles_) d += kv.second;
     if (lpack_.Vp) d += (lpack_.row1 - lpack_.row0) * (lp + lm);
     if (srows_.Vp) d += (srows_.row1 - srows_.row0) * (lp + lm);
+    if (direct_.Bvv) d += nv * direct_.qp * direct_.xp;
+    if (direct_.Vp) d += direct_.cap * (lp + lm);
+    if (direct_.planes) d += direct_.prow * nv * nv;
     return d * static_cast<int64_t>(sizeof(double));
+}
+
+// -----------------------------------------------------------------------------------
+// factor-direct particle ladder (pymes_set_integral_direct): nothing of size v^4 exists; the rows of the pair-packed V_abcd
+// are rebuilt from the virtual-virtual factors chunk by chunk inside every ladder call
+// -----------------------------------------------------------------------------------
+void Engine::set_integral_direct(int64_t chunk_bytes) {
+    if (chunk_bytes < 0) throw Error("pymes_set_integral_direct: chunk_bytes must be >= 0 (0: PYMES_DIRECT_CHUNK_BYTES, default 1 GiB)");
+    if (direct_.on) throw Error("the context is already factor-direct (pymes_set_integral_direct)");
+    refuse_if_sharded("pymes_set_integral_direct");
+    for (int p = 0; p < 16; ++p)
+        if (V_[p] || Vd_[p]) throw Error("pymes_set_integral_direct must be called before any pymes_set_V_* call");
+    if (chunk_bytes == 0) {
+        chunk_bytes = int64_t(1) << 30;
+        if (const char* e = getenv("PYMES_DIRECT_CHUNK_BYTES")) {
+            const long long b = atoll(e);
+            if (b > 0) chunk_bytes = b;
+        }
+    }
+    // the row builder: PYMES_DIRECT_BUILDER=gemm|fused; without it the fused kernel where the backend has it (every fused run
+    // was below every gemm run in profiles/direct/probe_direct.txt), else the gemm route
+    bool fused = dev::direct_rows_fused_ok();
+    if (const char* e = getenv("PYMES_DIRECT_BUILDER")) {
+        const std::string b(e);
+        if (b == "fused") {
+            if (!dev::direct_rows_fused_ok())
+                throw Error("PYMES_DIRECT_BUILDER=fused: the fused row builder of the factor-direct mode is not available in this backend");
+            fused = true;
+        } else if (b == "gemm") {
+            fused = false;
+        } else {
+            throw Error("PYMES_DIRECT_BUILDER must be gemm or fused (factor-direct mode, pymes_set_integral_direct)");
+        }
+    }
+    direct_.on = true;
+    direct_.fused = fused;
+    direct_.chunk_bytes = chunk_bytes;
+}
+
+void Engine::refuse_if_direct(const char* who) const {
+    if (!direct_.on) return;
+    throw Error(std::string(who) + ": not available on a factor-direct context (pymes_set_integral_direct): it holds the "
+                "virtual-virtual factors and rebuilds the undressed pair-packed rows of V_abcd chunk by chunk, never the full, "
+                "dressed or stored block");
+}
+
+// B_vv [nv][qp][xp] (device_api.h, direct_rows_fused) from the factors on the device, and the chunk buffers: cap rows of
+// V^+ / V^- at the ladder pitches and, for the gemm builder, as many planes V[a,b,:,:] — all within chunk_bytes (at least one row).
+void Engine::direct_setup(const double* Bd, int naux) {
+    const PairDims d = pair_dims();
+    const int64_t v = nv, nn = n, rowb = 8 * (d.vlp + d.vlm), planeb = 8 * v * v;
+    dev::stream_sync(stream);
+    for (double** p : {&direct_.Bvv, &direct_.Vp, &direct_.Vm, &direct_.planes}) {
+        dev::dfree(*p);
+        *p = nullptr;
+    }
+    direct_.naux = naux;
+    direct_.qp = (int64_t(naux) + 7) & ~int64_t(7);
+    direct_.xp = (v + 63) & ~int64_t(63);
+    direct_.cap = std::max<int64_t>(1, std::min<int64_t>(d.npp, direct_.chunk_bytes / (rowb + (direct_.fused ? 0 : planeb))));
+    direct_.prow = direct_.fused ? 0 : direct_.cap;
+    const int64_t bsz = v * direct_.qp * direct_.xp;
+    direct_.Bvv = static_cast<double*>(dev::dmalloc(sizeof(double) * bsz));
+    direct_.Vp = static_cast<double*>(dev::dmalloc(sizeof(double) * direct_.cap * d.vlp));
+    direct_.Vm = static_cast<double*>(dev::dmalloc(sizeof(double) * direct_.cap * d.vlm));
+    if (direct_.prow) direct_.planes = static_cast<double*>(dev::dmalloc(sizeof(double) * direct_.prow * v * v));
+    dev::memset_zero(direct_.Bvv, sizeof(double) * bsz, stream);
+    const int64_t dims[3] = {naux, v, v}, sst[3] = {nn * nn, nn, 1}, dst[3] = {direct_.xp, direct_.qp * direct_.xp, 1};
+    permute(1.0, make_view(const_cast<double*>(Bd) + no * nn + no, 3, dims, sst), "Qax", 0.0, make_view(direct_.Bvv, 3, dims, dst), "Qax");
+}
+
+void Engine::direct_build(int64_t c0, int64_t c1, int builder) {
+    const PairDims d = pair_dims();
+    const int64_t v = nv, plane = v * v, pa = direct_.qp * direct_.xp;
+    if (!direct_.Bvv) throw Error("factor-direct context: the integrals have not been set (pymes_set_V_from_factors)");
+    if (c0 < 0 || c1 > d.npp || c0 >= c1 || c1 - c0 > direct_.cap) throw Error("factor-direct context: bad chunk of pair rows");
+    const bool fused = builder < 0 ? direct_.fused : builder == 1;
+    if (fused) {
+        dev::direct_rows_fused(direct_.Bvv, direct_.Vp, direct_.Vm, nv, direct_.qp, direct_.xp, c0, c1, stream, d.vlp, d.vlm);
+        return;
+    }
+    if (!direct_.planes) throw Error("factor-direct context: the gemm builder needs its planes buffer (PYMES_DIRECT_BUILDER=gemm at set-up)");
+    // planes[r - c0][c][d] = sum_Q B_vv[a][Q][c] B_vv[b][Q][d] = V_abcd for the rows r = P(a,b) of the chunk: one batched product
+    // per a (consecutive b are consecutive rows); V_abdc is the transposed plane, so nothing is computed twice
+    for (int64_t r = c0; r < c1;) {
+        const int64_t a = a_of_pair_row(r), b = r - a * (a + 1) / 2;
+        const int64_t nb = std::min(c1, (a + 1) * (a + 2) / 2) - r;
+        const int64_t ad[2] = {direct_.naux, v}, as[2] = {direct_.xp, 1};
+        const int64_t bd[3] = {nb, direct_.naux, v}, bs[3] = {pa, direct_.xp, 1};
+        contract(1.0, make_view(direct_.Bvv + a * pa, 2, ad, as), "Qc", make_view(direct_.Bvv + b * pa, 3, bd, bs), "bQd", 0.0,
+                 make_view(direct_.planes + (r - c0) * plane, {nb, v, v}), "bcd", "b");
+        r += nb;
+    }
+    dev::gemm_group_sync();
+    // (the nr == 0 form of ladder_pack_V takes row r from V + r plane and packs every row as it is: the V^- rows of the pairs
+    // a == b, zero in the [nr,nr,nc,nc] form, are cleared afterwards as shard_rows_from does)
+    dev::ladder_pack_V(direct_.planes - c0 * plane, direct_.Vp, direct_.Vm, 0, nv, c0, c1, stream, d.vlp, d.vlm);
+    for (int64_t a = a_of_pair_row(c0); a < v; ++a) {
+        const int64_t r = a * (a + 3) / 2;
+        if (r >= c1) break;
+        if (r >= c0) dev::memset_zero(direct_.Vm + (r - c0) * d.vlm, sizeof(double) * d.vlm, stream);
+    }
+}
+
+void Engine::direct_ladder_products(int64_t row0, int64_t row1, const TView& SpT, const TView& AmT, const TView& LS,
+                                    const TView& LA) {
+    const PairDims d = pair_dims();
+    dev::gemm_group_sync();            // (the chunk buffers are rewritten below: nothing that reads them may still be queued)
+    for (int64_t c0 = row0; c0 < row1; c0 += direct_.cap) {
+        const int64_t c1 = std::min(row1, c0 + direct_.cap), m = c1 - c0;
+        direct_build(c0, c1);
+        GemmGroupScope grp(stream);
+        contract(1.0, packed_rows(direct_.Vp, m, d.npp), "rk", SpT, "kn", 0.0, slice(LS, 0, c0 - row0, c1 - row0), "rn");
+        if (d.opm > 0 && d.npm > 0)
+            contract(1.0, packed_rows(direct_.Vm, m, d.npm), "rk", AmT, "kn", 0.0, slice(LA, 0, c0 - row0, c1 - row0), "rn");
+        grp.close();
+    }
+}
+
+void Engine::direct_info(int64_t out[5]) const {
+    if (!direct_.on) throw Error("pymes_direct_info: the context is not factor-direct (pymes_set_integral_direct)");
+    const PairDims d = pair_dims();
+    out[0] = direct_.naux;
+    out[1] = direct_.cap;
+    out[2] = direct_.Bvv ? 8 * nv * direct_.qp * direct_.xp : 0;
+    out[3] = direct_.Vp ? 8 * (direct_.cap * (d.vlp + d.vlm) + direct_.prow * nv * nv) : 0;
+    out[4] = direct_.fused ? 1 : 0;
+}
+
+void Engine::direct_rows(int64_t r0, int64_t r1, const double** vp, const double** vm, int64_t* ldp, int64_t* ldm) {
+    if (!direct_.on) throw Error("pymes_direct_rows: the context is not factor-direct (pymes_set_integral_direct)");
+    if (capturing_) throw Error("pymes_direct_rows while a launch graph is being recorded");
+    direct_build(r0, r1);
+    dev::stream_sync(stream);
+    *vp = direct_.Vp;
+    *vm = direct_.Vm;
+    *ldp = pair_dims().vlp;
+    *ldm = pair_dims().vlm;
 }
 
 // The planes V[a,b,:,:] of this rank's pair rows (V0: the element V[0,0,0,0] of the virtual block, strides st), gathered in
@@ -2572,6 +2738,9 @@ void Engine::derive_from(Engine& src, int n_frozen, const double* C_host, int nv
     if (capturing_ || src.capturing_) fail("not inside a launch graph");
     if (src.shard_on_) fail("the source context shards its integrals (pymes_set_integral_shard): derive from a replicated context");
     if (shard_on_) fail("the destination context shards its integrals (pymes_set_integral_shard): it must be a plain empty context");
+    if (src.direct_.on)
+        fail("the source context is factor-direct (pymes_set_integral_direct) and holds no V_abcd: derive from a stored context");
+    if (direct_.on) fail("the destination context is factor-direct (pymes_set_integral_direct): it must be a plain empty context");
     if (src.device != device) fail("the source and the destination are on different devices");
     if (!C_host) fail("null pointer: C");
     if (n_frozen < 0 || n_frozen >= src.no)

@@ -241,6 +241,18 @@ void ladder_pack_V(const double* V, double* Vp, double* Vm, int nr, int nc, int6
 // product library only (the host simulator has no definition: a weak one in the engine throws).
 void ladder_pack_V_factors(const double* B, double* Vp, double* Vm, int naux, int n, int no, int64_t rp0, int64_t rp1,
                            stream_t s, int64_t ldvp, int64_t ldvm);
+// direct_rows_fused (factor-direct ladder, pymes_set_integral_direct): the same rows from the context's compact copy of the
+// virtual-virtual factors, every iteration.  Layout of Bvv: [nv][qp][xp] doubles, Bvv[a][Q][x] = B[Q, no+a, no+x], a slowest —
+// the Q-panel of one a is one contiguous [qp][xp] matrix —, qp = naux rounded up to a multiple of 8, xp = nv rounded up to a
+// multiple of 64, the padding ZERO (the kernel loads whole 8 x 64 panels without a bounds test; the products of the gemm
+// builder read the [naux][nv] part through strided views).  Block = one pair row and one 64 x 64 tile pair (tc >= td); each of
+// the 4 waves holds 2 x 2 MFMA blocks of X = V_abcd and of Y = V_abdc, so that every operand fragment read from LDS serves two
+// MFMAs; the four Q-panels are staged 8 Q at a time with 16-byte loads, double-buffered.  Writes Vp / Vm exactly as
+// ladder_pack_V does (pad columns of the pitch untouched).  The product library only: the engine's weak stand-in throws and
+// direct_rows_fused_ok() is false there.
+bool direct_rows_fused_ok();
+void direct_rows_fused(const double* Bvv, double* Vp, double* Vm, int nv, int64_t qp, int64_t xp, int64_t rp0, int64_t rp1,
+                       stream_t s, int64_t ldvp, int64_t ldvm);
 // ---- (T) correction (cc.cpp, Engine::ccsd_t): the energy of a batch of nt consecutive unique triples t0, t0 + 1, ... (numbered
 // i ascending, then j <= i, then k <= j).  W [nt][v][v][v] holds W_ijk of each (the connected triples of the six permuted
 // products); Y = W + the disconnected term V_ijab[j,k,b,c] t1[a,i] + V_ijab[i,k,a,c] t1[b,j] + V_ijab[i,j,a,b] t1[c,k] is formed

@@ -156,6 +156,7 @@ Engine::~Engine() {
         dev::dfree(lpack_.Vm);
         dev::dfree(srows_.Vp);
         dev::dfree(srows_.Vm);
+        for (double* p : {direct_.Bvv, direct_.Vp, direct_.Vm, direct_.planes}) dev::dfree(p);
         dev::dfree(eps_o);
         dev::dfree(eps_v);
         arena.release();
@@ -309,6 +310,7 @@ bool Engine::has_block(int pattern, bool dressed) const {
 }
 TView Engine::block(int pattern, bool dressed) {
     if ((pattern & 15) == 15) refuse_if_sharded("integral block 'abcd'");
+    if ((pattern & 15) == 15) refuse_if_direct("integral block 'abcd'");
     double* p = dressed ? Vd_[pattern & 15] : V_[pattern & 15];
     if (!p)
         throw Error(std::string(dressed ? "dressed" : "undressed") + " integral block '" + canonical_name(pattern) +
@@ -318,12 +320,14 @@ TView Engine::block(int pattern, bool dressed) {
 double* Engine::ensure_block(int pattern) {
     pattern &= 15;
     if (pattern == 15) refuse_if_sharded("storage of the block 'abcd'");
+    if (pattern == 15) refuse_if_direct("storage of the block 'abcd'");
     invalidate_static();
     if (!V_[pattern]) V_[pattern] = static_cast<double*>(dev::dmalloc(sizeof(double) * block_size(pattern)));
     return V_[pattern];
 }
 double* Engine::ensure_dressed(int pattern) {
     if (pattern == 15) refuse_if_sharded("dressing of the block 'abcd'");
+    if (pattern == 15) refuse_if_direct("dressing of the block 'abcd'");
     if (!Vd_[pattern]) Vd_[pattern] = static_cast<double*>(dev::dmalloc(sizeof(double) * block_size(pattern)));
     return Vd_[pattern];
 }
@@ -684,6 +688,7 @@ void Engine::contract(double alpha, const TView& A, const char* sa, const TView&
 // integral blocks
 // ---------------------------------------------------------------------------------
 void Engine::set_V_full(const double* V, bool on_device, const int64_t strides[4]) {
+    refuse_if_direct("set_V_pqrs (there are no factors to build the ladder rows from)");
     invalidate_static();
     if (shard_on_) {
         set_V_full_sharded(V, on_device, strides);
@@ -726,6 +731,7 @@ void Engine::set_V_full(const double* V, bool on_device, const int64_t strides[4
 
 void Engine::set_V_block(const char* name, const double* data, bool on_device, const int64_t strides[4]) {
     const int pat = pattern_of_name(name);
+    refuse_if_direct("set_V_block (there are no factors to build the ladder rows from)");
     invalidate_static();
     if (pat == 15 && shard_on_) {
         if (on_device) refuse_if_sharded("set_V_block('abcd') from device memory");
@@ -755,7 +761,8 @@ void Engine::set_V_from_factors(const double* B_host, int naux) {
     try {
         dev::memcpy_h2d(Bd, B_host, sizeof(double) * naux * nn * nn, stream);
         TView Bv = make_view(Bd, {naux, nn, nn});
-        for (int pat = 0; pat < (shard_on_ ? 15 : 16); ++pat) {
+        if (direct_.on) direct_setup(Bd, naux);                // B_vv and the chunk buffers, before any launch graph exists
+        for (int pat = 0; pat < (shard_on_ || direct_.on ? 15 : 16); ++pat) {
             if (!V_[pat]) V_[pat] = static_cast<double*>(dev::dmalloc(sizeof(double) * block_size(pat)));
             auto rng = [&](int pos, int64_t& lo, int64_t& hi) {
                 const bool virt = pat >> (3 - pos) & 1;
@@ -786,6 +793,12 @@ namespace dev {
 __attribute__((weak)) void ladder_pack_V_factors(const double*, double*, double*, int, int, int, int64_t, int64_t, stream_t,
                                                  int64_t, int64_t) {
     throw std::runtime_error("ladder_pack_V_factors: not available in this backend");
+}
+// ... and without the fused row builder of the factor-direct ladder (the gemm builder runs everywhere)
+__attribute__((weak)) bool direct_rows_fused_ok() { return false; }
+__attribute__((weak)) void direct_rows_fused(const double*, double*, double*, int, int64_t, int64_t, int64_t, int64_t, stream_t,
+                                             int64_t, int64_t) {
+    throw std::runtime_error("direct_rows_fused: not available in this backend");
 }
 // ... and without the (T) energy kernel
 __attribute__((weak)) int64_t triples_partial_doubles(int nv, int64_t nt) { return nt * ((int64_t)nv * (nv + 1) / 2); }

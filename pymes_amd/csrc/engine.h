@@ -195,7 +195,21 @@ class Engine {
     bool integral_shard() const { return shard_on_; }
     void refuse_if_sharded(const char* who) const;     // throws (naming the mode) when the context shards its integrals
     void shard_rows(const double** vp, const double** vm, int64_t* row0, int64_t* row1, int64_t* ldp, int64_t* ldm) const;
-    // bytes held for integrals: undressed and dressed blocks, the stored / packed ladder rows and the static packs
+    // Factor-direct particle ladder (pymes_set_integral_direct, before any set_V_*; set_V_from_factors only): V_abcd is never
+    // allocated, neither as a block nor as packed rows.  The context keeps the virtual-virtual factors B_vv (device_api.h,
+    // direct_rows_fused: the layout) and one pair of chunk buffers; ladder_t1 / ladder_sym (undressed) rebuild the V^+ / V^- rows
+    // of every chunk [c0,c1) of their row range from B_vv, each call, and multiply them at once.  chunk_bytes: the budget of the
+    // chunk buffers (0: PYMES_DIRECT_CHUNK_BYTES, default 1 GiB); the chunk edges depend on it and on (nv, naux) alone, so
+    // the launches of a recorded graph are static.
+    void set_integral_direct(int64_t chunk_bytes);
+    bool integral_direct() const { return direct_.on; }
+    void refuse_if_direct(const char* who) const;      // throws (naming the mode) on a factor-direct context
+    // {naux, rows per chunk, bytes of B_vv, bytes of the chunk buffers (rows and planes), builder (0 gemm, 1 fused)}
+    void direct_info(int64_t out[5]) const;
+    // the rows [r0,r1) (at most one chunk) built into the chunk buffers: device pointers and pitches, for tests (read-only)
+    void direct_rows(int64_t r0, int64_t r1, const double** vp, const double** vm, int64_t* ldp, int64_t* ldm);
+    // bytes held for integrals: undressed and dressed blocks, the stored / packed ladder rows, the static packs and, on a
+    // factor-direct context, B_vv and the chunk buffers
     int64_t integral_bytes() const;
     TView block(int pattern, bool dressed = false);       // throws if the block is absent
     double* ensure_block(int pattern);                    // storage of an undressed block (allocated if absent); cached
@@ -468,6 +482,16 @@ class Engine {
     void shard_rows_from_factors(const double* Bd, int naux);
     void check_shard_rows(const char* who, int64_t row0, int64_t row1, bool dressed) const;
     void check_shard_rank(const char* who, int rank, int world) const;
+    // factor-direct mode: B_vv [nv][qp][xp] (zero-padded, device_api.h), the chunk buffers Vp / Vm (cap rows at the ladder
+    // pitches) and, for the gemm builder, planes [prow][nv][nv] (prow <= cap rows of V[a,b,:,:] at a time)
+    struct Direct {
+        bool on = false, fused = false;
+        int64_t chunk_bytes = 0, naux = 0, qp = 0, xp = 0, cap = 0, prow = 0;
+        double *Bvv = nullptr, *Vp = nullptr, *Vm = nullptr, *planes = nullptr;
+    } direct_;
+    void direct_setup(const double* Bd, int naux);
+    // rows [c0,c1) (c1 - c0 <= cap) into the chunk buffers, by the builder of the context (or the one asked for: -1 = its own)
+    void direct_build(int64_t c0, int64_t c1, int builder = -1);
     struct LadderPack {   // V^+ / V^- rows of the pair-packed ladder
         double* Vp = nullptr;
         double* Vm = nullptr;
@@ -485,6 +509,9 @@ class Engine {
     // The rows [row0,row1) to multiply with: the stored rows of an integral-sharded context (the only copy; checked against
     // its (rank, world) and `dressed`), else the cache.
     PackedV ladder_rows(const char* who, int64_t row0, int64_t row1, bool dressed);
+    // Factor-direct mode: the two products of the particle ladder for the rows [row0,row1) (LS / LA: those rows of L), chunk by
+    // chunk: build the rows of the chunk from B_vv, multiply them with the packed amplitudes (SpT / AmT).
+    void direct_ladder_products(int64_t row0, int64_t row1, const TView& SpT, const TView& AmT, const TView& LS, const TView& LA);
     // V_klcd with (k,l) and (c,d) pair-packed (rows P(k,l) at the pitch of the V rows), packed on first use; static per
     // solve: dressed ijab == undressed ijab
     PackedV ijab_pack();

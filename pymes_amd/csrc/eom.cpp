@@ -1116,6 +1116,7 @@ void lambda_rdm2(Engine& e, const double* t1, const double* t2, const double* la
 
 double lambda_rdm2_expectation(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2) {
     e.refuse_if_sharded("rdm2_expectation");
+    e.refuse_if_direct("rdm2_expectation");
     for (int pat = 0; pat < 16; ++pat)
         if (!e.has_block(pat)) throw Error("rdm2_expectation: the operator block '" + canonical_name(pat) + "' is not set");
     rdm2_check(e, "rdm2_expectation", t1, t2, lam1, lam2);
@@ -1307,6 +1308,7 @@ IpEaSigma::IpEaSigma(Engine& eng, Kind kind_, const double* f_host, const double
     if (!f_host || !t2) throw Error("ip/ea sigma: null Fock matrix / amplitudes");
     const char* who = kind == IP ? "IP-EOM-CCSD sigma" : "EA-EOM-CCSD sigma";
     if (kind == EA) e.refuse_if_sharded(who);
+    if (kind == EA) e.refuse_if_direct(who);
     for (const char* name : blocks(kind))
         if (!e.has_block(pattern_of_name(name), dressed))
             throw Error(std::string(who) + ": the " + (dressed ? "dressed " : "") + "block '" + name + "' is missing");

@@ -2019,6 +2019,108 @@ __global__ void __launch_bounds__(256) ladder_pack_V_factors_kernel(const double
     }
 }
 
+// Factor-direct ladder (pymes_set_integral_direct): the same rows every iteration, from the compact factors Bvv [nv][qp][xp]
+// (device_api.h: the Q-panel of one a is a contiguous zero-padded [qp][xp] matrix, qp % 8 == 0, xp % 64 == 0, so whole panels
+// are loaded without a bounds test).  Block = one pair row P(a,b) and one 64 x 64 tile pair (tc >= td); wave w owns the
+// 32 x 32 quadrant (w >> 1, w & 1) of
+//   X[c,d] = sum_Q Bvv[a][Q][c] Bvv[b][Q][d] = V_abcd,    Y[c,d] = sum_Q Bvv[b][Q][c] Bvv[a][Q][d] = V_abdc
+// as 2 x 2 MFMA blocks of each: per 4 Q it reads 8 operand fragments from LDS for 8 MFMAs (ladder_pack_V_factors_kernel: 4
+// for 2).  The four panels (a / b rows, c / d columns) are staged 8 Q at a time, one 16-byte load per thread and panel, into
+// the other half of a double buffer while the MFMAs of the current stage run (one barrier per stage).  Pitch 80: the two Q
+// rows a half-wave reads lie 128 bytes apart in the banks.  Bounded to 128 registers (116 VGPR, no scratch): four waves per
+// SIMD, four blocks per CU (4 x 40 KB of LDS) cover the barrier and the L2 latency of the 8-Q stages; with the 174 registers
+// and 2 waves per SIMD the allocator takes when left alone the kernel ran at 23.9 instead of 33.1 TFLOP/s, a 16-Q stage
+// at 2 waves per SIMD at 27.8 (profiles/direct/).  A wave whose quadrant lies above the diagonal of a diagonal tile
+// or beyond nv has nothing to store and skips its MFMAs.  Consecutive blocks are the tile pairs of one row, consecutive rows
+// share a: the panels of a (qp x xp doubles, 1 MB at (200, 500)) stay in L2.
+constexpr int kDirT = 64, kDirK = 8, kDirP = 80;
+__global__ void __launch_bounds__(256, 4) direct_rows_fused_kernel(const double* __restrict__ Bvv, double* __restrict__ Vp,
+                                                                double* __restrict__ Vm, int nv, int xp, long apitch, int nstage,
+                                                                long rp0, long ntp, long npp, long npm) {
+    __shared__ __attribute__((aligned(16))) double sm[2][4][kDirK][kDirP];          // 40 KB: four blocks per CU
+    const long bid = blockIdx.x;
+    const long row = bid / ntp;               // local pair row
+    const long tp = bid - row * ntp;          // tile pair (tc >= td)
+    int a, b, tc, td;
+    unrank_pair(rp0 + row, a, b);
+    unrank_pair(tp, tc, td);
+    const int c0 = tc * kDirT, d0 = td * kDirT;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int wc = (w >> 1) * 32, wd = (w & 1) * 32, l15 = lane & 15, l4 = lane >> 4;
+    const bool work = c0 + wc < nv && d0 + wd < nv && c0 + wc + 31 >= d0 + wd;     // (wave-uniform)
+    // staging: Q row sk of the stage, columns sx, sx + 1 of each panel
+    const int sk = t >> 5, sx = (t & 31) * 2;
+    const double* __restrict__ gA = Bvv + a * apitch + (long)sk * xp + sx;
+    const double* __restrict__ gB = Bvv + b * apitch + (long)sk * xp + sx;
+    const long step = (long)kDirK * xp;
+    v2d r0, r1, r2, r3;
+    auto fetch = [&](long o) {
+        r0 = *reinterpret_cast<const v2d*>(gA + o + c0);
+        r1 = *reinterpret_cast<const v2d*>(gB + o + d0);
+        r2 = *reinterpret_cast<const v2d*>(gB + o + c0);
+        r3 = *reinterpret_cast<const v2d*>(gA + o + d0);
+    };
+    auto stash = [&](int buf) {
+        *reinterpret_cast<v2d*>(&sm[buf][0][sk][sx]) = r0;       // a, c: A operand of X
+        *reinterpret_cast<v2d*>(&sm[buf][1][sk][sx]) = r1;       // b, d: B operand of X
+        *reinterpret_cast<v2d*>(&sm[buf][2][sk][sx]) = r2;       // b, c: A operand of Y
+        *reinterpret_cast<v2d*>(&sm[buf][3][sk][sx]) = r3;       // a, d: B operand of Y
+    };
+    fetch(0);
+    stash(0);
+    __syncthreads();
+    v4d X[2][2], Y[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) X[i][j] = Y[i][j] = v4d{0.0, 0.0, 0.0, 0.0};
+    for (int st = 0; st < nstage; ++st) {
+        const int buf = st & 1;
+        const bool more = st + 1 < nstage;
+        if (more) fetch((long)(st + 1) * step);
+        if (work) {
+#pragma unroll
+            for (int kk = 0; kk < kDirK; kk += 4) {
+                const int k = kk + l4;
+                double xa[2], xb[2], ya[2], yb[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    xa[i] = sm[buf][0][k][wc + 16 * i + l15];
+                    xb[i] = sm[buf][1][k][wd + 16 * i + l15];
+                    ya[i] = sm[buf][2][k][wc + 16 * i + l15];
+                    yb[i] = sm[buf][3][k][wd + 16 * i + l15];
+                }
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        X[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[i], xb[j], X[i][j], 0, 0, 0);
+                        Y[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(ya[i], yb[j], Y[i][j], 0, 0, 0);
+                    }
+            }
+        }
+        if (more) stash(buf ^ 1);
+        __syncthreads();
+    }
+    if (!work) return;
+    double* __restrict__ vp = Vp + row * npp;
+    double* __restrict__ vm = Vm + row * npm;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int d = d0 + wd + 16 * j + l15;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int c = c0 + wc + 16 * i + l4 + 4 * e;
+                if (c < nv && d < nv && c >= d) {
+                    vp[(long)c * (c + 1) / 2 + d] = X[i][j][e] + Y[i][j][e];
+                    if (c > d) vm[(long)c * (c - 1) / 2 + d] = (a > b) ? X[i][j][e] - Y[i][j][e] : 0.0;   // zero rows for a == b
+                }
+            }
+        }
+}
+
 // T1 dressing of the BRA of the pair-packed V_abcd (ccsd.py:414-419 restricted to what the packed ladder reads):
 //   W[P(a,b)][cd] = V[P(a,b)][cd] - sum_k t[a,k] Pk[(b,k)][cd] + sgn sum_k t[b,k] Pk[(a,k)][cd],     a >= b,
 // Pk = the rows (x,k) (x slow) of V_kxcd packed over (c,d) like V itself; sgn = -1 for the symmetric half (V_alcd + V_aldc =
@@ -5097,6 +5199,25 @@ void ladder_pack_V_factors(const double* B, double* Vp, double* Vm, int naux, in
     if (nblk > 0x7fffffffL) throw std::runtime_error("ladder_pack_V_factors: grid too large");
     launch_kernel(ladder_pack_V_factors_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s, B, Vp, Vm, naux, n, no,
                  (long)rp0, ntp, npp, npm);
+}
+
+bool direct_rows_fused_ok() { return true; }
+
+void direct_rows_fused(const double* Bvv, double* Vp, double* Vm, int nv, int64_t qp, int64_t xp, int64_t rp0, int64_t rp1,
+                       stream_t s, int64_t ldvp, int64_t ldvm) {
+    if (rp1 <= rp0) return;
+    const long npair = (long)nv * (nv + 1) / 2;
+    // (the kernel loads whole 8 x 64 panels and writes the columns P(c,d) < v(v+1)/2 of the rows it is given: the padding
+    // of Bvv and the pitches are what keeps both in bounds)
+    if (nv < 1 || qp < kDirK || qp % kDirK || xp < nv || xp % kDirT || rp0 < 0 || rp1 > npair || ldvp < npair ||
+        ldvm < std::max<long>(npair - nv, 1) || xp > 0x7fffffffL || qp / kDirK > 0x7fffffffL)
+        throw std::runtime_error("direct_rows_fused: bad shape, padding or pair-row range");
+    const int nt = (nv + kDirT - 1) / kDirT;
+    const long ntp = (long)nt * (nt + 1) / 2;
+    const long nblk = (rp1 - rp0) * ntp;
+    if (nblk > 0x7fffffffL) throw std::runtime_error("direct_rows_fused: grid too large");
+    launch_kernel(direct_rows_fused_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)s, Bvv, Vp, Vm, nv, (int)xp,
+                  (long)(qp * xp), (int)(qp / kDirK), (long)rp0, ntp, (long)ldvp, (long)ldvm);
 }
 
 // nocc within the instantiated MFMA step counts, and the byte offsets inside a tile (16 a of packed rows of the widest half)

@@ -77,7 +77,7 @@ class DeviceArray:
 
 
 class Context:
-    def __init__(self, no, nv, device=0, workspace_bytes=0, lib=None, stream=None, allocator=None, shard=None):
+    def __init__(self, no, nv, device=0, workspace_bytes=0, lib=None, stream=None, allocator=None, shard=None, direct=None):
         self.lib = lib or _lib.default_library()
         self.no, self.nv, self.n = int(no), int(nv), int(no) + int(nv)
         self.device = int(device)
@@ -97,6 +97,17 @@ class Context:
                 self.handle = None
                 raise
             self.shard = (rank, world)
+        # direct = True | bytes: the factor-direct particle ladder (include/pymes_amd.h, pymes_set_integral_direct) — no V_abcd
+        # in any form; its pair-packed rows are rebuilt from the factors chunk by chunk (True: the default chunk budget)
+        self.direct = False
+        if direct is not None and direct is not False:
+            try:
+                self.lib.call("pymes_set_integral_direct", h, 0 if direct is True else int(direct))
+            except BaseException:
+                self.lib.call("pymes_ctx_destroy", h)
+                self.handle = None
+                raise
+            self.direct = True
         self._allocator = allocator      # optional callable(n_doubles) -> (ptr, keepalive), e.g. torch-backed
         self._pool = {}
         self._spare, self._spare_bytes = {}, 0      # released buffers by size, for reuse (see _recycle)
@@ -342,6 +353,24 @@ class Context:
         P = DeviceArray(self, vp.value, (rows, ldp.value), owned=False, keepalive=self).get()
         M = DeviceArray(self, vm.value, (rows, ldm.value), owned=False, keepalive=self).get()
         return P[:, :nv * (nv + 1) // 2].copy(), M[:, :nv * (nv - 1) // 2].copy(), r0.value, r1.value
+
+    def direct_info(self):
+        """Of a factor-direct context: naux, rows per chunk, bytes of B_vv, bytes of the chunk buffers, the row builder."""
+        info = (C.c_int64 * 5)()
+        self.lib.call("pymes_direct_info", self.handle, info)
+        return {"naux": info[0], "chunk_rows": info[1], "bvv_bytes": info[2], "chunk_buffer_bytes": info[3],
+                "builder": "fused" if info[4] else "gemm"}
+
+    def direct_rows(self, r0, r1):
+        """Host copies of the rows [r0, r1) (at most one chunk) of the pair-packed V_abcd as a factor-direct context builds
+        them: (Vp [rows, v(v+1)/2], Vm [rows, v(v-1)/2])."""
+        vp, vm = C.c_void_p(), C.c_void_p()
+        ldp, ldm = C.c_int64(), C.c_int64()
+        self.lib.call("pymes_direct_rows", self.handle, int(r0), int(r1), C.byref(vp), C.byref(vm), C.byref(ldp), C.byref(ldm))
+        rows, nv = int(r1) - int(r0), self.nv
+        P = DeviceArray(self, vp.value, (rows, ldp.value), owned=False, keepalive=self).get()
+        M = DeviceArray(self, vm.value, (rows, ldm.value), owned=False, keepalive=self).get()
+        return P[:, :nv * (nv + 1) // 2].copy(), M[:, :nv * (nv - 1) // 2].copy()
 
     def block_shape(self, name):
         return tuple(self.nv if ch in "abcd" else self.no for ch in name)

@@ -16,6 +16,7 @@ class DeviceIntegrals:
         self.dtype = np.dtype(np.float64)
         self.shape = (ctx.n,) * 4
         self.shard = ctx.shard
+        self.direct = getattr(ctx, "direct", False)
 
     @classmethod
     def from_V_pqrs(cls, no, t_V_pqrs, shard=None, **ctx_kwargs):
@@ -30,11 +31,14 @@ class DeviceIntegrals:
         return cls(ctx)
 
     @classmethod
-    def from_factors(cls, no, B, shard=None, **ctx_kwargs):
+    def from_factors(cls, no, B, shard=None, direct=None, **ctx_kwargs):
         """V[p,q,r,s] = sum_Q B[Q,p,r] B[Q,q,s], formed block by block with the fp64 MFMA GEMM.  shard = (rank, world): V_abcd
-        is never formed; that rank's rows of its pair-packed form are built straight from B."""
+        is never formed; that rank's rows of its pair-packed form are built straight from B.  direct = True | chunk bytes: the
+        factor-direct particle ladder (single rank) — V_abcd is not formed and no row of it is stored; the ladders of CCSD /
+        DCSD / CCD / DCD rebuild their rows from the virtual-virtual factors in every iteration
+        (include/pymes_amd.h, pymes_set_integral_direct)."""
         n = B.shape[1]
-        ctx = Context(no, n - no, shard=shard, **ctx_kwargs)
+        ctx = Context(no, n - no, shard=shard, direct=direct, **ctx_kwargs)
         ctx.set_V_from_factors(B)
         return cls(ctx)
 

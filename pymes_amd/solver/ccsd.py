@@ -496,6 +496,7 @@ class CCSD(ccd.CCD):
                 raise ValueError("rdm2=True: the two-particle density is that of the CCSD Lagrangian and its Lambda equations, "
                                  "not defined for DCSD")
             kwargs["density"] = True
+        direct = bool(getattr(t_V_pqrs, "direct", False))      # a factor-direct DeviceIntegrals (from_factors(..., direct=True))
         if kwargs.get("density"):          # refused by name before anything is truncated, uploaded or dressed
             if self.is_dcd:
                 raise ValueError("density=True: the Lambda equations are those of the CCSD similarity transform, not defined "
@@ -503,6 +504,9 @@ class CCSD(ccd.CCD):
             if self.shard_integrals:
                 raise ValueError("density=True with shard_integrals=True: the left sigma reads the whole V_abcd, which an "
                                  "integral-sharded context does not hold")
+            if direct:
+                raise ValueError("density=True with direct=True integrals: the left sigma reads the whole V_abcd, which a "
+                                 "factor-direct context does not hold")
         if kwargs.get("ee_roots"):         # likewise
             if self.is_dcd:
                 raise ValueError("ee_roots: the EOM-CCSD operator and its left vectors are those of the CCSD similarity "
@@ -510,6 +514,9 @@ class CCSD(ccd.CCD):
             if self.shard_integrals:
                 raise ValueError("ee_roots with shard_integrals=True: the left sigma reads the whole V_abcd, which an "
                                  "integral-sharded context does not hold")
+            if direct:
+                raise ValueError("ee_roots with direct=True integrals: the EOM sigma reads the whole V_abcd, which a "
+                                 "factor-direct context does not hold")
         if kwargs.get("dyson"):            # likewise
             if not (kwargs.get("ip_roots") or kwargs.get("ea_roots")):
                 raise ValueError("dyson=True needs ip_roots and / or ea_roots: the amplitudes are those of the IP / EA roots")
@@ -519,6 +526,9 @@ class CCSD(ccd.CCD):
             if self.shard_integrals:
                 raise ValueError("dyson=True with shard_integrals=True: the Lambda equations read the whole V_abcd, which an "
                                  "integral-sharded context does not hold")
+            if direct:
+                raise ValueError("dyson=True with direct=True integrals: the Lambda equations read the whole V_abcd, which a "
+                                 "factor-direct context does not hold")
         if isinstance(kwargs.get("triples"), str):          # likewise: triples="lambda" is Lambda-CCSD(T)
             if kwargs["triples"] != "lambda":
                 raise ValueError("triples=%r: expected True ((T)), \"lambda\" (Lambda-CCSD(T)) or False" % (kwargs["triples"],))
@@ -528,6 +538,12 @@ class CCSD(ccd.CCD):
             if self.shard_integrals:
                 raise ValueError("triples=\"lambda\" with shard_integrals=True: the Lambda equations read the whole V_abcd, "
                                  "which an integral-sharded context does not hold")
+            if direct:
+                raise ValueError("triples=\"lambda\" with direct=True integrals: the Lambda equations read the whole V_abcd, "
+                                 "which a factor-direct context does not hold")
+        if direct and kwargs.get("ea_roots"):
+            raise ValueError("ea_roots with direct=True integrals: the EA operator reads the whole V_abcd, which a "
+                             "factor-direct context does not hold")
         if frozen_core or fno_occ_threshold is not None or fno_nv is not None:
             return self._solve_fno(t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv,
                                    **kwargs)

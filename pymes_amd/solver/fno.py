@@ -145,12 +145,14 @@ def _factor_source(source, n):
     return B
 
 
-def truncate(no, t_fock_pq, source, *, n_frozen=0, occ_threshold=None, nv_keep=None, shard=None, device=0, lib=None):
+def truncate(no, t_fock_pq, source, *, n_frozen=0, occ_threshold=None, nv_keep=None, shard=None, direct=None, device=0,
+             lib=None):
     """Frozen core and frozen natural orbitals (definitions in the module docstring).
 
     ``source``: a host V_pqrs, a full-space replicated ``DeviceIntegrals`` (left as it is, apart from its orbital
     energies), or ``("factors", B)`` with V[p,q,r,s] = sum_Q B[Q,p,r] B[Q,q,s] (no full-space v^4 block is ever formed;
-    ``shard=(rank, world)`` then builds the new space's integrals with that integral shard).  ``device`` / ``lib``: where
+    ``shard=(rank, world)`` then builds the new space's integrals with that integral shard, ``direct=True | bytes`` as a
+    factor-direct context without any V_abcd, pymes_set_integral_direct).  ``device`` / ``lib``: where
     the contexts of a host source live.  With torch.distributed running one process per GPU, rank 0's choice of the
     space (C, eps') and its energies are used on every rank.  Returns an ``FNOResult``."""
     f = ccsd_t.check_canonical(no, t_fock_pq)
@@ -168,6 +170,9 @@ def truncate(no, t_fock_pq, source, *, n_frozen=0, occ_threshold=None, nv_keep=N
     if not factors and shard is not None:
         raise ValueError("shard= is supported with the ('factors', B) source only: a new space is not derived as a sharded "
                          "context from a replicated one")
+    if not factors and direct:
+        raise ValueError("direct= is supported with the ('factors', B) source only: a factor-direct context is built from "
+                         "factors, not derived from stored integrals")
     owned = []          # contexts made here and closed before returning
     result = None
     try:
@@ -185,6 +190,9 @@ def truncate(no, t_fock_pq, source, *, n_frozen=0, occ_threshold=None, nv_keep=N
                 if ints.shard is not None or ints.ctx.shard is not None:
                     raise ValueError("the source DeviceIntegrals are a sharded context (shard %s): frozen natural orbitals "
                                      "are derived from a replicated source" % (ints.ctx.shard,))
+                if getattr(ints, "direct", False):
+                    raise ValueError("the source DeviceIntegrals are a factor-direct context (direct=True): frozen natural "
+                                     "orbitals are derived from a stored source, or from ('factors', B)")
                 if (ints.no, ints.nv) != (no, nv):
                     raise ValueError("the integrals are for (no, nv) = (%d, %d), the Fock matrix for (%d, %d)"
                                      % (ints.no, ints.nv, no, nv))
@@ -226,7 +234,7 @@ def truncate(no, t_fock_pq, source, *, n_frozen=0, occ_threshold=None, nv_keep=N
             Ud.free()
             Bh = Bn.get()
             Bn.free()
-            new = DeviceIntegrals.from_factors(no - nf, Bh, shard=shard, device=ctx.device, lib=ctx.lib)
+            new = DeviceIntegrals.from_factors(no - nf, Bh, shard=shard, direct=direct, device=ctx.device, lib=ctx.lib)
         else:
             new = derive_context(ints, nf, Cm)
         result = FNOResult(fock=fock, ints=new, no=no - nf, nv=k, n_frozen=nf, occupations=occ, C=Cm, eps_v=eps_new,

@@ -34,9 +34,10 @@ class DeviceIntegrals:
     def from_factors(cls, no, B, shard=None, direct=None, **ctx_kwargs):
         """V[p,q,r,s] = sum_Q B[Q,p,r] B[Q,q,s], formed block by block with the fp64 MFMA GEMM.  shard = (rank, world): V_abcd
         is never formed; that rank's rows of its pair-packed form are built straight from B.  direct = True | chunk bytes: the
-        factor-direct particle ladder (single rank) — V_abcd is not formed and no row of it is stored; the ladders of CCSD /
-        DCSD / CCD / DCD rebuild their rows from the virtual-virtual factors in every iteration
-        (include/pymes_amd.h, pymes_set_integral_direct)."""
+        factor-direct particle ladder — V_abcd is not formed and no row of it is stored; the ladders of CCSD / DCSD / CCD /
+        DCD rebuild their rows from the virtual-virtual factors in every iteration (include/pymes_amd.h,
+        pymes_set_integral_direct).  One rank or several: in a multi-rank world every rank holds such a context (replicated)
+        and the pair-sharded loop rebuilds the rows of its own slab only; together with shard= it is refused."""
         n = B.shape[1]
         ctx = Context(no, n - no, shard=shard, direct=direct, **ctx_kwargs)
         ctx.set_V_from_factors(B)

@@ -5,12 +5,15 @@ and refuses by name every path that needs the full, dressed or stored block."""
 import contextlib
 import ctypes as C
 import io
+import os
 
 import numpy as np
 import pytest
 
+from oracle import cc_oracle as oc
 from oracle.cases import synthetic_case
 from pymes_amd import _lib
+from pymes_amd import dist as pdist
 from pymes_amd.device import Context
 from pymes_amd.integral.device import DeviceIntegrals
 from tests.test_shard_integrals import _energies, _pitch, pack_rows
@@ -19,10 +22,15 @@ SHAPES = ((5, 14), (4, 12), (3, 14), (3, 12))
 CAP = 31          # rows per chunk: not a triangular number (edges inside an a-row); 78 = 31 + 31 + 16, 105 = 3 x 31 + 12
 
 
+def _row_bytes(nv, builder="gemm"):
+    """Chunk budget per row: V^+ / V^- at the ladder pitches, plus one plane V[a,b,:,:] for the gemm builder."""
+    return 8 * (_pitch(nv * (nv + 1) // 2) + _pitch(nv * (nv - 1) // 2) + (nv * nv if builder == "gemm" else 0))
+
+
 def _chunk_bytes(nv, cap=CAP):
     """The budget that gives `cap` rows per chunk with the gemm builder: a row of V^+ / V^- at the ladder pitches plus one
     plane V[a,b,:,:] each."""
-    return cap * 8 * (_pitch(nv * (nv + 1) // 2) + _pitch(nv * (nv - 1) // 2) + nv * nv)
+    return cap * _row_bytes(nv, "gemm")
 
 
 def _bvv_bytes(nv, naux):
@@ -229,3 +237,90 @@ def test_solver_refusals_before_upload(sim):
         assert ints.ctx.integral_bytes() == before
     finally:
         ints.ctx.close()
+
+
+# (no, nv, seed): the shapes of test_sharded_residual_simulated_ranks (test_gpu_cc.py) and the degenerate pair shapes — no
+# antisymmetric occupied pair (no = 1), no antisymmetric virtual pair and one row in all (nv = 1), three rows (nv = 2)
+RANK_CASES = [(3, 5, 2), (6, 17, 3), (8, 24, 4), (1, 3, 21), (2, 1, 22), (3, 2, 23)]
+RANK_WORLDS = (1, 2, 3, 8)        # 8: empty slabs at the small shapes
+RANK_CAPS = (1, 7, None)          # rows per chunk (None: all rows); 7 divides no slab edge of these shapes
+
+
+def direct_sharded_residual_check(lib, cases, worlds, caps, tol):
+    """Simulated ranks on a factor-direct context: every rank's slab of the symmetry-reduced residual (T1 dressing on the
+    amplitude side, the only form such a context serves) computed one after the other into shared buffers, then the replicated
+    finish, against the oracle in numpy fp64 — for every chunk cap, so that chunks start at a rank's row0 and end inside its
+    slab.  On the same context the CCD form: ladder_sym (hole = 0, 1, 2) over each rank's pair rows against the stored
+    context's whole range and, for hole = 0, the plain einsum.  Returns the largest errors seen."""
+    builder = os.environ.get("PYMES_DIRECT_BUILDER") or \
+        ("fused" if lib.dll.pymes_backend().decode().startswith("hip") else "gemm")
+    worst = {"residual": 0.0, "ladder vs stored": 0.0, "ladder vs einsum": 0.0}
+    for no, nv, seed in cases:
+        f, V, B, eps = synthetic_case(no, nv, seed, scale=0.3)
+        rng = np.random.default_rng(seed)
+        t1 = rng.standard_normal((nv, no)) * 0.1
+        x = rng.standard_normal((nv, nv, no, no)) * 0.1
+        t2 = 0.5 * (x + x.transpose(1, 0, 3, 2))
+        Vb = oc.split_blocks(no, V)
+        fd_ref = oc.dressed_fock(no, f, t1, Vb)
+        Vd_ref = oc.dressed_V(t1, Vb)
+        r2_ref = {dcd: oc.ccsd_doubles_residual(no, fd_ref, t2, Vd_ref, is_dcsd=dcd) for dcd in (False, True)}
+        lad_ref = np.einsum("abcd,cdij->abij", Vb["abcd"], t2)
+        ov, npp = no * nv, nv * (nv + 1) // 2
+        stored = DeviceIntegrals.from_factors(no, B, lib=lib)
+        try:
+            c = stored.ctx
+            lad_stored = []
+            for hole in (0, 1, 2):
+                L = c.ladder_sym(c.array(t2), c.zeros((npp, no * no)), 0, npp, hole_ladder=hole)
+                lad_stored.append(c.ladder_sym_unpack(L, c.empty(t2.shape), beta=0.0).get())
+        finally:
+            stored.ctx.close()
+        err = float(np.abs(lad_stored[0] - lad_ref).max())
+        assert err < tol, ("stored ladder", no, nv, err)
+        for cap in caps:
+            rows = min(npp, cap or npp)
+            ints = DeviceIntegrals.from_factors(no, B, direct=rows * _row_bytes(nv, builder), lib=lib)
+            ctx = ints.ctx
+            try:
+                info = ctx.direct_info()
+                assert info["builder"] == builder and info["chunk_rows"] == rows, (no, nv, cap, info)
+                ctx.set_orbital_energies(eps[:no].copy(), eps[no:].copy())
+                dT1, dT2, dF = ctx.array(t1), ctx.array(t2), ctx.array(fd_ref)
+                for world in worlds:
+                    pad = lambda n: pdist.padded_rows(n, world)
+                    for dcd in (False, True):
+                        ctx.dress_V(dT1, ["klij", "iajb", "iabj"])      # V_abij and V_abcd are never dressed in this mode
+                        ETd, ETx, L = ctx.zeros((pad(ov), ov)), ctx.zeros((pad(ov), ov)), ctx.zeros((pad(npp), no * no))
+                        QK = ctx.zeros((pad(ov), no * no))
+                        for rank in range(world):
+                            ctx.residual_slab(dF, dT2, ETd, ETx, L, rank, world, is_dcd=dcd, dressed=True, t1=dT1, QK=QK)
+                        r2 = ctx.empty(t2.shape)
+                        ctx.residual_finish(dF, dT2, ETd, ETx, L, r2, is_dcd=dcd, dressed=True, t1=dT1, QK=QK)
+                        err = float(np.abs(r2.get() - r2_ref[dcd]).max())
+                        worst["residual"] = max(worst["residual"], err)
+                        assert err < tol, ("residual", builder, no, nv, cap, world, dcd, err)
+                    for hole in (0, 1, 2):
+                        L = ctx.zeros((npp, no * no))
+                        for rank in range(world):
+                            lo, hi = pdist.slab_rows(npp, rank, world)
+                            ctx.ladder_sym(dT2, L, lo, hi, hole_ladder=hole)
+                        got = ctx.ladder_sym_unpack(L, ctx.empty(t2.shape), beta=0.0).get()
+                        err = float(np.abs(got - lad_stored[hole]).max())
+                        worst["ladder vs stored"] = max(worst["ladder vs stored"], err)
+                        assert err < tol, ("ladder_sym against stored", builder, no, nv, cap, world, hole, err)
+                        if hole == 0:
+                            err = float(np.abs(got - lad_ref).max())
+                            worst["ladder vs einsum"] = max(worst["ladder vs einsum"], err)
+                            assert err < tol, ("ladder_sym against einsum", builder, no, nv, cap, world, err)
+            finally:
+                ctx.close()
+    print("direct simulated ranks,", builder, "builder: largest |error|", worst)
+    return worst
+
+
+@pytest.mark.parametrize("no,nv,seed", RANK_CASES)
+def test_direct_sharded_residual_simulated_ranks(sim, no, nv, seed):
+    """The host logic of the pair-sharded loop on a replicated factor-direct context (gemm builder): row slabs, chunk edges
+    that start at a rank's row0, empty slabs."""
+    direct_sharded_residual_check(sim, [(no, nv, seed)], RANK_WORLDS, RANK_CAPS, 1e-11)

@@ -261,3 +261,78 @@ def test_distributed_solver_host_logic(hostsim_lib, world, dress, monkeypatch):
         ref = oc.ccsd_solve(no, f, V, is_dcsd=dcsd, is_diis=diis, delta_e=1e-10)
         assert abs(e - ref["e"]) < 1e-10 and it == ref["iterations"], (no, nv, dcsd, diis, e, ref["e"], it)
         assert abs(t2sum - np.abs(ref["t2"]).sum()) < 1e-8 and asym < 1e-12
+
+
+# (kind, no, nv, seed): the shapes and seeds of _solver_worker, so that the oracle's solves are the expectation here too
+DIRECT_SOLVES = (("ccsd", 3, 7, 3), ("dcsd", 2, 5, 3), ("ccd", 3, 7, 4))
+
+
+def _direct_solver_worker(rank, world, port, libpath, out):
+    """The pair-sharded loop on replicated integrals from factors, stored and factor-direct (a chunk of 5 rows: 28 pair rows
+    at nv = 7, 15 at nv = 5; no slab edge of worlds 2, 3, 8 is a chunk edge): per solve the energy, the iteration count,
+    sum |t2| and every logged energy."""
+    import contextlib
+    import io
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    os.environ["LOCAL_RANK"] = "0"
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from oracle.cases import synthetic_case
+        from pymes_amd import _lib
+        from pymes_amd.integral.device import DeviceIntegrals
+        from pymes_amd.solver.ccd import CCD
+        from pymes_amd.solver.ccsd import CCSD
+        from tests.conftest import hostsim_library
+        from tests.test_direct_ladder import _row_bytes
+        from tests.test_shard_integrals import _energies
+        _lib._default = hostsim_library(libpath)
+        res = {}
+        for kind, no, nv, seed in DIRECT_SOLVES:
+            f, V, B, eps = synthetic_case(no, nv, seed=seed, scale=0.3)
+            for mode in ("stored", "direct"):
+                ints = DeviceIntegrals.from_factors(no, B, direct=5 * _row_bytes(nv, "gemm") if mode == "direct" else None)
+                try:
+                    assert bool(ints.direct) == (mode == "direct")
+                    if ints.direct:
+                        assert ints.ctx.direct_info()["chunk_rows"] == 5
+                    s = CCD(no, delta_e=1e-10) if kind == "ccd" else CCSD(no, delta_e=1e-10, is_dcsd=kind == "dcsd")
+                    buf = io.StringIO()
+                    with contextlib.redirect_stdout(buf):
+                        r = s.solve(f, ints)
+                    assert s.pair_sharded and s.hooked
+                    t2 = r["t2 amp" if kind == "ccd" else "t2"]
+                    res[(kind, mode)] = (float(r["ccd e" if kind == "ccd" else "ccsd e"]), int(s.iterations),
+                                         float(np.abs(t2).sum()), tuple(_energies(buf.getvalue())))
+                finally:
+                    ints.ctx.close()
+        out[rank] = res
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 3, 8])
+def test_distributed_solver_on_direct_integrals(hostsim_lib, world, monkeypatch):
+    """CCSD.solve / CCD.solve with a replicated factor-direct DeviceIntegrals in a multi-rank world: the pair-sharded loop
+    hands every rank's pair-row slab to the chunked row builder (8 ranks: empty slabs at nv = 5).  The simulator runs the
+    same products in the same order on both contexts, so direct equals stored bit for bit."""
+    from oracle import cc_oracle as oc
+    from oracle.cases import synthetic_case
+    for name in ("PYMES_DIRECT_BUILDER", "PYMES_DIRECT_CHUNK_BYTES", "PYMES_LADDER_DRESS", "PYMES_FORCE_SHARDED"):
+        monkeypatch.delenv(name, raising=False)
+    mgr = mp.Manager()
+    out = mgr.dict()
+    mp.spawn(_direct_solver_worker, args=(world, _free_port(), hostsim_lib.path, out), nprocs=world, join=True)
+    assert len(out) == world and all(out[r] == out[0] for r in range(world))          # ranks agree bit for bit
+    res = out[0]
+    for kind, no, nv, seed in DIRECT_SOLVES:
+        assert res[(kind, "direct")] == res[(kind, "stored")], (kind, res[(kind, "direct")], res[(kind, "stored")])
+        e, it, t2sum, hist = res[(kind, "direct")]
+        assert len(hist) > 3
+        f, V, B, eps = synthetic_case(no, nv, seed=seed, scale=0.3)
+        if kind == "ccd":
+            ref = oc.ccd_solve(no, f, V, delta_e=1e-10)
+        else:
+            ref = oc.ccsd_solve(no, f, V, is_dcsd=kind == "dcsd", delta_e=1e-10)
+        assert abs(e - ref["e"]) < 1e-10 and it == ref["iterations"], (kind, e, ref["e"], it, ref["iterations"])
+        assert abs(t2sum - np.abs(ref["t2"]).sum()) < 1e-8

@@ -48,7 +48,19 @@ ROW_CASES = [
     (5, 37, 23, 7, 0.1, ((1, 40), (303, 391), (650, 700))),           # below one 64-wide tile; naux no multiple of 4 or of 8
     (3, 70, 50, 9, 0.1, ((4, 130), (2100, 2250), (2400, 2480))),      # crosses the first tile edge, ragged second tile
     (2, 200, 40, 8, 0.05, ((10007, 10400),)),                         # four tiles; one chunk in the middle of the range
+    # loop edges of direct_rows_fused_kernel (no = 1): all rows in one chunk where there are at most 2200 of them
+    (1, 1, 1, 11, 0.1, ((0, 1),)),                                    # one row, no antisymmetric pair: only P holds anything
+    (1, 16, 5, 12, 0.1, ((0, 136),)),                                 # one stage (naux <= 8), one working wave
+    (1, 32, 8, 13, 0.1, ((0, 528),)),                                 # naux without Q padding, nv on the quadrant edge
+    (1, 33, 9, 14, 0.1, ((0, 561),)),                                 # two stages; a quadrant of one row and column
+    (1, 64, 16, 15, 0.1, ((0, 2080),)),                               # xp == nv: no pad column
+    (1, 65, 24, 16, 0.1, ((0, 2145),)),                               # a second tile of one column
+    # three tiles, the last of one column (c = 128): across the a = 63 / 64 tile edge, inside the a-row 128 (rows 8256 ..
+    # 8384), and up to the last row P(128,128) = 8384
+    (1, 129, 17, 17, 0.1, ((2070, 2120), (8260, 8300), (8320, 8385))),
 ]
+EDGE_ROW_CASES = ROW_CASES[3:]
+NO_DIAGONAL_ROW = {(8260, 8300)}        # the one range that lies inside an a-row short of its a == b row
 
 
 @pytest.mark.parametrize("builder", BUILDERS)
@@ -63,12 +75,38 @@ def test_rows_match_numpy_packing(gpu_lib, clean_env, builder, no, nv, naux, see
         assert info["builder"] == builder and info["chunk_rows"] == cap
         for r0, r1 in ranges:
             diag = [a * (a + 3) // 2 for a in range(nv) if r0 <= a * (a + 3) // 2 < r1]
-            assert diag, (r0, r1)
+            assert diag or (r0, r1) in NO_DIAGONAL_ROW, (r0, r1)
             P, M = ints.ctx.direct_rows(r0, r1)
             Pr, Mr = _rows_from_factors(B, no, r0, r1)
             print(builder, (no, nv, naux), (r0, r1), _rel(P, Pr), _rel(M, Mr))
             assert _rel(P, Pr) <= 1e-13 and _rel(M, Mr) <= 1e-13, (builder, r0, r1, _rel(P, Pr), _rel(M, Mr))
             assert not M[[d - r0 for d in diag]].any()
+    finally:
+        ints.ctx.close()
+
+
+@pytest.mark.parametrize("builder", BUILDERS)
+@pytest.mark.parametrize("no,nv,naux,seed,scale,ranges", EDGE_ROW_CASES)
+def test_single_rows_with_a_one_row_budget(gpu_lib, clean_env, builder, no, nv, naux, seed, scale, ranges):
+    """The same shapes on a context whose budget holds one row (a grid of the tile pairs of one row): the first row, the
+    last, an a == b row in between and its a > b neighbour."""
+    B = _factors(no, nv, naux, seed, scale)
+    npp, mid = nv * (nv + 1) // 2, (nv // 2) * (nv // 2 + 3) // 2
+    clean_env.setenv("PYMES_DIRECT_BUILDER", builder)
+    ints = DeviceIntegrals.from_factors(no, B, direct=8, device=0)
+    try:
+        info = ints.ctx.direct_info()
+        assert info["builder"] == builder and info["chunk_rows"] == 1
+        diag = {a * (a + 3) // 2 for a in range(nv)}
+        assert {0, npp - 1, mid} <= diag
+        for r in sorted({0, mid, min(mid + 1, npp - 1), npp - 1}):
+            P, M = ints.ctx.direct_rows(r, r + 1)
+            Pr, Mr = _rows_from_factors(B, no, r, r + 1)
+            print(builder, (no, nv, naux), "row", r, _rel(P, Pr), _rel(M, Mr))
+            assert _rel(P, Pr) <= 1e-13 and _rel(M, Mr) <= 1e-13, (builder, r, _rel(P, Pr), _rel(M, Mr))
+            assert Pr.any() and (r in diag or nv < 2 or Mr.any())
+            if r in diag:
+                assert not M.any()
     finally:
         ints.ctx.close()
 

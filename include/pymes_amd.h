@@ -912,6 +912,60 @@ int pymes_tdm1(pymes_ctx* ctx, const double* t1_dev, const double* t2_dev, const
                double* gammaL_host, double* gammaR_host, double* r0_host);
 int pymes_eom_correction(pymes_ctx* ctx, int n, const double* const* s_dev, const double* const* r_dev, const double* w_host,
                          const double* d_dev, double shift, double* const* q_dev, int64_t off2, int64_t len, double* norms_host);
+/* ---- EOM-CCSD linear response functions ---------------------------------------------------------------------------
+ * <<X;Y>>_z = sum_k [ <0|X|k><k|Y|0> / (z - w_k) - <0|Y|k><k|X|0> / (z + w_k) ] in its resolvent form, consistent with S_k(O) of
+ * the block above (plain inner product, exchange-symmetric doubles, t = T2).  O~: the T1-dressed one-body operator,
+ *   O~_ov[j,b] = O_ov,  O~_oo[j,i] = O_oo + O_ov t1,  O~_vv[a,b] = O_vv - t1 O_ov,  O~_vo[a,i] = O_vo + O_vv t1 - t1 O~_oo.
+ * Right property vector xi(O) = (R1(O), R2(O)): the CCSD residuals at (t1, t2) with all integrals zero and f = O, so that
+ * <l, xi(O)> = sum gammaL(l) O.  Written out:
+ *   xi1[a,i] = O~_vo[a,i] + sum_jb (2 t[a,b,i,j] - t[a,b,j,i]) O~_ov[j,b]
+ *   xi2 = S + S^T(1,0,3,2),  S[a,b,i,j] = sum_c O~_vv[a,c] t[c,b,i,j] - sum_k O~_oo[k,i] t[a,b,k,j]
+ * Left property vector eta(O): <eta(O), r> = sum_pq gammaR(r)[p,q] O[p,q] for every exchange-symmetric r, gammaR the right
+ * transition density above.  With Y = X(lambda1, lambda2) and g0 = <lambda, xi(O)>:
+ *   eta1[c,k] = 2 O~_ov[k,c] + 2 sum_ai lambda2[c,a,k,i] xi1[a,i] - sum_i lambda1[c,i] O~_oo[k,i] + sum_a O~_vv[a,c] lambda1[a,k]
+ *               - 2 sum_j Yoo[j,k] O~_ov[j,c] - 2 sum_b Yvv[c,b] O~_ov[k,b] - g0 lambda1[c,k]
+ *   eta2 = (E + E^T(1,0,3,2)) / 2 - g0 lambda2,  E[a,b,i,j] = -2 sum_k lambda2[a,b,k,j] O~_oo[i,k] + 2 sum_c O~_vv[c,a] lambda2[c,b,i,j]
+ *                                                            + 2 lambda1[a,i] O~_ov[j,b] - lambda1[a,j] O~_ov[i,b]
+ * x^O(z) = (z - A)^-1 xi(O) on the exchange-symmetric subspace (A: pymes_eom_sigma_apply);
+ *   <<X;Y>>_z = <eta(X), x^Y(z)> + <eta(Y), x^X(-z)>,   polarizability = -<<X;Y>>_z,   z = w + i gamma.
+ * Where a written-out formula and its definition disagree, the definition rules.
+ * pymes_response_vectors: xi1[z], eta1[z] [v,o] and xi2[z], eta2[z] [v,v,o,o] (arrays of k device pointers) and g0_host [k] for
+ * k <= 64 operators ops_host [k,n,n] (occupied orbitals first, undressed, need not be symmetric).  The intermediates contracted
+ * over o v are engine products with the operators stacked; the singles and g0 are one launch; xi2 and eta2 one launch each of ONE
+ * kernel, out_z = P(M_z T - N_z T + outer products) + s_z T for all operators, T read once per eight operators, nothing staged in
+ * LDS (no cap on nocc).  It reads no integral block.  Identical calls give identical bits (no atomics, fixed summation order);
+ * xi2 and eta2 are exchange-symmetric to the bit when t2 and lambda2 are.  Refused by name: null arguments, outputs that alias
+ * inputs or each other, t2 or lambda2 without the exchange symmetry, a context that is recording a launch graph.
+ * The linear solver's sweep over n systems (z_s - A) x_s = xi_s, flat vectors [x1 (v o) | zero pad | x2 (v v o o)] of len doubles
+ * with the doubles at off2, real and imaginary parts as two device vectors (all imaginary pointers null and Im z = 0: a real
+ * system).  p: the preconditioned direction, ap = A p as the sigma build left it, q = z p - ap formed on the fly; hp, hq: the
+ * nh <= PYMES_RESPONSE_HIST stored directions with (z - A) hp_j = hq_j and orthonormal hq_j; <u, v> = sum conj(u) v.
+ * pymes_response_dots: dots_host[s][2 j], [2 j + 1] = <hq_j, q> for j < nh, then <q, q> (two doubles, the second 0) and <q, r>;
+ * PYMES_RESPONSE_DOTS doubles per system.
+ * pymes_response_update, the linear-system counterpart of pymes_eom_correction — all systems in one launch and one pass:
+ *   ph = (p - sum_j g_j hp_j) inv,  qh = (q - sum_j g_j hq_j) inv  (written over p and ap: the next stored pair),
+ *   x += alpha ph,  r -= alpha qh,  pn = r / (z - d),  norms_host[s] = |r|^2,
+ * d_dev the diagonals of pymes_eom_diagonals in the flat layout; where |z - d| < floor the real part of z - d is replaced by
+ * floor with its sign kept.  p null: no step (pn and |r|^2 of the r given: the start of a solve).  Both entries cost one
+ * synchronisation whatever n (results through the pinned read-back ring up to 128 doubles), sum in a fixed order, and refuse null
+ * arguments, a flat layout that does not match (no, nv), systems that are half real and half complex, and a context that is
+ * recording a launch graph. */
+#define PYMES_RESPONSE_HIST 32
+#define PYMES_RESPONSE_DOTS (2 * (PYMES_RESPONSE_HIST + 2))
+typedef struct pymes_response_system {
+    double* x[2]; double* r[2]; double* p[2]; double* ap[2]; double* pn[2];      /* [0] real, [1] imaginary part */
+    const double* hp[PYMES_RESPONSE_HIST][2];
+    const double* hq[PYMES_RESPONSE_HIST][2];
+    double g[PYMES_RESPONSE_HIST][2];
+    double alpha[2], z[2], inv;
+    int nh;
+} pymes_response_system;
+int pymes_response_vectors(pymes_ctx* ctx, const double* t1_dev, const double* t2_dev, const double* lam1_dev, const double* lam2_dev,
+                           int k, const double* ops_host, double* const* xi1_dev, double* const* xi2_dev, double* const* eta1_dev,
+                           double* const* eta2_dev, double* g0_host);
+int pymes_response_dots(pymes_ctx* ctx, int n, const pymes_response_system* sys_host, int64_t off2, int64_t len, double* dots_host);
+int pymes_response_update(pymes_ctx* ctx, int n, const pymes_response_system* sys_host, const double* d_dev, double floor,
+                          int64_t off2, int64_t len, double* norms_host);
 /* (mr + i mi)[e] = 1 / ((zr + i zi) - (hr + i hi) d[e] + shift), e < n: the FEAST preconditioner 1 / (z - diag + 0.01)
  * (feast_eom_ccsd.py:342; hs = 1j dt for the real-time form :276-278) from the device-resident diagonal */
 int pymes_cshift_inv(pymes_ctx* ctx, const double* d_dev, double zr, double zi, double hr, double hi, double shift,

@@ -23,6 +23,17 @@ class ShardBuffers(C.Structure):
 
 c_pp = C.POINTER(C.c_void_p)
 
+RESPONSE_HIST = 32                       # PYMES_RESPONSE_HIST
+RESPONSE_DOTS = 2 * (RESPONSE_HIST + 2)  # PYMES_RESPONSE_DOTS
+
+
+class ResponseSystem(C.Structure):
+    """pymes_response_system of include/pymes_amd.h ([0] real, [1] imaginary part; a null imaginary part: a real system)."""
+    _fields_ = ([(k, C.c_void_p * 2) for k in ("x", "r", "p", "ap", "pn")]
+                + [(k, (C.c_void_p * 2) * RESPONSE_HIST) for k in ("hp", "hq")]
+                + [("g", (C.c_double * 2) * RESPONSE_HIST), ("alpha", C.c_double * 2), ("z", C.c_double * 2), ("inv", C.c_double),
+                   ("nh", C.c_int)])
+
 # name -> (restype, argtypes); exactly the declarations of include/pymes_amd.h
 SIGNATURES = {
     "pymes_last_error": (C.c_char_p, []),
@@ -190,6 +201,9 @@ SIGNATURES = {
     "pymes_tdm1": (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 7),
     "pymes_eom_correction": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                        C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "pymes_response_vectors": (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 6),
+    "pymes_response_dots": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "pymes_response_update": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_void_p]),
     "pymes_diis_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_pp, c_pp, c_i64_p, c_pp, c_pp]),
     "pymes_diis_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "pymes_diis_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_pp, c_pp, c_i64_p, C.c_int, C.c_int, C.c_int]),

@@ -1195,6 +1195,45 @@ int pymes_eom_correction(pymes_ctx* ctx, int n, const double* const* s, const do
     });
 }
 
+// ---- EOM-CCSD linear response (eom.cpp, response_vectors / response_dots / response_update) ----------------------------
+static_assert(sizeof(pymes_response_system) == sizeof(dev::ResponseSystem) && PYMES_RESPONSE_HIST == dev::kResponseHist &&
+                  PYMES_RESPONSE_DOTS == dev::kResponseDots && offsetof(pymes_response_system, nh) == offsetof(dev::ResponseSystem, nh) &&
+                  offsetof(pymes_response_system, g) == offsetof(dev::ResponseSystem, g),
+              "pymes_response_system is dev::ResponseSystem");
+int pymes_response_vectors(pymes_ctx* ctx, const double* t1, const double* t2, const double* lam1, const double* lam2, int k,
+                           const double* ops_host, double* const* xi1, double* const* xi2, double* const* eta1, double* const* eta2,
+                           double* g0_host) {
+    return guarded([&] {
+        need(t1, "t1"); need(t2, "t2"); need(lam1, "lam1"); need(lam2, "lam2"); need(ops_host, "ops"); need(xi1, "xi1");
+        need(xi2, "xi2"); need(eta1, "eta1"); need(eta2, "eta2"); need(g0_host, "g0");
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("response_vectors while a launch graph is being recorded");
+        pymes::response_vectors(e, t1, t2, lam1, lam2, k, ops_host, xi1, xi2, eta1, eta2, g0_host);
+    });
+}
+int pymes_response_dots(pymes_ctx* ctx, int n, const pymes_response_system* sys_host, int64_t off2, int64_t len, double* dots_host) {
+    return guarded([&] {
+        need(sys_host, "sys"); need(dots_host, "dots");
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("response_dots while a launch graph is being recorded");
+        const int64_t n1 = static_cast<int64_t>(e.nv) * e.no;
+        if (off2 < n1 || len != off2 + n1 * n1) throw pymes::Error("response_dots: the flat layout does not match (no, nv)");
+        pymes::response_dots(e, n, reinterpret_cast<const dev::ResponseSystem*>(sys_host), n1, off2, len, dots_host);
+    });
+}
+int pymes_response_update(pymes_ctx* ctx, int n, const pymes_response_system* sys_host, const double* d, double floor, int64_t off2,
+                          int64_t len, double* norms_host) {
+    return guarded([&] {
+        need(sys_host, "sys"); need(d, "d"); need(norms_host, "norms");
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("response_update while a launch graph is being recorded");
+        const int64_t n1 = static_cast<int64_t>(e.nv) * e.no;
+        if (off2 < n1 || len != off2 + n1 * n1) throw pymes::Error("response_update: the flat layout does not match (no, nv)");
+        if (!(floor >= 0.0)) throw pymes::Error("response_update: the floor must not be negative");
+        pymes::response_update(e, n, reinterpret_cast<const dev::ResponseSystem*>(sys_host), d, floor, n1, off2, len, norms_host);
+    });
+}
+
 // ---- IP- / EA-EOM-CCSD sigma (eom.cpp, IpEaSigma) -------------------------------------------------------------------------------
 int pymes_ipea_sigma_prepare(pymes_ctx* ctx, const double* f_host, const double* t2, int dressed, int kind, pymes_ipea** out) {
     return guarded([&] {

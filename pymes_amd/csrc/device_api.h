@@ -422,6 +422,51 @@ struct Tdm1Parts {
 };
 void tdm1_assemble(const Tdm1Parts& q, int k, int no, int nv, stream_t s);
 
+// ---- EOM-CCSD linear response (eom.cpp, response_vectors / response_dots / response_update; formulas:
+// include/pymes_amd.h, pymes_response_vectors).  The product library only (weak definitions in the engine throw, by name).
+// One-body operators times doubles, k <= kResponseOps operators per launch, T [v,v,o,o] exchange-symmetric (the caller's test):
+//   out_z[a,b,i,j] = P( sum_c M_z[a,c] T[c,b,i,j] - sum_k N_z[k,i] T[a,b,k,j] + u[a,i] w_z[j,b] - u[a,j] w_z[i,b] / 2 ) + scal[z] T[a,b,i,j],
+//   P(S) = S + S^T(1,0,3,2);  M [k,v,v], N [k,o,o], w [k,o,v] stacked, u [v,o] (u, w null: no outer products), scal [k] on the
+// device (null: zero).  One block per (a, b); the transposed half of P is read as T[a,c,i,j] and T[a,b,i,k], so every read runs
+// along ij and nothing is staged in LDS (no cap on nocc).  A thread holds the accumulators of eight operators while it reads T:
+// T is read once per eight operators.  No atomics, fixed summation order; out is exchange-symmetric to the bit when T is.
+constexpr int kResponseOps = 64;
+void response_doubles(const double* T, const double* M, const double* N, const double* u, const double* w, const double* scal,
+                      int k, int no, int nv, double* const* out, stream_t s);
+// The singles parts and g0 of k operators from the dressed blocks Ooo [k,o,o], Oov [k,o,v], Ovo [k,v,o], Ovv [k,v,v], lam1 [v,o],
+// Y = X(lam1, lam2) of pymes_tdm1 (Yoo, Yvv, Yov), the stacked XI1 [k,v,o] (the finished xi1) and L2X[z,c,k] = sum_ai lam2[c,a,k,i]
+// XI1[z,a,i]:  g0[z] = <lambda, xi(O_z)> (fixed tree), mg0[z] = -g0[z], xi1[z] <- XI1[z], eta1[z] as in the header.  One block per operator.
+struct ResponseSingles {
+    const double* Ooo = nullptr; const double* Oov = nullptr; const double* Ovo = nullptr; const double* Ovv = nullptr;
+    const double* lam1 = nullptr; const double* Yoo = nullptr; const double* Yvv = nullptr; const double* Yov = nullptr;
+    const double* XI1 = nullptr; const double* L2X = nullptr;
+    double* g0 = nullptr; double* mg0 = nullptr;
+};
+void response_singles(const ResponseSingles& q, int k, int no, int nv, double* const* xi1, double* const* eta1, stream_t s);
+// One linear system (z - A) x = xi of a solver sweep over flat vectors [x1 | pad | x2] (re, im pairs; every im pointer null: a real
+// system, zi = 0).  p: the preconditioned direction, ap = A p (the sigma build's output); q = z p - ap is formed on the fly.
+// hp / hq: the nh <= kResponseHist stored directions and their images (z - A) hp = hq, orthonormal hq.
+constexpr int kResponseHist = 32;
+struct ResponseSystem {
+    double* x[2]; double* r[2]; double* p[2]; double* ap[2]; double* pn[2];
+    const double* hp[kResponseHist][2];
+    const double* hq[kResponseHist][2];
+    double g[kResponseHist][2];          // g_j = <hq_j, q>
+    double alpha[2], z[2], inv;
+    int nh;
+};
+// dots: out[s][2 j .. 2 j + 1] = <hq_j, q> (j < nh), then <q, q> (one double pair, im 0) and <q, r>, <u, v> = sum conj(u) v;
+// kResponseDots doubles per system, fixed order (block partials in ws, response_ws_doubles(n, len) doubles, then one block per system).
+constexpr int kResponseDots = 2 * (kResponseHist + 2);
+int64_t response_ws_doubles(int n, int64_t len);
+void response_dots(const ResponseSystem* sys_dev, int n, int64_t n1, int64_t off2, int64_t len, double* ws, double* out_dev,
+                   stream_t s);
+// update (all systems, one launch, one pass): ph = (p - sum_j g_j hp_j) inv, qh = (q - sum_j g_j hq_j) inv written over p and ap;
+// x += alpha ph; r -= alpha qh; pn = r / (z - d) with |z - d| floored at `floor` (the sign of Re(z - d) kept); zero in the pad;
+// out_dev[s] = |r|^2.  p == null: no step (pn and |r|^2 of the r given).  d: the diagonals of eom_diagonals in the flat layout.
+void response_update(const ResponseSystem* sys_dev, int n, const double* d, double floor, int64_t n1, int64_t off2, int64_t len,
+                     double* ws, double* out_dev, stream_t s);
+
 // ---- the CCSD two-particle density (eom.cpp, lambda_rdm2 / lambda_rdm2_expectation).  The product library only
 // (the host simulator has no definition: weak ones in the engine throw, by name).
 // Gamma_ijab in the [v,v,o,o] layout from G [v,v,o,o] (G[a,b,i,j]: the sum of the products that multiply V_ijab[i,j,a,b]),

@@ -853,6 +853,22 @@ __attribute__((weak)) void rdm1_assemble(const double*, const double*, const dou
 __attribute__((weak)) void tdm1_assemble(const Tdm1Parts&, int, int, int, stream_t) {
     throw std::runtime_error("tdm1_assemble: not available in this backend");
 }
+// ... and without the linear-response kernels
+__attribute__((weak)) void response_doubles(const double*, const double*, const double*, const double*, const double*, const double*,
+                                            int, int, int, double* const*, stream_t) {
+    throw std::runtime_error("response_doubles: not available in this backend");
+}
+__attribute__((weak)) void response_singles(const ResponseSingles&, int, int, int, double* const*, double* const*, stream_t) {
+    throw std::runtime_error("response_singles: not available in this backend");
+}
+__attribute__((weak)) int64_t response_ws_doubles(int, int64_t) { return 1; }
+__attribute__((weak)) void response_dots(const ResponseSystem*, int, int64_t, int64_t, int64_t, double*, double*, stream_t) {
+    throw std::runtime_error("response_dots: not available in this backend");
+}
+__attribute__((weak)) void response_update(const ResponseSystem*, int, const double*, double, int64_t, int64_t, int64_t, double*,
+                                           double*, stream_t) {
+    throw std::runtime_error("response_update: not available in this backend");
+}
 // ... and without the two-particle density kernels (the products of lambda_rdm2 run; the assembly of ijab and the contractions
 // refuse by name)
 __attribute__((weak)) bool rdm2_assemble_ok(int) { return true; }            // (the stubs below refuse by name)

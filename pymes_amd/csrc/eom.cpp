@@ -1229,6 +1229,171 @@ void transition_densities(Engine& e, const double* t1, const double* t2, const d
     dev::stream_sync(e.stream);
 }
 
+// ---- the property vectors of the linear response function (eom.h): the T1 dressing of the k operators on the host
+// (k n^2 numbers), the o v-contracted intermediates as engine products with the operators stacked, one launch for the singles and
+// g0, one launch each for xi2 (T = t2) and eta2 (T = lambda2) -----------------------------------------------------------------------
+void response_vectors(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2, int k,
+                      const double* ops_host, double* const* xi1, double* const* xi2, double* const* eta1, double* const* eta2,
+                      double* g0_host) {
+    if (!t1 || !t2 || !lam1 || !lam2 || !ops_host || !xi1 || !xi2 || !eta1 || !eta2 || !g0_host)
+        throw Error("response_vectors: null argument");
+    if (k < 1 || k > dev::kResponseOps) throw Error("response_vectors: 1 <= k <= 64 operators per call");
+    std::vector<const double*> outs;
+    for (int z = 0; z < k; ++z) {
+        if (!xi1[z] || !xi2[z] || !eta1[z] || !eta2[z]) throw Error("response_vectors: null vector");
+        for (const double* out : {xi1[z], xi2[z], eta1[z], eta2[z]}) {
+            for (const double* in : {t1, t2, lam1, lam2})
+                if (in == out) throw Error("response_vectors: output aliases input");
+            for (const double* other : outs)
+                if (other == out) throw Error("response_vectors: two outputs are the same array");
+            outs.push_back(out);
+        }
+    }
+    const int64_t o = e.no, v = e.nv, n = o + v, K = k, n1 = v * o;
+    {
+        const int64_t d[4] = {v, v, o, o};
+        for (const double* x : {lam2, t2}) {
+            double out[2] = {0.0, 0.0};
+            dev::exchange_asymmetry(x, x, d, out, e.stream);
+            if (!(std::isfinite(out[1]) && out[0] <= 1e-13 * std::max(1.0, out[1])))
+                throw Error(x == lam2 ? "response_vectors: lambda2 does not have the exchange symmetry l2_abij = l2_baji"
+                                      : "response_vectors: t2 does not have the exchange symmetry t2_abij = t2_baji");
+        }
+    }
+    // the dressed blocks: O~_ov = O_ov, O~_oo = O_oo + O_ov t1, O~_vv = O_vv - t1 O_ov, O~_vo = O_vo + O_vv t1 - t1 O~_oo
+    std::vector<double> th(static_cast<size_t>(n1));
+    dev::memcpy_d2h(th.data(), t1, sizeof(double) * n1, e.stream);
+    dev::stream_sync(e.stream);
+    const size_t soo = static_cast<size_t>(K * o * o), svv = static_cast<size_t>(K * v * v), svo = static_cast<size_t>(K * n1);
+    std::vector<double> hoo(soo), hooT(soo), hvv(svv), hvvT(svv), hov(svo), hvo(svo);
+    for (int64_t z = 0; z < K; ++z) {
+        const double* O = ops_host + z * n * n;
+        double *oo = hoo.data() + z * o * o, *ooT = hooT.data() + z * o * o, *vv = hvv.data() + z * v * v,
+               *vvT = hvvT.data() + z * v * v, *ov = hov.data() + z * n1, *vo = hvo.data() + z * n1;
+        for (int64_t j = 0; j < o; ++j) {
+            for (int64_t b = 0; b < v; ++b) ov[j * v + b] = O[j * n + o + b];
+            for (int64_t i = 0; i < o; ++i) {
+                double s = O[j * n + i];
+                for (int64_t b = 0; b < v; ++b) s += ov[j * v + b] * th[b * o + i];
+                oo[j * o + i] = s;
+                ooT[i * o + j] = s;
+            }
+        }
+        for (int64_t a = 0; a < v; ++a) {
+            for (int64_t b = 0; b < v; ++b) {
+                double s = O[(o + a) * n + o + b];
+                for (int64_t j = 0; j < o; ++j) s -= th[a * o + j] * ov[j * v + b];
+                vv[a * v + b] = s;
+                vvT[b * v + a] = s;
+            }
+            for (int64_t i = 0; i < o; ++i) {
+                double s = O[(o + a) * n + i];
+                for (int64_t b = 0; b < v; ++b) s += O[(o + a) * n + o + b] * th[b * o + i];
+                for (int64_t j = 0; j < o; ++j) s -= th[a * o + j] * oo[j * o + i];
+                vo[a * o + i] = s;
+            }
+        }
+    }
+    struct Buf {
+        Engine& e;
+        double* p;
+        Buf(Engine& e_, int64_t m) : e(e_), p(e_.scratch_get(m)) {}
+        ~Buf() { e.scratch_put(p); }
+    } Ooo(e, K * o * o), OooT(e, K * o * o), Ovv(e, K * v * v), OvvT(e, K * v * v), Oov(e, K * n1), Ovo(e, K * n1), XI1(e, K * n1),
+        L2X(e, K * n1), Yvv(e, v * v), Yoo(e, o * o), Yov(e, n1), G(e, 2 * K);
+    auto up = [&](double* d, const std::vector<double>& h) { dev::memcpy_h2d(d, h.data(), sizeof(double) * h.size(), e.stream); };
+    up(Ooo.p, hoo); up(OooT.p, hooT); up(Ovv.p, hvv); up(OvvT.p, hvvT); up(Oov.p, hov); up(Ovo.p, hvo); up(XI1.p, hvo);
+    dev::stream_sync(e.stream);                 // (the host blocks die with this scope's vectors only after the copies have read them)
+    const TView T4 = mv(t2, {v, v, o, o}), LAM1 = mv(lam1, {v, o}), LAM2 = mv(lam2, {v, v, o, o});
+    const TView W = mv(Oov.p, {K, o, v}), X1 = mv(XI1.p, {K, v, o});
+    // xi1_z = O~_vo + (2 t - t^(ij)) . O~_ov
+    e.contract(2.0, T4, "abij", W, "zjb", 1.0, X1, "zai");
+    e.contract(-1.0, T4, "abji", W, "zjb", 1.0, X1, "zai");
+    // Y = X(lambda1, lambda2) of transition_densities
+    e.contract(1.0, LAM2, "abij", T4, "cbij", 0.0, mv(Yvv.p, {v, v}), "ac");
+    e.contract(1.0, LAM2, "abij", T4, "abkj", 0.0, mv(Yoo.p, {o, o}), "ki");
+    e.contract(2.0, LAM1, "ai", T4, "abij", 0.0, mv(Yov.p, {o, v}), "jb");
+    e.contract(-1.0, LAM1, "ai", T4, "abji", 1.0, mv(Yov.p, {o, v}), "jb");
+    // lambda2 . xi1_z
+    e.contract(1.0, LAM2, "caki", X1, "zai", 0.0, mv(L2X.p, {K, v, o}), "zck");
+    dev::ResponseSingles q;
+    q.Ooo = Ooo.p; q.Oov = Oov.p; q.Ovo = Ovo.p; q.Ovv = Ovv.p; q.lam1 = lam1; q.Yoo = Yoo.p; q.Yvv = Yvv.p; q.Yov = Yov.p;
+    q.XI1 = XI1.p; q.L2X = L2X.p; q.g0 = G.p; q.mg0 = G.p + K;
+    dev::response_singles(q, k, e.no, e.nv, xi1, eta1, e.stream);
+    dev::response_doubles(t2, Ovv.p, Ooo.p, nullptr, nullptr, nullptr, k, e.no, e.nv, xi2, e.stream);
+    dev::response_doubles(lam2, OvvT.p, OooT.p, lam1, Oov.p, G.p + K, k, e.no, e.nv, eta2, e.stream);
+    const int slot = dev::readback_start(G.p, k, e.stream);
+    dev::readback_wait(slot, g0_host, k);       // (enqueued behind the launches: the scratch buffers are free to go back)
+}
+
+// ---- the dots and the fused update of a response sweep (eom.h): the systems' descriptions go to the device in one copy -----------
+namespace {
+struct ResponseLaunch {
+    Engine& e;
+    double *sys, *ws, *out;
+    ResponseLaunch(Engine& e_, int n, const dev::ResponseSystem* host, int64_t len, int64_t nout)
+        : e(e_),
+          sys(e_.scratch_get((static_cast<int64_t>(sizeof(dev::ResponseSystem)) * n + 7) / 8)),
+          ws(e_.scratch_get(std::max<int64_t>(dev::response_ws_doubles(n, len), 1))),
+          out(e_.scratch_get(nout)) {
+        dev::memcpy_h2d(sys, host, sizeof(dev::ResponseSystem) * n, e.stream);
+    }
+    ~ResponseLaunch() {
+        e.scratch_put(out);
+        e.scratch_put(ws);
+        e.scratch_put(sys);
+    }
+    const dev::ResponseSystem* systems() const { return reinterpret_cast<const dev::ResponseSystem*>(sys); }
+};
+// the results of a sweep: through the pinned read-back ring where they fit a slot (128 doubles), else one copy; ONE synchronisation
+void response_read(Engine& e, const double* src, double* host, int64_t count) {
+    if (count <= 128) {
+        const int slot = dev::readback_start(src, static_cast<int>(count), e.stream);
+        dev::readback_wait(slot, host, static_cast<int>(count));
+        return;
+    }
+    dev::memcpy_d2h(host, src, sizeof(double) * count, e.stream);
+    dev::stream_sync(e.stream);
+}
+void response_check(const char* who, int n, const dev::ResponseSystem* sys, bool update) {
+    if (!sys) throw Error(std::string(who) + ": null argument");
+    if (n < 1 || n > 4096) throw Error(std::string(who) + ": 1 <= n <= 4096 systems per call");
+    for (int s = 0; s < n; ++s) {
+        const dev::ResponseSystem& S = sys[s];
+        const bool cplx = S.r[1] != nullptr, step = S.p[0] != nullptr;
+        if (S.nh < 0 || S.nh > dev::kResponseHist) throw Error(std::string(who) + ": 0 <= nh <= " + std::to_string(dev::kResponseHist) + " stored directions");
+        if (!S.r[0] || (update && (!S.x[0] || !S.pn[0])) || (!update && !step) || (step && !S.ap[0]))
+            throw Error(std::string(who) + ": null vector");
+        if (cplx ? ((update && (!S.x[1] || !S.pn[1])) || (step && (!S.p[1] || !S.ap[1])))
+                 : (S.x[1] || S.p[1] || S.ap[1] || S.pn[1] || S.z[1] != 0.0 || S.alpha[1] != 0.0))
+            throw Error(std::string(who) + ": a system is real (every imaginary part null, Im z = 0) or complex (none null)");
+        for (int j = 0; j < (step ? S.nh : 0); ++j) {
+            if (!S.hp[j][0] || !S.hq[j][0] || cplx != (S.hp[j][1] != nullptr) || cplx != (S.hq[j][1] != nullptr))
+                throw Error(std::string(who) + ": null stored direction");
+            if (!cplx && S.g[j][1] != 0.0) throw Error(std::string(who) + ": a real system with a complex coefficient");
+        }
+    }
+}
+}  // namespace
+
+void response_dots(Engine& e, int n, const dev::ResponseSystem* sys, int64_t n1, int64_t off2, int64_t len, double* dots_host) {
+    if (!dots_host) throw Error("response_dots: null argument");
+    response_check("response_dots", n, sys, false);
+    ResponseLaunch w(e, n, sys, len, static_cast<int64_t>(n) * dev::kResponseDots);
+    dev::memset_zero(w.out, sizeof(double) * n * dev::kResponseDots, e.stream);        // (a row is written up to 2 (nh + 2) only)
+    dev::response_dots(w.systems(), n, n1, off2, len, w.ws, w.out, e.stream);
+    response_read(e, w.out, dots_host, static_cast<int64_t>(n) * dev::kResponseDots);
+}
+
+void response_update(Engine& e, int n, const dev::ResponseSystem* sys, const double* d, double floor, int64_t n1, int64_t off2,
+                     int64_t len, double* norms_host) {
+    if (!d || !norms_host) throw Error("response_update: null argument");
+    response_check("response_update", n, sys, true);
+    ResponseLaunch w(e, n, sys, len, n);
+    dev::response_update(w.systems(), n, d, floor, n1, off2, len, w.ws, w.out, e.stream);
+    response_read(e, w.out, norms_host, n);
+}
+
 // ---- the Davidson correction of n roots over flat vectors (eom.h), sixteen roots per launch ----------------------------------------
 void davidson_correction(Engine& e, int n, const double* const* s, const double* const* r, const double* w_host, const double* d,
                          double shift, double* const* q, int64_t n1, int64_t off2, int64_t len, double* norms_host) {

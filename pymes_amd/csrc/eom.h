@@ -110,6 +110,23 @@ void transition_densities(Engine& e, const double* t1, const double* t2, const d
                           const double* const* l1, const double* const* l2, const double* const* r1, const double* const* r2,
                           double* gl_host, double* gr_host, double* r0_host);
 
+// The property vectors of k <= 64 one-body operators for the EOM-CCSD linear response function (definitions and
+// written-out formulas in include/pymes_amd.h, pymes_response_vectors): xi(O_z) = (R1(O_z), R2(O_z)) and the left vector
+// eta(O_z) into the device arrays xi1[z], eta1[z] [v,o] and xi2[z], eta2[z] [v,v,o,o], g0_host[z] = <lambda, xi(O_z)>.
+// ops_host [k,n,n] (occupied orbitals first, undressed: the T1 dressing is done here).  The contracted intermediates are engine
+// products with the k operators stacked; the singles and g0 are one launch, the doubles one launch each for xi2 and eta2.  Reads
+// no integral block; refuses (by name) t2 or lam2 without the exchange symmetry and outputs that alias inputs or each other.
+void response_vectors(Engine& e, const double* t1, const double* t2, const double* lam1, const double* lam2, int k,
+                      const double* ops_host, double* const* xi1, double* const* xi2, double* const* eta1, double* const* eta2,
+                      double* g0_host);
+// One sweep's arithmetic for n linear systems (z_s - A) x_s = xi_s over flat vectors (device_api.h, ResponseSystem; the
+// pointers of `sys` are device vectors of `len` doubles, the rest host values).  response_dots: the dots of the orthogonalisation
+// into dots_host [n, kResponseDots]; response_update: the fused step into norms_host [n] = |r_s|^2.  One launch pair and ONE
+// synchronisation each, whatever n.
+void response_dots(Engine& e, int n, const dev::ResponseSystem* sys, int64_t n1, int64_t off2, int64_t len, double* dots_host);
+void response_update(Engine& e, int n, const dev::ResponseSystem* sys, const double* d, double floor, int64_t n1, int64_t off2,
+                     int64_t len, double* norms_host);
+
 // For n roots over flat vectors of `len` doubles ([0,n1) singles, [n1,off2) zero pad, [off2,len) doubles; d the diagonal in the
 // same layout): q_n = (s_n - w_n r_n) / (w_n - d + shift) written (zero in the pad), norms[2 n] = |s_n - w_n r_n|^2,
 // norms[2 n + 1] = |r_n|^2 (one launch and one synchronisation per sixteen roots, fixed summation order).  The kernel of the

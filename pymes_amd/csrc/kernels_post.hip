@@ -1,5 +1,5 @@
 // Kernels of what follows a converged CCSD: the (T) energy, the frozen-natural-orbital density, IP- / EA-EOM-CCSD with the
-// Dyson assembly, the Lambda equations with the one-particle and transition densities (device_api.h).  Included at the end of
+// Dyson assembly, the Lambda equations with the one-particle and transition densities, the linear response (device_api.h).  Included at the end of
 // kernels.hip (one code object for the library), not compiled on its own.
 #include <hip/hip_runtime.h>
 
@@ -1181,6 +1181,331 @@ void rdm2_contract_packed(const double* X, const double* L, int no, int nv, doub
 void rdm2_contract_finish(const double* ws, int64_t nsums, double* out_dev, stream_t s) {
     if (!ws || !out_dev || nsums < 1) throw std::runtime_error("rdm2_contract_finish: bad argument");
     launch_kernel(lambda_norm_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, ws, (long)nsums, out_dev);
+}
+
+}  // namespace dev
+
+// ==== EOM-CCSD linear response: the property vectors and the solver's dots / update (device_api.h) =======================
+namespace {
+
+constexpr int kRespChunk = 8;            // operators whose accumulators a thread holds while it reads T once
+struct RespOut {                         // the k <= 64 outputs of one call, by value
+    double* p[dev::kResponseOps];
+};
+struct RespDoublesK {
+    const double* T; const double* M; const double* N; const double* u; const double* w; const double* scal;
+    int no, nv, k;
+};
+
+// Block (a v + b, chunk): thread t owns the elements e = (i, j) = t, t + 256, ... of the o x o tile of (a, b), for the operators
+// z0 .. z0 + 7.  With T exchange-symmetric, S[b,a,j,i] = sum_c M[b,c] T[a,c,i,j] - sum_k N[k,j] T[a,b,i,k]: the four sums are kept
+// apart and added at the end, so that the element (b,a,j,i) adds the same four numbers (A1 <-> A2, B1 <-> B2) and the same
+// outer products (R1 <-> R2): out is exchange-symmetric to the bit when T is.  Explicit fma only (no contraction of the rest).
+__global__ void __launch_bounds__(256) response_doubles_kernel(const RespDoublesK q, const RespOut out) {
+#pragma clang fp contract(off)
+    const int no = q.no, nv = q.nv;
+    const long oo = (long)no * no, vv = (long)nv * nv, vo = (long)nv * no;
+    const int a = (int)(blockIdx.x / (unsigned)nv), b = (int)(blockIdx.x % (unsigned)nv);
+    const int z0 = (int)blockIdx.y * kRespChunk, nz = min(kRespChunk, q.k - z0);
+    const double* __restrict__ T = q.T;
+    const double* __restrict__ M = q.M + (long)z0 * vv;
+    const double* __restrict__ N = q.N + (long)z0 * oo;
+    const double* __restrict__ Tab = T + ((long)a * nv + b) * oo;
+    for (long e = threadIdx.x; e < oo; e += 256) {
+        const int i = (int)(e / no), j = (int)(e % no);
+        double A1[kRespChunk], A2[kRespChunk], B1[kRespChunk], B2[kRespChunk];
+#pragma unroll
+        for (int z = 0; z < kRespChunk; ++z) A1[z] = A2[z] = B1[z] = B2[z] = 0.0;
+        for (int c = 0; c < nv; ++c) {
+            const double x1 = T[((long)c * nv + b) * oo + e];       // T[c,b,i,j]
+            const double x2 = T[((long)a * nv + c) * oo + e];       // T[a,c,i,j] = T[c,a,j,i]
+#pragma unroll
+            for (int z = 0; z < kRespChunk; ++z)
+                if (z < nz) {
+                    A1[z] = fma(M[z * vv + (long)a * nv + c], x1, A1[z]);
+                    A2[z] = fma(M[z * vv + (long)b * nv + c], x2, A2[z]);
+                }
+        }
+        for (int k = 0; k < no; ++k) {
+            const double y1 = Tab[(long)k * no + j];                // T[a,b,k,j]
+            const double y2 = Tab[(long)i * no + k];                // T[a,b,i,k] = T[b,a,k,i]
+#pragma unroll
+            for (int z = 0; z < kRespChunk; ++z)
+                if (z < nz) {
+                    B1[z] = fma(N[z * oo + (long)k * no + i], y1, B1[z]);
+                    B2[z] = fma(N[z * oo + (long)k * no + j], y2, B2[z]);
+                }
+        }
+        const double tab = Tab[e];
+#pragma unroll
+        for (int z = 0; z < kRespChunk; ++z)
+            if (z < nz) {
+                double r = (A1[z] + A2[z]) - (B1[z] + B2[z]);
+                if (q.u) {
+                    const double* __restrict__ u = q.u;
+                    const double* __restrict__ w = q.w + (long)(z0 + z) * vo;
+                    const double R1 = u[(long)a * no + i] * w[(long)j * nv + b] - 0.5 * (u[(long)a * no + j] * w[(long)i * nv + b]);
+                    const double R2 = u[(long)b * no + j] * w[(long)i * nv + a] - 0.5 * (u[(long)b * no + i] * w[(long)j * nv + a]);
+                    r += R1 + R2;
+                }
+                if (q.scal) r += q.scal[z0 + z] * tab;
+                out.p[z0 + z][((long)a * nv + b) * oo + e] = r;
+            }
+    }
+}
+
+struct RespSinglesK {
+    dev::ResponseSingles q;
+    int no, nv;
+};
+// One block per operator z.  g0: thread t adds its strided terms of the four blocks in order, then the fixed tree.
+__global__ void __launch_bounds__(256) response_singles_kernel(const RespSinglesK k, const RespOut xi1, const RespOut eta1) {
+    __shared__ double sr[256];
+    const int no = k.no, nv = k.nv, z = blockIdx.x, t = threadIdx.x;
+    const long oo = (long)no * no, vv = (long)nv * nv, vo = (long)nv * no;
+    const double* __restrict__ Ooo = k.q.Ooo + z * oo;
+    const double* __restrict__ Oov = k.q.Oov + z * vo;
+    const double* __restrict__ Ovo = k.q.Ovo + z * vo;
+    const double* __restrict__ Ovv = k.q.Ovv + z * vv;
+    const double* __restrict__ lam1 = k.q.lam1;
+    const double* __restrict__ Yoo = k.q.Yoo;
+    const double* __restrict__ Yvv = k.q.Yvv;
+    const double* __restrict__ Yov = k.q.Yov;
+    const double* __restrict__ X1 = k.q.XI1 + z * vo;
+    const double* __restrict__ L2X = k.q.L2X + z * vo;
+    double s = 0.0;
+    for (long e = t; e < vo; e += 256) s += lam1[e] * Ovo[e];
+    for (long e = t; e < oo; e += 256) s -= 2.0 * Yoo[e] * Ooo[e];
+    for (long e = t; e < vv; e += 256) s += 2.0 * Yvv[e] * Ovv[e];
+    for (long e = t; e < vo; e += 256) s += Yov[e] * Oov[e];
+    sr[t] = s;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) sr[t] += sr[t + h];
+        __syncthreads();
+    }
+    const double g0 = sr[0];
+    if (t == 0) {
+        k.q.g0[z] = g0;
+        k.q.mg0[z] = -g0;
+    }
+    double* __restrict__ x1 = xi1.p[z];
+    double* __restrict__ e1 = eta1.p[z];
+    for (long e = t; e < vo; e += 256) {
+        const int c = (int)(e / no), m = (int)(e % no);
+        double r = 2.0 * Oov[(long)m * nv + c] + 2.0 * L2X[e] - g0 * lam1[e];
+        for (int i = 0; i < no; ++i) r -= lam1[(long)c * no + i] * Ooo[(long)m * no + i];
+        for (int a = 0; a < nv; ++a) r += Ovv[(long)a * nv + c] * lam1[(long)a * no + m];
+        for (int j = 0; j < no; ++j) r -= 2.0 * Yoo[(long)j * no + m] * Oov[(long)j * nv + c];
+        for (int b = 0; b < nv; ++b) r -= 2.0 * Yvv[(long)c * nv + b] * Oov[(long)m * nv + b];
+        e1[e] = r;
+        x1[e] = X1[e];
+    }
+}
+
+// ---- the solver's two passes.  Block (bx, s) owns the elements [bx * kRespElems, (bx + 1) * kRespElems) of system s ---------------
+constexpr long kRespElems = 256 * 8;
+struct Cx {
+    double re, im;
+};
+__device__ __forceinline__ Cx resp_cmul(const Cx a, const Cx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+__device__ __forceinline__ double resp_ld(const double* p, long e) { return p ? p[e] : 0.0; }
+// q = z p - ap at element e
+__device__ __forceinline__ Cx resp_q(const dev::ResponseSystem& S, long e) {
+    const Cx p{S.p[0][e], resp_ld(S.p[1], e)}, z{S.z[0], S.z[1]};
+    const Cx zp = resp_cmul(z, p);
+    return {zp.re - S.ap[0][e], zp.im - resp_ld(S.ap[1], e)};
+}
+// The dots: a thread keeps q of its kRespPer elements in registers and adds one accumulator pair at a time; each pair is summed
+// over the block in a fixed order (block_sum: the wave's shuffle tree, then the four waves in order) — nothing but four doubles of LDS,
+// whatever the number of stored directions.
+constexpr int kRespPer = (int)(kRespElems / 256);
+__global__ void __launch_bounds__(256) response_dots_kernel(const dev::ResponseSystem* __restrict__ sys, long n1, long off2, long len,
+                                                            long nblk, double* __restrict__ ws) {
+    __shared__ double sh[8];
+    const int s = blockIdx.y, t = threadIdx.x;
+    const dev::ResponseSystem& S = sys[s];
+    const int nh = S.nh;
+    const long e0 = (long)blockIdx.x * kRespElems;
+    double* __restrict__ dst = ws + ((long)s * nblk + blockIdx.x) * dev::kResponseDots;
+    Cx q[kRespPer];
+    bool ok[kRespPer];
+    double qq = 0.0, cr = 0.0, ci = 0.0;
+#pragma unroll
+    for (int m = 0; m < kRespPer; ++m) {
+        const long e = e0 + t + 256L * m;
+        ok[m] = e < len && !(e >= n1 && e < off2);
+        q[m] = Cx{0.0, 0.0};
+        if (ok[m]) {
+            q[m] = resp_q(S, e);
+            const double rr = S.r[0][e], ri = resp_ld(S.r[1], e);
+            qq += q[m].re * q[m].re + q[m].im * q[m].im;
+            cr += q[m].re * rr + q[m].im * ri;
+            ci += q[m].re * ri - q[m].im * rr;
+        }
+    }
+    for (int j = 0; j < nh; ++j) {
+        double ar = 0.0, ai = 0.0;
+#pragma unroll
+        for (int m = 0; m < kRespPer; ++m)
+            if (ok[m]) {
+                const long e = e0 + t + 256L * m;
+                const double hr = S.hq[j][0][e], hi = resp_ld(S.hq[j][1], e);
+                ar += hr * q[m].re + hi * q[m].im;
+                ai += hr * q[m].im - hi * q[m].re;
+            }
+        ar = block_sum(ar, sh);
+        ai = block_sum(ai, sh);
+        if (t == 0) {
+            dst[2 * j] = ar;
+            dst[2 * j + 1] = ai;
+        }
+    }
+    qq = block_sum(qq, sh);
+    cr = block_sum(cr, sh);
+    ci = block_sum(ci, sh);
+    if (t == 0) {
+        dst[2 * nh] = qq;
+        dst[2 * nh + 1] = 0.0;
+        dst[2 * nh + 2] = cr;
+        dst[2 * nh + 3] = ci;
+    }
+}
+
+__global__ void __launch_bounds__(256) response_update_kernel(const dev::ResponseSystem* __restrict__ sys, const double* __restrict__ d,
+                                                              double floor, long n1, long off2, long len, long nblk,
+                                                              double* __restrict__ ws) {
+    __shared__ double sh[8];
+    const int s = blockIdx.y, t = threadIdx.x;
+    const dev::ResponseSystem& S = sys[s];
+    const int nh = S.nh;
+    const bool cplx = S.r[1] != nullptr, step = S.p[0] != nullptr;
+    const Cx alpha{S.alpha[0], S.alpha[1]};
+    const double inv = S.inv;
+    double nrm = 0.0;
+    const long e0 = (long)blockIdx.x * kRespElems, e1 = min(len, e0 + kRespElems);
+    for (long e = e0 + t; e < e1; e += 256) {
+        if (e >= n1 && e < off2) {
+            S.pn[0][e] = 0.0;
+            if (cplx) S.pn[1][e] = 0.0;
+            continue;
+        }
+        Cx r{S.r[0][e], resp_ld(S.r[1], e)};
+        if (step) {
+            Cx p{S.p[0][e], resp_ld(S.p[1], e)}, q = resp_q(S, e);
+            for (int j = 0; j < nh; ++j) {
+                const Cx g{S.g[j][0], S.g[j][1]};
+                const Cx gp = resp_cmul(g, Cx{S.hp[j][0][e], resp_ld(S.hp[j][1], e)}), gq = resp_cmul(g, Cx{S.hq[j][0][e], resp_ld(S.hq[j][1], e)});
+                p.re -= gp.re; p.im -= gp.im;
+                q.re -= gq.re; q.im -= gq.im;
+            }
+            p.re *= inv; p.im *= inv;
+            q.re *= inv; q.im *= inv;
+            const Cx ap = resp_cmul(alpha, p), aq = resp_cmul(alpha, q);
+            r.re -= aq.re; r.im -= aq.im;
+            S.x[0][e] += ap.re;
+            S.r[0][e] = r.re;
+            S.p[0][e] = p.re;
+            S.ap[0][e] = q.re;
+            if (cplx) {
+                S.x[1][e] += ap.im;
+                S.r[1][e] = r.im;
+                S.p[1][e] = p.im;
+                S.ap[1][e] = q.im;
+            }
+        }
+        double x = S.z[0] - d[e];
+        const double y = S.z[1];
+        if (x * x + y * y < floor * floor) x = copysign(floor, x);
+        const double den = x * x + y * y;
+        S.pn[0][e] = (r.re * x + r.im * y) / den;
+        if (cplx) S.pn[1][e] = (r.im * x - r.re * y) / den;
+        nrm += r.re * r.re + r.im * r.im;
+    }
+    nrm = block_sum(nrm, sh);
+    if (t == 0) ws[(long)s * nblk + blockIdx.x] = nrm;
+}
+
+// stage 2 of both: one block per system; thread t adds the block partials t, t + 256, ... of one accumulator in order, then
+// block_sum.  The dots (sys given) have 2 (nh + 2) accumulators per system, the rest of its row stays as it is; the update has one.
+__global__ void __launch_bounds__(256) response_final_kernel(const double* __restrict__ ws, long nblk,
+                                                             const dev::ResponseSystem* __restrict__ sys, int stride,
+                                                             double* __restrict__ out) {
+    __shared__ double sh[8];
+    const int s = blockIdx.x, t = threadIdx.x;
+    const int nacc = sys ? 2 * (sys[s].nh + 2) : 1;
+    for (int m = 0; m < nacc; ++m) {
+        double v = 0.0;
+        for (long b = t; b < nblk; b += 256) v += ws[((long)s * nblk + b) * stride + m];
+        v = block_sum(v, sh);
+        if (t == 0) out[(long)s * stride + m] = v;
+    }
+}
+
+long resp_blocks(int64_t len) { return (long)((len + kRespElems - 1) / kRespElems); }
+
+}  // namespace
+
+namespace dev {
+
+void response_doubles(const double* T, const double* M, const double* N, const double* u, const double* w, const double* scal,
+                      int k, int no, int nv, double* const* out, stream_t s) {
+    if (no < 1 || nv < 1 || nv > 46340) throw std::runtime_error("response_doubles: bad shape");
+    if (k < 1 || k > kResponseOps) throw std::runtime_error("response_doubles: 1 <= k <= 64 operators per call");
+    if (!T || !M || !N || !out || (u == nullptr) != (w == nullptr)) throw std::runtime_error("response_doubles: null operand");
+    RespOut o{};
+    for (int z = 0; z < k; ++z) {
+        if (!out[z]) throw std::runtime_error("response_doubles: null output");
+        o.p[z] = out[z];
+    }
+    const RespDoublesK q{T, M, N, u, w, scal, no, nv, k};
+    launch_kernel(response_doubles_kernel, dim3((unsigned)(nv * nv), (unsigned)((k + kRespChunk - 1) / kRespChunk)), dim3(256), 0,
+                  (hipStream_t)s, q, o);
+}
+
+void response_singles(const ResponseSingles& q, int k, int no, int nv, double* const* xi1, double* const* eta1, stream_t s) {
+    if (no < 1 || nv < 1) throw std::runtime_error("response_singles: bad shape");
+    if (k < 1 || k > kResponseOps) throw std::runtime_error("response_singles: 1 <= k <= 64 operators per call");
+    if (!q.Ooo || !q.Oov || !q.Ovo || !q.Ovv || !q.lam1 || !q.Yoo || !q.Yvv || !q.Yov || !q.XI1 || !q.L2X || !q.g0 || !q.mg0 ||
+        !xi1 || !eta1)
+        throw std::runtime_error("response_singles: null operand");
+    RespOut x{}, e{};
+    for (int z = 0; z < k; ++z) {
+        if (!xi1[z] || !eta1[z]) throw std::runtime_error("response_singles: null output");
+        x.p[z] = xi1[z];
+        e.p[z] = eta1[z];
+    }
+    const RespSinglesK kk{q, no, nv};
+    launch_kernel(response_singles_kernel, dim3((unsigned)k), dim3(256), 0, (hipStream_t)s, kk, x, e);
+}
+
+int64_t response_ws_doubles(int n, int64_t len) { return (int64_t)n * resp_blocks(len) * kResponseDots; }
+
+void response_dots(const ResponseSystem* sys_dev, int n, int64_t n1, int64_t off2, int64_t len, double* ws, double* out_dev,
+                   stream_t s) {
+    if (n < 1 || n > 65535) throw std::runtime_error("response_dots: 1 <= n <= 65535 systems per call");
+    if (!sys_dev || !ws || !out_dev || len < 1 || n1 < 0 || off2 < n1 || off2 > len) throw std::runtime_error("response_dots: bad argument");
+    const long nblk = resp_blocks(len);
+    if (nblk > 0x7fffffffL) throw std::runtime_error("response_dots: grid too large");
+    hipStream_t st = (hipStream_t)s;
+    launch_kernel(response_dots_kernel, dim3((unsigned)nblk, (unsigned)n), dim3(256), 0, st, sys_dev, (long)n1, (long)off2, (long)len,
+                  nblk, ws);
+    launch_kernel(response_final_kernel, dim3((unsigned)n), dim3(256), 0, st, (const double*)ws, nblk, sys_dev, (int)kResponseDots,
+                  out_dev);
+}
+
+void response_update(const ResponseSystem* sys_dev, int n, const double* d, double floor, int64_t n1, int64_t off2, int64_t len,
+                     double* ws, double* out_dev, stream_t s) {
+    if (n < 1 || n > 65535) throw std::runtime_error("response_update: 1 <= n <= 65535 systems per call");
+    if (!sys_dev || !d || !ws || !out_dev || len < 1 || n1 < 0 || off2 < n1 || off2 > len || !(floor >= 0.0))
+        throw std::runtime_error("response_update: bad argument");
+    const long nblk = resp_blocks(len);
+    if (nblk > 0x7fffffffL) throw std::runtime_error("response_update: grid too large");
+    hipStream_t st = (hipStream_t)s;
+    launch_kernel(response_update_kernel, dim3((unsigned)nblk, (unsigned)n), dim3(256), 0, st, sys_dev, d, floor, (long)n1, (long)off2,
+                  (long)len, nblk, ws);
+    launch_kernel(response_final_kernel, dim3((unsigned)n), dim3(256), 0, st, (const double*)ws, nblk,
+                  (const ResponseSystem*)nullptr, 1, out_dev);
 }
 
 }  // namespace dev

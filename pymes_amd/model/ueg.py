@@ -71,6 +71,19 @@ class UEG:
         self.init_basis_indices_map()
         return self.basis_fns
 
+    def density_operator(self, q):
+        """rho_q in the spatial plane-wave basis, for an integer momentum transfer q (in units of 2 pi / L): O[p,r] = 1 where
+        k_p - k_r = q, so that rho_-q is its transpose.  The one-body operator of the density response chi(q, w) =
+        <<rho_q; rho_-q>>_w (pymes_amd/solver/response.py)."""
+        if self.basis_fns is None:
+            raise RuntimeError("density_operator: call init_single_basis first")
+        q = np.asarray(q)
+        if q.shape != (3,) or not np.all(np.equal(np.mod(q, 1), 0)):
+            raise ValueError("density_operator: q must be three integers (units of 2 pi / L), not %r" % (q,))
+        k = np.array([self.basis_fns[2 * i].k for i in range(len(self.basis_fns) // 2)], dtype=np.int64)
+        diff = k[:, None, :] - k[None, :, :]
+        return np.all(diff == q.astype(np.int64)[None, None, :], axis=2).astype(np.float64)
+
     # ---- correlator (ueg.py:772-800); like the reference it zeroes the small entries of an array argument
     def trunc(self, kSquare):
         if self.k_cutoff is None:

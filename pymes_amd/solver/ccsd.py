@@ -541,6 +541,17 @@ class CCSD(ccd.CCD):
             if direct:
                 raise ValueError("triples=\"lambda\" with direct=True integrals: the Lambda equations read the whole V_abcd, "
                                  "which a factor-direct context does not hold")
+        if kwargs.get("response") is not None:          # likewise; the operators are checked against the basis of f as given
+            if self.is_dcd:
+                raise ValueError("response: the EOM-CCSD operator and the Lambda equations are those of the CCSD similarity "
+                                 "transform, not defined for DCSD")
+            if self.shard_integrals:
+                raise ValueError("response with shard_integrals=True: the sigma builds read the whole V_abcd, which an "
+                                 "integral-sharded context does not hold")
+            if direct:
+                raise ValueError("response with direct=True integrals: the sigma builds read the whole V_abcd, which a "
+                                 "factor-direct context does not hold")
+            kwargs["response"] = self._response_options(kwargs["response"], t_fock_pq.shape[0])
         if direct and kwargs.get("ea_roots"):
             raise ValueError("ea_roots with direct=True integrals: the EA operator reads the whole V_abcd, which a "
                              "factor-direct context does not hold")
@@ -582,9 +593,17 @@ class CCSD(ccd.CCD):
         # frozen_core / fno_* those of the correlated space; with density=True Lambda is solved once (dyson_r_epsilon=x: the
         # relative residual norm at which the Davidson runs stop, default 1e-8)
         dyson = bool(kwargs.get("dyson", False))
-        if density or ee_roots or dyson or lambda_t:       # (the left assembly's cap on nocc: before a context exists)
+        # response=dict(operators=[m,n,n], omegas=[...], gamma=0.0) (opt-in): the linear response function <<X;Y>>_z of the
+        # converged state at z = w + i gamma for every pair of the one-body operators (pymes_amd/solver/response.py): "response",
+        # "polarizability" [nf,m,m] and "response converged"; with frozen_core / fno_* the operators are transformed to the
+        # correlated space like f; Lambda is solved once and shared (response_r_epsilon=x: the relative residual norm at which
+        # the linear systems stop, default 1e-8)
+        response = kwargs.get("response")
+        if density or ee_roots or dyson or lambda_t or response is not None:       # (the left assembly's cap on nocc: before a context exists)
             from pymes_amd.solver import lambda_ccsd
-            lambda_ccsd.check_occupied(self.no, "EOM_CCSD_Transitions" if ee_roots and not density else "Lambda_CCSD")
+            lambda_ccsd.check_occupied(self.no, "EOM_CCSD_Transitions" if ee_roots and not density else
+                                       "EOM_CCSD_Response" if response is not None and not (density or dyson or lambda_t) else
+                                       "Lambda_CCSD")
         ints, own = self._integrals(t_fock_pq, t_V_pqrs)
         ctx = ints.ctx
         st = None
@@ -601,6 +620,9 @@ class CCSD(ccd.CCD):
                 for cls, n_roots in ((eom_dyson.IP_EOM_CCSD_Dyson, ip_roots), (eom_dyson.EA_EOM_CCSD_Dyson, ea_roots)):
                     if n_roots:
                         cls(self.no, n_roots=n_roots, device=self.device).check_context(ctx, False)
+            if response is not None:
+                from pymes_amd.solver import response as response_module
+                response_module.check_context(ctx, self.no)
             print_logging_info(algo_name)
             print_logging_info("Using dcsd: ", self.is_dcd, level=1)
             print_logging_info("Solving doubles amplitude equation", level=1)
@@ -662,6 +684,10 @@ class CCSD(ccd.CCD):
                                    level=1)
             ee = self._ee_transitions(t_fock_pq, ints, st, ee_roots, kwargs.get("ee_r_epsilon"), lam) if ee_roots else None
             dy = self._dyson(t_fock_pq, ints, st, ip_roots, ea_roots, kwargs.get("dyson_r_epsilon"), lam) if dyson else None
+            rs = None
+            if response is not None:
+                shared = lam if lam is not None else (self.ee_solver.result if ee_roots else self.dyson_lambda if dyson else None)
+                rs = self._response(t_fock_pq, ints, st, response, kwargs.get("response_r_epsilon"), shared)
             if kwargs.get("device_amplitudes"):
                 # device-resident hand-over to the callers of the solution (EOM-CCSD / FEAST: get_T1_dressed_V on the same
                 # DeviceIntegrals, EOM_CCSD.solve on the result): "t1" / "t2" are DeviceArrays of the integrals' context —
@@ -698,6 +724,8 @@ class CCSD(ccd.CCD):
                 res.update(ee)
             if dy is not None:
                 res.update(dy)
+            if rs is not None:
+                res.update({k: v for k, v in rs.items() if k not in res})      # (lambda1 / lambda2 only when not already there)
             return res
         finally:
             collector.__exit__()
@@ -797,7 +825,39 @@ class CCSD(ccd.CCD):
             setattr(self, tag + "_dyson_solver", solver)         # (vectors, residuals, residues(), spectral_function() of the last solve)
             res.update({tag + " dyson left": out["dyson left"], tag + " dyson right": out["dyson right"],
                         tag + " pole strengths": out["pole strengths"]})
+        self.dyson_lambda = None if lam is None else {"lambda1": lam[0], "lambda2": lam[1]}      # (shared with response=)
         return res
+
+    @staticmethod
+    def _response_options(options, n):
+        """The ``response=`` keyword as a dictionary with "operators" [m,n,n] float64, "omegas" and "gamma", refused by name
+        otherwise (before anything is uploaded)."""
+        from pymes_amd.solver.response import check_operators
+        if not isinstance(options, dict) or "operators" not in options or "omegas" not in options:
+            raise ValueError("response: expected dict(operators=[m,n,n], omegas=[...], gamma=0.0)")
+        unknown = set(options) - {"operators", "omegas", "gamma"}
+        if unknown:
+            raise ValueError("response: unknown option(s) %s" % sorted(unknown))
+        return {"operators": check_operators(options["operators"], n, "response"),
+                "omegas": np.atleast_1d(np.asarray(options["omegas"], dtype=np.float64)), "gamma": float(options.get("gamma", 0.0))}
+
+    def _response(self, t_fock_pq, ints, st, options, r_epsilon=None, lam=None):
+        """The linear response function of the converged amplitudes on the integrals' context (device hand-over as
+        ``_lambda_density``; ``lam``: a dictionary with "lambda1", "lambda2" of an earlier step, so that Lambda is solved once)."""
+        from pymes_amd.solver.response import EOM_CCSD_Response
+        f = t_fock_pq.get() if isinstance(t_fock_pq, DeviceArray) else np.asarray(t_fock_pq, dtype=np.float64)
+        t1, t2 = st["t1"], st["t2"]
+        fd = self.get_T1_dressed_fock(f, t1, ints)
+        solver = EOM_CCSD_Response(self.no, device=self.device)
+        if r_epsilon is not None:
+            solver.r_epsilon = float(r_epsilon)
+        dressed = self.get_T1_dressed_V(t1, ints, solver.BLOCKS)
+        out = solver.solve(fd, dressed, t2, t1, options["operators"], options["omegas"], gamma=options["gamma"],
+                           lam=None if lam is None else (lam["lambda1"], lam["lambda2"]),
+                           eps=(st["eps_i"], st["eps_a"]), level_shift=st["level_shift"])
+        self.response_solver = solver                    # (residuals, iterations, isotropic(), spectral_density() of the last solve)
+        return {"response": out["response"], "polarizability": out["polarizability"], "response converged": out["converged"],
+                "lambda1": out["lambda1"], "lambda2": out["lambda2"]}
 
     def _solve_fno(self, t_fock_pq, t_V_pqrs, level_shift, amps, sp, frozen_core, fno_occ_threshold, fno_nv, **kwargs):
         from pymes_amd.solver import fno
@@ -813,6 +873,12 @@ class CCSD(ccd.CCD):
                          nv_keep=fno_nv, device=self.device)
         print_logging_info("FNO: {} frozen core, {} of {} virtuals kept, dMP2 = {:.12f} ({:.3f} seconds)".format(
             r.n_frozen, r.nv, r.C.shape[0], r.de_mp2, time.time() - time_fno), level=1)
+        if kwargs.get("response") is not None:          # the operators in the correlated space, like f: U^T O U
+            U = np.zeros((t_fock_pq.shape[0], r.no + r.nv))
+            U[r.n_frozen:self.no, :r.no] = np.eye(r.no)
+            U[self.no:, r.no:] = r.C
+            opts = kwargs["response"]
+            kwargs["response"] = dict(opts, operators=np.einsum("px,zpq,qy->zxy", U, opts["operators"], U))
         no = self.no
         self.no = r.no
         try:

@@ -7,8 +7,13 @@ pymes_response_vectors), the dense resolvent, the sum over all states of the den
   xi(O) = (R1(O), R2(O)): the CCSD residuals at (t1, t2) with f = O and V = 0
   <eta(O), r> = sum gammaR(r) O for every symmetric r (gammaR of _transition_reference, linear in r and in f)
   x^O(z) = (z - A)^-1 xi(O),   <<X;Y>>_z = <eta(X), x^Y(z)> + <eta(Y), x^X(-z)>
+
+and the two passes of the linear solver's sweep over flat vectors by their contract in include/pymes_amd.h (``sweep_dots_reference``,
+``sweep_update_reference``: complex128, exactly rounded sums, with the magnitude of every expression for a forward error bound) and
+the solver's loop written with nothing but those two (``orthomin_reference``).
 """
 import functools
+import math
 
 import numpy as np
 import scipy.linalg
@@ -174,3 +179,144 @@ def two_electron_polarizability(f, V, O, z):
     """-<<O;O>>_z of the exact singlet states of two electrons (``two_electron_fci``)."""
     gaps, mom = T.two_electron_fci(f, V, O)
     return -(mom * (1.0 / (z - gaps) - 1.0 / (z + gaps))).sum()
+
+
+# ---- the solver's sweep: dots and the fused update over flat vectors (include/pymes_amd.h, pymes_response_dots / _update) --------------
+HIST = 32                   # PYMES_RESPONSE_HIST
+DOTS = 2 * (HIST + 2)       # PYMES_RESPONSE_DOTS
+
+
+class SweepSystem:
+    """One system of a sweep on the host: flat vectors x, r, p, ap (real or complex; p, ap None: no step), the stored directions
+    hp, hq (lists), the coefficients g, alpha, the shift z and the scale inv."""
+
+    def __init__(self, x=None, r=None, p=None, ap=None, hp=(), hq=(), g=(), alpha=0.0, z=0.0, inv=1.0):
+        self.x, self.r, self.p, self.ap = x, r, p, ap
+        self.hp, self.hq, self.g = list(hp), list(hq), list(g)
+        self.alpha, self.z, self.inv = complex(alpha), complex(z), float(inv)
+
+    @property
+    def nh(self):
+        return len(self.hq)
+
+
+def active_mask(length, n1, off2):
+    e = np.arange(length)
+    return (e < n1) | (e >= off2)
+
+
+def _c(v):
+    return np.asarray(v).astype(np.complex128)
+
+
+def mag(v):
+    """|Re| + |Im|, element by element (of a number: the same)."""
+    v = np.asarray(v)
+    return np.abs(v.real) + np.abs(v.imag)
+
+
+def fsum(*terms):
+    return math.fsum(np.concatenate([np.ravel(t) for t in terms]).tolist())
+
+
+def _inner(u, v):
+    """(Re, Im) of sum conj(u) v, every real product a term of its own in an exactly rounded sum."""
+    return fsum(u.real * v.real, u.imag * v.imag), fsum(u.real * v.imag, -(u.imag * v.real))
+
+
+def sweep_dots_reference(system, n1, off2):
+    """(row, magnitudes) [PYMES_RESPONSE_DOTS] each: <hq_j, q> for j < nh, <q, q> (its second double 0), <q, r> with
+    q = z p - ap, summed over the active elements; magnitudes: the same sums with every product replaced by the product of the
+    factors' |Re| + |Im|, mag(q) = mag(z) mag(p) + mag(ap)."""
+    S = system
+    act = active_mask(len(S.p), n1, off2)
+    p, ap, r = _c(S.p)[act], _c(S.ap)[act], _c(S.r)[act]
+    q, mq = S.z * p - ap, mag(S.z) * mag(p) + mag(ap)
+    row, mags = np.zeros(DOTS), np.zeros(DOTS)
+    for j in range(S.nh):
+        hq = _c(S.hq[j])[act]
+        row[2 * j], row[2 * j + 1] = _inner(hq, q)
+        mags[2 * j] = mags[2 * j + 1] = fsum(mag(hq) * mq)
+    nh = S.nh
+    row[2 * nh] = fsum(q.real * q.real, q.imag * q.imag)
+    mags[2 * nh] = fsum(mq * mq)
+    row[2 * nh + 2], row[2 * nh + 3] = _inner(q, r)
+    mags[2 * nh + 2] = mags[2 * nh + 3] = fsum(mq * mag(r))
+    return row, mags
+
+
+def sweep_update_reference(system, d, floor, n1, off2):
+    """(new, magnitudes, |r|^2, its magnitude sum, floored): ``new`` and ``magnitudes`` are dictionaries of the flat complex
+    vectors x, r, p, ap, pn after the update (p, ap None without a step; the pad of pn zero, of the others as given) and of the
+    element-wise magnitudes of their expressions (absolute values, every subtraction an addition); ``floored``: the elements
+    whose |z - d| was below the floor."""
+    S = system
+    length = len(S.r)
+    act = active_mask(length, n1, off2)
+    x, r = _c(S.x).copy(), _c(S.r).copy()
+    mx, mr = mag(x), mag(r)
+    new, mags = dict(p=None, ap=None), dict(p=None, ap=None)
+    if S.p is not None:
+        p, ap = _c(S.p).copy(), _c(S.ap).copy()
+        q, mq = S.z * p - ap, mag(S.z) * mag(p) + mag(ap)
+        mp = mag(p)
+        for j in range(S.nh):
+            p = p - S.g[j] * _c(S.hp[j])
+            q = q - S.g[j] * _c(S.hq[j])
+            mp = mp + mag(S.g[j]) * mag(S.hp[j])
+            mq = mq + mag(S.g[j]) * mag(S.hq[j])
+        p, q, mp, mq = p * S.inv, q * S.inv, mp * abs(S.inv), mq * abs(S.inv)
+        x[act] = (x + S.alpha * p)[act]
+        r[act] = (r - S.alpha * q)[act]
+        mx, mr = mx + mag(S.alpha) * mp, mr + mag(S.alpha) * mq
+        new["p"], new["ap"], mags["p"], mags["ap"] = p, q, mp, mq
+    w = S.z - np.asarray(d, dtype=np.float64)[act]
+    re, im = w.real.copy(), w.imag
+    low = np.abs(w) < floor
+    re[low] = np.copysign(floor, re[low])
+    den = re * re + im * im
+    pn, mpn = np.zeros(length, dtype=np.complex128), np.zeros(length)
+    pn[act] = r[act] * (re - 1j * im) / den
+    mpn[act] = mr[act] * (np.abs(re) + np.abs(im)) / den
+    new.update(x=x, r=r, pn=pn)
+    mags.update(x=mx, r=mr, pn=mpn)
+    ra = r[act]
+    floored = np.zeros(length, dtype=bool)
+    floored[act] = low
+    return new, mags, fsum(ra.real * ra.real, ra.imag * ra.imag), fsum(mr[act] * mr[act]), floored
+
+
+def orthomin_reference(A, d, xi, z, history, floor, r_epsilon, max_iter):
+    """The loop of ``EOM_CCSD_Response._sweep`` for one system (z - A) x = xi with a dense A and the two references above (no
+    pad): (x, sweeps, |xi - (z - A) x| / |xi| measured afresh).  A break-down or max_iter sweeps end the loop as they are: the
+    residual returned tells."""
+    n = len(xi)
+    S = SweepSystem(x=np.zeros(n, dtype=np.complex128), r=_c(xi), z=z)
+    new, _, nrm, _, _ = sweep_update_reference(S, d, floor, n, n)                   # p_0 = r_0 / (z - d), |xi|^2
+    norm0, pn = np.sqrt(nrm), new["pn"]
+    sweeps = 0
+    while sweeps < max_iter and norm0 > 0.0:
+        S.p = pn
+        S.ap = A @ S.p
+        row, _ = sweep_dots_reference(S, n, n)
+        nh = S.nh
+        g = row[0:2 * nh:2] + 1j * row[1:2 * nh:2]
+        qq, qr = row[2 * nh], complex(row[2 * nh + 2], row[2 * nh + 3])
+        left = qq - float((np.abs(g) ** 2).sum())
+        if not np.isfinite(left) or left <= 1e-12 * max(qq, 1e-300):
+            break
+        S.g, S.inv = list(g), 1.0 / np.sqrt(left)
+        S.alpha = qr * S.inv
+        new, _, nrm, _, _ = sweep_update_reference(S, d, floor, n, n)
+        S.x, S.r, pn = new["x"], new["r"], new["pn"]
+        S.hp.append(new["p"])
+        S.hq.append(new["ap"])
+        if len(S.hp) > history:
+            S.hp.pop(0)
+            S.hq.pop(0)
+        S.p = S.ap = None
+        sweeps += 1
+        if not np.isfinite(nrm) or np.sqrt(nrm) <= r_epsilon * norm0:
+            break
+    res = _c(xi) - (z * S.x - A @ S.x)
+    return S.x, sweeps, float(np.linalg.norm(res) / norm0) if norm0 > 0.0 else 0.0

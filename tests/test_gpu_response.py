@@ -79,6 +79,47 @@ def test_response_vectors_against_the_definitions(gpu_lib, no, nv, k):
     assert np.abs(got[1][0] - got[1][1]).max() > 1e-3 and np.abs(got[3][0] - got[3][1]).max() > 1e-3
 
 
+def test_response_vectors_with_a_full_pointer_table(gpu_lib):
+    """k = 64 at (2,3): the whole by-value pointer table, eight full chunks of eight operators; k = 65: the Python side's second
+    call with one operator.  Every operator against the definitions at the tolerance of
+    test_response_vectors_against_the_definitions; operator 64 of the k = 65 call is, to the bit, a k = 1 call of its own; xi2 and
+    eta2 are exchange-symmetric to the bit.  The 65 operators are seeded combinations of eight dense random ones: xi and eta are
+    linear in O (test_definitions_are_linear_in_the_operator), so eight evaluations of the definitions give all 65 references."""
+    from pymes_amd.device import Context
+    from pymes_amd.solver.response import OPS_MAX
+    no, nv = 2, 3
+    assert OPS_MAX == 64
+    t1, t2, lam, _, _ = X.density_inputs(no, nv, 9)
+    rng = np.random.default_rng(64)
+    basis, coef = rng.standard_normal((8, no + nv, no + nv)), rng.standard_normal((65, 8))
+    ops = np.einsum("zb,bpq->zpq", coef, basis)
+    defs = [P.xi_definition(no, t1, t2, O) + P.eta_definition(no, t1, t2, lam, O) for O in basis]
+    mix = lambda z, part: sum(c * d[part] for c, d in zip(coef[z], defs))
+    ref = [((mix(z, 0), mix(z, 1)), (mix(z, 2), mix(z, 3))) for z in range(65)]
+    ctx = Context(no, nv)
+    try:
+        full = _device_vectors(ctx, t1, t2, lam, ops[:64])
+        more = _device_vectors(ctx, t1, t2, lam, ops)
+        last = _device_vectors(ctx, t1, t2, lam, ops[64:])
+    finally:
+        ctx.close()
+    for k, got in ((64, full), (65, more)):
+        worst = 0.0
+        for z in range(k):
+            parts = (got[0][z], got[1][z], got[2][z], got[3][z])
+            want = (ref[z][0][0], ref[z][0][1], ref[z][1][0], ref[z][1][1])
+            errs = [np.abs(a - b).max() for a, b in zip(parts, want)] + [abs(got[4][z] - P.dot(lam, ref[z][0]))]
+            worst = max(worst, max(errs))
+            assert max(errs) < 1e-10, (k, z, errs)
+            assert np.array_equal(parts[1], parts[1].transpose(1, 0, 3, 2)) and np.array_equal(parts[3], parts[3].transpose(1, 0, 3, 2))
+        print("k = %d: largest error of xi1, xi2, eta1, eta2, g0 over all operators %.2e" % (k, worst))
+    for part in range(4):
+        assert np.array_equal(more[part][64], last[part][0])
+        for z in range(64):
+            assert np.array_equal(more[part][z], full[part][z])
+    assert more[4][64] == last[4][0] and np.array_equal(more[4][:64], full[4])
+
+
 # ---- 2. the adjoint identities on the device ---------------------------------------------------------------------------------------------
 def test_adjoint_identities_on_the_device_12_48(gpu_lib):
     """<eta(O), r> = sum gammaR(r) O and <l, xi(O)> = sum gammaL(l) O with the densities of ``device_tdm1``, for random

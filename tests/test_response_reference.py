@@ -1,8 +1,10 @@
 """CPU: the numpy reference of the EOM-CCSD linear response function (tests/_response_reference.py) — the written-out property
 vectors against their definitions, the dense resolvent against the full sum over states and against the exact two-electron
-value — and what of the device path needs no GPU: the declarations, the host side of the entries up to the kernels (host
+value, the references of the solver's sweep (dots, fused update, the Orthomin loop built from them) against dense solves and a
+case worked out by hand — and what of the device path needs no GPU: the declarations, the host side of the entries up to the kernels (host
 simulator), the refusals of ``CCSD.solve(response=...)`` and ``UEG.density_operator``."""
 import ctypes as C
+import functools
 import os
 import re
 from types import SimpleNamespace
@@ -34,6 +36,20 @@ def test_written_out_vectors_against_the_definitions(no, nv, seed):
     assert np.array_equal(P.xi_terms(no, t1, t2, O)[1], P.xi_terms(no, t1, t2, O)[1].transpose(1, 0, 3, 2))
 
 
+def test_definitions_are_linear_in_the_operator():
+    """xi(O) and eta(O) by definition are linear in O, to rounding: a GPU test with 65 operators takes its references from the
+    definitions of a few."""
+    no, nv = 2, 3
+    t1, t2, lam, _, _ = T.density_inputs(no, nv, 9)
+    rng = np.random.default_rng(64)
+    basis, coef = rng.standard_normal((3, no + nv, no + nv)), rng.standard_normal(3)
+    both = lambda O: P.xi_definition(no, t1, t2, O) + P.eta_definition(no, t1, t2, lam, O)
+    parts, whole = [both(O) for O in basis], both(np.einsum("b,bpq->pq", coef, basis))
+    for k in range(4):
+        mixed = sum(c * p[k] for c, p in zip(coef, parts))
+        assert np.abs(mixed - whole[k]).max() < 1e-13 * max(1.0, np.abs(whole[k]).max())
+
+
 @pytest.mark.parametrize("no,nv,seed", [(2, 3, 11), (3, 5, 12)])
 def test_dense_resolvent_against_the_sum_over_all_states(no, nv, seed):
     """<eta(X), (z - A)^-1 xi(Y)> + <eta(Y), (-z - A)^-1 xi(X)> equals the sum over ALL states of the dense eigenproblem with the
@@ -58,6 +74,75 @@ def test_dense_resolvent_against_two_electron_fci():
         want = P.two_electron_polarizability(ref["f"], ref["V"], ref["ops"][0], z)
         print("z = %s: polarizability %s, FCI %s" % (z, got, want))
         assert abs(got - want) < 1e-10 * max(1.0, abs(want))
+
+
+# ---- the references of the solver's sweep, before a kernel is judged by them ------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _orthomin_problem(no, nv, seed, hermitian):
+    """(A, d, xi, w1): A in an orthonormalised symmetric basis (the construction of ``DenseResponse.resolvent_norm``), its
+    diagonal, the xi of operator 0 in that basis."""
+    ref = P.reference_problem(no, nv, seed, hermitian, 2)
+    dense = ref["dense"]
+    Q, _ = np.linalg.qr(dense.co.B)
+    A = Q.T @ (dense.co.B @ np.linalg.solve(dense.G, dense.BA) @ np.linalg.solve(dense.G, dense.co.B.T @ Q))
+    return A, np.diag(A).copy(), Q.T @ dense.co.full(*dense.xi[0]), ref["w1"]
+
+
+@pytest.mark.parametrize("history", [1, 2, 12])
+@pytest.mark.parametrize("hermitian", [True, False], ids=["8-fold", "non-hermitian"])
+@pytest.mark.parametrize("no,nv,seed", [(2, 3, 11), (3, 5, 12)])
+def test_orthomin_reference_against_the_dense_solve(no, nv, seed, hermitian, history):
+    """The loop of ``EOM_CCSD_Response._sweep`` written with ``sweep_dots_reference`` and ``sweep_update_reference`` alone, at
+    z = 0, +-0.4 w1 and 0.4 w1 + 0.05i: it converges within 200 sweeps, its fresh residual is at r_epsilon, x is the dense
+    solution within 10 r_epsilon |xi| |(z - A)^-1|_2, and a window of 1 or 2 pairs slides (more sweeps than ``history``)."""
+    A, d, xi, w1 = _orthomin_problem(no, nv, seed, hermitian)
+    r_eps, floor, eye = 1e-10, 1e-3, np.eye(len(xi))
+    for z in (0.0, 0.4 * w1, -0.4 * w1, 0.4 * w1 + 0.05j):
+        x, sweeps, res = P.orthomin_reference(A, d, xi, z, history, floor, r_eps, 200)
+        want = np.linalg.solve(z * eye - A, xi.astype(np.complex128))
+        tol = 10.0 * r_eps * np.linalg.norm(xi) * np.linalg.norm(np.linalg.inv(z * eye - A), 2)
+        err = np.linalg.norm(x - want)
+        print("(%d,%d) %s history %d z = %s: %d sweeps, fresh residual %.2e, |x - dense| %.2e (tolerance %.2e)"
+              % (no, nv, "8-fold" if hermitian else "non-hermitian", history, z, sweeps, res, err, tol))
+        assert sweeps < 200 and res <= 1.01 * r_eps
+        assert err <= tol
+        assert np.imag(z) != 0.0 or np.abs(x.imag).max() == 0.0          # (a real system stays real)
+        if history <= 2:
+            assert sweeps > history
+
+
+def test_sweep_references_on_a_hand_made_case():
+    """Four active elements around a pad of NaN: the dots, the step and the floor against numbers worked out by hand."""
+    nan = np.nan
+    S = P.SweepSystem(x=np.array([1.0, nan, 0.0, 2.0, 1.0]), r=np.array([2.0, nan, 1.0, -1.0, 4.0]) + 0j,
+                      p=np.array([1.0, nan, 2.0, 0.0, 1.0]) + 1j * np.array([0.0, nan, 1.0, 1.0, 0.0]),
+                      ap=np.array([0.0, nan, 1.0, 1.0, 2.0]) + 0j, hp=[np.array([1.0, nan, 0.0, 0.0, 0.0]) + 0j],
+                      hq=[np.array([0.0, nan, 1j, 0.0, 0.0])], g=[2.0j], alpha=0.5, z=2.0, inv=0.5)
+    # q = 2 p - ap = [2, -, 3 + 2i, -1 + 2i, 0]
+    row, mags = P.sweep_dots_reference(S, 1, 2)
+    assert list(row[:6]) == [2.0, -3.0, 22.0, 0.0, 8.0, 0.0] and not row[6:].any()           # conj(i) (3 + 2i) = 2 - 3i
+    # mag(q) = 2 mag(p) + mag(ap) = [2, -, 7, 3, 4]
+    assert list(mags[:6]) == [7.0, 7.0, 4.0 + 49.0 + 9.0 + 16.0, 0.0, 4.0 + 7.0 + 3.0 + 16.0, 4.0 + 7.0 + 3.0 + 16.0] and not mags[6:].any()
+    d = np.array([1.0, nan, 2.0, 2.0 + 0.25, 4.0])
+    new, m, nrm, mnrm, floored = P.sweep_update_reference(S, d, 0.5, 1, 2)
+    # ph = (p - 2i hp) / 2 = [0.5 - i, -, 1 + 0.5i, 0.5i, 0.5];  qh = (q - 2i hq) / 2 = [1, -, 2.5 + i, -0.5 + i, 0]
+    assert np.array_equal(new["p"][[0, 2, 3, 4]], [0.5 - 1j, 1 + 0.5j, 0.5j, 0.5])
+    assert np.array_equal(new["ap"][[0, 2, 3, 4]], [1.0, 2.5 + 1j, -0.5 + 1j, 0.0])
+    assert np.array_equal(new["x"][[0, 2, 3, 4]], [1.25 - 0.5j, 0.5 + 0.25j, 2 + 0.25j, 1.25])
+    assert np.array_equal(new["r"][[0, 2, 3, 4]], [1.5, -0.25 - 0.5j, -0.75 - 0.5j, 4.0])
+    # z - d = [1, -, +0 -> 0.5, -0.25 -> -0.5, -2]
+    assert list(floored) == [False, False, True, True, False]
+    assert np.array_equal(new["pn"], [1.5, 0.0, -0.5 - 1j, 1.5 + 1j, -2.0]) and not np.signbit(new["pn"][1].real)
+    assert nrm == 2.25 + 0.3125 + 0.8125 + 16.0
+    # mag(qh) = ([2, -, 7, 3, 4] + 2 [0, -, 1, 0, 0]) / 2, mag(r) = [2, -, 1, 1, 4] + mag(qh) / 2
+    assert np.array_equal(m["r"][[0, 2, 3, 4]], [2.5, 3.25, 1.75, 5.0]) and mnrm == 2.5 ** 2 + 3.25 ** 2 + 1.75 ** 2 + 25.0
+    assert np.array_equal(m["pn"][[0, 2, 3, 4]], [2.5, 6.5, 3.5, 2.5])
+    # no step: x and r as given, pn and |r|^2 of the r given
+    S.p = S.ap = None
+    with np.errstate(all="ignore"):
+        new, m, nrm, _, floored = P.sweep_update_reference(S, d, 0.0, 1, 2)
+    assert new["p"] is None and np.array_equal(new["r"][[0, 2, 3, 4]], [2.0, 1.0, -1.0, 4.0]) and nrm == 22.0
+    assert np.array_equal(new["pn"][[0, 3, 4]], [2.0, 4.0, -2.0]) and not np.isfinite(new["pn"][2]) and not floored.any()
 
 
 # ---- what needs no GPU of the device path ---------------------------------------------------------------------------------------------

@@ -571,6 +571,57 @@ int pymes_ueg_eval_2b_corr(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mod
 int pymes_ueg_eval_2b_tab(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mode, double L, int lattice_cutoff,
                           const int32_t* k_int_host, const int32_t* index_map_host, const double* tab_scalar_host,
                           const double* tab_array_host, int64_t tab_len, double* V_dev);
+/* The same elements for a list: out_dev[t] = <pq|rs> of pqrs_dev[t][4] (int32, device), t < count -- the integral sectors of
+ * the momentum-sector solver (below), never a dense array.  One entry for all correlators: tab_array_host non-NULL selects the
+ * tables (with tab_scalar_host, tab_len as above), else correlator 0 is UEG.trunc with (k_cutoff, gamma) and 1..6 the named
+ * ones with params_host[4].  Momentum conservation is decided in exact integer arithmetic: an entry that does not conserve
+ * the vector is 0 (the dense builder range-checks only the flattened lookup index, like the reference, and sets a few such
+ * elements at some bases); an entry that names no orbital is NaN.  mode 2 is written already symmetrised,
+ * (E[p,r] + E[q,s]) / 2.  Synchronises; refused while a launch graph is being recorded. */
+int pymes_ueg_eval_2b_list(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mode, double L, double k_cutoff, double gamma,
+                           int lattice_cutoff, int correlator, const double* params_host, const int32_t* k_int_host,
+                           const double* tab_scalar_host, const double* tab_array_host, int64_t tab_len,
+                           const int32_t* pqrs_dev, int64_t count, double* out_dev);
+
+/* ---- momentum-sector CCD / DCD (pymes_amd/solver/ueg_cc.py, sectors.py; DESIGN "Momentum sectors") -------------
+ * A Hamiltonian whose orbitals carry a conserved integer vector keeps ~ o^2 v amplitudes, held block by block (one block
+ * per pair momentum, or per momentum transfer); every contraction of ccd.py:164-254 is one ragged batch of small products.
+ *
+ * pymes_sector_gemm: C[c..] = alpha op(A[a..]) op(B[b..]) + beta C[c..] for every record of a DEVICE-RESIDENT task table:
+ * row-major operands at element offsets a, b, c of the three arenas, leading dimensions lda, ldb, ldc, op = transpose when
+ * the flag is set (A is then stored k x m, B n x k).  m, n, k >= 0 (an empty block is legal; k = 0 scales C by beta).  One
+ * workgroup takes one PYMES_SECTOR_TILE_M x PYMES_SECTOR_TILE_N tile of one output block; tile0 is the number of tiles of
+ * all earlier records and ntiles their total.  No atomics, k summed in ascending order: identical calls give identical
+ * bits.  The kernel trusts the table (pymes_amd/solver/sectors.py checks it against the arena lengths before the upload);
+ * nothing outside the blocks is read or written, with beta = 0 the output block is not read, and C must not overlap A or B. */
+#define PYMES_SECTOR_TILE_M 32
+#define PYMES_SECTOR_TILE_N 16
+#define PYMES_SECTOR_TRANS_A 1
+#define PYMES_SECTOR_TRANS_B 2
+typedef struct pymes_sector_task {
+    int64_t m, n, k;
+    int64_t a, b, c;
+    int64_t lda, ldb, ldc;
+    int64_t flags;
+    int64_t tile0;
+    double alpha, beta;
+    int64_t reserved;
+} pymes_sector_task;
+int pymes_sector_gemm(pymes_ctx* ctx, const pymes_sector_task* tasks_dev, int ntask, int64_t ntiles, const double* A_dev,
+                      const double* B_dev, double* C_dev);
+/* dst[i] = beta dst[i] + a1 s1[m1[i]] + a2 s2[m2[i]], i < n (int64 maps on the device; s2_dev NULL: one source; beta = 0: dst
+ * is not read).  The moves between the three sector layouts, 2 D - C among them. */
+int pymes_sector_gather(pymes_ctx* ctx, double* dst_dev, int64_t n, double beta, double a1, const double* s1_dev,
+                        const int64_t* m1_dev, double a2, const double* s2_dev, const int64_t* m2_dev);
+/* The diagonal X_ac / X_ki terms (ccd.py:213-235) in the direct layout, rows g = (a,i) of row_len[g] elements from
+ * row_start[g] on: s[g] = sum_c Tt[g,c] W1[g,c] in ascending c, x_oo[i] = eps[i] + w sum_a s, x_vv[a] = eps[no + a] - w sum_i s,
+ * Ex[g,:] += (x_vv[a] - x_oo[i]) D[g,:].  row_of[a no + i] = g and ai_of[g] = a no + i; ws_dev: no nv + no + nv doubles. */
+int pymes_sector_xdiag(pymes_ctx* ctx, const double* Tt_dev, const double* W1_dev, const double* D_dev, double* Ex_dev,
+                       const double* eps_dev, double w, int no, int nv, const int64_t* row_start_dev, const int64_t* row_len_dev,
+                       const int64_t* row_of_dev, const int64_t* ai_of_dev, double* ws_dev);
+/* dt = r / (den + shift), t_out = t_in + dt over n elements (t_in_dev NULL: t_out = dt, the MP2 start; dt_dev NULL: not kept) */
+int pymes_sector_update(pymes_ctx* ctx, double* t_out_dev, double* dt_dev, const double* t_in_dev, const double* r_dev,
+                        const double* den_dev, double shift, int64_t n);
 
 /* ---- vector helpers for DIIS (pymes/mixer/diis.py:65-103) and norms ----------------- */
 /* out_host[p] = sum_i x[p][i]*y[p][i], npairs <= 16, deterministic reduction (synchronises) */

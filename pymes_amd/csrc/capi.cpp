@@ -910,6 +910,61 @@ int pymes_ueg_eval_2b_tab(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mode
         ueg_eval(ctx, n_p, n_ele, imax, mode, L, 0.0, 1.0, lattice_cutoff, k_int, index_map, tab_scalar, tab_array, tab_len, V);
     });
 }
+int pymes_ueg_eval_2b_list(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mode, double L, double k_cutoff, double gamma,
+                           int lattice_cutoff, int correlator, const double* params, const int32_t* k_int,
+                           const double* tab_scalar, const double* tab_array, int64_t tab_len, const int32_t* pqrs, int64_t count,
+                           double* out) {
+    return guarded([&] {
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("ueg_eval_2b_list while a launch graph is being recorded");
+        need(k_int, "k_int");
+        if (n_p < 1 || imax < 0 || mode < 0 || mode > 3 || count < 0) throw pymes::Error("ueg: bad arguments");
+        if (count > 0) { need(pqrs, "pqrs"); need(out, "out"); }
+        if (correlator < 0 || correlator > 6) throw pymes::Error("ueg: correlator must be 0 (trunc) .. 6");
+        if (correlator > 0) need(params, "params");
+        if (mode == 0 && (correlator > 0 || tab_array)) throw pymes::Error("ueg: mode 0 (Coulomb) has no correlator");
+        if (tab_array) {
+            const int64_t r = static_cast<int64_t>(lattice_cutoff) + 2 * imax, need_len = 3 * r * r + 1;
+            if (!tab_scalar || tab_len < need_len || tab_len > (int64_t(1) << 30)) throw pymes::Error("ueg: correlator tables must cover |n|^2 <= 3 (lattice_cutoff + 2 imax)^2");
+        }
+        for (int i = 0; i < 3 * n_p; ++i)       // the u_mat index of mode 1 spans momentum transfers up to 2 imax
+            if (k_int[i] < -imax || k_int[i] > imax) throw pymes::Error("ueg: k outside the index map");
+        if (count == 0) return;
+        int* kd = static_cast<int*>(dev::dmalloc(sizeof(int) * 3 * n_p));
+        try {
+            dev::memcpy_h2d(kd, k_int, sizeof(int) * 3 * n_p, e.stream);
+            dev::UegParams p{n_p, n_ele, imax, mode, L, L * L * L, correlator == 0 ? k_cutoff : 0.0, correlator == 0 ? gamma : 1.0,
+                             lattice_cutoff};
+            p.tab_scalar = tab_scalar; p.tab_array = tab_array; p.tab_len = static_cast<int>(tab_len);
+            p.corr_kind = tab_array ? 0 : correlator;
+            for (int i = 0; i < 4 && params && correlator > 0; ++i) p.corr_p[i] = params[i];
+            dev::ueg_two_body_list(p, kd, pqrs, count, out, e.stream);      // (drains the stream before it returns)
+        } catch (...) {
+            dev::dfree(kd);
+            throw;
+        }
+        dev::dfree(kd);
+    });
+}
+
+// ---- momentum-sector CCD / DCD (kernels_sector.hip; pymes_amd/solver/ueg_cc.py) --------------------------------------------------
+int pymes_sector_gemm(pymes_ctx* ctx, const pymes_sector_task* tasks, int ntask, int64_t ntiles, const double* A, const double* B,
+                      double* C) {
+    return guarded([&] { dev::sector_gemm(tasks, ntask, ntiles, A, B, C, E(ctx).stream); });
+}
+int pymes_sector_gather(pymes_ctx* ctx, double* dst, int64_t n, double beta, double a1, const double* s1, const int64_t* m1,
+                        double a2, const double* s2, const int64_t* m2) {
+    return guarded([&] { dev::sector_gather(dst, n, beta, a1, s1, m1, a2, s2, m2, E(ctx).stream); });
+}
+int pymes_sector_xdiag(pymes_ctx* ctx, const double* Tt, const double* W1, const double* D, double* Ex, const double* eps, double w,
+                       int no, int nv, const int64_t* row_start, const int64_t* row_len, const int64_t* row_of, const int64_t* ai_of,
+                       double* ws) {
+    return guarded([&] { dev::sector_xdiag(Tt, W1, D, Ex, eps, w, no, nv, row_start, row_len, row_of, ai_of, ws, E(ctx).stream); });
+}
+int pymes_sector_update(pymes_ctx* ctx, double* t_out, double* dt, const double* t_in, const double* r, const double* den,
+                        double shift, int64_t n) {
+    return guarded([&] { dev::sector_update(t_out, dt, t_in, r, den, shift, n, E(ctx).stream); });
+}
 
 int pymes_dots(pymes_ctx* ctx, int npairs, const double* const* x, const double* const* y, int64_t n,
                double* out) {

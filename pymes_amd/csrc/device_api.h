@@ -1,6 +1,7 @@
 // Device abstraction used by the host engine (engine.cpp).
 //
-// Product build: implemented by kernels.hip, kernels_post.hip and kernels_integrals.hip (hand-written gfx950 kernels).
+// Product build: implemented by kernels.hip, kernels_post.hip, kernels_integrals.hip and kernels_sector.hip (hand-written
+// gfx950 kernels).
 // tests/hostsim/ implements the same functions with plain CPU loops so that the
 // HOST logic (contraction planner, CC term sequencing, C-ABI plumbing) can be
 // exercised under `pytest -m "not gpu"`, valgrind and ASan.  The host simulator is
@@ -9,9 +10,11 @@
 #include <cstddef>
 #include <cstdint>
 
+struct pymes_sector_task;   // include/pymes_amd.h
+
 namespace dev {
 
-typedef void* stream_t;   // hipStream_t in the product build
+typedef void* stream_t;  // hipStream_t in the product build
 
 const char* backend_name();
 // throws std::runtime_error on failure
@@ -534,5 +537,20 @@ struct UegParams {
     int tab_len = 0;
 };
 void ueg_two_body(const UegParams& prm, const int* k_int_dev, const int* index_map_dev, double* V_dev, stream_t s);
+// out_dev[t] = V of pqrs_dev[t][4], t < count: the same elements for a list (include/pymes_amd.h, pymes_ueg_eval_2b_list).  The
+// product library only (the host simulator has no definition: a weak one in the engine throws).
+void ueg_two_body_list(const UegParams& prm, const int* k_int_dev, const int* pqrs_dev, int64_t count, double* out_dev, stream_t s);
+
+// ---- momentum-sector CCD / DCD (include/pymes_amd.h, pymes_sector_*; DESIGN "Momentum sectors").  The product library only
+// (weak definitions in the engine throw, by name).
+void sector_gemm(const pymes_sector_task* tasks_dev, int ntask, int64_t ntiles, const double* A, const double* B, double* C,
+                 stream_t s);
+void sector_gather(double* dst, int64_t n, double beta, double a1, const double* s1, const int64_t* m1, double a2, const double* s2,
+                   const int64_t* m2, stream_t s);
+void sector_xdiag(const double* Tt, const double* W1, const double* D, double* Ex, const double* eps, double w, int no, int nv,
+                  const int64_t* row_start, const int64_t* row_len, const int64_t* row_of, const int64_t* ai_of, double* ws,
+                  stream_t s);
+void sector_update(double* t_out, double* dt, const double* t_in, const double* r, const double* den, double shift, int64_t n,
+                   stream_t s);
 
 }  // namespace dev

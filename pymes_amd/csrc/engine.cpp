@@ -905,4 +905,22 @@ __attribute__((weak)) int energy_norms_start_sym(const double*, const double*, c
 __attribute__((weak)) void t2_layouts_sym(const double*, double*, double*, double*, int, int, stream_t) {
     throw std::runtime_error("t2_layouts_sym: not available in this backend");
 }
+// ... and without the momentum-sector kernels (kernels_sector.hip) and the list form of the electron-gas integrals
+__attribute__((weak)) void ueg_two_body_list(const UegParams&, const int*, const int*, int64_t, double*, stream_t) {
+    throw std::runtime_error("ueg_two_body_list: not available in this backend");
+}
+__attribute__((weak)) void sector_gemm(const pymes_sector_task*, int, int64_t, const double*, const double*, double*, stream_t) {
+    throw std::runtime_error("sector_gemm: not available in this backend");
+}
+__attribute__((weak)) void sector_gather(double*, int64_t, double, double, const double*, const int64_t*, double, const double*,
+                                         const int64_t*, stream_t) {
+    throw std::runtime_error("sector_gather: not available in this backend");
+}
+__attribute__((weak)) void sector_xdiag(const double*, const double*, const double*, double*, const double*, double, int, int,
+                                        const int64_t*, const int64_t*, const int64_t*, const int64_t*, double*, stream_t) {
+    throw std::runtime_error("sector_xdiag: not available in this backend");
+}
+__attribute__((weak)) void sector_update(double*, double*, const double*, const double*, const double*, double, int64_t, stream_t) {
+    throw std::runtime_error("sector_update: not available in this backend");
+}
 }  // namespace dev

@@ -16,8 +16,8 @@
 //
 // What lives here: every kernel that bench.py's timed workloads launch (a CCSD iteration, an EE sigma build, the Davidson /
 // FEAST algebra): bench.py hashes THIS file's text to accept the committed counter passes (profiles/r06).  The post-CCSD
-// families are in kernels_post.hip, the one-off integral builders in kernels_integrals.hip, both on launch.h and
-// device_util.h.  They are included at the end of this file, not compiled on their own: a code object per file made the first
+// families are in kernels_post.hip, the one-off integral builders in kernels_integrals.hip, the momentum-sector CCD / DCD
+// kernels in kernels_sector.hip, all on launch.h and device_util.h.  They are included at the end of this file, not compiled on their own: a code object per file made the first
 // integral build of a process 2.0-5.8 ms slower in six bench pairs of six (profiles/kernel_units/INDEX.md).  One unit also
 // means an edit there is compiled WITH the timed kernels: the hash not moving is a convention, compare code objects when in doubt.
 #include <hip/hip_runtime.h>
@@ -5603,3 +5603,4 @@ bool gemv_dispatch(const GemmProduct& p, hipStream_t st) {
 // (the rest of the translation unit: see the head of this file)
 #include "kernels_post.hip"
 #include "kernels_integrals.hip"
+#include "kernels_sector.hip"

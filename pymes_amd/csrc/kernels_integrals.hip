@@ -221,23 +221,11 @@ __global__ void ueg_effective_kernel(const UegK u, const int* __restrict__ kint,
     E[idx] = val / u.Omega;
 }
 
-// one thread per (p,q,r): s by momentum conservation through the flattened lookup (ueg.py:384-507)
-__global__ void ueg_scatter_kernel(const UegK u, const int* __restrict__ kint, const int* __restrict__ map,
-                                   const double* __restrict__ umat, const int* __restrict__ umat_index,
-                                   const double* __restrict__ E, double* __restrict__ V) {
-    const long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
+// V_pqrs of one momentum-conserving element (ueg.py:404-507); umat / E: what ueg_prepare made for modes 1 / 2
+__device__ __forceinline__ double ueg_element(const UegK& u, const int* __restrict__ kint, const double* __restrict__ umat,
+                                              const int* __restrict__ umat_index, const double* __restrict__ E, int p, int r,
+                                              int s, const int d[3]) {
     const long n = u.n_p;
-    if (idx >= n * n * n) return;
-    const int r = (int)(idx % n), q = (int)((idx / n) % n), p = (int)(idx / (n * n));
-    int d[3], ks[3];
-    for (int c = 0; c < 3; ++c) {
-        d[c] = kint[3 * r + c] - kint[3 * p + c];
-        ks[c] = kint[3 * q + c] - d[c];
-    }
-    const long loc = (long)u.m * u.m * (ks[0] + u.imax) + (long)u.m * (ks[1] + u.imax) + ks[2] + u.imax;
-    if (loc < 0 || loc >= (long)u.m * u.m * u.m) return;     // only the flattened index is range-checked (:397)
-    const int s = map[loc];
-    if (s < 0 || s >= u.n_p) return;
     double dk[3], dk2 = 0.0;
     long md = 0;
     for (int c = 0; c < 3; ++c) {
@@ -264,7 +252,51 @@ __global__ void ueg_scatter_kernel(const UegK u, const int* __restrict__ kint, c
     } else {
         w = E[(long)p * n + r];
     }
-    V[((long)(p * n + q) * n + r) * n + s] = w;
+    return w;
+}
+
+// one thread per (p,q,r): s by momentum conservation through the flattened lookup (ueg.py:384-507)
+__global__ void ueg_scatter_kernel(const UegK u, const int* __restrict__ kint, const int* __restrict__ map,
+                                   const double* __restrict__ umat, const int* __restrict__ umat_index,
+                                   const double* __restrict__ E, double* __restrict__ V) {
+    const long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    const long n = u.n_p;
+    if (idx >= n * n * n) return;
+    const int r = (int)(idx % n), q = (int)((idx / n) % n), p = (int)(idx / (n * n));
+    int d[3], ks[3];
+    for (int c = 0; c < 3; ++c) {
+        d[c] = kint[3 * r + c] - kint[3 * p + c];
+        ks[c] = kint[3 * q + c] - d[c];
+    }
+    const long loc = (long)u.m * u.m * (ks[0] + u.imax) + (long)u.m * (ks[1] + u.imax) + ks[2] + u.imax;
+    if (loc < 0 || loc >= (long)u.m * u.m * u.m) return;     // only the flattened index is range-checked (:397)
+    const int s = map[loc];
+    if (s < 0 || s >= u.n_p) return;
+    V[((long)(p * n + q) * n + r) * n + s] = ueg_element(u, kint, umat, umat_index, E, p, r, s, d);
+}
+
+// one thread per listed (p,q,r,s): the same element, conservation decided in exact integer arithmetic (a list entry that
+// does not conserve the vector is 0, one that names no orbital is NaN); mode 2 already symmetrised, (E[p,r] + E[q,s]) / 2
+__global__ void ueg_list_kernel(const UegK u, const int* __restrict__ kint, const double* __restrict__ umat,
+                                const int* __restrict__ umat_index, const double* __restrict__ E, const int* __restrict__ pqrs,
+                                long count, double* __restrict__ out) {
+    const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const int p = pqrs[4 * t], q = pqrs[4 * t + 1], r = pqrs[4 * t + 2], s = pqrs[4 * t + 3];
+    if (p < 0 || q < 0 || r < 0 || s < 0 || p >= u.n_p || q >= u.n_p || r >= u.n_p || s >= u.n_p) { out[t] = nan(""); return; }
+    int d[3], e[3];
+    bool ok = true;
+    for (int c = 0; c < 3; ++c) {
+        d[c] = kint[3 * r + c] - kint[3 * p + c];
+        e[c] = kint[3 * s + c] - kint[3 * q + c];
+        ok = ok && d[c] + e[c] == 0;
+    }
+    double w = 0.0;
+    if (ok) {
+        w = ueg_element(u, kint, umat, umat_index, E, p, r, s, d);
+        if (u.mode == 2) w = 0.5 * w + 0.5 * ueg_element(u, kint, umat, umat_index, E, q, s, r, e);
+    }
+    out[t] = w;
 }
 
 }  // namespace
@@ -346,8 +378,11 @@ double tc_triple_contraction(const double* L, int nb, int no, stream_t s) {
     return h;
 }
 
-void ueg_two_body(const UegParams& prm, const int* k_int_dev, const int* index_map_dev, double* V_dev, stream_t s) {
-    hipStream_t st = (hipStream_t)s;
+// The preparation steps shared by the dense builder and the list builder: the kernel parameters, the correlator tables, and
+// for mode 1 the u_mat table over the distinct momentum transfers, for mode 2 E[p,r]; then `fill(u, umat, uidx, E)` launches
+// the kernel that writes the integrals, and everything is released once the stream has drained.
+template <typename Fill>
+static void ueg_prepare_and_fill(const UegParams& prm, const int* k_int_dev, hipStream_t st, Fill fill) {
     UegK u;
     u.n_p = prm.n_p; u.n_occ = prm.n_ele / 2; u.imax = prm.imax; u.m = 2 * prm.imax + 1; u.mode = prm.mode;
     u.n_ele = prm.n_ele; u.lat = prm.lattice_cutoff; u.L = prm.L; u.Omega = prm.Omega; u.gamma = prm.gamma;
@@ -366,7 +401,6 @@ void ueg_two_body(const UegParams& prm, const int* k_int_dev, const int* index_m
         HIP_CHECK(copy_async(tabs + prm.tab_len, prm.tab_array, sizeof(double) * prm.tab_len, hipMemcpyHostToDevice, st));
         u.tab_s = tabs; u.tab_a = tabs + prm.tab_len; u.tab_len = prm.tab_len;
     }
-    HIP_CHECK(set_async(V_dev, 0, sizeof(double) * n * n * n * n, st));
     std::vector<int> kint(3 * n);
     HIP_CHECK(copy_async(kint.data(), k_int_dev, sizeof(int) * 3 * n, hipMemcpyDeviceToHost, st));
     wait_idle(st);
@@ -407,15 +441,36 @@ void ueg_two_body(const UegParams& prm, const int* k_int_dev, const int* index_m
             E = (double*)dmalloc(sizeof(double) * n * n);
             launch_kernel(ueg_effective_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st, u, k_int_dev, E);
         }
-        const long total = n * n * n;
-        launch_kernel(ueg_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, u, k_int_dev,
-                           index_map_dev, umat, uidx, E, V_dev);
+        fill(u, umat, uidx, E);
         wait_idle(st);
     } catch (...) {
         dfree(umat); dfree(E); dfree(dk_dev); dfree(uidx); dfree(dint_dev); dfree(tabs);
         throw;
     }
     dfree(umat); dfree(E); dfree(dk_dev); dfree(uidx); dfree(dint_dev); dfree(tabs);
+}
+
+void ueg_two_body(const UegParams& prm, const int* k_int_dev, const int* index_map_dev, double* V_dev, stream_t s) {
+    hipStream_t st = (hipStream_t)s;
+    const long n = prm.n_p;
+    HIP_CHECK(set_async(V_dev, 0, sizeof(double) * n * n * n * n, st));
+    ueg_prepare_and_fill(prm, k_int_dev, st, [&](const UegK& u, const double* umat, const int* uidx, const double* E) {
+        const long total = n * n * n;
+        launch_kernel(ueg_scatter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, u, k_int_dev, index_map_dev,
+                      umat, uidx, E, V_dev);
+    });
+}
+
+void ueg_two_body_list(const UegParams& prm, const int* k_int_dev, const int* pqrs_dev, int64_t count, double* out_dev, stream_t s) {
+    if (count < 0) throw std::runtime_error("ueg: negative list length");
+    if (count == 0) return;
+    if (!k_int_dev || !pqrs_dev || !out_dev) throw std::runtime_error("ueg: null argument");
+    if ((count + 255) / 256 > 0x7fffffffL) throw std::runtime_error("ueg: list too long for one call");
+    hipStream_t st = (hipStream_t)s;
+    ueg_prepare_and_fill(prm, k_int_dev, st, [&](const UegK& u, const double* umat, const int* uidx, const double* E) {
+        launch_kernel(ueg_list_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, u, k_int_dev, umat, uidx, E,
+                      pqrs_dev, (long)count, out_dev);
+    });
 }
 
 }  // namespace dev

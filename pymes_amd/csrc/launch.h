@@ -1,4 +1,4 @@
-// The ordered host layer of the HIP units (kernels.hip, kernels_post.hip, kernels_integrals.hip).
+// The ordered host layer of the HIP units (kernels.hip, kernels_post.hip, kernels_integrals.hip, kernels_sector.hip).
 //
 // kernels.hip defers small launches in its phase queue.  Whatever is not recorded there -- a kernel launch of its own, a
 // copy, a synchronisation, a graph boundary -- goes through the wrappers below, which launch the open phase first.  Below

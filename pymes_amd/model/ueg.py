@@ -289,6 +289,86 @@ class UEG:
             if own:
                 ctx.close()
 
+    # ---- the same integrals sector by sector (pymes_amd/solver/ueg_cc.py): never an [n_p]^4 array -------------------
+    SECTOR_CHUNK = 1 << 23        # integrals per pymes_ueg_eval_2b_list call (16 bytes of index list each)
+
+    def sector_tables(self):
+        """The momentum-sector tables of this basis (pymes_amd.solver.sectors.SectorTables)."""
+        from pymes_amd.solver.sectors import SectorTables
+        if self.basis_fns is None:
+            raise ValueError("Basis functions not initialized!")
+        n_p = len(self.basis_fns) // 2
+        return SectorTables(np.array([self.basis_fns[2 * i].k for i in range(n_p)], dtype=np.int64), self.n_ele // 2)
+
+    def eval_2b_sectors(self, tables, correlator=None, is_rpa_approx=False, is_only_2b=False, is_effect_2b=False, ctx=None):
+        """The integral sectors of ``tables`` as ``SectorIntegrals`` (``ctx``: the context they live in; its own otherwise).
+        Same modes and correlators as ``eval_2b_integrals``; is_effect_2b comes out already symmetrised (ueg.py:509-513).
+        Momentum conservation is exact here: the few non-conserving elements the dense builder sets at some bases through
+        its flattened lookup (like the reference) do not exist on this path."""
+        from pymes_amd.solver.sectors import BLOCKS
+        from pymes_amd.solver.ueg_cc import SectorIntegrals, upload_raw
+        start_time = time.time()
+        if self.basis_fns is None:
+            raise ValueError("Basis functions not initialized!")
+        n_p = len(self.basis_fns) // 2
+        k_int = np.ascontiguousarray([self.basis_fns[2 * i].k for i in range(n_p)], dtype=np.int32)
+        if tables.n != n_p or tables.no != self.n_ele // 2 or not np.array_equal(tables.k_int, k_int):
+            raise ValueError("eval_2b_sectors: the tables do not belong to this basis")
+        mode = self._mode(correlator, dict(is_rpa_approx=is_rpa_approx, is_only_2b=is_only_2b, is_effect_2b=is_effect_2b))
+        kind, prm, tab_s, tab_a = 0, [0.0] * 4, None, None
+        if correlator is not None:
+            self.correlator = correlator
+            correlator(np.float64(1.0))          # fixes the correlator's k_cutoff / gamma defaults like its first call would
+            is_trunc = getattr(correlator, "__name__", "") == "trunc" and getattr(correlator, "__self__", None) is self
+            spec = None if is_trunc else self._correlator_spec(correlator)
+            if spec is not None:
+                kind, prm = spec[0], list(map(float, spec[1])) + [0.0] * (4 - len(spec[1]))
+            elif not is_trunc:
+                tab_s, tab_a = self._correlator_tables(correlator, 30)
+        own = ctx is None
+        if own:
+            ctx = Context(tables.no, tables.nv, device=self.device, workspace_bytes=1 << 20)
+        try:
+            if ctx.recording:
+                raise RuntimeError("eval_2b_sectors: the context is recording a launch graph")
+            ints = SectorIntegrals(ctx, tables, own_ctx=own)
+            pieces = []             # (name, first sector, end sector, items), in arena order
+            for name in ints.NAMES:
+                if name not in BLOCKS:
+                    pieces.append((name, 0, 0, ints.sizes[name]))
+                    continue
+                off, s0 = tables.block_offsets(name), 0
+                while s0 < len(off) - 1:        # as many whole sectors as fit the chunk (at least one)
+                    s1 = max(int(np.searchsorted(off, off[s0] + self.SECTOR_CHUNK, side="right")) - 1, s0 + 1)
+                    pieces.append((name, s0, s1, int(off[s1] - off[s0])))
+                    s0 = s1
+            done, prm_c = 0, (C.c_double * 4)(*prm)
+            while pieces:
+                batch, count = [pieces.pop(0)], 0
+                while pieces and sum(p[3] for p in batch) + pieces[0][3] <= self.SECTOR_CHUNK:
+                    batch.append(pieces.pop(0))
+                pqrs = np.concatenate([tables.block_pqrs(nm, s0, s1) for nm, s0, s1, _ in batch])
+                count = len(pqrs)
+                assert count == sum(p[3] for p in batch)
+                if count:
+                    lst = upload_raw(ctx, pqrs)
+                    ctx.lib.call("pymes_ueg_eval_2b_list", ctx.handle, n_p, self.n_ele, self.imax, mode, float(self.L),
+                                 float(self.k_cutoff or 0.0), float(self.gamma or 1.0), 30, kind, prm_c,
+                                 k_int.ctypes.data_as(C.c_void_p),
+                                 tab_s.ctypes.data_as(C.c_void_p) if tab_s is not None else None,
+                                 tab_a.ctypes.data_as(C.c_void_p) if tab_a is not None else None,
+                                 len(tab_a) if tab_a is not None else 0, C.c_void_p(lst.ptr), count,
+                                 C.c_void_p(ints.arena.ptr + 8 * done))
+                    lst.free()
+                done += count
+            assert done == ints.total
+            print_logging_info("{:.3f} s spent on ".format(time.time() - start_time) + __name__, level=1)
+            return ints
+        except BaseException:
+            if own:
+                ctx.close()
+            raise
+
     # ---- host mirrors of the per-element helpers (ueg.py:518-596) ----------------------------------
     def _occ_kp(self):
         return np.array([self.basis_fns[i * 2].kp for i in range(self.n_ele // 2)])

@@ -1,0 +1,288 @@
+"""Momentum-sector tables of a closed-shell Hamiltonian whose orbitals carry a conserved integer vector (the electron gas,
+with or without twist).  Host side, numpy only.
+
+Every integral and amplitude conserves the vector: V_pqrs != 0 only if k_p + k_q = k_r + k_s, and T_abij only if
+k_a + k_b = k_i + k_j.  The same ~ o^2 v non-zeros of T are held in three block-diagonal layouts:
+
+  pp       one sector per P in {k_i + k_j}: T^P[(a,b),(i,j)] = T_abij, rows VV_P (ordered virtual pairs with k_a + k_b = P),
+           columns OO_P, row-major; the sectors concatenated are the canonical compact amplitude vector
+  direct   one sector per q in {k_a - k_i}: D^q[(a,i),(b,j)] = T_abij, rows PH_q, columns PH_{-q}
+  crossed  C^q[(a,j),(b,i)] = T_abij, the same row and column lists (read as [(a,i),(b,j)] it is T_baij)
+
+A sector without virtual pairs (or a q whose -q does not occur: twisted bases) is legal and empty.  The integral blocks
+each product reads are described by `BLOCKS`; `block_pqrs` lists their (p,q,r,s) sector by sector.  `gemm_tasks` writes the
+task table of one sector-batched product (include/pymes_amd.h, pymes_sector_gemm)."""
+import numpy as np
+
+# name -> (row set, column set, (p,q,r,s) from the row pair (r0,r1) and the column pair (c0,c1); virtuals already
+# shifted by no).  Sets: "oo" / "vv" pairs of pp sector P; "ph" = PH_q, "ph-" = PH_{-q} of ph sector q.
+BLOCKS = {
+    "klij": ("oo", "oo", lambda r0, r1, c0, c1: (r0, r1, c0, c1)),        # I^P[(k,l),(i,j)]
+    "klcd": ("oo", "vv", lambda r0, r1, c0, c1: (r0, r1, c0, c1)),        # V_klcd^P[(k,l),(c,d)]
+    "abij": ("vv", "oo", lambda r0, r1, c0, c1: (r0, r1, c0, c1)),        # pp layout of V_abij
+    "abcd": ("vv", "vv", lambda r0, r1, c0, c1: (r0, r1, c0, c1)),        # the ladder block
+    "ed":   ("vv", "oo", lambda r0, r1, c0, c1: (c0, c1, r0, r1)),        # V_ijab at T_abij (direct energy)
+    "ex":   ("vv", "oo", lambda r0, r1, c0, c1: (c0, c1, r1, r0)),        # V_ijba at T_abij (exchange energy)
+    "w1":   ("ph", "ph-", lambda c, k, d, l: (k, l, c, d)),               # W1^q[(c,k),(d,l)] = V_klcd
+    "wx":   ("ph", "ph-", lambda d, k, c, l: (k, l, c, d)),               # Wx^q[(d,k),(c,l)] = V_klcd
+    "wa":   ("ph", "ph", lambda a, i, c, k: (k, a, i, c)),                # Wa^q[(a,i),(c,k)] = V_kaic (Wb = Wa^T)
+    "w2":   ("ph", "ph", lambda c, k, b, j: (k, b, c, j)),                # W2^q[(c,k),(b,j)] = V_kbcj
+}
+FOCK_LISTS = ("pipi", "piip")       # diagonal of hf.construct_hf_matrix: f_pp = h_pp + sum_i (2 V_pipi - V_piip)
+
+
+def _expand(nr, nc, s0, s1):
+    """Sector, local row and local column of every element of the row-major blocks nr[s] x nc[s], s0 <= s < s1."""
+    size = nr[s0:s1] * nc[s0:s1]
+    sec = np.repeat(np.arange(s0, s1), size)
+    start = np.concatenate(([0], np.cumsum(size)))[:-1]
+    local = np.arange(int(size.sum())) - np.repeat(start, size)
+    w = np.maximum(nc[sec], 1)
+    return sec, local // w, local % w
+
+
+class SectorTables:
+    def __init__(self, k_int, no):
+        k = np.ascontiguousarray(k_int, dtype=np.int64)
+        if k.ndim != 2 or k.shape[1] != 3:
+            raise ValueError("SectorTables: k_int must be [n, 3] integers")
+        n, no = k.shape[0], int(no)
+        if not 0 < no < n:
+            raise ValueError("SectorTables: need 0 < no < n")
+        if len(np.unique(k, axis=0)) != n:
+            raise ValueError("SectorTables: two orbitals carry the same vector")
+        self.k_int, self.no, self.nv, self.n = k, no, n - no, n
+        nv = self.nv
+        bound = 2 * int(np.abs(k).max()) + 1
+        side = 2 * bound + 1
+
+        def key(v):
+            return ((v[..., 0] + bound) * side + v[..., 1] + bound) * side + v[..., 2] + bound
+
+        def unkey(x):
+            return np.stack([x // (side * side) - bound, x // side % side - bound, x % side - bound], axis=-1)
+
+        ko, kv = k[:no], k[no:]
+        # ---- pp sectors: P in {k_i + k_j}
+        oo_key = key(ko[:, None, :] + ko[None, :, :]).reshape(-1)
+        self.P_keys = np.unique(oo_key)
+        self.P = unkey(self.P_keys)
+        nP = len(self.P_keys)
+        self.oo_pairs, self.oo_off, self.oo_sec, self.oo_pos = self._group(oo_key, no, nP)
+        self.vv_pairs, self.vv_off, self.vv_sec, self.vv_pos = self._group(key(kv[:, None, :] + kv[None, :, :]).reshape(-1), nv, nP)
+        self.n_oo, self.n_vv = np.diff(self.oo_off), np.diff(self.vv_off)
+        # ---- ph sectors: q in {k_a - k_i}
+        ph_key = key(kv[:, None, :] - ko[None, :, :]).reshape(-1)
+        self.q_keys = np.unique(ph_key)
+        self.q = unkey(self.q_keys)
+        nq = len(self.q_keys)
+        sec = np.searchsorted(self.q_keys, ph_key)
+        order = np.argsort(sec, kind="stable")
+        self.ph_pairs = np.stack([order // no, order % no], axis=1)             # (a, i), a counted from the first virtual
+        self.ph_off = np.concatenate(([0], np.cumsum(np.bincount(sec, minlength=nq))))
+        self.ph_row = np.empty(nv * no, dtype=np.int64)                          # (a, i) -> global row
+        self.ph_row[order] = np.arange(nv * no)
+        neg_key = key(-self.q)
+        pos = np.minimum(np.searchsorted(self.q_keys, neg_key), nq - 1)
+        self.neg = np.where(self.q_keys[pos] == neg_key, pos, -1)               # sector of -q, -1: it does not occur
+        self.n_ph = np.diff(self.ph_off)
+        self.n_hp = np.where(self.neg >= 0, self.n_ph[np.maximum(self.neg, 0)], 0)     # |PH_{-q}|
+        # ---- element offsets of the block families
+        self._sizes = {"oo": self.n_oo, "vv": self.n_vv, "ph": self.n_ph, "ph-": self.n_hp}
+        self._off = {}
+        self.pp_off = self.offsets("vv", "oo")
+        self.nnz = int(self.pp_off[-1])
+        self._maps()
+
+    def _group(self, pair_key, m, nP):
+        """Ordered pairs (x, y), x, y < m, grouped by the pp sector their key belongs to (pairs of other keys dropped)."""
+        pos = np.minimum(np.searchsorted(self.P_keys, pair_key), nP - 1)
+        sec = np.where(self.P_keys[pos] == pair_key, pos, -1)
+        keep = np.flatnonzero(sec >= 0)
+        order = keep[np.argsort(sec[keep], kind="stable")]
+        off = np.concatenate(([0], np.cumsum(np.bincount(sec[keep], minlength=nP))))
+        where = np.full(m * m, -1, dtype=np.int64)
+        where[order] = np.arange(len(order)) - off[sec[order]]
+        return np.stack([order // m, order % m], axis=1), off, sec, where
+
+    def offsets(self, rows, cols):
+        """Element offsets (len = sectors + 1) of the concatenated row-major blocks |rows_s| x |cols_s|."""
+        if (rows, cols) not in self._off:
+            self._off[rows, cols] = np.concatenate(([0], np.cumsum(self._sizes[rows] * self._sizes[cols]))).astype(np.int64)
+        return self._off[rows, cols]
+
+    def _pairs(self, kind, sec, local):
+        if kind == "oo":
+            return self.oo_pairs[self.oo_off[sec] + local]
+        if kind == "vv":
+            return self.vv_pairs[self.vv_off[sec] + local]
+        if kind == "ph-":
+            sec = self.neg[sec]
+        return self.ph_pairs[self.ph_off[sec] + local]
+
+    def _pp_index(self, a, b, i, j):
+        ab, ij = a * self.nv + b, i * self.no + j
+        sec = self.oo_sec[ij]
+        assert np.array_equal(sec, self.vv_sec[ab])
+        return self.pp_off[sec] + self.vv_pos[ab] * self.n_oo[sec] + self.oo_pos[ij]
+
+    def _maps(self):
+        """The gather maps between the layouts (int64, one entry per non-zero)."""
+        nq = len(self.q_keys)
+        self.d_off = self.offsets("ph", "ph-")
+        sec, lr, lc = _expand(self.n_ph, self.n_hp, 0, nq)
+        if len(sec) != self.nnz:
+            raise AssertionError("sector layouts disagree: pp holds %d elements, ph %d" % (self.nnz, len(sec)))
+        row, col = self._pairs("ph", sec, lr), self._pairs("ph-", sec, lc)
+        self.d_from_pp = self._pp_index(row[:, 0], col[:, 0], row[:, 1], col[:, 1])       # D^q[(a,i),(b,j)] = T_abij
+        self.c_from_pp = self._pp_index(row[:, 0], col[:, 0], col[:, 1], row[:, 1])       # C^q[(a,j),(b,i)] = T_abij
+        partner = self.d_off[self.neg[sec]] + lc * self.n_ph[sec] + lr                     # block -q, transposed
+        self.d_partner = partner
+        self.pp_to_d, self.pp_to_c = self._inverse(self.d_from_pp), self._inverse(self.c_from_pp)
+        self.pp_to_dT, self.pp_to_cT = partner[self.pp_to_d], partner[self.pp_to_c]       # Ex^T(1,0,3,2) at each pp element
+        a, b, i, j = self.abij()
+        self.pp_swap = self._pp_index(b, a, j, i)                                          # T_baji at each pp element
+        # rows of the direct layout: where each starts, how long it is, which (a, i) it belongs to
+        g = np.arange(self.nv * self.no)
+        s = np.searchsorted(self.ph_off, g, side="right") - 1
+        self.row_start = self.d_off[s] + (g - self.ph_off[s]) * self.n_hp[s]
+        self.row_len = self.n_hp[s].astype(np.int64)
+
+    def _inverse(self, perm):
+        inv = np.full(self.nnz, -1, dtype=np.int64)
+        inv[perm] = np.arange(self.nnz)
+        if len(perm) != self.nnz or (inv < 0).any():
+            raise AssertionError("sector layouts are not permutations of one another")
+        return inv
+
+    def abij(self):
+        """(a, b, i, j) of every element of the compact vector (a, b counted from the first virtual)."""
+        sec, lr, lc = _expand(self.n_vv, self.n_oo, 0, len(self.P_keys))
+        ab, ij = self._pairs("vv", sec, lr), self._pairs("oo", sec, lc)
+        return ab[:, 0], ab[:, 1], ij[:, 0], ij[:, 1]
+
+    # ---- integrals ---------------------------------------------------------------------------------------------
+    def n_sectors(self, name):
+        return len(self.P_keys) if BLOCKS[name][0] in ("oo", "vv") else len(self.q_keys)
+
+    def block_offsets(self, name):
+        return self.offsets(*BLOCKS[name][:2])
+
+    def block_pqrs(self, name, s0=0, s1=None):
+        """(p,q,r,s) (int32 [count, 4]) of the elements of block family `name`, sectors s0 <= s < s1, in storage order."""
+        if name in FOCK_LISTS:
+            p, i = np.repeat(np.arange(self.n), self.no), np.tile(np.arange(self.no), self.n)
+            return np.stack([p, i, p, i] if name == "pipi" else [p, i, i, p], axis=1).astype(np.int32)
+        rows, cols, spec = BLOCKS[name]
+        s1 = self.n_sectors(name) if s1 is None else s1
+        sec, lr, lc = _expand(self._sizes[rows], self._sizes[cols], s0, s1)
+        r, c = self._pairs(rows, sec, lr), self._pairs(cols, sec, lc)
+        shift = lambda kind: self.no if kind == "vv" else 0
+        if rows.startswith("ph"):
+            idx = spec(r[:, 0] + self.no, r[:, 1], c[:, 0] + self.no, c[:, 1])
+        else:
+            idx = spec(r[:, 0] + shift(rows), r[:, 1] + shift(rows), c[:, 0] + shift(cols), c[:, 1] + shift(cols))
+        return np.stack(idx, axis=1).astype(np.int32)
+
+    def conserving(self, pqrs):
+        k = self.k_int
+        return np.all(k[pqrs[:, 0]] + k[pqrs[:, 1]] == k[pqrs[:, 2]] + k[pqrs[:, 3]], axis=1)
+
+    # ---- amplitudes --------------------------------------------------------------------------------------------
+    def compact(self, dense, name="T2"):
+        """The compact vector of a dense [v,v,o,o] array; weight outside the support is refused."""
+        dense = np.asarray(dense)
+        if dense.shape != (self.nv, self.nv, self.no, self.no):
+            raise ValueError("%s: expected a [v,v,o,o] array of shape %s" % (name, ((self.nv,) * 2 + (self.no,) * 2,)))
+        idx = self.abij()
+        out = np.ascontiguousarray(dense[idx], dtype=np.float64)
+        if np.count_nonzero(dense) != np.count_nonzero(out):
+            raise ValueError("%s has weight outside the momentum-conserving support" % name)
+        return out
+
+    def to_dense(self, vec):
+        out = np.zeros((self.nv, self.nv, self.no, self.no))
+        out[self.abij()] = vec
+        return out
+
+    def denominators(self, eps):
+        """e_i + e_j - e_a - e_b at every element of the compact vector (eps: all n orbital energies)."""
+        a, b, i, j = self.abij()
+        eps = np.asarray(eps, dtype=np.float64)
+        return eps[i] + eps[j] - eps[self.no + a] - eps[self.no + b]
+
+    # ---- products ----------------------------------------------------------------------------------------------
+    def gemm_tasks(self, a, b, c, alpha=1.0, beta=0.0, trans_b=False):
+        """Task table of C^s = alpha A^s' B^s'' + beta C^s over all sectors.  a, b, c = (rows, cols, negated): the block
+        family of the operand as stored (before `trans_b`), and whether the operand of sector q is block -q."""
+        nsec = len(self.P_keys) if a[0] in ("oo", "vv") else len(self.q_keys)
+        ident = np.arange(nsec)
+
+        def view(op):
+            rows, cols, negated = op
+            src = self.neg if negated else ident
+            flip = {"ph": "ph-", "ph-": "ph"}
+            if negated:       # block -q of a family (rows, cols) has the sizes of (flip rows, flip cols) at q
+                rows, cols = flip[rows], flip[cols]
+            off = np.where(src >= 0, self.offsets(*op[:2])[np.maximum(src, 0)], 0)
+            return self._sizes[rows], self._sizes[cols], off
+
+        ar, ac, ao = view(a)
+        br, bc, bo = view(b)
+        cr, cc, co = view(c)
+        ldb = bc
+        if trans_b:
+            br, bc = bc, br
+        if not (np.array_equal(ar, cr) and np.array_equal(bc, cc) and np.array_equal(ac, br)):
+            raise AssertionError("gemm_tasks: the operand shapes do not chain")
+        return make_tasks(ar, bc, ac, ao, bo, co, ac, ldb, cc, alpha, beta, trans_b=trans_b)
+
+
+TASK_DTYPE = np.dtype([("m", "<i8"), ("n", "<i8"), ("k", "<i8"), ("a", "<i8"), ("b", "<i8"), ("c", "<i8"), ("lda", "<i8"),
+                       ("ldb", "<i8"), ("ldc", "<i8"), ("flags", "<i8"), ("tile0", "<i8"), ("alpha", "<f8"), ("beta", "<f8"),
+                       ("reserved", "<i8")])       # pymes_sector_task of include/pymes_amd.h
+TILE_M, TILE_N = 32, 16
+TRANS_A, TRANS_B = 1, 2
+
+
+def make_tasks(m, n, k, a, b, c, lda, ldb, ldc, alpha=1.0, beta=0.0, trans_a=False, trans_b=False):
+    """pymes_sector_task records (numpy structured array) with the tile prefix filled in; scalars broadcast."""
+    m = np.atleast_1d(np.asarray(m, dtype=np.int64))
+    t = np.zeros(len(m), dtype=TASK_DTYPE)
+    for name, val in (("m", m), ("n", n), ("k", k), ("a", a), ("b", b), ("c", c), ("lda", lda), ("ldb", ldb), ("ldc", ldc),
+                      ("alpha", alpha), ("beta", beta)):
+        t[name] = val
+    t["flags"] = np.asarray(trans_a, dtype=np.int64) * TRANS_A + np.asarray(trans_b, dtype=np.int64) * TRANS_B
+    tiles = -(-t["m"] // TILE_M) * -(-t["n"] // TILE_N)
+    t["tile0"] = np.concatenate(([0], np.cumsum(tiles)))[:-1]
+    return t
+
+
+def task_tiles(tasks):
+    return int((-(-tasks["m"] // TILE_M) * -(-tasks["n"] // TILE_N)).sum())
+
+
+def check_tasks(tasks, len_a, len_b, len_c):
+    """Every element a task reads or writes lies inside its arena (the kernel trusts the table)."""
+    t = tasks
+    if len(t) == 0:
+        return
+    if (t["m"] < 0).any() or (t["n"] < 0).any() or (t["k"] < 0).any() or (t["flags"] & ~3).any():
+        raise ValueError("sector_gemm: negative extent or unknown flag in the task table")
+    ta, tb = (t["flags"] & TRANS_A) != 0, (t["flags"] & TRANS_B) != 0
+    live = (t["m"] > 0) & (t["n"] > 0)
+
+    def span(rows, cols, ld, off, on):
+        on = on & (rows > 0) & (cols > 0)
+        if ((ld < cols) & on).any() or ((off < 0) & on).any():
+            raise ValueError("sector_gemm: leading dimension below the row length, or a negative offset")
+        return np.where(on, off + (rows - 1) * ld + cols, 0)
+
+    ends = (span(np.where(ta, t["k"], t["m"]), np.where(ta, t["m"], t["k"]), t["lda"], t["a"], live),
+            span(np.where(tb, t["n"], t["k"]), np.where(tb, t["k"], t["n"]), t["ldb"], t["b"], live),
+            span(t["m"], t["n"], t["ldc"], t["c"], live))
+    for end, cap, nm in zip(ends, (len_a, len_b, len_c), "ABC"):
+        if end.max() > cap:
+            raise ValueError("sector_gemm: a task reaches past the end of operand %s" % nm)
+    if task_tiles(t) > 0x7fffffff:
+        raise ValueError("sector_gemm: too many tiles for one launch")

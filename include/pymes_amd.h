@@ -622,6 +622,27 @@ int pymes_sector_xdiag(pymes_ctx* ctx, const double* Tt_dev, const double* W1_de
 /* dt = r / (den + shift), t_out = t_in + dt over n elements (t_in_dev NULL: t_out = dt, the MP2 start; dt_dev NULL: not kept) */
 int pymes_sector_update(pymes_ctx* ctx, double* t_out_dev, double* dt_dev, const double* t_in_dev, const double* r_dev,
                         const double* den_dev, double shift, int64_t n);
+/* Momentum-blocked (T) (pymes_amd/solver/ueg_cc.py, sector_triples_energy): *e_out_host = sum of m_ijk S_ijk over
+ * the unique occupied triples [t_begin, t_end) in the order of pymes_ccsd_t (i ascending, j <= i, k <= j,
+ * t = i(i+1)(i+2)/6 + j(j+1)/2 + k), for amplitudes without singles.  Momentum conservation leaves one term in each sum of
+ * w_ijk, so the operands come with their implied index left out (sectors.TriplesTables), virtuals counted from no:
+ *   Vv[i,a,b] = V[i,f*,a,b] [o,v,v]   Vo[i,j,a] = V[i,j,a,m*] [o,o,v]   Tc[i,j,a] = T[a,b*,i,j] [o,o,v]   m_of[i,j,a] = m* or -1
+ * with an exact 0 wherever the implied orbital does not exist (the kernel relies on it).  k_int_dev: int32 [no + nv, 3];
+ * orb_of_dev: the int32 lookup grid vector -> orbital (-1: none) over the box box_host = {lo[3], dims[3]}, row-major; a
+ * vector outside the box names no orbital.  With c the virtual of k_i + k_j + k_k - k_a - k_b (if any),
+ *   Wt[a,b] = w(ijk;abc) + w(ikj;acb) + w(jik;bac) + w(jki;bca) + w(kij;cab) + w(kji;cba),
+ *   w(xyz;pqr) = Vv[x,p,q] Tc[z,y,r] - (m = m_of[x,y,p]) >= 0 ? Vo[x,y,p] Tc[m,z,q] : 0,
+ *   S = 1/3 sum_{a,b: c} Wt[a,b] (4 Wt[a,b] + Wt[b,c] + Wt[c,a] - 2 Wt[c,b] - 2 Wt[a,c] - 2 Wt[b,a]) / (e_i + e_j + e_k - e_a - e_b - e_c).
+ * The range is worked off in batches of as many triples as ws_bytes hold, nv^2 + ceil(nv / 32)^2 + 1 doubles each (a workspace
+ * below one triple is refused); every slab element that is read is written in the same call.  No atomics: one partial per
+ * workgroup, added in index order; the value of a triple has the same bits for every batch size, range and repetition, and
+ * the sum adds the values in triple order, carrying the rounding error of every add along
+ * (Neumaier), so it is the exactly rounded sum of the values but for the last unit.  per_triple_dev (t_end - t_begin doubles) may be NULL.  The kernels trust m_of < no
+ * and orb_of < no + nv.  Synchronises; refused while a launch graph is being recorded. */
+int pymes_sector_triples(pymes_ctx* ctx, int no, int nv, const double* eps_dev, const int32_t* k_int_dev, const int32_t* orb_of_dev,
+                         const int32_t* box_host, const int32_t* m_of_dev, const double* Tc_dev, const double* Vv_dev,
+                         const double* Vo_dev, int64_t t_begin, int64_t t_end, double* ws_dev, int64_t ws_bytes,
+                         double* per_triple_dev, double* e_out_host);
 
 /* ---- vector helpers for DIIS (pymes/mixer/diis.py:65-103) and norms ----------------- */
 /* out_host[p] = sum_i x[p][i]*y[p][i], npairs <= 16, deterministic reduction (synchronises) */

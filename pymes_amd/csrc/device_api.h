@@ -552,5 +552,10 @@ void sector_xdiag(const double* Tt, const double* W1, const double* D, double* E
                   stream_t s);
 void sector_update(double* t_out, double* dt, const double* t_in, const double* r, const double* den, double shift, int64_t n,
                    stream_t s);
+// momentum-blocked (T) (include/pymes_amd.h, pymes_sector_triples): the sum of m_ijk S_ijk over the triples
+// [t_begin, t_end), in batches of as many v x v slabs as ws_bytes hold.  Drains the stream before it returns.
+double sector_triples(int no, int nv, const double* eps, const int32_t* k_int, const int32_t* orb_of, const int32_t* box_host,
+                      const int32_t* m_of, const double* Tc, const double* Vv, const double* Vo, int64_t t_begin, int64_t t_end,
+                      double* ws, int64_t ws_bytes, double* per_triple, stream_t s);
 
 }  // namespace dev

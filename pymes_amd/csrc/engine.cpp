@@ -923,4 +923,9 @@ __attribute__((weak)) void sector_xdiag(const double*, const double*, const doub
 __attribute__((weak)) void sector_update(double*, double*, const double*, const double*, const double*, double, int64_t, stream_t) {
     throw std::runtime_error("sector_update: not available in this backend");
 }
+__attribute__((weak)) double sector_triples(int, int, const double*, const int32_t*, const int32_t*, const int32_t*, const int32_t*,
+                                            const double*, const double*, const double*, int64_t, int64_t, double*, int64_t, double*,
+                                            stream_t) {
+    throw std::runtime_error("sector_triples: not available in this backend");
+}
 }  // namespace dev

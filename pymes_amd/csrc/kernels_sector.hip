@@ -1,10 +1,14 @@
 // Kernels of the momentum-sector CCD / DCD path (pymes_amd/solver/ueg_cc.py; DESIGN "Momentum sectors"): a ragged batched
-// fp64 product over a device-resident task table, the gathers between the three sector layouts, and the element-wise tails.
+// fp64 product over a device-resident task table, the gathers between the three sector layouts, and the element-wise tails;
+// and of the momentum-blocked (T) on the same path: the W slab, the energy partials and their ordered sum.
 // Included at the end of kernels.hip (one code object for the library), not compiled on its own.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
+#include <string>
+#include <vector>
 
 #include "../../include/pymes_amd.h"
 #include "device_api.h"
@@ -160,6 +164,175 @@ __global__ void sector_update_kernel(double* __restrict__ t_out, double* __restr
     }
 }
 
+// ---- momentum-blocked (T) (include/pymes_amd.h, pymes_sector_triples) ---------------------------------------------
+// Every operand has its implied index left out: Vv[i,a,b] = V[i,f*,a,b], Vo[i,j,a] = V[i,j,a,m*], Tc[i,j,a] = T[a,b*,i,j],
+// m_of[i,j,a] = m* or -1; a position whose implied orbital does not exist holds an exact 0.  For a triple (i,j,k) and a pair
+// (a,b) the third virtual c is the orbital with k_i + k_j + k_k - k_a - k_b, if there is one: W_ijk is a v x v slab Wt[a,b].
+struct TriplesBox { int lo[3], dim[3]; };
+constexpr int kTrTile = 32;          // a 32 x 32 tile of (a,b) per 256-thread workgroup: thread (ty, tx) keeps a = a0 + ty + 8 q, b = b0 + tx
+
+// t = i (i+1) (i+2) / 6 + j (j+1) / 2 + k, i >= j >= k: the order of pymes_ccsd_t
+__device__ __forceinline__ void triple_of(long t, int& i, int& j, int& k) {
+    int ii = 0;
+    while ((long)(ii + 1) * (ii + 2) * (ii + 3) / 6 <= t) ++ii;
+    const long r = t - (long)ii * (ii + 1) * (ii + 2) / 6;
+    int jj = 0;
+    while ((long)(jj + 1) * (jj + 2) / 2 <= r) ++jj;
+    i = ii;
+    j = jj;
+    k = (int)(r - (long)jj * (jj + 1) / 2);
+}
+// the orbital that carries (x,y,z), -1 if none: every axis is checked against the box, nothing is wrapped into it
+__device__ __forceinline__ int triples_orb(const int* __restrict__ orb_of, const TriplesBox& bx, int x, int y, int z) {
+    x -= bx.lo[0];
+    y -= bx.lo[1];
+    z -= bx.lo[2];
+    if (x < 0 || x >= bx.dim[0] || y < 0 || y >= bx.dim[1] || z < 0 || z >= bx.dim[2]) return -1;
+    return orb_of[((long)x * bx.dim[1] + y) * bx.dim[2] + z];
+}
+// w(xyz;pqr) = Vv[x,p,q] Tc[z,y,r] - Vo[x,y,p] Tc[m_of[x,y,p],z,q]; `vv` = Vv[x,p,q], read by the caller
+__device__ __forceinline__ double triples_w(double vv, int x, int y, int z, int p, int q, int r, int no, long v,
+                                            const int* __restrict__ m_of, const double* __restrict__ Tc,
+                                            const double* __restrict__ Vo) {
+    const long xyp = ((long)x * no + y) * v + p;
+    const int m = m_of[xyp];
+    double w = vv * Tc[((long)z * no + y) * v + r];
+    if (m >= 0) w = fma(-Vo[xyp], Tc[((long)m * no + z) * v + q], w);
+    return w;
+}
+// the 32 x 32 tile X[b0 .., a0 ..] of a row-major v x v slab into LDS, read along the contiguous index: tr[b - b0][a - a0]
+__device__ __forceinline__ void triples_stage(double (*tr)[kTrTile + 1], const double* __restrict__ X, int nv, int a0, int b0,
+                                              int tx, int ty) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int bb = b0 + ty + 8 * q, aa = a0 + tx;
+        tr[ty + 8 * q][tx] = (bb < nv && aa < nv) ? X[(long)bb * nv + aa] : 0.0;
+    }
+    __syncthreads();
+}
+
+// Wt[a,b] of the triple t0 + blockIdx.y: the twelve products in the order of the formula, 0 where c is no virtual.  Every
+// element of the slab is written here.  Global reads along b (Vv[i,a,b], Tc[.,.,b], the store) are contiguous; Vv[j,b,a]
+// comes through the transposed LDS tile; what is indexed by c is a gather inside rows that the L2 holds.
+__global__ void __launch_bounds__(256) sector_triples_w_kernel(int no, int nv, const int* __restrict__ k_int,
+                                                               const int* __restrict__ orb_of, TriplesBox bx,
+                                                               const int* __restrict__ m_of, const double* __restrict__ Tc,
+                                                               const double* __restrict__ Vv, const double* __restrict__ Vo,
+                                                               long t0, double* __restrict__ Wt) {
+    __shared__ double tr[kTrTile][kTrTile + 1];
+    int i, j, k;
+    triple_of(t0 + blockIdx.y, i, j, k);
+    const int tiles_b = (nv + kTrTile - 1) / kTrTile;
+    const int a0 = (blockIdx.x / tiles_b) * kTrTile, b0 = (blockIdx.x % tiles_b) * kTrTile;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const long v = nv, vv = v * v;
+    const double* __restrict__ Vi = Vv + i * vv;
+    const double* __restrict__ Vj = Vv + j * vv;
+    const double* __restrict__ Vk = Vv + k * vv;
+    triples_stage(tr, Vj, nv, a0, b0, tx, ty);
+    const int b = b0 + tx;
+    if (b >= nv) return;
+    int K[3], kb[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        K[d] = k_int[3 * i + d] + k_int[3 * j + d] + k_int[3 * k + d];
+        kb[d] = k_int[3 * (no + b) + d];
+    }
+    double* __restrict__ W = Wt + (long)blockIdx.y * vv;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int a = a0 + ty + 8 * q;
+        if (a >= nv) continue;
+        const int* ka = k_int + 3 * (no + a);
+        const int c = triples_orb(orb_of, bx, K[0] - ka[0] - kb[0], K[1] - ka[1] - kb[1], K[2] - ka[2] - kb[2]) - no;
+        double w = 0.0;
+        if (c >= 0) {
+            w = triples_w(Vi[a * v + b], i, j, k, a, b, c, no, v, m_of, Tc, Vo);                 // w(ijk;abc)
+            w += triples_w(Vi[a * v + c], i, k, j, a, c, b, no, v, m_of, Tc, Vo);                // w(ikj;acb)
+            w += triples_w(tr[tx][ty + 8 * q], j, i, k, b, a, c, no, v, m_of, Tc, Vo);           // w(jik;bac)
+            w += triples_w(Vj[b * v + c], j, k, i, b, c, a, no, v, m_of, Tc, Vo);                // w(jki;bca)
+            w += triples_w(Vk[c * v + a], k, i, j, c, a, b, no, v, m_of, Tc, Vo);                // w(kij;cab)
+            w += triples_w(Vk[c * v + b], k, j, i, c, b, a, no, v, m_of, Tc, Vo);                // w(kji;cba)
+        }
+        W[a * v + b] = w;
+    }
+}
+
+// One partial per workgroup: sum over the tile's (a,b) with a virtual c of
+// Wt[a,b] (4 Wt[a,b] + Wt[b,c] + Wt[c,a] - 2 Wt[c,b] - 2 Wt[a,c] - 2 Wt[b,a]) / (e_i + e_j + e_k - e_a - e_b - e_c),
+// each thread over its four elements in ascending a, then a fixed tree over the 256 threads.
+__global__ void __launch_bounds__(256) sector_triples_e_kernel(int no, int nv, const double* __restrict__ eps,
+                                                               const int* __restrict__ k_int, const int* __restrict__ orb_of,
+                                                               TriplesBox bx, long t0, const double* __restrict__ Wt,
+                                                               double* __restrict__ partial) {
+    __shared__ double tr[kTrTile][kTrTile + 1];
+    __shared__ double red[256];
+    int i, j, k;
+    triple_of(t0 + blockIdx.y, i, j, k);
+    const int tiles_b = (nv + kTrTile - 1) / kTrTile;
+    const int a0 = (blockIdx.x / tiles_b) * kTrTile, b0 = (blockIdx.x % tiles_b) * kTrTile;
+    const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
+    const long v = nv;
+    const double* __restrict__ W = Wt + (long)blockIdx.y * v * v;
+    triples_stage(tr, W, nv, a0, b0, tx, ty);
+    const int b = b0 + tx;
+    double acc = 0.0;
+    if (b < nv) {
+        int K[3], kb[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            K[d] = k_int[3 * i + d] + k_int[3 * j + d] + k_int[3 * k + d];
+            kb[d] = k_int[3 * (no + b) + d];
+        }
+        const double eo = eps[i] + eps[j] + eps[k];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int a = a0 + ty + 8 * q;
+            if (a >= nv) continue;
+            const int* ka = k_int + 3 * (no + a);
+            const int c = triples_orb(orb_of, bx, K[0] - ka[0] - kb[0], K[1] - ka[1] - kb[1], K[2] - ka[2] - kb[2]) - no;
+            if (c < 0) continue;
+            const double wab = W[a * v + b];
+            const double r = 4.0 * wab + W[b * v + c] + W[c * v + a] - 2.0 * W[c * v + b] - 2.0 * W[a * v + c]
+                             - 2.0 * tr[tx][ty + 8 * q];
+            acc += wab * r / (eo - eps[no + a] - eps[no + b] - eps[no + c]);
+        }
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) partial[(long)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+}
+
+// per[t] = m_ijk S / 3, S the partials of triple t0 + t added in index order: one workgroup per triple brings 256 partials
+// at a time into LDS (one contiguous read), and its first thread adds them one after the other
+__global__ void __launch_bounds__(256) sector_triples_sum_kernel(const double* __restrict__ partial, long ntiles, long t0,
+                                                                 double* __restrict__ per, double* __restrict__ out) {
+    __shared__ double buf[256];
+    const int t = blockIdx.x, tid = threadIdx.x;
+    const double* __restrict__ p = partial + t * ntiles;
+    double s = 0.0;
+    for (long q0 = 0; q0 < ntiles; q0 += 256) {
+        buf[tid] = q0 + tid < ntiles ? p[q0 + tid] : 0.0;
+        __syncthreads();
+        if (tid == 0) {
+            const int n = (int)(ntiles - q0 < 256 ? ntiles - q0 : 256);
+            for (int r = 0; r < n; ++r) s += buf[r];
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    int i, j, k;
+    triple_of(t0 + t, i, j, k);
+    const double m = (i == j && j == k) ? 1.0 : (i == j || j == k) ? 3.0 : 6.0;
+    const double val = m * (s / 3.0);
+    per[t] = val;
+    if (out) out[t] = val;
+}
+
 }  // namespace
 
 namespace dev {
@@ -207,6 +380,58 @@ void sector_update(double* t_out, double* dt, const double* t_in, const double* 
     if (n == 0) return;
     if (!t_out || !r || !den) throw std::runtime_error("sector_update: null argument");
     launch_kernel(sector_update_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, t_out, dt, t_in, r, den, shift, (long)n);
+}
+
+double sector_triples(int no, int nv, const double* eps, const int32_t* k_int, const int32_t* orb_of, const int32_t* box_host,
+                      const int32_t* m_of, const double* Tc, const double* Vv, const double* Vo, int64_t t_begin, int64_t t_end,
+                      double* ws, int64_t ws_bytes, double* per_triple, stream_t s) {
+    if (no < 1 || nv < 1 || nv > (1 << 20)) throw std::runtime_error("sector_triples: bad orbital counts");
+    if (!eps || !k_int || !orb_of || !box_host || !m_of || !Tc || !Vv || !Vo || !ws)
+        throw std::runtime_error("sector_triples: null argument");
+    const int64_t total = (int64_t)no * (no + 1) * (no + 2) / 6;
+    if (t_begin < 0 || t_end < t_begin || t_end > total)
+        throw std::runtime_error("sector_triples: triple range [" + std::to_string(t_begin) + ", " + std::to_string(t_end) +
+                                 ") outside [0, " + std::to_string(total) + "]");
+    TriplesBox bx;
+    int64_t points = 1;
+    for (int d = 0; d < 3; ++d) {
+        bx.lo[d] = box_host[d];
+        bx.dim[d] = box_host[3 + d];
+        if (bx.dim[d] < 1) throw std::runtime_error("sector_triples: empty lookup box");
+        points *= bx.dim[d];
+        if (points > 0x7fffffffL) throw std::runtime_error("sector_triples: the lookup box holds more than 2^31 points");
+    }
+    const int64_t tiles1 = (nv + kTrTile - 1) / kTrTile, ntiles = tiles1 * tiles1, slab = (int64_t)nv * nv;
+    const int64_t each = slab + ntiles + 1;                   // per triple: the slab, one partial per tile, the value
+    const int64_t fit = ws_bytes / 8 / each;
+    if (fit < 1) throw std::runtime_error("sector_triples: the workspace does not hold one triple (" + std::to_string(8 * each) +
+                                          " bytes)");
+    const int64_t nb = std::min<int64_t>(fit, 65535);         // triples per batch: one grid row each
+    double* Wt = ws;
+    double* partial = ws + nb * slab;
+    double* per = partial + nb * ntiles;
+    hipStream_t st = (hipStream_t)s;
+    std::vector<double> host((size_t)std::min<int64_t>(nb, std::max<int64_t>(t_end - t_begin, 1)));
+    // the values are added in triple order with the rounding error of every add carried along (Neumaier): thousands of
+    // terms of one sign would otherwise lose more than the values themselves are good for.  volatile: no reassociation.
+    volatile double sum = 0.0, carry = 0.0;
+    for (int64_t t0 = t_begin; t0 < t_end; t0 += nb) {
+        const int n = (int)std::min<int64_t>(nb, t_end - t0);
+        const dim3 grid((unsigned)ntiles, (unsigned)n);
+        launch_kernel(sector_triples_w_kernel, grid, dim3(256), 0, st, no, nv, k_int, orb_of, bx, m_of, Tc, Vv, Vo, (long)t0, Wt);
+        launch_kernel(sector_triples_e_kernel, grid, dim3(256), 0, st, no, nv, eps, k_int, orb_of, bx, (long)t0, (const double*)Wt,
+                      partial);
+        launch_kernel(sector_triples_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, (const double*)partial, (long)ntiles,
+                      (long)t0, per, per_triple ? per_triple + (t0 - t_begin) : (double*)nullptr);
+        HIP_CHECK(copy_async(host.data(), per, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        wait_idle(st);
+        for (int q = 0; q < n; ++q) {                         // in triple order, whatever the batch size
+            const double x = host[q], s = sum + x;
+            carry += std::fabs(sum) >= std::fabs(x) ? (sum - s) + x : (x - s) + sum;
+            sum = s;
+        }
+    }
+    return sum + carry;
 }
 
 }  // namespace dev

@@ -300,6 +300,31 @@ class UEG:
         n_p = len(self.basis_fns) // 2
         return SectorTables(np.array([self.basis_fns[2 * i].k for i in range(n_p)], dtype=np.int64), self.n_ele // 2)
 
+    def _list_evaluator(self, k_int, correlator, flags):
+        """``pymes_ueg_eval_2b_list`` with this basis and correlator bound: f(ctx, pqrs_ptr, count, out_ptr)."""
+        n_p = len(k_int)
+        mode = self._mode(correlator, flags)
+        kind, prm, tab_s, tab_a = 0, [0.0] * 4, None, None
+        if correlator is not None:
+            self.correlator = correlator
+            correlator(np.float64(1.0))          # fixes the correlator's k_cutoff / gamma defaults like its first call would
+            is_trunc = getattr(correlator, "__name__", "") == "trunc" and getattr(correlator, "__self__", None) is self
+            spec = None if is_trunc else self._correlator_spec(correlator)
+            if spec is not None:
+                kind, prm = spec[0], list(map(float, spec[1])) + [0.0] * (4 - len(spec[1]))
+            elif not is_trunc:
+                tab_s, tab_a = self._correlator_tables(correlator, 30)
+        prm_c = (C.c_double * 4)(*prm)
+
+        def eval_list(ctx, pqrs_ptr, count, out_ptr):
+            ctx.lib.call("pymes_ueg_eval_2b_list", ctx.handle, n_p, self.n_ele, self.imax, mode, float(self.L),
+                         float(self.k_cutoff or 0.0), float(self.gamma or 1.0), 30, kind, prm_c,
+                         k_int.ctypes.data_as(C.c_void_p),
+                         tab_s.ctypes.data_as(C.c_void_p) if tab_s is not None else None,
+                         tab_a.ctypes.data_as(C.c_void_p) if tab_a is not None else None,
+                         len(tab_a) if tab_a is not None else 0, C.c_void_p(pqrs_ptr), count, C.c_void_p(out_ptr))
+        return eval_list
+
     def eval_2b_sectors(self, tables, correlator=None, is_rpa_approx=False, is_only_2b=False, is_effect_2b=False, ctx=None):
         """The integral sectors of ``tables`` as ``SectorIntegrals`` (``ctx``: the context they live in; its own otherwise).
         Same modes and correlators as ``eval_2b_integrals``; is_effect_2b comes out already symmetrised (ueg.py:509-513).
@@ -314,17 +339,8 @@ class UEG:
         k_int = np.ascontiguousarray([self.basis_fns[2 * i].k for i in range(n_p)], dtype=np.int32)
         if tables.n != n_p or tables.no != self.n_ele // 2 or not np.array_equal(tables.k_int, k_int):
             raise ValueError("eval_2b_sectors: the tables do not belong to this basis")
-        mode = self._mode(correlator, dict(is_rpa_approx=is_rpa_approx, is_only_2b=is_only_2b, is_effect_2b=is_effect_2b))
-        kind, prm, tab_s, tab_a = 0, [0.0] * 4, None, None
-        if correlator is not None:
-            self.correlator = correlator
-            correlator(np.float64(1.0))          # fixes the correlator's k_cutoff / gamma defaults like its first call would
-            is_trunc = getattr(correlator, "__name__", "") == "trunc" and getattr(correlator, "__self__", None) is self
-            spec = None if is_trunc else self._correlator_spec(correlator)
-            if spec is not None:
-                kind, prm = spec[0], list(map(float, spec[1])) + [0.0] * (4 - len(spec[1]))
-            elif not is_trunc:
-                tab_s, tab_a = self._correlator_tables(correlator, 30)
+        eval_list = self._list_evaluator(k_int, correlator, dict(is_rpa_approx=is_rpa_approx, is_only_2b=is_only_2b,
+                                                                 is_effect_2b=is_effect_2b))
         own = ctx is None
         if own:
             ctx = Context(tables.no, tables.nv, device=self.device, workspace_bytes=1 << 20)
@@ -342,7 +358,7 @@ class UEG:
                     s1 = max(int(np.searchsorted(off, off[s0] + self.SECTOR_CHUNK, side="right")) - 1, s0 + 1)
                     pieces.append((name, s0, s1, int(off[s1] - off[s0])))
                     s0 = s1
-            done, prm_c = 0, (C.c_double * 4)(*prm)
+            done = 0
             while pieces:
                 batch, count = [pieces.pop(0)], 0
                 while pieces and sum(p[3] for p in batch) + pieces[0][3] <= self.SECTOR_CHUNK:
@@ -352,18 +368,59 @@ class UEG:
                 assert count == sum(p[3] for p in batch)
                 if count:
                     lst = upload_raw(ctx, pqrs)
-                    ctx.lib.call("pymes_ueg_eval_2b_list", ctx.handle, n_p, self.n_ele, self.imax, mode, float(self.L),
-                                 float(self.k_cutoff or 0.0), float(self.gamma or 1.0), 30, kind, prm_c,
-                                 k_int.ctypes.data_as(C.c_void_p),
-                                 tab_s.ctypes.data_as(C.c_void_p) if tab_s is not None else None,
-                                 tab_a.ctypes.data_as(C.c_void_p) if tab_a is not None else None,
-                                 len(tab_a) if tab_a is not None else 0, C.c_void_p(lst.ptr), count,
-                                 C.c_void_p(ints.arena.ptr + 8 * done))
+                    eval_list(ctx, lst.ptr, count, ints.arena.ptr + 8 * done)
                     lst.free()
                 done += count
             assert done == ints.total
             print_logging_info("{:.3f} s spent on ".format(time.time() - start_time) + __name__, level=1)
             return ints
+        except BaseException:
+            if own:
+                ctx.close()
+            raise
+
+    def eval_2b_triples(self, tables, correlator=None, is_rpa_approx=False, is_only_2b=False, is_effect_2b=False, ctx=None):
+        """The two integral families of the momentum-blocked (T), ``SectorTriplesIntegrals`` (Vv[i,a,b] = V[i,f*,a,b] and
+        Vo[i,j,a] = V[i,j,a,m*]; pymes_amd.solver.ueg_cc), for the ``SectorTables`` (or ``TriplesTables``) of this
+        basis.  Modes, correlators and ``ctx`` as ``eval_2b_sectors``.  The lists are evaluated in chunks of SECTOR_CHUNK
+        positions: the entries whose implied orbital exists by ``pymes_ueg_eval_2b_list``, then placed; every other
+        position is an exact 0."""
+        from pymes_amd.solver.sectors import TriplesTables
+        from pymes_amd.solver.ueg_cc import SectorTriplesIntegrals, gather, upload_raw, view
+        start_time = time.time()
+        if self.basis_fns is None:
+            raise ValueError("Basis functions not initialized!")
+        ttab = tables if isinstance(tables, TriplesTables) else TriplesTables(tables)
+        n_p = len(self.basis_fns) // 2
+        k_int = np.ascontiguousarray([self.basis_fns[2 * i].k for i in range(n_p)], dtype=np.int32)
+        if ttab.n != n_p or ttab.no != self.n_ele // 2 or not np.array_equal(ttab.tables.k_int, k_int):
+            raise ValueError("eval_2b_triples: the tables do not belong to this basis")
+        eval_list = self._list_evaluator(k_int, correlator, dict(is_rpa_approx=is_rpa_approx, is_only_2b=is_only_2b,
+                                                                 is_effect_2b=is_effect_2b))
+        own = ctx is None
+        if own:
+            ctx = Context(ttab.no, ttab.nv, device=self.device, workspace_bytes=1 << 20)
+        try:
+            if ctx.recording:
+                raise RuntimeError("eval_2b_triples: the context is recording a launch graph")
+            tints = SectorTriplesIntegrals(ctx, ttab, own_ctx=own)
+            for family, dst in (("vv", tints.Vv), ("vo", tints.Vo)):
+                for e0 in range(0, ttab.sizes[family], self.SECTOR_CHUNK):
+                    e1 = min(e0 + self.SECTOR_CHUNK, ttab.sizes[family])
+                    pqrs, valid = ttab.list_pqrs(family, e0, e1)
+                    nvalid = int(valid.sum())
+                    vals = ctx.zeros((nvalid + 1,))                           # the last slot stays 0: what invalid positions read
+                    if nvalid:
+                        lst = upload_raw(ctx, pqrs[valid])
+                        eval_list(ctx, lst.ptr, nvalid, vals.ptr)
+                        lst.free()
+                    place = upload_raw(ctx, np.where(valid, np.cumsum(valid) - 1, nvalid).astype(np.int64))
+                    place.count = e1 - e0
+                    gather(ctx, view(dst, e0, e1 - e0), vals, place)
+                    place.free()
+                    vals.free()
+            print_logging_info("{:.3f} s spent on ".format(time.time() - start_time) + __name__, level=1)
+            return tints
         except BaseException:
             if own:
                 ctx.close()

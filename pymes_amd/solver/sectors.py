@@ -238,6 +238,82 @@ class SectorTables:
         return make_tasks(ar, bc, ac, ao, bo, co, ac, ldb, cc, alpha, beta, trans_b=trans_b)
 
 
+class TriplesTables:
+    """The implied-index tables of the momentum-blocked (T), from a `SectorTables`.  Host side, numpy only.
+
+    With k_p + k_q = k_r + k_s every sum of w_ijk[a,b,c] = sum_f V_iabc[i,f,a,b] T[c,f,k,j] - sum_m V_ijak[i,j,a,m] T[b,c,m,k]
+    has at most one term, so each operand is held with its implied index left out:
+
+      Vv[i,a,b] = V[i, f*, a, b]   f* the virtual with k_a + k_b - k_i        list family "vv", shape [o,v,v]
+      Vo[i,j,a] = V[i, j, a, m*]   m* the occupied with k_i + k_j - k_a       list family "vo", shape [o,o,v]; m_of = m*
+      Tc[i,j,a] = T[a, b*, i, j]   b* the virtual with k_i + k_j - k_a        `implied_map` into the compact pp vector
+
+    A position whose implied orbital does not exist holds an exact 0 (in m_of: -1).  `orb_of` is the dense lookup grid
+    vector -> orbital over the box [lo, lo + dims) of the orbitals' own vectors, -1 where no orbital sits; a vector outside
+    the box names no orbital and is never wrapped into it (`lookup` checks every axis)."""
+
+    FAMILIES = ("vv", "vo")
+
+    def __init__(self, tables):
+        if not isinstance(tables, SectorTables):
+            raise TypeError("TriplesTables: a SectorTables is needed")
+        self.tables = tables
+        k, no, nv = tables.k_int, tables.no, tables.nv
+        self.no, self.nv, self.n = no, nv, tables.n
+        self.lo = k.min(axis=0).astype(np.int64)
+        self.dims = (k.max(axis=0) - self.lo + 1).astype(np.int64)
+        if int(np.prod(self.dims)) > 0x7fffffff:
+            raise ValueError("TriplesTables: the box of the orbital vectors holds more than 2^31 points")
+        self.orb_of = np.full(tuple(self.dims), -1, dtype=np.int32)
+        rel = k - self.lo
+        self.orb_of[rel[:, 0], rel[:, 1], rel[:, 2]] = np.arange(tables.n, dtype=np.int32)
+        self.box = np.concatenate((self.lo, self.dims)).astype(np.int32)         # what the kernel takes: lo[3], dims[3]
+        ko, kv = k[:no], k[no:]
+        m = self.lookup(ko[:, None, None, :] + ko[None, :, None, :] - kv[None, None, :, :])
+        self.m_of = np.where(m < no, m, -1).astype(np.int32)                      # [o,o,v]: occupied or -1
+        b = self.b_of = np.where(m >= no, m - no, -1)                             # [o,o,v]: b* counted from the first virtual
+        ok = b >= 0
+        i, j, a = np.nonzero(ok)
+        self.implied_map = np.full((no, no, nv), tables.nnz, dtype=np.int64)      # invalid: the appended zero slot
+        self.implied_map[ok] = tables._pp_index(a, b[ok], i, j)
+        self.sizes = {"vv": no * nv * nv, "vo": no * no * nv}
+
+    def lookup(self, vec):
+        """Orbital index of every integer vector of `vec` [..., 3], -1 where there is none (outside the box included)."""
+        rel = np.asarray(vec, dtype=np.int64) - self.lo
+        inside = np.all((rel >= 0) & (rel < self.dims), axis=-1)
+        rel = np.where(inside[..., None], rel, 0)
+        return np.where(inside, self.orb_of[rel[..., 0], rel[..., 1], rel[..., 2]], -1).astype(np.int64)
+
+    def list_pqrs(self, family, e0=0, e1=None):
+        """((p,q,r,s) int32 [count, 4], valid bool [count]) of the positions e0 <= e < e1 of list family "vv" or "vo" in
+        storage order.  Where `valid` is False the implied orbital does not exist: the row then names orbital 0 in its place
+        and must not be evaluated (the stored value there is an exact 0)."""
+        no, nv, k = self.no, self.nv, self.tables.k_int
+        e1 = self.sizes[family] if e1 is None else e1
+        e = np.arange(e0, e1, dtype=np.int64)
+        if family == "vv":                      # Vv[i,a,b] = V[i, f*, a, b]
+            i, a, b = e // (nv * nv), e // nv % nv + no, e % nv + no
+            f = self.lookup(k[a] + k[b] - k[i])
+            valid = f >= no
+            idx = (i, np.where(valid, f, 0), a, b)
+        elif family == "vo":                    # Vo[i,j,a] = V[i, j, a, m*]
+            i, j, a = e // (no * nv), e // nv % no, e % nv + no
+            m = self.lookup(k[i] + k[j] - k[a])
+            valid = (m >= 0) & (m < no)
+            idx = (i, j, a, np.where(valid, m, 0))
+        else:
+            raise KeyError(family)
+        return np.stack(idx, axis=1).astype(np.int32), valid
+
+    def implied(self, T):
+        """Tc [o,o,v] of a compact pp vector."""
+        T = np.asarray(T, dtype=np.float64)
+        if T.shape != (self.tables.nnz,):
+            raise ValueError("TriplesTables.implied: a compact vector of %d elements is needed" % self.tables.nnz)
+        return np.append(T, 0.0)[self.implied_map]
+
+
 TASK_DTYPE = np.dtype([("m", "<i8"), ("n", "<i8"), ("k", "<i8"), ("a", "<i8"), ("b", "<i8"), ("c", "<i8"), ("lda", "<i8"),
                        ("ldb", "<i8"), ("ldc", "<i8"), ("flags", "<i8"), ("tile0", "<i8"), ("alpha", "<f8"), ("beta", "<f8"),
                        ("reserved", "<i8")])       # pymes_sector_task of include/pymes_amd.h

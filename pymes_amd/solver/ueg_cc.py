@@ -8,19 +8,23 @@ layouts are gathers, and the diagonal X_ac / X_ki terms, the update and the ener
 sectors"; the numpy restatement the tests compare with is tests/_sector_reference.py).  The dense path (``CCD``, ``CCSD``) is
 untouched."""
 import ctypes as C
+import os
 import time
 
 import numpy as np
 
 from pymes_amd import _lib
+from pymes_amd import dist as pdist
 from pymes_amd.device import Context, DeviceArray
 from pymes_amd.log import print_logging_info
 from pymes_amd.mixer import diis
 from pymes_amd.solver import sectors
 from pymes_amd.solver.ccd import quiet_collector
-from pymes_amd.solver.sectors import BLOCKS, FOCK_LISTS, SectorTables
+from pymes_amd.solver import ccsd_t
+from pymes_amd.solver.sectors import BLOCKS, FOCK_LISTS, SectorTables, TriplesTables
 
-__all__ = ["SectorTables", "SectorIntegrals", "SectorAmplitudes", "SectorCCD"]
+__all__ = ["SectorTables", "SectorIntegrals", "SectorAmplitudes", "SectorCCD", "TriplesTables", "SectorTriplesIntegrals",
+           "sector_triples_energy"]
 
 
 def upload_raw(ctx, host):
@@ -175,6 +179,134 @@ class SectorAmplitudes:
         return t.to_dense(self.get())
 
 
+class SectorTriplesIntegrals:
+    """The two integral families of the momentum-blocked (T) on the device (``UEG.eval_2b_triples``), with their
+    ``TriplesTables``:
+
+      Vv[i,a,b] = V[i, f*, a, b], shape [o,v,v], f* the virtual with k_a + k_b - k_i
+      Vo[i,j,a] = V[i, j, a, m*], shape [o,o,v], m* the occupied with k_i + k_j - k_a
+
+    Contract: a position whose implied orbital does not exist holds an exact 0.0 (never a NaN, never left unwritten); the
+    kernel multiplies it with the equally exact 0 of ``Tc`` there.  No ``+`` and no scaling (left out)."""
+
+    def __init__(self, ctx, ttab, own_ctx=False):
+        self.ctx, self.tables, self._own = ctx, ttab, own_ctx
+        self.Vv = ctx.empty((ttab.no, ttab.nv, ttab.nv))
+        self.Vo = ctx.empty((ttab.no, ttab.no, ttab.nv))
+        self._dev = None
+
+    @property
+    def nbytes(self):
+        return self.Vv.nbytes + self.Vo.nbytes
+
+    def device_tables(self):
+        """(k_int, orb_of, m_of as int32 device bytes; the implied map of ``Tc`` as an int64 gather map)"""
+        if self._dev is None:
+            t = self.tables
+            if t.m_of.max(initial=-1) >= t.no or t.orb_of.max() >= t.n or t.implied_map.min() < 0 or \
+                    t.implied_map.max() > t.tables.nnz:
+                raise AssertionError("triples tables: an index points outside its array")
+            i32 = lambda x: upload_raw(self.ctx, np.append(np.ascontiguousarray(x, dtype=np.int32).reshape(-1),
+                                                           np.zeros(x.size % 2, dtype=np.int32)))
+            imap = upload_raw(self.ctx, t.implied_map.reshape(-1))
+            imap.count = t.implied_map.size
+            self._dev = (i32(t.tables.k_int), i32(t.orb_of), i32(t.m_of), imap)
+        return self._dev
+
+    def close(self):
+        if self._own and self.ctx.handle:
+            self.ctx.close()
+
+
+TRIPLES_WS_ENV, TRIPLES_WS_DEFAULT = "PYMES_SECTOR_TRIPLES_BYTES", 1 << 30
+
+
+def triple_bytes(nv):
+    """Workspace bytes of one triple in ``pymes_sector_triples``: the v x v slab, one partial per 32 x 32 tile, the value."""
+    return 8 * (nv * nv + (-(-nv // 32)) ** 2 + 1)
+
+
+def _hermitian(ints, rtol=1e-12):
+    """V_klcd = V_cdkl, sector by sector: ``klcd``^P against ``abij``^P transposed."""
+    tab = ints.tables
+    sec, lr, lc = sectors._expand(tab.n_oo, tab.n_vv, 0, len(tab.P_keys))
+    kl, ab = ints["klcd"].get(), ints["abij"].get()
+    if not len(kl):
+        return True
+    return np.abs(kl - ab[tab.pp_off[sec] + lc * tab.n_oo[sec] + lr]).max() <= rtol * max(np.abs(ab).max(), 1e-300)
+
+
+def _check_triples(who, ints, tints):
+    """The refusals of the (T) inputs that need no amplitudes (``SectorCCD.solve`` makes them before it iterates)."""
+    if not isinstance(ints, SectorIntegrals):
+        raise TypeError(who + ": ints must be SectorIntegrals (UEG.eval_2b_sectors)")
+    if not isinstance(tints, SectorTriplesIntegrals):
+        raise TypeError(who + ": the triples integrals must be SectorTriplesIntegrals (UEG.eval_2b_triples)")
+    tab, other = ints.tables, tints.tables.tables
+    same = other is tab or (other.no == tab.no and np.array_equal(other.k_int, tab.k_int))
+    if not same or tints.ctx is not ints.ctx:
+        raise ValueError(who + ": the triples integrals belong to other tables or another context than the integrals")
+    if ints.ctx.recording:
+        raise RuntimeError(who + ": the context is recording a launch graph")
+    if not _hermitian(ints):
+        raise ValueError(who + ": the integrals are not Hermitian (V_pqrs = V_rspq fails between the klcd and abij sectors); "
+                         "(T) is not defined for transcorrelated integrals, and Lambda-(T) does not exist on sectors yet")
+
+
+def sector_triples_energy(eps, ints, tints, amps, triple_range=None, per_triple=False, workspace_bytes=None):
+    """E(T) of doubles amplitudes on the momentum sectors (singles vanish there, so CCD(T) is CCSD(T)): the sum of m_ijk S_ijk
+    of tests/_triples_reference.py by ``pymes_sector_triples``, never an array larger than ``tints``.
+
+    eps: the orbital energies (or a diagonal Fock matrix); ints: the ``SectorIntegrals``; tints: the
+    ``SectorTriplesIntegrals`` of the same tables and context (``UEG.eval_2b_triples``); amps: ``SectorAmplitudes``, a compact
+    vector or a dense [v,v,o,o] array with T_abij = T_baji.  ``triple_range=(begin, end)``: only those triples (the order of
+    ``pymes_ccsd_t``), no collective; otherwise all of them, split over the ranks by ``ccsd_t.rank_range`` and all-reduced
+    when ``torch.distributed`` runs one process per GPU.  The triples are worked off in batches of as many v x v slabs as
+    ``workspace_bytes`` hold (default: the environment's PYMES_SECTOR_TRIPLES_BYTES, else 1 GiB; at least one triple); the
+    value of a triple does not depend on it.  Returns the energy, or (energy, per-triple values of the range as a host
+    array) with ``per_triple=True``.  Refused: integrals without V_pqrs = V_rspq (transcorrelated ones)."""
+    who = "sector_triples_energy"
+    _check_triples(who, ints, tints)
+    tab, ctx, tt = ints.tables, ints.ctx, tints.tables
+    eps = np.asarray(eps, dtype=np.float64)
+    if eps.ndim == 2:
+        if np.count_nonzero(eps - np.diag(eps.diagonal())):
+            raise ValueError(who + ": the Fock matrix must be diagonal (it is for a momentum-conserving Hamiltonian)")
+        eps = eps.diagonal().copy()
+    if eps.shape != (tab.n,):
+        raise ValueError(who + ": %d orbital energies for %d orbitals" % (eps.size, tab.n))
+    vec = SectorCCD._compact(tab, amps)
+    if len(vec) and np.abs(vec - vec[tab.pp_swap]).max() > 1e-13 * max(np.abs(vec).max(), 1e-300):
+        raise ValueError(who + ": the amplitudes are not exchange-symmetric (T_abij = T_baji)")
+    no, nv = tab.no, tab.nv
+    lo, hi, reduce = ccsd_t._triple_chunk(no, triple_range)
+    if not 0 <= lo <= hi <= ccsd_t.n_triples(no):
+        raise ValueError(who + ": triple range [%d, %d) outside [0, %d]" % (lo, hi, ccsd_t.n_triples(no)))
+    if workspace_bytes is None:
+        workspace_bytes = int(os.environ.get(TRIPLES_WS_ENV, TRIPLES_WS_DEFAULT))
+    each = triple_bytes(nv)
+    ws_bytes = each * max(1, min(int(workspace_bytes) // each, max(hi - lo, 1)))
+    k_dev, orb_dev, m_dev, imap = tints.device_tables()
+    temps = [ctx.array(np.append(vec, 0.0)), ctx.empty((no, no, nv)), ctx.array(eps), ctx.empty((ws_bytes // 8,))]
+    src, Tc, eps_dev, ws = temps
+    out = ctx.empty((max(hi - lo, 1),)) if per_triple else None
+    e = C.c_double()
+    try:
+        gather(ctx, Tc, src, imap)
+        ctx.lib.call("pymes_sector_triples", ctx.handle, no, nv, C.c_void_p(eps_dev.ptr), C.c_void_p(k_dev.ptr),
+                     C.c_void_p(orb_dev.ptr), tt.box.ctypes.data_as(C.c_void_p), C.c_void_p(m_dev.ptr), C.c_void_p(Tc.ptr),
+                     C.c_void_p(tints.Vv.ptr), C.c_void_p(tints.Vo.ptr), int(lo), int(hi), C.c_void_p(ws.ptr), int(ws_bytes),
+                     C.c_void_p(out.ptr if out is not None else None), C.byref(e))
+        values = out.get()[:hi - lo] if out is not None else None
+    finally:
+        for t in temps + ([out] if out is not None else []):
+            t.free()
+    energy = float(e.value)
+    if reduce:
+        energy = float(pdist.allreduce_sum([energy])[0])
+    return (energy, values) if per_triple else energy
+
+
 class SectorCCD:
     def __init__(self, no, delta_e=1.e-8, is_dcd=False, is_diis=True, is_dr_ccd=False, is_bruekner=False, device=0):
         if is_dr_ccd or is_bruekner:
@@ -280,12 +412,15 @@ class SectorCCD:
                              "(V_pqrs = V_qpsr), which the sector residual needs")
         return eps
 
-    def solve(self, eps, ints, level_shift=0., amps=None, **kwargs):
+    def solve(self, eps, ints, level_shift=0., amps=None, triples=None, **kwargs):
         """The loop of ``CCD.solve`` (ccd.py:24-162) on the compact vector.  eps: the orbital energies (or a diagonal Fock
-        matrix); ints: ``SectorIntegrals``."""
+        matrix); ints: ``SectorIntegrals``.  ``triples``: the ``SectorTriplesIntegrals`` of the same tables; the result then
+        also holds "(t) e" (``sector_triples_energy`` of the final amplitudes) and "ccd(t) e"."""
         algo_name = "ccd.solve"
         time_ccd = time.time()
         eps = self._checks(eps, ints)
+        if triples is not None:
+            _check_triples("SectorCCD.solve", ints, triples)
         tab, ctx, no = ints.tables, ints.ctx, self.no
         max_iter, delta_e = kwargs.get("max_iter", self.max_iter), kwargs.get("delta_e", self.delta_e)
         with quiet_collector():
@@ -346,8 +481,13 @@ class SectorCCD:
             result = ctx.empty((n,)).copy_from(t2)       # (t2 itself goes back to the pool; the mixer may hold the rest)
             ctx.pool_put(t2)
             ctx.pool_put(r2)
-            return {"ccd e": e_ccd, "t2 amp": SectorAmplitudes(tab, result), "hole e": eps[:no], "particle e": eps[no:],
-                    "dE": dE}
+            out = {"ccd e": e_ccd, "t2 amp": SectorAmplitudes(tab, result), "hole e": eps[:no], "particle e": eps[no:],
+                   "dE": dE}
+            if triples is not None:
+                out["(t) e"] = sector_triples_energy(eps, ints, triples, out["t2 amp"])
+                out["ccd(t) e"] = e_ccd + out["(t) e"]
+                print_logging_info("(T) correction = {:.12f}".format(out["(t) e"]), level=1)
+            return out
 
     @staticmethod
     def _update(ctx, t_out, dt, t_in, r, den, shift):

@@ -156,6 +156,8 @@ SIGNATURES = {
     "pymes_sector_update": (C.c_int, [C.c_void_p] * 6 + [C.c_double, C.c_int64]),
     "pymes_sector_triples": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int64, C.c_int64, C.c_void_p,
                                                                                           C.c_int64, C.c_void_p, c_double_p]),
+    "pymes_sector_triples_lambda": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11 +
+                                    [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, c_double_p]),
     "pymes_hf_fock_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pymes_fcidump_header": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pymes_fcidump_read_host": (C.c_int, [C.c_char_p, C.c_int, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),

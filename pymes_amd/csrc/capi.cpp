@@ -976,6 +976,18 @@ int pymes_sector_triples(pymes_ctx* ctx, int no, int nv, const double* eps, cons
                                      e.stream);
     });
 }
+int pymes_sector_triples_lambda(pymes_ctx* ctx, int no, int nv, const double* eps, const int32_t* k_int, const int32_t* orb_of,
+                                const int32_t* box, const int32_t* m_of, const double* Tc, const double* Lc, const double* VvR,
+                                const double* VoR, const double* VvL, const double* VoL, int64_t t_begin, int64_t t_end,
+                                double* ws, int64_t ws_bytes, double* per_triple, double* e_out) {
+    return guarded([&] {
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("sector_triples_lambda while a launch graph is being recorded");
+        need(e_out, "e_out");
+        *e_out = dev::sector_triples_lambda(no, nv, eps, k_int, orb_of, box, m_of, Tc, Lc, VvR, VoR, VvL, VoL, t_begin, t_end, ws,
+                                            ws_bytes, per_triple, e.stream);
+    });
+}
 
 int pymes_dots(pymes_ctx* ctx, int npairs, const double* const* x, const double* const* y, int64_t n,
                double* out) {

@@ -557,5 +557,11 @@ void sector_update(double* t_out, double* dt, const double* t_in, const double* 
 double sector_triples(int no, int nv, const double* eps, const int32_t* k_int, const int32_t* orb_of, const int32_t* box_host,
                       const int32_t* m_of, const double* Tc, const double* Vv, const double* Vo, int64_t t_begin, int64_t t_end,
                       double* ws, int64_t ws_bytes, double* per_triple, stream_t s);
+// momentum-blocked Lambda-(T) (include/pymes_amd.h, pymes_sector_triples_lambda): the same with a right-hand and a
+// left-hand slab per triple.  Drains the stream before it returns.
+double sector_triples_lambda(int no, int nv, const double* eps, const int32_t* k_int, const int32_t* orb_of,
+                             const int32_t* box_host, const int32_t* m_of, const double* Tc, const double* Lc, const double* VvR,
+                             const double* VoR, const double* VvL, const double* VoL, int64_t t_begin, int64_t t_end, double* ws,
+                             int64_t ws_bytes, double* per_triple, stream_t s);
 
 }  // namespace dev

@@ -928,4 +928,10 @@ __attribute__((weak)) double sector_triples(int, int, const double*, const int32
                                             stream_t) {
     throw std::runtime_error("sector_triples: not available in this backend");
 }
+__attribute__((weak)) double sector_triples_lambda(int, int, const double*, const int32_t*, const int32_t*, const int32_t*,
+                                                   const int32_t*, const double*, const double*, const double*, const double*,
+                                                   const double*, const double*, int64_t, int64_t, double*, int64_t, double*,
+                                                   stream_t) {
+    throw std::runtime_error("sector_triples_lambda: not available in this backend");
+}
 }  // namespace dev

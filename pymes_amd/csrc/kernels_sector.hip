@@ -1,6 +1,7 @@
 // Kernels of the momentum-sector CCD / DCD path (pymes_amd/solver/ueg_cc.py; DESIGN "Momentum sectors"): a ragged batched
 // fp64 product over a device-resident task table, the gathers between the three sector layouts, and the element-wise tails;
-// and of the momentum-blocked (T) on the same path: the W slab, the energy partials and their ordered sum.
+// and of the momentum-blocked (T) on the same path: the W slab, the energy partials and their ordered sum;
+// and the two-slab energy kernel of the Lambda-(T).
 // Included at the end of kernels.hip (one code object for the library), not compiled on its own.
 #include <hip/hip_runtime.h>
 
@@ -307,6 +308,57 @@ __global__ void __launch_bounds__(256) sector_triples_e_kernel(int no, int nv, c
     if (tid == 0) partial[(long)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
 }
 
+// Lambda-(T): the same tiles, the same order of adds and the same tree as sector_triples_e_kernel on two slabs,
+// sum of WR[a,b] (4 WL[a,b] + WL[b,c] + WL[c,a] - 2 WL[c,b] - 2 WL[a,c] - 2 WL[b,a]) / D.  WR[a,b] and WL[a,b] are read along b;
+// WL[b,a] comes through the LDS transpose; the four reads indexed by c are gathers inside rows of WL that the L2 holds.
+__global__ void __launch_bounds__(256) sector_triples_lambda_e_kernel(int no, int nv, const double* __restrict__ eps,
+                                                                      const int* __restrict__ k_int,
+                                                                      const int* __restrict__ orb_of, TriplesBox bx, long t0,
+                                                                      const double* __restrict__ WRt,
+                                                                      const double* __restrict__ WLt,
+                                                                      double* __restrict__ partial) {
+    __shared__ double tr[kTrTile][kTrTile + 1];
+    __shared__ double red[256];
+    int i, j, k;
+    triple_of(t0 + blockIdx.y, i, j, k);
+    const int tiles_b = (nv + kTrTile - 1) / kTrTile;
+    const int a0 = (blockIdx.x / tiles_b) * kTrTile, b0 = (blockIdx.x % tiles_b) * kTrTile;
+    const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
+    const long v = nv;
+    const double* __restrict__ WR = WRt + (long)blockIdx.y * v * v;
+    const double* __restrict__ WL = WLt + (long)blockIdx.y * v * v;
+    triples_stage(tr, WL, nv, a0, b0, tx, ty);
+    const int b = b0 + tx;
+    double acc = 0.0;
+    if (b < nv) {
+        int K[3], kb[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            K[d] = k_int[3 * i + d] + k_int[3 * j + d] + k_int[3 * k + d];
+            kb[d] = k_int[3 * (no + b) + d];
+        }
+        const double eo = eps[i] + eps[j] + eps[k];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int a = a0 + ty + 8 * q;
+            if (a >= nv) continue;
+            const int* ka = k_int + 3 * (no + a);
+            const int c = triples_orb(orb_of, bx, K[0] - ka[0] - kb[0], K[1] - ka[1] - kb[1], K[2] - ka[2] - kb[2]) - no;
+            if (c < 0) continue;
+            const double r = 4.0 * WL[a * v + b] + WL[b * v + c] + WL[c * v + a] - 2.0 * WL[c * v + b] - 2.0 * WL[a * v + c]
+                             - 2.0 * tr[tx][ty + 8 * q];
+            acc += WR[a * v + b] * r / (eo - eps[no + a] - eps[no + b] - eps[no + c]);
+        }
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) partial[(long)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+}
+
 // per[t] = m_ijk S / 3, S the partials of triple t0 + t added in index order: one workgroup per triple brings 256 partials
 // at a time into LDS (one contiguous read), and its first thread adds them one after the other
 __global__ void __launch_bounds__(256) sector_triples_sum_kernel(const double* __restrict__ partial, long ntiles, long t0,
@@ -332,6 +384,37 @@ __global__ void __launch_bounds__(256) sector_triples_sum_kernel(const double* _
     per[t] = val;
     if (out) out[t] = val;
 }
+
+// the lookup box of a triples entry, checked: {lo[3], dims[3]} on the host
+TriplesBox triples_box(const std::string& who, const int32_t* box_host) {
+    TriplesBox bx;
+    int64_t points = 1;
+    for (int d = 0; d < 3; ++d) {
+        bx.lo[d] = box_host[d];
+        bx.dim[d] = box_host[3 + d];
+        if (bx.dim[d] < 1) throw std::runtime_error(who + ": empty lookup box");
+        points *= bx.dim[d];
+        if (points > 0x7fffffffL) throw std::runtime_error(who + ": the lookup box holds more than 2^31 points");
+    }
+    return bx;
+}
+void triples_range(const std::string& who, int no, int64_t t_begin, int64_t t_end) {
+    const int64_t total = (int64_t)no * (no + 1) * (no + 2) / 6;
+    if (t_begin < 0 || t_end < t_begin || t_end > total)
+        throw std::runtime_error(who + ": triple range [" + std::to_string(t_begin) + ", " + std::to_string(t_end) +
+                                 ") outside [0, " + std::to_string(total) + "]");
+}
+// the values are added in triple order with the rounding error of every add carried along (Neumaier): thousands of
+// terms of one sign would otherwise lose more than the values themselves are good for.  volatile: no reassociation.
+struct OrderedSum {
+    volatile double sum = 0.0, carry = 0.0;
+    void add(double x) {
+        const double s = sum + x;
+        carry += std::fabs(sum) >= std::fabs(x) ? (sum - s) + x : (x - s) + sum;
+        sum = s;
+    }
+    double value() const { return sum + carry; }
+};
 
 }  // namespace
 
@@ -388,19 +471,8 @@ double sector_triples(int no, int nv, const double* eps, const int32_t* k_int, c
     if (no < 1 || nv < 1 || nv > (1 << 20)) throw std::runtime_error("sector_triples: bad orbital counts");
     if (!eps || !k_int || !orb_of || !box_host || !m_of || !Tc || !Vv || !Vo || !ws)
         throw std::runtime_error("sector_triples: null argument");
-    const int64_t total = (int64_t)no * (no + 1) * (no + 2) / 6;
-    if (t_begin < 0 || t_end < t_begin || t_end > total)
-        throw std::runtime_error("sector_triples: triple range [" + std::to_string(t_begin) + ", " + std::to_string(t_end) +
-                                 ") outside [0, " + std::to_string(total) + "]");
-    TriplesBox bx;
-    int64_t points = 1;
-    for (int d = 0; d < 3; ++d) {
-        bx.lo[d] = box_host[d];
-        bx.dim[d] = box_host[3 + d];
-        if (bx.dim[d] < 1) throw std::runtime_error("sector_triples: empty lookup box");
-        points *= bx.dim[d];
-        if (points > 0x7fffffffL) throw std::runtime_error("sector_triples: the lookup box holds more than 2^31 points");
-    }
+    triples_range("sector_triples", no, t_begin, t_end);
+    const TriplesBox bx = triples_box("sector_triples", box_host);
     const int64_t tiles1 = (nv + kTrTile - 1) / kTrTile, ntiles = tiles1 * tiles1, slab = (int64_t)nv * nv;
     const int64_t each = slab + ntiles + 1;                   // per triple: the slab, one partial per tile, the value
     const int64_t fit = ws_bytes / 8 / each;
@@ -412,9 +484,7 @@ double sector_triples(int no, int nv, const double* eps, const int32_t* k_int, c
     double* per = partial + nb * ntiles;
     hipStream_t st = (hipStream_t)s;
     std::vector<double> host((size_t)std::min<int64_t>(nb, std::max<int64_t>(t_end - t_begin, 1)));
-    // the values are added in triple order with the rounding error of every add carried along (Neumaier): thousands of
-    // terms of one sign would otherwise lose more than the values themselves are good for.  volatile: no reassociation.
-    volatile double sum = 0.0, carry = 0.0;
+    OrderedSum total;
     for (int64_t t0 = t_begin; t0 < t_end; t0 += nb) {
         const int n = (int)std::min<int64_t>(nb, t_end - t0);
         const dim3 grid((unsigned)ntiles, (unsigned)n);
@@ -425,13 +495,51 @@ double sector_triples(int no, int nv, const double* eps, const int32_t* k_int, c
                       (long)t0, per, per_triple ? per_triple + (t0 - t_begin) : (double*)nullptr);
         HIP_CHECK(copy_async(host.data(), per, sizeof(double) * n, hipMemcpyDeviceToHost, st));
         wait_idle(st);
-        for (int q = 0; q < n; ++q) {                         // in triple order, whatever the batch size
-            const double x = host[q], s = sum + x;
-            carry += std::fabs(sum) >= std::fabs(x) ? (sum - s) + x : (x - s) + sum;
-            sum = s;
-        }
+        for (int q = 0; q < n; ++q) total.add(host[q]);       // in triple order, whatever the batch size
     }
-    return sum + carry;
+    return total.value();
+}
+
+// Lambda-(T): sector_triples with a right-hand slab WR (VvR, VoR, Tc) and a left-hand slab WL (VvL, VoL, Lc) per triple.  The
+// two slabs come from two launches of the unchanged sector_triples_w_kernel: a side index on blockIdx.z would put a select
+// of three base pointers in front of every gather of a kernel whose (T) timings are recorded, to save one launch (~10 us)
+// per batch of kernels that run for milliseconds.
+double sector_triples_lambda(int no, int nv, const double* eps, const int32_t* k_int, const int32_t* orb_of,
+                             const int32_t* box_host, const int32_t* m_of, const double* Tc, const double* Lc, const double* VvR,
+                             const double* VoR, const double* VvL, const double* VoL, int64_t t_begin, int64_t t_end, double* ws,
+                             int64_t ws_bytes, double* per_triple, stream_t s) {
+    if (no < 1 || nv < 1 || nv > (1 << 20)) throw std::runtime_error("sector_triples_lambda: bad orbital counts");
+    if (!eps || !k_int || !orb_of || !box_host || !m_of || !Tc || !Lc || !VvR || !VoR || !VvL || !VoL || !ws)
+        throw std::runtime_error("sector_triples_lambda: null argument");
+    triples_range("sector_triples_lambda", no, t_begin, t_end);
+    const TriplesBox bx = triples_box("sector_triples_lambda", box_host);
+    const int64_t tiles1 = (nv + kTrTile - 1) / kTrTile, ntiles = tiles1 * tiles1, slab = (int64_t)nv * nv;
+    const int64_t each = 2 * slab + ntiles + 1;               // per triple: two slabs, one partial per tile, the value
+    const int64_t fit = ws_bytes / 8 / each;
+    if (fit < 1) throw std::runtime_error("sector_triples_lambda: the workspace does not hold one triple (" +
+                                          std::to_string(8 * each) + " bytes)");
+    const int64_t nb = std::min<int64_t>(fit, 65535);         // triples per batch: one grid row each
+    double* WR = ws;
+    double* WL = ws + nb * slab;
+    double* partial = WL + nb * slab;
+    double* per = partial + nb * ntiles;
+    hipStream_t st = (hipStream_t)s;
+    std::vector<double> host((size_t)std::min<int64_t>(nb, std::max<int64_t>(t_end - t_begin, 1)));
+    OrderedSum total;
+    for (int64_t t0 = t_begin; t0 < t_end; t0 += nb) {
+        const int n = (int)std::min<int64_t>(nb, t_end - t0);
+        const dim3 grid((unsigned)ntiles, (unsigned)n);
+        launch_kernel(sector_triples_w_kernel, grid, dim3(256), 0, st, no, nv, k_int, orb_of, bx, m_of, Tc, VvR, VoR, (long)t0, WR);
+        launch_kernel(sector_triples_w_kernel, grid, dim3(256), 0, st, no, nv, k_int, orb_of, bx, m_of, Lc, VvL, VoL, (long)t0, WL);
+        launch_kernel(sector_triples_lambda_e_kernel, grid, dim3(256), 0, st, no, nv, eps, k_int, orb_of, bx, (long)t0,
+                      (const double*)WR, (const double*)WL, partial);
+        launch_kernel(sector_triples_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, (const double*)partial, (long)ntiles,
+                      (long)t0, per, per_triple ? per_triple + (t0 - t_begin) : (double*)nullptr);
+        HIP_CHECK(copy_async(host.data(), per, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        wait_idle(st);
+        for (int q = 0; q < n; ++q) total.add(host[q]);       // in triple order, whatever the batch size
+    }
+    return total.value();
 }
 
 }  // namespace dev

@@ -379,12 +379,14 @@ class UEG:
                 ctx.close()
             raise
 
-    def eval_2b_triples(self, tables, correlator=None, is_rpa_approx=False, is_only_2b=False, is_effect_2b=False, ctx=None):
+    def eval_2b_triples(self, tables, correlator=None, is_rpa_approx=False, is_only_2b=False, is_effect_2b=False, ctx=None,
+                        both_sides=False):
         """The two integral families of the momentum-blocked (T), ``SectorTriplesIntegrals`` (Vv[i,a,b] = V[i,f*,a,b] and
         Vo[i,j,a] = V[i,j,a,m*]; pymes_amd.solver.ueg_cc), for the ``SectorTables`` (or ``TriplesTables``) of this
         basis.  Modes, correlators and ``ctx`` as ``eval_2b_sectors``.  The lists are evaluated in chunks of SECTOR_CHUNK
         positions: the entries whose implied orbital exists by ``pymes_ueg_eval_2b_list``, then placed; every other
-        position is an exact 0."""
+        position is an exact 0.  ``both_sides``: also the excitation-type partners VvR[i,a,b] = V[a,b,i,f*] and
+        VoR[i,j,a] = V[a,m*,i,j] that Lambda-(T) reads (list families "vv_r", "vo_r")."""
         from pymes_amd.solver.sectors import TriplesTables
         from pymes_amd.solver.ueg_cc import SectorTriplesIntegrals, gather, upload_raw, view
         start_time = time.time()
@@ -403,10 +405,11 @@ class UEG:
         try:
             if ctx.recording:
                 raise RuntimeError("eval_2b_triples: the context is recording a launch graph")
-            tints = SectorTriplesIntegrals(ctx, ttab, own_ctx=own)
-            for family, dst in (("vv", tints.Vv), ("vo", tints.Vo)):
-                for e0 in range(0, ttab.sizes[family], self.SECTOR_CHUNK):
-                    e1 = min(e0 + self.SECTOR_CHUNK, ttab.sizes[family])
+            tints = SectorTriplesIntegrals(ctx, ttab, own_ctx=own, both_sides=both_sides)
+            families = [("vv", tints.Vv), ("vo", tints.Vo)] + ([("vv_r", tints.VvR), ("vo_r", tints.VoR)] if both_sides else [])
+            for family, dst in families:
+                for e0 in range(0, dst.size, self.SECTOR_CHUNK):
+                    e1 = min(e0 + self.SECTOR_CHUNK, dst.size)
                     pqrs, valid = ttab.list_pqrs(family, e0, e1)
                     nvalid = int(valid.sum())
                     vals = ctx.zeros((nvalid + 1,))                           # the last slot stays 0: what invalid positions read

@@ -212,9 +212,9 @@ class SectorTables:
         return eps[i] + eps[j] - eps[self.no + a] - eps[self.no + b]
 
     # ---- products ----------------------------------------------------------------------------------------------
-    def gemm_tasks(self, a, b, c, alpha=1.0, beta=0.0, trans_b=False):
+    def gemm_tasks(self, a, b, c, alpha=1.0, beta=0.0, trans_b=False, trans_a=False):
         """Task table of C^s = alpha A^s' B^s'' + beta C^s over all sectors.  a, b, c = (rows, cols, negated): the block
-        family of the operand as stored (before `trans_b`), and whether the operand of sector q is block -q."""
+        family of the operand as stored (before `trans_a` / `trans_b`), and whether the operand of sector q is block -q."""
         nsec = len(self.P_keys) if a[0] in ("oo", "vv") else len(self.q_keys)
         ident = np.arange(nsec)
 
@@ -230,12 +230,14 @@ class SectorTables:
         ar, ac, ao = view(a)
         br, bc, bo = view(b)
         cr, cc, co = view(c)
-        ldb = bc
+        lda, ldb = ac, bc
+        if trans_a:
+            ar, ac = ac, ar
         if trans_b:
             br, bc = bc, br
         if not (np.array_equal(ar, cr) and np.array_equal(bc, cc) and np.array_equal(ac, br)):
             raise AssertionError("gemm_tasks: the operand shapes do not chain")
-        return make_tasks(ar, bc, ac, ao, bo, co, ac, ldb, cc, alpha, beta, trans_b=trans_b)
+        return make_tasks(ar, bc, ac, ao, bo, co, lda, ldb, cc, alpha, beta, trans_a=trans_a, trans_b=trans_b)
 
 
 class TriplesTables:
@@ -248,11 +250,17 @@ class TriplesTables:
       Vo[i,j,a] = V[i, j, a, m*]   m* the occupied with k_i + k_j - k_a       list family "vo", shape [o,o,v]; m_of = m*
       Tc[i,j,a] = T[a, b*, i, j]   b* the virtual with k_i + k_j - k_a        `implied_map` into the compact pp vector
 
+    Lambda-(T) also reads the excitation-type integrals with the same implied orbitals:
+
+      VvR[i,a,b] = V[a, b, i, f*]                                              list family "vv_r", shape [o,v,v]
+      VoR[i,j,a] = V[a, m*, i, j]                                              list family "vo_r", shape [o,o,v]
+
     A position whose implied orbital does not exist holds an exact 0 (in m_of: -1).  `orb_of` is the dense lookup grid
     vector -> orbital over the box [lo, lo + dims) of the orbitals' own vectors, -1 where no orbital sits; a vector outside
     the box names no orbital and is never wrapped into it (`lookup` checks every axis)."""
 
     FAMILIES = ("vv", "vo")
+    RIGHT_FAMILIES = ("vv_r", "vo_r")       # the same positions and implied orbitals, V with bra and ket exchanged
 
     def __init__(self, tables):
         if not isinstance(tables, SectorTables):
@@ -286,10 +294,13 @@ class TriplesTables:
         return np.where(inside, self.orb_of[rel[..., 0], rel[..., 1], rel[..., 2]], -1).astype(np.int64)
 
     def list_pqrs(self, family, e0=0, e1=None):
-        """((p,q,r,s) int32 [count, 4], valid bool [count]) of the positions e0 <= e < e1 of list family "vv" or "vo" in
-        storage order.  Where `valid` is False the implied orbital does not exist: the row then names orbital 0 in its place
+        """((p,q,r,s) int32 [count, 4], valid bool [count]) of the positions e0 <= e < e1 of list family "vv" or "vo" (or
+        their right-hand partners "vv_r", "vo_r": (r,s,p,q) of the same position) in storage order.  Where `valid` is False the implied orbital does not exist: the row then names orbital 0 in its place
         and must not be evaluated (the stored value there is an exact 0)."""
         no, nv, k = self.no, self.nv, self.tables.k_int
+        if family in self.RIGHT_FAMILIES:
+            pqrs, valid = self.list_pqrs(family[:2], e0, e1)
+            return np.ascontiguousarray(pqrs[:, [2, 3, 0, 1]]), valid
         e1 = self.sizes[family] if e1 is None else e1
         e = np.arange(e0, e1, dtype=np.int64)
         if family == "vv":                      # Vv[i,a,b] = V[i, f*, a, b]

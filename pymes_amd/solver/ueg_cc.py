@@ -6,7 +6,11 @@ The tables (``pymes_amd.solver.sectors``) hold the non-zeros in three block-diag
 ccd.py:164-254 is one launch of the ragged batched product ``pymes_sector_gemm`` over all sectors, the moves between the
 layouts are gathers, and the diagonal X_ac / X_ki terms, the update and the energy are element-wise tails (DESIGN "Momentum
 sectors"; the numpy restatement the tests compare with is tests/_sector_reference.py).  The dense path (``CCD``, ``CCSD``) is
-untouched."""
+untouched.
+
+On the same tables: the perturbative triples (``sector_triples_energy``), and for integrals without
+V_pqrs = V_rspq (the transcorrelated electron gas) the Lambda equations of CCD and DCD as the transposed Jacobian of that
+residual (``SectorLambda``) with the Lambda-(T) correction on top (``sector_lambda_triples_energy``)."""
 import ctypes as C
 import os
 import time
@@ -24,7 +28,7 @@ from pymes_amd.solver import ccsd_t
 from pymes_amd.solver.sectors import BLOCKS, FOCK_LISTS, SectorTables, TriplesTables
 
 __all__ = ["SectorTables", "SectorIntegrals", "SectorAmplitudes", "SectorCCD", "TriplesTables", "SectorTriplesIntegrals",
-           "sector_triples_energy"]
+           "sector_triples_energy", "SectorLambda", "sector_lambda_triples_energy"]
 
 
 def upload_raw(ctx, host):
@@ -105,6 +109,49 @@ class DeviceTables:
         self.square_left_sub = table(S, F, F, alpha=-1.0, beta=1.0)              # Ed^q -= Wa^q D^q
         self.square_left_add = table(S, F, F, beta=1.0)                           # Ed^q += Y^q (C^q - D^q)
         self.square_left = table(S, F, F)                                         # Rc^q = Xc^q C^q
+        self._adjoint = None
+
+    def adjoint(self):
+        """The task tables and maps of the Lambda residual (``SectorLambda``): every product of the list above
+        with the operand that held T exchanged for the output, built on first use.  In the ph layouts the adjoint of a
+        product that read block -q of an operand writes the cotangent of that block, so the tables below are written for
+        the output sector q and read blocks -q where the forward product wrote them."""
+        if self._adjoint is not None:
+            return self._adjoint
+        ctx, tab = self.ctx, self.tab
+        F, S, Fn, Sn = ("ph", "ph-", False), ("ph", "ph", False), ("ph", "ph-", True), ("ph", "ph", True)
+        vo, oo, ov, vv = ("vv", "oo", False), ("oo", "oo", False), ("oo", "vv", False), ("vv", "vv", False)
+        size = lambda op: int(tab.offsets(*op[:2])[-1])
+
+        def table(a, b, c, **kw):
+            return Tasks(ctx, tab.gemm_tasks(a, b, c, **kw), size(a), size(b), size(c))
+
+        def imap(host):
+            arr = upload_raw(ctx, np.ascontiguousarray(host, dtype=np.int64))
+            arr.count = len(host)
+            return arr
+
+        class Adjoint:
+            pass
+        at = Adjoint()
+        at.ladder_t = table(vv, vo, vo, beta=1.0, trans_a=True)                # G^P += (V_abcd^P)^T lam^P
+        at.hole_t = table(vo, oo, vo, beta=1.0, trans_b=True)                  # G^P += lam^P (I^P)^T
+        at.t_lam = table(vo, vo, oo, trans_a=True)                             # M^P = (T^P)^T lam^P
+        at.hole_quad_t = table(ov, oo, vo, beta=1.0, trans_a=True)             # G^P += (V_klcd^P)^T M^P
+        at.sq_tn = table(Fn, Fn, S, trans_a=True)                              # Z^q = (Tt^{-q})^T yRd^{-q}  (cotangent of X^q)
+        at.right_t = table(F, Sn, F, trans_b=True)                             # zTt^q = yRd^q (X^{-q})^T
+        at.right_t_add = table(F, Sn, F, beta=1.0, trans_b=True)               # zTt^q += yEd^q (W2^{-q})^T
+        at.left_tn_add = table(Fn, Sn, F, beta=1.0, trans_a=True)              # zTt^q += (W1^{-q})^T Z^{-q}
+        at.sq_t_left_neg = table(S, F, F, alpha=-1.0, trans_a=True)            # zD^q = -(Wa^q)^T yEd^q
+        at.sq_t_left = table(S, F, F, trans_a=True)                            # zM^q = (Y^q)^T yEd^q
+        at.sq_t_left_add = table(S, F, F, beta=1.0, trans_a=True)              # zC^q += (Xc^q)^T yRc^q
+        at.right_neg = table(F, Sn, F, alpha=-1.0)                             # zC^q = -yEc^q Wa^{-q}
+        at.outer = table(F, F, S, trans_b=True)                                # zY^q = yEd^q (C^q - D^q)^T;  zXc^q = yRc^q (C^q)^T
+        at.sq_right_t_add = table(S, Fn, F, beta=1.0, trans_b=True)            # zD^q += zY^q (Wx^{-q})^T;  zC^q += zXc^q (Wx^{-q})^T
+        at.dT_from_pp, at.cT_from_pp = imap(tab.d_from_pp[tab.d_partner]), imap(tab.c_from_pp[tab.d_partner])
+        at.pp_swap = imap(tab.pp_swap)
+        self._adjoint = at
+        return at
 
 
 class SectorIntegrals:
@@ -187,17 +234,44 @@ class SectorTriplesIntegrals:
       Vo[i,j,a] = V[i, j, a, m*], shape [o,o,v], m* the occupied with k_i + k_j - k_a
 
     Contract: a position whose implied orbital does not exist holds an exact 0.0 (never a NaN, never left unwritten); the
-    kernel multiplies it with the equally exact 0 of ``Tc`` there.  No ``+`` and no scaling (left out)."""
+    kernel multiplies it with the equally exact 0 of ``Tc`` there.
 
-    def __init__(self, ctx, ttab, own_ctx=False):
-        self.ctx, self.tables, self._own = ctx, ttab, own_ctx
+    ``both_sides`` (``UEG.eval_2b_triples(..., both_sides=True)``) adds the excitation-type partners that
+    Lambda-(T) reads, VvR[i,a,b] = V[a, b, i, f*] and VoR[i,j,a] = V[a, m*, i, j]; they are None otherwise.  ``+`` and scaling
+    (the transcorrelated Hamiltonian is ``only_2b + effect_2b``) go through ``ctx.lincomb``, so exact zeros stay exact zeros."""
+
+    SIDES = ("Vv", "Vo", "VvR", "VoR")
+
+    def __init__(self, ctx, ttab, own_ctx=False, both_sides=False):
+        self.ctx, self.tables, self._own, self.both_sides = ctx, ttab, own_ctx, bool(both_sides)
         self.Vv = ctx.empty((ttab.no, ttab.nv, ttab.nv))
         self.Vo = ctx.empty((ttab.no, ttab.no, ttab.nv))
+        self.VvR = ctx.empty((ttab.no, ttab.nv, ttab.nv)) if both_sides else None
+        self.VoR = ctx.empty((ttab.no, ttab.no, ttab.nv)) if both_sides else None
         self._dev = None
 
     @property
     def nbytes(self):
-        return self.Vv.nbytes + self.Vo.nbytes
+        return sum(getattr(self, nm).nbytes for nm in self.SIDES if getattr(self, nm) is not None)
+
+    def _combine(self, terms):
+        out = SectorTriplesIntegrals(self.ctx, self.tables, both_sides=self.both_sides)
+        out._dev = self._dev
+        for nm in self.SIDES:
+            if getattr(self, nm) is not None:
+                self.ctx.lincomb(getattr(out, nm), [getattr(t, nm) for t, _ in terms], [c for _, c in terms])
+        return out
+
+    def __add__(self, other):
+        if not isinstance(other, SectorTriplesIntegrals) or other.tables.tables is not self.tables.tables \
+                or other.ctx is not self.ctx or other.both_sides != self.both_sides:
+            raise ValueError("SectorTriplesIntegrals: only integrals of the same tables, context and sides can be added")
+        return self._combine([(self, 1.0), (other, 1.0)])
+
+    def __mul__(self, factor):
+        return self._combine([(self, float(factor))])
+
+    __rmul__ = __mul__
 
     def device_tables(self):
         """(k_int, orb_of, m_of as int32 device bytes; the implied map of ``Tc`` as an int64 gather map)"""
@@ -226,6 +300,11 @@ def triple_bytes(nv):
     return 8 * (nv * nv + (-(-nv // 32)) ** 2 + 1)
 
 
+def lambda_triple_bytes(nv):
+    """Workspace bytes of one triple in ``pymes_sector_triples_lambda``: two v x v slabs, one partial per tile, the value."""
+    return 8 * (2 * nv * nv + (-(-nv // 32)) ** 2 + 1)
+
+
 def _hermitian(ints, rtol=1e-12):
     """V_klcd = V_cdkl, sector by sector: ``klcd``^P against ``abij``^P transposed."""
     tab = ints.tables
@@ -236,8 +315,9 @@ def _hermitian(ints, rtol=1e-12):
     return np.abs(kl - ab[tab.pp_off[sec] + lc * tab.n_oo[sec] + lr]).max() <= rtol * max(np.abs(ab).max(), 1e-300)
 
 
-def _check_triples(who, ints, tints):
-    """The refusals of the (T) inputs that need no amplitudes (``SectorCCD.solve`` makes them before it iterates)."""
+def _check_triples(who, ints, tints, left=False):
+    """The refusals of the (T) inputs that need no amplitudes (``SectorCCD.solve`` makes them before it iterates).  ``left``:
+    for Lambda-(T), which needs both sides of the triples integrals and no Hermitian V."""
     if not isinstance(ints, SectorIntegrals):
         raise TypeError(who + ": ints must be SectorIntegrals (UEG.eval_2b_sectors)")
     if not isinstance(tints, SectorTriplesIntegrals):
@@ -248,9 +328,15 @@ def _check_triples(who, ints, tints):
         raise ValueError(who + ": the triples integrals belong to other tables or another context than the integrals")
     if ints.ctx.recording:
         raise RuntimeError(who + ": the context is recording a launch graph")
-    if not _hermitian(ints):
+    if left:
+        if not tints.both_sides:
+            raise ValueError(who + ": the triples integrals lack the right-hand families VvR / VoR "
+                             "(UEG.eval_2b_triples(..., both_sides=True))")
+    elif not _hermitian(ints):
         raise ValueError(who + ": the integrals are not Hermitian (V_pqrs = V_rspq fails between the klcd and abij sectors); "
-                         "(T) is not defined for transcorrelated integrals, and Lambda-(T) does not exist on sectors yet")
+                         "(T) is not defined for transcorrelated integrals, and Lambda-(T) does not exist on sectors yet under "
+                         "this keyword: pass the integrals of UEG.eval_2b_triples(..., both_sides=True) as lambda_triples= "
+                         "to SectorCCD.solve, or call sector_lambda_triples_energy")
 
 
 def sector_triples_energy(eps, ints, tints, amps, triple_range=None, per_triple=False, workspace_bytes=None):
@@ -300,6 +386,76 @@ def sector_triples_energy(eps, ints, tints, amps, triple_range=None, per_triple=
         values = out.get()[:hi - lo] if out is not None else None
     finally:
         for t in temps + ([out] if out is not None else []):
+            t.free()
+    energy = float(e.value)
+    if reduce:
+        energy = float(pdist.allreduce_sum([energy])[0])
+    return (energy, values) if per_triple else energy
+
+
+def _symmetric_compact(who, tab, amps, what):
+    vec = SectorCCD._compact(tab, amps, "lambda" if what.startswith("lambda") else "amps")
+    if len(vec) and np.abs(vec - vec[tab.pp_swap]).max() > 1e-13 * max(np.abs(vec).max(), 1e-300):
+        raise ValueError(who + ": %s not exchange-symmetric (X_abij = X_baji)" % what)
+    return vec
+
+
+def sector_lambda_triples_energy(eps, ints, tints, amps, lam, triple_range=None, per_triple=False, workspace_bytes=None):
+    """E_Lambda(T) on the momentum sectors: the triples correction for integrals without V_pqrs = V_rspq (transcorrelated
+    ones), the formulas of tests/_lambda_triples_reference.py with lam1 = None (singles vanish on the sectors), by
+    ``pymes_sector_triples_lambda``.  With a Hermitian V and lam = 2 T - T^x it is the (T) of
+    ``sector_triples_energy``.
+
+    tints: ``UEG.eval_2b_triples(..., both_sides=True)``; amps and lam: ``SectorAmplitudes``, a compact vector or a dense
+    [v,v,o,o] array, lam in the library's normalisation (``SectorLambda``; A^T lam + eta = 0).  Everything else as
+    ``sector_triples_energy``: triple ranges, the split over ranks and the all-reduce, batches of as many triples as
+    ``workspace_bytes`` hold (``lambda_triple_bytes(nv)`` each: two slabs).  Nothing asks for V_pqrs = V_rspq."""
+    who = "sector_lambda_triples_energy"
+    _check_triples(who, ints, tints, left=True)
+    tab, ctx, tt = ints.tables, ints.ctx, tints.tables
+    eps = np.asarray(eps, dtype=np.float64)
+    if eps.ndim == 2:
+        if np.count_nonzero(eps - np.diag(eps.diagonal())):
+            raise ValueError(who + ": the Fock matrix must be diagonal (it is for a momentum-conserving Hamiltonian)")
+        eps = eps.diagonal().copy()
+    if eps.shape != (tab.n,):
+        raise ValueError(who + ": %d orbital energies for %d orbitals" % (eps.size, tab.n))
+    vec = _symmetric_compact(who, tab, amps, "the amplitudes are")
+    lvec = _symmetric_compact(who, tab, lam, "lambda is")
+    no, nv = tab.no, tab.nv
+    lo, hi, reduce = ccsd_t._triple_chunk(no, triple_range)
+    if not 0 <= lo <= hi <= ccsd_t.n_triples(no):
+        raise ValueError(who + ": triple range [%d, %d) outside [0, %d]" % (lo, hi, ccsd_t.n_triples(no)))
+    if workspace_bytes is None:
+        workspace_bytes = int(os.environ.get(TRIPLES_WS_ENV, TRIPLES_WS_DEFAULT))
+    each = lambda_triple_bytes(nv)
+    ws_bytes = each * max(1, min(int(workspace_bytes) // each, max(hi - lo, 1)))
+    k_dev, orb_dev, m_dev, imap = tints.device_tables()
+    # Lc[i,j,a] = L[a,b*,i,j], L = (2 lam + lam^x) / 3: the implied map, and the same map behind the exchange of a and b
+    a, b, i, j = tab.abij()
+    swapped = upload_raw(ctx, np.append(tab._pp_index(b, a, i, j), tab.nnz)[tt.implied_map.reshape(-1)])
+    swapped.count = imap.count
+    temps = [swapped]
+
+    def temp(make, arg):                     # one at a time, so that whatever was allocated is freed if a later one fails
+        temps.append(make(arg))
+        return temps[-1]
+    e = C.c_double()
+    try:
+        src, lsrc = temp(ctx.array, np.append(vec, 0.0)), temp(ctx.array, np.append(lvec, 0.0))
+        Tc, Lc = temp(ctx.empty, (no, no, nv)), temp(ctx.empty, (no, no, nv))
+        eps_dev, ws = temp(ctx.array, eps), temp(ctx.empty, (ws_bytes // 8,))
+        out = temp(ctx.empty, (max(hi - lo, 1),)) if per_triple else None
+        gather(ctx, Tc, src, imap)
+        gather(ctx, Lc, lsrc, imap, 2.0 / 3.0, lsrc, swapped, 1.0 / 3.0)
+        ctx.lib.call("pymes_sector_triples_lambda", ctx.handle, no, nv, C.c_void_p(eps_dev.ptr), C.c_void_p(k_dev.ptr),
+                     C.c_void_p(orb_dev.ptr), tt.box.ctypes.data_as(C.c_void_p), C.c_void_p(m_dev.ptr), C.c_void_p(Tc.ptr),
+                     C.c_void_p(Lc.ptr), C.c_void_p(tints.VvR.ptr), C.c_void_p(tints.VoR.ptr), C.c_void_p(tints.Vv.ptr),
+                     C.c_void_p(tints.Vo.ptr), int(lo), int(hi), C.c_void_p(ws.ptr), int(ws_bytes),
+                     C.c_void_p(out.ptr if out is not None else None), C.byref(e))
+        values = out.get()[:hi - lo] if out is not None else None
+    finally:
+        for t in temps:
             t.free()
     energy = float(e.value)
     if reduce:
@@ -378,14 +534,14 @@ class SectorCCD:
         return R.get()
 
     @staticmethod
-    def _compact(tab, amps):
+    def _compact(tab, amps, name="amps"):
         if isinstance(amps, SectorAmplitudes):
             if amps.tables is not tab and not (np.array_equal(amps.tables.k_int, tab.k_int) and amps.tables.no == tab.no):
                 raise ValueError("SectorCCD: the tables of the amplitudes do not match the integrals")
             vec = amps.get()
         else:
             vec = np.asarray(amps)
-            vec = tab.compact(vec, "amps") if vec.ndim == 4 else vec
+            vec = tab.compact(vec, name) if vec.ndim == 4 else vec
         vec = np.ascontiguousarray(vec, dtype=np.float64)
         if vec.shape != (tab.nnz,):
             raise ValueError("SectorCCD: the tables of the amplitudes do not match the integrals")
@@ -412,15 +568,20 @@ class SectorCCD:
                              "(V_pqrs = V_qpsr), which the sector residual needs")
         return eps
 
-    def solve(self, eps, ints, level_shift=0., amps=None, triples=None, **kwargs):
+    def solve(self, eps, ints, level_shift=0., amps=None, triples=None, lambda_triples=None, **kwargs):
         """The loop of ``CCD.solve`` (ccd.py:24-162) on the compact vector.  eps: the orbital energies (or a diagonal Fock
         matrix); ints: ``SectorIntegrals``.  ``triples``: the ``SectorTriplesIntegrals`` of the same tables; the result then
-        also holds "(t) e" (``sector_triples_energy`` of the final amplitudes) and "ccd(t) e"."""
+        also holds "(t) e" (``sector_triples_energy`` of the final amplitudes) and "ccd(t) e".  ``lambda_triples``: the
+        ``SectorTriplesIntegrals`` with both sides (``UEG.eval_2b_triples(..., both_sides=True)``), for integrals without
+        V_pqrs = V_rspq: Lambda is solved after the amplitudes (``SectorLambda``, threshold ``lambda_threshold``, default
+        1e-8) and the result also holds "lambda2", "lambda (t) e" (``sector_lambda_triples_energy``) and "ccd(t)_lambda e"."""
         algo_name = "ccd.solve"
         time_ccd = time.time()
         eps = self._checks(eps, ints)
         if triples is not None:
             _check_triples("SectorCCD.solve", ints, triples)
+        if lambda_triples is not None:
+            _check_triples("SectorCCD.solve", ints, lambda_triples, left=True)
         tab, ctx, no = ints.tables, ints.ctx, self.no
         max_iter, delta_e = kwargs.get("max_iter", self.max_iter), kwargs.get("delta_e", self.delta_e)
         with quiet_collector():
@@ -487,6 +648,15 @@ class SectorCCD:
                 out["(t) e"] = sector_triples_energy(eps, ints, triples, out["t2 amp"])
                 out["ccd(t) e"] = e_ccd + out["(t) e"]
                 print_logging_info("(T) correction = {:.12f}".format(out["(t) e"]), level=1)
+            if lambda_triples is not None:
+                left = SectorLambda(no, kwargs.get("lambda_threshold", 1.e-8), is_dcd=self.is_dcd, is_diis=self.is_diis)
+                lam = left.solve(eps, ints, out["t2 amp"], level_shift=level_shift, max_iter=kwargs.get("lambda_max_iter", 100))
+                out["lambda2"] = lam["lambda2"]
+                out["lambda (t) e"] = sector_lambda_triples_energy(eps, ints, lambda_triples, out["t2 amp"], lam["lambda2"])
+                out["ccd(t)_lambda e"] = e_ccd + out["lambda (t) e"]
+                print_logging_info("Lambda residual norm = {:.3e} after {} iterations".format(lam["lambda residual"],
+                                                                                               lam["iterations"]), level=1)
+                print_logging_info("Lambda-(T) correction = {:.12f}".format(out["lambda (t) e"]), level=1)
             return out
 
     @staticmethod
@@ -503,3 +673,174 @@ class SectorCCD:
             xs, ys = xs + [dt2], ys + [dt2]
         d = ctx.dots(xs, ys)
         return 2.0 * d[0], -d[1], d[2], (d[3] if dt2 is not None else 0.0)
+
+
+class SectorLambda:
+    """The Lambda equations of the momentum-sector CCD / DCD: J(T)^T lam + eta = 0, J = dR/dT of the compact
+    residual of ``SectorCCD.residual`` on the exchange-symmetric vectors, eta = 2 ed - ex, plain inner product over the
+    compact elements (the dense library's convention: for CCD, ``lambda2.to_dense()`` is the lambda2 of ``Lambda_CCSD``;
+    lambda1 vanishes like T1).  Lambda is the transpose of the Jacobian of the sector residual itself, so DCD has one too.
+    The integrals need V_pqrs = V_qpsr only: no V_pqrs = V_rspq."""
+
+    def __init__(self, no, threshold=1.e-8, is_dcd=False, is_diis=True):
+        self.no, self.threshold, self.is_dcd, self.is_diis = no, threshold, is_dcd, is_diis
+        self.max_iter = 100
+        if self.is_diis:
+            self.mixer = diis.DIIS(dim_space=6)
+
+    def _checks(self, eps, ints, amps):
+        who = "SectorLambda.solve"
+        if not isinstance(ints, SectorIntegrals):
+            raise TypeError(who + ": ints must be SectorIntegrals (UEG.eval_2b_sectors); the dense path is Lambda_CCSD")
+        tab, ctx = ints.tables, ints.ctx
+        if ctx.recording:
+            raise RuntimeError(who + ": the context is recording a launch graph")
+        eps = np.asarray(eps, dtype=np.float64)
+        if eps.ndim == 2:
+            if np.count_nonzero(eps - np.diag(eps.diagonal())):
+                raise ValueError(who + ": the Fock matrix must be diagonal (it is for a momentum-conserving Hamiltonian)")
+            eps = eps.diagonal().copy()
+        if tab.no != self.no or eps.shape != (tab.n,):
+            raise ValueError(who + ": the tables of the integrals (no = %d, n = %d) do not match the solver (no = %d) "
+                             "and the %d orbital energies" % (tab.no, tab.n, self.no, eps.size))
+        w1 = ints["w1"].get()
+        if len(w1) and np.abs(w1 - w1[tab.d_partner]).max() > 1e-12 * max(np.abs(w1).max(), 1e-300):
+            raise ValueError(who + ": the integrals are not symmetric under the exchange of the two electrons "
+                             "(V_pqrs = V_qpsr), which the sector residual needs")
+        return eps, _symmetric_compact(who, tab, amps, "the amplitudes are")
+
+    # ---- what depends on T alone: its three layouts, hole(T), X = W1 Tt, Y = D Wx, Xc = C Wx -----------------------------
+    def hoist(self, ints, T):
+        ctx, tab, dt = ints.ctx, ints.tables, ints.device_tables()
+        nnz, nsq = max(tab.nnz, 1), max(dt.nsq, 1)
+        quad = not self.is_dcd
+        h = {"T": T, "D": ctx.empty((nnz,)), "C": ctx.empty((nnz,)), "Tt": ctx.empty((nnz,)), "X": ctx.empty((nsq,))}
+        gather(ctx, h["D"], T, dt.d_from_pp)
+        gather(ctx, h["C"], T, dt.c_from_pp)
+        gather(ctx, h["Tt"], T, dt.d_from_pp, 2.0, T, dt.c_from_pp, -1.0)
+        dt.to_square.run(ints["w1"], h["Tt"], h["X"])                      # X^q = W1^q Tt^{-q}
+        h["hole"] = ints["klij"]
+        if quad:
+            h["hole"] = ctx.empty((max(ints.sizes["klij"], 1),)).copy_from(ints["klij"])
+            dt.hole_quad.run(ints["klcd"], T, h["hole"])                   # I^P = V_klij^P + V_klcd^P T^P
+            h["CmD"], h["Y"], h["Xc"] = ctx.empty((nnz,)), ctx.empty((nsq,)), ctx.empty((nsq,))
+            gather(ctx, h["CmD"], T, dt.c_from_pp, 1.0, T, dt.d_from_pp, -1.0)
+            dt.to_square.run(h["D"], ints["wx"], h["Y"])                   # Y^q = D^q Wx^{-q}
+            dt.to_square.run(h["C"], ints["wx"], h["Xc"])                  # Xc^q = C^q Wx^{-q}
+        h["eta"] = ctx.empty((nnz,))
+        ctx.lincomb(h["eta"], [ints["ed"], ints["ex"]], [2.0, -1.0])
+        h["zero"] = ctx.zeros((tab.n,))
+        return h
+
+    def workspace(self, ints):
+        ctx, tab = ints.ctx, ints.tables
+        nnz = max(tab.nnz, 1)
+        ws = {k: ctx.empty((nnz,)) for k in ("yRd", "yRc", "yEd", "yEc", "zTt", "zD", "zC", "Gp", "Gs")}
+        ws["Z"] = ctx.empty((max(ints.device_tables().nsq, 1),))
+        ws["x"] = ctx.empty((tab.no * tab.nv + tab.n,))
+        if not self.is_dcd:
+            ws["zM"] = ctx.empty((nnz,))
+            ws["sq"] = ctx.empty((max(ints.device_tables().nsq, 1),))
+            ws["M"] = ctx.empty((max(ints.sizes["klij"], 1),))
+        return ws
+
+    # ---- G = J(T)^T lam + eta: the adjoint of every product of SectorCCD.residual (tests/_sector_lambda_reference.py) ------
+    def residual(self, ints, eps_dev, h, lam, G, ws):
+        ctx, tab, dt = ints.ctx, ints.tables, ints.device_tables()
+        at = dt.adjoint()
+        quad = not self.is_dcd
+        w = 1.0 if quad else 0.5
+        yRd, yRc, yEd, yEc, zTt, zD, zC, Gp, Z = (ws[k] for k in ("yRd", "yRc", "yEd", "yEc", "zTt", "zD", "zC", "Gp", "Z"))
+        # the cotangents of Rd, Rc and of Ed, Ec (which enter as Ex + Ex^T(1,0,3,2)): gathers through the inverse maps
+        gather(ctx, yRd, lam, dt.d_from_pp)
+        gather(ctx, yRc, lam, dt.c_from_pp)
+        gather(ctx, yEd, lam, dt.d_from_pp, 1.0, lam, at.dT_from_pp, 1.0)
+        gather(ctx, yEc, lam, dt.c_from_pp, 1.0, lam, at.cT_from_pp, 1.0)
+        # pp layout: G^P = eta^P + V_abcd^P^T lam^P + lam^P I^P^T + [CCD] V_klcd^P^T (T^P^T lam^P)
+        Gp.copy_from(h["eta"])
+        at.ladder_t.run(ints["abcd"], lam, Gp)
+        at.hole_t.run(lam, h["hole"], Gp)
+        if quad:
+            at.t_lam.run(h["T"], lam, ws["M"])
+            at.hole_quad_t.run(ints["klcd"], ws["M"], Gp)
+        # ph layouts: the cotangents of Tt, D and C
+        at.sq_tn.run(h["Tt"], yRd, Z)                            # Z^q = Tt^{-q}^T yRd^{-q}             (of X, from Rd = Tt X)
+        at.right_t.run(yRd, h["X"], zTt)                         # zTt^q = yRd^q X^{-q}^T
+        at.right_t_add.run(yEd, ints["w2"], zTt)                 # zTt^q += yEd^q W2^{-q}^T
+        at.left_tn_add.run(ints["w1"], Z, zTt)                   # zTt^q += W1^{-q}^T Z^{-q}            (X = W1 Tt)
+        at.sq_t_left_neg.run(ints["wa"], yEd, zD)                # zD^q = -Wa^q^T yEd^q
+        at.right_neg.run(yEc, ints["wa"], zC)                    # zC^q = -yEc^q Wa^{-q}                (Ec = -C Wa^T)
+        if quad:
+            sq = ws["sq"]
+            at.sq_t_left.run(h["Y"], yEd, ws["zM"])              # zM^q = Y^q^T yEd^q                   (of C - D)
+            at.outer.run(yEd, h["CmD"], sq)                      # zY^q = yEd^q (C^q - D^q)^T
+            at.sq_right_t_add.run(sq, ints["wx"], zD)            # zD^q += zY^q Wx^{-q}^T               (Y = D Wx)
+            at.sq_t_left_add.run(h["Xc"], yRc, zC)               # zC^q += Xc^q^T yRc^q
+            at.outer.run(yRc, h["C"], sq)                        # zXc^q = yRc^q C^q^T
+            at.sq_right_t_add.run(sq, ints["wx"], zC)            # zC^q += zXc^q Wx^{-q}^T              (Xc = C Wx)
+        # the diagonal X_ac / X_ki term, Ed[g,:] += scale(T)[g] D[g,:]: zD[g,:] += scale(T)[g] yEd[g,:] is the forward call
+        # with yEd in the place of D; zTt[g,:] -= w (rho_a + rho_i) W1[g,:], rho the row sums of yEd o D, is the same call with
+        # the operands exchanged and eps = 0
+        rows = (C.c_void_p(dt.row_start.ptr), C.c_void_p(dt.row_len.ptr), C.c_void_p(dt.row_of.ptr), C.c_void_p(dt.ai_of.ptr),
+                C.c_void_p(ws["x"].ptr))
+        ctx.lib.call("pymes_sector_xdiag", ctx.handle, C.c_void_p(h["Tt"].ptr), C.c_void_p(ints["w1"].ptr), C.c_void_p(yEd.ptr),
+                     C.c_void_p(zD.ptr), C.c_void_p(eps_dev.ptr), w, tab.no, tab.nv, *rows)
+        ctx.lib.call("pymes_sector_xdiag", ctx.handle, C.c_void_p(yEd.ptr), C.c_void_p(h["D"].ptr), C.c_void_p(ints["w1"].ptr),
+                     C.c_void_p(zTt.ptr), C.c_void_p(h["zero"].ptr), w, tab.no, tab.nv, *rows)
+        # back to the pp vector through the inverse maps (D = T[d_from_pp], C = T[c_from_pp], Tt = 2 D - C) ...
+        gather(ctx, Gp, zD, dt.pp_to_d, 1.0, zC, dt.pp_to_c, 1.0, beta=1.0)
+        gather(ctx, Gp, zTt, dt.pp_to_d, 2.0, zTt, dt.pp_to_c, -1.0, beta=1.0)
+        if quad:
+            gather(ctx, Gp, ws["zM"], dt.pp_to_c, 1.0, ws["zM"], dt.pp_to_d, -1.0, beta=1.0)
+        # ... and on the exchange-symmetric vectors: the plain adjoint is not symmetric (DESIGN 8k).  0.5 x + 0.5 y is one
+        # rounding of the exact mean whichever comes first, so G is symmetric to the bit
+        gather(ctx, ws["Gs"], Gp, at.pp_swap)
+        ctx.lincomb(G, [Gp, ws["Gs"]], [0.5, 0.5])
+        return G
+
+    def get_residual(self, eps, ints, amps, lam):
+        """G(lam) = J(T)^T lam + eta for compact (or dense) amplitudes and lambda, as a host vector."""
+        tab, ctx = ints.tables, ints.ctx
+        T, L = ctx.array(SectorCCD._compact(tab, amps)), ctx.array(SectorCCD._compact(tab, lam, "lambda"))
+        G = self.residual(ints, ctx.array(np.asarray(eps, dtype=np.float64)), self.hoist(ints, T), L, ctx.empty((tab.nnz,)),
+                          self.workspace(ints))
+        return G.get()
+
+    def solve(self, eps, ints, amps, level_shift=0., lam=None, **kwargs):
+        """lam <- lam + G(lam) / (den + level_shift) with the DIIS mixer, from lam = 0 (or ``lam``), until |G| is below the
+        threshold.  Returns {"lambda2": SectorAmplitudes, "lambda residual": |G|, "iterations", "converged"}."""
+        eps, vec = self._checks(eps, ints, amps)
+        tab, ctx = ints.tables, ints.ctx
+        max_iter, threshold = kwargs.get("max_iter", self.max_iter), kwargs.get("threshold", self.threshold)
+        n = tab.nnz
+        start = np.zeros(n) if lam is None else _symmetric_compact("SectorLambda.solve", tab, lam, "lambda is")
+        with quiet_collector():
+            eps_dev, den = ctx.array(eps), ctx.array(tab.denominators(eps))
+            h, ws = self.hoist(ints, ctx.array(vec)), self.workspace(ints)
+            l2, g2 = ctx.pool_get((n,)), ctx.pool_get((n,))
+            l2.set(start)
+            dl_fixed = None if self.is_diis else ctx.pool_get((n,))
+            iteration, norm, converged = 0, np.inf, False
+            while True:
+                self.residual(ints, eps_dev, h, l2, g2, ws)
+                norm = float(np.sqrt(ctx.dots([g2], [g2])[0]))
+                print_logging_info("Lambda iteration = ", iteration, " |G| = {:.6e}".format(norm), level=2)
+                converged = norm <= threshold
+                if converged or iteration >= max_iter:
+                    break
+                iteration += 1
+                if self.is_diis:
+                    l2n, dl2 = ctx.pool_get((n,)), ctx.pool_get((n,))
+                    SectorCCD._update(ctx, l2n, dl2, l2, g2, den, level_shift)
+                    self.mixer.mix([dl2], [l2n], release=ctx.pool_put, out=[l2], defer_log=True, native=True)
+                    self.mixer.log_last()
+                else:
+                    SectorCCD._update(ctx, l2, dl_fixed, l2, g2, den, level_shift)
+            if not converged:
+                print_logging_info("A converged Lambda is not found!", level=1)
+            self.iterations = iteration
+            result = ctx.empty((n,)).copy_from(l2)
+            ctx.pool_put(l2)
+            ctx.pool_put(g2)
+            return {"lambda2": SectorAmplitudes(tab, result), "lambda residual": norm, "iterations": iteration,
+                    "converged": converged}

@@ -124,6 +124,10 @@ int pymes_permute(pymes_ctx* ctx, double alpha, const double* in_dev, const char
 int pymes_dgemm(pymes_ctx* ctx, int64_t M, int64_t N, int64_t K, double alpha, const double* A_dev, int64_t a_sm,
                 int64_t a_sk, const double* B_dev, int64_t b_sk, int64_t b_sn, double beta, double* C_dev,
                 int64_t ldc);
+/* ... with the beta term read from another array of C's layout: C = alpha*A*B + beta*Cin (Cin_dev NULL: from C itself) */
+int pymes_dgemm_cin(pymes_ctx* ctx, int64_t M, int64_t N, int64_t K, double alpha, const double* A_dev, int64_t a_sm,
+                    int64_t a_sk, const double* B_dev, int64_t b_sk, int64_t b_sn, double beta, const double* Cin_dev,
+                    double* C_dev, int64_t ldc);
 
 /* ---- integrals: pymes/integral/partition.py:4-39 -------------------------------- */
 /* V[n,n,n,n] (host: C-contiguous, strides ignored; device: element strides or NULL) -> 16 blocks */

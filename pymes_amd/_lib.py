@@ -68,6 +68,8 @@ SIGNATURES = {
                                 C.c_double, C.c_void_p, C.c_char_p, c_i64_p]),
     "pymes_dgemm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64,
                               C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64]),
+    "pymes_dgemm_cin": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64,
+                                  C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_int64]),
     "pymes_set_V_pqrs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64_p]),
     "pymes_set_V_block": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_int, c_i64_p]),
     "pymes_V_exchange_asymmetry": (C.c_int, [C.c_void_p, c_double_p]),

@@ -284,6 +284,11 @@ int pymes_permute(pymes_ctx* ctx, double alpha, const double* in, const char* li
 }
 int pymes_dgemm(pymes_ctx* ctx, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t a_sm,
                 int64_t a_sk, const double* B, int64_t b_sk, int64_t b_sn, double beta, double* C, int64_t ldc) {
+    return pymes_dgemm_cin(ctx, M, N, K, alpha, A, a_sm, a_sk, B, b_sk, b_sn, beta, nullptr, C, ldc);
+}
+int pymes_dgemm_cin(pymes_ctx* ctx, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t a_sm,
+                    int64_t a_sk, const double* B, int64_t b_sk, int64_t b_sn, double beta, const double* Cin, double* C,
+                    int64_t ldc) {
     return guarded([&] {
         Engine& e = Eq(ctx);
         dev::Gemm g{};
@@ -291,6 +296,7 @@ int pymes_dgemm(pymes_ctx* ctx, int64_t M, int64_t N, int64_t K, double alpha, c
         g.A = A; g.a_sm = a_sm; g.a_sk = a_sk;
         g.B = B; g.b_sk = b_sk; g.b_sn = b_sn;
         g.C = C; g.ldc = ldc;
+        g.Cin = beta != 0.0 ? Cin : nullptr;
         g.nb1 = g.nb2 = 1;
         g.splitk_ws = e.splitk_ws();
         g.splitk_ws_doubles = e.splitk_ws_doubles();

@@ -68,7 +68,12 @@ struct GemmK {
     // ws[i][ks], reduced by splitk_reduce_kernel over the tail tiles.  `whole` is a multiple of 8 (XCD remap per part).
     long whole = 0, tail = 0;
     int mixed = 0;
+    // Fat edge tiling of the LDS-DMA kernel (A K-contiguous, B N-contiguous only): bit 0 — M mod 128 is in 1..16, tiles_m is
+    // floor(M / 128) and the tiles of the last tile row are 144 rows high; bit 1 — the same for N.  A partial tile is
+    // [rows][its own width, 128 or 144] in a workspace slot sized for the launch's largest tile (glds_fat_slot).
+    int fat = 0;
 };
+__host__ __device__ inline long glds_fat_slot(int fat) { return (long)((fat & 1) ? 144 : 128) * ((fat & 2) ? 144 : 128); }
 
 // blocks are dealt round-robin over the 8 XCDs (b and b+8 share an L2): give each
 // XCD a contiguous range of logical ids so neighbouring tiles share an L2 (bijective).
@@ -76,6 +81,37 @@ __device__ __forceinline__ long xcd_remap(long b, long nblk) {
     const long q = nblk >> 3, r = nblk & 7;
     const long xcd = b & 7, pos = b >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
+}
+
+// tile row / column of tile `gt` in the batch-major, grouped order (groups of 8 tile rows, column by column inside a group).
+// Fat tiling: the plain tiles first, in that order, then the fat ones — the 144-row tiles of the last tile row, then the
+// 144-column tiles of the last tile column, the corner last.  The whole tiles of a launch are dealt to the XCDs in equal
+// shares of equal tiles, a whole number per CU; a fat tile among them keeps its CU (and the launch) an eighth of a tile-time
+// longer, so the fat ones are to be the tiles that plan_dma cuts along K.
+__device__ __forceinline__ void gemm_tile_rc(const GemmK& g, const long gt, int& tm, int& tn) {
+    const int tiles = g.tiles_m * g.tiles_n;
+    const int t = (int)(gt - (gt / tiles) * tiles);
+    int rows = g.tiles_m, cols = g.tiles_n;
+    if (g.fat) {
+        rows -= g.fat & 1;
+        cols -= (g.fat >> 1) & 1;
+        int e = t - rows * cols;
+        if (e >= 0) {
+            if (g.fat & 1) {
+                if (e < cols) { tm = rows; tn = e; return; }
+                e -= cols;
+            }
+            tm = e;
+            tn = cols;
+            return;
+        }
+    }
+    const int group_sz = 8 * cols;
+    const int grp = t / group_sz;
+    const int gm = min(rows - grp * 8, 8);
+    const int tin = t - grp * group_sz;
+    tm = grp * 8 + tin % gm;
+    tn = tin / gm;
 }
 
 // STREAM (64 x 64 tiles only): ONE LDS buffer instead of two — the next k-tile waits in registers while this one is
@@ -446,25 +482,47 @@ __device__ __forceinline__ unsigned lds_addr_of(const double* p) {
 // the whole product; `Wpart` = destination of a partial tile [128][128] (k-split), or null: alpha / beta epilogue into C.
 // (Every wave has passed the barrier behind its last LDS read when the function returns: a persistent kernel may call it
 // again at once — the hybrid stream-K launch of round 5 did)
-template <bool AKC, bool BKC>
+//
+// Fat tile kinds (FAT != 0; A K-contiguous, B N-contiguous only; GemmK::fat): a ragged edge of at most 16 rows (columns) is
+// one more row (column) of 16 x 16 blocks of the neighbouring tile instead of a tile of its own with 64 MFMAs per k step on
+// clamped rows.  FAT bit 0: the tile is 144 rows high.  The ninth row block's A strip [16 rows][16 k] (same XOR swizzle) has
+// an LDS region of its own (an LDS-DMA destination is lane-linear), one more DMA per k-tile for the waves wm == 0; its eight
+// column blocks are spread over the waves: wave (wm, wn) takes the blocks 4 wn + 2 wm + {0, 1} — B fragments it holds anyway —
+// and reads one strip fragment more per k step.  FAT bit 1: 144 columns wide, B strip [16 k][16 n] loaded by the waves
+// wn == 1, row blocks 4 wm + 2 wn + {0, 1} per wave.  18 MFMAs per k step and wave instead of 16.  FAT == 3 (the one corner
+// tile of a product that is ragged both ways): both, and wave (1, 1) takes the corner block (21 MFMAs).  SEL = wm | wn << 1
+// as far as the kind needs it (wm for bit 0, wn for bit 1) makes the fragment choice a compile-time one: the k loop of
+// every kind is as free of run-time bounds and VALU work as the plain one, and FAT == 0 compiles to the plain tile.
+template <bool AKC, bool BKC, int FAT = 0, int SEL = 0, bool FAT_ORDER = (FAT != 0)>
 __device__ __forceinline__ void dgemm_glds_tile(const GemmK& g, const long gt, const int kbeg, const int kend,
                                                 double* __restrict__ Wpart) {
+    static_assert(FAT == 0 || (AKC && !BKC), "fat tiles: A K-contiguous, B N-contiguous");
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int BM = 128, BN = 128, WM = 64, WN = 64, FM = 4, FN = 4;
     constexpr int A_PITCH = AKC ? BK : (BM + 16);
     constexpr int A_TILE = AKC ? BM * BK : BK * A_PITCH;
     constexpr int B_PITCH = BKC ? BK : (BN + 16);
     constexpr int B_TILE = BKC ? BN * BK : BK * B_PITCH;
+    constexpr bool FATM = (FAT & 1) != 0, FATN = (FAT & 2) != 0;
+    constexpr int XM = 2 * (SEL & 1);             // FATM: the extra row block times this wave's B fragments XM, XM + 1
+    constexpr int XN = SEL & 2;                   // FATN: this wave's A fragments XN, XN + 1 times the extra column block
+    constexpr bool CORNER = FAT == 3 && SEL == 3;
+    constexpr int STRIP = 16 * BK;                // doubles of one strip buffer
+    constexpr int WPITCH = FATN ? BN + 16 : BN;   // row pitch of a partial tile
+    // (a fat kind has its own LDS layout, A tiles | A strips | B tiles | B strips: each strip within the 16-bit immediate
+    // offset of its tile's fragment addresses; the strips exist in the fat kernel's LDS only)
     double* As = smem;
-    double* Bs = smem + 2 * A_TILE;
+    double* AsS = smem + 2 * A_TILE;
+    double* Bs = smem + 2 * A_TILE + (FAT != 0 ? 2 * STRIP : 0);
+    double* BsS = Bs + 2 * B_TILE;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform (LDS-DMA base = M0)
-    const int wm = wave >> 1, wn = wave & 1;
+    const int wm = FATM ? (SEL & 1) : wave >> 1, wn = FATN ? (SEL >> 1) : wave & 1;      // (a fat kind knows them)
     const int l15 = lane & 15, l4 = lane >> 4;
 
     const int tiles = g.tiles_m * g.tiles_n;
-    const long z = gt / tiles;
+    const long z = FAT != 0 ? (long)uni((int)(gt / tiles)) : gt / tiles;      // (fat kinds: the batch index in SGPRs too)
     const int t = (int)(gt - z * tiles);
     constexpr int GROUP = 8;
     const int group_sz = GROUP * g.tiles_n;
@@ -472,8 +530,10 @@ __device__ __forceinline__ void dgemm_glds_tile(const GemmK& g, const long gt, c
     const int first_m = grp * GROUP;
     const int gm = min(g.tiles_m - first_m, GROUP);
     const int tin = t - grp * group_sz;
-    const int tm = uni(first_m + tin % gm);
-    const int tn = uni(tin / gm);
+    int tm_v = first_m + tin % gm, tn_v = tin / gm;
+    if constexpr (FAT_ORDER) gemm_tile_rc(g, gt, tm_v, tn_v);      // (a launch of the fat tiling has its own tile order)
+    const int tm = uni(tm_v);
+    const int tn = uni(tn_v);
     const long z1 = z / g.nb2, z2 = z - z1 * g.nb2;
     const int m0 = tm * BM, n0 = tn * BN;
     const int nkt = (kend - kbeg + BK - 1) / BK;
@@ -514,12 +574,37 @@ __device__ __forceinline__ void dgemm_glds_tile(const GemmK& g, const long gt, c
     constexpr int B_DSTEP = BKC ? 8 * BK : B_PITCH;
 
     const unsigned a_lds = uni((int)lds_addr_of(As + a_dst)), b_lds = uni((int)lds_addr_of(Bs + b_dst));
+    // strips: one wave-instruction is half a strip.  A strip: rows 8 wn .. + 8 by wave (0, wn), lane -> (row, chunk slot) as
+    // in the tile, rows clamped to M - 1; B strip: k-rows 8 wm .. + 8 by wave (wm, 1), lane -> (k-row, columns 2 (lane & 7)),
+    // columns clamped to Nc - 2.  Offsets are relative to ua / ub like the tile's (the host checks 144 * ld * 8 < 2^32).
+    constexpr bool A_STRIP = FATM && !(SEL & 1), B_STRIP = FATN && (SEL & 2);
+    unsigned aso = 0, bso = 0, as_lds = 0, bs_lds = 0;
+    if constexpr (A_STRIP) {
+        const int row = wn * 8 + (lane >> 3);
+        const int cg = (lane & 7) ^ ((row >> 1) & 7);
+        aso = ((unsigned)(min(m0 + BM + row, g.M - 1) - m0) * (unsigned)g.a_ld + cg * 2) * 8u;
+        as_lds = uni((int)lds_addr_of(AsS + wn * (STRIP / 2)));
+    }
+    if constexpr (B_STRIP) {
+        bso = ((unsigned)(wm * 8 + (lane >> 3)) * (unsigned)g.b_ld + (unsigned)(min(n0 + BN + 2 * (lane & 7), g.Nc - 2) - n0)) * 8u;
+        bs_lds = uni((int)lds_addr_of(BsS + wm * (STRIP / 2)));
+    }
+    // (the 128 rows / columns of a tile that is fat in M / N are never clamped: their lane offsets differ by wave-uniform
+    // steps — A: instructions j and j + 2 are 16 rows apart with the same swizzle; B: k-rows — which go to the scalar base
+    // instead, five address registers fewer where the two kinds meet)
+    const long a_jstep = FATM ? 16L * 8 * g.a_ld : 0, b_jstep = FATN ? 8L * g.b_ld : 0;
+    auto ua_of = [&](int j) { return FATM ? ua + (j >> 1) * a_jstep : ua; };
+    auto ao_of = [&](int j) { return FATM ? ao[j & 1] : ao[j]; };
+    auto ub_of = [&](int j) { return FATN ? ub + j * b_jstep : ub; };
+    auto bo_of = [&](int j) { return FATN ? bo[0] : bo[j]; };
     auto stage_dma = [&](int buf) {      // one full k-tile, then advance the source bases
         const unsigned as = a_lds + buf * (A_TILE * 8), bs = b_lds + buf * (B_TILE * 8);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) glds16_su(ua, ao[j], as + j * (A_DSTEP * 8));
+        for (int j = 0; j < 4; ++j) glds16_su(ua_of(j), ao_of(j), as + j * (A_DSTEP * 8));
 #pragma unroll
-        for (int j = 0; j < 4; ++j) glds16_su(ub, bo[j], bs + j * (B_DSTEP * 8));
+        for (int j = 0; j < 4; ++j) glds16_su(ub_of(j), bo_of(j), bs + j * (B_DSTEP * 8));
+        if constexpr (A_STRIP) glds16_su(ua, aso, as_lds + buf * (STRIP * 8));
+        if constexpr (B_STRIP) glds16_su(ub, bso, bs_lds + buf * (STRIP * 8));
         ua += a_kstep;
         ub += b_kstep;
     };
@@ -545,10 +630,19 @@ __device__ __forceinline__ void dgemm_glds_tile(const GemmK& g, const long gt, c
             } else {
                 in_b = k0 + wave * 4 + j < kend;
             }
-            if (in_a) glds16_su(ua, ao[j], as + j * (A_DSTEP * 8));
+            if (in_a) glds16_su(ua_of(j), ao_of(j), as + j * (A_DSTEP * 8));
             else *reinterpret_cast<v2d*>(As + buf * A_TILE + a_dst + j * A_DSTEP + 2 * lane) = zero;
-            if (in_b) glds16_su(ub, bo[j], bs + j * (B_DSTEP * 8));
+            if (in_b) glds16_su(ub_of(j), bo_of(j), bs + j * (B_DSTEP * 8));
             else *reinterpret_cast<v2d*>(Bs + buf * B_TILE + b_dst + j * B_DSTEP + 2 * lane) = zero;
+        }
+        if constexpr (A_STRIP) {
+            const int row = wn * 8 + (lane >> 3);
+            if (k0 + (((lane & 7) ^ ((row >> 1) & 7)) << 1) < kend) glds16_su(ua, aso, as_lds + buf * (STRIP * 8));
+            else *reinterpret_cast<v2d*>(AsS + buf * STRIP + wn * (STRIP / 2) + 2 * lane) = zero;
+        }
+        if constexpr (B_STRIP) {
+            if (k0 + wm * 8 + (lane >> 3) < kend) glds16_su(ub, bso, bs_lds + buf * (STRIP * 8));
+            else *reinterpret_cast<v2d*>(BsS + buf * STRIP + wm * (STRIP / 2) + 2 * lane) = zero;
         }
     };
 
@@ -569,6 +663,29 @@ __device__ __forceinline__ void dgemm_glds_tile(const GemmK& g, const long gt, c
     }
     constexpr int A_FSTEP = AKC ? 16 * BK : 16;
     constexpr int B_FSTEP = BKC ? 16 * BK : 16;
+
+    // fat kinds: accumulators of the extra blocks, strip fragment offsets (A strip: row l15 of [16][16 k] swizzled as the
+    // tile; B strip: k-row kk * 4 + l4 of [16 k][16]), one strip fragment per operand buffer
+    v4d accm[2], accn[2], accc;
+    double ea[2], eb[2];
+    if constexpr (FAT != 0) accm[0] = accm[1] = accn[0] = accn[1] = accc = v4d{0.0, 0.0, 0.0, 0.0};
+    // (the A strip fragment's offset is the tile fragment's less the wave's row offset — a constant here —: the same address
+    // register with another immediate; the B strip fragment of k step kk is at lane + 64 kk)
+    auto read_strips = [&](int buf, int kk, int x) {
+        if constexpr (FATM) ea[x] = AsS[buf * STRIP + a_koff[kk] - (SEL & 1) * WM * BK];
+        if constexpr (FATN) eb[x] = BsS[buf * STRIP + kk * 64 + lane];
+    };
+    auto mfma_strips = [&](const double (&ra_)[FM], const double (&rb_)[FN], int x) {
+        if constexpr (FATM) {
+            accm[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(ea[x], rb_[XM], accm[0], 0, 0, 0);
+            accm[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(ea[x], rb_[XM + 1], accm[1], 0, 0, 0);
+        }
+        if constexpr (FATN) {
+            accn[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(ra_[XN], eb[x], accn[0], 0, 0, 0);
+            accn[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(ra_[XN + 1], eb[x], accn[1], 0, 0, 0);
+        }
+        if constexpr (CORNER) accc = __builtin_amdgcn_mfma_f64_16x16x4f64(ea[x], eb[x], accc, 0, 0, 0);
+    };
 
     double a[2][FM], b[2][FN];
     auto read_frags = [&](const double* as, const double* bs, int kk, double (&ra_)[FM], double (&rb_)[FN]) {
@@ -597,14 +714,24 @@ __device__ __forceinline__ void dgemm_glds_tile(const GemmK& g, const long gt, c
         const double* as = As + cur * A_TILE;
         const double* bs = Bs + cur * B_TILE;
         read_frags(as, bs, 1, a[1], b[1]);
+        read_strips(cur, 1, 1);
         mfma_step(a[0], b[0]);
+        mfma_strips(a[0], b[0], 0);
         read_frags(as, bs, 2, a[0], b[0]);
+        read_strips(cur, 2, 0);
         mfma_step(a[1], b[1]);
+        mfma_strips(a[1], b[1], 1);
         read_frags(as, bs, 3, a[1], b[1]);
+        read_strips(cur, 3, 1);
         mfma_step(a[0], b[0]);
+        mfma_strips(a[0], b[0], 0);
         landed();
-        if (next) read_frags(As + (cur ^ 1) * A_TILE, Bs + (cur ^ 1) * B_TILE, 0, a[0], b[0]);
+        if (next) {
+            read_frags(As + (cur ^ 1) * A_TILE, Bs + (cur ^ 1) * B_TILE, 0, a[0], b[0]);
+            read_strips(cur ^ 1, 0, 0);
+        }
         mfma_step(a[1], b[1]);
+        mfma_strips(a[1], b[1], 1);
     };
     const std::integral_constant<int, 0> buf0;
     const std::integral_constant<int, 1> buf1;
@@ -614,6 +741,7 @@ __device__ __forceinline__ void dgemm_glds_tile(const GemmK& g, const long gt, c
         else stage_tail(0, kbeg);
         landed();
         read_frags(As, Bs, 0, a[0], b[0]);
+        read_strips(0, 0, 0);
         int kt = 0;
         // steady state: the tile after the current one and the one after that are both full
         for (; kt + 2 < nfull; kt += 2) {
@@ -633,6 +761,25 @@ __device__ __forceinline__ void dgemm_glds_tile(const GemmK& g, const long gt, c
     }
 
     // ---- epilogue (as dgemm_kernel) -----------------------------------------------------------------
+    if constexpr (FAT != 0) {      // the extra blocks: block (mb, nb) of the tile's 9 x 8, 8 x 9 or 9 x 9
+        auto emit = [&](const v4d& v, int mb, int nb) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int mt = mb * 16 + l4 + 4 * r, nt = nb * 16 + l15;
+                if (Wpart) {
+                    Wpart[mt * WPITCH + nt] = v[r];
+                } else if (m0 + mt < g.M && n0 + nt < g.N) {
+                    const long off = z1 * g.c_b1 + z2 * g.c_b2 + (long)(m0 + mt) * g.ldc + (n0 + nt);
+                    double o = g.alpha * v[r];
+                    if (g.beta != 0.0) o += g.beta * g.Cin[off];
+                    g.C[off] = o;
+                }
+            }
+        };
+        if constexpr (FATM) { emit(accm[0], 8, 4 * wn + XM); emit(accm[1], 8, 4 * wn + XM + 1); }
+        if constexpr (FATN) { emit(accn[0], 4 * wm + XN, 8); emit(accn[1], 4 * wm + XN + 1, 8); }
+        if constexpr (CORNER) emit(accc, 8, 8);
+    }
     if (Wpart) {
         double* __restrict__ W = Wpart;
 #pragma unroll
@@ -641,7 +788,7 @@ __device__ __forceinline__ void dgemm_glds_tile(const GemmK& g, const long gt, c
             for (int j = 0; j < FN; ++j)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    W[(wm * WM + i * 16 + l4 + 4 * r) * BN + wn * WN + j * 16 + l15] = acc[i][j][r];
+                    W[(wm * WM + i * 16 + l4 + 4 * r) * WPITCH + wn * WN + j * 16 + l15] = acc[i][j][r];
         return;
     }
     double* C = g.C + z1 * g.c_b1 + z2 * g.c_b2;
@@ -703,6 +850,58 @@ __global__ void __launch_bounds__(kThreads, 2) dgemm_glds_kernel(const GemmK g) 
                              : (b < g.whole ? xcd_remap(b, g.whole) : g.whole + xcd_remap(b - g.whole, (long)gridDim.x - g.whole));
     dgemm_glds_body<AKC, BKC>(g, id);
 }
+
+// The fat tiling's launch (GemmK::fat != 0): the same blocks, cuts and order; a block finds its tile's kind — plain, fat in
+// M, fat in N, both — and its wave's share of the extra blocks by a wave-uniform switch OUTSIDE the k loop, which is
+// instantiated per case.  A kernel of its own, so that dgemm_glds_kernel<true, false> stays the code object it was.
+__global__ void __launch_bounds__(kThreads, 2) dgemm_glds_fat_kernel(const GemmK g) {
+    const long b = blockIdx.x;
+    const long bid = !g.mixed ? xcd_remap(b, gridDim.x)
+                              : (b < g.whole ? xcd_remap(b, g.whole) : g.whole + xcd_remap(b - g.whole, (long)gridDim.x - g.whole));
+    long lt;
+    int ks;
+    bool cut;
+    if (g.mixed) {
+        if (bid < g.whole) { lt = bid; ks = 0; cut = false; }
+        else {
+            const long r = bid - g.whole;
+            ks = uni((int)(r / g.tail));
+            lt = g.whole + (r - (long)ks * g.tail);
+            cut = true;
+        }
+    } else {
+        lt = bid / g.nsplit;
+        ks = uni((int)(bid - lt * g.nsplit));
+        cut = g.nsplit > 1;
+    }
+    const int kbeg = cut ? ks * g.kchunk : 0;
+    const int kend = cut ? min(g.K, kbeg + g.kchunk) : g.K;
+    double* W = cut ? g.ws + ((lt - (g.mixed ? g.whole : 0)) * g.nsplit + ks) * glds_fat_slot(g.fat) : nullptr;
+    const long gt = g.tile_begin + lt;
+    int tm, tn;
+    gemm_tile_rc(g, gt, tm, tn);
+    const int kind = uni((((g.fat & 1) && tm == g.tiles_m - 1) ? 1 : 0) | (((g.fat & 2) && tn == g.tiles_n - 1) ? 2 : 0));
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    switch (kind) {
+        case 0: dgemm_glds_tile<true, false, 0, 0, true>(g, gt, kbeg, kend, W); break;
+        case 1:
+            if (wm) dgemm_glds_tile<true, false, 1, 1>(g, gt, kbeg, kend, W);
+            else dgemm_glds_tile<true, false, 1, 0>(g, gt, kbeg, kend, W);
+            break;
+        case 2:
+            if (wn) dgemm_glds_tile<true, false, 2, 2>(g, gt, kbeg, kend, W);
+            else dgemm_glds_tile<true, false, 2, 0>(g, gt, kbeg, kend, W);
+            break;
+        default:
+            switch (wave) {
+                case 0: dgemm_glds_tile<true, false, 3, 0>(g, gt, kbeg, kend, W); break;
+                case 1: dgemm_glds_tile<true, false, 3, 2>(g, gt, kbeg, kend, W); break;
+                case 2: dgemm_glds_tile<true, false, 3, 1>(g, gt, kbeg, kend, W); break;
+                default: dgemm_glds_tile<true, false, 3, 3>(g, gt, kbeg, kend, W); break;
+            }
+    }
+}
 // Grouped launch of mid-size products on the LDS-DMA kernel (A K-contiguous, B N-contiguous — the layout of the pair-packed
 // ladders and of every product with a symmetric pair matrix on the left): the four halves of the particle ladder and of
 // Q_kb at (20,80) are 26-52 tiles of 128 x 128 each, K ~ 3200 — alone each under-fills the chip and falls back to 64 x 64
@@ -726,19 +925,24 @@ __device__ __forceinline__ void splitk_reduce_body(const GemmK& g, const int BM,
     const int first_m = grp * GROUP;
     const int gm = min(g.tiles_m - first_m, GROUP);
     const int tin = t - grp * group_sz;
-    const int tm = first_m + tin % gm;
-    const int tn = tin / gm;
+    int tm = first_m + tin % gm;
+    int tn = tin / gm;
+    if (g.fat) gemm_tile_rc(g, gt, tm, tn);
     const long z1 = z / g.nb2, z2 = z - z1 * g.nb2;
     double* C = g.C + z1 * g.c_b1 + z2 * g.c_b2;
     const double* Cin = g.Cin + z1 * g.c_b1 + z2 * g.c_b2;
-    const double* __restrict__ W = g.ws + lt * g.nsplit * (long)(BM * BN);
+    // fat tiling (BM = BN = 128): the tile's own extents, [rows][width] in a slot sized for the launch's largest tile
+    const int bmt = ((g.fat & 1) && tm == g.tiles_m - 1) ? BM + 16 : BM;
+    const int bnt = ((g.fat & 2) && tn == g.tiles_n - 1) ? BN + 16 : BN;
+    const long st = g.fat ? glds_fat_slot(g.fat) : (long)BM * BN;
+    const double* __restrict__ W = g.ws + lt * g.nsplit * st;
     // blockIdx.y cuts the tile into 256-element pieces: a launch with few tiles and many splits (huge K, tiny
     // output) still spreads over the chip
     const int e = piece * 256 + threadIdx.x;
-    const int r = e / BN, c = e - r * BN;
+    if (e >= bmt * bnt) return;
+    const int r = e / bnt, c = e - r * bnt;
     const int m = tm * BM + r, n = tn * BN + c;
     if (m >= g.M || n >= g.N) return;
-    const long st = (long)BM * BN;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     int k = 0;
     for (; k + 16 <= g.nsplit; k += 16) {       // sixteen loads in flight (a chain of single loads is a latency chain:
@@ -3809,6 +4013,13 @@ void launch_gemm_glds(const GemmK& k, long nblocks, hipStream_t st) {
     launch_kernel(dgemm_glds_kernel<AKC, BKC>, dim3((unsigned)nblocks), dim3(kThreads), lds, st, k);
 }
 
+// fat tiling: the two operand tiles plus an A strip and a B strip of 2 KB per buffer; 2 x 77.8 KB still fit a CU's 160 KB
+void launch_gemm_glds_fat(const GemmK& k, long nblocks, hipStream_t st) {
+    constexpr size_t lds = (size_t)2 * (128 * BK + BK * (128 + 16) + 2 * 16 * BK) * sizeof(double);
+    allow_dynamic_lds<dgemm_glds_fat_kernel>(lds);
+    launch_kernel(dgemm_glds_fat_kernel, dim3((unsigned)nblocks), dim3(kThreads), lds, st, k);
+}
+
 // smallest K range per block that still goes to the LDS-DMA kernel (measured at (20,80), DESIGN 5: below it the
 // register-staged kernel wins)
 inline long dma_min_k() { return 384L; }
@@ -3952,6 +4163,27 @@ inline GemmK make_gemmk(const GemmProduct& p, int BM, int BN) {
     k.a_b1 = g.a_b1; k.a_b2 = g.a_b2; k.b_b1 = g.b_b1; k.b_b2 = g.b_b2; k.c_b1 = g.c_b1; k.c_b2 = g.c_b2;
     k.ws = nullptr;
     return k;
+}
+
+// Which ragged edges of a product on the LDS-DMA kernel are folded into fat tiles (GemmK::fat; 0: today's tiling).  Only the
+// layout with fat tile kinds (A K-contiguous, B N-contiguous), a remainder of 1..16 behind at least one full tile, and lane
+// offsets of the A strip (row 143) that still fit 32 bits.  By default only launches of at least 512 tiles of today's
+// tiling: a fat tile takes 9/8 tile-times, so folding pays where the launch runs several rounds of 256 tiles and the saved
+// row of edge tiles (7/8 of a tile-time each) is whole rounds' worth of MFMA work; a launch of one or two rounds lasts as
+// long as its longest block, which folding makes longer.  An explicit PYMES_GEMM_PLAN ("whole,cuts" of today's tile
+// count) keeps today's tiling.  PYMES_GEMM_FAT=0: never; =1: wherever the kernel supports it, and an explicit plan then
+// counts the fat tiling's tiles.
+inline int fat_edges(const GemmProduct& p, const GemmK& k, long tiles) {
+    if (!p.akc || p.bkc) return 0;
+    const char* e = getenv("PYMES_GEMM_FAT");
+    const int mode = e && *e ? atoi(e) : -1;
+    if (mode == 0) return 0;
+    if (mode != 1 && (tiles < 512 || getenv("PYMES_GEMM_PLAN"))) return 0;
+    int fat = 0;
+    const int rm = k.M % 128, rn = k.N % 128;
+    if (k.M > 128 && rm >= 1 && rm <= 16 && 144 * k.a_ld * 8 + 4096 < (1L << 32)) fat |= 1;
+    if (k.N > 128 && rn >= 1 && rn <= 16) fat |= 2;
+    return fat;
 }
 
 // k-split of the last, partially filled round of tiles (all of them for a small output).  Tiles all cost the same, so a
@@ -4570,6 +4802,22 @@ void gemm(const Gemm& g, stream_t s) {
                         (p.bkc ? 128 : 16) * k.b_ld * 8 + 4096 < (1L << 32);
     DmaPlan plan{tiles, 0, 1};
     if (dma_ok) plan = plan_dma(tiles, ktiles, ws_tiles);
+    if (const int fat = dma_ok ? fat_edges(p, k, tiles) : 0) {
+        // the fat tiling's tile count, its own plan and workspace slots; where the workspace (not the plan) bounds the cut
+        // of the fat tail, today's tiling stays
+        GemmK kf = k;
+        kf.fat = fat;
+        if (fat & 1) --kf.tiles_m;
+        if (fat & 2) --kf.tiles_n;
+        const long tiles_f = (long)kf.tiles_m * kf.tiles_n * p.nbatch;
+        const long ws_tiles_f = g.splitk_ws ? g.splitk_ws_doubles / glds_fat_slot(fat) : 0;
+        // (the same rule for the fat tile count: where the tail is smaller than the fat tiles' number, the rest of them are
+        // the last whole tiles — a round of whole tiles fewer to cut them all measured slower at 3600^3, 784 tiles, 55 fat:
+        // 512 + 272 / 5 1367 us against 768 + 16 / 8 1323, profiles/fat_edge/probe_fat_edge_3600.txt)
+        const DmaPlan pf = plan_dma(tiles_f, ktiles, ws_tiles_f), pu = plan_dma(tiles_f, ktiles, 1L << 40);
+        if (pf.whole == pu.whole && pf.s == pu.s) { k = kf; plan = pf; }
+    }
+    const long tiles_run = (long)k.tiles_m * k.tiles_n * p.nbatch;      // (== tiles unless the tiling is fat)
     // (per cut >= 256 deep on 128 x 128 tiles, 128 on smaller ones)
     const TailSplit ts = dma_ok ? TailSplit{tiles, 0, 1} : plan_tail(tiles, ktiles, slots, (BM == 128 && BN == 128) ? 16 : 8, ws_tiles);
 
@@ -4596,14 +4844,15 @@ void gemm(const Gemm& g, stream_t s) {
     int nsplit = 1;
     if (dma_ok) {
         // one grid: plan.whole whole tiles, then plan.tail tiles cut plan.s ways (ks-major); one reduction over the tail tiles
-        if (cut_k(ktiles, plan.s, &k) == 1) { plan.whole = tiles; plan.tail = 0; }
+        if (cut_k(ktiles, plan.s, &k) == 1) { plan.whole = tiles_run; plan.tail = 0; }
         k.mixed = 1;
         k.whole = plan.whole;
         k.tail = plan.tail;
         k.ws = plan.tail > 0 ? g.splitk_ws : nullptr;
         const long nblocks = plan.whole + plan.tail * k.nsplit;
         if (nblocks > 0x7fffffffL) throw std::runtime_error("gemm: grid too large");
-        if (p.akc && p.bkc) launch_gemm_glds<true, true>(k, nblocks, st);
+        if (k.fat) launch_gemm_glds_fat(k, nblocks, st);
+        else if (p.akc && p.bkc) launch_gemm_glds<true, true>(k, nblocks, st);
         else if (p.akc) launch_gemm_glds<true, false>(k, nblocks, st);
         else if (p.bkc) launch_gemm_glds<false, true>(k, nblocks, st);
         else launch_gemm_glds<false, false>(k, nblocks, st);
@@ -4613,7 +4862,8 @@ void gemm(const Gemm& g, stream_t s) {
             GemmK r = k;                   // the reduction sees the tail tiles as a launch of its own: ws[i][ks], i from 0
             r.tile_begin = plan.whole;
             r.mixed = 0;
-            launch_kernel(splitk_reduce_kernel, dim3((unsigned)plan.tail, 64u), dim3(256), 0, st, r, 128, 128);
+            const unsigned pieces = (unsigned)((k.fat ? glds_fat_slot(k.fat) : 16384L) / 256);      // 64, 72 or 81
+            launch_kernel(splitk_reduce_kernel, dim3((unsigned)plan.tail, pieces), dim3(256), 0, st, r, 128, 128);
             nsplit = -k.nsplit;            // logged as a negative split
         }
     } else {
@@ -4626,7 +4876,8 @@ void gemm(const Gemm& g, stream_t s) {
                            (long)g.M, (long)g.N, (long)g.K, (long)p.nbatch, BM, BN, g_stream64 ? "s" : "", (int)p.akc,
                            (int)p.bkc, p.vec, (int)used_dma, nsplit, p.flops);
         if (used_dma && len > 0 && len < (int)sizeof buf)
-            snprintf(buf + len, sizeof buf - len, " plan=%ld+%ld/%d", plan.whole, plan.tail, plan.tail ? k.nsplit : 1);
+            snprintf(buf + len, sizeof buf - len, "%s plan=%ld+%ld/%d", k.fat == 3 ? " fat=mn" : k.fat == 2 ? " fat=n" : k.fat ? " fat=m" : "",
+                     plan.whole, plan.tail, plan.tail ? k.nsplit : 1);
         span.finish(p.flops, used_dma ? 1 : 0, n_kernels, buf);
     }
 }

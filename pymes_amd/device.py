@@ -282,7 +282,12 @@ class Context:
                       None if in_view is None else i64_array(in_view[1]), float(beta), C.c_void_p(out.ptr), lo.encode(), None)
         return out
 
-    def dgemm(self, M, N, K, alpha, A, a_sm, a_sk, B, b_sk, b_sn, beta, Cmat, ldc):
+    def dgemm(self, M, N, K, alpha, A, a_sm, a_sk, B, b_sk, b_sn, beta, Cmat, ldc, Cin=None):
+        """``Cin``: the array the beta term is read from (C's layout); None: from ``Cmat`` itself."""
+        if Cin is not None:
+            self.lib.call("pymes_dgemm_cin", self.handle, M, N, K, float(alpha), C.c_void_p(A.ptr), a_sm, a_sk,
+                          C.c_void_p(B.ptr), b_sk, b_sn, float(beta), C.c_void_p(Cin.ptr), C.c_void_p(Cmat.ptr), ldc)
+            return
         self.lib.call("pymes_dgemm", self.handle, M, N, K, float(alpha), C.c_void_p(A.ptr), a_sm, a_sk,
                       C.c_void_p(B.ptr), b_sk, b_sn, float(beta), C.c_void_p(Cmat.ptr), ldc)
 

@@ -662,6 +662,31 @@ int pymes_sector_triples_lambda(pymes_ctx* ctx, int no, int nv, const double* ep
                                 const double* Lc_dev, const double* VvR_dev, const double* VoR_dev, const double* VvL_dev,
                                 const double* VoL_dev, int64_t t_begin, int64_t t_end, double* ws_dev, int64_t ws_bytes,
                                 double* per_triple_dev, double* e_out_host);
+/* Sector densities (pymes_amd/solver/ueg_cc.py, SectorDensity).
+ * pymes_sector_bin_sums: out[b] = beta out[b] + alpha sum_j src[list[j]], off[b] <= j < off[b + 1], b < nbins (int64 CSR on the
+ * device: nbins + 1 offsets; the sums of a density arena over the bins of the momentum transfer).  A workgroup owns four
+ * consecutive bins; a bin of at most 256 elements is summed by one wavefront, a longer one by the whole workgroup; each
+ * thread adds in ascending list order, then a fixed tree.  No atomics: identical calls give identical bits.  An empty bin
+ * gives alpha 0 (+ beta out[b]); with beta = 0 out is not read.  The kernel trusts the lists (the host checks them). */
+int pymes_sector_bin_sums(pymes_ctx* ctx, double* out_dev, int64_t nbins, const int64_t* off_dev, const int64_t* list_dev,
+                          const double* src_dev, double alpha, double beta);
+/* The V_abcd part of the transfer sums, never an array over the v^4 sectors: for every bin vector q = bin_q[b] (int32 [nbins,3])
+ *   out[b] = sum over the rows (a,b) of the pp layout with c = orb(k_a + q), d = orb(k_b - q) both virtual of
+ *            sum_ij lam[(a,b),ij] T[(c,d),ij].
+ * Row r of the pp layout: the virtual pair vv_pairs[r] (int32 [rows,2], counted from the first virtual), row_len[r] contiguous
+ * doubles from row_start[r] on in both compact vectors; row_of_pair[c nv + d] is the row of a virtual pair or -1.  k_int_dev,
+ * orb_of_dev, box_host: as pymes_sector_triples.  One workgroup owns a bin (at most max_groups workgroups stride over the
+ * bins; 0: one per bin); its threads stride over all rows in ascending order, then a fixed tree: no atomics, and the value
+ * of a bin has the same bits for every max_groups and every repetition.  A bin no row reaches is an exact +0.0. */
+int pymes_sector_pair_transfer(pymes_ctx* ctx, double* out_dev, int64_t nbins, const int32_t* bin_q_dev, const int32_t* k_int_dev,
+                               const int32_t* orb_of_dev, const int32_t* box_host, int no, int nv, int64_t rows,
+                               const int32_t* vv_pairs_dev, const int64_t* row_start_dev, const int64_t* row_len_dev,
+                               const int64_t* row_of_pair_dev, const double* lam_dev, const double* T_dev, int max_groups);
+/* gamma of the sector densities from the row sums rho[g] = sum_c x[g,c] y[g,c] of the direct layout (rows as
+ * pymes_sector_xdiag): gamma[no + a] = sum_i rho[row(a,i)], gamma[i] = -sum_a rho[row(a,i)], every sum in ascending order.
+ * gamma_dev: no + nv doubles; ws_dev: no nv doubles. */
+int pymes_sector_gamma(pymes_ctx* ctx, const double* x_dev, const double* y_dev, int no, int nv, const int64_t* row_start_dev,
+                       const int64_t* row_len_dev, const int64_t* row_of_dev, double* gamma_dev, double* ws_dev);
 
 /* ---- vector helpers for DIIS (pymes/mixer/diis.py:65-103) and norms ----------------- */
 /* out_host[p] = sum_i x[p][i]*y[p][i], npairs <= 16, deterministic reduction (synchronises) */

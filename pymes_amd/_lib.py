@@ -160,6 +160,12 @@ SIGNATURES = {
                                                                                           C.c_int64, C.c_void_p, c_double_p]),
     "pymes_sector_triples_lambda": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11 +
                                     [C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, c_double_p]),
+    # sector densities: bin sums of a density arena, the fused V_abcd transfer sums, gamma from row sums
+    "pymes_sector_bin_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                        C.c_double]),
+    "pymes_sector_pair_transfer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64]
+                                   + [C.c_void_p] * 6 + [C.c_int]),
+    "pymes_sector_gamma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
     "pymes_hf_fock_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pymes_fcidump_header": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pymes_fcidump_read_host": (C.c_int, [C.c_char_p, C.c_int, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -994,6 +994,23 @@ int pymes_sector_triples_lambda(pymes_ctx* ctx, int no, int nv, const double* ep
                                             ws_bytes, per_triple, e.stream);
     });
 }
+int pymes_sector_bin_sums(pymes_ctx* ctx, double* out, int64_t nbins, const int64_t* off, const int64_t* list, const double* src,
+                          double alpha, double beta) {
+    return guarded([&] { dev::sector_bin_sums(out, nbins, off, list, src, alpha, beta, E(ctx).stream); });
+}
+int pymes_sector_pair_transfer(pymes_ctx* ctx, double* out, int64_t nbins, const int32_t* bin_q, const int32_t* k_int,
+                               const int32_t* orb_of, const int32_t* box, int no, int nv, int64_t rows, const int32_t* vv_pairs,
+                               const int64_t* row_start, const int64_t* row_len, const int64_t* row_of_pair, const double* lam,
+                               const double* T, int max_groups) {
+    return guarded([&] {
+        dev::sector_pair_transfer(out, nbins, bin_q, k_int, orb_of, box, no, nv, rows, vv_pairs, row_start, row_len, row_of_pair,
+                                  lam, T, max_groups, E(ctx).stream);
+    });
+}
+int pymes_sector_gamma(pymes_ctx* ctx, const double* x, const double* y, int no, int nv, const int64_t* row_start,
+                       const int64_t* row_len, const int64_t* row_of, double* gamma, double* ws) {
+    return guarded([&] { dev::sector_gamma(x, y, no, nv, row_start, row_len, row_of, gamma, ws, E(ctx).stream); });
+}
 
 int pymes_dots(pymes_ctx* ctx, int npairs, const double* const* x, const double* const* y, int64_t n,
                double* out) {

@@ -563,5 +563,14 @@ double sector_triples_lambda(int no, int nv, const double* eps, const int32_t* k
                              const int32_t* box_host, const int32_t* m_of, const double* Tc, const double* Lc, const double* VvR,
                              const double* VoR, const double* VvL, const double* VoL, int64_t t_begin, int64_t t_end, double* ws,
                              int64_t ws_bytes, double* per_triple, stream_t s);
+// sector densities (include/pymes_amd.h, pymes_sector_bin_sums / _pair_transfer / _gamma)
+void sector_bin_sums(double* out, int64_t nbins, const int64_t* off, const int64_t* list, const double* src, double alpha,
+                     double beta, stream_t s);
+void sector_pair_transfer(double* out, int64_t nbins, const int32_t* bin_q, const int32_t* k_int, const int32_t* orb_of,
+                          const int32_t* box_host, int no, int nv, int64_t rows, const int32_t* vv_pairs, const int64_t* row_start,
+                          const int64_t* row_len, const int64_t* row_of_pair, const double* lam, const double* T, int max_groups,
+                          stream_t s);
+void sector_gamma(const double* x, const double* y, int no, int nv, const int64_t* row_start, const int64_t* row_len,
+                  const int64_t* row_of, double* gamma, double* ws, stream_t s);
 
 }  // namespace dev

@@ -934,4 +934,17 @@ __attribute__((weak)) double sector_triples_lambda(int, int, const double*, cons
                                                    stream_t) {
     throw std::runtime_error("sector_triples_lambda: not available in this backend");
 }
+__attribute__((weak)) void sector_bin_sums(double*, int64_t, const int64_t*, const int64_t*, const double*, double, double,
+                                           stream_t) {
+    throw std::runtime_error("sector_bin_sums: not available in this backend");
+}
+__attribute__((weak)) void sector_pair_transfer(double*, int64_t, const int32_t*, const int32_t*, const int32_t*, const int32_t*,
+                                                int, int, int64_t, const int32_t*, const int64_t*, const int64_t*, const int64_t*,
+                                                const double*, const double*, int, stream_t) {
+    throw std::runtime_error("sector_pair_transfer: not available in this backend");
+}
+__attribute__((weak)) void sector_gamma(const double*, const double*, int, int, const int64_t*, const int64_t*, const int64_t*,
+                                        double*, double*, stream_t) {
+    throw std::runtime_error("sector_gamma: not available in this backend");
+}
 }  // namespace dev

@@ -1,7 +1,8 @@
 // Kernels of the momentum-sector CCD / DCD path (pymes_amd/solver/ueg_cc.py; DESIGN "Momentum sectors"): a ragged batched
 // fp64 product over a device-resident task table, the gathers between the three sector layouts, and the element-wise tails;
 // and of the momentum-blocked (T) on the same path: the W slab, the energy partials and their ordered sum;
-// and the two-slab energy kernel of the Lambda-(T).
+// and the two-slab energy kernel of the Lambda-(T); and the bin sums, the fused V_abcd transfer sums and the gamma
+// sums of the sector densities.
 // Included at the end of kernels.hip (one code object for the library), not compiled on its own.
 #include <hip/hip_runtime.h>
 
@@ -416,6 +417,122 @@ struct OrderedSum {
     double value() const { return sum + carry; }
 };
 
+// ---- sector densities: sums of a density arena over the bins of the momentum transfer -------------------------------
+// out[b] = beta out[b] + alpha sum_j src[list[j]], off[b] <= j < off[b + 1].  A workgroup owns four consecutive bins.  A bin of
+// at most kBinShort elements is summed by one wavefront (lane l adds j = off + l, off + l + 64, ... in ascending order, then a
+// fixed tree over the 64 lanes); a longer one by the whole workgroup (256 strides, a tree over 256), one long bin after the
+// other.  Which of the two a bin takes depends on its length alone: no atomics, identical calls give identical bits.  With
+// beta == 0 out is not read.
+constexpr long kBinShort = 256;
+__global__ void __launch_bounds__(256) sector_bin_sums_kernel(double* __restrict__ out, long nbins, const long* __restrict__ off,
+                                                              const long* __restrict__ list, const double* __restrict__ src,
+                                                              double alpha, double beta) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const long b0 = blockIdx.x * 4L;
+    {
+        const long b = b0 + wave;
+        bool mine = false;
+        double acc = 0.0;
+        if (b < nbins) {
+            const long lo = off[b], hi = off[b + 1];
+            mine = hi - lo <= kBinShort;
+            if (mine)
+                for (long j = lo + lane; j < hi; j += 64) acc += src[list[j]];
+        }
+        red[tid] = acc;
+        __syncthreads();
+        for (int s = 32; s > 0; s >>= 1) {
+            if (lane < s) red[tid] += red[tid + s];
+            __syncthreads();
+        }
+        if (mine && lane == 0) {
+            const double v = alpha * red[tid];
+            out[b] = beta == 0.0 ? v : beta * out[b] + v;
+        }
+        __syncthreads();
+    }
+    for (int w = 0; w < 4; ++w) {
+        const long b = b0 + w;
+        if (b >= nbins) break;
+        const long lo = off[b], hi = off[b + 1];
+        if (hi - lo <= kBinShort) continue;             // (the same for every thread of the workgroup)
+        double acc = 0.0;
+        for (long j = lo + tid; j < hi; j += 256) acc += src[list[j]];
+        red[tid] = acc;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) red[tid] += red[tid + s];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const double v = alpha * red[0];
+            out[b] = beta == 0.0 ? v : beta * out[b] + v;
+        }
+        __syncthreads();
+    }
+}
+
+// The V_abcd part of the transfer sums without an array over the v^4 sectors: for the bin vector q,
+//   out[bin] = sum over rows (a,b) of the pp layout with c = orb(k_a + q) and d = orb(k_b - q) both virtual of
+//              sum_ij lam[(a,b),ij] T[(c,d),ij]
+// (k_c + k_d = k_a + k_b, so the row (c,d) lies in the sector of (a,b) and has as many columns).  row_of_pair[c nv + d] is the
+// row of the virtual pair, -1 if it has none.  One workgroup owns a bin and the workgroups stride over the bins: thread t
+// takes the rows t, t + 256, ... in ascending order, each dot in ascending ij, then a fixed tree over the 256 partials -- the
+// value of a bin does not depend on the grid.  A bin that no row reaches is an exact +0.0.
+__global__ void __launch_bounds__(256) sector_pair_transfer_kernel(
+        double* __restrict__ out, long nbins, const int* __restrict__ bin_q, const int* __restrict__ k_int,
+        const int* __restrict__ orb_of, TriplesBox bx, int no, int nv, long rows, const int* __restrict__ vv_pairs,
+        const long* __restrict__ row_start, const long* __restrict__ row_len, const long* __restrict__ row_of_pair,
+        const double* __restrict__ lam, const double* __restrict__ T) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    for (long bin = blockIdx.x; bin < nbins; bin += gridDim.x) {
+        const int qx = bin_q[3 * bin], qy = bin_q[3 * bin + 1], qz = bin_q[3 * bin + 2];
+        double acc = 0.0;
+        for (long r = tid; r < rows; r += 256) {
+            const int a = no + vv_pairs[2 * r], b = no + vv_pairs[2 * r + 1];
+            const int c = triples_orb(orb_of, bx, k_int[3 * a] + qx, k_int[3 * a + 1] + qy, k_int[3 * a + 2] + qz);
+            if (c < no) continue;
+            const int d = triples_orb(orb_of, bx, k_int[3 * b] - qx, k_int[3 * b + 1] - qy, k_int[3 * b + 2] - qz);
+            if (d < no) continue;
+            const long r2 = row_of_pair[(long)(c - no) * nv + (d - no)];
+            if (r2 < 0) continue;
+            const long len = row_len[r];
+            const double* __restrict__ x = lam + row_start[r];
+            const double* __restrict__ y = T + row_start[r2];
+            double dot = 0.0;
+            for (long j = 0; j < len; ++j) dot = fma(x[j], y[j], dot);
+            acc += dot;
+        }
+        red[tid] = acc;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) red[tid] += red[tid + s];
+            __syncthreads();
+        }
+        if (tid == 0) out[bin] = red[0];
+        __syncthreads();
+    }
+}
+
+// rho[g] = sum_c x[g,c] y[g,c] over the rows of the direct layout (the kernel of sector_xdiag, which keeps its sums to itself);
+// gamma[no + a] = sum_i rho[row(a,i)], gamma[i] = -sum_a rho[row(a,i)], in ascending order
+__global__ void sector_gamma_kernel(const double* __restrict__ rho, const long* __restrict__ row_of, int no, int nv,
+                                    double* __restrict__ gamma) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= no + nv) return;
+    double acc = 0.0;
+    if (p < no) {
+        for (long a = 0; a < nv; ++a) acc += rho[row_of[a * no + p]];
+        gamma[p] = -acc;
+    } else {
+        const long a = p - no;
+        for (int i = 0; i < no; ++i) acc += rho[row_of[a * no + i]];
+        gamma[p] = acc;
+    }
+}
+
 }  // namespace
 
 namespace dev {
@@ -540,6 +657,44 @@ double sector_triples_lambda(int no, int nv, const double* eps, const int32_t* k
         for (int q = 0; q < n; ++q) total.add(host[q]);       // in triple order, whatever the batch size
     }
     return total.value();
+}
+
+void sector_bin_sums(double* out, int64_t nbins, const int64_t* off, const int64_t* list, const double* src, double alpha,
+                     double beta, stream_t s) {
+    if (nbins < 0 || nbins > 4 * 0x7fffffffL) throw std::runtime_error("sector_bin_sums: bad bin count");
+    if (nbins == 0) return;
+    if (!out || !off || !list || !src) throw std::runtime_error("sector_bin_sums: null argument");
+    launch_kernel(sector_bin_sums_kernel, dim3((unsigned)((nbins + 3) / 4)), dim3(256), 0, (hipStream_t)s, out, (long)nbins,
+                  reinterpret_cast<const long*>(off), reinterpret_cast<const long*>(list), src, alpha, beta);
+}
+
+void sector_pair_transfer(double* out, int64_t nbins, const int32_t* bin_q, const int32_t* k_int, const int32_t* orb_of,
+                          const int32_t* box_host, int no, int nv, int64_t rows, const int32_t* vv_pairs, const int64_t* row_start,
+                          const int64_t* row_len, const int64_t* row_of_pair, const double* lam, const double* T, int max_groups,
+                          stream_t s) {
+    if (no < 1 || nv < 1 || nv > (1 << 20)) throw std::runtime_error("sector_pair_transfer: bad orbital counts");
+    if (nbins < 0 || rows < 0 || max_groups < 0) throw std::runtime_error("sector_pair_transfer: negative count");
+    if (nbins == 0) return;
+    if (!out || !bin_q || !k_int || !orb_of || !box_host || !vv_pairs || !row_start || !row_len || !row_of_pair || !lam || !T)
+        throw std::runtime_error("sector_pair_transfer: null argument");
+    const TriplesBox bx = triples_box("sector_pair_transfer", box_host);
+    int64_t grid = std::min<int64_t>(nbins, 0x7fffffffL);
+    if (max_groups > 0) grid = std::min<int64_t>(grid, max_groups);
+    launch_kernel(sector_pair_transfer_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)s, out, (long)nbins, bin_q, k_int,
+                  orb_of, bx, no, nv, (long)rows, vv_pairs, reinterpret_cast<const long*>(row_start),
+                  reinterpret_cast<const long*>(row_len), reinterpret_cast<const long*>(row_of_pair), lam, T);
+}
+
+void sector_gamma(const double* x, const double* y, int no, int nv, const int64_t* row_start, const int64_t* row_len,
+                  const int64_t* row_of, double* gamma, double* ws, stream_t s) {
+    if (no < 1 || nv < 1) throw std::runtime_error("sector_gamma: bad orbital counts");
+    if (!x || !y || !row_start || !row_len || !row_of || !gamma || !ws) throw std::runtime_error("sector_gamma: null argument");
+    const long rows = (long)no * nv;
+    hipStream_t st = (hipStream_t)s;
+    launch_kernel(sector_rowsum_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, x, y,
+                  reinterpret_cast<const long*>(row_start), reinterpret_cast<const long*>(row_len), rows, ws);
+    launch_kernel(sector_gamma_kernel, dim3((unsigned)((no + nv + 63) / 64)), dim3(64), 0, st, (const double*)ws,
+                  reinterpret_cast<const long*>(row_of), no, nv, gamma);
 }
 
 }  // namespace dev

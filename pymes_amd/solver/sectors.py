@@ -325,6 +325,82 @@ class TriplesTables:
         return np.append(T, 0.0)[self.implied_map]
 
 
+class TransferBins:
+    """The bins of the momentum transfer q = k_r - k_p of an element (p,q,r,s), for the transfer sums and the structure
+    factor of the sector densities, from a `SectorTables`.  Host side, numpy only.
+
+      q, neg, zero    the bin vectors (every k_r - k_p over all orbital pairs, sorted by key: closed under negation, also on
+                      twisted bases), the bin of -q, the bin of q = 0
+      csr[name]       per stored family of `BLOCKS`: (offsets int64 [bins + 1], element indices int64 grouped by bin, each
+                      group ascending).  ``abcd`` has none: its sums come from the rows of the pp layout (``pair_rows``)
+      oo_count        per bin, the number of occupied pairs (i,j) with k_j - k_i = q
+      ip_off, ip_orb  per bin, the orbitals p of the pairs (i occupied, p) with k_i - k_p = q
+    """
+
+    STORED = tuple(nm for nm in BLOCKS if nm != "abcd")
+
+    def __init__(self, tables):
+        if not isinstance(tables, SectorTables):
+            raise TypeError("TransferBins: a SectorTables is needed")
+        self.tables = tables
+        k, no, n = tables.k_int, tables.no, tables.n
+        bound = 2 * int(np.abs(k).max()) + 1
+        side = 2 * bound + 1
+        self._key = lambda v: ((v[..., 0] + bound) * side + v[..., 1] + bound) * side + v[..., 2] + bound
+        diff = self._key(k[None, :, :] - k[:, None, :])                        # [p, r]: k_r - k_p
+        self.keys = np.unique(diff)
+        x = self.keys
+        self.q = np.stack([x // (side * side) - bound, x // side % side - bound, x % side - bound], axis=-1)
+        self.nbins = len(x)
+        self.neg = np.searchsorted(x, self._key(-self.q))
+        if not np.array_equal(x[self.neg], self._key(-self.q)):
+            raise AssertionError("TransferBins: the bins are not closed under negation")
+        self.zero = int(np.searchsorted(x, self._key(np.zeros(3, dtype=np.int64))))
+        self.csr = {}
+        for name in self.STORED:
+            pqrs = tables.block_pqrs(name)
+            self.csr[name] = self._group(np.searchsorted(x, self._key(k[pqrs[:, 2]] - k[pqrs[:, 0]])))
+        oo = np.searchsorted(x, diff[:no, :no].reshape(-1))
+        self.oo_count = np.bincount(oo, minlength=self.nbins).astype(np.int64)
+        ip = np.searchsorted(x, diff[:, :no].reshape(-1))                       # [p, i]: k_i - k_p
+        self.ip_off, order = self._group(ip)
+        self.ip_orb = order // no
+
+    def _group(self, bins):
+        off = np.concatenate(([0], np.cumsum(np.bincount(bins, minlength=self.nbins)))).astype(np.int64)
+        return off, np.argsort(bins, kind="stable").astype(np.int64)
+
+    def bin_of(self, vec):
+        """The bin of every integer vector of `vec` [..., 3], -1 where it is no bin."""
+        key = self._key(np.asarray(vec, dtype=np.int64))
+        pos = np.minimum(np.searchsorted(self.keys, key), self.nbins - 1)
+        return np.where(self.keys[pos] == key, pos, -1)
+
+    def pair_rows(self):
+        """The rows of the pp layout as ``pymes_sector_pair_transfer`` takes them: (vv_pairs int32 [rows,2], row_start int64,
+        row_len int64, row_of_pair int64 [nv nv], -1 where a virtual pair has no row)."""
+        t = self.tables
+        sec = np.repeat(np.arange(len(t.P_keys)), t.n_vv)
+        local = np.arange(len(sec)) - t.vv_off[sec]
+        row_start = (t.pp_off[sec] + local * t.n_oo[sec]).astype(np.int64)
+        row_of_pair = np.full(t.nv * t.nv, -1, dtype=np.int64)
+        row_of_pair[t.vv_pairs[:, 0] * t.nv + t.vv_pairs[:, 1]] = np.arange(len(sec))
+        return t.vv_pairs.astype(np.int32), row_start, t.n_oo[sec].astype(np.int64), row_of_pair
+
+    def shells(self):
+        """(|q|^2 of every shell, ascending; the shell of every bin): the bins grouped for the spherical average."""
+        q2 = (self.q * self.q).sum(axis=1)
+        values, shell = np.unique(q2, return_inverse=True)
+        return values, shell.reshape(-1)
+
+    def reference_terms(self, gamma):
+        """Per bin, the part of N (S(q) - 1) that the reference determinant and gamma give at q != 0 (``full_rdm2``):
+        -2 #{(i,j): k_j - k_i = q} - sum_{i,p: k_i - k_p = q} gamma_p - sum_{i,p: k_p - k_i = q} gamma_p."""
+        which = np.repeat(np.arange(self.nbins), np.diff(self.ip_off))
+        g = np.bincount(which, weights=np.asarray(gamma, dtype=np.float64)[self.ip_orb], minlength=self.nbins)
+        return -2.0 * self.oo_count - (g + g[self.neg])          # (even in q to the bit: the sum of two terms commutes)
+
+
 TASK_DTYPE = np.dtype([("m", "<i8"), ("n", "<i8"), ("k", "<i8"), ("a", "<i8"), ("b", "<i8"), ("c", "<i8"), ("lda", "<i8"),
                        ("ldb", "<i8"), ("ldc", "<i8"), ("flags", "<i8"), ("tile0", "<i8"), ("alpha", "<f8"), ("beta", "<f8"),
                        ("reserved", "<i8")])       # pymes_sector_task of include/pymes_amd.h

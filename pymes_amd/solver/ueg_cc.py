@@ -10,7 +10,9 @@ untouched.
 
 On the same tables: the perturbative triples (``sector_triples_energy``), and for integrals without
 V_pqrs = V_rspq (the transcorrelated electron gas) the Lambda equations of CCD and DCD as the transposed Jacobian of that
-residual (``SectorLambda``) with the Lambda-(T) correction on top (``sector_lambda_triples_energy``)."""
+residual (``SectorLambda``) with the Lambda-(T) correction on top (``sector_lambda_triples_energy``); and from
+the amplitudes and their Lambda the response densities (``sector_density`` / ``SectorDensity``): the momentum
+distribution n(k), the expectation value of a second two-body operator, the transfer sums and the static structure factor S(q)."""
 import ctypes as C
 import os
 import time
@@ -28,7 +30,7 @@ from pymes_amd.solver import ccsd_t
 from pymes_amd.solver.sectors import BLOCKS, FOCK_LISTS, SectorTables, TriplesTables
 
 __all__ = ["SectorTables", "SectorIntegrals", "SectorAmplitudes", "SectorCCD", "TriplesTables", "SectorTriplesIntegrals",
-           "sector_triples_energy", "SectorLambda", "sector_lambda_triples_energy"]
+           "sector_triples_energy", "SectorLambda", "sector_lambda_triples_energy", "SectorDensity", "sector_density"]
 
 
 def upload_raw(ctx, host):
@@ -110,6 +112,7 @@ class DeviceTables:
         self.square_left_add = table(S, F, F, beta=1.0)                           # Ed^q += Y^q (C^q - D^q)
         self.square_left = table(S, F, F)                                         # Rc^q = Xc^q C^q
         self._adjoint = None
+        self._density = None
 
     def adjoint(self):
         """The task tables and maps of the Lambda residual (``SectorLambda``): every product of the list above
@@ -152,6 +155,31 @@ class DeviceTables:
         at.pp_swap = imap(tab.pp_swap)
         self._adjoint = at
         return at
+
+    def density(self):
+        """The task tables of ``SectorDensity``: every product of the list above with the operand that held an
+        integral block exchanged for the output (outer-product shapes), next to those of ``adjoint()``; built on first use."""
+        if self._density is not None:
+            return self._density
+        ctx, tab, at = self.ctx, self.tab, self.adjoint()
+        F, S, Fn, Sn = ("ph", "ph-", False), ("ph", "ph", False), ("ph", "ph-", True), ("ph", "ph", True)
+        vo, oo, ov = ("vv", "oo", False), ("oo", "oo", False), ("oo", "vv", False)
+        size = lambda op: int(tab.offsets(*op[:2])[-1])
+
+        def table(a, b, c, **kw):
+            return Tasks(ctx, tab.gemm_tasks(a, b, c, **kw), size(a), size(b), size(c))
+
+        class Density:
+            pass
+        dn = Density()
+        dn.t_lam, dn.sq_tn, dn.outer, dn.left_tn_add = at.t_lam, at.sq_tn, at.outer, at.left_tn_add
+        dn.m_tt = table(oo, vo, ov, trans_b=True)                              # G_klcd^P = M^P (T^P)^T
+        dn.sq_right_t = table(S, Fn, F, trans_b=True)                          # G_w1^q = Z^q (Tt^{-q})^T
+        dn.outer_neg = table(F, F, S, alpha=-1.0, trans_b=True)                # G_wa^q = -yEd^q (D^q)^T
+        dn.sq_tn_sub = table(Fn, Fn, S, alpha=-1.0, beta=1.0, trans_a=True)    # G_wa^q -= (yEc^{-q})^T C^{-q}
+        dn.left_tn = table(Fn, Sn, F, trans_a=True)                            # G_wx^q = (D^{-q})^T zY^{-q}
+        self._density = dn
+        return dn
 
 
 class SectorIntegrals:
@@ -568,13 +596,16 @@ class SectorCCD:
                              "(V_pqrs = V_qpsr), which the sector residual needs")
         return eps
 
-    def solve(self, eps, ints, level_shift=0., amps=None, triples=None, lambda_triples=None, **kwargs):
+    def solve(self, eps, ints, level_shift=0., amps=None, triples=None, lambda_triples=None, density=False, **kwargs):
         """The loop of ``CCD.solve`` (ccd.py:24-162) on the compact vector.  eps: the orbital energies (or a diagonal Fock
         matrix); ints: ``SectorIntegrals``.  ``triples``: the ``SectorTriplesIntegrals`` of the same tables; the result then
         also holds "(t) e" (``sector_triples_energy`` of the final amplitudes) and "ccd(t) e".  ``lambda_triples``: the
         ``SectorTriplesIntegrals`` with both sides (``UEG.eval_2b_triples(..., both_sides=True)``), for integrals without
         V_pqrs = V_rspq: Lambda is solved after the amplitudes (``SectorLambda``, threshold ``lambda_threshold``, default
-        1e-8) and the result also holds "lambda2", "lambda (t) e" (``sector_lambda_triples_energy``) and "ccd(t)_lambda e"."""
+        1e-8) and the result also holds "lambda2", "lambda (t) e" (``sector_lambda_triples_energy``) and "ccd(t)_lambda e".
+        ``density``: Lambda is solved (once; shared with ``lambda_triples``) and the result also holds "lambda2", "lambda
+        residual", "density" (the ``SectorDensity``), "n(k)", "density e" (L(eps, ints): the correlation energy again, from
+        the densities), "structure factor" and "structure factor q" (DESIGN 8l)."""
         algo_name = "ccd.solve"
         time_ccd = time.time()
         eps = self._checks(eps, ints)
@@ -648,10 +679,18 @@ class SectorCCD:
                 out["(t) e"] = sector_triples_energy(eps, ints, triples, out["t2 amp"])
                 out["ccd(t) e"] = e_ccd + out["(t) e"]
                 print_logging_info("(T) correction = {:.12f}".format(out["(t) e"]), level=1)
-            if lambda_triples is not None:
+            if lambda_triples is not None or density:
                 left = SectorLambda(no, kwargs.get("lambda_threshold", 1.e-8), is_dcd=self.is_dcd, is_diis=self.is_diis)
                 lam = left.solve(eps, ints, out["t2 amp"], level_shift=level_shift, max_iter=kwargs.get("lambda_max_iter", 100))
                 out["lambda2"] = lam["lambda2"]
+            if density:
+                out["lambda residual"] = lam["lambda residual"]
+                dens = sector_density(eps, ints, out["t2 amp"], lam["lambda2"], is_dcd=self.is_dcd)
+                out["density"], out["n(k)"] = dens, dens.momentum_distribution()
+                out["density e"] = dens.lagrangian(eps, ints)
+                out["structure factor"], out["structure factor q"] = dens.structure_factor()
+                print_logging_info("Energy from the densities = {:.12f}".format(out["density e"]), level=1)
+            if lambda_triples is not None:
                 out["lambda (t) e"] = sector_lambda_triples_energy(eps, ints, lambda_triples, out["t2 amp"], lam["lambda2"])
                 out["ccd(t)_lambda e"] = e_ccd + out["lambda (t) e"]
                 print_logging_info("Lambda residual norm = {:.3e} after {} iterations".format(lam["lambda residual"],
@@ -844,3 +883,245 @@ class SectorLambda:
             ctx.pool_put(g2)
             return {"lambda2": SectorAmplitudes(tab, result), "lambda residual": norm, "iterations": iteration,
                     "converged": converged}
+
+
+def _diagonal_eps(who, tab, eps):
+    eps = np.asarray(eps, dtype=np.float64)
+    if eps.ndim == 2:
+        if np.count_nonzero(eps - np.diag(eps.diagonal())):
+            raise ValueError(who + ": the Fock matrix must be diagonal (it is for a momentum-conserving Hamiltonian)")
+        eps = eps.diagonal().copy()
+    if eps.shape != (tab.n,):
+        raise ValueError(who + ": %d orbital energies for %d orbitals" % (eps.size, tab.n))
+    return eps
+
+
+def sector_density(eps, ints, amps, lam, is_dcd=False):
+    """The one- and two-particle response densities of the momentum-sector CCD / DCD (``SectorDensity``) for
+    amplitudes and their Lambda (``SectorLambda``; both ``SectorAmplitudes``, a compact vector or a dense [v,v,o,o] array,
+    exchange-symmetric).  eps: the orbital energies (or a diagonal Fock matrix); ints: the ``SectorIntegrals`` whose tables
+    and context the density lives in (the densities themselves do not read the integrals).  Refused: anything but
+    ``SectorIntegrals``, amplitudes of other tables, off the support or not symmetric, a non-diagonal Fock matrix, a recording
+    context."""
+    who = "sector_density"
+    if not isinstance(ints, SectorIntegrals):
+        raise TypeError(who + ": ints must be SectorIntegrals (UEG.eval_2b_sectors); the dense path is Lambda_CCSD.rdm2")
+    tab = ints.tables
+    if ints.ctx.recording:
+        raise RuntimeError(who + ": the context is recording a launch graph")
+    eps = _diagonal_eps(who, tab, eps)
+    vec = _symmetric_compact(who, tab, amps, "the amplitudes are")
+    lvec = _symmetric_compact(who, tab, lam, "lambda is")
+    return SectorDensity(ints, eps, vec, lvec, is_dcd)
+
+
+class SectorDensity:
+    """gamma and the density arena G of L(eps, V) = E(T; V) + <lam, R(T; eps, V)> at fixed (T, lam) on the momentum sectors
+    (DESIGN 8l): gamma_p = dL/d eps_p (diagonal: momentum is conserved), G = dL/d(arena), one number per stored integral element
+    of every family of ``sectors.BLOCKS`` but ``abcd``, whose part is formed on the fly (<lam, W_abcd T> through the ladder
+    product; the fused ``pymes_sector_pair_transfer`` for the transfer sums).  L is linear in (eps, V), so for every operator W
+    held as ``SectorIntegrals``, L(eps_W, W) = gamma . eps_W + <G, W>.  Built as the term-by-term adjoint of the product list of
+    ``SectorCCD.residual`` with respect to its integral operands (tests/_sector_density_reference.py), so DCD has one too.
+    Made by ``sector_density``."""
+
+    FAMILIES = sectors.TransferBins.STORED
+
+    def __init__(self, ints, eps, vec, lvec, is_dcd=False):
+        ctx, tab = ints.ctx, ints.tables
+        self.ctx, self.tables, self.is_dcd, self.eps = ctx, tab, bool(is_dcd), eps
+        self._dt = ints.device_tables()
+        sizes = [ints.sizes[nm] for nm in self.FAMILIES]
+        self.offsets = dict(zip(self.FAMILIES, np.concatenate(([0], np.cumsum(sizes)))[:-1]))
+        self.sizes = dict(zip(self.FAMILIES, sizes))
+        self.arena = ctx.empty((max(int(sum(sizes)), 1),))
+        self.gamma = ctx.empty((tab.n,))
+        self.T, self.lam = ctx.array(vec), ctx.array(lvec)
+        self._bins = self._bins_dev = None
+        self._build()
+
+    def __getitem__(self, name):
+        return view(self.arena, self.offsets[name], self.sizes[name])
+
+    def _build(self):
+        ctx, tab, dt = self.ctx, self.tables, self._dt
+        at, dn = dt.adjoint(), dt.density()
+        quad = not self.is_dcd
+        nnz, nsq = max(tab.nnz, 1), max(dt.nsq, 1)
+        T, lam = self.T, self.lam
+        D, Cx, Tt, yRd, yRc, yEd, yEc = (ctx.empty((nnz,)) for _ in range(7))
+        Z = ctx.empty((nsq,))
+        # the simple members: G_abij = lam, G_ed = 2 T, G_ex = -T, and the pp layout
+        self["abij"].copy_from(lam)
+        ctx.lincomb(self["ed"], [T], [2.0])
+        ctx.lincomb(self["ex"], [T], [-1.0])
+        M = self["klij"]
+        dn.t_lam.run(T, lam, M)                                  # G_klij^P = M^P = (T^P)^T lam^P
+        if quad:
+            dn.m_tt.run(M, T, self["klcd"])                      # G_klcd^P = M^P (T^P)^T
+        else:
+            self["klcd"].zero_()
+            self["wx"].zero_()
+        # the ph layouts of T and the cotangents of Rd, Rc, Ed, Ec (the first rows of the table of DESIGN 8k)
+        gather(ctx, D, T, dt.d_from_pp)
+        gather(ctx, Cx, T, dt.c_from_pp)
+        gather(ctx, Tt, T, dt.d_from_pp, 2.0, T, dt.c_from_pp, -1.0)
+        gather(ctx, yRd, lam, dt.d_from_pp)
+        gather(ctx, yRc, lam, dt.c_from_pp)
+        gather(ctx, yEd, lam, dt.d_from_pp, 1.0, lam, at.dT_from_pp, 1.0)
+        gather(ctx, yEc, lam, dt.c_from_pp, 1.0, lam, at.cT_from_pp, 1.0)
+        dn.sq_tn.run(Tt, yRd, Z)                                 # Z^q = (Tt^{-q})^T yRd^{-q}          (of X = W1 Tt)
+        dn.sq_right_t.run(Z, Tt, self["w1"])                     # G_w1^q = Z^q (Tt^{-q})^T
+        dn.sq_tn.run(Tt, yEd, self["w2"])                        # G_w2^q = (Tt^{-q})^T yEd^{-q}       (Ed = Tt W2)
+        dn.outer_neg.run(yEd, D, self["wa"])                     # G_wa^q = -yEd^q (D^q)^T             (Ed -= Wa D)
+        dn.sq_tn_sub.run(yEc, Cx, self["wa"])                    # G_wa^q -= (yEc^{-q})^T C^{-q}       (Ec = -C Wa^T)
+        if quad:
+            CmD = ctx.empty((nnz,))
+            gather(ctx, CmD, T, dt.c_from_pp, 1.0, T, dt.d_from_pp, -1.0)
+            dn.outer.run(yEd, CmD, Z)                            # zY^q = yEd^q (C^q - D^q)^T
+            dn.left_tn.run(D, Z, self["wx"])                     # G_wx^q = (D^{-q})^T zY^{-q}         (Y = D Wx)
+            dn.outer.run(yRc, Cx, Z)                             # zXc^q = yRc^q (C^q)^T
+            dn.left_tn_add.run(Cx, Z, self["wx"])                # G_wx^q += (C^{-q})^T zXc^{-q}       (Xc = C Wx)
+        # the diagonal X_ac / X_ki term: rho the row sums of yEd o D; gamma is rho summed by orbital, and its W1 part
+        # G_w1[g,:] -= w (rho_a + rho_i) Tt[g,:] is the second call of SectorLambda.residual with W1 and Tt exchanged
+        rows = (C.c_void_p(dt.row_start.ptr), C.c_void_p(dt.row_len.ptr), C.c_void_p(dt.row_of.ptr))
+        scratch, zero = ctx.empty((tab.no * tab.nv + tab.n,)), ctx.zeros((tab.n,))
+        ctx.lib.call("pymes_sector_gamma", ctx.handle, C.c_void_p(yEd.ptr), C.c_void_p(D.ptr), tab.no, tab.nv, *rows,
+                     C.c_void_p(self.gamma.ptr), C.c_void_p(scratch.ptr))
+        ctx.lib.call("pymes_sector_xdiag", ctx.handle, C.c_void_p(yEd.ptr), C.c_void_p(D.ptr), C.c_void_p(Tt.ptr),
+                     C.c_void_p(self["w1"].ptr), C.c_void_p(zero.ptr), 1.0 if quad else 0.5, tab.no, tab.nv, *rows,
+                     C.c_void_p(dt.ai_of.ptr), C.c_void_p(scratch.ptr))
+
+    # ---- one-body ---------------------------------------------------------------------------------------------------
+    def momentum_distribution(self):
+        """n(k_p) = gamma_p + 2 [p occupied], per orbital (host array)."""
+        n = self.gamma.get()
+        n[:self.tables.no] += 2.0
+        return n
+
+    # ---- expectation values -----------------------------------------------------------------------------------------
+    def _operator(self, who, W):
+        if not isinstance(W, SectorIntegrals):
+            raise TypeError(who + ": W must be SectorIntegrals (UEG.eval_2b_sectors)")
+        if W.tables is not self.tables or W.ctx is not self.ctx:
+            raise ValueError(who + ": W belongs to other tables or another context than the density")
+        if self.ctx.recording:
+            raise RuntimeError(who + ": the context is recording a launch graph")
+        w1 = W["w1"].get()
+        if len(w1) and np.abs(w1 - w1[self.tables.d_partner]).max() > 1e-12 * max(np.abs(w1).max(), 1e-300):
+            raise ValueError(who + ": W is not symmetric under the exchange of the two electrons (W_pqrs = W_qpsr), which "
+                             "the sector densities need")
+
+    def lagrangian(self, eps, W):
+        """L(eps, W) = gamma . eps + <G, W>: one fixed-tree dot per stored family, <lam, W_abcd T> for the ladder block."""
+        who = "SectorDensity.lagrangian"
+        self._operator(who, W)
+        return self._lagrangian(_diagonal_eps(who, self.tables, eps), W)
+
+    def _lagrangian(self, eps, W):
+        ctx, tab = self.ctx, self.tables
+        ladder = ctx.zeros((max(tab.nnz, 1),))
+        self._dt.ladder.run(W["abcd"], self.T, ladder)
+        live = [nm for nm in self.FAMILIES if self.sizes[nm]]
+        xs, ys = [self[nm] for nm in live], [W[nm] for nm in live]
+        if tab.nnz:
+            xs, ys = xs + [self.lam], ys + [view(ladder, 0, tab.nnz)]
+        d = ctx.dots(xs + [self.gamma], ys + [ctx.array(eps)])
+        return float(np.sum(d))
+
+    def expectation(self, W, one_body=None, mean_field=True):
+        """The expectation value of the two-body operator W (``SectorIntegrals`` with W_pqrs = W_qpsr) and, if given, of the
+        diagonal one-body operator ``one_body`` (one number per orbital): L(one_body + f_HF[W], W), f_HF[W]_p =
+        sum_i (2 W_pipi - W_piip) as in ``hf_orbital_energies``, without the reference determinant's own value.  With W the
+        Hamiltonian's integrals and the kinetic energies it is the correlation energy of converged amplitudes.
+        ``mean_field=False`` leaves f_HF[W] out, L(one_body, W): the derivative of the energy along W when the orbital
+        energies are held fixed."""
+        who = "SectorDensity.expectation"
+        self._operator(who, W)
+        kinetic = np.zeros(self.tables.n) if one_body is None else np.asarray(one_body, dtype=np.float64)
+        if kinetic.shape != (self.tables.n,):
+            raise ValueError(who + ": one number per orbital is needed for the one-body operator")
+        return self._lagrangian(W.hf_orbital_energies(kinetic) if mean_field else kinetic, W)
+
+    # ---- transfer sums and the structure factor ---------------------------------------------------------------------
+    def bins(self):
+        if self._bins is None:
+            self._bins = sectors.TransferBins(self.tables)
+        return self._bins
+
+    def _bin_tables(self):
+        """The CSR of every stored family, the bin vectors and the rows of the pp layout on the device, checked first (the
+        kernels trust them)."""
+        if self._bins_dev is None:
+            ctx, tab, tb = self.ctx, self.tables, self.bins()
+
+            def imap(host, limit):
+                host = np.ascontiguousarray(host, dtype=np.int64)
+                if len(host) and (host.min() < -1 or host.max() >= limit):
+                    raise AssertionError("transfer bins: an index points outside its array")
+                return upload_raw(ctx, host)
+
+            def i32(x):
+                x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1)
+                return upload_raw(ctx, np.append(x, np.zeros(x.size % 2, dtype=np.int32)))
+            csr = {}
+            for nm in self.FAMILIES:
+                off, order = tb.csr[nm]
+                if off[0] != 0 or off[-1] != self.sizes[nm] or (np.diff(off) < 0).any() or len(order) != self.sizes[nm] \
+                        or (len(order) and order.min() < 0):
+                    raise AssertionError("transfer bins: the lists of family %s do not cover it" % nm)
+                csr[nm] = (imap(off, self.sizes[nm] + 1), imap(order, max(self.sizes[nm], 1)))
+            tt = TriplesTables(tab)
+            vv, start, length, of_pair = tb.pair_rows()
+            if len(vv) and (vv.min() < 0 or vv.max() >= tab.nv or start.min() < 0 or (start + length).max() > tab.nnz
+                            or tt.orb_of.max() >= tab.n):
+                raise AssertionError("transfer bins: a row of the pp layout points outside the compact vector")
+            self._bins_dev = {"csr": csr, "q": i32(tb.q), "k": i32(tab.k_int), "orb": i32(tt.orb_of), "box": tt.box,
+                              "rows": len(vv), "vv": i32(vv), "start": imap(start, tab.nnz + 1),
+                              "len": imap(length, tab.nnz + 1), "of_pair": imap(of_pair, max(len(vv), 1))}
+        return self._bins_dev
+
+    def stored_transfer(self, out=None):
+        """The stored families' part of s(q) on the device: one launch of ``pymes_sector_bin_sums`` per family."""
+        ctx, tb, bd = self.ctx, self.bins(), self._bin_tables()
+        out = ctx.empty((tb.nbins,)) if out is None else out
+        for n, nm in enumerate(self.FAMILIES):
+            off, order = bd["csr"][nm]
+            ctx.lib.call("pymes_sector_bin_sums", ctx.handle, C.c_void_p(out.ptr), tb.nbins, C.c_void_p(off.ptr),
+                         C.c_void_p(order.ptr), C.c_void_p(self[nm].ptr), 1.0, 0.0 if n == 0 else 1.0)
+        return out
+
+    def pair_transfer(self, out=None, max_groups=0):
+        """The ``abcd`` part of s(q) on the device (``pymes_sector_pair_transfer``)."""
+        ctx, tab, tb, bd = self.ctx, self.tables, self.bins(), self._bin_tables()
+        out = ctx.empty((tb.nbins,)) if out is None else out
+        ctx.lib.call("pymes_sector_pair_transfer", ctx.handle, C.c_void_p(out.ptr), tb.nbins, C.c_void_p(bd["q"].ptr),
+                     C.c_void_p(bd["k"].ptr), C.c_void_p(bd["orb"].ptr), bd["box"].ctypes.data_as(C.c_void_p), tab.no, tab.nv,
+                     bd["rows"], C.c_void_p(bd["vv"].ptr), C.c_void_p(bd["start"].ptr), C.c_void_p(bd["len"].ptr),
+                     C.c_void_p(bd["of_pair"].ptr), C.c_void_p(self.lam.ptr), C.c_void_p(self.T.ptr), int(max_groups))
+        return out
+
+    def transfer_sums(self, symmetrize=True):
+        """(s per bin, the bin vectors [bins,3]): s(q) = the sum of G over all families and elements (p,q,r,s) with
+        k_r - k_p = q.  The plain s is not even in q (the product list treats the two electrons differently; DESIGN 8l);
+        ``symmetrize`` returns S2(q) = (s(q) + s(-q)) / 2, which goes with Gamma_pqrs = (G_pqrs + G_qpsr) / 2."""
+        if self.ctx.recording:
+            raise RuntimeError("SectorDensity.transfer_sums: the context is recording a launch graph")
+        tb = self.bins()
+        s = self.stored_transfer().get() + self.pair_transfer().get()
+        if symmetrize:
+            s = 0.5 * s + 0.5 * s[tb.neg]
+        return s, tb.q
+
+    def structure_factor(self, shells=False):
+        """(S(q) per bin, the bin vectors), in the convention of ``lambda_ccsd.full_rdm2``: for q != 0
+        S(q) = 1 + [-2 #{(i,j): k_j - k_i = q} - sum_{i,p: k_i - k_p = +-q} gamma_p + 2 S2(q)] / N, and S(0) = N.  ``shells``:
+        (the average of S over the bins of equal |q|^2, those |q|^2 in units of the integer vectors)."""
+        tb, N = self.bins(), 2 * self.tables.no
+        s2, q = self.transfer_sums(symmetrize=True)
+        bracket = tb.reference_terms(self.gamma.get()) + 2.0 * s2
+        bracket[tb.zero] = N * (N - 1)
+        S = 1.0 + bracket / N
+        if not shells:
+            return S, q
+        values, shell = tb.shells()
+        return np.bincount(shell, weights=S) / np.bincount(shell), values

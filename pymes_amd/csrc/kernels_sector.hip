@@ -1,8 +1,8 @@
 // Kernels of the momentum-sector CCD / DCD path (pymes_amd/solver/ueg_cc.py; DESIGN "Momentum sectors"): a ragged batched
 // fp64 product over a device-resident task table, the gathers between the three sector layouts, and the element-wise tails;
 // and of the momentum-blocked (T) on the same path: the W slab, the energy partials and their ordered sum;
-// and the two-slab energy kernel of the Lambda-(T); and the bin sums, the fused V_abcd transfer sums and the gamma
-// sums of the sector densities.
+// and the two-slab instantiation of the energy kernel for the Lambda-(T) (what the two share: DESIGN 8m); and the
+// bin sums, the fused V_abcd transfer sums and the gamma sums of the sector densities.
 // Included at the end of kernels.hip (one code object for the library), not compiled on its own.
 #include <hip/hip_runtime.h>
 
@@ -213,6 +213,37 @@ __device__ __forceinline__ void triples_stage(double (*tr)[kTrTile + 1], const d
     __syncthreads();
 }
 
+// What the W kernel and the energy kernel know of their place before they touch a slab: the triple of the grid row, the
+// 32 x 32 tile of the grid column, the thread's (ty, tx) in it and its column b.  Every thread takes part in triples_stage;
+// only one with b < nv then asks for the momenta, and for the third virtual of its rows a = row(q) < nv.
+struct TriplesTile {
+    int i, j, k, a0, b0, tx, ty, b, K[3], kb[3];
+    __device__ __forceinline__ TriplesTile(long t0, int nv) {
+        triple_of(t0 + blockIdx.y, i, j, k);
+        const int tiles_b = (nv + kTrTile - 1) / kTrTile;
+        a0 = (blockIdx.x / tiles_b) * kTrTile;
+        b0 = (blockIdx.x % tiles_b) * kTrTile;
+        tx = threadIdx.x & 31;
+        ty = threadIdx.x >> 5;
+        b = b0 + tx;
+    }
+    __device__ __forceinline__ int row(int q) const { return a0 + ty + 8 * q; }
+    // K = k_i + k_j + k_k and k_b
+    __device__ __forceinline__ void momenta(const int* __restrict__ k_int, int no) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            K[d] = k_int[3 * i + d] + k_int[3 * j + d] + k_int[3 * k + d];
+            kb[d] = k_int[3 * (no + b) + d];
+        }
+    }
+    // the virtual c of (a,b), counted from the first virtual; negative if there is none
+    __device__ __forceinline__ int third(const int* __restrict__ k_int, const int* __restrict__ orb_of, const TriplesBox& bx,
+                                         int no, int a) const {
+        const int* ka = k_int + 3 * (no + a);
+        return triples_orb(orb_of, bx, K[0] - ka[0] - kb[0], K[1] - ka[1] - kb[1], K[2] - ka[2] - kb[2]) - no;
+    }
+};
+
 // Wt[a,b] of the triple t0 + blockIdx.y: the twelve products in the order of the formula, 0 where c is no virtual.  Every
 // element of the slab is written here.  Global reads along b (Vv[i,a,b], Tc[.,.,b], the store) are contiguous; Vv[j,b,a]
 // comes through the transposed LDS tile; what is indexed by c is a gather inside rows that the L2 holds.
@@ -222,36 +253,26 @@ __global__ void __launch_bounds__(256) sector_triples_w_kernel(int no, int nv, c
                                                                const double* __restrict__ Vv, const double* __restrict__ Vo,
                                                                long t0, double* __restrict__ Wt) {
     __shared__ double tr[kTrTile][kTrTile + 1];
-    int i, j, k;
-    triple_of(t0 + blockIdx.y, i, j, k);
-    const int tiles_b = (nv + kTrTile - 1) / kTrTile;
-    const int a0 = (blockIdx.x / tiles_b) * kTrTile, b0 = (blockIdx.x % tiles_b) * kTrTile;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    TriplesTile tl(t0, nv);
+    const int i = tl.i, j = tl.j, k = tl.k, b = tl.b;
     const long v = nv, vv = v * v;
     const double* __restrict__ Vi = Vv + i * vv;
     const double* __restrict__ Vj = Vv + j * vv;
     const double* __restrict__ Vk = Vv + k * vv;
-    triples_stage(tr, Vj, nv, a0, b0, tx, ty);
-    const int b = b0 + tx;
+    triples_stage(tr, Vj, nv, tl.a0, tl.b0, tl.tx, tl.ty);
     if (b >= nv) return;
-    int K[3], kb[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        K[d] = k_int[3 * i + d] + k_int[3 * j + d] + k_int[3 * k + d];
-        kb[d] = k_int[3 * (no + b) + d];
-    }
+    tl.momenta(k_int, no);
     double* __restrict__ W = Wt + (long)blockIdx.y * vv;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const int a = a0 + ty + 8 * q;
+        const int a = tl.row(q);
         if (a >= nv) continue;
-        const int* ka = k_int + 3 * (no + a);
-        const int c = triples_orb(orb_of, bx, K[0] - ka[0] - kb[0], K[1] - ka[1] - kb[1], K[2] - ka[2] - kb[2]) - no;
+        const int c = tl.third(k_int, orb_of, bx, no, a);
         double w = 0.0;
         if (c >= 0) {
             w = triples_w(Vi[a * v + b], i, j, k, a, b, c, no, v, m_of, Tc, Vo);                 // w(ijk;abc)
             w += triples_w(Vi[a * v + c], i, k, j, a, c, b, no, v, m_of, Tc, Vo);                // w(ikj;acb)
-            w += triples_w(tr[tx][ty + 8 * q], j, i, k, b, a, c, no, v, m_of, Tc, Vo);           // w(jik;bac)
+            w += triples_w(tr[tl.tx][tl.ty + 8 * q], j, i, k, b, a, c, no, v, m_of, Tc, Vo);     // w(jik;bac)
             w += triples_w(Vj[b * v + c], j, k, i, b, c, a, no, v, m_of, Tc, Vo);                // w(jki;bca)
             w += triples_w(Vk[c * v + a], k, i, j, c, a, b, no, v, m_of, Tc, Vo);                // w(kij;cab)
             w += triples_w(Vk[c * v + b], k, j, i, c, b, a, no, v, m_of, Tc, Vo);                // w(kji;cba)
@@ -261,94 +282,39 @@ __global__ void __launch_bounds__(256) sector_triples_w_kernel(int no, int nv, c
 }
 
 // One partial per workgroup: sum over the tile's (a,b) with a virtual c of
-// Wt[a,b] (4 Wt[a,b] + Wt[b,c] + Wt[c,a] - 2 Wt[c,b] - 2 Wt[a,c] - 2 Wt[b,a]) / (e_i + e_j + e_k - e_a - e_b - e_c),
-// each thread over its four elements in ascending a, then a fixed tree over the 256 threads.
+// WR[a,b] (4 WL[a,b] + WL[b,c] + WL[c,a] - 2 WL[c,b] - 2 WL[a,c] - 2 WL[b,a]) / (e_i + e_j + e_k - e_a - e_b - e_c),
+// each thread over its four elements in ascending a, then a fixed tree over the 256 threads.  WL[a,b] is read along b,
+// WL[b,a] comes through the LDS transpose, the four reads indexed by c are gathers inside rows of WL that the L2 holds.
+// (T) is the one-slab instantiation, WR = WL = Wt: WRt is not read and WL[a,b] stands in front as well.  Lambda-(T)
+// reads the factor in front from the right-hand slab.
+template <bool kTwoSlabs>
 __global__ void __launch_bounds__(256) sector_triples_e_kernel(int no, int nv, const double* __restrict__ eps,
                                                                const int* __restrict__ k_int, const int* __restrict__ orb_of,
-                                                               TriplesBox bx, long t0, const double* __restrict__ Wt,
-                                                               double* __restrict__ partial) {
+                                                               TriplesBox bx, long t0, const double* __restrict__ WRt,
+                                                               const double* __restrict__ WLt, double* __restrict__ partial) {
     __shared__ double tr[kTrTile][kTrTile + 1];
     __shared__ double red[256];
-    int i, j, k;
-    triple_of(t0 + blockIdx.y, i, j, k);
-    const int tiles_b = (nv + kTrTile - 1) / kTrTile;
-    const int a0 = (blockIdx.x / tiles_b) * kTrTile, b0 = (blockIdx.x % tiles_b) * kTrTile;
-    const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
-    const long v = nv;
-    const double* __restrict__ W = Wt + (long)blockIdx.y * v * v;
-    triples_stage(tr, W, nv, a0, b0, tx, ty);
-    const int b = b0 + tx;
-    double acc = 0.0;
-    if (b < nv) {
-        int K[3], kb[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            K[d] = k_int[3 * i + d] + k_int[3 * j + d] + k_int[3 * k + d];
-            kb[d] = k_int[3 * (no + b) + d];
-        }
-        const double eo = eps[i] + eps[j] + eps[k];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int a = a0 + ty + 8 * q;
-            if (a >= nv) continue;
-            const int* ka = k_int + 3 * (no + a);
-            const int c = triples_orb(orb_of, bx, K[0] - ka[0] - kb[0], K[1] - ka[1] - kb[1], K[2] - ka[2] - kb[2]) - no;
-            if (c < 0) continue;
-            const double wab = W[a * v + b];
-            const double r = 4.0 * wab + W[b * v + c] + W[c * v + a] - 2.0 * W[c * v + b] - 2.0 * W[a * v + c]
-                             - 2.0 * tr[tx][ty + 8 * q];
-            acc += wab * r / (eo - eps[no + a] - eps[no + b] - eps[no + c]);
-        }
-    }
-    red[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) partial[(long)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
-}
-
-// Lambda-(T): the same tiles, the same order of adds and the same tree as sector_triples_e_kernel on two slabs,
-// sum of WR[a,b] (4 WL[a,b] + WL[b,c] + WL[c,a] - 2 WL[c,b] - 2 WL[a,c] - 2 WL[b,a]) / D.  WR[a,b] and WL[a,b] are read along b;
-// WL[b,a] comes through the LDS transpose; the four reads indexed by c are gathers inside rows of WL that the L2 holds.
-__global__ void __launch_bounds__(256) sector_triples_lambda_e_kernel(int no, int nv, const double* __restrict__ eps,
-                                                                      const int* __restrict__ k_int,
-                                                                      const int* __restrict__ orb_of, TriplesBox bx, long t0,
-                                                                      const double* __restrict__ WRt,
-                                                                      const double* __restrict__ WLt,
-                                                                      double* __restrict__ partial) {
-    __shared__ double tr[kTrTile][kTrTile + 1];
-    __shared__ double red[256];
-    int i, j, k;
-    triple_of(t0 + blockIdx.y, i, j, k);
-    const int tiles_b = (nv + kTrTile - 1) / kTrTile;
-    const int a0 = (blockIdx.x / tiles_b) * kTrTile, b0 = (blockIdx.x % tiles_b) * kTrTile;
-    const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
+    TriplesTile tl(t0, nv);
+    const int tid = threadIdx.x, b = tl.b;
     const long v = nv;
     const double* __restrict__ WR = WRt + (long)blockIdx.y * v * v;
     const double* __restrict__ WL = WLt + (long)blockIdx.y * v * v;
-    triples_stage(tr, WL, nv, a0, b0, tx, ty);
-    const int b = b0 + tx;
+    triples_stage(tr, WL, nv, tl.a0, tl.b0, tl.tx, tl.ty);
     double acc = 0.0;
     if (b < nv) {
-        int K[3], kb[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            K[d] = k_int[3 * i + d] + k_int[3 * j + d] + k_int[3 * k + d];
-            kb[d] = k_int[3 * (no + b) + d];
-        }
-        const double eo = eps[i] + eps[j] + eps[k];
+        tl.momenta(k_int, no);
+        const double eo = eps[tl.i] + eps[tl.j] + eps[tl.k];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int a = a0 + ty + 8 * q;
+            const int a = tl.row(q);
             if (a >= nv) continue;
-            const int* ka = k_int + 3 * (no + a);
-            const int c = triples_orb(orb_of, bx, K[0] - ka[0] - kb[0], K[1] - ka[1] - kb[1], K[2] - ka[2] - kb[2]) - no;
+            const int c = tl.third(k_int, orb_of, bx, no, a);
             if (c < 0) continue;
-            const double r = 4.0 * WL[a * v + b] + WL[b * v + c] + WL[c * v + a] - 2.0 * WL[c * v + b] - 2.0 * WL[a * v + c]
-                             - 2.0 * tr[tx][ty + 8 * q];
-            acc += WR[a * v + b] * r / (eo - eps[no + a] - eps[no + b] - eps[no + c]);
+            const double wl = WL[a * v + b];
+            const double r = 4.0 * wl + WL[b * v + c] + WL[c * v + a] - 2.0 * WL[c * v + b] - 2.0 * WL[a * v + c]
+                             - 2.0 * tr[tl.tx][tl.ty + 8 * q];
+            const double wr = kTwoSlabs ? WR[a * v + b] : wl;
+            acc += wr * r / (eo - eps[no + a] - eps[no + b] - eps[no + c]);
         }
     }
     red[tid] = acc;
@@ -416,6 +382,54 @@ struct OrderedSum {
     }
     double value() const { return sum + carry; }
 };
+
+// The host side of (T) and Lambda-(T) (dev::sector_triples, dev::sector_triples_lambda): the triples of [t_begin, t_end) in
+// batches of as many as `ws` holds, one grid row each.  ws: the slab(s) of the batch, then one partial per tile, then the
+// values.  Without `left` there is one slab W (Tc, Vv, Vo) per triple and the energy kernel reads it on both sides.  With it
+// there are two, WR from `right` and WL from `left`, by two launches of the unchanged sector_triples_w_kernel: a side index
+// on blockIdx.z would put a select of three base pointers in front of every gather of a kernel whose (T) timings are
+// recorded, to save one launch (~10 us) per batch of kernels that run for milliseconds.
+struct TriplesSide { const double *Tc, *Vv, *Vo; };
+double sector_triples_run(const std::string& who, int no, int nv, const double* eps, const int32_t* k_int, const int32_t* orb_of,
+                          const int32_t* box_host, const int32_t* m_of, const TriplesSide& right, const TriplesSide* left,
+                          int64_t t_begin, int64_t t_end, double* ws, int64_t ws_bytes, double* per_triple, dev::stream_t s) {
+    if (no < 1 || nv < 1 || nv > (1 << 20)) throw std::runtime_error(who + ": bad orbital counts");
+    if (!eps || !k_int || !orb_of || !box_host || !m_of || !right.Tc || !right.Vv || !right.Vo || !ws ||
+        (left && (!left->Tc || !left->Vv || !left->Vo)))
+        throw std::runtime_error(who + ": null argument");
+    triples_range(who, no, t_begin, t_end);
+    const TriplesBox bx = triples_box(who, box_host);
+    const int64_t tiles1 = (nv + kTrTile - 1) / kTrTile, ntiles = tiles1 * tiles1, slab = (int64_t)nv * nv;
+    const int64_t each = (left ? 2 : 1) * slab + ntiles + 1;  // per triple: the slab(s), one partial per tile, the value
+    const int64_t fit = ws_bytes / 8 / each;
+    if (fit < 1)
+        throw std::runtime_error(who + ": the workspace does not hold one triple (" + std::to_string(8 * each) + " bytes)");
+    const int64_t nb = std::min<int64_t>(fit, 65535);         // triples per batch: one grid row each
+    double* WR = ws;
+    double* WL = left ? ws + nb * slab : ws;
+    double* partial = WL + nb * slab;
+    double* per = partial + nb * ntiles;
+    hipStream_t st = (hipStream_t)s;
+    std::vector<double> host((size_t)std::min<int64_t>(nb, std::max<int64_t>(t_end - t_begin, 1)));
+    OrderedSum total;
+    for (int64_t t0 = t_begin; t0 < t_end; t0 += nb) {
+        const int n = (int)std::min<int64_t>(nb, t_end - t0);
+        const dim3 grid((unsigned)ntiles, (unsigned)n);
+        launch_kernel(sector_triples_w_kernel, grid, dim3(256), 0, st, no, nv, k_int, orb_of, bx, m_of, right.Tc, right.Vv,
+                      right.Vo, (long)t0, WR);
+        if (left)
+            launch_kernel(sector_triples_w_kernel, grid, dim3(256), 0, st, no, nv, k_int, orb_of, bx, m_of, left->Tc, left->Vv,
+                          left->Vo, (long)t0, WL);
+        launch_kernel(left ? sector_triples_e_kernel<true> : sector_triples_e_kernel<false>, grid, dim3(256), 0, st, no, nv, eps,
+                      k_int, orb_of, bx, (long)t0, (const double*)WR, (const double*)WL, partial);
+        launch_kernel(sector_triples_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, (const double*)partial, (long)ntiles,
+                      (long)t0, per, per_triple ? per_triple + (t0 - t_begin) : (double*)nullptr);
+        HIP_CHECK(copy_async(host.data(), per, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        wait_idle(st);
+        for (int q = 0; q < n; ++q) total.add(host[q]);       // in triple order, whatever the batch size
+    }
+    return total.value();
+}
 
 // ---- sector densities: sums of a density arena over the bins of the momentum transfer -------------------------------
 // out[b] = beta out[b] + alpha sum_j src[list[j]], off[b] <= j < off[b + 1].  A workgroup owns four consecutive bins.  A bin of
@@ -585,78 +599,18 @@ void sector_update(double* t_out, double* dt, const double* t_in, const double* 
 double sector_triples(int no, int nv, const double* eps, const int32_t* k_int, const int32_t* orb_of, const int32_t* box_host,
                       const int32_t* m_of, const double* Tc, const double* Vv, const double* Vo, int64_t t_begin, int64_t t_end,
                       double* ws, int64_t ws_bytes, double* per_triple, stream_t s) {
-    if (no < 1 || nv < 1 || nv > (1 << 20)) throw std::runtime_error("sector_triples: bad orbital counts");
-    if (!eps || !k_int || !orb_of || !box_host || !m_of || !Tc || !Vv || !Vo || !ws)
-        throw std::runtime_error("sector_triples: null argument");
-    triples_range("sector_triples", no, t_begin, t_end);
-    const TriplesBox bx = triples_box("sector_triples", box_host);
-    const int64_t tiles1 = (nv + kTrTile - 1) / kTrTile, ntiles = tiles1 * tiles1, slab = (int64_t)nv * nv;
-    const int64_t each = slab + ntiles + 1;                   // per triple: the slab, one partial per tile, the value
-    const int64_t fit = ws_bytes / 8 / each;
-    if (fit < 1) throw std::runtime_error("sector_triples: the workspace does not hold one triple (" + std::to_string(8 * each) +
-                                          " bytes)");
-    const int64_t nb = std::min<int64_t>(fit, 65535);         // triples per batch: one grid row each
-    double* Wt = ws;
-    double* partial = ws + nb * slab;
-    double* per = partial + nb * ntiles;
-    hipStream_t st = (hipStream_t)s;
-    std::vector<double> host((size_t)std::min<int64_t>(nb, std::max<int64_t>(t_end - t_begin, 1)));
-    OrderedSum total;
-    for (int64_t t0 = t_begin; t0 < t_end; t0 += nb) {
-        const int n = (int)std::min<int64_t>(nb, t_end - t0);
-        const dim3 grid((unsigned)ntiles, (unsigned)n);
-        launch_kernel(sector_triples_w_kernel, grid, dim3(256), 0, st, no, nv, k_int, orb_of, bx, m_of, Tc, Vv, Vo, (long)t0, Wt);
-        launch_kernel(sector_triples_e_kernel, grid, dim3(256), 0, st, no, nv, eps, k_int, orb_of, bx, (long)t0, (const double*)Wt,
-                      partial);
-        launch_kernel(sector_triples_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, (const double*)partial, (long)ntiles,
-                      (long)t0, per, per_triple ? per_triple + (t0 - t_begin) : (double*)nullptr);
-        HIP_CHECK(copy_async(host.data(), per, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-        wait_idle(st);
-        for (int q = 0; q < n; ++q) total.add(host[q]);       // in triple order, whatever the batch size
-    }
-    return total.value();
+    return sector_triples_run("sector_triples", no, nv, eps, k_int, orb_of, box_host, m_of, {Tc, Vv, Vo}, nullptr, t_begin, t_end,
+                              ws, ws_bytes, per_triple, s);
 }
 
-// Lambda-(T): sector_triples with a right-hand slab WR (VvR, VoR, Tc) and a left-hand slab WL (VvL, VoL, Lc) per triple.  The
-// two slabs come from two launches of the unchanged sector_triples_w_kernel: a side index on blockIdx.z would put a select
-// of three base pointers in front of every gather of a kernel whose (T) timings are recorded, to save one launch (~10 us)
-// per batch of kernels that run for milliseconds.
+// Lambda-(T): a right-hand slab WR (VvR, VoR, Tc) and a left-hand slab WL (VvL, VoL, Lc) per triple
 double sector_triples_lambda(int no, int nv, const double* eps, const int32_t* k_int, const int32_t* orb_of,
                              const int32_t* box_host, const int32_t* m_of, const double* Tc, const double* Lc, const double* VvR,
                              const double* VoR, const double* VvL, const double* VoL, int64_t t_begin, int64_t t_end, double* ws,
                              int64_t ws_bytes, double* per_triple, stream_t s) {
-    if (no < 1 || nv < 1 || nv > (1 << 20)) throw std::runtime_error("sector_triples_lambda: bad orbital counts");
-    if (!eps || !k_int || !orb_of || !box_host || !m_of || !Tc || !Lc || !VvR || !VoR || !VvL || !VoL || !ws)
-        throw std::runtime_error("sector_triples_lambda: null argument");
-    triples_range("sector_triples_lambda", no, t_begin, t_end);
-    const TriplesBox bx = triples_box("sector_triples_lambda", box_host);
-    const int64_t tiles1 = (nv + kTrTile - 1) / kTrTile, ntiles = tiles1 * tiles1, slab = (int64_t)nv * nv;
-    const int64_t each = 2 * slab + ntiles + 1;               // per triple: two slabs, one partial per tile, the value
-    const int64_t fit = ws_bytes / 8 / each;
-    if (fit < 1) throw std::runtime_error("sector_triples_lambda: the workspace does not hold one triple (" +
-                                          std::to_string(8 * each) + " bytes)");
-    const int64_t nb = std::min<int64_t>(fit, 65535);         // triples per batch: one grid row each
-    double* WR = ws;
-    double* WL = ws + nb * slab;
-    double* partial = WL + nb * slab;
-    double* per = partial + nb * ntiles;
-    hipStream_t st = (hipStream_t)s;
-    std::vector<double> host((size_t)std::min<int64_t>(nb, std::max<int64_t>(t_end - t_begin, 1)));
-    OrderedSum total;
-    for (int64_t t0 = t_begin; t0 < t_end; t0 += nb) {
-        const int n = (int)std::min<int64_t>(nb, t_end - t0);
-        const dim3 grid((unsigned)ntiles, (unsigned)n);
-        launch_kernel(sector_triples_w_kernel, grid, dim3(256), 0, st, no, nv, k_int, orb_of, bx, m_of, Tc, VvR, VoR, (long)t0, WR);
-        launch_kernel(sector_triples_w_kernel, grid, dim3(256), 0, st, no, nv, k_int, orb_of, bx, m_of, Lc, VvL, VoL, (long)t0, WL);
-        launch_kernel(sector_triples_lambda_e_kernel, grid, dim3(256), 0, st, no, nv, eps, k_int, orb_of, bx, (long)t0,
-                      (const double*)WR, (const double*)WL, partial);
-        launch_kernel(sector_triples_sum_kernel, dim3((unsigned)n), dim3(256), 0, st, (const double*)partial, (long)ntiles,
-                      (long)t0, per, per_triple ? per_triple + (t0 - t_begin) : (double*)nullptr);
-        HIP_CHECK(copy_async(host.data(), per, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-        wait_idle(st);
-        for (int q = 0; q < n; ++q) total.add(host[q]);       // in triple order, whatever the batch size
-    }
-    return total.value();
+    const TriplesSide left{Lc, VvL, VoL};
+    return sector_triples_run("sector_triples_lambda", no, nv, eps, k_int, orb_of, box_host, m_of, {Tc, VvR, VoR}, &left,
+                              t_begin, t_end, ws, ws_bytes, per_triple, s);
 }
 
 void sector_bin_sums(double* out, int64_t nbins, const int64_t* off, const int64_t* list, const double* src, double alpha,

@@ -10,6 +10,7 @@ caller's own is tabulated over the lattice shells and looked up on the device), 
 (2*30+1)^3 lattice sum per (p,r) pair in the reference — runs as HIP kernels (``pymes_ueg_eval_2b``);
 the O(n_occ^2 n_pw) mean-field contractions stay on the host like the reference's.
 """
+import contextlib
 import ctypes as C
 import time
 import warnings
@@ -325,6 +326,30 @@ class UEG:
                          len(tab_a) if tab_a is not None else 0, C.c_void_p(pqrs_ptr), count, C.c_void_p(out_ptr))
         return eval_list
 
+    @contextlib.contextmanager
+    def _sector_frame(self, who, tables, correlator, flags, ctx):
+        """What ``eval_2b_sectors`` and ``eval_2b_triples`` share around their bodies: the ``SectorTables`` must belong to
+        this basis; the list evaluator is bound; without ``ctx`` a context of its own is made; a recording context is
+        refused; and a context of its own is closed again if the body raises.  Yields (ctx, whether it is its own, f)."""
+        if self.basis_fns is None:
+            raise ValueError("Basis functions not initialized!")
+        n_p = len(self.basis_fns) // 2
+        k_int = np.ascontiguousarray([self.basis_fns[2 * i].k for i in range(n_p)], dtype=np.int32)
+        if tables.n != n_p or tables.no != self.n_ele // 2 or not np.array_equal(tables.k_int, k_int):
+            raise ValueError(who + ": the tables do not belong to this basis")
+        eval_list = self._list_evaluator(k_int, correlator, flags)
+        own = ctx is None
+        if own:
+            ctx = Context(tables.no, tables.nv, device=self.device, workspace_bytes=1 << 20)
+        try:
+            if ctx.recording:
+                raise RuntimeError(who + ": the context is recording a launch graph")
+            yield ctx, own, eval_list
+        except BaseException:
+            if own:
+                ctx.close()
+            raise
+
     def eval_2b_sectors(self, tables, correlator=None, is_rpa_approx=False, is_only_2b=False, is_effect_2b=False, ctx=None):
         """The integral sectors of ``tables`` as ``SectorIntegrals`` (``ctx``: the context they live in; its own otherwise).
         Same modes and correlators as ``eval_2b_integrals``; is_effect_2b comes out already symmetrised (ueg.py:509-513).
@@ -333,20 +358,8 @@ class UEG:
         from pymes_amd.solver.sectors import BLOCKS
         from pymes_amd.solver.ueg_cc import SectorIntegrals, upload_raw
         start_time = time.time()
-        if self.basis_fns is None:
-            raise ValueError("Basis functions not initialized!")
-        n_p = len(self.basis_fns) // 2
-        k_int = np.ascontiguousarray([self.basis_fns[2 * i].k for i in range(n_p)], dtype=np.int32)
-        if tables.n != n_p or tables.no != self.n_ele // 2 or not np.array_equal(tables.k_int, k_int):
-            raise ValueError("eval_2b_sectors: the tables do not belong to this basis")
-        eval_list = self._list_evaluator(k_int, correlator, dict(is_rpa_approx=is_rpa_approx, is_only_2b=is_only_2b,
-                                                                 is_effect_2b=is_effect_2b))
-        own = ctx is None
-        if own:
-            ctx = Context(tables.no, tables.nv, device=self.device, workspace_bytes=1 << 20)
-        try:
-            if ctx.recording:
-                raise RuntimeError("eval_2b_sectors: the context is recording a launch graph")
+        flags = dict(is_rpa_approx=is_rpa_approx, is_only_2b=is_only_2b, is_effect_2b=is_effect_2b)
+        with self._sector_frame("eval_2b_sectors", tables, correlator, flags, ctx) as (ctx, own, eval_list):
             ints = SectorIntegrals(ctx, tables, own_ctx=own)
             pieces = []             # (name, first sector, end sector, items), in arena order
             for name in ints.NAMES:
@@ -374,10 +387,6 @@ class UEG:
             assert done == ints.total
             print_logging_info("{:.3f} s spent on ".format(time.time() - start_time) + __name__, level=1)
             return ints
-        except BaseException:
-            if own:
-                ctx.close()
-            raise
 
     def eval_2b_triples(self, tables, correlator=None, is_rpa_approx=False, is_only_2b=False, is_effect_2b=False, ctx=None,
                         both_sides=False):
@@ -393,18 +402,8 @@ class UEG:
         if self.basis_fns is None:
             raise ValueError("Basis functions not initialized!")
         ttab = tables if isinstance(tables, TriplesTables) else TriplesTables(tables)
-        n_p = len(self.basis_fns) // 2
-        k_int = np.ascontiguousarray([self.basis_fns[2 * i].k for i in range(n_p)], dtype=np.int32)
-        if ttab.n != n_p or ttab.no != self.n_ele // 2 or not np.array_equal(ttab.tables.k_int, k_int):
-            raise ValueError("eval_2b_triples: the tables do not belong to this basis")
-        eval_list = self._list_evaluator(k_int, correlator, dict(is_rpa_approx=is_rpa_approx, is_only_2b=is_only_2b,
-                                                                 is_effect_2b=is_effect_2b))
-        own = ctx is None
-        if own:
-            ctx = Context(ttab.no, ttab.nv, device=self.device, workspace_bytes=1 << 20)
-        try:
-            if ctx.recording:
-                raise RuntimeError("eval_2b_triples: the context is recording a launch graph")
+        flags = dict(is_rpa_approx=is_rpa_approx, is_only_2b=is_only_2b, is_effect_2b=is_effect_2b)
+        with self._sector_frame("eval_2b_triples", ttab.tables, correlator, flags, ctx) as (ctx, own, eval_list):
             tints = SectorTriplesIntegrals(ctx, ttab, own_ctx=own, both_sides=both_sides)
             families = [("vv", tints.Vv), ("vo", tints.Vo)] + ([("vv_r", tints.VvR), ("vo_r", tints.VoR)] if both_sides else [])
             for family, dst in families:
@@ -424,10 +423,6 @@ class UEG:
                     vals.free()
             print_logging_info("{:.3f} s spent on ".format(time.time() - start_time) + __name__, level=1)
             return tints
-        except BaseException:
-            if own:
-                ctx.close()
-            raise
 
     # ---- host mirrors of the per-element helpers (ueg.py:518-596) ----------------------------------
     def _occ_kp(self):

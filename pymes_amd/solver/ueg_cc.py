@@ -73,35 +73,49 @@ def gather(ctx, dst, s1, m1, a1=1.0, s2=None, m2=None, a2=0.0, beta=0.0):
                  C.c_void_p(m2.ptr if m2 is not None else 0))
 
 
+def upload_map(ctx, host, limit, who="sector tables: a gather map points outside its source", lowest=0):
+    """An int64 gather map (or index list) on the device with its length as ``.count``, refused unless every entry lies in
+    [lowest, limit): the kernels trust it."""
+    host = np.ascontiguousarray(host, dtype=np.int64).reshape(-1)
+    if len(host) and (host.min() < lowest or host.max() >= limit):
+        raise AssertionError(who)
+    arr = upload_raw(ctx, host)
+    arr.count = len(host)
+    return arr
+
+
+def upload_i32(ctx, host):
+    """An int32 table on the device, padded with a 0 to a whole number of doubles."""
+    host = np.ascontiguousarray(host, dtype=np.int32).reshape(-1)
+    return upload_raw(ctx, np.append(host, np.zeros(host.size % 2, dtype=np.int32)))
+
+
 class DeviceTables:
     """The gather maps, row tables and task tables of one ``SectorTables`` in one context (uploaded once, kept with the
     integrals)."""
 
+    # the operands of ``SectorTables.gemm_tasks`` (rows, columns, block -q in place of q): F, S, Fn, Sn of the ph layouts and
+    # vo, oo, ov, vv of the pp layout, in the order every table list below unpacks them
+    OPERANDS = (("ph", "ph-", False), ("ph", "ph", False), ("ph", "ph-", True), ("ph", "ph", True),
+                ("vv", "oo", False), ("oo", "oo", False), ("oo", "vv", False), ("vv", "vv", False))
+
+    def size(self, op):
+        return int(self.tab.offsets(*op[:2])[-1])
+
+    def table(self, a, b, c, **kw):
+        return Tasks(self.ctx, self.tab.gemm_tasks(a, b, c, **kw), self.size(a), self.size(b), self.size(c))
+
     def __init__(self, ctx, tab):
         self.ctx, self.tab = ctx, tab
-
-        def imap(host, limit):
-            host = np.ascontiguousarray(host, dtype=np.int64)
-            if len(host) and (host.min() < 0 or host.max() >= limit):
-                raise AssertionError("sector tables: a gather map points outside its source")
-            arr = upload_raw(ctx, host)
-            arr.count = len(host)
-            return arr
-
         nnz, rows = tab.nnz, tab.no * tab.nv
         for name in ("d_from_pp", "c_from_pp", "pp_to_d", "pp_to_c", "pp_to_dT", "pp_to_cT"):
-            setattr(self, name, imap(getattr(tab, name), nnz))
-        self.row_start, self.row_len = imap(tab.row_start, nnz + 1), imap(tab.row_len, nnz + 1)
+            setattr(self, name, upload_map(ctx, getattr(tab, name), nnz))
+        self.row_start, self.row_len = upload_map(ctx, tab.row_start, nnz + 1), upload_map(ctx, tab.row_len, nnz + 1)
         ai = np.empty(rows, dtype=np.int64)
         ai[tab.ph_row] = np.arange(rows)
-        self.row_of, self.ai_of = imap(tab.ph_row, rows), imap(ai, rows)
-        F, S, Fn, Sn = ("ph", "ph-", False), ("ph", "ph", False), ("ph", "ph-", True), ("ph", "ph", True)
-        vo, oo, ov, vv = ("vv", "oo", False), ("oo", "oo", False), ("oo", "vv", False), ("vv", "vv", False)
-        self.nsq = int(tab.offsets("ph", "ph")[-1])
-        size = lambda op: int(tab.offsets(*op[:2])[-1])
-
-        def table(a, b, c, **kw):
-            return Tasks(ctx, tab.gemm_tasks(a, b, c, **kw), size(a), size(b), size(c))
+        self.row_of, self.ai_of = upload_map(ctx, tab.ph_row, rows), upload_map(ctx, ai, rows)
+        table, (F, S, Fn, Sn, vo, oo, ov, vv) = self.table, self.OPERANDS
+        self.nsq = self.size(S)
         self.hole_quad = table(ov, vo, oo, beta=1.0)            # I^P += V_klcd^P T^P
         self.hole = table(vo, oo, vo, beta=1.0)                 # R^P += T^P I^P
         self.ladder = table(vv, vo, vo, beta=1.0)               # R^P += V_abcd^P T^P
@@ -114,6 +128,28 @@ class DeviceTables:
         self._adjoint = None
         self._density = None
 
+    def layouts(self, T, D=None, Cx=None, Tt=None, CmD=None):
+        """The direct and crossed layouts of a compact vector into the caller's buffers, those that are given, in this
+        order: D = T[d_from_pp], C = T[c_from_pp], Tt = 2 D - C, CmD = C - D (one gather each)."""
+        ctx, d, c = self.ctx, self.d_from_pp, self.c_from_pp
+        if D is not None:
+            gather(ctx, D, T, d)
+        if Cx is not None:
+            gather(ctx, Cx, T, c)
+        if Tt is not None:
+            gather(ctx, Tt, T, d, 2.0, T, c, -1.0)
+        if CmD is not None:
+            gather(ctx, CmD, T, c, 1.0, T, d, -1.0)
+
+    def cotangents(self, lam, yRd, yRc, yEd, yEc):
+        """The cotangents of Rd, Rc and of Ed, Ec (which enter as Ex + Ex^T(1,0,3,2)) into the caller's buffers: gathers of
+        lambda through the inverse maps (the first rows of the table of DESIGN 8k)."""
+        ctx, at = self.ctx, self.adjoint()
+        gather(ctx, yRd, lam, self.d_from_pp)
+        gather(ctx, yRc, lam, self.c_from_pp)
+        gather(ctx, yEd, lam, self.d_from_pp, 1.0, lam, at.dT_from_pp, 1.0)
+        gather(ctx, yEc, lam, self.c_from_pp, 1.0, lam, at.cT_from_pp, 1.0)
+
     def adjoint(self):
         """The task tables and maps of the Lambda residual (``SectorLambda``): every product of the list above
         with the operand that held T exchanged for the output, built on first use.  In the ph layouts the adjoint of a
@@ -122,17 +158,7 @@ class DeviceTables:
         if self._adjoint is not None:
             return self._adjoint
         ctx, tab = self.ctx, self.tab
-        F, S, Fn, Sn = ("ph", "ph-", False), ("ph", "ph", False), ("ph", "ph-", True), ("ph", "ph", True)
-        vo, oo, ov, vv = ("vv", "oo", False), ("oo", "oo", False), ("oo", "vv", False), ("vv", "vv", False)
-        size = lambda op: int(tab.offsets(*op[:2])[-1])
-
-        def table(a, b, c, **kw):
-            return Tasks(ctx, tab.gemm_tasks(a, b, c, **kw), size(a), size(b), size(c))
-
-        def imap(host):
-            arr = upload_raw(ctx, np.ascontiguousarray(host, dtype=np.int64))
-            arr.count = len(host)
-            return arr
+        table, (F, S, Fn, Sn, vo, oo, ov, vv) = self.table, self.OPERANDS
 
         class Adjoint:
             pass
@@ -151,8 +177,9 @@ class DeviceTables:
         at.right_neg = table(F, Sn, F, alpha=-1.0)                             # zC^q = -yEc^q Wa^{-q}
         at.outer = table(F, F, S, trans_b=True)                                # zY^q = yEd^q (C^q - D^q)^T;  zXc^q = yRc^q (C^q)^T
         at.sq_right_t_add = table(S, Fn, F, beta=1.0, trans_b=True)            # zD^q += zY^q (Wx^{-q})^T;  zC^q += zXc^q (Wx^{-q})^T
-        at.dT_from_pp, at.cT_from_pp = imap(tab.d_from_pp[tab.d_partner]), imap(tab.c_from_pp[tab.d_partner])
-        at.pp_swap = imap(tab.pp_swap)
+        at.dT_from_pp = upload_map(ctx, tab.d_from_pp[tab.d_partner], tab.nnz)
+        at.cT_from_pp = upload_map(ctx, tab.c_from_pp[tab.d_partner], tab.nnz)
+        at.pp_swap = upload_map(ctx, tab.pp_swap, tab.nnz)
         self._adjoint = at
         return at
 
@@ -161,13 +188,7 @@ class DeviceTables:
         integral block exchanged for the output (outer-product shapes), next to those of ``adjoint()``; built on first use."""
         if self._density is not None:
             return self._density
-        ctx, tab, at = self.ctx, self.tab, self.adjoint()
-        F, S, Fn, Sn = ("ph", "ph-", False), ("ph", "ph", False), ("ph", "ph-", True), ("ph", "ph", True)
-        vo, oo, ov = ("vv", "oo", False), ("oo", "oo", False), ("oo", "vv", False)
-        size = lambda op: int(tab.offsets(*op[:2])[-1])
-
-        def table(a, b, c, **kw):
-            return Tasks(ctx, tab.gemm_tasks(a, b, c, **kw), size(a), size(b), size(c))
+        at, table, (F, S, Fn, Sn, vo, oo, ov, _) = self.adjoint(), self.table, self.OPERANDS
 
         class Density:
             pass
@@ -305,14 +326,11 @@ class SectorTriplesIntegrals:
         """(k_int, orb_of, m_of as int32 device bytes; the implied map of ``Tc`` as an int64 gather map)"""
         if self._dev is None:
             t = self.tables
-            if t.m_of.max(initial=-1) >= t.no or t.orb_of.max() >= t.n or t.implied_map.min() < 0 or \
-                    t.implied_map.max() > t.tables.nnz:
-                raise AssertionError("triples tables: an index points outside its array")
-            i32 = lambda x: upload_raw(self.ctx, np.append(np.ascontiguousarray(x, dtype=np.int32).reshape(-1),
-                                                           np.zeros(x.size % 2, dtype=np.int32)))
-            imap = upload_raw(self.ctx, t.implied_map.reshape(-1))
-            imap.count = t.implied_map.size
-            self._dev = (i32(t.tables.k_int), i32(t.orb_of), i32(t.m_of), imap)
+            outside = "triples tables: an index points outside its array"
+            if t.m_of.max(initial=-1) >= t.no or t.orb_of.max() >= t.n:
+                raise AssertionError(outside)
+            imap = upload_map(self.ctx, t.implied_map, t.tables.nnz + 1, outside)
+            self._dev = tuple(upload_i32(self.ctx, x) for x in (t.tables.k_int, t.orb_of, t.m_of)) + (imap,)
         return self._dev
 
     def close(self):
@@ -341,6 +359,48 @@ def _hermitian(ints, rtol=1e-12):
     if not len(kl):
         return True
     return np.abs(kl - ab[tab.pp_off[sec] + lc * tab.n_oo[sec] + lr]).max() <= rtol * max(np.abs(ab).max(), 1e-300)
+
+
+def _diagonal_eps(who, tab, eps, check_length=True):
+    """The orbital energies as a vector, from a vector or from a diagonal Fock matrix."""
+    eps = np.asarray(eps, dtype=np.float64)
+    if eps.ndim == 2:
+        if np.count_nonzero(eps - np.diag(eps.diagonal())):
+            raise ValueError(who + ": the Fock matrix must be diagonal (it is for a momentum-conserving Hamiltonian)")
+        eps = eps.diagonal().copy()
+    if check_length and eps.shape != (tab.n,):
+        raise ValueError(who + ": %d orbital energies for %d orbitals" % (eps.size, tab.n))
+    return eps
+
+
+def _exchange_symmetric(ints):
+    """V_pqrs = V_qpsr where the product list needs it: the X_ac / X_ki sums read W1 where ccd.py:213-220 reads V_lkdc."""
+    w1 = ints["w1"].get()
+    return not len(w1) or np.abs(w1 - w1[ints.tables.d_partner]).max() <= 1e-12 * max(np.abs(w1).max(), 1e-300)
+
+
+def _check_solver_inputs(who, no, eps, ints, dense_hint):
+    """The refusals that ``SectorCCD.solve`` and ``SectorLambda.solve`` share; returns the orbital energies as a vector."""
+    if not isinstance(ints, SectorIntegrals):
+        raise TypeError(who + ": ints must be SectorIntegrals (UEG.eval_2b_sectors); the dense path is " + dense_hint)
+    tab = ints.tables
+    if ints.ctx.recording:
+        raise RuntimeError(who + ": the context is recording a launch graph")
+    eps = _diagonal_eps(who, tab, eps, check_length=False)
+    if tab.no != no or eps.shape != (tab.n,):
+        raise ValueError(who + ": the tables of the integrals (no = %d, n = %d) do not match the solver (no = %d) "
+                         "and the %d orbital energies" % (tab.no, tab.n, no, eps.size))
+    if not _exchange_symmetric(ints):
+        raise ValueError(who + ": the integrals are not symmetric under the exchange of the two electrons "
+                         "(V_pqrs = V_qpsr), which the sector residual needs")
+    return eps
+
+
+def _symmetric_compact(who, tab, amps, what, identity="(X_abij = X_baji)"):
+    vec = SectorCCD._compact(tab, amps, "lambda" if what.startswith("lambda") else "amps")
+    if len(vec) and np.abs(vec - vec[tab.pp_swap]).max() > 1e-13 * max(np.abs(vec).max(), 1e-300):
+        raise ValueError(who + ": %s not exchange-symmetric %s" % (what, identity))
+    return vec
 
 
 def _check_triples(who, ints, tints, left=False):
@@ -379,53 +439,7 @@ def sector_triples_energy(eps, ints, tints, amps, triple_range=None, per_triple=
     ``workspace_bytes`` hold (default: the environment's PYMES_SECTOR_TRIPLES_BYTES, else 1 GiB; at least one triple); the
     value of a triple does not depend on it.  Returns the energy, or (energy, per-triple values of the range as a host
     array) with ``per_triple=True``.  Refused: integrals without V_pqrs = V_rspq (transcorrelated ones)."""
-    who = "sector_triples_energy"
-    _check_triples(who, ints, tints)
-    tab, ctx, tt = ints.tables, ints.ctx, tints.tables
-    eps = np.asarray(eps, dtype=np.float64)
-    if eps.ndim == 2:
-        if np.count_nonzero(eps - np.diag(eps.diagonal())):
-            raise ValueError(who + ": the Fock matrix must be diagonal (it is for a momentum-conserving Hamiltonian)")
-        eps = eps.diagonal().copy()
-    if eps.shape != (tab.n,):
-        raise ValueError(who + ": %d orbital energies for %d orbitals" % (eps.size, tab.n))
-    vec = SectorCCD._compact(tab, amps)
-    if len(vec) and np.abs(vec - vec[tab.pp_swap]).max() > 1e-13 * max(np.abs(vec).max(), 1e-300):
-        raise ValueError(who + ": the amplitudes are not exchange-symmetric (T_abij = T_baji)")
-    no, nv = tab.no, tab.nv
-    lo, hi, reduce = ccsd_t._triple_chunk(no, triple_range)
-    if not 0 <= lo <= hi <= ccsd_t.n_triples(no):
-        raise ValueError(who + ": triple range [%d, %d) outside [0, %d]" % (lo, hi, ccsd_t.n_triples(no)))
-    if workspace_bytes is None:
-        workspace_bytes = int(os.environ.get(TRIPLES_WS_ENV, TRIPLES_WS_DEFAULT))
-    each = triple_bytes(nv)
-    ws_bytes = each * max(1, min(int(workspace_bytes) // each, max(hi - lo, 1)))
-    k_dev, orb_dev, m_dev, imap = tints.device_tables()
-    temps = [ctx.array(np.append(vec, 0.0)), ctx.empty((no, no, nv)), ctx.array(eps), ctx.empty((ws_bytes // 8,))]
-    src, Tc, eps_dev, ws = temps
-    out = ctx.empty((max(hi - lo, 1),)) if per_triple else None
-    e = C.c_double()
-    try:
-        gather(ctx, Tc, src, imap)
-        ctx.lib.call("pymes_sector_triples", ctx.handle, no, nv, C.c_void_p(eps_dev.ptr), C.c_void_p(k_dev.ptr),
-                     C.c_void_p(orb_dev.ptr), tt.box.ctypes.data_as(C.c_void_p), C.c_void_p(m_dev.ptr), C.c_void_p(Tc.ptr),
-                     C.c_void_p(tints.Vv.ptr), C.c_void_p(tints.Vo.ptr), int(lo), int(hi), C.c_void_p(ws.ptr), int(ws_bytes),
-                     C.c_void_p(out.ptr if out is not None else None), C.byref(e))
-        values = out.get()[:hi - lo] if out is not None else None
-    finally:
-        for t in temps + ([out] if out is not None else []):
-            t.free()
-    energy = float(e.value)
-    if reduce:
-        energy = float(pdist.allreduce_sum([energy])[0])
-    return (energy, values) if per_triple else energy
-
-
-def _symmetric_compact(who, tab, amps, what):
-    vec = SectorCCD._compact(tab, amps, "lambda" if what.startswith("lambda") else "amps")
-    if len(vec) and np.abs(vec - vec[tab.pp_swap]).max() > 1e-13 * max(np.abs(vec).max(), 1e-300):
-        raise ValueError(who + ": %s not exchange-symmetric (X_abij = X_baji)" % what)
-    return vec
+    return _triples_energy("sector_triples_energy", eps, ints, tints, amps, None, triple_range, per_triple, workspace_bytes)
 
 
 def sector_lambda_triples_energy(eps, ints, tints, amps, lam, triple_range=None, per_triple=False, workspace_bytes=None):
@@ -438,49 +452,53 @@ def sector_lambda_triples_energy(eps, ints, tints, amps, lam, triple_range=None,
     [v,v,o,o] array, lam in the library's normalisation (``SectorLambda``; A^T lam + eta = 0).  Everything else as
     ``sector_triples_energy``: triple ranges, the split over ranks and the all-reduce, batches of as many triples as
     ``workspace_bytes`` hold (``lambda_triple_bytes(nv)`` each: two slabs).  Nothing asks for V_pqrs = V_rspq."""
-    who = "sector_lambda_triples_energy"
-    _check_triples(who, ints, tints, left=True)
+    return _triples_energy("sector_lambda_triples_energy", eps, ints, tints, amps, lam, triple_range, per_triple,
+                           workspace_bytes)
+
+
+def _triples_energy(who, eps, ints, tints, amps, lam, triple_range, per_triple, workspace_bytes):
+    """The driver behind ``sector_triples_energy`` (``lam`` None: one slab per triple, ``pymes_sector_triples``) and
+    ``sector_lambda_triples_energy`` (two slabs, ``pymes_sector_triples_lambda``)."""
+    left = lam is not None
+    _check_triples(who, ints, tints, left=left)
     tab, ctx, tt = ints.tables, ints.ctx, tints.tables
-    eps = np.asarray(eps, dtype=np.float64)
-    if eps.ndim == 2:
-        if np.count_nonzero(eps - np.diag(eps.diagonal())):
-            raise ValueError(who + ": the Fock matrix must be diagonal (it is for a momentum-conserving Hamiltonian)")
-        eps = eps.diagonal().copy()
-    if eps.shape != (tab.n,):
-        raise ValueError(who + ": %d orbital energies for %d orbitals" % (eps.size, tab.n))
-    vec = _symmetric_compact(who, tab, amps, "the amplitudes are")
-    lvec = _symmetric_compact(who, tab, lam, "lambda is")
+    eps = _diagonal_eps(who, tab, eps)
+    vec = _symmetric_compact(who, tab, amps, "the amplitudes are", "(X_abij = X_baji)" if left else "(T_abij = T_baji)")
+    lvec = _symmetric_compact(who, tab, lam, "lambda is") if left else None
     no, nv = tab.no, tab.nv
     lo, hi, reduce = ccsd_t._triple_chunk(no, triple_range)
     if not 0 <= lo <= hi <= ccsd_t.n_triples(no):
         raise ValueError(who + ": triple range [%d, %d) outside [0, %d]" % (lo, hi, ccsd_t.n_triples(no)))
     if workspace_bytes is None:
         workspace_bytes = int(os.environ.get(TRIPLES_WS_ENV, TRIPLES_WS_DEFAULT))
-    each = lambda_triple_bytes(nv)
+    each = lambda_triple_bytes(nv) if left else triple_bytes(nv)
     ws_bytes = each * max(1, min(int(workspace_bytes) // each, max(hi - lo, 1)))
     k_dev, orb_dev, m_dev, imap = tints.device_tables()
-    # Lc[i,j,a] = L[a,b*,i,j], L = (2 lam + lam^x) / 3: the implied map, and the same map behind the exchange of a and b
-    a, b, i, j = tab.abij()
-    swapped = upload_raw(ctx, np.append(tab._pp_index(b, a, i, j), tab.nnz)[tt.implied_map.reshape(-1)])
-    swapped.count = imap.count
-    temps = [swapped]
+    temps = []
 
-    def temp(make, arg):                     # one at a time, so that whatever was allocated is freed if a later one fails
-        temps.append(make(arg))
+    def temp(make, *args):                   # one at a time, so that whatever was allocated is freed if a later one fails
+        temps.append(make(*args))
         return temps[-1]
+    ptr = lambda arr: C.c_void_p(arr.ptr if arr is not None else None)
     e = C.c_double()
     try:
-        src, lsrc = temp(ctx.array, np.append(vec, 0.0)), temp(ctx.array, np.append(lvec, 0.0))
-        Tc, Lc = temp(ctx.empty, (no, no, nv)), temp(ctx.empty, (no, no, nv))
+        src, Tc = temp(ctx.array, np.append(vec, 0.0)), temp(ctx.empty, (no, no, nv))
+        operands = [Tc, tints.Vv, tints.Vo]
+        if left:
+            # Lc[i,j,a] = L[a,b*,i,j], L = (2 lam + lam^x) / 3: the implied map, and the same map behind the exchange of a and b
+            a, b, i, j = tab.abij()
+            swapped = temp(upload_map, ctx, np.append(tab._pp_index(b, a, i, j), tab.nnz)[tt.implied_map.reshape(-1)],
+                           tab.nnz + 1)
+            lsrc, Lc = temp(ctx.array, np.append(lvec, 0.0)), temp(ctx.empty, (no, no, nv))
+            operands = [Tc, Lc, tints.VvR, tints.VoR, tints.Vv, tints.Vo]
         eps_dev, ws = temp(ctx.array, eps), temp(ctx.empty, (ws_bytes // 8,))
         out = temp(ctx.empty, (max(hi - lo, 1),)) if per_triple else None
         gather(ctx, Tc, src, imap)
-        gather(ctx, Lc, lsrc, imap, 2.0 / 3.0, lsrc, swapped, 1.0 / 3.0)
-        ctx.lib.call("pymes_sector_triples_lambda", ctx.handle, no, nv, C.c_void_p(eps_dev.ptr), C.c_void_p(k_dev.ptr),
-                     C.c_void_p(orb_dev.ptr), tt.box.ctypes.data_as(C.c_void_p), C.c_void_p(m_dev.ptr), C.c_void_p(Tc.ptr),
-                     C.c_void_p(Lc.ptr), C.c_void_p(tints.VvR.ptr), C.c_void_p(tints.VoR.ptr), C.c_void_p(tints.Vv.ptr),
-                     C.c_void_p(tints.Vo.ptr), int(lo), int(hi), C.c_void_p(ws.ptr), int(ws_bytes),
-                     C.c_void_p(out.ptr if out is not None else None), C.byref(e))
+        if left:
+            gather(ctx, Lc, lsrc, imap, 2.0 / 3.0, lsrc, swapped, 1.0 / 3.0)
+        ctx.lib.call("pymes_sector_triples_lambda" if left else "pymes_sector_triples", ctx.handle, no, nv, ptr(eps_dev),
+                     ptr(k_dev), ptr(orb_dev), tt.box.ctypes.data_as(C.c_void_p), ptr(m_dev), *map(ptr, operands), int(lo),
+                     int(hi), ptr(ws), int(ws_bytes), ptr(out), C.byref(e))
         values = out.get()[:hi - lo] if out is not None else None
     finally:
         for t in temps:
@@ -514,9 +532,7 @@ class SectorCCD:
         dt.hole.run(T, hole, R)
         dt.ladder.run(ints["abcd"], T, R)
         # direct and crossed layouts of T, and Tt = 2 D - C
-        gather(ctx, D, T, dt.d_from_pp)
-        gather(ctx, Cx, T, dt.c_from_pp)
-        gather(ctx, Tt, T, dt.d_from_pp, 2.0, T, dt.c_from_pp, -1.0)
+        dt.layouts(T, D, Cx, Tt)
         dt.to_square.run(ints["w1"], Tt, sq)                     # X^q = W1^q Tt^{-q}
         dt.from_square_neg.run(Tt, sq, Rd)                       # Rd^q = Tt^q X^{-q}                  (:202-204)
         dt.from_square_neg.run(Tt, ints["w2"], Ed)               # Ed^q = Tt^q W2^{-q}
@@ -524,7 +540,7 @@ class SectorCCD:
         dt.from_square_neg_t.run(Cx, ints["wa"], Ec)             # Ec^q = -C^q Wb^{-q},  Wb = Wa^T
         if quad:
             CmD, Rc = ws["CmD"], ws["Rc"]
-            gather(ctx, CmD, T, dt.c_from_pp, 1.0, T, dt.d_from_pp, -1.0)
+            dt.layouts(T, CmD=CmD)
             dt.to_square.run(D, ints["wx"], sq)                  # Y^q = D^q Wx^{-q}
             dt.square_left_add.run(sq, CmD, Ed)                  # Ed^q += Y^q (C^q - D^q)             (:237-240)
             dt.to_square.run(Cx, ints["wx"], sq)                 # Xc^q = C^q Wx^{-q}
@@ -576,25 +592,7 @@ class SectorCCD:
         return vec
 
     def _checks(self, eps, ints):
-        if not isinstance(ints, SectorIntegrals):
-            raise TypeError("SectorCCD.solve: ints must be SectorIntegrals (UEG.eval_2b_sectors); the dense path is CCD")
-        tab, ctx = ints.tables, ints.ctx
-        if ctx.recording:
-            raise RuntimeError("SectorCCD.solve: the context is recording a launch graph")
-        eps = np.asarray(eps, dtype=np.float64)
-        if eps.ndim == 2:
-            if np.count_nonzero(eps - np.diag(eps.diagonal())):
-                raise ValueError("SectorCCD.solve: the Fock matrix must be diagonal (it is for a momentum-conserving Hamiltonian)")
-            eps = eps.diagonal().copy()
-        if tab.no != self.no or eps.shape != (tab.n,):
-            raise ValueError("SectorCCD.solve: the tables of the integrals (no = %d, n = %d) do not match the solver (no = %d) "
-                             "and the %d orbital energies" % (tab.no, tab.n, self.no, eps.size))
-        # the product list needs V_klcd = V_lkdc (the X_ac / X_ki sums read W1 where ccd.py:213-220 reads V_lkdc)
-        w1 = ints["w1"].get()
-        if len(w1) and np.abs(w1 - w1[tab.d_partner]).max() > 1e-12 * max(np.abs(w1).max(), 1e-300):
-            raise ValueError("SectorCCD.solve: the integrals are not symmetric under the exchange of the two electrons "
-                             "(V_pqrs = V_qpsr), which the sector residual needs")
-        return eps
+        return _check_solver_inputs("SectorCCD.solve", self.no, eps, ints, "CCD")
 
     def solve(self, eps, ints, level_shift=0., amps=None, triples=None, lambda_triples=None, density=False, **kwargs):
         """The loop of ``CCD.solve`` (ccd.py:24-162) on the compact vector.  eps: the orbital energies (or a diagonal Fock
@@ -634,23 +632,14 @@ class SectorCCD:
             e_mp2 = e_dir + e_exc
             print("MP2 energy = ", e_mp2)
             if amps is not None:
-                vec = self._compact(tab, amps)
-                if np.abs(vec - vec[tab.pp_swap]).max() > 1e-13 * max(np.abs(vec).max(), 1e-300):
-                    raise ValueError("SectorCCD.solve: the amplitudes are not exchange-symmetric (T_abij = T_baji), which the "
-                                     "sector residual needs")
-                t2.set(vec)
+                t2.set(_symmetric_compact("SectorCCD.solve", tab, amps, "the amplitudes are",
+                                          "(T_abij = T_baji), which the sector residual needs"))
             dE, iteration, e_last = np.abs(e_mp2), 0, e_mp2
             e_ccd = e_dir_ccd = e_ex_ccd = 0.
             while np.abs(dE) > delta_e and iteration <= max_iter:
                 iteration += 1
                 self.residual(ints, eps_dev, t2, r2, ws)                              # ccd.py:100-102
-                if self.is_diis:
-                    t2n, dt2 = ctx.pool_get((n,)), ctx.pool_get((n,))
-                    self._update(ctx, t2n, dt2, t2, r2, den, level_shift)             # :123-124
-                    self.mixer.mix([dt2], [t2n], release=ctx.pool_put, out=[t2], defer_log=True, native=True)   # :126-127
-                else:
-                    dt2 = dt_fixed
-                    self._update(ctx, t2, dt2, t2, r2, den, level_shift)
+                dt2 = self._step(ctx, t2, r2, den, level_shift, dt_fixed)           # :123-127
                 e_dir_ccd, e_ex_ccd, nt2, nr2 = self._energy(ctx, ints, t2, dt2)      # :132 and the norms, one pass
                 if self.is_diis:
                     self.mixer.log_last()
@@ -704,6 +693,17 @@ class SectorCCD:
                      C.c_void_p(t_in.ptr if t_in is not None else 0), C.c_void_p(r.ptr), C.c_void_p(den.ptr), float(shift),
                      t_out.size)
 
+    def _step(self, ctx, x, r, den, shift, dx_fixed):
+        """x <- x + r / (den + shift), through the DIIS mixer if there is one (its log line is the caller's:
+        ``mixer.log_last()``); returns the step dx.  The step of ``SectorCCD.solve`` and of ``SectorLambda.solve``."""
+        if not self.is_diis:
+            SectorCCD._update(ctx, x, dx_fixed, x, r, den, shift)
+            return dx_fixed
+        xn, dx = ctx.pool_get(x.shape), ctx.pool_get(x.shape)
+        SectorCCD._update(ctx, xn, dx, x, r, den, shift)
+        self.mixer.mix([dx], [xn], release=ctx.pool_put, out=[x], defer_log=True, native=True)
+        return dx
+
     @staticmethod
     def _energy(ctx, ints, t2, dt2=None):
         """(direct, exchange, |T|^2, |dT|^2): ccd.py:256-262 on the compact vector, one launch and one synchronisation."""
@@ -729,24 +729,10 @@ class SectorLambda:
 
     def _checks(self, eps, ints, amps):
         who = "SectorLambda.solve"
-        if not isinstance(ints, SectorIntegrals):
-            raise TypeError(who + ": ints must be SectorIntegrals (UEG.eval_2b_sectors); the dense path is Lambda_CCSD")
-        tab, ctx = ints.tables, ints.ctx
-        if ctx.recording:
-            raise RuntimeError(who + ": the context is recording a launch graph")
-        eps = np.asarray(eps, dtype=np.float64)
-        if eps.ndim == 2:
-            if np.count_nonzero(eps - np.diag(eps.diagonal())):
-                raise ValueError(who + ": the Fock matrix must be diagonal (it is for a momentum-conserving Hamiltonian)")
-            eps = eps.diagonal().copy()
-        if tab.no != self.no or eps.shape != (tab.n,):
-            raise ValueError(who + ": the tables of the integrals (no = %d, n = %d) do not match the solver (no = %d) "
-                             "and the %d orbital energies" % (tab.no, tab.n, self.no, eps.size))
-        w1 = ints["w1"].get()
-        if len(w1) and np.abs(w1 - w1[tab.d_partner]).max() > 1e-12 * max(np.abs(w1).max(), 1e-300):
-            raise ValueError(who + ": the integrals are not symmetric under the exchange of the two electrons "
-                             "(V_pqrs = V_qpsr), which the sector residual needs")
-        return eps, _symmetric_compact(who, tab, amps, "the amplitudes are")
+        eps = _check_solver_inputs(who, self.no, eps, ints, "Lambda_CCSD")
+        return eps, _symmetric_compact(who, ints.tables, amps, "the amplitudes are")
+
+    _step = SectorCCD._step
 
     # ---- what depends on T alone: its three layouts, hole(T), X = W1 Tt, Y = D Wx, Xc = C Wx -----------------------------
     def hoist(self, ints, T):
@@ -754,16 +740,14 @@ class SectorLambda:
         nnz, nsq = max(tab.nnz, 1), max(dt.nsq, 1)
         quad = not self.is_dcd
         h = {"T": T, "D": ctx.empty((nnz,)), "C": ctx.empty((nnz,)), "Tt": ctx.empty((nnz,)), "X": ctx.empty((nsq,))}
-        gather(ctx, h["D"], T, dt.d_from_pp)
-        gather(ctx, h["C"], T, dt.c_from_pp)
-        gather(ctx, h["Tt"], T, dt.d_from_pp, 2.0, T, dt.c_from_pp, -1.0)
+        dt.layouts(T, h["D"], h["C"], h["Tt"])
         dt.to_square.run(ints["w1"], h["Tt"], h["X"])                      # X^q = W1^q Tt^{-q}
         h["hole"] = ints["klij"]
         if quad:
             h["hole"] = ctx.empty((max(ints.sizes["klij"], 1),)).copy_from(ints["klij"])
             dt.hole_quad.run(ints["klcd"], T, h["hole"])                   # I^P = V_klij^P + V_klcd^P T^P
             h["CmD"], h["Y"], h["Xc"] = ctx.empty((nnz,)), ctx.empty((nsq,)), ctx.empty((nsq,))
-            gather(ctx, h["CmD"], T, dt.c_from_pp, 1.0, T, dt.d_from_pp, -1.0)
+            dt.layouts(T, CmD=h["CmD"])
             dt.to_square.run(h["D"], ints["wx"], h["Y"])                   # Y^q = D^q Wx^{-q}
             dt.to_square.run(h["C"], ints["wx"], h["Xc"])                  # Xc^q = C^q Wx^{-q}
         h["eta"] = ctx.empty((nnz,))
@@ -790,11 +774,7 @@ class SectorLambda:
         quad = not self.is_dcd
         w = 1.0 if quad else 0.5
         yRd, yRc, yEd, yEc, zTt, zD, zC, Gp, Z = (ws[k] for k in ("yRd", "yRc", "yEd", "yEc", "zTt", "zD", "zC", "Gp", "Z"))
-        # the cotangents of Rd, Rc and of Ed, Ec (which enter as Ex + Ex^T(1,0,3,2)): gathers through the inverse maps
-        gather(ctx, yRd, lam, dt.d_from_pp)
-        gather(ctx, yRc, lam, dt.c_from_pp)
-        gather(ctx, yEd, lam, dt.d_from_pp, 1.0, lam, at.dT_from_pp, 1.0)
-        gather(ctx, yEc, lam, dt.c_from_pp, 1.0, lam, at.cT_from_pp, 1.0)
+        dt.cotangents(lam, yRd, yRc, yEd, yEc)
         # pp layout: G^P = eta^P + V_abcd^P^T lam^P + lam^P I^P^T + [CCD] V_klcd^P^T (T^P^T lam^P)
         Gp.copy_from(h["eta"])
         at.ladder_t.run(ints["abcd"], lam, Gp)
@@ -868,13 +848,9 @@ class SectorLambda:
                 if converged or iteration >= max_iter:
                     break
                 iteration += 1
+                self._step(ctx, l2, g2, den, level_shift, dl_fixed)
                 if self.is_diis:
-                    l2n, dl2 = ctx.pool_get((n,)), ctx.pool_get((n,))
-                    SectorCCD._update(ctx, l2n, dl2, l2, g2, den, level_shift)
-                    self.mixer.mix([dl2], [l2n], release=ctx.pool_put, out=[l2], defer_log=True, native=True)
                     self.mixer.log_last()
-                else:
-                    SectorCCD._update(ctx, l2, dl_fixed, l2, g2, den, level_shift)
             if not converged:
                 print_logging_info("A converged Lambda is not found!", level=1)
             self.iterations = iteration
@@ -883,17 +859,6 @@ class SectorLambda:
             ctx.pool_put(g2)
             return {"lambda2": SectorAmplitudes(tab, result), "lambda residual": norm, "iterations": iteration,
                     "converged": converged}
-
-
-def _diagonal_eps(who, tab, eps):
-    eps = np.asarray(eps, dtype=np.float64)
-    if eps.ndim == 2:
-        if np.count_nonzero(eps - np.diag(eps.diagonal())):
-            raise ValueError(who + ": the Fock matrix must be diagonal (it is for a momentum-conserving Hamiltonian)")
-        eps = eps.diagonal().copy()
-    if eps.shape != (tab.n,):
-        raise ValueError(who + ": %d orbital energies for %d orbitals" % (eps.size, tab.n))
-    return eps
 
 
 def sector_density(eps, ints, amps, lam, is_dcd=False):
@@ -944,7 +909,7 @@ class SectorDensity:
 
     def _build(self):
         ctx, tab, dt = self.ctx, self.tables, self._dt
-        at, dn = dt.adjoint(), dt.density()
+        dn = dt.density()
         quad = not self.is_dcd
         nnz, nsq = max(tab.nnz, 1), max(dt.nsq, 1)
         T, lam = self.T, self.lam
@@ -962,13 +927,8 @@ class SectorDensity:
             self["klcd"].zero_()
             self["wx"].zero_()
         # the ph layouts of T and the cotangents of Rd, Rc, Ed, Ec (the first rows of the table of DESIGN 8k)
-        gather(ctx, D, T, dt.d_from_pp)
-        gather(ctx, Cx, T, dt.c_from_pp)
-        gather(ctx, Tt, T, dt.d_from_pp, 2.0, T, dt.c_from_pp, -1.0)
-        gather(ctx, yRd, lam, dt.d_from_pp)
-        gather(ctx, yRc, lam, dt.c_from_pp)
-        gather(ctx, yEd, lam, dt.d_from_pp, 1.0, lam, at.dT_from_pp, 1.0)
-        gather(ctx, yEc, lam, dt.c_from_pp, 1.0, lam, at.cT_from_pp, 1.0)
+        dt.layouts(T, D, Cx, Tt)
+        dt.cotangents(lam, yRd, yRc, yEd, yEc)
         dn.sq_tn.run(Tt, yRd, Z)                                 # Z^q = (Tt^{-q})^T yRd^{-q}          (of X = W1 Tt)
         dn.sq_right_t.run(Z, Tt, self["w1"])                     # G_w1^q = Z^q (Tt^{-q})^T
         dn.sq_tn.run(Tt, yEd, self["w2"])                        # G_w2^q = (Tt^{-q})^T yEd^{-q}       (Ed = Tt W2)
@@ -976,7 +936,7 @@ class SectorDensity:
         dn.sq_tn_sub.run(yEc, Cx, self["wa"])                    # G_wa^q -= (yEc^{-q})^T C^{-q}       (Ec = -C Wa^T)
         if quad:
             CmD = ctx.empty((nnz,))
-            gather(ctx, CmD, T, dt.c_from_pp, 1.0, T, dt.d_from_pp, -1.0)
+            dt.layouts(T, CmD=CmD)
             dn.outer.run(yEd, CmD, Z)                            # zY^q = yEd^q (C^q - D^q)^T
             dn.left_tn.run(D, Z, self["wx"])                     # G_wx^q = (D^{-q})^T zY^{-q}         (Y = D Wx)
             dn.outer.run(yRc, Cx, Z)                             # zXc^q = yRc^q (C^q)^T
@@ -1006,8 +966,7 @@ class SectorDensity:
             raise ValueError(who + ": W belongs to other tables or another context than the density")
         if self.ctx.recording:
             raise RuntimeError(who + ": the context is recording a launch graph")
-        w1 = W["w1"].get()
-        if len(w1) and np.abs(w1 - w1[self.tables.d_partner]).max() > 1e-12 * max(np.abs(w1).max(), 1e-300):
+        if not _exchange_symmetric(W):
             raise ValueError(who + ": W is not symmetric under the exchange of the two electrons (W_pqrs = W_qpsr), which "
                              "the sector densities need")
 
@@ -1053,16 +1012,8 @@ class SectorDensity:
         kernels trust them)."""
         if self._bins_dev is None:
             ctx, tab, tb = self.ctx, self.tables, self.bins()
-
-            def imap(host, limit):
-                host = np.ascontiguousarray(host, dtype=np.int64)
-                if len(host) and (host.min() < -1 or host.max() >= limit):
-                    raise AssertionError("transfer bins: an index points outside its array")
-                return upload_raw(ctx, host)
-
-            def i32(x):
-                x = np.ascontiguousarray(x, dtype=np.int32).reshape(-1)
-                return upload_raw(ctx, np.append(x, np.zeros(x.size % 2, dtype=np.int32)))
+            imap = lambda host, limit: upload_map(ctx, host, limit, "transfer bins: an index points outside its array", -1)
+            i32 = lambda host: upload_i32(ctx, host)
             csr = {}
             for nm in self.FAMILIES:
                 off, order = tb.csr[nm]

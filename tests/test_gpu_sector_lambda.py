@@ -266,6 +266,8 @@ def test_kernel_matches_the_two_slab_restatement(ctx, case):
 
 @pytest.mark.parametrize("case", [(14, 5), (14, 8), "twist"], ids=str)
 def test_hermitian_operands_with_L_equal_T_give_the_triples_kernel(ctx, case):
+    """(T) and Lambda-(T) are the one-slab and the two-slab instantiation of one energy kernel: with equal slabs
+    they give equal bits, which a kernel that reads the wrong slab somewhere does not."""
     tab, tt = support(case)
     eps, Tc, Vv, Vo = random_operands(tt, 31)
     n = R.n_triples(tt.no)
@@ -275,6 +277,7 @@ def test_hermitian_operands_with_L_equal_T_give_the_triples_kernel(ctx, case):
     record(f"(T) identity {case}: worst |Lambda-(T) - (T)| / scale = "
            f"{(np.abs(p_l - p_t)[scale > 0] / scale[scale > 0]).max():.2e}")
     assert (np.abs(p_l - p_t) <= 1e-12 * scale).all() and np.count_nonzero(p_t) > 0
+    assert np.array_equal(p_l.view(np.int64), p_t.view(np.int64)) and e_l == e_t
 
 
 def test_batches_and_ranges_give_identical_bits(ctx):

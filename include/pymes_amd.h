@@ -687,6 +687,54 @@ int pymes_sector_pair_transfer(pymes_ctx* ctx, double* out_dev, int64_t nbins, c
  * gamma_dev: no + nv doubles; ws_dev: no nv doubles. */
 int pymes_sector_gamma(pymes_ctx* ctx, const double* x_dev, const double* y_dev, int no, int nv, const int64_t* row_start_dev,
                        const int64_t* row_len_dev, const int64_t* row_of_dev, double* gamma_dev, double* ws_dev);
+/* Sector IP- / EA-EOM-CCD (pymes_amd/solver/ueg_eom.py, SectorIPEASigma): one momentum block of the IP (kind 0) or EA
+ * (kind 1) operator of tests/_ipea_reference.py with t1 = 0 and a diagonal Fock matrix, for the target orbital p (an index over
+ * all no + nv orbitals: occupied for IP, virtual for EA).  The block is the singles element r1[p] and the doubles with their
+ * implied virtual b* left out, at the positions t = x no + y:
+ *   IP  R[i,j] = r2[i,j,b*], k_b* = k_i + k_j - k_p, [no,no]        EA  R[a,j] = r2[a,b*,j], k_b* = k_p + k_j - k_a, [nv,no]
+ * b_of[t] = b* counted from the first virtual, or -1: such a position is not part of the space.  k_int_dev, orb_of_dev, box_host
+ * and the exact-zero contract of Tc, Vv, Vo, VvR, VoR: as pymes_sector_triples / pymes_sector_triples_lambda.  All three are
+ * refused while a launch graph is being recorded.
+ *
+ * pymes_sector_ipea_prepare: what depends on the target alone, every sum in ascending index order.  L_dev: no + nv doubles,
+ * L_oo then L_vv (the x of pymes_sector_xdiag with w = 1).  With orbv(q) the virtual that carries q (counted from the first
+ * virtual), a term being left out where there is none, and pv = p - no:
+ *   IP  d2[t] = L[no + b*] - L[i] - L[j]            W[t] = -2 Vo[j,i,b*] + Vo[i,j,b*]
+ *       U[t]  = -VoR[j,i,b*] + sum_k { c = orbv(k_k + k_p - k_i): Vo[k,p,c] (-2 Tc[k,j,c] + Tc[j,k,c]) + Vo[p,k,c] Tc[k,j,c];
+ *                                      c = orbv(k_k + k_p - k_j): Vo[p,k,c] Tc[i,k,c] }
+ *               - sum_c { orbv(k_i + k_j - k_c) = d: Vv[p,c,d] Tc[i,j,c] }
+ *   EA  d2[t] = L[no + a] + L[no + b*] - L[j]       W[t] = 2 Vv[j,b*,a] - Vv[j,a,b*]
+ *       U[t]  = VvR[j,b*,a] + sum_k { c = orbv(k_k + k_a - k_p): Vv[k,c,pv] (2 Tc[k,j,c] - Tc[j,k,c]) - Vv[k,pv,c] Tc[k,j,c];
+ *                                     c = orbv(k_k + k_b* - k_p): -Vv[k,pv,c] Tc[j,k,c];
+ *                                     m the occupied with k_p + k_j - k_k: Vo[k,m,pv] Tc[k,m,a] }
+ * and U = W = 0, d2 = outside (finite, non-zero) where b_of[t] < 0.  d2 is the doubles part of the preconditioner's diagonal
+ * (d1 = -L[p] / L[p]) and the coefficient of R in s2; U is everything r1 multiplies in s2; s1 = -+ L[p] r1 + sum_t W[t] R[t].
+ *
+ * pymes_sector_ipea_pack: the k <= 32 vectors r2_dev[z] (npos doubles each) into the operands of the products, the vector index
+ * running fastest: XR[ph[t] k + z] = R_z[t], XX[ph[t] k + z] = R_z[partner[t]], XP[pair[t] k + z] = R_z[t] for the positions
+ * inside the space.  ph, partner, pair: int64 [npos] on the device, -1 outside the space, bijections of the space onto
+ * [0, count) resp. an involution of it (sectors.QuasiparticleTables; the host checks them, the kernels trust them).
+ *
+ * pymes_sector_ipea_assemble: s2_z[t] = d2[t] R_z[t] + r1_z U[t] + G1[ph[t] k + z] + G2[ph_partner[t] k + z] + H[pair[t] k + z],
+ * added in this order, an exact +0.0 outside the space, and s1_z = d1 r1_z + sum_t W[t] R_z[t] (one workgroup per vector:
+ * each thread over t = tid, tid + 256, ... ascending, then a fixed tree).  G1 = PA XR + PB XX, G2 = MDU XX (the ring products),
+ * H the ladder product of XP, all from pymes_sector_gemm.  r1_dev[z], s1_dev[z] point at one double.  No atomics: identical
+ * calls give identical bits, and a vector's sigma does not depend on the others of its call. */
+int pymes_sector_ipea_prepare(pymes_ctx* ctx, int kind, int target, int no, int nv, const int32_t* k_int_dev,
+                              const int32_t* orb_of_dev, const int32_t* box_host, const int32_t* b_of_dev, const double* L_dev,
+                              const double* Tc_dev, const double* Vv_dev, const double* Vo_dev, const double* VvR_dev,
+                              const double* VoR_dev, double outside, double* U_dev, double* W_dev, double* d2_dev);
+int pymes_sector_ipea_pack(pymes_ctx* ctx, int k, const double* const* r2_dev, int64_t npos, const int64_t* ph_dev,
+                           const int64_t* partner_dev, const int64_t* pair_dev, double* XR_dev, double* XX_dev, double* XP_dev);
+int pymes_sector_ipea_assemble(pymes_ctx* ctx, int k, const double* const* r1_dev, const double* const* r2_dev,
+                               double* const* s1_dev, double* const* s2_dev, int64_t npos, const int64_t* ph_dev,
+                               const int64_t* ph_partner_dev, const int64_t* pair_dev, const double* d2_dev, const double* U_dev,
+                               const double* W_dev, double d1, const double* G1_dev, const double* G2_dev, const double* H_dev);
+/* pymes_eom_correction (below) for flat vectors [x1 (n1) | zero pad | x2] of any lengths, n1 >= 1, off2 >= n1, len > off2: the
+ * same kernels.  Refused while a launch graph is being recorded. */
+int pymes_sector_ipea_correction(pymes_ctx* ctx, int n, const double* const* s_dev, const double* const* r_dev, const double* w_host,
+                                 const double* d_dev, double shift, double* const* q_dev, int64_t n1, int64_t off2, int64_t len,
+                                 double* norms_host);
 
 /* ---- vector helpers for DIIS (pymes/mixer/diis.py:65-103) and norms ----------------- */
 /* out_host[p] = sum_i x[p][i]*y[p][i], npairs <= 16, deterministic reduction (synchronises) */

@@ -166,6 +166,14 @@ SIGNATURES = {
     "pymes_sector_pair_transfer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64]
                                    + [C.c_void_p] * 6 + [C.c_int]),
     "pymes_sector_gamma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    # sector IP- / EA-EOM-CCD: what depends on the target, operand packing, assembly, the Davidson correction on any lengths
+    "pymes_sector_ipea_prepare": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_double]
+                                  + [C.c_void_p] * 3),
+    "pymes_sector_ipea_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
+    "pymes_sector_ipea_assemble": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 6
+                                   + [C.c_double] + [C.c_void_p] * 3),
+    "pymes_sector_ipea_correction": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                               C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "pymes_hf_fock_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pymes_fcidump_header": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pymes_fcidump_read_host": (C.c_int, [C.c_char_p, C.c_int, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1011,6 +1011,49 @@ int pymes_sector_gamma(pymes_ctx* ctx, const double* x, const double* y, int no,
                        const int64_t* row_len, const int64_t* row_of, double* gamma, double* ws) {
     return guarded([&] { dev::sector_gamma(x, y, no, nv, row_start, row_len, row_of, gamma, ws, E(ctx).stream); });
 }
+// ---- sector IP- / EA-EOM-CCD (kernels_sector.hip; pymes_amd/solver/ueg_eom.py) -----------------------------------------
+int pymes_sector_ipea_prepare(pymes_ctx* ctx, int kind, int target, int no, int nv, const int32_t* k_int, const int32_t* orb_of,
+                              const int32_t* box, const int32_t* b_of, const double* L, const double* Tc, const double* Vv,
+                              const double* Vo, const double* VvR, const double* VoR, double outside, double* U, double* W,
+                              double* d2) {
+    return guarded([&] {
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("sector_ipea_prepare while a launch graph is being recorded");
+        dev::sector_ipea_prepare(kind, target, no, nv, k_int, orb_of, box, b_of, L, Tc, Vv, Vo, VvR, VoR, outside, U, W, d2, e.stream);
+    });
+}
+int pymes_sector_ipea_pack(pymes_ctx* ctx, int k, const double* const* r2, int64_t npos, const int64_t* ph, const int64_t* partner,
+                           const int64_t* pair, double* XR, double* XX, double* XP) {
+    return guarded([&] {
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("sector_ipea_pack while a launch graph is being recorded");
+        dev::sector_ipea_pack(k, r2, npos, ph, partner, pair, XR, XX, XP, e.stream);
+    });
+}
+int pymes_sector_ipea_assemble(pymes_ctx* ctx, int k, const double* const* r1, const double* const* r2, double* const* s1,
+                               double* const* s2, int64_t npos, const int64_t* ph, const int64_t* ph_partner, const int64_t* pair,
+                               const double* d2, const double* U, const double* W, double d1, const double* G1, const double* G2,
+                               const double* H) {
+    return guarded([&] {
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("sector_ipea_assemble while a launch graph is being recorded");
+        dev::sector_ipea_assemble(k, r1, r2, s1, s2, npos, ph, ph_partner, pair, d2, U, W, d1, G1, G2, H, e.stream);
+    });
+}
+int pymes_sector_ipea_correction(pymes_ctx* ctx, int n, const double* const* s, const double* const* r, const double* w_host,
+                                 const double* d, double shift, double* const* q, int64_t n1, int64_t off2, int64_t len,
+                                 double* norms_host) {
+    return guarded([&] {
+        need(s, "s"); need(r, "r"); need(w_host, "w"); need(d, "d"); need(q, "q"); need(norms_host, "norms");
+        if (n < 0 || n > 4096) throw pymes::Error("sector_ipea_correction: 0 <= n <= 4096");
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("sector_ipea_correction while a launch graph is being recorded");
+        if (n1 < 1 || off2 < n1 || len <= off2) throw pymes::Error("sector_ipea_correction: the flat layout is not [x1 | pad | x2]");
+        for (int z = 0; z < n; ++z)
+            if (!s[z] || !r[z] || !q[z]) throw pymes::Error("sector_ipea_correction: null vector");
+        pymes::davidson_correction(e, n, s, r, w_host, d, shift, q, n1, off2, len, norms_host);
+    });
+}
 
 int pymes_dots(pymes_ctx* ctx, int npairs, const double* const* x, const double* const* y, int64_t n,
                double* out) {

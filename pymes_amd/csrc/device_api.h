@@ -572,5 +572,16 @@ void sector_pair_transfer(double* out, int64_t nbins, const int32_t* bin_q, cons
                           stream_t s);
 void sector_gamma(const double* x, const double* y, int no, int nv, const int64_t* row_start, const int64_t* row_len,
                   const int64_t* row_of, double* gamma, double* ws, stream_t s);
+// Sector IP- / EA-EOM-CCD (formulas in include/pymes_amd.h, pymes_sector_ipea_*): what depends on the target alone
+// (kind 0 = IP, 1 = EA), the k <= 32 vectors into the operands of the products, and the assembly of their sigma vectors.
+void sector_ipea_prepare(int kind, int target, int no, int nv, const int32_t* k_int, const int32_t* orb_of, const int32_t* box_host,
+                         const int32_t* b_of, const double* L, const double* Tc, const double* Vv, const double* Vo,
+                         const double* VvR, const double* VoR, double outside, double* U, double* W, double* d2, stream_t s);
+void sector_ipea_pack(int k, const double* const* r2, int64_t npos, const int64_t* ph, const int64_t* partner, const int64_t* pair,
+                      double* XR, double* XX, double* XP, stream_t s);
+void sector_ipea_assemble(int k, const double* const* r1, const double* const* r2, double* const* s1, double* const* s2,
+                          int64_t npos, const int64_t* ph, const int64_t* ph_partner, const int64_t* pair, const double* d2,
+                          const double* U, const double* W, double d1, const double* G1, const double* G2, const double* H,
+                          stream_t s);
 
 }  // namespace dev

@@ -947,4 +947,19 @@ __attribute__((weak)) void sector_gamma(const double*, const double*, int, int, 
                                         double*, double*, stream_t) {
     throw std::runtime_error("sector_gamma: not available in this backend");
 }
+__attribute__((weak)) void sector_ipea_prepare(int, int, int, int, const int32_t*, const int32_t*, const int32_t*, const int32_t*,
+                                               const double*, const double*, const double*, const double*, const double*,
+                                               const double*, double, double*, double*, double*, stream_t) {
+    throw std::runtime_error("sector_ipea_prepare: not available in this backend");
+}
+__attribute__((weak)) void sector_ipea_pack(int, const double* const*, int64_t, const int64_t*, const int64_t*, const int64_t*,
+                                            double*, double*, double*, stream_t) {
+    throw std::runtime_error("sector_ipea_pack: not available in this backend");
+}
+__attribute__((weak)) void sector_ipea_assemble(int, const double* const*, const double* const*, double* const*, double* const*,
+                                                int64_t, const int64_t*, const int64_t*, const int64_t*, const double*,
+                                                const double*, const double*, double, const double*, const double*, const double*,
+                                                stream_t) {
+    throw std::runtime_error("sector_ipea_assemble: not available in this backend");
+}
 }  // namespace dev

@@ -2,7 +2,8 @@
 // fp64 product over a device-resident task table, the gathers between the three sector layouts, and the element-wise tails;
 // and of the momentum-blocked (T) on the same path: the W slab, the energy partials and their ordered sum;
 // and the two-slab instantiation of the energy kernel for the Lambda-(T) (what the two share: DESIGN 8m); and the
-// bin sums, the fused V_abcd transfer sums and the gamma sums of the sector densities.
+// bin sums, the fused V_abcd transfer sums and the gamma sums of the sector densities; and the per-target
+// preparation, the operand packing and the assembly of the sector IP- / EA-EOM-CCD sigma.
 // Included at the end of kernels.hip (one code object for the library), not compiled on its own.
 #include <hip/hip_runtime.h>
 
@@ -547,6 +548,156 @@ __global__ void sector_gamma_kernel(const double* __restrict__ rho, const long* 
     }
 }
 
+// ---- sector IP- / EA-EOM-CCD (include/pymes_amd.h, pymes_sector_ipea_*) ------------------------------------------------
+// One momentum block of the operator: the singles element r1[p] and the doubles R[x,y] with their implied virtual b* left out
+// (IP: x = i, y = j, k_b = k_i + k_j - k_p; EA: x = a, y = j, k_b = k_p + k_j - k_a).  The kernels below are written once for
+// both kinds: they see positions t = x no + y, the maps of sectors.QuasiparticleTables (-1 outside the space) and, in the
+// prepare kernel, the kind as a template argument.
+constexpr int kQpMax = 32;
+struct QpIn {            // the k <= 32 vectors of one call, by value: r1_z (one element) and r2_z (npos elements)
+    const double* r1[kQpMax];
+    const double* r2[kQpMax];
+};
+struct QpOut {
+    double* s1[kQpMax];
+    double* s2[kQpMax];
+};
+__device__ __forceinline__ int qp_virtual(const int* __restrict__ orb_of, const TriplesBox& bx, int no, int x, int y, int z) {
+    return triples_orb(orb_of, bx, x, y, z) - no;           // counted from the first virtual; negative: none, or occupied
+}
+
+// What depends on the target alone, one thread per position t = (x,y), every sum in ascending index order:
+//   d2[t]  IP  L_b* - L_i - L_j                      EA  L_a + L_b* - L_j                    (`outside` where b* does not exist)
+//   W[t]   IP  -2 Vo[j,i,b*] + Vo[i,j,b*]            EA  2 Vv[j,b*,a] - Vv[j,a,b*]           (s1 = -+ L_pp r1 + sum_t W[t] R[t])
+//   U[t]   everything r1 multiplies in s2[t], the formulas of include/pymes_amd.h (pymes_sector_ipea_prepare)
+// The implied orbital of each inner sum comes from the lookup box; Tc and the four lists hold an exact 0 where theirs does
+// not exist.  p: the target, an orbital index over all no + nv.
+template <bool kIp>
+__global__ void __launch_bounds__(256) sector_qp_prepare_kernel(int p, int no, int nv, const int* __restrict__ k_int,
+                                                                const int* __restrict__ orb_of, TriplesBox bx,
+                                                                const int* __restrict__ b_of, const double* __restrict__ L,
+                                                                const double* __restrict__ Tc, const double* __restrict__ Vv,
+                                                                const double* __restrict__ Vo, const double* __restrict__ VvR,
+                                                                const double* __restrict__ VoR, double outside,
+                                                                double* __restrict__ U, double* __restrict__ W,
+                                                                double* __restrict__ d2) {
+    const long npos = (long)(kIp ? no : nv) * no;
+    const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (t >= npos) return;
+    const int b = b_of[t];
+    if (b < 0) {
+        U[t] = 0.0;
+        W[t] = 0.0;
+        d2[t] = outside;
+        return;
+    }
+    const int x = (int)(t / no), y = (int)(t % no);
+    const long v = nv;
+    auto oov = [&](int i, int j, int a) { return ((long)i * no + j) * v + a; };
+    auto ovv = [&](int i, int a, int c) { return ((long)i * v + a) * v + c; };
+    const int* kp = k_int + 3 * p;
+    double u;
+    if (kIp) {
+        const int i = x, j = y;
+        const int *ki = k_int + 3 * i, *kj = k_int + 3 * j;
+        d2[t] = L[no + b] - L[i] - L[j];
+        W[t] = -2.0 * Vo[oov(j, i, b)] + Vo[oov(i, j, b)];
+        u = -VoR[oov(j, i, b)];
+        for (int k = 0; k < no; ++k) {
+            const int* kk = k_int + 3 * k;
+            int c = qp_virtual(orb_of, bx, no, kk[0] + kp[0] - ki[0], kk[1] + kp[1] - ki[1], kk[2] + kp[2] - ki[2]);
+            if (c >= 0)
+                u += Vo[oov(k, p, c)] * (-2.0 * Tc[oov(k, j, c)] + Tc[oov(j, k, c)]) + Vo[oov(p, k, c)] * Tc[oov(k, j, c)];
+            c = qp_virtual(orb_of, bx, no, kk[0] + kp[0] - kj[0], kk[1] + kp[1] - kj[1], kk[2] + kp[2] - kj[2]);
+            if (c >= 0) u += Vo[oov(p, k, c)] * Tc[oov(i, k, c)];
+        }
+        for (int c = 0; c < nv; ++c) {
+            const int* kc = k_int + 3 * (no + c);
+            const int d = qp_virtual(orb_of, bx, no, ki[0] + kj[0] - kc[0], ki[1] + kj[1] - kc[1], ki[2] + kj[2] - kc[2]);
+            if (d >= 0) u -= Vv[ovv(p, c, d)] * Tc[oov(i, j, c)];
+        }
+    } else {
+        const int a = x, j = y, pv = p - no;
+        const int *ka = k_int + 3 * (no + a), *kb = k_int + 3 * (no + b), *kj = k_int + 3 * j;
+        d2[t] = L[no + a] + L[no + b] - L[j];
+        W[t] = 2.0 * Vv[ovv(j, b, a)] - Vv[ovv(j, a, b)];
+        u = VvR[ovv(j, b, a)];
+        for (int k = 0; k < no; ++k) {
+            const int* kk = k_int + 3 * k;
+            int c = qp_virtual(orb_of, bx, no, kk[0] + ka[0] - kp[0], kk[1] + ka[1] - kp[1], kk[2] + ka[2] - kp[2]);
+            if (c >= 0)
+                u += Vv[ovv(k, c, pv)] * (2.0 * Tc[oov(k, j, c)] - Tc[oov(j, k, c)]) - Vv[ovv(k, pv, c)] * Tc[oov(k, j, c)];
+            c = qp_virtual(orb_of, bx, no, kk[0] + kb[0] - kp[0], kk[1] + kb[1] - kp[1], kk[2] + kb[2] - kp[2]);
+            if (c >= 0) u -= Vv[ovv(k, pv, c)] * Tc[oov(j, k, c)];
+            const int m = triples_orb(orb_of, bx, kp[0] + kj[0] - kk[0], kp[1] + kj[1] - kk[1], kp[2] + kj[2] - kk[2]);
+            if (m >= 0 && m < no) u += Vo[oov(k, m, pv)] * Tc[oov(k, m, a)];
+        }
+    }
+    U[t] = u;
+}
+
+// Forward: the k vectors into the three operands of the products, the vector index running fastest.  Block (bx, z) takes 256
+// positions of vector z:  XR[ph[t], z] = R_z[t],  XX[ph[t], z] = R_z[partner[t]] (the exchanged element),  XP[pair[t], z] = R_z[t].
+// The maps are bijections of the space onto [0, count), so every element of the three is written, each once.
+__global__ void __launch_bounds__(256) sector_qp_pack_kernel(QpIn in, int k, long npos, const long* __restrict__ ph,
+                                                             const long* __restrict__ partner, const long* __restrict__ pair,
+                                                             double* __restrict__ XR, double* __restrict__ XX,
+                                                             double* __restrict__ XP) {
+    const int z = blockIdx.y;
+    const long t = blockIdx.x * 256L + threadIdx.x;
+    if (t >= npos) return;
+    const long g = ph[t];
+    if (g < 0) return;
+    const double* __restrict__ r2 = in.r2[z];
+    const double a = r2[t];
+    XR[g * k + z] = a;
+    XX[g * k + z] = r2[partner[t]];
+    XP[pair[t] * k + z] = a;
+}
+
+// Backward: s2_z[t] = d2[t] R_z[t] + r1_z U[t] + G1[ph[t], z] + G2[ph_partner[t], z] + H[pair[t], z], added in this order, and an
+// exact +0.0 at a position outside the space; the last block of every vector z adds s1_z = d1 r1_z + sum_t W[t] R_z[t]
+// (each thread over t = tid, tid + 256, ... in ascending order, then a fixed tree): no atomics, identical calls, identical bits.
+__global__ void __launch_bounds__(256) sector_qp_assemble_kernel(QpIn in, QpOut out, int k, long npos, const long* __restrict__ ph,
+                                                                 const long* __restrict__ ph_partner,
+                                                                 const long* __restrict__ pair, const double* __restrict__ d2,
+                                                                 const double* __restrict__ U, const double* __restrict__ W,
+                                                                 double d1, const double* __restrict__ G1,
+                                                                 const double* __restrict__ G2, const double* __restrict__ H) {
+    __shared__ double red[256];
+    const int z = blockIdx.y, tid = threadIdx.x;
+    const double* r2 = in.r2[z];
+    const double r1 = in.r1[z][0];
+    if (blockIdx.x == gridDim.x - 1) {
+        double acc = 0.0;
+        for (long t = tid; t < npos; t += 256) acc = fma(W[t], r2[t], acc);
+        red[tid] = acc;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) red[tid] += red[tid + s];
+            __syncthreads();
+        }
+        if (tid == 0) out.s1[z][0] = d1 * r1 + red[0];
+        return;
+    }
+    const long t = blockIdx.x * 256L + tid;
+    if (t >= npos) return;
+    const long g = ph[t];
+    double v = 0.0;
+    if (g >= 0) {
+        v = fma(r1, U[t], d2[t] * r2[t]);
+        v += G1[g * k + z];
+        v += G2[ph_partner[t] * k + z];
+        v += H[pair[t] * k + z];
+    }
+    out.s2[z][t] = v;
+}
+
+void qp_check(const char* who, int k, int64_t npos) {
+    if (k < 1 || k > kQpMax) throw std::runtime_error(std::string(who) + ": 1 <= k <= 32 vectors per call");
+    if (npos < 1 || (npos + 255) / 256 + 1 > 0x7fffffffL) throw std::runtime_error(std::string(who) + ": bad number of positions");
+}
+
 }  // namespace
 
 namespace dev {
@@ -649,6 +800,59 @@ void sector_gamma(const double* x, const double* y, int no, int nv, const int64_
                   reinterpret_cast<const long*>(row_start), reinterpret_cast<const long*>(row_len), rows, ws);
     launch_kernel(sector_gamma_kernel, dim3((unsigned)((no + nv + 63) / 64)), dim3(64), 0, st, (const double*)ws,
                   reinterpret_cast<const long*>(row_of), no, nv, gamma);
+}
+
+void sector_ipea_prepare(int kind, int target, int no, int nv, const int32_t* k_int, const int32_t* orb_of, const int32_t* box_host,
+                         const int32_t* b_of, const double* L, const double* Tc, const double* Vv, const double* Vo,
+                         const double* VvR, const double* VoR, double outside, double* U, double* W, double* d2, stream_t s) {
+    const std::string who = "sector_ipea_prepare";
+    if (no < 1 || nv < 1 || nv > (1 << 20)) throw std::runtime_error(who + ": bad orbital counts");
+    if (kind != 0 && kind != 1) throw std::runtime_error(who + ": kind must be 0 (IP) or 1 (EA)");
+    if (kind == 0 ? (target < 0 || target >= no) : (target < no || target >= no + nv))
+        throw std::runtime_error(who + (kind == 0 ? ": the target is not an occupied orbital" : ": the target is not a virtual orbital"));
+    if (!k_int || !orb_of || !box_host || !b_of || !L || !Tc || !Vv || !Vo || !VvR || !VoR || !U || !W || !d2)
+        throw std::runtime_error(who + ": null argument");
+    if (!(outside != 0.0) || !std::isfinite(outside)) throw std::runtime_error(who + ": the value outside the space must be finite and non-zero");
+    const TriplesBox bx = triples_box(who, box_host);
+    const long npos = (long)(kind == 0 ? no : nv) * no;
+    const dim3 grid((unsigned)((npos + 255) / 256));
+    launch_kernel(kind == 0 ? sector_qp_prepare_kernel<true> : sector_qp_prepare_kernel<false>, grid, dim3(256), 0, (hipStream_t)s,
+                  target, no, nv, k_int, orb_of, bx, b_of, L, Tc, Vv, Vo, VvR, VoR, outside, U, W, d2);
+}
+
+void sector_ipea_pack(int k, const double* const* r2, int64_t npos, const int64_t* ph, const int64_t* partner, const int64_t* pair,
+                      double* XR, double* XX, double* XP, stream_t s) {
+    qp_check("sector_ipea_pack", k, npos);
+    if (!r2 || !ph || !partner || !pair || !XR || !XX || !XP) throw std::runtime_error("sector_ipea_pack: null argument");
+    QpIn in{};
+    for (int z = 0; z < k; ++z) {
+        if (!r2[z]) throw std::runtime_error("sector_ipea_pack: null vector");
+        in.r2[z] = r2[z];
+    }
+    launch_kernel(sector_qp_pack_kernel, dim3((unsigned)((npos + 255) / 256), (unsigned)k), dim3(256), 0, (hipStream_t)s, in, k,
+                  (long)npos, reinterpret_cast<const long*>(ph), reinterpret_cast<const long*>(partner),
+                  reinterpret_cast<const long*>(pair), XR, XX, XP);
+}
+
+void sector_ipea_assemble(int k, const double* const* r1, const double* const* r2, double* const* s1, double* const* s2,
+                          int64_t npos, const int64_t* ph, const int64_t* ph_partner, const int64_t* pair, const double* d2,
+                          const double* U, const double* W, double d1, const double* G1, const double* G2, const double* H,
+                          stream_t s) {
+    qp_check("sector_ipea_assemble", k, npos);
+    if (!r1 || !r2 || !s1 || !s2 || !ph || !ph_partner || !pair || !d2 || !U || !W || !G1 || !G2 || !H)
+        throw std::runtime_error("sector_ipea_assemble: null argument");
+    QpIn in{};
+    QpOut out{};
+    for (int z = 0; z < k; ++z) {
+        if (!r1[z] || !r2[z] || !s1[z] || !s2[z]) throw std::runtime_error("sector_ipea_assemble: null vector");
+        in.r1[z] = r1[z];
+        in.r2[z] = r2[z];
+        out.s1[z] = s1[z];
+        out.s2[z] = s2[z];
+    }
+    launch_kernel(sector_qp_assemble_kernel, dim3((unsigned)((npos + 255) / 256 + 1), (unsigned)k), dim3(256), 0, (hipStream_t)s, in,
+                  out, k, (long)npos, reinterpret_cast<const long*>(ph), reinterpret_cast<const long*>(ph_partner),
+                  reinterpret_cast<const long*>(pair), d2, U, W, d1, G1, G2, H);
 }
 
 }  // namespace dev

@@ -424,6 +424,39 @@ class UEG:
             print_logging_info("{:.3f} s spent on ".format(time.time() - start_time) + __name__, level=1)
             return tints
 
+    def eval_2b_ladder(self, tables, targets, correlator=None, is_rpa_approx=False, is_only_2b=False, is_effect_2b=False, ctx=None):
+        """The V_abcd blocks that the particle ladder of the sector EA-EOM-CCD reads outside the stored pair sectors, as
+        ``SectorLadderIntegrals`` (pymes_amd.solver.ueg_eom): per virtual target p (an index over all orbitals) the
+        blocks at the pair momenta k_p + k_j that are no sum of two occupied momenta (``QuasiparticleTables.extra_pqrs``).
+        ``tables``: the ``SectorTables`` (or ``TriplesTables``) of this basis; modes, correlators and ``ctx`` as
+        ``eval_2b_sectors``.  The lists are evaluated in chunks of SECTOR_CHUNK elements by ``pymes_ueg_eval_2b_list``."""
+        from pymes_amd.solver.sectors import TriplesTables
+        from pymes_amd.solver.ueg_cc import upload_raw
+        from pymes_amd.solver.ueg_eom import SectorLadderIntegrals
+        start_time = time.time()
+        if self.basis_fns is None:
+            raise ValueError("Basis functions not initialized!")
+        ttab = tables if isinstance(tables, TriplesTables) else TriplesTables(tables)
+        flags = dict(is_rpa_approx=is_rpa_approx, is_only_2b=is_only_2b, is_effect_2b=is_effect_2b)
+        with self._sector_frame("eval_2b_ladder", ttab.tables, correlator, flags, ctx) as (ctx, own, eval_list):
+            lad = SectorLadderIntegrals(ctx, ttab, targets)
+            try:
+                for p, qt in lad.qtabs.items():
+                    for j in qt.extra_columns():                                # one block at a time: the lists stay small
+                        pqrs, off = qt.extra_pqrs(j), int(qt.extra_off[j])
+                        for e0 in range(0, len(pqrs), self.SECTOR_CHUNK):
+                            e1 = min(e0 + self.SECTOR_CHUNK, len(pqrs))
+                            lst = upload_raw(ctx, pqrs[e0:e1])
+                            try:
+                                eval_list(ctx, lst.ptr, e1 - e0, lad.arenas[p].ptr + 8 * (off + e0))
+                            finally:
+                                lst.free()
+            except BaseException:
+                lad.close()
+                raise
+            print_logging_info("{:.3f} s spent on ".format(time.time() - start_time) + __name__, level=1)
+            return lad
+
     # ---- host mirrors of the per-element helpers (ueg.py:518-596) ----------------------------------
     def _occ_kp(self):
         return np.array([self.basis_fns[i * 2].kp for i in range(self.n_ele // 2)])

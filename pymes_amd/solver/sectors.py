@@ -325,6 +325,181 @@ class TriplesTables:
         return np.append(T, 0.0)[self.implied_map]
 
 
+class QuasiparticleTables:
+    """The tables of one momentum block of the sector IP- / EA-EOM-CCD operator, from a `TriplesTables`.  Host side,
+    numpy only.
+
+    H-bar conserves the momentum, so the operator is block diagonal in the momentum of the removed (IP: -k_p, `target` p
+    occupied) or added (EA: +k_p, p virtual, counted over all n) electron.  A block is the singles element r1[p] and the doubles
+    with their implied index left out:
+
+      IP   R[i,j] = r2[i, j, b*], shape [o,o], b* the virtual with k_i + k_j - k_p
+      EA   R[a,j] = r2[a, b*, j], shape [v,o], b* the virtual with k_p + k_j - k_a
+
+    A position (x,y) whose implied orbital does not exist is not part of the space (`b_of` = -1 there, every map below too).
+    With `count` = dim - 1 positions inside:
+
+      b_of       b* counted from the first virtual (int32)
+      partner    the position of the exchanged element: IP (j,i), EA (b*,j)   (r2[j,i,b] resp. r2[b,a,j]; an involution)
+      ph         position -> [0, count): row x of R is a vector over PH_q, q = k_x - k_p (IP) / k_p - k_x (EA), its element
+                 (b*, y); the rows follow each other, each in the order of PH_q
+      ph_partner ph[partner]
+      pair       position -> [0, count): IP the element (i,j) of OO_P, the pair sectors P with a b* one after the other; EA the
+                 element (a,b*) of VV_P, P = k_p + k_j, column after column of R
+
+    All four maps are bijections of the space.  `tasks(k)` writes the task tables of the products of one apply for k stacked
+    vectors, every operand in the views above with the vector index running fastest ([count, k])."""
+
+    KINDS = ("ip", "ea")
+    # the preconditioner's diagonal at a position outside the space: far below every eigenvalue, so that w - d + shift of the
+    # Davidson correction is positive there and (s - w r) / (w - d + shift) = +0.0 / 1e30 stays an exact +0.0
+    OUTSIDE = -1.0e30
+
+    def __init__(self, ttab, kind, target):
+        if not isinstance(ttab, TriplesTables):
+            raise TypeError("QuasiparticleTables: a TriplesTables is needed")
+        if kind not in self.KINDS:
+            raise ValueError("QuasiparticleTables: kind must be 'ip' or 'ea'")
+        tab = ttab.tables
+        no, nv, n, k = tab.no, tab.nv, tab.n, tab.k_int
+        p = int(target)
+        if kind == "ip" and not 0 <= p < no:
+            raise ValueError("QuasiparticleTables: the IP target %d is not an occupied orbital (0 <= p < %d)" % (p, no))
+        if kind == "ea" and not no <= p < n:
+            raise ValueError("QuasiparticleTables: the EA target %d is not a virtual orbital (%d <= p < %d)" % (p, no, n))
+        self.ttab, self.tables, self.kind, self.target = ttab, tab, kind, p
+        nx = no if kind == "ip" else nv
+        self.shape, self.npos = (nx, no), nx * no
+        x, y = np.repeat(np.arange(nx), no), np.tile(np.arange(no), nx)
+        orb = ttab.lookup(k[x] + k[y] - k[p] if kind == "ip" else k[p] + k[y] - k[no + x])
+        b = np.where(orb >= no, orb - no, -1)
+        inside = b >= 0
+        self.b_of, self.inside, self.count = b.astype(np.int32), inside, int(inside.sum())
+        self.dim = self.count + 1
+        pos = np.flatnonzero(inside)
+        xi, yi, bi = x[pos], y[pos], b[pos]
+        self.partner = np.full(self.npos, -1, dtype=np.int64)
+        self.partner[pos] = yi * no + xi if kind == "ip" else bi * no + yi
+        # rows of R as vectors over PH_q: the element (b*, y) of the sector it lies in
+        g = tab.ph_row[bi * no + yi]
+        sec = np.searchsorted(tab.ph_off, g, side="right") - 1
+        self.row_sec = np.full(nx, -1, dtype=np.int64)
+        self.row_sec[xi] = sec
+        if not np.array_equal(self.row_sec[xi], sec):
+            raise AssertionError("QuasiparticleTables: a row of R spans two ph sectors")
+        self.row_len = np.where(self.row_sec >= 0, tab.n_ph[np.maximum(self.row_sec, 0)], 0)
+        self.row_off = np.concatenate(([0], np.cumsum(self.row_len))).astype(np.int64)
+        self.ph = np.full(self.npos, -1, dtype=np.int64)
+        self.ph[pos] = self.row_off[xi] + g - tab.ph_off[sec]
+        self.ph_partner = np.full(self.npos, -1, dtype=np.int64)
+        self.ph_partner[pos] = self.ph[self.partner[pos]]
+        # the pair view: OO_P of the sectors with a b* (IP), VV_P of P = k_p + k_j column by column (EA)
+        self.pair = np.full(self.npos, -1, dtype=np.int64)
+        if kind == "ip":
+            sec = tab.oo_sec[pos]                                   # (position i no + j is the pair index of oo_sec)
+            self.pair_sec = np.unique(sec)
+            self.pair_len = tab.n_oo[self.pair_sec]
+            self.pair_off = np.concatenate(([0], np.cumsum(self.pair_len))).astype(np.int64)
+            self.pair[pos] = self.pair_off[np.searchsorted(self.pair_sec, sec)] + tab.oo_pos[pos]
+        else:
+            # one block per column j, its virtual pairs (a, b*) in ascending a: the order of VV_P where P is a pp sector.  A
+            # pair momentum k_p + k_j that is no sum of two occupied momenta has no pp sector (no T, no V_klcd, no stored
+            # V_abcd there): its ladder block is the `extra` family, `extra_pqrs` lists it.
+            order = np.lexsort((xi, yi))
+            self.pair[pos[order]] = np.arange(self.count)
+            self.pair_len = np.bincount(yi, minlength=no).astype(np.int64)
+            self.pair_off = np.concatenate(([0], np.cumsum(self.pair_len))).astype(np.int64)
+            self.pair_a, self.pair_b = xi[order], bi[order]
+            ab = xi * nv + bi
+            sec = tab.vv_sec[ab]
+            self.pair_sec = np.full(no, -1, dtype=np.int64)
+            self.pair_sec[yi] = sec
+            stored = sec >= 0
+            if not np.array_equal(self.pair_sec[yi], sec) or \
+                    not np.array_equal(self.pair[pos[stored]], self.pair_off[yi[stored]] + tab.vv_pos[ab[stored]]) or \
+                    not np.array_equal(tab.n_vv[sec[stored]], self.pair_len[yi[stored]]):
+                raise AssertionError("QuasiparticleTables: a column of R is not the row list of its pp sector")
+            self.mid_len = np.where(self.pair_sec >= 0, tab.n_oo[np.maximum(self.pair_sec, 0)], 0)
+            self.mid_off = np.concatenate(([0], np.cumsum(self.mid_len))).astype(np.int64)
+            self.extra_len = np.where(self.pair_sec < 0, self.pair_len, 0)
+            self.extra_off = np.concatenate(([0], np.cumsum(self.extra_len ** 2))).astype(np.int64)
+        self.check()
+
+    @property
+    def extra_size(self):
+        """Elements of the `extra` ladder family (EA): V_abcd at the pair momenta k_p + k_j that are no pp sector."""
+        return int(self.extra_off[-1]) if self.kind == "ea" else 0
+
+    def extra_columns(self):
+        """The columns j of an EA block whose pair momentum k_p + k_j is no pp sector (and that are not empty)."""
+        return np.flatnonzero(self.extra_len) if self.kind == "ea" else np.zeros(0, dtype=np.int64)
+
+    def extra_pqrs(self, column=None):
+        """(p,q,r,s) int32 [count, 4] of the `extra` ladder family: per column j without a pp sector the block V[a,b,c,d],
+        rows (a,b) and columns (c,d) the column's pairs, row-major, from element `extra_off[j]` on.  `column`: that block
+        alone; None: all of them, one after the other."""
+        out = [np.zeros((0, 4), dtype=np.int32)]
+        for j in (self.extra_columns() if column is None else [int(column)]):
+            lo, hi = self.pair_off[j], self.pair_off[j + 1]
+            a, b = (self.pair_a[lo:hi] + self.tables.no).astype(np.int32), (self.pair_b[lo:hi] + self.tables.no).astype(np.int32)
+            m = hi - lo
+            out.append(np.stack([np.repeat(a, m), np.repeat(b, m), np.tile(a, m), np.tile(b, m)], axis=1))
+        return np.concatenate(out)
+
+    def check(self):
+        """Every map lies in range and is a bijection of the space onto [0, count) (the kernels trust them)."""
+        for name in ("ph", "ph_partner", "pair"):
+            m = getattr(self, name)
+            if (m[~self.inside] != -1).any() or not np.array_equal(np.sort(m[self.inside]), np.arange(self.count)):
+                raise AssertionError("QuasiparticleTables: the map '%s' is no bijection of the space" % name)
+        q = self.partner[self.inside]
+        if (self.partner[~self.inside] != -1).any() or not self.inside[q].all() \
+                or not np.array_equal(self.partner[q], np.flatnonzero(self.inside)):
+            raise AssertionError("QuasiparticleTables: the exchange partner is no involution of the space")
+        if int(self.row_off[-1]) != self.count or int(self.pair_off[-1]) != self.count:
+            raise AssertionError("QuasiparticleTables: a view does not hold the space")
+
+    def tasks(self, k):
+        """name -> (task table, lengths of A, B, C) of the products of one apply of k stacked vectors:
+
+          ring   G^x = S^q(x) X^x per row x, S a square [(a,i),(d,l)] of ph sector q(x) (PA, PB, MDU), X and G in the ph view;
+                 ring_add the same with beta = 1
+          IP  hole    H^P = (I^P)^T R^P for the pair sectors with a b*
+          EA  ladder  H^j = V_abcd^P R^j, P = k_p + k_j;  quad: M^j = V_klcd^P R^j;  quad_back: H^j += T^P M^j"""
+        tab, k = self.tables, int(k)
+        if k < 1:
+            raise ValueError("QuasiparticleTables.tasks: at least one vector is needed")
+        total, nsq = self.count * k, int(tab.offsets("ph", "ph")[-1])
+        rows = np.flatnonzero(self.row_sec >= 0)
+        rs, rl, ro = self.row_sec[rows], self.row_len[rows], self.row_off[rows] * k
+        sq = tab.offsets("ph", "ph")[rs]
+        out = {"ring": (make_tasks(rl, k, rl, sq, ro, ro, rl, k, k), nsq, total, total),
+               "ring_add": (make_tasks(rl, k, rl, sq, ro, ro, rl, k, k, beta=1.0), nsq, total, total)}
+        if self.kind == "ip":
+            ps, pl, po = self.pair_sec, self.pair_len, self.pair_off[:-1] * k
+            out["hole"] = (make_tasks(pl, k, pl, tab.offsets("oo", "oo")[ps], po, po, pl, k, k, trans_a=True),
+                           int(tab.offsets("oo", "oo")[-1]), total, total)
+        else:
+            cols = np.flatnonzero(self.pair_sec >= 0)
+            ps, pl, po = self.pair_sec[cols], self.pair_len[cols], self.pair_off[cols] * k
+            ml, mo, mid = self.mid_len[cols], self.mid_off[cols] * k, int(self.mid_off[-1]) * k
+            out["ladder"] = (make_tasks(pl, k, pl, tab.offsets("vv", "vv")[ps], po, po, pl, k, k),
+                             int(tab.offsets("vv", "vv")[-1]), total, total)
+            out["quad"] = (make_tasks(ml, k, pl, tab.offsets("oo", "vv")[ps], po, mo, pl, k, k),
+                           int(tab.offsets("oo", "vv")[-1]), total, mid)
+            out["quad_back"] = (make_tasks(pl, k, ml, tab.pp_off[ps], mo, po, ml, k, k, beta=1.0), tab.nnz, mid, total)
+            cols = np.flatnonzero(self.extra_len)
+            pl, po = self.pair_len[cols], self.pair_off[cols] * k
+            out["ladder_extra"] = (make_tasks(pl, k, pl, self.extra_off[cols], po, po, pl, k, k), self.extra_size, total, total)
+        return out
+
+
+def square_transpose(tables):
+    """The gather map that transposes every block of a ("ph", "ph") family: out[(r,c) of sector q] = in[(c,r) of sector q]."""
+    sec, lr, lc = _expand(tables.n_ph, tables.n_ph, 0, len(tables.q_keys))
+    return tables.offsets("ph", "ph")[sec] + lc * tables.n_ph[sec] + lr
+
+
 class TransferBins:
     """The bins of the momentum transfer q = k_r - k_p of an element (p,q,r,s), for the transfer sums and the structure
     factor of the sector densities, from a `SectorTables`.  Host side, numpy only.

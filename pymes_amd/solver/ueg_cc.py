@@ -30,7 +30,17 @@ from pymes_amd.solver import ccsd_t
 from pymes_amd.solver.sectors import BLOCKS, FOCK_LISTS, SectorTables, TriplesTables
 
 __all__ = ["SectorTables", "SectorIntegrals", "SectorAmplitudes", "SectorCCD", "TriplesTables", "SectorTriplesIntegrals",
-           "sector_triples_energy", "SectorLambda", "sector_lambda_triples_energy", "SectorDensity", "sector_density"]
+           "sector_triples_energy", "SectorLambda", "sector_lambda_triples_energy", "SectorDensity", "sector_density",
+           "SectorIPEAHoist", "SectorIPEASigma", "SectorIP_EOM_CCD", "SectorEA_EOM_CCD", "SectorLadderIntegrals"]
+_EOM_NAMES = ("SectorIPEAHoist", "SectorIPEASigma", "SectorIP_EOM_CCD", "SectorEA_EOM_CCD", "SectorLadderIntegrals")
+
+
+def __getattr__(name):
+    """The sector EOM (``ueg_eom``) is re-exported here; it imports this module, so it is bound on first use."""
+    if name in _EOM_NAMES:
+        from pymes_amd.solver import ueg_eom
+        return getattr(ueg_eom, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def upload_raw(ctx, host):
@@ -594,7 +604,8 @@ class SectorCCD:
     def _checks(self, eps, ints):
         return _check_solver_inputs("SectorCCD.solve", self.no, eps, ints, "CCD")
 
-    def solve(self, eps, ints, level_shift=0., amps=None, triples=None, lambda_triples=None, density=False, **kwargs):
+    def solve(self, eps, ints, level_shift=0., amps=None, triples=None, lambda_triples=None, density=False, quasiparticles=None,
+              **kwargs):
         """The loop of ``CCD.solve`` (ccd.py:24-162) on the compact vector.  eps: the orbital energies (or a diagonal Fock
         matrix); ints: ``SectorIntegrals``.  ``triples``: the ``SectorTriplesIntegrals`` of the same tables; the result then
         also holds "(t) e" (``sector_triples_energy`` of the final amplitudes) and "ccd(t) e".  ``lambda_triples``: the
@@ -603,7 +614,11 @@ class SectorCCD:
         1e-8) and the result also holds "lambda2", "lambda (t) e" (``sector_lambda_triples_energy``) and "ccd(t)_lambda e".
         ``density``: Lambda is solved (once; shared with ``lambda_triples``) and the result also holds "lambda2", "lambda
         residual", "density" (the ``SectorDensity``), "n(k)", "density e" (L(eps, ints): the correlation energy again, from
-        the densities), "structure factor" and "structure factor q" (DESIGN 8l)."""
+        the densities), "structure factor" and "structure factor q" (DESIGN 8l).  ``quasiparticles``: a dictionary
+        ``dict(tints=..., ip=[...], ea=[...], n_roots=1, ladders=...)`` -- ``tints`` the ``SectorTriplesIntegrals`` with both
+        sides (it may be the object passed as ``lambda_triples``), ``ip`` / ``ea`` the target orbitals, ``ladders`` the
+        ``SectorLadderIntegrals`` of the EA targets -- adds "ip e", "ea e" [targets, n_roots], "ip singles weight", "ea singles
+        weight" and, with both lists, "qp gap" (``ueg_eom.sector_quasiparticles``)."""
         algo_name = "ccd.solve"
         time_ccd = time.time()
         eps = self._checks(eps, ints)
@@ -611,6 +626,10 @@ class SectorCCD:
             _check_triples("SectorCCD.solve", ints, triples)
         if lambda_triples is not None:
             _check_triples("SectorCCD.solve", ints, lambda_triples, left=True)
+        if quasiparticles is not None:
+            if not isinstance(quasiparticles, dict) or "tints" not in quasiparticles:
+                raise ValueError("SectorCCD.solve: quasiparticles must be a dictionary with 'tints' and the target lists 'ip' / 'ea'")
+            _check_triples("SectorCCD.solve", ints, quasiparticles["tints"], left=True)
         tab, ctx, no = ints.tables, ints.ctx, self.no
         max_iter, delta_e = kwargs.get("max_iter", self.max_iter), kwargs.get("delta_e", self.delta_e)
         with quiet_collector():
@@ -685,6 +704,9 @@ class SectorCCD:
                 print_logging_info("Lambda residual norm = {:.3e} after {} iterations".format(lam["lambda residual"],
                                                                                                lam["iterations"]), level=1)
                 print_logging_info("Lambda-(T) correction = {:.12f}".format(out["lambda (t) e"]), level=1)
+            if quasiparticles is not None:
+                from pymes_amd.solver.ueg_eom import sector_quasiparticles
+                out.update(sector_quasiparticles(no, eps, ints, out["t2 amp"], **quasiparticles))
             return out
 
     @staticmethod
@@ -714,6 +736,26 @@ class SectorCCD:
         return 2.0 * d[0], -d[1], d[2], (d[3] if dt2 is not None else 0.0)
 
 
+def hoist_amplitudes(ints, T, quad):
+    """What depends on the amplitudes alone, shared by ``SectorLambda`` and the sector EOM (``ueg_eom.SectorIPEASigma``): the three
+    layouts of T, X = W1 Tt, the hole intermediate I^P = V_klij^P (+ V_klcd^P T^P) and, with ``quad`` (CCD; always for the EOM,
+    whose H-bar has the quadratic pieces also for DCD amplitudes), C - D and the squares Y = D Wx, Xc = C Wx."""
+    ctx, tab, dt = ints.ctx, ints.tables, ints.device_tables()
+    nnz, nsq = max(tab.nnz, 1), max(dt.nsq, 1)
+    h = {"T": T, "D": ctx.empty((nnz,)), "C": ctx.empty((nnz,)), "Tt": ctx.empty((nnz,)), "X": ctx.empty((nsq,))}
+    dt.layouts(T, h["D"], h["C"], h["Tt"])
+    dt.to_square.run(ints["w1"], h["Tt"], h["X"])                      # X^q = W1^q Tt^{-q}
+    h["hole"] = ints["klij"]
+    if quad:
+        h["hole"] = ctx.empty((max(ints.sizes["klij"], 1),)).copy_from(ints["klij"])
+        dt.hole_quad.run(ints["klcd"], T, h["hole"])                   # I^P = V_klij^P + V_klcd^P T^P
+        h["CmD"], h["Y"], h["Xc"] = ctx.empty((nnz,)), ctx.empty((nsq,)), ctx.empty((nsq,))
+        dt.layouts(T, CmD=h["CmD"])
+        dt.to_square.run(h["D"], ints["wx"], h["Y"])                   # Y^q = D^q Wx^{-q}
+        dt.to_square.run(h["C"], ints["wx"], h["Xc"])                  # Xc^q = C^q Wx^{-q}
+    return h
+
+
 class SectorLambda:
     """The Lambda equations of the momentum-sector CCD / DCD: J(T)^T lam + eta = 0, J = dR/dT of the compact
     residual of ``SectorCCD.residual`` on the exchange-symmetric vectors, eta = 2 ed - ex, plain inner product over the
@@ -734,23 +776,11 @@ class SectorLambda:
 
     _step = SectorCCD._step
 
-    # ---- what depends on T alone: its three layouts, hole(T), X = W1 Tt, Y = D Wx, Xc = C Wx -----------------------------
+    # ---- what depends on T alone (``hoist_amplitudes``), and eta ----------------------------------------------------------
     def hoist(self, ints, T):
-        ctx, tab, dt = ints.ctx, ints.tables, ints.device_tables()
-        nnz, nsq = max(tab.nnz, 1), max(dt.nsq, 1)
-        quad = not self.is_dcd
-        h = {"T": T, "D": ctx.empty((nnz,)), "C": ctx.empty((nnz,)), "Tt": ctx.empty((nnz,)), "X": ctx.empty((nsq,))}
-        dt.layouts(T, h["D"], h["C"], h["Tt"])
-        dt.to_square.run(ints["w1"], h["Tt"], h["X"])                      # X^q = W1^q Tt^{-q}
-        h["hole"] = ints["klij"]
-        if quad:
-            h["hole"] = ctx.empty((max(ints.sizes["klij"], 1),)).copy_from(ints["klij"])
-            dt.hole_quad.run(ints["klcd"], T, h["hole"])                   # I^P = V_klij^P + V_klcd^P T^P
-            h["CmD"], h["Y"], h["Xc"] = ctx.empty((nnz,)), ctx.empty((nsq,)), ctx.empty((nsq,))
-            dt.layouts(T, CmD=h["CmD"])
-            dt.to_square.run(h["D"], ints["wx"], h["Y"])                   # Y^q = D^q Wx^{-q}
-            dt.to_square.run(h["C"], ints["wx"], h["Xc"])                  # Xc^q = C^q Wx^{-q}
-        h["eta"] = ctx.empty((nnz,))
+        ctx, tab = ints.ctx, ints.tables
+        h = hoist_amplitudes(ints, T, not self.is_dcd)
+        h["eta"] = ctx.empty((max(tab.nnz, 1),))
         ctx.lincomb(h["eta"], [ints["ed"], ints["ex"]], [2.0, -1.0])
         h["zero"] = ctx.zeros((tab.n,))
         return h

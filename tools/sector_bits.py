@@ -13,10 +13,14 @@ quantity is not reproducible; two checkouts whose reproducible lines agree compu
                  and tests/test_gpu_sector_lambda.py: per-triple values and the sum at (14,2), (14,8), the twisted support, and
                  at (14,5) with a workspace of 1, 5 and all triples; Lambda-(T) with both sides equal ("lambda L=T": the (T) bits
                  if the two entries share their energy kernel)
+  ipea cases     the sector IP / EA-EOM-CCD at the solver cases, Coulomb and transcorrelated, the lowest and the
+                 highest admissible target of either kind: sigma of 3 seeded stacked vectors, the flat diagonal, and the roots,
+                 singles weights and residuals of a one-root solve of 6 passes.  Printed after the 292 lines of the other cases, and only by a
+                 checkout that has pymes_amd/solver/ueg_eom.py
 
     python3 tools/sector_bits.py [--out FILE]
-It uses the package and the test helpers of the checkout it lies in, and only names that older checkouts of the sector path
-have too: copy it into one to compare."""
+It uses the package and the test helpers of the checkout it lies in; the first 292 lines need only names that older checkouts
+of the sector path have too: copy it into one to compare."""
 import argparse
 import functools
 import hashlib
@@ -94,6 +98,37 @@ def kernel_lines(ctx, emit):
             emit(name, "lambda L=T sum", e)
 
 
+def ipea_lines(ctx, case, emit):
+    from pymes_amd.solver.sectors import TriplesTables
+    from pymes_amd.solver.ueg_eom import SectorEA_EOM_CCD, SectorIP_EOM_CCD, SectorIPEASigma
+    m = twisted_model() if case == "twist" else model(*case, k_cutoff=1.0)
+    tab = m.sector_tables()
+    tt = TriplesTables(tab)
+    kin = np.array([b.kinetic for b in m.basis_fns[::2]])
+    T = symmetric(tab, 11, 0.1)
+    for kind in ("coulomb", "tc"):
+        terms = [{}] if kind == "coulomb" else [dict(correlator=m.trunc, is_only_2b=True),
+                                                dict(correlator=m.trunc, is_effect_2b=True)]
+        total = lambda f, *a, **kw: functools.reduce(operator.add, [quiet(f, *a, ctx=ctx, **t, **kw) for t in terms])
+        ints, tints = total(m.eval_2b_sectors, tab), total(m.eval_2b_triples, tt, both_sides=True)
+        eps = ints.hf_orbital_energies(kin)
+        for op, cls, targets in (("ip", SectorIP_EOM_CCD, [0, tab.no - 1]), ("ea", SectorEA_EOM_CCD, [tab.no, tab.n - 1])):
+            ladders = total(m.eval_2b_ladder, tt, targets) if op == "ea" else None
+            sig = SectorIPEASigma(op, eps, ints, tints, T, ladders=ladders)
+            rng = np.random.default_rng(5)
+            for p in targets:
+                name, qt = "%s %s %s target %d" % (case, kind, op, p), sig.tables_of(p)
+                r1, R = rng.standard_normal(3), rng.standard_normal((3,) + qt.shape) * qt.inside.reshape(qt.shape)
+                s1, S = sig.get_sigma(p, r1, R)
+                emit(name, "sigma", np.concatenate([s1, S.ravel()]))
+                emit(name, "diagonals", sig.diagonals(p).get())
+            sig.close()
+            res = quiet(cls(tab.no, n_roots=1, max_iter=6).solve, eps, ints, tints, T,
+                        targets, ladders=ladders)
+            for key in (op + " e", "singles weight", "residuals"):
+                emit("%s %s %s" % (case, kind, op), key, res[key])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also append the lines to this file")
@@ -112,6 +147,9 @@ def main():
         kernel_lines(ctx, emit)
         for case in SOLVER_CASES:
             solver_lines(ctx, case, emit)
+        if os.path.exists(os.path.join(ROOT, "pymes_amd", "solver", "ueg_eom.py")):
+            for case in SOLVER_CASES:
+                ipea_lines(ctx, case, emit)
     finally:
         ctx.close()
 

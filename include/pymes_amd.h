@@ -736,6 +736,25 @@ int pymes_sector_ipea_correction(pymes_ctx* ctx, int n, const double* const* s_d
                                  const double* d_dev, double shift, double* const* q_dev, int64_t n1, int64_t off2, int64_t len,
                                  double* norms_host);
 
+/* One Arnoldi step on a device-resident basis (pymes_amd/solver/ueg_eom.py, SectorSpectralFunction).  The basis is one
+ * matrix whose rows lie `pitch` doubles apart (a multiple of 32, at least len) with len valid doubles each; what lies between
+ * len and pitch is neither read nor written.  On entry the rows 0..j are orthonormal and row j+1 holds w = H v_j; the call needs
+ * j + 2 rows.  hess_dev is row-major with rows ldh doubles apart, ldh >= j + 1, and j + 2 rows are written to.  On exit
+ *   hess[i ldh + j] = h_i + h'_i, i <= j, of two rounds of classical Gram-Schmidt (h = V w, w' = w - V^T h, h' = V w',
+ *                     w'' = w' - V^T h'),
+ *   hess[(j+1) ldh + j] = |w''|  and  row j+1 = w'' / |w''|,
+ * or, on breakdown (not |w''| > breakdown |w|), hess[(j+1) ldh + j] = 0.0 exactly, row j+1 = +0.0 everywhere and
+ * status_dev[0] = j + 1 if it held 0 (the caller zeroes it before the first step; the first breakdown stays).
+ * Nothing is read back and the host does not wait.  No atomics: every dot is a fixed tree whose shape depends on len alone --
+ * not on j, pitch, or the rows allocated --, so identical calls give identical bits.  ws_dev: *ws_doubles doubles of scratch;
+ * with ws_dev == NULL the call only writes the size that (len, j) need into *ws_doubles (it grows with j) and the other
+ * pointers may be NULL.  Refused by name: a null argument, j outside [0, PYMES_SECTOR_ARNOLDI_MAX), len < 1, pitch < len or no
+ * multiple of 32, ldh < j + 1, a breakdown threshold that is negative or not finite, a workspace that is too small, and a
+ * context that is recording a launch graph. */
+#define PYMES_SECTOR_ARNOLDI_MAX 512
+int pymes_sector_arnoldi_step(pymes_ctx* ctx, double* basis_dev, int64_t pitch, int64_t len, int j, double* hess_dev, int64_t ldh,
+                              double breakdown, double* ws_dev, int64_t* ws_doubles, int64_t* status_dev);
+
 /* ---- vector helpers for DIIS (pymes/mixer/diis.py:65-103) and norms ----------------- */
 /* out_host[p] = sum_i x[p][i]*y[p][i], npairs <= 16, deterministic reduction (synchronises) */
 int pymes_dots(pymes_ctx* ctx, int npairs, const double* const* x_dev, const double* const* y_dev, int64_t n,

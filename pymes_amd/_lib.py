@@ -174,6 +174,9 @@ SIGNATURES = {
                                    + [C.c_double] + [C.c_void_p] * 3),
     "pymes_sector_ipea_correction": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                                C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    # one Arnoldi step on a device-resident basis: CGS2 of row j+1, column j of the Hessenberg matrix, the breakdown flag
+    "pymes_sector_arnoldi_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                            C.c_double, C.c_void_p, c_i64_p, C.c_void_p]),
     "pymes_hf_fock_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pymes_fcidump_header": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pymes_fcidump_read_host": (C.c_int, [C.c_char_p, C.c_int, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1054,6 +1054,18 @@ int pymes_sector_ipea_correction(pymes_ctx* ctx, int n, const double* const* s, 
         pymes::davidson_correction(e, n, s, r, w_host, d, shift, q, n1, off2, len, norms_host);
     });
 }
+// ---- one Arnoldi step on a device-resident basis (kernels_sector.hip; pymes_amd/solver/ueg_eom.py) ---------------------
+int pymes_sector_arnoldi_step(pymes_ctx* ctx, double* basis, int64_t pitch, int64_t len, int j, double* hess, int64_t ldh,
+                              double breakdown, double* ws, int64_t* ws_doubles, int64_t* status) {
+    return guarded([&] {
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("sector_arnoldi_step while a launch graph is being recorded");
+        need(ws_doubles, "ws_doubles");
+        if (ws) { need(basis, "basis"); need(hess, "hess"); need(status, "status"); }
+        const int64_t wanted = dev::sector_arnoldi_step(basis, pitch, len, j, hess, ldh, breakdown, ws, *ws_doubles, status, e.stream);
+        if (!ws) *ws_doubles = wanted;
+    });
+}
 
 int pymes_dots(pymes_ctx* ctx, int npairs, const double* const* x, const double* const* y, int64_t n,
                double* out) {

@@ -583,5 +583,10 @@ void sector_ipea_assemble(int k, const double* const* r1, const double* const* r
                           int64_t npos, const int64_t* ph, const int64_t* ph_partner, const int64_t* pair, const double* d2,
                           const double* U, const double* W, double d1, const double* G1, const double* G2, const double* H,
                           stream_t s);
+// One Arnoldi step on a device-resident basis (include/pymes_amd.h, pymes_sector_arnoldi_step): two rounds of classical
+// Gram-Schmidt of row j+1 against the rows 0..j, column j of the Hessenberg matrix, the breakdown flag.  Returns the doubles of
+// workspace that (len, j) need; with ws == nullptr that is all it does.
+int64_t sector_arnoldi_step(double* basis, int64_t pitch, int64_t len, int j, double* hess, int64_t ldh, double breakdown,
+                            double* ws, int64_t ws_doubles, int64_t* status, stream_t s);
 
 }  // namespace dev

@@ -962,4 +962,8 @@ __attribute__((weak)) void sector_ipea_assemble(int, const double* const*, const
                                                 stream_t) {
     throw std::runtime_error("sector_ipea_assemble: not available in this backend");
 }
+__attribute__((weak)) int64_t sector_arnoldi_step(double*, int64_t, int64_t, int, double*, int64_t, double, double*, int64_t,
+                                                  int64_t*, stream_t) {
+    throw std::runtime_error("sector_arnoldi_step: not available in this backend");
+}
 }  // namespace dev

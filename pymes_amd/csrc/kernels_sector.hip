@@ -3,7 +3,8 @@
 // and of the momentum-blocked (T) on the same path: the W slab, the energy partials and their ordered sum;
 // and the two-slab instantiation of the energy kernel for the Lambda-(T) (what the two share: DESIGN 8m); and the
 // bin sums, the fused V_abcd transfer sums and the gamma sums of the sector densities; and the per-target
-// preparation, the operand packing and the assembly of the sector IP- / EA-EOM-CCD sigma.
+// preparation, the operand packing and the assembly of the sector IP- / EA-EOM-CCD sigma; and one Arnoldi step on a
+// device-resident basis for the sector spectral functions.
 // Included at the end of kernels.hip (one code object for the library), not compiled on its own.
 #include <hip/hip_runtime.h>
 
@@ -698,9 +699,241 @@ void qp_check(const char* who, int k, int64_t npos) {
     if (npos < 1 || (npos + 255) / 256 + 1 > 0x7fffffffL) throw std::runtime_error(std::string(who) + ": bad number of positions");
 }
 
+// ---- one Arnoldi step on a device-resident basis (include/pymes_amd.h, pymes_sector_arnoldi_step) ---------------------
+// Rows 0..j of the basis are orthonormal, row j+1 holds w = H v_j.  Two rounds of classical Gram-Schmidt, cut along the vector
+// into chunks of kArnChunkSmall or kArnChunkLarge doubles (by len alone), four launches, no host round trip:
+//   dots      p1[c][i] = <V_i, w> on chunk c (one wave per row), wn[c] = |w|^2 on chunk c
+//   update 1  h = sum_c p1[c][.]; w' = w - sum_i h_i V_i on chunk c (ascending i); p2[c][i] = <V_i, w'> on the same chunk, which
+//             the update has just pulled through the cache
+//   update 2  h' = sum_c p2[c][.]; w'' = w' - sum_i h'_i V_i on chunk c; pn[c] = |w''|^2 on chunk c; hess[i,j] = h_i + h'_i
+//   scale     |w''|^2 = sum_c pn[c], |w|^2 = sum_c wn[c]; row j+1 = w'' / |w''|, or +0.0 on breakdown; hess[j+1,j]; status
+// Every dot is a fixed tree: a lane adds its elements of a chunk in ascending order, a butterfly over the 64 lanes, and the
+// chunks one after the other in ascending order -- nothing depends on j, pitch, the grid or the rows allocated.  No atomics.
+// Nothing at or beyond len is read or written.
+constexpr int kArnMax = PYMES_SECTOR_ARNOLDI_MAX;
+constexpr int kArnChunkSmall = 256, kArnChunkLarge = 1024;
+constexpr long kArnLargeFrom = 1L << 18;     // len from which the large chunk is taken: below it the small one gives more
+                                             // workgroups (a chunk is one workgroup of the update kernels), beyond it the
+                                             // partial sums every workgroup adds up again would outgrow its own chunk
+constexpr int kArnRowsPerBlock = 16;         // rows of one block of the dots kernel: 4 waves x 4 rows
+static_assert(kArnMax == 512, "hs[] below and the header agree on the cap");
+
+__device__ __forceinline__ double arn_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// <row, w> on one chunk for one wave: lane l takes the elements l, l + 64, ... (nvalid of them exist), w in registers
+template <int KPL>
+__device__ __forceinline__ double arn_wave_dot(const double* __restrict__ row, const double (&w)[KPL], long nvalid, int lane) {
+    double v[KPL];
+#pragma unroll
+    for (int k = 0; k < KPL; ++k) v[k] = (lane + 64 * k < nvalid) ? row[lane + 64 * k] : 0.0;
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < KPL; ++k) acc = fma(v[k], w[k], acc);
+    return arn_wave_sum(acc);
+}
+// hs[i] = sum_c p[c R + i], c ascending, for the rows 0..j
+__device__ __forceinline__ void arn_reduce_rows(const double* __restrict__ p, int nch, int R, int j, double* hs, int tid) {
+    for (int i = tid; i <= j; i += 256) {
+        double s = 0.0;
+        for (int c = 0; c < nch; ++c) s += p[(long)c * R + i];
+        hs[i] = s;
+    }
+}
+// sum_c x[c]: thread t over c = t, t + 256, ... ascending, then a fixed tree; every thread gets the sum
+__device__ __forceinline__ double arn_block_total(const double* __restrict__ x, int nch, double* red, int tid) {
+    double s = 0.0;
+    for (int c = tid; c < nch; c += 256) s += x[c];
+    __syncthreads();
+    red[tid] = s;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) red[tid] += red[tid + st];
+        __syncthreads();
+    }
+    return red[0];
+}
+// acc[k] = w[e_k] - sum_i hs[i] V_i[e_k], i ascending, for the thread's elements e_k = c0 + tid + 256 k below len (0.0 beyond)
+template <int EPT>
+__device__ __forceinline__ void arn_update(const double* __restrict__ basis, long pitch, long len, int j, long c0,
+                                           const double* hs, double (&acc)[EPT], int tid) {
+    // (an element beyond len reads the last valid one instead, so the row loop has no branch, and is set to 0.0 at the end;
+    // 16 / EPT rows are unrolled: the loads of 16 elements are in flight before the first fma needs one)
+    long at[EPT];
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+        const long e = c0 + tid + 256 * k;
+        at[k] = e < len ? e : len - 1;
+        acc[k] = (basis + (long)(j + 1) * pitch)[at[k]];
+    }
+#pragma unroll 16 / EPT
+    for (int i = 0; i <= j; ++i) {
+        const double* __restrict__ row = basis + (long)i * pitch;
+        const double h = hs[i];
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) acc[k] = fma(-h, row[at[k]], acc[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < EPT; ++k)
+        if (c0 + tid + 256 * k >= len) acc[k] = 0.0;
+}
+
+template <int KPL>
+__global__ void __launch_bounds__(256) sector_arnoldi_dots_kernel(const double* __restrict__ basis, long pitch, long len, int j,
+                                                                  int R, double* __restrict__ p1, double* __restrict__ wn) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = blockIdx.x;
+    const long c0 = (long)c * (64 * KPL), nvalid = len - c0;
+    const double* __restrict__ wrow = basis + (long)(j + 1) * pitch + c0;
+    double w[KPL];
+#pragma unroll
+    for (int k = 0; k < KPL; ++k) w[k] = (lane + 64 * k < nvalid) ? wrow[lane + 64 * k] : 0.0;
+    if (blockIdx.y == 0 && wave == 0) {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < KPL; ++k) acc = fma(w[k], w[k], acc);
+        acc = arn_wave_sum(acc);
+        if (lane == 0) wn[c] = acc;
+    }
+#pragma unroll
+    for (int r = 0; r < kArnRowsPerBlock / 4; ++r) {
+        const int i = blockIdx.y * kArnRowsPerBlock + wave + 4 * r;          // (a row past j reads row j and writes nothing: no
+        const double d = arn_wave_dot<KPL>(basis + (long)(i <= j ? i : j) * pitch + c0, w, nvalid, lane);     // branch between rows)
+        if (lane == 0 && i <= j) p1[(long)c * R + i] = d;
+    }
+}
+
+template <int EPT>
+__global__ void __launch_bounds__(256) sector_arnoldi_first_kernel(double* __restrict__ basis, long pitch, long len, int j, int nch,
+                                                                   int R, const double* __restrict__ p1, double* __restrict__ p2,
+                                                                   double* __restrict__ h1) {
+    __shared__ double hs[kArnMax];
+    __shared__ double wl[256 * EPT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = blockIdx.x;
+    const long c0 = (long)c * (256 * EPT);
+    arn_reduce_rows(p1, nch, R, j, hs, tid);
+    __syncthreads();
+    if (c == 0)
+        for (int i = tid; i <= j; i += 256) h1[i] = hs[i];
+    double acc[EPT];
+    arn_update<EPT>(basis, pitch, len, j, c0, hs, acc, tid);
+    double* __restrict__ wrow = basis + (long)(j + 1) * pitch;
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+        const long e = c0 + tid + 256 * k;
+        wl[tid + 256 * k] = acc[k];
+        if (e < len) wrow[e] = acc[k];
+    }
+    __syncthreads();
+    constexpr int KPL = 4 * EPT;
+    double w[KPL];
+#pragma unroll
+    for (int k = 0; k < KPL; ++k) w[k] = wl[lane + 64 * k];
+    for (int i = wave; i <= j; i += 4) {
+        const double d = arn_wave_dot<KPL>(basis + (long)i * pitch + c0, w, len - c0, lane);
+        if (lane == 0) p2[(long)c * R + i] = d;
+    }
+}
+
+template <int EPT>
+__global__ void __launch_bounds__(256) sector_arnoldi_second_kernel(double* __restrict__ basis, long pitch, long len, int j, int nch,
+                                                                    int R, const double* __restrict__ p2,
+                                                                    const double* __restrict__ h1, double* __restrict__ pn,
+                                                                    double* __restrict__ hess, long ldh) {
+    __shared__ double hs[kArnMax];
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x;
+    const long c0 = (long)c * (256 * EPT);
+    arn_reduce_rows(p2, nch, R, j, hs, tid);
+    __syncthreads();
+    if (c == 0)
+        for (int i = tid; i <= j; i += 256) hess[(long)i * ldh + j] = h1[i] + hs[i];
+    double acc[EPT];
+    arn_update<EPT>(basis, pitch, len, j, c0, hs, acc, tid);
+    double* __restrict__ wrow = basis + (long)(j + 1) * pitch;
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+        const long e = c0 + tid + 256 * k;
+        if (e < len) wrow[e] = acc[k];
+        s = fma(acc[k], acc[k], s);
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) red[tid] += red[tid + st];
+        __syncthreads();
+    }
+    if (tid == 0) pn[c] = red[0];
+}
+
+template <int EPT>
+__global__ void __launch_bounds__(256) sector_arnoldi_scale_kernel(double* __restrict__ basis, long pitch, long len, int j, int nch,
+                                                                   const double* __restrict__ wn, const double* __restrict__ pn,
+                                                                   double breakdown, double* __restrict__ hess, long ldh,
+                                                                   long* __restrict__ status) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const long c0 = (long)blockIdx.x * (256 * EPT);
+    const double nrm = sqrt(arn_block_total(pn, nch, red, tid));
+    const double wnorm = sqrt(arn_block_total(wn, nch, red, tid));
+    const bool broke = !(nrm > breakdown * wnorm);
+    double* __restrict__ wrow = basis + (long)(j + 1) * pitch;
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+        const long e = c0 + tid + 256 * k;
+        if (e < len) wrow[e] = broke ? 0.0 : wrow[e] / nrm;
+    }
+    if (blockIdx.x == 0 && tid == 0) {
+        hess[(long)(j + 1) * ldh + j] = broke ? 0.0 : nrm;
+        if (broke && status[0] == 0) status[0] = j + 1;
+    }
+}
+
+template <int EPT>
+void arnoldi_launch(double* basis, long pitch, long len, int j, int nch, double* hess, long ldh, double breakdown, double* ws,
+                    long* status, hipStream_t st) {
+    const int R = j + 1;
+    double *p1 = ws, *p2 = p1 + (long)nch * R, *wn = p2 + (long)nch * R, *pn = wn + nch, *h1 = pn + nch;
+    const dim3 chunks((unsigned)nch), block(256);
+    launch_kernel(sector_arnoldi_dots_kernel<4 * EPT>, dim3((unsigned)nch, (unsigned)((R + kArnRowsPerBlock - 1) / kArnRowsPerBlock)),
+                  block, 0, st, (const double*)basis, pitch, len, j, R, p1, wn);
+    launch_kernel(sector_arnoldi_first_kernel<EPT>, chunks, block, 0, st, basis, pitch, len, j, nch, R, (const double*)p1, p2, h1);
+    launch_kernel(sector_arnoldi_second_kernel<EPT>, chunks, block, 0, st, basis, pitch, len, j, nch, R, (const double*)p2,
+                  (const double*)h1, pn, hess, ldh);
+    launch_kernel(sector_arnoldi_scale_kernel<EPT>, chunks, block, 0, st, basis, pitch, len, j, nch, (const double*)wn,
+                  (const double*)pn, breakdown, hess, ldh, status);
+}
+
 }  // namespace
 
 namespace dev {
+
+int64_t sector_arnoldi_step(double* basis, int64_t pitch, int64_t len, int j, double* hess, int64_t ldh, double breakdown,
+                            double* ws, int64_t ws_doubles, int64_t* status, stream_t s) {
+    const std::string who = "sector_arnoldi_step";
+    if (len < 1 || len > (1L << 40)) throw std::runtime_error(who + ": bad vector length");
+    if (j < 0 || j >= kArnMax) throw std::runtime_error(who + ": j must lie in [0, " + std::to_string(kArnMax) + ")");
+    const long chunk = len < kArnLargeFrom ? kArnChunkSmall : kArnChunkLarge;
+    const long nch = (len + chunk - 1) / chunk;
+    const int64_t need = 2 * nch * (j + 1) + 2 * nch + (j + 1);
+    if (!ws) return need;                                   // the query form: nothing is launched
+    if (!basis || !hess || !status) throw std::runtime_error(who + ": null argument");
+    if (pitch < len || pitch % 32) throw std::runtime_error(who + ": pitch must be a multiple of 32 doubles and at least len");
+    if (ldh < j + 1) throw std::runtime_error(who + ": ldh is too small for column j");
+    if (!(breakdown >= 0.0) || !std::isfinite(breakdown)) throw std::runtime_error(who + ": the breakdown threshold must be finite and not negative");
+    if (ws_doubles < need)
+        throw std::runtime_error(who + ": the workspace is too small (" + std::to_string(need) + " doubles are needed)");
+    if (chunk == kArnChunkSmall)
+        arnoldi_launch<1>(basis, pitch, len, j, (int)nch, hess, ldh, breakdown, ws, reinterpret_cast<long*>(status), (hipStream_t)s);
+    else
+        arnoldi_launch<4>(basis, pitch, len, j, (int)nch, hess, ldh, breakdown, ws, reinterpret_cast<long*>(status), (hipStream_t)s);
+    return need;
+}
 
 void sector_gemm(const pymes_sector_task* tasks_dev, int ntask, int64_t ntiles, const double* A, const double* B, double* C,
                  stream_t s) {

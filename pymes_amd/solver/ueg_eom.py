@@ -31,7 +31,7 @@ from pymes_amd.solver.ueg_cc import (SectorIntegrals, Tasks, _check_solver_input
                                      _symmetric_compact, gather, hoist_amplitudes, upload_i32, upload_map, view)
 
 __all__ = ["SectorLadderIntegrals", "SectorIPEAHoist", "SectorIPEASigma", "SectorIP_EOM_CCD", "SectorEA_EOM_CCD",
-           "sector_quasiparticles"]
+           "sector_quasiparticles", "SectorSpectralFunction", "KrylovBasis", "sector_spectral"]
 
 MAX_STACK = 32          # vectors per launch of the pack and assembly kernels (kQpMax of kernels_sector.hip)
 
@@ -435,3 +435,251 @@ def sector_quasiparticles(no, eps, ints, amps, tints=None, ip=None, ea=None, n_r
     if "ip e" in out and "ea e" in out:
         out["qp gap"] = float(out["ip e"].min() + out["ea e"].min())
     return out
+
+
+# ---- spectral functions A(k, w) and pole strengths Z_k -----------------------------------------------------------------
+ARNOLDI_MAX = 512       # PYMES_SECTOR_ARNOLDI_MAX of include/pymes_amd.h: the most basis vectors pymes_sector_arnoldi_step takes
+_SIGN = {"ip": 1.0, "ea": -1.0}
+
+
+def arnoldi_workspace(ctx, length, j):
+    """The doubles of scratch that ``pymes_sector_arnoldi_step`` needs for vectors of ``length`` at step ``j`` (its query form)."""
+    size = C.c_int64(0)
+    ctx.lib.call("pymes_sector_arnoldi_step", ctx.handle, None, 0, int(length), int(j), None, 0, 0.0, None, C.byref(size), None)
+    return int(size.value)
+
+
+def arnoldi_step(ctx, basis, pitch, length, j, hess, ldh, breakdown, ws, status):
+    """One step of the device Arnoldi process (include/pymes_amd.h): CGS2 of row j+1 of ``basis`` against the rows 0..j, column j
+    of ``hess``; nothing is read back.  ``status``: a device array of one 8-byte integer, zero before the first step."""
+    ctx.lib.call("pymes_sector_arnoldi_step", ctx.handle, C.c_void_p(basis.ptr), int(pitch), int(length), int(j),
+                 C.c_void_p(hess.ptr), int(ldh), float(breakdown), C.c_void_p(ws.ptr), C.byref(C.c_int64(ws.size)),
+                 C.c_void_p(status.ptr))
+
+
+def shifted_hessenberg(Hbar, kind, z, chunk=64):
+    """(y_1(z), y_k(z)) of (z + s H_k) y = e_1 for the shifts z, s = +1 (IP) / -1 (EA), from the [k+1, k] Hessenberg matrix."""
+    k, z = Hbar.shape[1], np.atleast_1d(z).astype(np.complex128)
+    e1 = np.zeros((k, 1), dtype=np.complex128)
+    e1[0] = 1.0
+    first, last = np.zeros(len(z), dtype=np.complex128), np.zeros(len(z), dtype=np.complex128)
+    sH, eye = _SIGN[kind] * Hbar[:k], np.eye(k)
+    for lo in range(0, len(z), chunk):
+        zz = z[lo:lo + chunk]
+        y = np.linalg.solve(zz[:, None, None] * eye[None] + sH[None], e1[None])[:, :, 0]
+        first[lo:lo + chunk], last[lo:lo + chunk] = y[:, 0], y[:, -1]
+    return first, last
+
+
+class KrylovBasis:
+    """What ``SectorSpectralFunction.solve(..., keep_basis=True)`` keeps per target: the basis on the device and its Hessenberg
+    matrix.  ``close()`` frees the device arrays."""
+
+    def __init__(self, ctx):
+        self.ctx, self._targets = ctx, {}
+
+    def _add(self, kind, target, layout, basis, pitch, Hbar):
+        self._targets[int(target)] = SimpleNamespace(kind=kind, layout=layout, basis=basis, pitch=pitch, Hbar=Hbar)
+
+    def hessenberg(self, target):
+        """The [k+1, k] Hessenberg matrix of the target (host); its last row holds h_{k+1,k} alone, 0.0 after a breakdown."""
+        return self._targets[int(target)].Hbar.copy()
+
+    def rows(self, target):
+        """The k+1 basis rows of the target as flat device vectors of its layout (views; the last one is zero after a breakdown)."""
+        t = self._targets[int(target)]
+        return [subspace.view(self.ctx, t.basis, i * t.pitch, (t.layout.nflat,)) for i in range(t.Hbar.shape[0])]
+
+    def solution(self, target, z):
+        """x(z) = V_k y(z), (z + s H_k) y = e_1, as two flat device vectors (real part, imaginary part) of the target's layout:
+        G(z) = N_p x_1(z)."""
+        t = self._targets[int(target)]
+        k, sH = t.Hbar.shape[1], _SIGN[t.kind] * t.Hbar[:t.Hbar.shape[1]]
+        e1 = np.zeros(k, dtype=np.complex128)
+        e1[0] = 1.0
+        y = np.linalg.solve(complex(z) * np.eye(k) + sH, e1)
+        out = [t.layout.empty(), t.layout.empty()]
+        self.ctx.lincomb_multi(out, self.rows(target)[:k], np.stack([y.real, y.imag], axis=1))
+        return tuple(out)
+
+    def close(self):
+        for t in self._targets.values():
+            t.basis.free()
+        self._targets = {}
+
+
+class SectorSpectralFunction:
+    """The diagonal one-particle Green's function of the electron gas on the sector path, its spectral function A(k, w) and the
+    pole strengths Z_k.  H-bar conserves momentum, t1 = lambda1 = 0 and no two orbitals share a momentum, so the Dyson
+    amplitudes of DESIGN 8f collapse to the singles element: for an occupied target p
+
+        G_pp(z) = N_p [(z + H_IP)^-1]_11,  N_p = n(k_p) / 2        (the hole part, poles at -w_k)
+
+    and for a virtual one G_pp(z) = N_p [(z - H_EA)^-1]_11, N_p = 1 - n(k_p) / 2 (the particle part), with H the momentum block that
+    ``SectorIPEASigma`` applies and n(k) from the ``SectorDensity``: the only place Lambda enters.  All frequencies share the
+    Krylov space K_m(H, e_1): one Arnoldi run per target (m real applies, each followed by ``pymes_sector_arnoldi_step`` on the
+    device, no host round trip per step), G from the m x m Hessenberg matrix alone, the residual of every shift h_{m+1,m} |y_m(z)|.
+    Only the majority part of a momentum is computed: the particle part of an occupied momentum (weight 1 - n(k)/2) and the hole
+    part of a virtual one are left out; "K norm" says how much weight the computed part holds.
+
+    max_dim: the most basis vectors per target (at most ``ARNOLDI_MAX``); r_epsilon: the run stops when the residual of every
+    shift lies below it; check_every: steps between two read-backs of the Hessenberg matrix; breakdown: the relative norm below
+    which a new direction counts as none (the space is invariant and the result exact)."""
+
+    def __init__(self, no, max_dim=256, r_epsilon=1.e-6, check_every=16, breakdown=1.e-10):
+        who = "SectorSpectralFunction"
+        if not 1 <= int(max_dim) <= ARNOLDI_MAX:
+            raise ValueError(who + ": max_dim must lie in [1, %d] (the cap of pymes_sector_arnoldi_step)" % ARNOLDI_MAX)
+        if int(check_every) < 1:
+            raise ValueError(who + ": check_every must be at least 1")
+        self.no, self.max_dim, self.r_epsilon = no, int(max_dim), float(r_epsilon)
+        self.check_every, self.breakdown = int(check_every), float(breakdown)
+
+    @staticmethod
+    def _occupations(who, ints, density):
+        """n(k) over all orbitals from a ``SectorDensity`` of the same tables and context, or from an array."""
+        tab = ints.tables
+        if hasattr(density, "momentum_distribution"):
+            if density.tables is not tab or density.ctx is not ints.ctx:
+                raise ValueError(who + ": the density belongs to other tables or another context")
+            return np.asarray(density.momentum_distribution(), dtype=np.float64)
+        nk = np.asarray(density, dtype=np.float64)
+        if nk.shape != (tab.n,):
+            raise ValueError(who + ": n(k) must hold one number per orbital (%d), not %s" % (tab.n, nk.shape))
+        return nk
+
+    def solve(self, eps, ints, tints, amps, density, omegas, eta, ip=None, ea=None, ladders=None, hoist=None, keep_basis=False):
+        """G(w + i eta) for the frequencies ``omegas`` and the targets ``ip`` (occupied orbitals) and / or ``ea`` (virtual, counted
+        over all n).  eps, ints, tints, amps, ladders, hoist: as ``SectorIPEASigma``; density: the ``SectorDensity`` of the same
+        amplitudes and their Lambda, or n(k) over all n orbitals.
+
+        Returns, with K = "ip" / "ea": "K G" complex [targets, omegas]; "K A" = -Im G / pi; "K residuals" [targets, omegas], the
+        residual h_{m+1,m} |y_m(z)| of (z +- H) x = e_1; "K converged" (all residuals below r_epsilon, or breakdown), "K krylov
+        dim", "K breakdown", "K norm" (N_p), "K targets"; per target the lists "K poles" (the Ritz values in the energy convention
+        of DESIGN 8f D3: -theta for IP, +theta for EA), "K pole strengths" (Z_j = N_p S_1j (S^-1)_j1) and "K pole residuals"
+        (h_{m+1,m} |S_mj| / |S_:j|), complex128 because a non-Hermitian block may hold conjugate pairs; "K qp e" / "K qp z": the
+        real pole of largest |Z_j| among those with a residual below r_epsilon, NaN where there is none; "A" [all targets, omegas]
+        (the IP targets, then the EA targets: "targets") and "omegas".  With ``keep_basis`` also "K basis", a ``KrylovBasis``.
+        Refused by name: everything ``SectorIPEASigma`` refuses, a density of other tables or context or n(k) of the wrong length,
+        eta <= 0, neither ip nor ea."""
+        who = "SectorSpectralFunction.solve"
+        if ip is None and ea is None:
+            raise ValueError(who + ": give the targets ip= and / or ea=")
+        if not float(eta) > 0.0:
+            raise ValueError(who + ": eta must be positive")
+        if isinstance(ints, SectorIntegrals) and ints.tables.no != self.no:
+            raise ValueError(who + ": the tables of the integrals (no = %d) do not match the solver (no = %d)"
+                             % (ints.tables.no, self.no))
+        omegas = np.atleast_1d(np.asarray(omegas, dtype=np.float64))
+        z = omegas + 1j * float(eta)
+        t_start = time.time()
+        own_hoist = hoist is None
+        if own_hoist:
+            hoist = SectorIPEAHoist(eps, ints, tints, amps, who)
+        out = {"omegas": omegas}
+        try:
+            nk = self._occupations(who, ints, density)
+            for kind, targets in (("ip", ip), ("ea", ea)):
+                if targets is None:
+                    continue
+                sig = SectorIPEASigma(kind, eps, ints, tints, amps, ladders=ladders if kind == "ea" else None, hoist=hoist)
+                try:
+                    with quiet_collector():
+                        out.update(self._run(sig, kind, [int(p) for p in np.atleast_1d(targets)], nk, z, keep_basis))
+                finally:
+                    sig.close()
+        finally:
+            if own_hoist:
+                hoist.close()
+        kinds = [K for K in ("ip", "ea") if K + " A" in out]
+        out["A"] = np.vstack([out[K + " A"] for K in kinds])
+        out["targets"] = np.concatenate([out[K + " targets"] for K in kinds])
+        print_logging_info("SectorSpectralFunction finished in {:.3f} seconds".format(time.time() - t_start), level=1)
+        return out
+
+    def _run(self, sig, K, targets, nk, z, keep_basis):
+        ctx, nt, nz = sig.ctx, len(targets), len(z)
+        res = {K + " G": np.zeros((nt, nz), dtype=np.complex128), K + " residuals": np.zeros((nt, nz)),
+               K + " converged": np.zeros(nt, dtype=bool), K + " krylov dim": np.zeros(nt, dtype=np.int64),
+               K + " breakdown": np.zeros(nt, dtype=bool), K + " norm": np.zeros(nt), K + " targets": np.array(targets, dtype=np.int64),
+               K + " poles": [], K + " pole strengths": [], K + " pole residuals": [],
+               K + " qp e": np.full(nt, np.nan), K + " qp z": np.full(nt, np.nan)}
+        kept = KrylovBasis(ctx) if keep_basis else None
+        for n, p in enumerate(targets):
+            qt, lay = sig.tables_of(p), sig.layout(p)
+            norm = 0.5 * nk[p] if K == "ip" else 1.0 - 0.5 * nk[p]
+            basis, pitch, Hbar, broke = self._arnoldi(sig, p, qt, lay, K, z)
+            k = Hbar.shape[1]
+            first, last = shifted_hessenberg(Hbar, K, z)
+            res[K + " G"][n], res[K + " residuals"][n] = norm * first, abs(Hbar[k, k - 1]) * np.abs(last)
+            res[K + " krylov dim"][n], res[K + " breakdown"][n], res[K + " norm"][n] = k, broke, norm
+            res[K + " converged"][n] = broke or bool(np.all(res[K + " residuals"][n] < self.r_epsilon))
+            theta, S = np.linalg.eig(Hbar[:k])
+            strength = (norm * S[0, :] * np.linalg.inv(S)[:, 0]).astype(np.complex128)
+            pres = abs(Hbar[k, k - 1]) * np.abs(S[-1, :]) / np.linalg.norm(S, axis=0)
+            energy = (-_SIGN[K] * theta).astype(np.complex128)
+            res[K + " poles"].append(energy)
+            res[K + " pole strengths"].append(strength)
+            res[K + " pole residuals"].append(pres)
+            ok = (pres < self.r_epsilon) & (np.abs(energy.imag) <= 1e-12 * np.maximum(1.0, np.abs(energy.real)))
+            if ok.any():
+                best = np.flatnonzero(ok)[np.argmax(np.abs(strength[ok]))]
+                res[K + " qp e"][n], res[K + " qp z"][n] = energy[best].real, strength[best].real
+            print_logging_info("SectorSpectralFunction {} target {:d}: Krylov dimension {:d}, largest residual {:.3e}, N_p = {:.6f}, "
+                               "quasi-particle pole {:.10f} with Z = {:.6f}".format(K, p, k, res[K + " residuals"][n].max(), norm,
+                                                                                    res[K + " qp e"][n], res[K + " qp z"][n]), level=2)
+            if keep_basis:
+                kept._add(K, p, lay, basis, pitch, Hbar)
+            else:
+                basis.free()
+            sig.forget(p)
+        res[K + " A"] = -res[K + " G"].imag / np.pi
+        if keep_basis:
+            res[K + " basis"] = kept
+        return res
+
+    def _arnoldi(self, sig, p, qt, lay, K, z):
+        """The Arnoldi run of one target: (basis on the device, its pitch, the [k+1, k] Hessenberg matrix on the host, breakdown).
+        The basis is zero-filled first, so the pad of the layout and of the pitch stays zero in every row; one read-back of the
+        Hessenberg matrix and the status every ``check_every`` steps and at the end."""
+        ctx = sig.ctx
+        m_cap = min(self.max_dim, qt.dim)            # the Krylov dimension cannot exceed the dimension of the block
+        length, pitch = lay.nflat, -(-lay.nflat // 32) * 32
+        basis = ctx.zeros(((m_cap + 1) * pitch,))
+        ldh = m_cap
+        state = ctx.zeros(((m_cap + 1) * ldh + 1,))   # the Hessenberg matrix, row-major, and the status word behind it
+        status = subspace.view(ctx, state, (m_cap + 1) * ldh, (1,))
+        ws = ctx.empty((arnoldi_workspace(ctx, length, m_cap - 1),))
+        row = lambda i: subspace.view(ctx, basis, i * pitch, (length,))
+        lay.part1(row(0)).set(np.ones(lay.shape1))
+        try:
+            j = 0
+            while True:
+                stop = min(j + self.check_every, m_cap)
+                for jj in range(j, stop):
+                    src, dst = row(jj), row(jj + 1)
+                    sig.apply_many(p, [lay.part1(src)], [lay.part2(src)], out1=[lay.part1(dst)], out2=[lay.part2(dst)])
+                    arnoldi_step(ctx, basis, pitch, length, jj, state, ldh, self.breakdown, ws, status)
+                j = stop
+                host = state.get()
+                flag = int(host[-1:].view(np.int64)[0])
+                k = flag if flag else j
+                Hbar = np.ascontiguousarray(host[:-1].reshape(m_cap + 1, ldh)[:k + 1, :k])
+                if flag or j >= m_cap:
+                    return basis, pitch, Hbar, bool(flag)
+                last = shifted_hessenberg(Hbar, K, z)[1]
+                if np.all(abs(Hbar[k, k - 1]) * np.abs(last) < self.r_epsilon):
+                    return basis, pitch, Hbar, False
+        except Exception:
+            basis.free()
+            raise
+        finally:
+            state.free()
+            ws.free()
+
+
+def sector_spectral(no, eps, ints, amps, density, *, tints, omegas, eta, ip=None, ea=None, ladders=None, **kwargs):
+    """What ``SectorCCD.solve(..., spectral=dict(tints=..., omegas=..., eta=..., ip=[...], ea=[...], ladders=..., max_dim=...))``
+    adds to its result: the keys of ``SectorSpectralFunction.solve``.  Further keywords go to the constructor (max_dim,
+    r_epsilon, check_every, breakdown)."""
+    return SectorSpectralFunction(no, **kwargs).solve(eps, ints, tints, amps, density, omegas, eta, ip=ip, ea=ea, ladders=ladders)

@@ -17,6 +17,9 @@ quantity is not reproducible; two checkouts whose reproducible lines agree compu
                  highest admissible target of either kind: sigma of 3 seeded stacked vectors, the flat diagonal, and the roots,
                  singles weights and residuals of a one-root solve of 6 passes.  Printed after the 292 lines of the other cases, and only by a
                  checkout that has pymes_amd/solver/ueg_eom.py
+  gf cases       the sector spectral functions at the same cases and targets: the Hessenberg matrix of a 20-step device
+                 Arnoldi run (pymes_sector_arnoldi_step), G at 9 frequencies and its residuals, for a fixed n(k).  Printed after
+                 the 404 lines of the other cases, and only by a checkout whose ueg_eom has SectorSpectralFunction
 
     python3 tools/sector_bits.py [--out FILE]
 It uses the package and the test helpers of the checkout it lies in; the first 292 lines need only names that older checkouts
@@ -129,6 +132,32 @@ def ipea_lines(ctx, case, emit):
                 emit("%s %s %s" % (case, kind, op), key, res[key])
 
 
+def gf_lines(ctx, case, emit):
+    from pymes_amd.solver.sectors import TriplesTables
+    from pymes_amd.solver.ueg_eom import SectorSpectralFunction
+    m = twisted_model() if case == "twist" else model(*case, k_cutoff=1.0)
+    tab = m.sector_tables()
+    tt = TriplesTables(tab)
+    kin = np.array([b.kinetic for b in m.basis_fns[::2]])
+    T, nk = symmetric(tab, 11, 0.1), np.linspace(1.9, 0.1, tab.n)
+    for kind in ("coulomb", "tc"):
+        terms = [{}] if kind == "coulomb" else [dict(correlator=m.trunc, is_only_2b=True),
+                                                dict(correlator=m.trunc, is_effect_2b=True)]
+        total = lambda f, *a, **kw: functools.reduce(operator.add, [quiet(f, *a, ctx=ctx, **t, **kw) for t in terms])
+        ints, tints = total(m.eval_2b_sectors, tab), total(m.eval_2b_triples, tt, both_sides=True)
+        eps = ints.hf_orbital_energies(kin)
+        for op, targets in (("ip", [0, tab.no - 1]), ("ea", [tab.no, tab.n - 1])):
+            ladders = total(m.eval_2b_ladder, tt, targets) if op == "ea" else None
+            res = quiet(SectorSpectralFunction(tab.no, max_dim=20, r_epsilon=0.0).solve, eps, ints, tints, T, nk,
+                        np.linspace(-3.0, 3.0, 9), 0.1, keep_basis=True, ladders=ladders, **{op: targets})
+            for n, p in enumerate(targets):
+                name = "%s %s %s target %d" % (case, kind, op, p)
+                emit(name, "gf hessenberg", res[op + " basis"].hessenberg(p))
+                emit(name, "gf G", np.concatenate([res[op + " G"][n].real, res[op + " G"][n].imag]))
+                emit(name, "gf residuals", res[op + " residuals"][n])
+            res[op + " basis"].close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also append the lines to this file")
@@ -150,6 +179,10 @@ def main():
         if os.path.exists(os.path.join(ROOT, "pymes_amd", "solver", "ueg_eom.py")):
             for case in SOLVER_CASES:
                 ipea_lines(ctx, case, emit)
+            from pymes_amd.solver import ueg_eom
+            if hasattr(ueg_eom, "SectorSpectralFunction"):
+                for case in SOLVER_CASES:
+                    gf_lines(ctx, case, emit)
     finally:
         ctx.close()
 

@@ -34,14 +34,16 @@ def ctx(gpu_lib):
 
 
 # ---- pymes_sector_gemm alone ---------------------------------------------------------------------------------------
-def ragged_case(seed, nblocks, hi=130, small_n=False):
+def ragged_case(seed, nblocks, hi=130, small_n=False, forced=None):
     """Seeded task table over NaN-padded arenas (operand blocks separated by NaN gaps, leading dimensions above the row
-    lengths) and what numpy makes of it."""
+    lengths) and what numpy makes of it.  ``forced``: the (m, n, k) tuples of sizes the first blocks take."""
     rng = np.random.default_rng(seed)
     m, n, k = (rng.integers(1, hi + 1, nblocks) for _ in range(3))
     if small_n:
         n = rng.integers(1, 8, nblocks)
-    for arr, forced in ((m, (0, 1, 64, 65, 128, 129, 130)), (n, (1, 0, 16, 17, 1, 33, 130)), (k, (7, 5, 0, 1, 33, 130, 31))):
+    if forced is None:
+        forced = ((0, 1, 64, 65, 128, 129, 130), (1, 0, 16, 17, 1, 33, 130), (7, 5, 0, 1, 33, 130, 31))
+    for arr, forced in zip((m, n, k), forced):
         arr[:min(nblocks, len(forced))] = forced[:nblocks]      # 0-sized blocks, n = 1, k no multiple of 4, tile edges
     ta, tb = rng.integers(0, 2, nblocks).astype(bool), rng.integers(0, 2, nblocks).astype(bool)
     beta = rng.integers(0, 2, nblocks).astype(float)

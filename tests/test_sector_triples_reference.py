@@ -148,6 +148,31 @@ def test_twisted_k_list_with_an_orbital_on_the_edge_of_the_box():
     assert np.count_nonzero(want) > 10 and err <= 1e-13 * np.abs(want).max()
 
 
+@pytest.mark.parametrize("no,nv,live", [(4, 7, 20), (8, 8, 100), (3, 1, 0)])
+def test_line_lattice_orbital_counts_no_electron_gas_has(no, nv, live):
+    """tests/_sector_lattices.line_lattice: the lists the GPU edge tests run on (tests/test_gpu_sector_edges.py), here against
+    the dense reference.  nv = 1: check_layouts cuts every list at the fixed positions [0, 1, 7, ...], which a list of three
+    elements does not have, so only the values are compared there (all of them an exact +0.0)."""
+    from tests._sector_lattices import line_lattice
+    k, _ = line_lattice(no, nv)
+    tab, tt = tr.tables_for(k, no)
+    assert (tt.no, tt.nv) == (no, nv) and tt.dims.tolist() == [no + nv, 1, 1]
+    V = tr.conserving_V(k, 17)
+    rng = np.random.default_rng(19)
+    eps = np.concatenate((np.sort(rng.random(no)) - 2.0, np.sort(rng.random(nv)) + 1.0))
+    T = symmetric_amplitudes(tab, 23)
+    if nv > 1:
+        check_layouts(tab, tt, V, T)
+    err, want, got = compare(no, tab, tt, V, eps, T)
+    scale = tr.per_triple(tt, eps, *tr.triples_integrals(tt, V), tt.implied(T))[1]
+    print(f"line lattice ({no},{nv}): max|per triple| = {np.abs(want).max():.2e}, worst difference {err:.1e}, "
+          f"{int((scale > 0).sum())} of {len(want)} triples live")
+    assert len(want) == R.n_triples(no) and int((scale > 0).sum()) == live
+    assert err <= 1e-13 * np.abs(want).max()
+    if live == 0:
+        assert np.array_equal(got.view(np.int64), np.zeros(len(got), dtype=np.int64))
+
+
 def test_tables_refuse_what_they_cannot_hold():
     with pytest.raises(TypeError, match="a SectorTables is needed"):
         tr.TriplesTables(np.zeros((3, 3)))

@@ -586,6 +586,18 @@ int pymes_ueg_eval_2b_list(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mod
                            int lattice_cutoff, int correlator, const double* params_host, const int32_t* k_int_host,
                            const double* tab_scalar_host, const double* tab_array_host, int64_t tab_len,
                            const int32_t* pqrs_dev, int64_t count, double* out_dev);
+/* The state that list form prepares (the kernel parameters, the correlator tables, for mode 1 the u_mat table with its index, for
+ * mode 2 E[p,r]), kept on the device as a ladder term: the element a term defines for (p,q,r,s) is exactly what
+ * pymes_ueg_eval_2b_list with the same arguments writes for that entry, bit for bit -- both run one device function.  The
+ * arguments are those of the list form up to tab_len.  *term is an opaque handle of this context: pymes_ueg_ladder_term_free
+ * releases it, and so does pymes_ctx_destroy for every term still alive.  pymes_ueg_ladder_term_bytes: the device bytes a term
+ * holds (nothing for modes 0 and 3 without tables, ~ 8 n_p^2 for mode 2).  create synchronises and is refused while a launch
+ * graph is being recorded. */
+int pymes_ueg_ladder_term_create(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mode, double L, double k_cutoff, double gamma,
+                                 int lattice_cutoff, int correlator, const double* params_host, const int32_t* k_int_host,
+                                 const double* tab_scalar_host, const double* tab_array_host, int64_t tab_len, void** term);
+int pymes_ueg_ladder_term_free(pymes_ctx* ctx, void* term);
+int pymes_ueg_ladder_term_bytes(pymes_ctx* ctx, const void* term, int64_t* bytes);
 
 /* ---- momentum-sector CCD / DCD (pymes_amd/solver/ueg_cc.py, sectors.py; DESIGN "Momentum sectors") -------------
  * A Hamiltonian whose orbitals carry a conserved integer vector keeps ~ o^2 v amplitudes, held block by block (one block
@@ -613,6 +625,25 @@ typedef struct pymes_sector_task {
 } pymes_sector_task;
 int pymes_sector_gemm(pymes_ctx* ctx, const pymes_sector_task* tasks_dev, int ntask, int64_t ntiles, const double* A_dev,
                       const double* B_dev, double* C_dev);
+/* The direct particle ladder: C^t = alpha op(A^t) B^t + beta C^t for every record of a device-resident task table, with
+ *   A^t[(a,b),(c,d)] = sum_{q < nterms} coef_host[q] w_q(a,b,c,d)
+ * never read from memory: w_q is the element of ladder term q (above) and (a,b), (c,d) are the entries first_dev[t] + row and
+ * first_dev[t] + column of vv_rows_dev, the vv pair list as absolute orbital indices (int32 [rows, 2], the order of
+ * SectorTables.vv_pairs); first_dev: int64, one per task; k_int_dev: int32 [n_p, 3].  Of a record m, n, k, b, c, ldb, ldc,
+ * alpha, beta, tile0 and PYMES_SECTOR_TRANS_A are used (tile0 and ntiles as pymes_sector_gemm counts them, whatever tile the
+ * kernel takes); a and lda are ignored.  With TRANS_A the element at output row (a,b) and summation index (c,d) is w(c,d,a,b).
+ * Contract: every output element adds its k products in ascending order with fma from +0.0 and ends with the rounded
+ * alpha acc (+ rounded beta C) of pymes_sector_gemm -- for one term with coefficient 1 the result has the bits of
+ * pymes_sector_gemm on the stored block.  Several terms are combined as pymes_lincomb combines stored arenas, s = 0 then
+ * s = s + w_q coef_q in ascending q with product and sum rounded separately: the bits of the stored sum for sums of terms that
+ * were each scaled at most once (coefficients that are powers of two: any order of scaling and adding).  No atomics; identical
+ * calls give identical bits; nothing outside m, n, k is read or written; with beta = 0 the output is not read.  The kernel
+ * trusts the task table, first_dev and vv_rows_dev (pymes_amd/solver/ueg_cc.py checks them before the upload).  Refused: more
+ * than PYMES_SECTOR_LADDER_MAX_TERMS terms, a term of another context or of another n_p, terms of different L. */
+#define PYMES_SECTOR_LADDER_MAX_TERMS 4
+int pymes_sector_ladder_direct(pymes_ctx* ctx, const pymes_sector_task* tasks_dev, int ntask, int64_t ntiles,
+                               const int64_t* first_dev, const int32_t* vv_rows_dev, const int32_t* k_int_dev, int n_p, int nterms,
+                               void* const* terms, const double* coef_host, const double* B_dev, double* C_dev);
 /* dst[i] = beta dst[i] + a1 s1[m1[i]] + a2 s2[m2[i]], i < n (int64 maps on the device; s2_dev NULL: one source; beta = 0: dst
  * is not read).  The moves between the three sector layouts, 2 D - C among them. */
 int pymes_sector_gather(pymes_ctx* ctx, double* dst_dev, int64_t n, double beta, double a1, const double* s1_dev,

@@ -150,6 +150,14 @@ SIGNATURES = {
     "pymes_ueg_eval_2b_list": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                          C.c_int, C.c_int, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                          C.c_int64, C.c_void_p]),
+    # the prepared state of that list form kept as a term of the direct sector ladder, and the ladder itself
+    "pymes_ueg_ladder_term_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                               C.c_double, C.c_int, C.c_int, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int64, C.POINTER(C.c_void_p)]),
+    "pymes_ueg_ladder_term_free": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pymes_ueg_ladder_term_bytes": (C.c_int, [C.c_void_p, C.c_void_p, c_i64_p]),
+    "pymes_sector_ladder_direct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int, C.c_int, C.c_void_p, c_double_p, C.c_void_p, C.c_void_p]),
     # momentum-sector CCD / DCD (include/pymes_amd.h): ragged batched product, layout gathers, element-wise tails
     "pymes_sector_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pymes_sector_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p,

@@ -3,7 +3,9 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <algorithm>
+#include <map>
 #include <mutex>
 #include <set>
 #include <string>
@@ -38,6 +40,8 @@ thread_local std::string g_err;
 std::mutex g_eom_mu;
 std::set<pymes_eom*> g_eom_live;
 std::set<pymes_ipea*> g_ipea_live;          // (the IP / EA handles, same rule, same mutex)
+std::map<dev::UegLadderTerm*, pymes_ctx*> g_ladder_terms;      // (the live ladder terms and their contexts, same mutex: a term
+                                                               // still alive goes with its context)
 
 template <class F>
 int guarded(F&& f) {
@@ -141,6 +145,17 @@ int pymes_ctx_destroy(pymes_ctx* ctx) {
                     delete h->s;
                     h->s = nullptr;
                     h->ctx = nullptr;
+                }
+            for (auto it = g_ladder_terms.begin(); it != g_ladder_terms.end();)
+                if (it->second == ctx) {
+                    if (ctx->e) {
+                        dev::set_device(ctx->e->device);
+                        dev::stream_sync(ctx->e->stream);
+                    }
+                    dev::ueg_ladder_term_free(it->first);
+                    it = g_ladder_terms.erase(it);
+                } else {
+                    ++it;
                 }
         }
         delete ctx->e;
@@ -916,6 +931,39 @@ int pymes_ueg_eval_2b_tab(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mode
         ueg_eval(ctx, n_p, n_ele, imax, mode, L, 0.0, 1.0, lattice_cutoff, k_int, index_map, tab_scalar, tab_array, tab_len, V);
     });
 }
+// The checks and the parameter block that the list form and a ladder term share: `run(p, k_int_dev)` with the orbitals' vectors
+// uploaded for its duration.
+static void ueg_list_frame(Engine& e, int n_p, int n_ele, int imax, int mode, double L, double k_cutoff, double gamma,
+                           int lattice_cutoff, int correlator, const double* params, const int32_t* k_int, const double* tab_scalar,
+                           const double* tab_array, int64_t tab_len, bool empty,
+                           const std::function<void(const dev::UegParams&, const int*)>& run) {
+    need(k_int, "k_int");
+    if (n_p < 1 || imax < 0 || mode < 0 || mode > 3) throw pymes::Error("ueg: bad arguments");
+    if (correlator < 0 || correlator > 6) throw pymes::Error("ueg: correlator must be 0 (trunc) .. 6");
+    if (correlator > 0) need(params, "params");
+    if (mode == 0 && (correlator > 0 || tab_array)) throw pymes::Error("ueg: mode 0 (Coulomb) has no correlator");
+    if (tab_array) {
+        const int64_t r = static_cast<int64_t>(lattice_cutoff) + 2 * imax, need_len = 3 * r * r + 1;
+        if (!tab_scalar || tab_len < need_len || tab_len > (int64_t(1) << 30)) throw pymes::Error("ueg: correlator tables must cover |n|^2 <= 3 (lattice_cutoff + 2 imax)^2");
+    }
+    for (int i = 0; i < 3 * n_p; ++i)       // the u_mat index of mode 1 spans momentum transfers up to 2 imax
+        if (k_int[i] < -imax || k_int[i] > imax) throw pymes::Error("ueg: k outside the index map");
+    if (empty) return;
+    int* kd = static_cast<int*>(dev::dmalloc(sizeof(int) * 3 * n_p));
+    try {
+        dev::memcpy_h2d(kd, k_int, sizeof(int) * 3 * n_p, e.stream);
+        dev::UegParams p{n_p, n_ele, imax, mode, L, L * L * L, correlator == 0 ? k_cutoff : 0.0, correlator == 0 ? gamma : 1.0,
+                         lattice_cutoff};
+        p.tab_scalar = tab_scalar; p.tab_array = tab_array; p.tab_len = static_cast<int>(tab_len);
+        p.corr_kind = tab_array ? 0 : correlator;
+        for (int i = 0; i < 4 && params && correlator > 0; ++i) p.corr_p[i] = params[i];
+        run(p, kd);                         // (drains the stream before it returns)
+    } catch (...) {
+        dev::dfree(kd);
+        throw;
+    }
+    dev::dfree(kd);
+}
 int pymes_ueg_eval_2b_list(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mode, double L, double k_cutoff, double gamma,
                            int lattice_cutoff, int correlator, const double* params, const int32_t* k_int,
                            const double* tab_scalar, const double* tab_array, int64_t tab_len, const int32_t* pqrs, int64_t count,
@@ -924,32 +972,53 @@ int pymes_ueg_eval_2b_list(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mod
         Engine& e = E(ctx);
         if (e.capturing()) throw pymes::Error("ueg_eval_2b_list while a launch graph is being recorded");
         need(k_int, "k_int");
-        if (n_p < 1 || imax < 0 || mode < 0 || mode > 3 || count < 0) throw pymes::Error("ueg: bad arguments");
+        if (count < 0) throw pymes::Error("ueg: bad arguments");
         if (count > 0) { need(pqrs, "pqrs"); need(out, "out"); }
-        if (correlator < 0 || correlator > 6) throw pymes::Error("ueg: correlator must be 0 (trunc) .. 6");
-        if (correlator > 0) need(params, "params");
-        if (mode == 0 && (correlator > 0 || tab_array)) throw pymes::Error("ueg: mode 0 (Coulomb) has no correlator");
-        if (tab_array) {
-            const int64_t r = static_cast<int64_t>(lattice_cutoff) + 2 * imax, need_len = 3 * r * r + 1;
-            if (!tab_scalar || tab_len < need_len || tab_len > (int64_t(1) << 30)) throw pymes::Error("ueg: correlator tables must cover |n|^2 <= 3 (lattice_cutoff + 2 imax)^2");
-        }
-        for (int i = 0; i < 3 * n_p; ++i)       // the u_mat index of mode 1 spans momentum transfers up to 2 imax
-            if (k_int[i] < -imax || k_int[i] > imax) throw pymes::Error("ueg: k outside the index map");
-        if (count == 0) return;
-        int* kd = static_cast<int*>(dev::dmalloc(sizeof(int) * 3 * n_p));
-        try {
-            dev::memcpy_h2d(kd, k_int, sizeof(int) * 3 * n_p, e.stream);
-            dev::UegParams p{n_p, n_ele, imax, mode, L, L * L * L, correlator == 0 ? k_cutoff : 0.0, correlator == 0 ? gamma : 1.0,
-                             lattice_cutoff};
-            p.tab_scalar = tab_scalar; p.tab_array = tab_array; p.tab_len = static_cast<int>(tab_len);
-            p.corr_kind = tab_array ? 0 : correlator;
-            for (int i = 0; i < 4 && params && correlator > 0; ++i) p.corr_p[i] = params[i];
-            dev::ueg_two_body_list(p, kd, pqrs, count, out, e.stream);      // (drains the stream before it returns)
-        } catch (...) {
-            dev::dfree(kd);
-            throw;
-        }
-        dev::dfree(kd);
+        ueg_list_frame(e, n_p, n_ele, imax, mode, L, k_cutoff, gamma, lattice_cutoff, correlator, params, k_int, tab_scalar,
+                       tab_array, tab_len, count == 0,
+                       [&](const dev::UegParams& p, const int* kd) { dev::ueg_two_body_list(p, kd, pqrs, count, out, e.stream); });
+    });
+}
+int pymes_ueg_ladder_term_create(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mode, double L, double k_cutoff, double gamma,
+                                 int lattice_cutoff, int correlator, const double* params, const int32_t* k_int,
+                                 const double* tab_scalar, const double* tab_array, int64_t tab_len, void** term) {
+    return guarded([&] {
+        need(term, "term");
+        *term = nullptr;
+        Engine& e = E(ctx);
+        if (e.capturing()) throw pymes::Error("ueg_ladder_term_create while a launch graph is being recorded");
+        ueg_list_frame(e, n_p, n_ele, imax, mode, L, k_cutoff, gamma, lattice_cutoff, correlator, params, k_int, tab_scalar,
+                       tab_array, tab_len, false, [&](const dev::UegParams& p, const int* kd) {
+                           dev::UegLadderTerm* t = dev::ueg_ladder_term_create(p, kd, e.stream);
+                           std::lock_guard<std::mutex> lock(g_eom_mu);
+                           g_ladder_terms[t] = ctx;
+                           *term = t;
+                       });
+    });
+}
+static dev::UegLadderTerm* ladder_term_of(pymes_ctx* ctx, const void* term, const char* who) {      // (g_eom_mu held)
+    auto it = g_ladder_terms.find(static_cast<dev::UegLadderTerm*>(const_cast<void*>(term)));
+    if (it == g_ladder_terms.end() || it->second != ctx)
+        throw pymes::Error(std::string(who) + ": not a live ladder term of this context");
+    return it->first;
+}
+int pymes_ueg_ladder_term_free(pymes_ctx* ctx, void* term) {
+    return guarded([&] {
+        if (!term) return;
+        Engine& e = E(ctx);
+        std::lock_guard<std::mutex> lock(g_eom_mu);
+        dev::UegLadderTerm* t = ladder_term_of(ctx, term, "ueg_ladder_term_free");
+        dev::stream_sync(e.stream);             // a ladder launch that reads the term's tables may still be in flight
+        g_ladder_terms.erase(t);
+        dev::ueg_ladder_term_free(t);
+    });
+}
+int pymes_ueg_ladder_term_bytes(pymes_ctx* ctx, const void* term, int64_t* bytes) {
+    return guarded([&] {
+        need(bytes, "bytes");
+        E(ctx);
+        std::lock_guard<std::mutex> lock(g_eom_mu);
+        dev::ueg_ladder_term_info(ladder_term_of(ctx, term, "ueg_ladder_term_bytes"), bytes, nullptr, nullptr);
     });
 }
 
@@ -957,6 +1026,23 @@ int pymes_ueg_eval_2b_list(pymes_ctx* ctx, int n_p, int n_ele, int imax, int mod
 int pymes_sector_gemm(pymes_ctx* ctx, const pymes_sector_task* tasks, int ntask, int64_t ntiles, const double* A, const double* B,
                       double* C) {
     return guarded([&] { dev::sector_gemm(tasks, ntask, ntiles, A, B, C, E(ctx).stream); });
+}
+int pymes_sector_ladder_direct(pymes_ctx* ctx, const pymes_sector_task* tasks, int ntask, int64_t ntiles, const int64_t* first,
+                               const int32_t* vv_rows, const int32_t* k_int, int n_p, int nterms, void* const* terms,
+                               const double* coef, const double* B, double* C) {
+    return guarded([&] {
+        Engine& e = E(ctx);
+        if (nterms < 1 || nterms > PYMES_SECTOR_LADDER_MAX_TERMS)
+            throw pymes::Error("sector_ladder_direct: between 1 and " + std::to_string(PYMES_SECTOR_LADDER_MAX_TERMS) +
+                               " terms per call");
+        need(terms, "terms"); need(coef, "coef");
+        const dev::UegLadderTerm* ts[PYMES_SECTOR_LADDER_MAX_TERMS];
+        {
+            std::lock_guard<std::mutex> lock(g_eom_mu);
+            for (int q = 0; q < nterms; ++q) ts[q] = ladder_term_of(ctx, terms[q], "sector_ladder_direct");
+        }
+        dev::sector_ladder_direct(tasks, ntask, ntiles, first, vv_rows, k_int, n_p, nterms, ts, coef, B, C, e.stream);
+    });
 }
 int pymes_sector_gather(pymes_ctx* ctx, double* dst, int64_t n, double beta, double a1, const double* s1, const int64_t* m1,
                         double a2, const double* s2, const int64_t* m2) {

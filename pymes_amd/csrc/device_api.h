@@ -540,11 +540,21 @@ void ueg_two_body(const UegParams& prm, const int* k_int_dev, const int* index_m
 // out_dev[t] = V of pqrs_dev[t][4], t < count: the same elements for a list (include/pymes_amd.h, pymes_ueg_eval_2b_list).  The
 // product library only (the host simulator has no definition: a weak one in the engine throws).
 void ueg_two_body_list(const UegParams& prm, const int* k_int_dev, const int* pqrs_dev, int64_t count, double* out_dev, stream_t s);
+// The prepared state behind that list form, kept: a term of the direct sector ladder (include/pymes_amd.h,
+// pymes_ueg_ladder_term_create).  create drains the stream before it returns; info: device bytes held, orbitals, box length.
+// The product library only, like the list form.
+struct UegLadderTerm;
+UegLadderTerm* ueg_ladder_term_create(const UegParams& prm, const int* k_int_dev, stream_t s);
+void ueg_ladder_term_free(UegLadderTerm* t);
+void ueg_ladder_term_info(const UegLadderTerm* t, int64_t* bytes, int* n_p, double* L);
 
 // ---- momentum-sector CCD / DCD (include/pymes_amd.h, pymes_sector_*; DESIGN "Momentum sectors").  The product library only
 // (weak definitions in the engine throw, by name).
 void sector_gemm(const pymes_sector_task* tasks_dev, int ntask, int64_t ntiles, const double* A, const double* B, double* C,
                  stream_t s);
+void sector_ladder_direct(const pymes_sector_task* tasks_dev, int ntask, int64_t ntiles, const int64_t* first_dev,
+                          const int32_t* vv_rows_dev, const int32_t* k_int_dev, int n_p, int nterms,
+                          const UegLadderTerm* const* terms, const double* coef_host, const double* B, double* C, stream_t s);
 void sector_gather(double* dst, int64_t n, double beta, double a1, const double* s1, const int64_t* m1, double a2, const double* s2,
                    const int64_t* m2, stream_t s);
 void sector_xdiag(const double* Tt, const double* W1, const double* D, double* Ex, const double* eps, double w, int no, int nv,

@@ -909,6 +909,18 @@ __attribute__((weak)) void t2_layouts_sym(const double*, double*, double*, doubl
 __attribute__((weak)) void ueg_two_body_list(const UegParams&, const int*, const int*, int64_t, double*, stream_t) {
     throw std::runtime_error("ueg_two_body_list: not available in this backend");
 }
+__attribute__((weak)) UegLadderTerm* ueg_ladder_term_create(const UegParams&, const int*, stream_t) {
+    throw std::runtime_error("ueg_ladder_term_create: not available in this backend");
+}
+__attribute__((weak)) void ueg_ladder_term_free(UegLadderTerm*) {}
+__attribute__((weak)) void ueg_ladder_term_info(const UegLadderTerm*, int64_t*, int*, double*) {
+    throw std::runtime_error("ueg_ladder_term_info: not available in this backend");
+}
+__attribute__((weak)) void sector_ladder_direct(const pymes_sector_task*, int, int64_t, const int64_t*, const int32_t*, const int32_t*,
+                                                int, int, const UegLadderTerm* const*, const double*, const double*, double*,
+                                                stream_t) {
+    throw std::runtime_error("sector_ladder_direct: not available in this backend");
+}
 __attribute__((weak)) void sector_gemm(const pymes_sector_task*, int, int64_t, const double*, const double*, double*, stream_t) {
     throw std::runtime_error("sector_gemm: not available in this backend");
 }

@@ -221,15 +221,28 @@ __global__ void ueg_effective_kernel(const UegK u, const int* __restrict__ kint,
     E[idx] = val / u.Omega;
 }
 
-// V_pqrs of one momentum-conserving element (ueg.py:404-507); umat / E: what ueg_prepare made for modes 1 / 2
-__device__ __forceinline__ double ueg_element(const UegK& u, const int* __restrict__ kint, const double* __restrict__ umat,
-                                              const int* __restrict__ umat_index, const double* __restrict__ E, int p, int r,
-                                              int s, const int d[3]) {
+// One orbital as the element functions below take it: its index, its integer vector and the float momentum 2 pi k / L the
+// reference forms from it (ueg_kp) -- from the global table (ueg_orb) or from wherever a kernel has staged it.
+struct UegOrb { int idx, k[3]; double kp[3]; };
+__device__ __forceinline__ UegOrb ueg_orb(const UegK& u, const int* __restrict__ kint, int idx) {
+    UegOrb o;
+    o.idx = idx;
+    for (int c = 0; c < 3; ++c) {
+        o.k[c] = kint[3 * idx + c];
+        o.kp[c] = ueg_kp(o.k[c], u.L);
+    }
+    return o;
+}
+
+// V_pqrs of one momentum-conserving element (ueg.py:404-507); umat / E: what ueg_prepare made for modes 1 / 2; d = k_r - k_p
+__device__ __forceinline__ double ueg_element(const UegK& u, const double* __restrict__ umat, const int* __restrict__ umat_index,
+                                              const double* __restrict__ E, const UegOrb& p, const UegOrb& r, const UegOrb& s,
+                                              const int d[3]) {
     const long n = u.n_p;
     double dk[3], dk2 = 0.0;
     long md = 0;
     for (int c = 0; c < 3; ++c) {
-        dk[c] = ueg_kp(kint[3 * r + c], u.L) - ueg_kp(kint[3 * p + c], u.L);
+        dk[c] = r.kp[c] - p.kp[c];
         dk2 += dk[c] * dk[c];
         md += (long)d[c] * d[c];
     }
@@ -243,14 +256,35 @@ __device__ __forceinline__ double ueg_element(const UegK& u, const int* __restri
         const double um = umat[umat_index[((long)(d[0] + 2 * u.imax) * w4 + (d[1] + 2 * u.imax)) * w4 + d[2] + 2 * u.imax]];
         if (fabs(dk2) > 0.0) {
             double rsdk = 0.0;
-            for (int c = 0; c < 3; ++c) rsdk += (ueg_kp(kint[3 * r + c], u.L) - ueg_kp(kint[3 * s + c], u.L)) * dk[c];
+            for (int c = 0; c < 3; ++c) rsdk += (r.kp[c] - s.kp[c]) * dk[c];
             const double x = ueg_u<false>(dk2, md, u);
             w = (4.0 * M_PI / dk2 + um + dk2 * x - rsdk * x) / u.Omega;
         } else {
             w = um / u.Omega;
         }
     } else {
-        w = E[(long)p * n + r];
+        w = E[(long)p.idx * n + r.idx];
+    }
+    return w;
+}
+
+// <pq|rs> as the list form defines it (include/pymes_amd.h, pymes_ueg_eval_2b_list): conservation decided in exact integer
+// arithmetic (an entry that does not conserve the vector is 0); mode 2 already symmetrised, (E[p,r] + E[q,s]) / 2.  The one
+// body of ueg_list_kernel and of the direct sector ladder (kernels_sector.hip), which therefore agree to the bit.
+__device__ __forceinline__ double ueg_pair_element(const UegK& u, const double* __restrict__ umat,
+                                                   const int* __restrict__ umat_index, const double* __restrict__ E,
+                                                   const UegOrb& p, const UegOrb& q, const UegOrb& r, const UegOrb& s) {
+    int d[3], e[3];
+    bool ok = true;
+    for (int c = 0; c < 3; ++c) {
+        d[c] = r.k[c] - p.k[c];
+        e[c] = s.k[c] - q.k[c];
+        ok = ok && d[c] + e[c] == 0;
+    }
+    double w = 0.0;
+    if (ok) {
+        w = ueg_element(u, umat, umat_index, E, p, r, s, d);
+        if (u.mode == 2) w = 0.5 * w + 0.5 * ueg_element(u, umat, umat_index, E, q, s, r, e);
     }
     return w;
 }
@@ -272,11 +306,11 @@ __global__ void ueg_scatter_kernel(const UegK u, const int* __restrict__ kint, c
     if (loc < 0 || loc >= (long)u.m * u.m * u.m) return;     // only the flattened index is range-checked (:397)
     const int s = map[loc];
     if (s < 0 || s >= u.n_p) return;
-    V[((long)(p * n + q) * n + r) * n + s] = ueg_element(u, kint, umat, umat_index, E, p, r, s, d);
+    V[((long)(p * n + q) * n + r) * n + s] =
+        ueg_element(u, umat, umat_index, E, ueg_orb(u, kint, p), ueg_orb(u, kint, r), ueg_orb(u, kint, s), d);
 }
 
-// one thread per listed (p,q,r,s): the same element, conservation decided in exact integer arithmetic (a list entry that
-// does not conserve the vector is 0, one that names no orbital is NaN); mode 2 already symmetrised, (E[p,r] + E[q,s]) / 2
+// one thread per listed (p,q,r,s): ueg_pair_element of the entry; one that names no orbital is NaN
 __global__ void ueg_list_kernel(const UegK u, const int* __restrict__ kint, const double* __restrict__ umat,
                                 const int* __restrict__ umat_index, const double* __restrict__ E, const int* __restrict__ pqrs,
                                 long count, double* __restrict__ out) {
@@ -284,19 +318,96 @@ __global__ void ueg_list_kernel(const UegK u, const int* __restrict__ kint, cons
     if (t >= count) return;
     const int p = pqrs[4 * t], q = pqrs[4 * t + 1], r = pqrs[4 * t + 2], s = pqrs[4 * t + 3];
     if (p < 0 || q < 0 || r < 0 || s < 0 || p >= u.n_p || q >= u.n_p || r >= u.n_p || s >= u.n_p) { out[t] = nan(""); return; }
-    int d[3], e[3];
-    bool ok = true;
-    for (int c = 0; c < 3; ++c) {
-        d[c] = kint[3 * r + c] - kint[3 * p + c];
-        e[c] = kint[3 * s + c] - kint[3 * q + c];
-        ok = ok && d[c] + e[c] == 0;
+    out[t] = ueg_pair_element(u, umat, umat_index, E, ueg_orb(u, kint, p), ueg_orb(u, kint, q), ueg_orb(u, kint, r),
+                              ueg_orb(u, kint, s));
+}
+
+// What the integral kernels read besides the orbitals' vectors, prepared once: the kernel parameters, the correlator tables,
+// for mode 1 the u_mat table over the distinct momentum transfers with its index, for mode 2 E[p,r].  It lives until
+// ueg_release: for one fill (the dense and the list builder) or as long as a ladder term (dev::UegLadderTerm).
+struct UegPrepared {
+    UegK u;
+    double *umat = nullptr, *E = nullptr, *tabs = nullptr;
+    int* uidx = nullptr;
+    int64_t bytes = 0;          // device bytes held
+};
+void ueg_release(UegPrepared& s) {
+    dev::dfree(s.umat); dev::dfree(s.E); dev::dfree(s.uidx); dev::dfree(s.tabs);
+    s.umat = s.E = s.tabs = nullptr;
+    s.uidx = nullptr;
+    s.bytes = 0;
+}
+// Returns with the tables complete (the stream has drained): the temporaries of the u_mat build are gone.
+UegPrepared ueg_prepare(const dev::UegParams& prm, const int* k_int_dev, hipStream_t st) {
+    UegPrepared s;
+    UegK& u = s.u;
+    u.n_p = prm.n_p; u.n_occ = prm.n_ele / 2; u.imax = prm.imax; u.m = 2 * prm.imax + 1; u.mode = prm.mode;
+    u.n_ele = prm.n_ele; u.lat = prm.lattice_cutoff; u.L = prm.L; u.Omega = prm.Omega; u.gamma = prm.gamma;
+    const double kc = prm.k_cutoff * 2 * M_PI / prm.L;
+    u.kc2g = kc * kc * (1 + 0.00001);
+    u.tab_s = u.tab_a = nullptr;
+    u.tab_len = 0;
+    u.kind = prm.corr_kind; u.p0 = prm.corr_p[0]; u.p1 = prm.corr_p[1]; u.p2 = prm.corr_p[2];
+    if (u.kind < 0 || u.kind > 6) throw std::runtime_error("ueg: unknown correlator kind");
+    const long n = prm.n_p;
+    double* dk_dev = nullptr;
+    int* dint_dev = nullptr;
+    try {
+        if (prm.tab_array) {
+            if (!prm.tab_scalar || prm.tab_len < 1) throw std::runtime_error("ueg: both correlator tables are needed");
+            s.tabs = (double*)dev::dmalloc(sizeof(double) * 2 * prm.tab_len);
+            s.bytes += sizeof(double) * 2 * prm.tab_len;
+            HIP_CHECK(copy_async(s.tabs, prm.tab_scalar, sizeof(double) * prm.tab_len, hipMemcpyHostToDevice, st));
+            HIP_CHECK(copy_async(s.tabs + prm.tab_len, prm.tab_array, sizeof(double) * prm.tab_len, hipMemcpyHostToDevice, st));
+            u.tab_s = s.tabs; u.tab_a = s.tabs + prm.tab_len; u.tab_len = prm.tab_len;
+        }
+        std::vector<int> kint(3 * n);
+        HIP_CHECK(copy_async(kint.data(), k_int_dev, sizeof(int) * 3 * n, hipMemcpyDeviceToHost, st));
+        wait_idle(st);
+        if (prm.mode == 1) {
+            // distinct momentum transfers d = k_r - k_p, with the float d_k of their first (p,r) pair
+            const int w4 = 4 * prm.imax + 1;
+            std::vector<int> index((size_t)w4 * w4 * w4, -1);
+            std::vector<double> dks;
+            std::vector<int> dints;
+            for (long p = 0; p < n; ++p)
+                for (long r = 0; r < n; ++r) {
+                    int d[3];
+                    for (int c = 0; c < 3; ++c) {
+                        d[c] = kint[3 * r + c] - kint[3 * p + c];
+                        if (d[c] < -2 * prm.imax || d[c] > 2 * prm.imax) throw std::runtime_error("ueg: k outside the index map");
+                    }
+                    int& slot = index[((size_t)(d[0] + 2 * prm.imax) * w4 + (d[1] + 2 * prm.imax)) * w4 + d[2] + 2 * prm.imax];
+                    if (slot < 0) {
+                        slot = (int)(dks.size() / 3);
+                        for (int c = 0; c < 3; ++c) dints.push_back(d[c]);
+                        for (int c = 0; c < 3; ++c)
+                            dks.push_back(((double)(kint[3 * r + c] * 2) * M_PI) / prm.L - ((double)(kint[3 * p + c] * 2) * M_PI) / prm.L);
+                    }
+                }
+            const int nd = (int)(dks.size() / 3);
+            s.umat = (double*)dev::dmalloc(sizeof(double) * nd);
+            dk_dev = (double*)dev::dmalloc(sizeof(double) * 3 * nd);
+            s.uidx = (int*)dev::dmalloc(sizeof(int) * index.size());
+            dint_dev = (int*)dev::dmalloc(sizeof(int) * 3 * nd);
+            s.bytes += sizeof(double) * nd + sizeof(int) * index.size();
+            HIP_CHECK(copy_async(dint_dev, dints.data(), sizeof(int) * 3 * nd, hipMemcpyHostToDevice, st));
+            HIP_CHECK(copy_async(dk_dev, dks.data(), sizeof(double) * 3 * nd, hipMemcpyHostToDevice, st));
+            HIP_CHECK(copy_async(s.uidx, index.data(), sizeof(int) * index.size(), hipMemcpyHostToDevice, st));
+            launch_kernel(ueg_nabla_kernel, dim3(nd), dim3(256), 0, st, u, dk_dev, dint_dev, s.umat);
+        } else if (prm.mode == 2) {
+            s.E = (double*)dev::dmalloc(sizeof(double) * n * n);
+            s.bytes += sizeof(double) * n * n;
+            launch_kernel(ueg_effective_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st, u, k_int_dev, s.E);
+        }
+        wait_idle(st);          // (the host lists above and the two temporaries are read by the stream until here)
+    } catch (...) {
+        dev::dfree(dk_dev); dev::dfree(dint_dev);
+        ueg_release(s);
+        throw;
     }
-    double w = 0.0;
-    if (ok) {
-        w = ueg_element(u, kint, umat, umat_index, E, p, r, s, d);
-        if (u.mode == 2) w = 0.5 * w + 0.5 * ueg_element(u, kint, umat, umat_index, E, q, s, r, e);
-    }
-    out[t] = w;
+    dev::dfree(dk_dev); dev::dfree(dint_dev);
+    return s;
 }
 
 }  // namespace
@@ -378,76 +489,19 @@ double tc_triple_contraction(const double* L, int nb, int no, stream_t s) {
     return h;
 }
 
-// The preparation steps shared by the dense builder and the list builder: the kernel parameters, the correlator tables, and
-// for mode 1 the u_mat table over the distinct momentum transfers, for mode 2 E[p,r]; then `fill(u, umat, uidx, E)` launches
-// the kernel that writes the integrals, and everything is released once the stream has drained.
+// The dense builder and the list builder: ueg_prepare, then `fill(u, umat, uidx, E)` launches the kernel that writes the
+// integrals, and everything is released once the stream has drained.
 template <typename Fill>
 static void ueg_prepare_and_fill(const UegParams& prm, const int* k_int_dev, hipStream_t st, Fill fill) {
-    UegK u;
-    u.n_p = prm.n_p; u.n_occ = prm.n_ele / 2; u.imax = prm.imax; u.m = 2 * prm.imax + 1; u.mode = prm.mode;
-    u.n_ele = prm.n_ele; u.lat = prm.lattice_cutoff; u.L = prm.L; u.Omega = prm.Omega; u.gamma = prm.gamma;
-    const double kc = prm.k_cutoff * 2 * M_PI / prm.L;
-    u.kc2g = kc * kc * (1 + 0.00001);
-    u.tab_s = u.tab_a = nullptr;
-    u.tab_len = 0;
-    u.kind = prm.corr_kind; u.p0 = prm.corr_p[0]; u.p1 = prm.corr_p[1]; u.p2 = prm.corr_p[2];
-    if (u.kind < 0 || u.kind > 6) throw std::runtime_error("ueg: unknown correlator kind");
-    const long n = prm.n_p;
-    double* tabs = nullptr;
-    if (prm.tab_array) {
-        if (!prm.tab_scalar || prm.tab_len < 1) throw std::runtime_error("ueg: both correlator tables are needed");
-        tabs = (double*)dmalloc(sizeof(double) * 2 * prm.tab_len);
-        HIP_CHECK(copy_async(tabs, prm.tab_scalar, sizeof(double) * prm.tab_len, hipMemcpyHostToDevice, st));
-        HIP_CHECK(copy_async(tabs + prm.tab_len, prm.tab_array, sizeof(double) * prm.tab_len, hipMemcpyHostToDevice, st));
-        u.tab_s = tabs; u.tab_a = tabs + prm.tab_len; u.tab_len = prm.tab_len;
-    }
-    std::vector<int> kint(3 * n);
-    HIP_CHECK(copy_async(kint.data(), k_int_dev, sizeof(int) * 3 * n, hipMemcpyDeviceToHost, st));
-    wait_idle(st);
-    double *umat = nullptr, *E = nullptr, *dk_dev = nullptr;
-    int *uidx = nullptr, *dint_dev = nullptr;
+    UegPrepared s = ueg_prepare(prm, k_int_dev, st);
     try {
-        if (prm.mode == 1) {
-            // distinct momentum transfers d = k_r - k_p, with the float d_k of their first (p,r) pair
-            const int w4 = 4 * prm.imax + 1;
-            std::vector<int> index((size_t)w4 * w4 * w4, -1);
-            std::vector<double> dks;
-            std::vector<int> dints;
-            for (long p = 0; p < n; ++p)
-                for (long r = 0; r < n; ++r) {
-                    int d[3];
-                    for (int c = 0; c < 3; ++c) {
-                        d[c] = kint[3 * r + c] - kint[3 * p + c];
-                        if (d[c] < -2 * prm.imax || d[c] > 2 * prm.imax) throw std::runtime_error("ueg: k outside the index map");
-                    }
-                    int& slot = index[((size_t)(d[0] + 2 * prm.imax) * w4 + (d[1] + 2 * prm.imax)) * w4 + d[2] + 2 * prm.imax];
-                    if (slot < 0) {
-                        slot = (int)(dks.size() / 3);
-                        for (int c = 0; c < 3; ++c) dints.push_back(d[c]);
-                        for (int c = 0; c < 3; ++c)
-                            dks.push_back(((double)(kint[3 * r + c] * 2) * M_PI) / prm.L - ((double)(kint[3 * p + c] * 2) * M_PI) / prm.L);
-                    }
-                }
-            const int nd = (int)(dks.size() / 3);
-            umat = (double*)dmalloc(sizeof(double) * nd);
-            dk_dev = (double*)dmalloc(sizeof(double) * 3 * nd);
-            uidx = (int*)dmalloc(sizeof(int) * index.size());
-            dint_dev = (int*)dmalloc(sizeof(int) * 3 * nd);
-            HIP_CHECK(copy_async(dint_dev, dints.data(), sizeof(int) * 3 * nd, hipMemcpyHostToDevice, st));
-            HIP_CHECK(copy_async(dk_dev, dks.data(), sizeof(double) * 3 * nd, hipMemcpyHostToDevice, st));
-            HIP_CHECK(copy_async(uidx, index.data(), sizeof(int) * index.size(), hipMemcpyHostToDevice, st));
-            launch_kernel(ueg_nabla_kernel, dim3(nd), dim3(256), 0, st, u, dk_dev, dint_dev, umat);
-        } else if (prm.mode == 2) {
-            E = (double*)dmalloc(sizeof(double) * n * n);
-            launch_kernel(ueg_effective_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, st, u, k_int_dev, E);
-        }
-        fill(u, umat, uidx, E);
+        fill(s.u, s.umat, s.uidx, s.E);
         wait_idle(st);
     } catch (...) {
-        dfree(umat); dfree(E); dfree(dk_dev); dfree(uidx); dfree(dint_dev); dfree(tabs);
+        ueg_release(s);
         throw;
     }
-    dfree(umat); dfree(E); dfree(dk_dev); dfree(uidx); dfree(dint_dev); dfree(tabs);
+    ueg_release(s);
 }
 
 void ueg_two_body(const UegParams& prm, const int* k_int_dev, const int* index_map_dev, double* V_dev, stream_t s) {
@@ -471,6 +525,34 @@ void ueg_two_body_list(const UegParams& prm, const int* k_int_dev, const int* pq
         launch_kernel(ueg_list_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, u, k_int_dev, umat, uidx, E,
                       pqrs_dev, (long)count, out_dev);
     });
+}
+
+// A ladder term (include/pymes_amd.h, pymes_ueg_ladder_term_create): the prepared state of one Hamiltonian piece, kept until
+// ueg_ladder_term_free -- what pymes_sector_ladder_direct evaluates its V_abcd elements from.
+struct UegLadderTerm {
+    UegPrepared s;
+};
+UegLadderTerm* ueg_ladder_term_create(const UegParams& prm, const int* k_int_dev, stream_t s) {
+    if (!k_int_dev) throw std::runtime_error("ueg: null argument");
+    UegLadderTerm* t = new UegLadderTerm;
+    try {
+        t->s = ueg_prepare(prm, k_int_dev, (hipStream_t)s);
+    } catch (...) {
+        delete t;
+        throw;
+    }
+    return t;
+}
+void ueg_ladder_term_free(UegLadderTerm* t) {
+    if (!t) return;
+    ueg_release(t->s);
+    delete t;
+}
+void ueg_ladder_term_info(const UegLadderTerm* t, int64_t* bytes, int* n_p, double* L) {
+    if (!t) throw std::runtime_error("ueg: null ladder term");
+    if (bytes) *bytes = t->s.bytes;
+    if (n_p) *n_p = t->s.u.n_p;
+    if (L) *L = t->s.u.L;
 }
 
 }  // namespace dev

@@ -4,7 +4,8 @@
 // and the two-slab instantiation of the energy kernel for the Lambda-(T) (what the two share: DESIGN 8m); and the
 // bin sums, the fused V_abcd transfer sums and the gamma sums of the sector densities; and the per-target
 // preparation, the operand packing and the assembly of the sector IP- / EA-EOM-CCD sigma; and one Arnoldi step on a
-// device-resident basis for the sector spectral functions.
+// device-resident basis for the sector spectral functions; and the direct particle ladder, the ragged product with
+// V_abcd generated from ladder terms instead of read.
 // Included at the end of kernels.hip (one code object for the library), not compiled on its own.
 #include <hip/hip_runtime.h>
 
@@ -104,6 +105,130 @@ __global__ void __launch_bounds__(256) sector_gemm_kernel(const pymes_sector_tas
         double* out = C + t.c + gr * t.ldc + gc;
         const double v = __dmul_rn(t.alpha, acc[i]);       // (rounded on its own: the update is v + beta C, not an fma)
         *out = t.beta == 0.0 ? v : __dadd_rn(v, __dmul_rn(t.beta, *out));
+    }
+}
+
+// ---- the direct particle ladder (include/pymes_amd.h, pymes_sector_ladder_direct) ------------------------------------
+// sector_gemm_kernel with an A that is never read: A^t[(a,b),(c,d)] = sum_q coef_q w_q(a,b,c,d), w_q the element of ladder term q
+// (ueg_pair_element, kernels_integrals.hip: the body of ueg_list_kernel), generated panel by panel straight into LDS.  Rows and
+// columns are entries first[t] + r of the vv pair list (absolute orbital indices).  One workgroup takes a 32 x 32 tile: n = |OO_P|
+// is at most 27 for 54 electrons, so every element of A is generated once.  The tiles are found through the task table's tile0,
+// which counts 32 x 16 tiles: a workgroup whose number lies beyond the 32 x 32 tiles of its task leaves at once.
+constexpr int kLdBM = 32, kLdBN = 32, kLdBK = 64, kLdTerms = PYMES_SECTOR_LADDER_MAX_TERMS;
+struct LadderTerms {             // by value: the terms of one launch
+    int n;
+    double coef[kLdTerms];
+    UegK u[kLdTerms];
+    const double* umat[kLdTerms];
+    const int* uidx[kLdTerms];
+    const double* E[kLdTerms];
+};
+struct LadderPair { UegOrb x, y; };          // one entry of the vv pair list with the momenta of its two orbitals
+__device__ __forceinline__ LadderPair ladder_pair(const UegK& u, const int* __restrict__ vv_rows, const int* __restrict__ k_int,
+                                                  long row) {
+    LadderPair p;
+    p.x = ueg_orb(u, k_int, vv_rows[2 * row]);
+    p.y = ueg_orb(u, k_int, vv_rows[2 * row + 1]);
+    return p;
+}
+// B^t[k0 .. k0 + 64, col0 .. col0 + 32) into registers, read along n; 0 beyond k or n
+__device__ __forceinline__ void ladder_b_load(double (&b)[8], long k, long n, long ldb, const double* __restrict__ Bb, long col0,
+                                              long k0, int tid) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int idx = tid + 256 * i;
+        const long gk = k0 + (idx >> 5), gc = col0 + (idx & 31);
+        b[i] = (gk < k && gc < n) ? Bb[gk * ldb + gc] : 0.0;
+    }
+}
+
+// Every output element adds its k products in ascending order with fma from +0.0 and ends with the tail of sector_gemm_kernel:
+// for one term with coefficient 1 the bits of pymes_sector_gemm on the stored block.  Several terms are combined as
+// pymes_lincomb combines stored arenas (s = 0; s = s + w_q coef_q in ascending q, product and sum rounded one after the other:
+// whether lincomb_body contracts them does not matter for a coefficient that is a power of two, and a scaled stored arena was
+// rounded once already).  Per panel: the columns' momenta and the B panel (loaded one panel ahead into registers) go into
+// LDS; each thread generates 8 elements of its row (tid & 31) of A into LDS; then 64 steps of 2 rows x 2 columns per thread.
+// The float momenta 2 pi k / L are staged with the integer ones (the host checks that the terms share L), so an element costs
+// no global gather for modes 0 and 3, one u_mat lookup for mode 1 and two E lookups for mode 2.  No atomics; with beta == 0
+// the output is not read; nothing outside m, n, k is read or written.
+__global__ void __launch_bounds__(256) sector_ladder_direct_kernel(const pymes_sector_task* __restrict__ tasks, int ntask,
+                                                                   const long* __restrict__ first, const int* __restrict__ vv_rows,
+                                                                   const int* __restrict__ k_int, const LadderTerms T,
+                                                                   const double* __restrict__ B, double* C) {
+    __shared__ double As[kLdBK][kLdBM + 1];
+    __shared__ double Bs[kLdBK][kLdBN + 1];
+    __shared__ LadderPair cols[kLdBK];
+    const long tile = blockIdx.x;
+    int lo = 0, hi = ntask - 1;
+    while (lo < hi) {                                   // the last task that starts at or before this tile
+        const int mid = (lo + hi + 1) >> 1;
+        if (tasks[mid].tile0 <= tile) lo = mid; else hi = mid - 1;
+    }
+    // (the fields are read where they are needed, the four of the tail after the loop: the whole record held in scalar
+    // registers across the generation would not fit next to the terms' parameters)
+    const pymes_sector_task* __restrict__ tp = tasks + lo;
+    struct { long m, n, k, ldb, tile0; } t = {tp->m, tp->n, tp->k, tp->ldb, tp->tile0};
+    const long tiles_n = (t.n + kLdBN - 1) / kLdBN, tiles_m = (t.m + kLdBM - 1) / kLdBM, local = tile - t.tile0;
+    if (local < 0 || local >= tiles_m * tiles_n) return;
+    const long row0 = (local / tiles_n) * kLdBM, col0 = (local % tiles_n) * kLdBN, f0 = first[lo];
+    const bool ta = tp->flags & PYMES_SECTOR_TRANS_A;
+    const double* __restrict__ Bb = B + tp->b;
+    const int tid = threadIdx.x, tx = tid & 15, rg = (tid >> 4) * 2, grow = tid & 31, gk0 = tid >> 5;
+    const bool row_live = row0 + grow < t.m;
+    LadderPair rp;
+    if (row_live) rp = ladder_pair(T.u[0], vv_rows, k_int, f0 + row0 + grow);
+    double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+    double b[8];
+    if (t.k > 0) ladder_b_load(b, t.k, t.n, t.ldb, Bb, col0, 0, tid);
+    for (long k0 = 0; k0 < t.k; k0 += kLdBK) {
+        if (tid < kLdBK && k0 + tid < t.k) cols[tid] = ladder_pair(T.u[0], vv_rows, k_int, f0 + k0 + tid);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int idx = tid + 256 * i;
+            Bs[idx >> 5][idx & 31] = b[i];
+        }
+        __syncthreads();
+        if (k0 + kLdBK < t.k) ladder_b_load(b, t.k, t.n, t.ldb, Bb, col0, k0 + kLdBK, tid);
+#pragma unroll 1
+        for (int i = 0; i < 8; ++i) {
+            const int kk = gk0 + 8 * i;
+            double a = 0.0;
+            if (row_live && k0 + kk < t.k) {
+                const LadderPair cp = cols[kk];
+                const LadderPair& bra = ta ? cp : rp;
+                const LadderPair& ket = ta ? rp : cp;
+                for (int q = 0; q < T.n; ++q) {
+                    const double w = ueg_pair_element(T.u[q], T.umat[q], T.uidx[q], T.E[q], bra.x, bra.y, ket.x, ket.y);
+                    a = __dadd_rn(a, __dmul_rn(w, T.coef[q]));
+                }
+            }
+            As[kk][grow] = a;
+        }
+        __syncthreads();
+#pragma unroll 16
+        for (int kk = 0; kk < kLdBK; ++kk) {
+            const double b0 = Bs[kk][tx], b1 = Bs[kk][tx + 16], a0 = As[kk][rg], a1 = As[kk][rg + 1];
+            acc[0][0] = fma(a0, b0, acc[0][0]);
+            acc[0][1] = fma(a0, b1, acc[0][1]);
+            acc[1][0] = fma(a1, b0, acc[1][0]);
+            acc[1][1] = fma(a1, b1, acc[1][1]);
+        }
+        __syncthreads();
+    }
+    const long c0 = tp->c, ldc = tp->ldc;
+    const double alpha = tp->alpha, beta = tp->beta;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const long gr = row0 + rg + i;
+        if (gr >= t.m) continue;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const long gc = col0 + tx + 16 * j;
+            if (gc >= t.n) continue;
+            double* out = C + c0 + gr * ldc + gc;
+            const double v = __dmul_rn(alpha, acc[i][j]);      // (the tail of sector_gemm_kernel)
+            *out = beta == 0.0 ? v : __dadd_rn(v, __dmul_rn(beta, *out));
+        }
     }
 }
 
@@ -941,6 +1066,35 @@ void sector_gemm(const pymes_sector_task* tasks_dev, int ntask, int64_t ntiles, 
     if (ntask == 0 || ntiles == 0) return;
     if (!tasks_dev || !A || !B || !C) throw std::runtime_error("sector_gemm: null argument");
     launch_kernel(sector_gemm_kernel, dim3((unsigned)ntiles), dim3(256), 0, (hipStream_t)s, tasks_dev, ntask, A, B, C);
+}
+
+void sector_ladder_direct(const pymes_sector_task* tasks_dev, int ntask, int64_t ntiles, const int64_t* first_dev,
+                          const int32_t* vv_rows_dev, const int32_t* k_int_dev, int n_p, int nterms,
+                          const UegLadderTerm* const* terms, const double* coef_host, const double* B, double* C, stream_t s) {
+    const std::string who = "sector_ladder_direct";
+    if (ntask < 0 || ntiles < 0 || ntiles > 0x7fffffffL) throw std::runtime_error(who + ": bad task or tile count");
+    if (nterms < 1 || nterms > kLdTerms)
+        throw std::runtime_error(who + ": between 1 and " + std::to_string(kLdTerms) + " terms per call");
+    if (!terms || !coef_host) throw std::runtime_error(who + ": null argument");
+    LadderTerms T{};
+    T.n = nterms;
+    for (int q = 0; q < nterms; ++q) {
+        if (!terms[q]) throw std::runtime_error(who + ": null term");
+        const UegPrepared& p = terms[q]->s;
+        if (p.u.n_p != n_p) throw std::runtime_error(who + ": a term was made for another basis (" + std::to_string(p.u.n_p) +
+                                                     " orbitals, the call names " + std::to_string(n_p) + ")");
+        if (p.u.L != terms[0]->s.u.L) throw std::runtime_error(who + ": the terms were made for different box lengths");
+        if (!std::isfinite(coef_host[q])) throw std::runtime_error(who + ": a coefficient is not finite");
+        T.coef[q] = coef_host[q];
+        T.u[q] = p.u;
+        T.umat[q] = p.umat;
+        T.uidx[q] = p.uidx;
+        T.E[q] = p.E;
+    }
+    if (ntask == 0 || ntiles == 0) return;
+    if (!tasks_dev || !first_dev || !vv_rows_dev || !k_int_dev || !B || !C) throw std::runtime_error(who + ": null argument");
+    launch_kernel(sector_ladder_direct_kernel, dim3((unsigned)ntiles), dim3(256), 0, (hipStream_t)s, tasks_dev, ntask,
+                  reinterpret_cast<const long*>(first_dev), vv_rows_dev, k_int_dev, T, B, C);
 }
 
 void sector_gather(double* dst, int64_t n, double beta, double a1, const double* s1, const int64_t* m1, double a2, const double* s2,

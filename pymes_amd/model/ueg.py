@@ -317,13 +317,22 @@ class UEG:
                 tab_s, tab_a = self._correlator_tables(correlator, 30)
         prm_c = (C.c_double * 4)(*prm)
 
+        def bound(ctx):
+            return (ctx.handle, n_p, self.n_ele, self.imax, mode, float(self.L), float(self.k_cutoff or 0.0),
+                    float(self.gamma or 1.0), 30, kind, prm_c, k_int.ctypes.data_as(C.c_void_p),
+                    tab_s.ctypes.data_as(C.c_void_p) if tab_s is not None else None,
+                    tab_a.ctypes.data_as(C.c_void_p) if tab_a is not None else None, len(tab_a) if tab_a is not None else 0)
+
         def eval_list(ctx, pqrs_ptr, count, out_ptr):
-            ctx.lib.call("pymes_ueg_eval_2b_list", ctx.handle, n_p, self.n_ele, self.imax, mode, float(self.L),
-                         float(self.k_cutoff or 0.0), float(self.gamma or 1.0), 30, kind, prm_c,
-                         k_int.ctypes.data_as(C.c_void_p),
-                         tab_s.ctypes.data_as(C.c_void_p) if tab_s is not None else None,
-                         tab_a.ctypes.data_as(C.c_void_p) if tab_a is not None else None,
-                         len(tab_a) if tab_a is not None else 0, C.c_void_p(pqrs_ptr), count, C.c_void_p(out_ptr))
+            ctx.lib.call("pymes_ueg_eval_2b_list", *bound(ctx), C.c_void_p(pqrs_ptr), count, C.c_void_p(out_ptr))
+
+        def make_term(ctx):
+            """The same state kept on the device as a term of the direct ladder (``pymes_ueg_ladder_term_create``)."""
+            from pymes_amd.solver.ueg_cc import LadderTerm
+            handle = C.c_void_p()
+            ctx.lib.call("pymes_ueg_ladder_term_create", *bound(ctx), C.byref(handle))
+            return LadderTerm(ctx, handle, k_int)
+        eval_list.make_term = make_term
         return eval_list
 
     @contextlib.contextmanager
@@ -350,20 +359,26 @@ class UEG:
                 ctx.close()
             raise
 
-    def eval_2b_sectors(self, tables, correlator=None, is_rpa_approx=False, is_only_2b=False, is_effect_2b=False, ctx=None):
+    def eval_2b_sectors(self, tables, correlator=None, is_rpa_approx=False, is_only_2b=False, is_effect_2b=False, ctx=None,
+                        ladder="stored"):
         """The integral sectors of ``tables`` as ``SectorIntegrals`` (``ctx``: the context they live in; its own otherwise).
         Same modes and correlators as ``eval_2b_integrals``; is_effect_2b comes out already symmetrised (ueg.py:509-513).
         Momentum conservation is exact here: the few non-conserving elements the dense builder sets at some bases through
-        its flattened lookup (like the reference) do not exist on this path."""
+        its flattened lookup (like the reference) do not exist on this path.  ``ladder="direct"``: no ``abcd`` block is
+        listed, evaluated or stored -- the object carries one ladder term instead, from which the ladder product generates
+        the same elements."""
         from pymes_amd.solver.sectors import BLOCKS
         from pymes_amd.solver.ueg_cc import SectorIntegrals, upload_raw
         start_time = time.time()
+        if ladder not in ("stored", "direct"):
+            raise ValueError("eval_2b_sectors: ladder must be \"stored\" or \"direct\"")
         flags = dict(is_rpa_approx=is_rpa_approx, is_only_2b=is_only_2b, is_effect_2b=is_effect_2b)
         with self._sector_frame("eval_2b_sectors", tables, correlator, flags, ctx) as (ctx, own, eval_list):
-            ints = SectorIntegrals(ctx, tables, own_ctx=own)
+            terms = [(1.0, eval_list.make_term(ctx))] if ladder == "direct" else None
+            ints = SectorIntegrals(ctx, tables, own_ctx=own, ladder_terms=terms)
             pieces = []             # (name, first sector, end sector, items), in arena order
             for name in ints.NAMES:
-                if name not in BLOCKS:
+                if name not in BLOCKS or not ints.sizes[name]:        # (a list; or the ladder block of a direct object)
                     pieces.append((name, 0, 0, ints.sizes[name]))
                     continue
                 off, s0 = tables.block_offsets(name), 0

@@ -184,6 +184,13 @@ class SectorTables:
             idx = spec(r[:, 0] + shift(rows), r[:, 1] + shift(rows), c[:, 0] + shift(cols), c[:, 1] + shift(cols))
         return np.stack(idx, axis=1).astype(np.int32)
 
+    def ladder_rows(self):
+        """What the direct ladder (include/pymes_amd.h, pymes_sector_ladder_direct) reads in place of the ``abcd`` lists: the vv
+        pair list as absolute orbital indices (int32 [rows, 2], the order of ``vv_pairs``) and the first row of every pp
+        sector in it (int64, one per sector).  Element (r, c) of ``abcd`` sector s is <pq|rs> with (p,q) = rows[first[s] + r]
+        and (r,s) = rows[first[s] + c]."""
+        return (self.vv_pairs + self.no).astype(np.int32), self.vv_off[:-1].astype(np.int64)
+
     def conserving(self, pqrs):
         k = self.k_int
         return np.all(k[pqrs[:, 0]] + k[pqrs[:, 1]] == k[pqrs[:, 2]] + k[pqrs[:, 3]], axis=1)

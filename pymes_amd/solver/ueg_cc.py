@@ -12,7 +12,9 @@ On the same tables: the perturbative triples (``sector_triples_energy``, DESIGN 
 V_pqrs = V_rspq (the transcorrelated electron gas) the Lambda equations of CCD and DCD as the transposed Jacobian of that
 residual (``SectorLambda``) with the Lambda-(T) correction on top (``sector_lambda_triples_energy``); and from
 the amplitudes and their Lambda the response densities (``sector_density`` / ``SectorDensity``): the momentum
-distribution n(k), the expectation value of a second two-body operator, the transfer sums and the static structure factor S(q)."""
+distribution n(k), the expectation value of a second two-body operator, the transfer sums and the static structure factor S(q).
+The ladder block V_abcd is either stored like every other family or, for ``UEG.eval_2b_sectors(..., ladder="direct")``, generated
+inside the ladder product from ``LadderTerm`` objects (``SectorIntegrals.ladder``)."""
 import ctypes as C
 import os
 import time
@@ -29,8 +31,8 @@ from pymes_amd.solver.ccd import quiet_collector
 from pymes_amd.solver import ccsd_t
 from pymes_amd.solver.sectors import BLOCKS, FOCK_LISTS, SectorTables, TriplesTables
 
-__all__ = ["SectorTables", "SectorIntegrals", "SectorAmplitudes", "SectorCCD", "TriplesTables", "SectorTriplesIntegrals",
-           "sector_triples_energy", "SectorLambda", "sector_lambda_triples_energy", "SectorDensity", "sector_density",
+__all__ = ["SectorTables", "SectorIntegrals", "LadderTerm", "SectorAmplitudes", "SectorCCD", "TriplesTables",
+           "SectorTriplesIntegrals", "sector_triples_energy", "SectorLambda", "sector_lambda_triples_energy", "SectorDensity", "sector_density",
            "SectorIPEAHoist", "SectorIPEASigma", "SectorIP_EOM_CCD", "SectorEA_EOM_CCD", "SectorLadderIntegrals",
            "SectorSpectralFunction"]
 _EOM_NAMES = ("SectorIPEAHoist", "SectorIPEASigma", "SectorIP_EOM_CCD", "SectorEA_EOM_CCD", "SectorLadderIntegrals",
@@ -67,6 +69,7 @@ class Tasks:
         sectors.check_tasks(tasks, len_a, len_b, len_c)
         self.ctx, self.count, self.tiles = ctx, len(tasks), sectors.task_tiles(tasks)
         self.lens = (int(len_a), int(len_b), int(len_c))
+        self.extent = np.maximum(tasks["m"], tasks["k"]) if len(tasks) else np.zeros(0, dtype=np.int64)    # rows / columns of A
         self.dev = upload_raw(ctx, tasks.view(np.int64) if len(tasks) else np.zeros(14, dtype=np.int64))
 
     def run(self, A, B, Cm):
@@ -215,28 +218,79 @@ class DeviceTables:
         return dn
 
 
+class LadderTerm:
+    """One term of the direct particle ladder on the device (include/pymes_amd.h, pymes_ueg_ladder_term_create): what one
+    ``UEG.eval_2b_sectors(..., ladder="direct")`` call prepared instead of the ``abcd`` blocks.  Shared by the
+    ``SectorIntegrals`` that sum or scale it and freed with the last of them, or with the context."""
+
+    def __init__(self, ctx, handle, k_int):
+        self.ctx, self.handle, self.k_int = ctx, handle, np.array(k_int, dtype=np.int32)
+        nbytes = C.c_int64()
+        ctx.lib.call("pymes_ueg_ladder_term_bytes", ctx.handle, handle, C.byref(nbytes))
+        self.nbytes = int(nbytes.value)
+
+    def free(self):
+        if self.handle and self.ctx.handle:           # (a closed context has released its terms)
+            self.ctx.lib.call("pymes_ueg_ladder_term_free", self.ctx.handle, self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class SectorIntegrals:
     """The integral sectors of one Hamiltonian on the device: every block family of ``sectors.BLOCKS`` in the layout its
     product reads, plus the ``pipi`` / ``piip`` lists of the (diagonal) Fock matrix, in one arena.  Supports ``+`` and
-    scaling (the transcorrelated Hamiltonian is ``only_2b + effect_2b``)."""
+    scaling (the transcorrelated Hamiltonian is ``only_2b + effect_2b``).
+
+    ``ladder_terms``: a list of (coefficient, ``LadderTerm``) makes it a direct object: the ``abcd`` family has
+    size 0 and ``ladder`` evaluates V_abcd = sum coefficient * term inside the product.  ``+`` of two direct objects
+    concatenates their lists (at most ``MAX_LADDER_TERMS`` terms), ``*`` scales the coefficients."""
 
     NAMES = tuple(BLOCKS) + FOCK_LISTS
+    MAX_LADDER_TERMS = 4            # PYMES_SECTOR_LADDER_MAX_TERMS
 
-    def __init__(self, ctx, tables, arena=None, own_ctx=False):
+    def __init__(self, ctx, tables, arena=None, own_ctx=False, ladder_terms=None):
         self.ctx, self.tables, self._own = ctx, tables, own_ctx
+        self.ladder_terms = None if ladder_terms is None else self._checked_terms(ctx, tables, ladder_terms)
         sizes = [int(tables.block_offsets(nm)[-1]) if nm in BLOCKS else tables.n * tables.no for nm in self.NAMES]
+        if self.direct:
+            sizes[self.NAMES.index("abcd")] = 0
         self.offsets = dict(zip(self.NAMES, np.concatenate(([0], np.cumsum(sizes)))[:-1]))
         self.sizes = dict(zip(self.NAMES, sizes))
         self.total = int(sum(sizes))
         self.arena = ctx.empty((self.total,)) if arena is None else arena
         self._dev = None
+        self._ladder_dev = None
+
+    @classmethod
+    def _checked_terms(cls, ctx, tables, terms):
+        terms = [(float(c), t) for c, t in terms]
+        if not 1 <= len(terms) <= cls.MAX_LADDER_TERMS:
+            raise ValueError("SectorIntegrals: a direct ladder takes between 1 and %d terms, %d were given"
+                             % (cls.MAX_LADDER_TERMS, len(terms)))
+        for _, t in terms:
+            if not isinstance(t, LadderTerm) or t.ctx is not ctx or not t.handle:
+                raise ValueError("SectorIntegrals: a ladder term must be a live LadderTerm of the same context")
+            if t.k_int.shape != tables.k_int.shape or not np.array_equal(t.k_int, tables.k_int):
+                raise ValueError("SectorIntegrals: a ladder term was made for another basis (its k_int differs from the tables')")
+        return terms
+
+    @property
+    def direct(self):
+        return self.ladder_terms is not None
 
     def __getitem__(self, name):
         return view(self.arena, self.offsets[name], self.sizes[name])
 
     @property
     def nbytes(self):
-        return 8 * self.total
+        """Device bytes of the integrals: the arena, and for a direct object what its (distinct) ladder terms hold."""
+        terms = {id(t): t.nbytes for _, t in self.ladder_terms or ()}
+        return 8 * self.total + sum(terms.values())
 
     def device_tables(self):
         if self._dev is None:
@@ -244,19 +298,52 @@ class SectorIntegrals:
         return self._dev
 
     def _combine(self, terms):
-        out = SectorIntegrals(self.ctx, self.tables)
+        ladder = None
+        if self.direct:
+            ladder = [(c * lc, t) for obj, c in terms for lc, t in obj.ladder_terms]
+        out = SectorIntegrals(self.ctx, self.tables, ladder_terms=ladder)
         self.ctx.lincomb(out.arena, [t.arena for t, _ in terms], [c for _, c in terms])
         return out
 
     def __add__(self, other):
         if not isinstance(other, SectorIntegrals) or other.tables is not self.tables or other.ctx is not self.ctx:
             raise ValueError("SectorIntegrals: only integrals of the same tables and context can be added")
+        if self.direct != other.direct:
+            raise ValueError("SectorIntegrals: integrals with a direct ladder and integrals with a stored ladder cannot be "
+                             "added (evaluate both with the same ladder=)")
         return self._combine([(self, 1.0), (other, 1.0)])
 
     def __mul__(self, factor):
         return self._combine([(self, float(factor))])
 
     __rmul__ = __mul__
+
+    def ladder(self, tasks, X, Y):
+        """The particle-ladder product of a task table built on the (vv, vv) family -- ``DeviceTables.ladder`` or
+        ``adjoint().ladder_t`` --: Y^P = alpha op(V_abcd^P) X^P + beta Y^P.  A stored object reads its ``abcd`` blocks
+        (``pymes_sector_gemm``); a direct one generates them inside ``pymes_sector_ladder_direct``."""
+        if not self.direct:
+            tasks.run(self["abcd"], X, Y)
+            return
+        ctx, tab = self.ctx, self.tables
+        if ctx.recording:
+            raise RuntimeError("SectorIntegrals.ladder: the context is recording a launch graph (direct ladder)")
+        if self._ladder_dev is None:
+            rows, first = tab.ladder_rows()
+            if len(rows) and (rows.min() < tab.no or rows.max() >= tab.n):
+                raise AssertionError("sector tables: the vv pair list names an orbital that is no virtual")
+            self._ladder_dev = (upload_i32(ctx, rows), upload_raw(ctx, first if len(first) else np.zeros(1, dtype=np.int64)),
+                                upload_i32(ctx, tab.k_int), first, len(rows))
+        rows_dev, first_dev, k_dev, first, nrows = self._ladder_dev
+        if tasks.ctx is not ctx or tasks.count != len(first) or (len(first) and (first + tasks.extent).max() > nrows):
+            raise ValueError("SectorIntegrals.ladder: the task table is not one of the (vv, vv) family of these tables")
+        if X.size < tasks.lens[1] or Y.size < tasks.lens[2]:
+            raise ValueError("sector_ladder_direct: an operand is shorter than the task table was checked for")
+        coef = (C.c_double * len(self.ladder_terms))(*[c for c, _ in self.ladder_terms])
+        ctx.lib.call("pymes_sector_ladder_direct", ctx.handle, C.c_void_p(tasks.dev.ptr), tasks.count, tasks.tiles,
+                     C.c_void_p(first_dev.ptr), C.c_void_p(rows_dev.ptr), C.c_void_p(k_dev.ptr), tab.n,
+                     len(self.ladder_terms), _lib.ptr_array([t.handle.value for _, t in self.ladder_terms]), coef,
+                     C.c_void_p(X.ptr), C.c_void_p(Y.ptr))
 
     def hf_orbital_energies(self, kinetic):
         """The diagonal of ``hf.construct_hf_matrix`` (the Fock matrix is diagonal here): h_pp + sum_i (2 V_pipi - V_piip)."""
@@ -269,6 +356,13 @@ class SectorIntegrals:
     def close(self):
         if self._own and self.ctx.handle:
             self.ctx.close()
+
+
+def _refuse_direct_ea(who, ints, *options):
+    """The EA particle ladder reads V_abcd blocks of its own: not yet in direct form."""
+    if getattr(ints, "direct", False) and any(isinstance(o, dict) and len(o.get("ea") or ()) for o in options):
+        raise ValueError(who + ": the integrals carry a direct ladder, and the EA particle ladder reads stored V_abcd blocks: "
+                         "evaluate them with ladder=\"stored\" for 'ea' targets")
 
 
 class SectorAmplitudes:
@@ -542,7 +636,7 @@ class SectorCCD:
             hole = ws["I"].copy_from(hole)
             dt.hole_quad.run(ints["klcd"], T, hole)
         dt.hole.run(T, hole, R)
-        dt.ladder.run(ints["abcd"], T, R)
+        ints.ladder(dt.ladder, T, R)
         # direct and crossed layouts of T, and Tt = 2 D - C
         dt.layouts(T, D, Cx, Tt)
         dt.to_square.run(ints["w1"], Tt, sq)                     # X^q = W1^q Tt^{-q}
@@ -627,6 +721,7 @@ class SectorCCD:
         algo_name = "ccd.solve"
         time_ccd = time.time()
         eps = self._checks(eps, ints)
+        _refuse_direct_ea("SectorCCD.solve", ints, quasiparticles, spectral)
         if triples is not None:
             _check_triples("SectorCCD.solve", ints, triples)
         if lambda_triples is not None:
@@ -821,7 +916,7 @@ class SectorLambda:
         dt.cotangents(lam, yRd, yRc, yEd, yEc)
         # pp layout: G^P = eta^P + V_abcd^P^T lam^P + lam^P I^P^T + [CCD] V_klcd^P^T (T^P^T lam^P)
         Gp.copy_from(h["eta"])
-        at.ladder_t.run(ints["abcd"], lam, Gp)
+        ints.ladder(at.ladder_t, lam, Gp)
         at.hole_t.run(lam, h["hole"], Gp)
         if quad:
             at.t_lam.run(h["T"], lam, ws["M"])
@@ -1023,7 +1118,7 @@ class SectorDensity:
     def _lagrangian(self, eps, W):
         ctx, tab = self.ctx, self.tables
         ladder = ctx.zeros((max(tab.nnz, 1),))
-        self._dt.ladder.run(W["abcd"], self.T, ladder)
+        W.ladder(self._dt.ladder, self.T, ladder)
         live = [nm for nm in self.FAMILIES if self.sizes[nm]]
         xs, ys = [self[nm] for nm in live], [W[nm] for nm in live]
         if tab.nnz:

@@ -27,7 +27,7 @@ from pymes_amd.log import print_logging_info
 from pymes_amd.solver import sectors, subspace
 from pymes_amd.solver.ccd import quiet_collector
 from pymes_amd.solver.sectors import QuasiparticleTables, TriplesTables
-from pymes_amd.solver.ueg_cc import (SectorIntegrals, Tasks, _check_solver_inputs, _check_triples,
+from pymes_amd.solver.ueg_cc import (SectorIntegrals, Tasks, _check_solver_inputs, _check_triples, _refuse_direct_ea,
                                      _symmetric_compact, gather, hoist_amplitudes, upload_i32, upload_map, view)
 
 __all__ = ["SectorLadderIntegrals", "SectorIPEAHoist", "SectorIPEASigma", "SectorIP_EOM_CCD", "SectorEA_EOM_CCD",
@@ -161,6 +161,8 @@ class SectorIPEASigma:
             raise ValueError(who + ": kind must be 'ip' or 'ea'")
         if hoist is not None and (not isinstance(hoist, SectorIPEAHoist) or hoist.ints is not ints or hoist.tints is not tints):
             raise ValueError(who + ": the hoist belongs to other integrals")
+        if kind == "ea":
+            _refuse_direct_ea(who, ints, {"ea": [0]})
         self._own_hoist = hoist is None
         self.hoist = h = SectorIPEAHoist(eps, ints, tints, amps, who) if hoist is None else hoist
         tab, ctx = h.tables, h.ctx

@@ -193,6 +193,61 @@ def test_apply_many_gpu(gpu_lib, monkeypatch):
     check_apply_many(gpu_lib, monkeypatch, 6, 17, 4, 1e-10)
 
 
+def branch_handle(ctx, case):
+    """The right build's handle on the blocks of a tests/_eom_branch_cases.Case, its flags checked against numpy."""
+    from pymes_amd.solver.eom_ccsd import _Sigma
+    from tests import _eom_branch_cases as BC
+    case.upload(ctx, _Sigma.BLOCKS)
+    sig = _Sigma(ctx, case.f, ctx.array(case.t2))
+    assert BC.handle_flags(sig) == case.flags, (case.no, case.nv, case.break_)
+    return sig
+
+
+def test_sigma_branch_cases_can_fail():
+    """The oracle alone: every broken input of every lattice case moves sigma2 by more than 1e-4 of its size when it is
+    symmetrised, for a symmetric and for a general trial vector — no case passes on the wrong branch."""
+    from tests import _eom_branch_cases as BC
+    for no, nv in ((3, 5), (7, 6), (5, 2), (3, 4), (17, 4), (16, 3)):
+        for (want, brk) in BC.STATES:
+            case = BC.Case(no, nv, 7, brk)
+            assert case.flags == tuple(bool(x) for x in want)
+            u1s, u2s = BC.vectors(no, nv, 3, (True, False))
+            for u1, u2 in zip(u1s, u2s):
+                moved = BC.sensitivity(case, u1, u2)
+                assert set(moved) == set(brk)
+
+
+def test_sigma_branch_lattice_host_logic(hostsim_lib, monkeypatch):
+    """The seven (v_sym, t_sym, hole_sym) states of the sigma build (tests/_eom_branch_cases.py) through the host engine on the CPU
+    stand-in, k = 3 symmetric, general and mixed, declared and detected; the stand-in sets fused_ok = (nocc <= 3), so (3,5) runs
+    the fused side of every fork and (5,2) the other; then the batch boundaries at (3,4): k = 17, flushes of 8 + 1 and 8 + 8 + 1
+    deferred ladders, a mixed batch.  The same cases run on the kernels in tests/test_gpu_eom_branches.py.  The LEFT build has no
+    twin here: the stand-in has no lambda_assemble ("not available in this backend"), so its host logic runs on the GPU only."""
+    from pymes_amd.device import Context
+    from tests import _eom_branch_cases as BC
+    monkeypatch.setattr(_lib, "_default", hostsim_lib)
+    for no, nv in ((3, 5), (5, 2)):
+        for (want, brk), name in zip(BC.STATES, BC.STATE_IDS):
+            case = BC.Case(no, nv, 7, brk)
+            ctx = Context(no, nv)
+            try:
+                sig = branch_handle(ctx, case)
+                assert BC.handle_flags(sig) == tuple(bool(x) for x in want) and sig.fused_ok == (no <= 3)
+                BC.lattice_right(ctx, sig, case, label="(%d,%d) %s" % (no, nv, name))
+            finally:
+                ctx.close()
+    no, nv = 3, 4
+    for k, sy, brk in BC.BOUNDARY_RIGHT:
+        case = BC.Case(no, nv, 7, brk)
+        ctx = Context(no, nv)
+        try:
+            sig = branch_handle(ctx, case)
+            u1s, u2s = BC.vectors(no, nv, 100 + k, sy)
+            BC.check_right(ctx, sig, case, u1s, u2s, list(sy), BC.right_tol(no, nv), label="(3,4) %s" % ("+".join(brk) or "none"))
+        finally:
+            ctx.close()
+
+
 def test_product_host_logic(hostsim_lib, monkeypatch):
     run_product(hostsim_lib, monkeypatch)
 

@@ -15,7 +15,10 @@ Shapes (no, nv), nvirt tiny so that every array is at most 9 x 8100 doubles:
 1. every entry point at every shape, as a launch (``forced``) and as a recorded phase task (default switches, checked through
    ``phase_stats``), against numpy;  2. the boundary: the predicates and the refusals by name, without a leaked allocation;
 3. the engine at (90,2) — fused — and (91,2) — permutes, ladder_sym_unpack, assembly in separate passes — against the oracles,
-   phases on and off, with the branch that ran asserted.  Integrals come from eight density-fitting factors."""
+   phases on and off, with the branch that ran asserted.  Integrals come from eight density-fitting factors.
+3b. the sigma build's other branches on the same two contexts (tests/_eom_branch_cases.py): a symmetric vector — at 91 the packed
+   build that is not fused —, a handle over an unsymmetric T2 (t_sym = hole_sym = 0) with a symmetric and a general vector, two
+   symmetric vectors at 91 (vector by vector); the left build on an unsymmetric T2 at (88,2), the last nocc it admits."""
 import contextlib
 import functools
 import os
@@ -31,6 +34,7 @@ from oracle import slab_oracle as so
 from oracle.cases import synthetic_factors
 from pymes_amd import _lib
 from pymes_amd.device import Context
+from tests import _eom_branch_cases as BC
 from tests import test_gpu_loop_edges as LE
 from tests import test_gpu_sym_tail as ST
 from tests.test_gpu_sym_tail import env, forced, grid_energies, sym4
@@ -717,3 +721,134 @@ def test_eom_sigma_branch(engines, phase):
     assert a[4] and not b[4]
     if phase is None:
         assert fused_by_the_log(a[5]) and not fused_by_the_log(b[5])
+
+
+# ---- 3b. the other branches of the sigma build on both sides of the cap (tests/_eom_branch_cases.py; the lattice at small shapes:
+# tests/test_gpu_eom_branches.py).  eom_pass above runs a general vector on the all-symmetric handle only ---------------------------------
+@functools.lru_cache(maxsize=None)
+def branch_inputs(no):
+    """On the problem of ``engine_inputs(no, 2)``: two trial vectors WITH the exchange symmetry, T2 plus noise without it (a
+    handle with t_sym = hole_sym = 0 on the shared integrals), and the oracle's sigma for (amplitudes, vector) in
+    ("T", "sym0"), ("T", "sym1"), ("Tn", "sym0"), ("Tn", "gen") — "gen" is the general vector of engine_inputs —, once."""
+    from pymes_amd.solver.eom_ccsd import _Sigma
+    nv = 2
+    c = engine_inputs(no, nv)
+    rng = np.random.default_rng(11 * no + nv)
+    vec = {"gen": (c["u1"], c["u2"])}
+    for z in range(2):
+        vec["sym%d" % z] = (rng.standard_normal((nv, no)), 0.5 * sym4(rng, no, nv))       # (the size of the general one)
+    amp = {"T": c["t2"], "Tn": np.ascontiguousarray(c["t2"] + 0.02 * rng.standard_normal(c["t2"].shape))}
+    Vu = so.FactorBlocks(no, c["B"])
+    Vb = {k: Vu(k) for k in _Sigma.BLOCKS}
+    flags = {k: BC.expected_flags(no, Vb, t) for k, t in amp.items()}
+    assert flags == {"T": (True, True, True), "Tn": (True, False, False)}
+    sigma = {}
+    for a, v in (("T", "sym0"), ("T", "sym1"), ("Tn", "sym0"), ("Tn", "gen")):
+        u1, u2 = vec[v]
+        sigma[a, v] = (eo.sigma_singles(no, c["f"], Vb, u1, u2, amp[a]), eo.sigma_doubles(no, c["f"], Vb, u1, u2, amp[a]))
+    return dict(vec=vec, amp=amp, flags=flags, sigma=sigma)
+
+
+def branch_pass(engines, no, phase, amps, names):
+    """One ``apply_many`` of the named vectors (symmetry detected on the device) on a handle over the named amplitudes, into
+    NaN-filled arrays: ([(sigma1, sigma2)], the same vectors built one by one, the handle's flags, tasks recorded, task kinds);
+    past the cap, and at the cap (above PYMES_NOCC_MAX_LAMBDA), the left build on the handle must refuse by name."""
+    from pymes_amd.solver.lambda_ccsd import LeftSigma
+    key = ("branch", no, phase, amps, names)
+    if key not in engines.cache:
+        ctx, c, b = engines(no), engine_inputs(no, 2), branch_inputs(no)
+        nv = 2
+        with env(ctx, PYMES_PHASE=phase, PYMES_PHASE_MAX_US=None):
+            sig = LeftSigma(ctx, c["f"], ctx.array(b["amp"][amps]))
+            try:
+                d1, d2 = [ctx.array(b["vec"][n][0]) for n in names], [ctx.array(b["vec"][n][1]) for n in names]
+                o1 = [ctx.array(np.full((nv, no), np.nan)) for _ in names]
+                o2 = [ctx.array(np.full((nv, nv, no, no), np.nan)) for _ in names]
+                before = ctx.phase_stats()["tasks"]
+                kinds = set()
+                with task_kinds(ctx, phase, kinds):
+                    sig.apply_many(d1, d2, out1=o1, out2=o2)
+                    got = [(x.get(), y.get()) for x, y in zip(o1, o2)]
+                recorded = ctx.phase_stats()["tasks"] - before
+                single = [tuple(x.get() for x in sig.apply(d1[z], d2[z])) for z in range(len(names))]
+                l2 = ctx.array(b["vec"]["sym0"][1])
+                held = _live()
+                refusal = ("apply_left: nocc too large for the fused pair kernels" if no > limit("PYMES_NOCC_MAX_FUSED") else
+                           "lambda_assemble: nocc = %d is too large for the LDS tile" % no)
+                with pytest.raises(E, match=refusal):          # (into arrays of the caller: nothing is allocated on the way in)
+                    sig.apply_left_many([d1[0]], [l2], syms=[True], out1=[o1[0]], out2=[o2[0]])
+                assert _live() == held
+                engines.cache[key] = (got, single, BC.handle_flags(sig) + (sig.fused_ok, sig.many_ok), recorded, kinds)
+            finally:
+                sig.close()
+    return engines.cache[key]
+
+
+BRANCH_CASES = [("T", ("sym0",)), ("Tn", ("sym0",)), ("Tn", ("gen",))]
+BRANCH_IDS = ["T-sym", "Tn-sym", "Tn-general"]
+
+
+@pytest.mark.parametrize("phase", PHASES, ids=PHASE_IDS)
+@pytest.mark.parametrize("amps,names", BRANCH_CASES, ids=BRANCH_IDS)
+@pytest.mark.parametrize("no", [90, 91])
+def test_eom_sigma_branches_both_sides(engines, no, amps, names, phase):
+    """A trial vector WITH the exchange symmetry on the all-symmetric handle — at 91 the packed build that is not fused: a scaled
+    copy of Dx, the symmetrisation by permutes, the packed terms, ladder_sym_unpack —, and a symmetric and a general vector on
+    a handle over an unsymmetric T2 (t_sym = hole_sym = 0: the T . B5 term inside the symmetrisation, Bn without the held-back u1
+    term), against oracle/eom_oracle.py at the bounds of test_eom_sigma_both_sides, with the flags of the handle asserted."""
+    b = branch_inputs(no)
+    got, _, flags, recorded, kinds = branch_pass(engines, no, phase, amps, names)
+    fused = no == 90
+    assert flags == b["flags"][amps] + (fused, fused and amps == "T")
+    assert (recorded > 0) == (phase is None)
+    print("branch (%d,2) amplitudes %s vector %s %s: flags %s" % (no, amps, names[0], "phases" if phase is None else "PYMES_PHASE=0", flags))
+    for n, (s1, s2) in zip(names, got):
+        assert np.all(np.isfinite(s1)) and np.all(np.isfinite(s2))
+        assert close_to(s1, b["sigma"][amps, n][0], TOL)
+        assert close_to(s2, b["sigma"][amps, n][1], 10 * TOL)
+    if phase is None:
+        assert fused_by_the_log(kinds) == fused
+        if names == ("sym0",) and amps == "T":              # the packed rows are unpacked by a kernel of their own past the cap only
+            assert ("unpackL" in kinds) == (not fused)
+
+
+@pytest.mark.parametrize("phase", PHASES, ids=PHASE_IDS)
+def test_eom_sigma_two_symmetric_vectors_past_the_cap(engines, phase):
+    """k = 2 symmetric vectors at 91: many_ok is false, so the batch goes vector by vector — each result in its own array,
+    equal to the build of that vector alone (the same kernels in the same order: printed whether to the bit), at the oracle."""
+    no, names = 91, ("sym0", "sym1")
+    b = branch_inputs(no)
+    got, single, flags, _, _ = branch_pass(engines, no, phase, "T", names)
+    assert flags == (True, True, True, False, False)
+    print("branch (91,2) k = 2 symmetric vectors %s" % ("phases" if phase is None else "PYMES_PHASE=0"))
+    for n, (s1, s2), (t1_, t2_) in zip(names, got, single):
+        assert np.all(np.isfinite(s1)) and np.all(np.isfinite(s2))
+        assert close_to(s1, b["sigma"]["T", n][0], TOL)
+        assert close_to(s2, b["sigma"]["T", n][1], 10 * TOL)
+        print("   batch == single to the bit:", np.array_equal(s1, t1_) and np.array_equal(s2, t2_))
+        assert close_to(s1, t1_, TOL) and close_to(s2, t2_, 10 * TOL)
+    assert np.abs(got[0][1] - got[1][1]).max() > 1e-3
+
+
+def test_left_build_on_unsymmetric_T_at_the_lambda_cap(gpu_lib):
+    """The left build admits nocc <= PYMES_NOCC_MAX_LAMBDA = 88 < 90 (refused by name at 89 and 90: branch_pass above and
+    test_lambda_assemble_refuses_by_name), so its run on a handle with t_sym = hole_sym = 0 is at (88,2): k = 2, stacked and
+    one by one, against tests/_lambda_reference.left_sigma at the bound of tests/test_gpu_lambda.py."""
+    from pymes_amd.solver.lambda_ccsd import LeftSigma
+    no, nv = limit("PYMES_NOCC_MAX_LAMBDA"), 2
+    f, Vb, t2, l1, l2, _ = LE._apply_case(no, nv, False)
+    rng = np.random.default_rng(88)
+    case = BC.Case(no, nv, 0, ("t2",), problem=(f, Vb, np.ascontiguousarray(t2 + 0.02 * rng.standard_normal(t2.shape))))
+    assert case.flags == (True, False, False)
+    before = _live()
+    ctx = Context(no, nv, lib=gpu_lib)
+    try:
+        case.upload(ctx, LeftSigma.BLOCKS)
+        sig = LeftSigma(ctx, f, ctx.array(case.t2))
+        assert BC.handle_flags(sig) == case.flags and sig.fused_ok
+        l1s, l2s = [l1, rng.standard_normal(l1.shape)], [l2, sym4(rng, no, nv)]
+        assert BC.check_left(ctx, sig, case, l1s, l2s, None, BC.LEFT_TOL, label="(88,2) t2") <= BC.LEFT_TOL
+        sig.close()
+    finally:
+        ctx.close()
+    assert _live() == before

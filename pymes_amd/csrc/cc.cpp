@@ -942,29 +942,6 @@ void Engine::ladder_sym_multi(const double* const* xs, int k, double* L_all, boo
     }
 }
 
-void Engine::ladder_sym_adjoint(const double* x, double* LSp, double* LAp, bool dressed) {
-    refuse_if_sharded("ladder_sym_adjoint");
-    refuse_if_direct("ladder_sym_adjoint");
-    const PairDims d = pair_dims();
-    const int64_t o = no, v = nv, npp = d.npp, npm = d.npm, opp = d.opp, opm = d.opm, ldp = d.ldp, ldm = d.ldm;
-    if (ensure_ladder_pack(0, npp, dressed)) {
-        stats.permute_calls++;
-        stats.permute_bytes += 8.0 * 2.0 * double(npp) * double(v * v);
-    }
-    ArenaScope scope(arena);
-    // the summed pair (a,b) is the ROW index of V+ / V-: the antisymmetric half of x is packed by the same pairs P(a,b)
-    // (PACK_AM_PROWS; the rows of diagonal pairs are zero, as the rows of V- are)
-    double* Sp = arena.alloc(npp * ldp);
-    double* Am = arena.alloc(npp * ldm);
-    dev::ladder_pack_T(x, nullptr, Sp, Am, no, nv, dev::PACK_ROW_HALF | dev::PACK_AM_PROWS, ldp, ldm, stream);
-    stats.permute_calls++;
-    stats.permute_bytes += 8.0 * 2.0 * double(v * v * o * o);
-    contract(1.0, packed_rows(lpack_.Vp, npp, npp), "kr", pitched(Sp, npp, opp, ldp), "kn", 0.0,
-             slice(make_view(LSp, {npp, o * o}), 1, 0, opp), "rn");
-    if (opm > 0 && npm > 0)
-        contract(1.0, packed_rows(lpack_.Vm, npp, npm), "kr", pitched(Am, npp, opm, ldm), "kn", 0.0, make_view(LAp, {npm, opm}), "rn");
-}
-
 void Engine::ladder_sym_adjoint_multi(const double* const* xs, int k, double* LSp, double* LAp, bool dressed) {
     refuse_if_sharded("ladder_sym_adjoint_multi");
     refuse_if_direct("ladder_sym_adjoint_multi");
@@ -976,8 +953,9 @@ void Engine::ladder_sym_adjoint_multi(const double* const* xs, int k, double* LS
         stats.permute_bytes += 8.0 * 2.0 * double(npp) * double(v * v);
     }
     ArenaScope scope(arena);
-    // the packed halves of vector z in the columns [z ld, (z + 1) ld) of rows of pitch k ld (the pad columns zeroed: they go
-    // through the product as columns of their own)
+    // the summed pair (a,b) is the ROW index of V+ / V-: the antisymmetric half of x is packed by the same pairs P(a,b)
+    // (PACK_AM_PROWS; the rows of diagonal pairs are zero, as the rows of V- are).  The packed halves of vector z lie in the
+    // columns [z ld, (z + 1) ld) of rows of pitch k ld (the pad columns zeroed: they go through the product as columns of their own)
     double* Sp = arena.alloc(npp * K * ldp);
     double* Am = arena.alloc(npp * K * ldm);
     zero(make_view(Sp, {npp * K * ldp}));

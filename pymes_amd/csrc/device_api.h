@@ -384,8 +384,8 @@ void ipea_correction(int n, const double* const* sv, const double* const* rv, co
 // The product library only (the host simulator has no definition: weak ones in the engine throw).
 // Assembly of the left sigma from its partial results, one pass, one launch (one block per virtual pair a >= b and one for the
 // singles; o (o + 1) + 256 doubles of LDS, refused beyond 64 KB; no atomics, fixed summation order).  With raw_abij = D_abij + cd Pd[(a,i),(b,j)] + Px[(a,j),(b,i)] + cx Pd[(a,j),(b,i)]
-// (D [v,v,o,o]; Pd, Px [ov,ov]; all null: zero) and the pair-packed ladder halves (Engine::ladder_sym_adjoint; may be null): Lp
-// rows P(a,b) of length o^2 with LS in the first o(o+1)/2 columns, La [v(v-1)/2][o(o-1)/2] by strictly-lower pairs:
+// (D [v,v,o,o]; Pd, Px [ov,ov]; all null: zero) and the pair-packed ladder halves (Engine::ladder_sym_adjoint_multi; may be null): Lp
+// rows P(a,b) of pitch lp_ld with LS in the first o(o+1)/2 columns, La rows Q(a,b) of pitch la_ld with LA in the first o(o-1)/2, by strictly-lower pairs:
 //   s2_abij = (raw_abij + raw_baji) / 2 + LS[P(ab)][P(ij)] + sgn(a-b) sgn(i-j) LA[Q(ab)][Q(ij)],   s1 = S1 [v,o]
 // Vijab == null: out1 = s1, out2 = s2.  Otherwise the Lambda update with eta2_abij = 2 V_ijab[i,j,a,b] - V_ijab[i,j,b,a] read
 // from the stored [o,o,v,v] block and eta1 [v,o]:  res = eta + s;  out = lam - res / d (out may alias lam; lam1 = lam2 = null: zero);  err = -err_scale res / d,
@@ -400,7 +400,7 @@ struct LambdaParts {
     const double* lam1 = nullptr; const double* lam2 = nullptr;
     double* out1 = nullptr; double* out2 = nullptr; double* err1 = nullptr; double* err2 = nullptr;
     double* ws = nullptr; double* norm_dev = nullptr;
-    int64_t lp_ld = 0, la_ld = 0;      // row pitches of Lp / La (0: o^2 and o (o - 1) / 2); the stacked left build passes k vectors' halves side by side
+    int64_t lp_ld = 0, la_ld = 0;      // row pitches of Lp / La where given: the left build passes the halves of its k vectors side by side
 };
 int64_t lambda_assemble_ws_doubles(int nv);
 void lambda_assemble(const LambdaParts& q, int no, int nv, stream_t s);

@@ -246,17 +246,14 @@ class Engine {
     // the particle ladder of k exchange-symmetric vectors x_z [v,v,o,o] at once: L_all[z] (k consecutive [v(v+1)/2][o*o]
     // arrays) = pair-packed V_abcd . x_z, one batched launch per half (S / A) over all k vectors
     void ladder_sym_multi(const double* const* xs, int k, double* L_all, bool dressed);
-    // the ADJOINT of the particle ladder for an exchange-symmetric x: M_cdij = sum_ab V_abcd x_abij, pair-packed.  With
+    // the ADJOINT of the particle ladder for k >= 1 exchange-symmetric x_z: M_cdij = sum_ab V_abcd x_abij, pair-packed.  With
     // V_abcd = V_badc alone (no hermiticity) the packed rows of V^T are the packed rows of V transposed,
     //   (V^T)+[(cd),(ab)] = V_abcd + V_bacd = V+[(ab),(cd)],   (V^T)-[(cd),(ab)] = V-[(ab),(cd)],
     // so these are the two products of ladder_sym with the cached V+ / V- read through a transposed view: a quarter of the
-    // flops of the plain product whatever the integrals.  LS: rows P(c,d) of length o*o, the symmetric half in the first
-    // o(o+1)/2 columns (the layout of ladder_sym; the rest of a row is not written); LA [v(v-1)/2][o(o-1)/2]: the
-    // antisymmetric half by strictly-lower pairs Q(c,d).
-    void ladder_sym_adjoint(const double* x, double* LS, double* LA, bool dressed);
-    // ... for k vectors through ONE product per half: the packed operands side by side, vector z in the columns [z ldp, z ldp +
-    // opp) of rows of pitch k ldp (ldp = ladder_adjoint_pitch(true); the antisymmetric half alike with ldm).  LS [npp][k ldp],
-    // LA [max(npm,1)][k ldm]: the row of pair r for vector z starts at LS + r k ldp + z ldp
+    // flops of the plain product whatever the integrals.  ONE product per half for all k vectors: the packed operands side by
+    // side, vector z in the columns [z ldp, z ldp + opp) of rows of pitch k ldp (ldp = ladder_adjoint_pitch(true); the
+    // antisymmetric half, by strictly-lower pairs Q(c,d), alike with ldm).  LS [npp][k ldp], LA [max(npm,1)][k ldm] (not written
+    // when either extent is one): the row of pair r for vector z starts at LS + r k ldp + z ldp
     void ladder_sym_adjoint_multi(const double* const* xs, int k, double* LS, double* LA, bool dressed);
     PairDims pair_dims() const { return PairDims(no, nv); }
     int64_t ladder_adjoint_pitch(bool symmetric_half) const { return pair_dims().adjoint_pitch(symmetric_half); }

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <initializer_list>
+#include <optional>
 #include <string>
 
 namespace pymes {
@@ -598,20 +599,26 @@ void EomSigma::apply(int k, const double* const* u1, const double* const* u2, co
 // chain backwards with every product transposed — the same hoisted operands through transposed views, no new intermediate of
 // V and T.  The steps under the permutation P(ijab,jiba) (:377) see l2 + l2^T = 2 l2, the unpermuted ones (:380-383) l2; the
 // result is projected back onto the symmetric subspace by the assembly kernel.
-struct EomSigma::LeftParts {
+//
+// The partial results of A^T l for K >= 1 vectors — S1, D, Pd, Px stacked by vector, the packed ladder halves of the K vectors
+// side by side in rows of pitch K ld (Engine::ladder_sym_adjoint_multi) — and what dev::lambda_assemble reads of them, one
+// description per vector: the caller adds the coefficients, the outputs and, for a Lambda step, the operands of the update.
+struct EomSigma::LeftBuild {
+    const int64_t K, n1, n2;
+    const PairDims pd;
+    const bool la;                     // the antisymmetric ladder half exists
     Tmp S1, D, Pd, Px, Lp, La;
-    bool packed;
-    LeftParts(EomSigma& s, bool build)
-        : S1(s, build ? static_cast<int64_t>(s.nv) * s.no : 1), D(s, build ? static_cast<int64_t>(s.nv) * s.nv * s.no * s.no : 1),
-          Pd(s, build ? static_cast<int64_t>(s.nv) * s.nv * s.no * s.no : 1),
-          Px(s, build ? static_cast<int64_t>(s.nv) * s.nv * s.no * s.no : 1),
-          Lp(s, build && s.v_sym ? static_cast<int64_t>(s.nv) * (s.nv + 1) / 2 * s.no * s.no : 1),
-          La(s, build && s.v_sym ? std::max<int64_t>(static_cast<int64_t>(s.nv) * (s.nv - 1) / 2 * (s.no * (s.no - 1) / 2), 1) : 1),
-          packed(build && s.v_sym) {}
-    void fill(dev::LambdaParts& q) const {
-        q.D = D; q.Pd = Pd; q.Px = Px; q.S1 = S1;
-        q.Lp = packed ? Lp.p : nullptr;
-        q.La = packed ? La.p : nullptr;
+    std::vector<dev::LambdaParts> parts;
+    LeftBuild(EomSigma& s, int k)
+        : K(k), n1(static_cast<int64_t>(s.nv) * s.no), n2(n1 * n1), pd(s.no, s.nv), la(s.v_sym && s.no > 1 && s.nv > 1),
+          S1(s, K * n1), D(s, K * n2), Pd(s, K * n2), Px(s, K * n2), Lp(s, s.v_sym ? pd.npp * K * pd.adj_ldp : 1),
+          La(s, la ? pd.npm * K * pd.adj_ldm : 1), parts(static_cast<size_t>(k)) {
+        for (int64_t z = 0; z < K; ++z) {
+            dev::LambdaParts& q = parts[z];
+            q.S1 = S1.p + z * n1; q.D = D.p + z * n2; q.Pd = Pd.p + z * n2; q.Px = Px.p + z * n2;
+            if (s.v_sym) { q.Lp = Lp.p + z * pd.adj_ldp; q.lp_ld = K * pd.adj_ldp; }
+            if (la) { q.La = La.p + z * pd.adj_ldm; q.la_ld = K * pd.adj_ldm; }
+        }
     }
 };
 
@@ -633,69 +640,6 @@ void EomSigma::left_prepare() {
     left_ready = true;
 }
 
-void EomSigma::left_partials(const double* l1, const double* l2, LeftParts& w) {
-    const int64_t o = no, v = nv, ov = o * v, ov2 = ov * ov;
-    const Ops q{e};
-    const TView L1 = mv(l1, {v, o}), L2 = mv(l2, {v, v, o, o}), T4 = mv(T, {v, v, o, o});
-    const TView Vijab = V("ijab"), Vijka = V("ijka"), Vijak = V("ijak"), Viabc = V("iabc");
-    const TView S = mv(w.S1, {v, o}), D = mv(w.D, {v, v, o, o}), FOV = mv(fov, {o, v});
-    auto P4 = [&](const double* p) { return mv(p, {v, o, v, o}); };
-    // ---- singles() backwards: the l1 row of A^T ------------------------------------------------------------------------------------
-    q.C(1.0, mv(W1, {v, o, v, o}), "ckai", L1, "ai", 0.0, S, "ck");
-    q.C(1.0, mv(Gvv_s, {v, v}), "ac", L1, "ai", 1.0, S, "ci");
-    q.C(1.0, L1, "ai", mv(Goo_s, {o, o}), "ki", 1.0, S, "ak");
-    {
-        // the adjoint of ut = 2 u2 - u2^(ab): utb collects what singles() contracts ut with, then D = 2 utb - utb^(ab)
-        Tmp utb(*this, v * v * o * o);
-        const TView Ub = mv(utb, {v, v, o, o});
-        q.C(1.0, mv(fov, {o, v, 1}), "jbx", mv(l1, {1, v, o}), "xai", 0.0, Ub, "baji");          // (an outer product: K = 1)
-        q.C(-1.0, Vijka, "jkib", L1, "ai", 1.0, Ub, "abjk");
-        q.C(1.0, Viabc, "jabc", L1, "ai", 1.0, Ub, "bcji");
-        q.P(2.0, Ub, "abij", 0.0, D, "abij");
-        q.P(-1.0, Ub, "baij", 1.0, D, "abij");
-    }
-    // ---- doubles() backwards.  Pair layouts of l2 in one pass: ld[(a,i),(b,j)] = lx[(a,j),(b,i)] = l2_abij, and Q = ld + 2 lx as
-    // matrices — what Dx receives: 2 lx where it enters D, ld / 2 . 2 through the half of it that Dd carries ---------------------
-    Tmp ld(*this, ov2), lx(*this, ov2), Q(*this, ov2);
-    dev::t2_layouts(l2, ld, lx, Q, no, nv, e.stream, 1.0, 2.0);
-    Tmp Xoo(*this, o * o), Xvv(*this, v * v), Bn(*this, o * o * o * o);
-    const TView XooV = mv(Xoo, {o, o}), XvvV = mv(Xvv, {v, v}), BnV = mv(Bn, {o, o, o, o});
-    // the terms that wrote D (:334-361): their operand against 2 l2
-    q.C(2.0, L2, "abij", T4, "cbij", 0.0, XvvV, "ac");
-    q.C(2.0, mv(WW, {v, v, o, v}), "abid", L2, "abij", 1.0, S, "dj");
-    q.C(2.0, mv(Gvv, {v, v}), "ad", L2, "abij", 1.0, D, "dbij");
-    q.C(2.0, mv(Goo, {o, o}), "li", L2, "abij", 1.0, D, "ablj", "ab");
-    q.C(2.0, L2, "abij", mv(A3, {o, o, v, o}), "libj", 1.0, S, "al");
-    q.C(2.0, L2, "abij", mv(A4, {o, o, v, o}), "liaj", 1.0, S, "bl");
-    q.C(-2.0, L2, "abij", mv(A6, {o, v, o, o}), "laji", 1.0, S, "bl");
-    q.C(-2.0, L2, "abij", V("iajk"), "kbij", 1.0, S, "ak");
-    // T . B5 (:338) and T . Bn (:381) share Bn^ = T^T l2
-    q.C(1.0, T4, "abkl", L2, "abij", 0.0, BnV, "klij");
-    q.C(2.0, Vijka, "klid", BnV, "klij", 1.0, S, "dj");
-    // the two (ov)^3 products, transposed: Pd = M12^T ld (the adjoint of utd, which enters as 2 Pd - Pd^(ab): cd, cx of the
-    // assembly), Px = MDU^T Q
-    q.C(1.0, P4(M12), "aidl", P4(ld), "aibj", 0.0, P4(w.Pd), "dlbj");
-    q.C(2.0, P4(Td), "akbj", P4(ld), "aibj", 0.0, XooV, "ki");
-    q.C(1.0, P4(MDU), "ajdl", P4(Q), "ajbi", 0.0, P4(w.Px), "dlbi");
-    // one-index dressings backwards
-    q.C(-2.0, Vijka, "klid", XooV, "ki", 1.0, S, "dl");
-    q.C(1.0, Vijak, "kldi", XooV, "ki", 1.0, S, "dl");
-    q.C(-1.0, FOV, "kd", XooV, "ki", 1.0, S, "di");
-    q.C(1.0, mv(Aoo, {o, v, o, v}), "kdlc", XooV, "ki", 1.0, P4(w.Px), "dlci");
-    q.C(2.0, Viabc, "ladc", XvvV, "ac", 1.0, S, "dl");
-    q.C(-1.0, Viabc, "lacd", XvvV, "ac", 1.0, S, "dl");
-    q.C(-1.0, XvvV, "ac", FOV, "lc", 1.0, S, "al");
-    q.C(1.0, XvvV, "ac", slice(mv(BB, {o, v, o, v + o}), 3, 0, v), "kdlc", 1.0, P4(w.Px), "akdl");
-    // ---- the unpermuted terms (:380-383) against l2 ----------------------------------------------------------------------------------
-    q.C(1.0, L2, "abij", mv(B2, {o, o, o, o}), "klij", 1.0, D, "abkl");
-    q.C(1.0, Vijab, "kldc", BnV, "klij", 1.0, D, "dcij");
-    // the particle ladder backwards: sum_ab V_abcd l2_abij.  With V_abcd = V_badc (every Hamiltonian the package is fed; no
-    // hermiticity needed) the packed rows V+ / V- of the right build are read in the other orientation — a quarter of the flops
-    // of the plain product, for dressed and transcorrelated blocks alike
-    if (w.packed) e.ladder_sym_adjoint(l2, w.Lp, w.La, dressed);
-    else q.C(1.0, V("abcd"), "abcd", L2, "abij", 1.0, D, "cdij");
-}
-
 void EomSigma::apply_left(int k, const double* const* l1, const double* const* l2, const int* sym, double* const* o1,
                           double* const* o2) {
     if (k < 1) return;
@@ -706,66 +650,79 @@ void EomSigma::apply_left(int k, const double* const* l1, const double* const* l
         if (!(sym && sym[z]) && !exchange_symmetric(l2[z], nv, no))
             throw Error("eom sigma apply_left: the left doubles do not have the exchange symmetry l2_abij = l2_baji");
     left_prepare();
-    auto one = [&](int z) {
-        LeftParts w(*this, true);
-        left_partials(l1[z], l2[z], w);
-        dev::LambdaParts q;
-        w.fill(q);
-        q.cd = 2.0; q.cx = -1.0;
-        q.out1 = o1[z]; q.out2 = o2[z];
-        dev::lambda_assemble(q, no, nv, e.stream);
+    auto build = [&](int lo, int hi) {
+        LeftBuild w(*this, hi - lo);
+        left_build(l1 + lo, l2 + lo, w);
+        for (int z = lo; z < hi; ++z) {
+            dev::LambdaParts& q = w.parts[z - lo];
+            q.cd = 2.0; q.cx = -1.0;
+            q.out1 = o1[z]; q.out2 = o2[z];
+            dev::lambda_assemble(q, no, nv, e.stream);
+        }
     };
-    if (k < 2) { one(0); return; }
-    const int step = stack_limit();
+    const int step = k > 1 ? stack_limit() : 1;
     for (int lo = 0; lo < k; lo += step) {
         const int hi = std::min(k, lo + step);
-        if (hi - lo < 2) { one(lo); continue; }
         try {
-            left_stack(hi - lo, l1 + lo, l2 + lo, o1 + lo, o2 + lo);
+            build(lo, hi);
         } catch (const Error& err) {
-            if (std::string(err.what()).find("memory") == std::string::npos) throw;
+            if (hi - lo < 2 || std::string(err.what()).find("memory") == std::string::npos) throw;
             trim();                    // out of device memory in the middle of a stacked build: one vector at a time
-            for (int z = lo; z < hi; ++z) one(z);
+            for (int z = lo; z < hi; ++z) build(z, z + 1);
         }
     }
 }
 
-// ---- A^T l for k left vectors at once: left_partials() with a leading vector index on every vector-dependent operand, so that
-// every hoisted operand and every V+ / V- row is read once per call.  The two (ov)^3 products run transposed — PdT[z] = ld_z M12,
-// PxT[z] = Q_z MDU with the k symmetric pair matrices stacked along the rows: ONE GEMM each — which the assembly does not see:
-// it reads Pd and Px only through raw_abij + raw_baji, the sum of an element and its transpose.  The packed ladder halves of the
-// k vectors lie side by side in the columns of one product per half (Engine::ladder_sym_adjoint_multi).
-void EomSigma::left_stack(int k, const double* const* l1, const double* const* l2, double* const* o1, double* const* o2) {
-    const int64_t o = no, v = nv, ov = o * v, ov2 = ov * ov, K = k, n1 = v * o, n2 = v * v * o * o;
+// ---- the partial results of A^T l for the K = w.K left vectors l1[z], l2[z]: every vector-dependent operand carries a leading
+// vector index, so that every hoisted operand and every V+ / V- row is read once per call.  A stack of one is the caller's vector,
+// read in place.  The two (ov)^3 products run transposed — PdT[z] = ld_z M12, PxT[z] = Q_z MDU with the K symmetric pair matrices
+// stacked along the rows: ONE GEMM each — which the assembly does not see: it reads Pd and Px only through raw_abij + raw_baji,
+// the sum of an element and its transpose.  For the same reason every term of Px may lie either way: the two small products that
+// add into it are placed the way their GEMM writes them, without a copy for any K.  The packed ladder halves of the K vectors
+// lie side by side in the columns of one product per half (Engine::ladder_sym_adjoint_multi).
+void EomSigma::left_build(const double* const* l1, const double* const* l2, LeftBuild& w) {
+    const int64_t o = no, v = nv, ov = o * v, ov2 = ov * ov, K = w.K, n1 = w.n1, n2 = w.n2;
+    const int k = static_cast<int>(K);
     const Ops q{e};
-    Tmp L1S(*this, K * n1), L2S(*this, K * n2), S1(*this, K * n1), Dd(*this, K * n2), Pd(*this, K * ov2), Px(*this, K * ov2);
+    std::optional<Tmp> L1S, L2S;
+    if (k > 1) {
+        L1S.emplace(*this, K * n1);
+        L2S.emplace(*this, K * n2);
+    }
+    const double *l1s = k > 1 ? L1S->p : l1[0], *l2s = k > 1 ? L2S->p : l2[0];
+    // Pair layouts of l2 in one pass: ld[(a,i),(b,j)] = lx[(a,j),(b,i)] = l2_abij, and Q = ld + 2 lx as matrices — what Dx
+    // receives: 2 lx where it enters D, ld / 2 . 2 through the half of it that Dd carries
     Tmp ld(*this, K * ov2), lx(*this, K * ov2), Q(*this, K * ov2);
     for (int z = 0; z < k; ++z) {
-        dev::memcpy_d2d(L1S.p + z * n1, l1[z], sizeof(double) * n1, e.stream);
-        dev::memcpy_d2d(L2S.p + z * n2, l2[z], sizeof(double) * n2, e.stream);
+        if (k > 1) {
+            dev::memcpy_d2d(L1S->p + z * n1, l1[z], sizeof(double) * n1, e.stream);
+            dev::memcpy_d2d(L2S->p + z * n2, l2[z], sizeof(double) * n2, e.stream);
+        }
         dev::t2_layouts(l2[z], ld.p + z * ov2, lx.p + z * ov2, Q.p + z * ov2, no, nv, e.stream, 1.0, 2.0);
     }
-    const TView L1 = mv(L1S, {K, v, o}), L2 = mv(L2S, {K, v, v, o, o}), T4 = mv(T, {v, v, o, o});
+    const TView L1 = mv(l1s, {K, v, o}), L2 = mv(l2s, {K, v, v, o, o}), T4 = mv(T, {v, v, o, o});
     const TView Vijab = V("ijab"), Vijka = V("ijka"), Vijak = V("ijak"), Viabc = V("iabc");
-    const TView S = mv(S1, {K, v, o}), D = mv(Dd, {K, v, v, o, o}), FOV = mv(fov, {o, v});
+    const TView S = mv(w.S1, {K, v, o}), D = mv(w.D, {K, v, v, o, o}), FOV = mv(fov, {o, v});
     auto P4 = [&](const double* p) { return mv(p, {v, o, v, o}); };
     auto P5 = [&](const double* p) { return mv(p, {K, v, o, v, o}); };
-    // ---- singles() backwards ------------------------------------------------------------------------------------------------------
+    // ---- singles() backwards: the l1 row of A^T ------------------------------------------------------------------------------------
     q.C(1.0, mv(W1, {v, o, v, o}), "ckai", L1, "zai", 0.0, S, "zck");
     q.C(1.0, mv(Gvv_s, {v, v}), "ac", L1, "zai", 1.0, S, "zci");
     q.C(1.0, L1, "zai", mv(Goo_s, {o, o}), "ki", 1.0, S, "zak");
     {
+        // the adjoint of ut = 2 u2 - u2^(ab): utb collects what singles() contracts ut with, then D = 2 utb - utb^(ab)
         Tmp utb(*this, K * n2);
         const TView Ub = mv(utb, {K, v, v, o, o});
-        q.C(1.0, mv(fov, {o, v, 1}), "jbx", mv(L1S, {K, 1, v, o}), "zxai", 0.0, Ub, "zbaji");
+        q.C(1.0, mv(fov, {o, v, 1}), "jbx", mv(l1s, {K, 1, v, o}), "zxai", 0.0, Ub, "zbaji");   // (an outer product: K = 1)
         q.C(-1.0, Vijka, "jkib", L1, "zai", 1.0, Ub, "zabjk");
         q.C(1.0, Viabc, "jabc", L1, "zai", 1.0, Ub, "zbcji");
         q.P(2.0, Ub, "zabij", 0.0, D, "zabij");
         q.P(-1.0, Ub, "zbaij", 1.0, D, "zabij");
     }
-    // ---- doubles() backwards --------------------------------------------------------------------------------------------------------
+    // ---- doubles() backwards ---------------------------------------------------------------------------------------------------------
     Tmp Xoo(*this, K * o * o), Xvv(*this, K * v * v), Bn(*this, K * o * o * o * o);
     const TView XooV = mv(Xoo, {K, o, o}), XvvV = mv(Xvv, {K, v, v}), BnV = mv(Bn, {K, o, o, o, o});
+    // the terms that wrote D (:334-361): their operand against 2 l2
     q.C(2.0, L2, "zabij", T4, "cbij", 0.0, XvvV, "zac");
     q.C(2.0, mv(WW, {v, v, o, v}), "abid", L2, "zabij", 1.0, S, "zdj");
     q.C(2.0, mv(Gvv, {v, v}), "ad", L2, "zabij", 1.0, D, "zdbij", "z");
@@ -774,38 +731,31 @@ void EomSigma::left_stack(int k, const double* const* l1, const double* const* l
     q.C(2.0, L2, "zabij", mv(A4, {o, o, v, o}), "liaj", 1.0, S, "zbl");
     q.C(-2.0, L2, "zabij", mv(A6, {o, v, o, o}), "laji", 1.0, S, "zbl");
     q.C(-2.0, L2, "zabij", V("iajk"), "kbij", 1.0, S, "zak");
+    // T . B5 (:338) and T . Bn (:381) share Bn^ = T^T l2
     q.C(1.0, T4, "abkl", L2, "zabij", 0.0, BnV, "zklij");
     q.C(2.0, Vijka, "klid", BnV, "zklij", 1.0, S, "zdj");
-    q.C(1.0, P5(ld), "zbjai", P4(M12), "aidl", 0.0, P5(Pd), "zbjdl");                   // (M12^T ld_z)^T, all z: one GEMM
+    // the two (ov)^3 products: Pd = M12^T ld (the adjoint of utd, which enters as 2 Pd - Pd^(ab): cd, cx of the assembly),
+    // Px = MDU^T Q, both held transposed
+    q.C(1.0, P5(ld), "zbjai", P4(M12), "aidl", 0.0, P5(w.Pd), "zbjdl");                 // (M12^T ld_z)^T, all z: one GEMM
     q.C(2.0, P4(Td), "akbj", P5(ld), "zaibj", 0.0, XooV, "zki");
-    q.C(1.0, P5(Q), "zbiaj", P4(MDU), "ajdl", 0.0, P5(Px), "zbidl");                    // (MDU^T Q_z)^T, all z: one GEMM
+    q.C(1.0, P5(Q), "zbiaj", P4(MDU), "ajdl", 0.0, P5(w.Px), "zbidl");                  // (MDU^T Q_z)^T, all z: one GEMM
+    // one-index dressings backwards
     q.C(-2.0, Vijka, "klid", XooV, "zki", 1.0, S, "zdl");
     q.C(1.0, Vijak, "kldi", XooV, "zki", 1.0, S, "zdl");
     q.C(-1.0, FOV, "kd", XooV, "zki", 1.0, S, "zdi");
-    q.C(1.0, mv(Aoo, {o, v, o, v}), "kdlc", XooV, "zki", 1.0, P5(Px), "zcidl");         // (into the transposed Px)
+    q.C(1.0, mv(Aoo, {o, v, o, v}), "kdlc", XooV, "zki", 1.0, P5(w.Px), "zdlci", "z");
     q.C(2.0, Viabc, "ladc", XvvV, "zac", 1.0, S, "zdl");
     q.C(-1.0, Viabc, "lacd", XvvV, "zac", 1.0, S, "zdl");
     q.C(-1.0, XvvV, "zac", FOV, "lc", 1.0, S, "zal");
-    q.C(1.0, XvvV, "zac", slice(mv(BB, {o, v, o, v + o}), 3, 0, v), "kdlc", 1.0, P5(Px), "zdlak");
+    q.C(1.0, XvvV, "zac", slice(mv(BB, {o, v, o, v + o}), 3, 0, v), "kdlc", 1.0, P5(w.Px), "zakdl");
+    // ---- the unpermuted terms (:380-383) against l2 ----------------------------------------------------------------------------------
     q.C(1.0, L2, "zabij", mv(B2, {o, o, o, o}), "klij", 1.0, D, "zabkl");
     q.C(1.0, Vijab, "kldc", BnV, "zklij", 1.0, D, "zdcij");
-    const PairDims pd = e.pair_dims();
-    const int64_t npp = pd.npp, npm = std::max<int64_t>(pd.npm, 1), ldp = pd.adj_ldp, ldm = pd.adj_ldm;
-    const bool la = v_sym && o > 1 && v > 1;
-    Tmp Lp(*this, v_sym ? npp * K * ldp : 1), La(*this, la ? npm * K * ldm : 1);
-    if (v_sym) e.ladder_sym_adjoint_multi(l2, k, Lp, La, dressed);
+    // the particle ladder backwards: sum_ab V_abcd l2_abij.  With V_abcd = V_badc (every Hamiltonian the package is fed; no
+    // hermiticity needed) the packed rows V+ / V- of the right build are read in the other orientation — a quarter of the flops
+    // of the plain product, for dressed and transcorrelated blocks alike
+    if (v_sym) e.ladder_sym_adjoint_multi(l2, k, w.Lp, w.La, dressed);
     else q.C(1.0, V("abcd"), "abcd", L2, "zabij", 1.0, D, "zcdij");
-    for (int z = 0; z < k; ++z) {
-        dev::LambdaParts w;
-        w.D = Dd.p + z * n2; w.Pd = Pd.p + z * ov2; w.Px = Px.p + z * ov2; w.S1 = S1.p + z * n1;
-        if (v_sym) {
-            w.Lp = Lp.p + z * ldp; w.lp_ld = K * ldp;
-            if (la) { w.La = La.p + z * ldm; w.la_ld = K * ldm; }
-        }
-        w.cd = 2.0; w.cx = -1.0;
-        w.out1 = o1[z]; w.out2 = o2[z];
-        dev::lambda_assemble(w, no, nv, e.stream);
-    }
 }
 
 double EomSigma::lambda_step(const double* lam1, const double* lam2, const double* eo_host, const double* ev_host, double shift,
@@ -826,14 +776,15 @@ double EomSigma::lambda_step(const double* lam1, const double* lam2, const doubl
         dev::stream_sync(e.stream);
         eps_host_ = eps;
     }
-    LeftParts w(*this, !start);
-    if (!start) left_partials(lam1, lam2, w);
-    Tmp ws(*this, dev::lambda_assemble_ws_doubles(nv)), nrm(*this, 32);
+    std::optional<LeftBuild> w;
     dev::LambdaParts q;
     if (!start) {                          // (start: lambda = 0, no partial results: out = -eta / d, nothing is read)
-        w.fill(q);
+        w.emplace(*this, 1);
+        left_build(&lam1, &lam2, *w);
+        q = w->parts[0];
         q.lam1 = lam1; q.lam2 = lam2;
     }
+    Tmp ws(*this, dev::lambda_assemble_ws_doubles(nv)), nrm(*this, 32);
     q.cd = 2.0; q.cx = -1.0;
     q.Vijab = V("ijab").p; q.eta1 = eta1; q.eo = eps_dev; q.ev = eps_dev + no; q.shift = shift; q.err_scale = err_scale;
     q.out1 = out1; q.out2 = out2; q.err1 = err1; q.err2 = err2; q.ws = ws; q.norm_dev = nrm;

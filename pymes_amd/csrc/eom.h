@@ -32,8 +32,8 @@ class EomSigma {
     // ---- the adjoint build: o = A^T l for the sigma A of apply() under the plain inner product over both arrays, on
     // the exchange-symmetric subspace, from the SAME hoisted intermediates read through transposed operand views.  l2[z] must
     // have the exchange symmetry (sym[z] != 0: the caller knows; else tested here, one reduction and a synchronisation; refused
-    // by name otherwise).  k > 1 vectors go through every product stacked (left_stack: one GEMM per large product), k = 1 through
-    // the single-vector path.  apply() is not affected: nothing it reads is written.
+    // by name otherwise).  The k vectors go through every product stacked (left_build: one GEMM per large product); k = 1 is a
+    // stack of one, read in place.  apply() is not affected: nothing it reads is written.
     void apply_left(int k, const double* const* l1, const double* const* l2, const int* sym, double* const* o1,
                     double* const* o2);
     // One Lambda iteration for eta1[a,i] = 2 f_ov[i,a], eta2[a,b,i,j] = 2 V_ijab[i,j,a,b] - V_ijab[i,j,b,a] (read from the block):
@@ -66,9 +66,8 @@ class EomSigma {
     bool left_ready = false;
     void left_check() const;
     void left_prepare();
-    struct LeftParts;
-    void left_partials(const double* l1, const double* l2, LeftParts& w);
-    void left_stack(int k, const double* const* l1, const double* const* l2, double* const* o1, double* const* o2);
+    struct LeftBuild;                 // the partial results of K vectors and their K descriptions for the assembly
+    void left_build(const double* const* l1, const double* const* l2, LeftBuild& w);
     void general_operands();          // LK3, LK2 (trial vectors without exchange symmetry), on first use
     bool v_sym = false, t_sym = false, hole_sym = false, fused_ok = false, many_ok = false;
     TView V(const char* name) const;

@@ -711,7 +711,7 @@ namespace {
 // fastest index, the o x o tile in LDS carries the transposition), one extra block for the singles.  With
 //   raw_abij = D_abij + cd Pd[(a,i),(b,j)] + Px[(a,j),(b,i)] + cx Pd[(a,j),(b,i)]
 // the left sigma is  s2_abij = (raw_abij + raw_baji) / 2 + LS[P(ab)][P(ij)] + sgn(a-b) sgn(i-j) LA[Q(ab)][Q(ij)],  s1 = S1 (LS in
-// the rows Lp of length o^2, LA dense by strictly-lower pairs: the two halves of the packed ladder adjoint).  Without V_ijab that is what is written
+// the rows Lp of pitch lp_ld, LA by strictly-lower pairs in rows of pitch la_ld: the two halves of the packed ladder adjoint).  Without V_ijab that is what is written
 // (out1, out2).  With it the block goes on to the Lambda update: eta2_abij = 2 V[i,j,a,b] - V[i,j,b,a] read from the stored
 // [o,o,v,v] block (a strided gather of two numbers per element, both index orders from the same two loads),
 //   res = eta + s,  out = lam - res / d,  err = -es res / d,  d2 = ev[a] + ev[b] - eo[i] - eo[j] - shift,  d1 = ev[a] - eo[i] - shift
@@ -723,7 +723,7 @@ struct LambdaK {
     const double* lam1; const double* lam2;
     double* out1; double* out2; double* err1; double* err2; double* ws;
     double cd, cx, shift, es;
-    long lp_ld, la_ld;          // row pitches of Lp / La (o^2 and o (o - 1) / 2 unless the ladder halves of k vectors lie side by side)
+    long lp_ld, la_ld;          // row pitches of Lp / La (the ladder halves of k >= 1 vectors lie side by side)
     int no, nv;
 };
 
@@ -1004,7 +1004,7 @@ void lambda_assemble(const LambdaParts& q, int no, int nv, stream_t s) {
     if (!q.out1 || !q.out2) throw std::runtime_error("lambda_assemble: null output");
     if (q.D && (!q.Pd || !q.Px || !q.S1)) throw std::runtime_error("lambda_assemble: incomplete partial results");
     if (!q.D && (q.Pd || q.Px || q.S1 || q.Lp || q.La)) throw std::runtime_error("lambda_assemble: partial results without the direct one");
-    if (q.lp_ld < 0 || q.la_ld < 0 || (q.lp_ld && q.lp_ld < (int64_t)no * (no + 1) / 2) || (q.la_ld && q.la_ld < (int64_t)no * (no - 1) / 2))
+    if ((q.Lp && q.lp_ld < (int64_t)no * (no + 1) / 2) || (q.La && q.la_ld < (int64_t)no * (no - 1) / 2))
         throw std::runtime_error("lambda_assemble: bad row pitch of the ladder halves");
     const bool update = q.Vijab != nullptr;
     if ((q.La && !q.Lp) || (!q.lam1 != !q.lam2)) throw std::runtime_error("lambda_assemble: inconsistent operands");
@@ -1013,8 +1013,7 @@ void lambda_assemble(const LambdaParts& q, int no, int nv, stream_t s) {
     const long npairs = (long)nv * (nv + 1) / 2;
     if (npairs + 1 > 0x7fffffffL) throw std::runtime_error("lambda_assemble: grid too large");
     const LambdaK k{q.D, q.Pd, q.Px, q.Lp, q.La, q.S1, q.Vijab, q.eta1, q.eo, q.ev, q.lam1, q.lam2, q.out1, q.out2, q.err1, q.err2,
-                    q.ws, q.cd, q.cx, q.shift, q.err_scale, q.lp_ld ? (long)q.lp_ld : (long)no * no,
-                    q.la_ld ? (long)q.la_ld : (long)no * (no - 1) / 2, no, nv};
+                    q.ws, q.cd, q.cx, q.shift, q.err_scale, (long)q.lp_ld, (long)q.la_ld, no, nv};
     hipStream_t st = (hipStream_t)s;
     launch_kernel(lambda_assemble_kernel, dim3((unsigned)(npairs + 1)), dim3(256), lds, st, k);
     if (update) launch_kernel(lambda_norm_kernel, dim3(1), dim3(256), 0, st, (const double*)q.ws, npairs + 1, q.norm_dev);

@@ -6,7 +6,7 @@ symmetric; nothing symmetric) and the left build on a symmetric T only.  Here th
 are reached by noise on single inputs, ASSERTED through pymes_eom_sigma_flags against numpy, and run
   a. right, k = 3 symmetric / general / mixed vectors, declared and detected, at (3,5) and (7,6) (no > nv, odd no); (3,5)
      with phase launches on, off and serial (every mode against the oracle; whether the modes agree to the bit is printed)
-  b. left, k = 1 and 3, the same states, shapes and modes: left_partials / left_stack with t_sym or hole_sym false
+  b. left, k = 1 and 3, the same states, shapes and modes: left_build with t_sym or hole_sym false
   c. the batch boundaries at (3,4): k = 17, flushes of the deferred ladders at eight vectors, a mixed batch
   d. stacked builds with o^2 = 289 > 256 at (17,4), and o^2 = 256 at (16,3)
   e. extents of one and two
@@ -121,7 +121,7 @@ def lattice_left(ctx, sig, case, keep, label):
 @pytest.mark.parametrize("state", BC.STATES, ids=BC.STATE_IDS)
 @pytest.mark.parametrize("shape", LATTICE_SHAPES, ids=lambda s: "%dx%d" % s)
 def test_lattice_left(gpu_lib, shape, state):
-    """The first runs of left_partials / left_stack on a handle whose flags are not all set: a wrong number here is a finding in
+    """left_build, as a stack of one and of three, on a handle whose flags are not all set: a wrong number here is a finding in
     csrc/eom.cpp."""
     want, brk = state
     case = BC.Case(shape[0], shape[1], SEED, brk)

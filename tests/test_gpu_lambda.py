@@ -1,7 +1,7 @@
 """GPU: the adjoint of the EE-EOM-CCSD sigma build, the CCSD Lambda equations and the one-particle density
 (pymes_amd/solver/lambda_ccsd.py; csrc/eom.cpp, EomSigma::apply_left / lambda_step, lambda_rdm1; include/pymes_amd.h).  The left
 apply against the adjoint term tables (tests/_lambda_reference.py) and against the device's own right apply, the Lambda solve
-against a dense solve, the density against its definition and against a finite difference of the device CCSD energy, the
+against a dense solve, one Lambda step from a random lambda against the same tables, the density against its definition and against a finite difference of the device CCSD energy, the
 combinations of CCSD.solve, refusals and housekeeping."""
 import contextlib
 import ctypes as C
@@ -15,6 +15,7 @@ import pytest
 from oracle import cc_oracle as oc
 from oracle.cases import synthetic_case
 from pymes_amd import _lib
+from tests import _eom_branch_cases as BC
 from tests import _lambda_reference as R
 
 pytestmark = pytest.mark.gpu
@@ -149,6 +150,59 @@ def test_unconverged_solve_returns_the_vector_its_norm_belongs_to(gpu_lib):
     norm = np.sqrt(((o1 + e1) ** 2).sum() + ((o2 + e2) ** 2).sum())
     print("reported %.6e  recomputed %.6e" % (out["residual norm"], norm))
     assert abs(norm - out["residual norm"]) < 1e-12
+
+
+STEP_SHIFT = 0.25
+
+
+@functools.lru_cache(maxsize=None)
+def _step_case(no, nv, packed):
+    """(f, blocks, t2, lam1, lam2, res1, res2, A^T lam) for one Lambda step from a random exchange-symmetric lambda: 8-fold
+    symmetric integrals, a non-symmetric Fock matrix and, unless ``packed``, noise without V_abcd = V_badc on the abcd block only
+    (tests/_eom_branch_cases.branch_case), so that the ladder adjoint is the plain product."""
+    f, Vb, t2 = BC.branch_case(no, nv, 11, () if packed else ("abcd",))
+    l1, l2 = _vectors(no, nv, seed=6)
+    s1, s2 = R.left_sigma(no, f, Vb, l1, l2, t2)
+    n1, n2 = R.eta(no, f, Vb)
+    return f, Vb, t2, l1, l2, s1 + n1, s2 + n2, max(np.abs(s1).max(), np.abs(s2).max())
+
+
+@pytest.mark.parametrize("packed", [True, False], ids=["packed-ladder", "abcd-broken"])
+@pytest.mark.parametrize("no,nv", [(1, 3), (3, 1), (2, 2), (3, 5), (6, 17)])
+def test_lambda_step_from_a_random_lambda_against_the_reference(gpu_lib, no, nv, packed):
+    """lambda_step feeds a stack of one into the UPDATE form of the assembly: out = lam - res / d, err = -res / d and |res| for
+    res = eta + A^T lam against tests/_lambda_reference.py at the bound of test_left_apply_against_the_reference, 1e-10 of the
+    largest element of A^T lam.  (1,3): no antisymmetric ladder half (o (o - 1) / 2 = 0); (3,1): v (v - 1) / 2 = 0, and a
+    one-element abcd block cannot lose its symmetry; (2,2): the smallest shape with both halves; (6,17): o (o + 1) / 2 = 21 is
+    odd, the pad column of the packed operand is live."""
+    from pymes_amd.device import Context
+    from pymes_amd.solver.lambda_ccsd import LeftSigma
+    f, Vb, t2, l1, l2, r1, r2, scale = _step_case(no, nv, packed)
+    eps_o, eps_v = f.diagonal()[:no].copy(), f.diagonal()[no:].copy()
+    d1 = eps_v[:, None] - eps_o[None, :] - STEP_SHIFT
+    d2 = (eps_v[:, None, None, None] + eps_v[None, :, None, None] - eps_o[None, None, :, None] - eps_o[None, None, None, :]
+          - STEP_SHIFT)
+    ctx = Context(no, nv)
+    try:
+        for name in LeftSigma.BLOCKS:
+            ctx.set_V_block(name, np.ascontiguousarray(Vb[name]))
+        sig = LeftSigma(ctx, f, ctx.array(t2))
+        assert sig.v_sym == BC.expected_flags(no, Vb, t2)[0] == (packed or nv == 1)
+        a1, a2 = ctx.array(l1), ctx.array(l2)
+        o1, e1 = [ctx.array(np.full(l1.shape, np.nan)) for _ in range(2)]
+        o2, e2 = [ctx.array(np.full(l2.shape, np.nan)) for _ in range(2)]
+        norm = sig.lambda_step((a1, a2), eps_o, eps_v, STEP_SHIFT, (o1, o2), (e1, e2))
+        got = [x.get() for x in (o1, o2, e1, e2)]
+        sig.close()
+    finally:
+        ctx.close()
+    want = (l1 - r1 / d1, l2 - r2 / d2, -r1 / d1, -r2 / d2)
+    errs = [np.abs(g - w).max() for g, w in zip(got, want)]
+    nerr = abs(norm - np.sqrt((r1 ** 2).sum() + (r2 ** 2).sum()))
+    print(no, nv, "packed" if packed else "abcd broken", "out1 %.2e out2 %.2e err1 %.2e err2 %.2e norm %.2e, all / max |A^T lam|" % tuple(
+        x / scale for x in errs + [nerr]))
+    assert all(np.all(np.isfinite(g)) for g in got)
+    assert max(errs) <= 1e-10 * scale and nerr <= 1e-10 * scale
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,6 +1,6 @@
 """GPU: left EOM-CCSD eigenvectors, transition densities and strengths (pymes_amd/solver/eom_transitions.py; csrc/eom.cpp,
-EomSigma::left_stack, transition_densities; include/pymes_amd.h, pymes_tdm1).  The stacked left apply against the single one,
-the density kernel against the definitions, the solver against the dense eigenproblem (tests/_transition_reference.py), the
+EomSigma::left_build, transition_densities; include/pymes_amd.h, pymes_tdm1).  The stacked left apply against the single one
+(the same build as a stack of one, called once per vector), the density kernel against the definitions, the solver against the dense eigenproblem (tests/_transition_reference.py), the
 normalisation, the opt-in of CCSD.solve, refusals."""
 import contextlib
 import ctypes as C
